@@ -9,18 +9,27 @@ run_env.py:78-92; the driver's K = 20 is ONE launch); `single_launch_sibling` in
 (`flexenv_step`).  Inputs (series table, action pool) are resident in HBM before the timed region starts; nothing crosses
 PCIe inside it (tools/pcie_probe.py has the host-buffer rates).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline only: set-up, the device brought to its operating clocks by untimed steps of the same
+kind, W warm-up steps, the K timed steps, then the JSON line (`value`, `ms_per_step`, `roofline` from the timed region's own
+HIP events).  `--dump-outputs DIR` writes what the last timed step returned — reward, done, info, failed, the stacked
+observation and the bus voltages of every environment (rank 0) — as DIR/<name>.npy (float32 / float64; a fixed seeded sample
+of environments, listed in env_index.npy, if they would exceed 64 MB); inputs are seeded, so two builds can be compared output
+for output.  `--full` adds every other leg described below; without it those keys of the line are null.
 
 Environments are independent, so ranks share nothing on the data path of the headline metric (weak scaling, no
 collective); the only collectives there are the contract's barrier and the max-over-ranks of the elapsed time.  Under
 N > 1 the line also carries `value_device_events` (max over ranks of the HIP-event time of each rank's K steps: the figure without
-the closing barrier's own collective), what the process group reports about itself (`dist`), and per training leg the all-reduce
-counts against the schedule and `replica_max_abs_diff`; training legs that have not finished after --train-deadline seconds are
-given up and the line is printed without them.
+the closing barrier's own collective), what the process group reports about itself (`dist`), and with --full per training leg the
+all-reduce counts against the schedule and `replica_max_abs_diff`; training legs that have not finished after --train-deadline
+seconds are given up and the line is printed without them.
 
-Next to the headline the same JSON line carries:
+With --full, next to the headline the same JSON line carries, as well as the solver, launch-form,
+observation-form and tolerance siblings, the event-bracketed launch time and the kernel's resource / counter report in
+`roofline`, the learner rooflines and the CPU baseline:
   * `sustained`: the same env-only step over >= 2048 steps in this process, run FIRST (the device enters the timed region at its
     operating clocks);
   * `train`: the TRAINING loop of model.py:198-267 + model.py:40-71 — rollout (policy inference + env step + replay
@@ -62,6 +71,11 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=2048)
     ap.add_argument("--warmup", type=int, default=256)
     ap.add_argument("--envs", type=int, default=N_ENVS, help="envs per GPU (the metric is quoted at 4096)")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beyond the headline: sustained, siblings, event-bracketed launches and counter report, training "
+                         "legs, kernel shares, learner rooflines, CPU baseline (the --no-* flags below drop legs of a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train", action="store_true", help="skip the training legs (`train`)")
     ap.add_argument("--no-sustained", action="store_true", help="skip the >= 2048-step env-only leg (`sustained`)")
@@ -630,6 +644,28 @@ def roofline_details(a, env, kern_ms):
     return out
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: {name: host array with the environments on axis 0} -> path/<name>.npy in float32 (float16 / integer / bool
+    arrays) or float64.  If they exceed `budget` bytes in all, a fixed seeded sample of environments is written, sorted, and
+    its indices as env_index.npy."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    per_env = sum(v.nbytes for v in arrays.values()) / max(1, n)
+    if per_env * n > budget:
+        keep = max(1, int(budget // (per_env + 8)))            # (+ 8 bytes of env_index per environment kept)
+        idx = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["env_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return sorted(arrays)
+
+
 def main():
     a = parse_args()
     if a.kernel_shares_child:
@@ -645,7 +681,7 @@ def main():
     if a.gpus != world:
         print(f"[bench] --gpus {a.gpus} but WORLD_SIZE={world}: reporting n_gpus = {world}", file=sys.stderr)
     shares = None
-    if rank == 0 and not distributed and not a.no_train and not a.no_kernel_shares:
+    if a.full and rank == 0 and not distributed and not a.no_train and not a.no_kernel_shares:
         shares = spawn_kernel_shares()                          # before this process touches the GPU
 
     import torch
@@ -719,9 +755,9 @@ def main():
                     torch.empty(n_steps, a.envs, dtype=torch.uint8, device=dev),
                     torch.empty(n_steps, a.envs, 7, dtype=torch.float64, device=dev),
                     torch.empty(n_steps, a.envs, dtype=torch.uint8, device=dev))
-            many_out[n_steps] = env.step_many_prepared(pool, steps=n_steps, auto_reset=True, out=out_)[0]
+            many_out[n_steps] = env.step_many_prepared(pool, steps=n_steps, auto_reset=True, out=out_)
             return
-        many_out[n_steps]()
+        many_out[n_steps][0]()
 
     if many:
         L_ = max(1, a.steps_per_launch)
@@ -815,20 +851,25 @@ def main():
     # (round 5): the device then enters the W warm-up steps and the K timed steps at its operating clocks, as it would in any
     # use where environment steps follow one another.  Measured (tools/launch_seq_probe.py, profiles/r05w_launch_seq_probe.txt):
     # the 20-step region the driver asks for takes 245-252 us on a busy device and 283-293 us on one that idled for 50-500 ms
-    # of host-side set-up (W = 5 steps = 60 us do not bring the clocks back); `config.timed_after` says so in the line.
+    # of host-side set-up (W = 5 steps = 60 us do not bring the clocks back); `config.timed_after` says so in the line.  A plain
+    # run issues the same steps untimed; --full times them and reports `sustained`.
     sustained = None
+    n_sus = 0
     if not a.no_sustained:
         n_sus = max(2048, ACTION_POOL * (a.steps // ACTION_POOL))
         barrier()
-        s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        t1 = time.perf_counter()
-        s0.record()
-        run_steps(n_sus)
-        s1.record()
-        barrier()
-        sus_elapsed = max_over_ranks(time.perf_counter() - t1)
-        sustained = {"steps": n_sus, "value": a.envs * world * n_sus / sus_elapsed, "unit": "env-steps/s",
-                     "ms_per_step": sus_elapsed / n_sus * 1e3, "device_ms_per_step": s0.elapsed_time(s1) / n_sus}
+        if a.full:
+            s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t1 = time.perf_counter()
+            s0.record()
+            run_steps(n_sus)
+            s1.record()
+            barrier()
+            sus_elapsed = max_over_ranks(time.perf_counter() - t1)
+            sustained = {"steps": n_sus, "value": a.envs * world * n_sus / sus_elapsed, "unit": "env-steps/s",
+                         "ms_per_step": sus_elapsed / n_sus * 1e3, "device_ms_per_step": s0.elapsed_time(s1) / n_sus}
+        else:
+            run_steps(n_sus)
 
     run_steps(a.warmup)                                   # W untimed warm-up steps
 
@@ -848,29 +889,45 @@ def main():
     dev_ms = ev0.elapsed_time(ev1)
     dev_ms_max = max_over_ranks(dev_ms)
 
+    # --dump-outputs: what the LAST timed step returned, read before anything else steps the environments.  The many form's last
+    # launch is the remainder (K mod L) if there is one; a step's outputs are its row of that launch's buffers.
+    if a.dump_outputs and rank == 0:
+        if many:
+            L = max(1, a.steps_per_launch)
+            reward, done, info, failed = (t[-1] for t in many_out[a.steps % L or L][1])
+        else:
+            reward, done, info, failed = env.reward, env.done, env.info, env.failed
+        obs = env.obs if a.stacked_obs else env.obs_view(torch.empty_like(env.obs))     # the row push: the stacked view
+        arrays = {"reward": reward, "done": done, "info": info, "failed": failed, "obs": obs, "voltage": env.peek("V")}
+        names = dump_outputs(a.dump_outputs, {k: v.cpu().numpy() for k, v in arrays.items()})
+        print(f"[bench] outputs of the last timed step -> {a.dump_outputs}: {', '.join(names)}", file=sys.stderr)
+
     # roofline leg.  The timed region above is K back-to-back launches of ONE kernel (flex_step_kernel) on one
     # stream, bracketed by the HIP events ev0/ev1 on that stream: dev_ms / K is its average launch duration
-    # (rocprofv3 --kernel-trace --stats of the same command agrees: profiles/).  A second pass brackets every
+    # (rocprofv3 --kernel-trace --stats of the same command agrees: profiles/).  With --full a second pass brackets every
     # launch with its own event pair; that figure carries ~2 us of event overhead per launch and is reported
     # as `bracketed_launch_ms` only.
-    n_ev = 12 if many else min(max(a.steps, 64), 400)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_ev)]
-    torch.cuda.synchronize()
-    for k, (s, e) in enumerate(evs):
-        s.record()
-        if many:
-            many_launch(a.steps_per_launch_used)          # (a launch of the timed region's length)
-        else:
-            one_step(k)
-        e.record()
-    torch.cuda.synchronize()
-    durs = sorted(s.elapsed_time(e) for s, e in evs)
-    # the kernel's average launch duration: from the longer of the two event-bracketed regions (a 20-step region is
-    # 0.3 ms, where the event pair's own ~5 us shows)
-    kern_ms = sustained["device_ms_per_step"] if sustained is not None and a.steps < 256 else dev_ms / a.steps
-    if many and a.steps < 256:
-        # (per vector step, from launches of the timed region's own length: the median of the event-bracketed ones above)
-        kern_ms = durs[len(durs) // 2] / a.steps_per_launch_used
+    durs = None
+    kern_ms = dev_ms / a.steps
+    if a.full:
+        n_ev = 12 if many else min(max(a.steps, 64), 400)
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_ev)]
+        torch.cuda.synchronize()
+        for k, (s, e) in enumerate(evs):
+            s.record()
+            if many:
+                many_launch(a.steps_per_launch_used)          # (a launch of the timed region's length)
+            else:
+                one_step(k)
+            e.record()
+        torch.cuda.synchronize()
+        durs = sorted(s.elapsed_time(e) for s, e in evs)
+        # the kernel's average launch duration: from the longer of the two event-bracketed regions (a 20-step region is
+        # 0.3 ms, where the event pair's own ~5 us shows)
+        kern_ms = sustained["device_ms_per_step"] if sustained is not None and a.steps < 256 else dev_ms / a.steps
+        if many and a.steps < 256:
+            # (per vector step, from launches of the timed region's own length: the median of the event-bracketed ones above)
+            kern_ms = durs[len(durs) // 2] / a.steps_per_launch_used
     failed_frac = float(env.failed.float().mean().item())
     iters_mean = float(env.peek("PF_ITERS").float().mean().item())
     sweeps_mean = float(env.peek("PF_SWEEPS").float().mean().item())
@@ -879,7 +936,7 @@ def main():
     # sibling figure with the OTHER solver (north_star names Newton-Raphson; the headline runs the sweep solver whose result
     # Newton's fp64 mismatch test verifies): same step, same inputs, >= 512 launches as 16-step graphs, HIP events
     sibling = None
-    if not a.no_sustained:
+    if a.full and not a.no_sustained:
         other = "newton" if a.solver == "sweep" else "sweep"
         try:
             env2 = VecFlexProvisionEnv({}, a.envs, device=f"cuda:{local_rank}", net=net, series=series,
@@ -923,7 +980,7 @@ def main():
     # sibling figure with the OTHER launch form (one flexenv_step launch per step, HIP graphs of 16 <-> flexenv_step_many): same
     # steps, same inputs, same results; 1024 steps, HIP events on the launch stream
     form_sibling = None
-    if not a.no_sustained and not a.stacked_obs:
+    if a.full and not a.no_sustained and not a.stacked_obs:
         try:
             env6 = VecFlexProvisionEnv({}, a.envs, device=f"cuda:{local_rank}", net=net, series=series,
                                        seed=1234 + 1000 * rank, warm_start=bool(a.warm_start), pf_tol=a.pf_tol,
@@ -975,7 +1032,7 @@ def main():
 
     # sibling figure with the OTHER observation form (stacked copy per step <-> row push): same step, same inputs
     obs_sibling = None
-    if not a.no_sustained:
+    if a.full and not a.no_sustained:
         try:
             env3 = VecFlexProvisionEnv({}, a.envs, device=f"cuda:{local_rank}", net=net, series=series,
                                        seed=1234 + 1000 * rank, warm_start=bool(a.warm_start), pf_tol=a.pf_tol,
@@ -1021,7 +1078,7 @@ def main():
     # (pf.py:101-102, default tolerance 1e-8) — which is a choice, not the contract.  Same step, same inputs, pf_tol = 1e-6;
     # the deviation of its voltages from the headline's after the same steps from the same seed is measured and reported.
     tol_sibling = None
-    if not a.no_sustained and a.pf_tol < 1e-6:
+    if a.full and not a.no_sustained and a.pf_tol < 1e-6:
         try:
             envs_t = []
             for tol in (1e-6, a.pf_tol):
@@ -1070,7 +1127,7 @@ def main():
         # of new observation features are the two fp32 mirror rows), 4 220 B when the stacked fp32 observation is materialised
         b_alg = B_ALG_WITH_OBS if a.stacked_obs else B_ALG_CORE
         achieved = b_alg * a.envs / (kern_ms * 1e-3) / 1e9
-        roof_extra = roofline_details(a, env, kern_ms)
+        roof_extra = roofline_details(a, env, kern_ms) if a.full else {}
         out = {
             # BASELINE.json's metric string verbatim; the "+ PF-kernel HBM GB/s" half is `roofline.achieved`
             "metric": "env-steps/sec (33-bus, 4096 envs/GPU) at 1/2/4/8 MI355X + PF-kernel HBM GB/s",
@@ -1082,6 +1139,7 @@ def main():
             "dist": dist_info,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": bool(a.full),
             "ms_per_step": elapsed / a.steps * 1e3,
             "value_device_events": total_env_steps / (dev_ms_max * 1e-3),
             "higher_is_better": True,
@@ -1123,7 +1181,8 @@ def main():
                 "warm_start": bool(a.warm_start), "launches_per_step": (1.0 / a.steps_per_launch_used), "hip_graph": used_graph, "hip_graph_uploaded": used_graph,
                 "timing": ("barrier + synchronize | K steps | barrier + synchronize, clock; MAX over ranks (value_device_events: MAX "
                            "over ranks of the HIP-event time of each rank's K steps)" if distributed else "synchronize | K steps | synchronize"),
-                "timed_after": ("the `sustained` leg (%d steps), then W warm-up steps" % sustained["steps"]) if sustained else "W warm-up steps",
+                "timed_after": (("the `sustained` leg (%d steps), then W warm-up steps" % sustained["steps"]) if sustained else
+                                ("%d untimed steps of the same kind, then W warm-up steps" % n_sus) if n_sus else "W warm-up steps"),
                 "device_ms_per_step": dev_ms / a.steps, "solver": ("sweep (mixed fp64/fp32 increments) + fp64 Newton verification" if a.solver == "sweep" else "newton (fp64, tree elimination)"),
                 "pf_newton_iters_mean": iters_mean, "pf_sweeps_mean": sweeps_mean,
                 "pf_sweeps_counts": "sweeps executed by the environment's wavefront (two environments per wavefront run until both have passed)",
@@ -1141,7 +1200,7 @@ def main():
                 # one launch = `steps_per_launch` vector steps of `envs_per_gpu` environments: algorithmic bytes per launch =
                 # algorithmic_bytes_per_env_step x envs x steps_per_launch, over avg_launch_ms
                 "steps_per_launch": a.steps_per_launch_used, "device_ms_per_vector_step": kern_ms,
-                "avg_launch_ms": kern_ms * a.steps_per_launch_used, "bracketed_launch_ms": durs[len(durs) // 2],
+                "avg_launch_ms": kern_ms * a.steps_per_launch_used, "bracketed_launch_ms": durs[len(durs) // 2] if durs else None,
             }, **roof_extra),
             "single_launch_sibling" if many else "many_steps_sibling": form_sibling,
             "stacked_sibling" if not a.stacked_obs else "rows_sibling": obs_sibling,
@@ -1157,9 +1216,10 @@ def main():
     # rank takes part — with N > 1 the gradient bucket goes through RCCL — and a failure is recorded, not fatal
     train = None
     train_failed = False
+    train_on = a.full and not a.no_train
     emitted = []
     deadline = None
-    if distributed and not a.no_train and a.train_deadline > 0:
+    if distributed and train_on and a.train_deadline > 0:
         # N > 1 only.  A collective that cannot complete inside a training leg (a rank that died, a transport fault) ends in the
         # process group's own abort after its 180 s timeout — which would take rank 0 down BEFORE it printed the line whose headline
         # part (env-steps/s over all ranks, already measured above) the scaling curve is computed from.  So: if the legs have not
@@ -1181,7 +1241,7 @@ def main():
         deadline = threading.Timer(a.train_deadline, _give_up)
         deadline.daemon = True
         deadline.start()
-    if not a.no_train:
+    if train_on:
         # (alg, agents, envs per GPU, batch divisor): every configuration at the trainer's default batch (envs / 4 x 32:
         # 1.47 samples per transition) AND at the reference's own sample reuse (envs x 32: 5.87)
         if distributed:
@@ -1209,7 +1269,7 @@ def main():
             time.sleep(3600)
         emitted.append("legs finished")                   # (a timer already past its cancel point finds this and returns)
     learner = None
-    if rank == 0 and not distributed and not a.no_train:
+    if rank == 0 and not distributed and train_on:
         try:
             learner = learner_rooflines()
         except Exception as exc:
@@ -1217,7 +1277,7 @@ def main():
 
     if rank == 0:
         out.update({"train": train, "train_kernel_shares": shares, "learner_rooflines": learner})
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(net, series, a.cpu_seconds, envs=a.envs)
             cb = out["cpu_baseline"]
             # the ratio is reported for orientation only (the roofline fraction is the figure of merit); like for like in the

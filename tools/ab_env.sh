@@ -2,7 +2,7 @@
 # A/B legs of the env-only bench (usage on the GPU box: tools/ab_env.sh <tag>): sweep acceleration on/off, sweep_tol fraction
 R=$GRAFT_REPO_ROOT
 tag=$1
-B="python bench.py --no-train --no-cpu-baseline --steps 512 --warmup 64"
+B="python bench.py --full --no-train --no-cpu-baseline --steps 512 --warmup 64"
 pick() { python - "$1" <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 # same-box A/B of env-kernel builds: tools/libflexenv_hip_var{A,B,...}.so (FLEX_LIB_OVERRIDE), env-only bench, three rounds interleaved
 # usage on the GPU box: tools/ab_variants.sh <tag> A B C ...
 R=$GRAFT_REPO_ROOT; tag=$1; shift
-B="python bench.py --no-train --no-cpu-baseline --no-kernel-shares --steps 512 --warmup 64"
+B="python bench.py --full --no-train --no-cpu-baseline --no-kernel-shares --steps 512 --warmup 64"
 for round in 1 2 3; do
   for v in "$@"; do
     FLEX_LIB_OVERRIDE=$R/tools/libflexenv_hip_var$v.so $B > gpurun_out/${tag}_var${v}_$round.json 2>gpurun_out/${tag}_var.err || { tail -3 gpurun_out/${tag}_var.err; exit 1; }
