@@ -31,10 +31,19 @@ DEFAULT_ALG_ARGS = dict(  # madrl/args/default.yaml merged with alg_args/maddpg.
     num_eval_episodes=10, action_low=0, action_high=1.0, action_bias=0.0, action_scale=1.0,
 )
 
+# alg_args/facmaddpg.yaml over the defaults above (kept apart: DEFAULT_ALG_ARGS is the MADDPG configuration)
+FACMADDPG_ALG_ARGS = dict(
+    policy_lrate=1.0e-3, value_lrate=1.0e-3, mixer_lrate=1.0e-3, gaussian_policy=False, action_enforcebound=True,
+    policy_update_epochs=1, value_update_epochs=1, mixer_update_epochs=1, grad_clip_eps=1.0, fixed_policy_std=1.0,
+    double_q=True, target_lr=0.01, hypernet_layers=2, hypernet_embed=64, mixing_embed_dim=64,
+    hyper_initialization_nonzeros=False, gated=False, skip_connections=False, mixer=True, behaviour_update_freq=60,
+    target_update_freq=4800,
+)
+
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--alg", choices=["maddpg", "safemaddpg", "matd3", "iddpg"], default="maddpg")
+    ap.add_argument("--alg", choices=["maddpg", "safemaddpg", "matd3", "iddpg", "facmaddpg"], default="maddpg")
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--episodes", type=int, default=3)
     ap.add_argument("--agents", type=int, default=5, choices=[3, 5])
@@ -44,7 +53,7 @@ def main():
     import torch
     import safe_marl_amd  # noqa: F401
     from safe_marl_amd.flex_env import VecFlexProvisionEnv
-    from safe_marl_amd.learner import IDDPG, MADDPG, MATD3, SAFEMADDPG
+    from safe_marl_amd.learner import FACMADDPG, IDDPG, MADDPG, MATD3, SAFEMADDPG
     from safe_marl_amd.network import create_network
     from safe_marl_amd.series import make_synthetic_series
     from safe_marl_amd.trainer import PGTrainer
@@ -68,11 +77,14 @@ def main():
     env = VecFlexProvisionEnv(env_args, a.envs, device=f"cuda:{local}", net=net, series=series,
                               seed=1234 + 1000 * rank, warm_start=True)
     alg = dict(DEFAULT_ALG_ARGS)
+    if a.alg == "facmaddpg":
+        alg.update(FACMADDPG_ALG_ARGS)
     alg.update(alg=a.alg, agent_num=env.n_agents, obs_size=env.obs_size, state_size=env.state_size,
                action_dim=4, v_min=0.9, v_max=1.1)
     args = convert(alg)
     torch.manual_seed(0)
-    trainer = PGTrainer(args, {"maddpg": MADDPG, "safemaddpg": SAFEMADDPG, "matd3": MATD3, "iddpg": IDDPG}[a.alg], env, None,
+    trainer = PGTrainer(args, {"maddpg": MADDPG, "safemaddpg": SAFEMADDPG, "matd3": MATD3, "iddpg": IDDPG,
+                                 "facmaddpg": FACMADDPG}[a.alg], env, None,
                         batch_scale=a.batch_scale, replay_capacity=a.envs * 96 * 2)
     stat = {}
     trainer.behaviour_net.train_process(stat, trainer)          # warm-up episode (allocations, rocBLAS plans)
@@ -92,7 +104,8 @@ def main():
                "value": a.envs * world * steps / dt, "unit": "env-steps/s", "n_gpus": world, "envs_per_gpu": a.envs,
                "n_agents": env.n_agents, "vector_steps": steps, "ms_per_vector_step": dt / steps * 1e3,
                "batch": trainer.effective_batch_size(),
-               "grad_steps": int(steps // args.behaviour_update_freq) * 11,
+               "grad_steps": int(steps // args.behaviour_update_freq) * (args.value_update_epochs + args.policy_update_epochs
+                                                                         + (args.mixer_update_epochs if args.mixer else 0)),
                "stat": {k: (float(v) if not isinstance(v, float) else v) for k, v in stat.items()}}
         print(json.dumps(out))
     if world > 1:

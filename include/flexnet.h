@@ -523,6 +523,55 @@ int flexnet_window_refresh(const FlexWindowRefreshArgs* args, const FlexTdLossAr
  * guarantees that nothing still reads what the refresh writes (trainer.py:81-108 order: the loss's kernels are done). */
 int flexnet_clip_rmsprop_refresh(const FlexClipRmspropArgs* opt, const FlexWindowRefreshArgs* refresh, const FlexTdLossArgs* td, void* stream);
 
+/* QMIX mixer of FACMADDPG (madrl/critics/qmix.py:53-81) in the shipped configuration (facmaddpg.yaml: two-layer
+ * hypernetworks of width FLEXNET_QMIX_EMBED, mixing_embed_dim FLEXNET_QMIX_EMBED, q_embed_dim 1, not gated, no skip
+ * connections).  Weights in the layout of the reference's state_dict.  One wavefront per 32 samples on
+ * v_mfma_f32_32x32x2_f32 (exact fp32); no atomics, bit-reproducible, no allocation or host synchronisation.
+ * forward:  q_tot [B] from agent_qs [B, n] and state [B, ld_state]; with h1 non-NULL also the first-layer outputs
+ *           [B, 256] = [relu(hyper_w_1.0) | relu(hyper_w_final.0) | hyper_b_1 | relu(V.0)] the backward reads.
+ * backward: d_agent_qs [B, n] from d_q_tot [B], agent_qs and h1; with want_param_grads also d_w1 [B, 64 n] (gradient of
+ *           hyper_w_1.2's output, before abs), d_wf [B, 64] (hyper_w_final.2's output) and d_pre1 [B, 256] (the four
+ *           first-layer pre-activations, in h1's column order): the parameter gradients are flexnet_wgrad reductions of
+ *           those against h1 and the state.  The backward does not read the state or the first-layer weights.
+ * n_agents 1..FLEXNET_MAX_AGENTS, state_dim a multiple of 16 up to FLEXNET_QMIX_MAX_STATE, ld_state a multiple of 4,
+ * float4-read tensors 16-byte aligned; else FLEXNET_EUNSUPPORTED (missing tensors: FLEXNET_EINVAL), before any HIP call. */
+#define FLEXNET_QMIX_EMBED 64
+#define FLEXNET_QMIX_MAX_STATE 1024
+typedef struct {
+    int64_t batch;             /* B */
+    int64_t ld_state;          /* row pitch of state in floats */
+    int32_t n_agents;
+    int32_t state_dim;         /* S = n_agents * obs_size */
+    int32_t want_param_grads;  /* backward: 1 = also d_w1, d_wf, d_pre1 */
+    int32_t pad0;
+    const float* agent_qs;     /* [B, n] */
+    const float* state;        /* [B, ld_state] (forward) */
+    const float* w1_0_w;       /* hyper_w_1.0: [64, S], [64] */
+    const float* w1_0_b;
+    const float* w1_2_w;       /* hyper_w_1.2: [64 n, 64], [64 n] */
+    const float* w1_2_b;
+    const float* wf_0_w;       /* hyper_w_final.0: [64, S], [64] */
+    const float* wf_0_b;
+    const float* wf_2_w;       /* hyper_w_final.2: [64, 64], [64] */
+    const float* wf_2_b;
+    const float* b1_w;         /* hyper_b_1: [64, S], [64] */
+    const float* b1_b;
+    const float* v_0_w;        /* V.0: [64, S], [64] */
+    const float* v_0_b;
+    const float* v_2_w;        /* V.2: [1, 64], [1] */
+    const float* v_2_b;
+    float* q_tot;              /* forward out [B] */
+    float* h1;                 /* forward out (optional) / backward in [B, 256] */
+    const float* d_q_tot;      /* backward in [B] */
+    float* d_agent_qs;         /* backward out [B, n] */
+    float* d_w1;               /* backward out [B, 64 n] */
+    float* d_wf;               /* backward out [B, 64] */
+    float* d_pre1;             /* backward out [B, 256] */
+} FlexQmixArgs;
+
+int flexnet_qmix_forward(const FlexQmixArgs* args, void* stream);
+int flexnet_qmix_backward(const FlexQmixArgs* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

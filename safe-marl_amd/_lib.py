@@ -77,6 +77,7 @@ SYMBOLS = (
     "pf_solve_batch", "flexenv_safety_project", "flexenv_safety_project_env", "flexenv_version", "flexenv_abi_version",
     "flexnet_actor_forward", "flexnet_critic_tail_forward", "flexnet_critic_tail_backward", "flexnet_rollout_pack", "flexnet_wgrad", "flexnet_lnrelu_forward", "flexnet_lnrelu_backward", "flexnet_clip_rmsprop", "flexnet_clip_rmsprop_refresh", "flexnet_td_loss", "flexnet_td_stats", "flexnet_critic_td_backward", "flexnet_critic_td_backward_phases", "flexnet_wgrad_critic_finish",
     "flexnet_scaled_sum", "flexnet_agent_sum_explore", "flexnet_gather_rows", "flexnet_gather_rows_td", "flexnet_window_refresh", "flexnet_gather_window", "flexnet_linear2", "flexnet_gru_backward",
+    "flexnet_qmix_forward", "flexnet_qmix_backward",
     "flexopf_qp_work_doubles", "flexopf_qp_solve",
 )
 
@@ -209,6 +210,19 @@ class FlexAgentSumArgs(C.Structure):
                [(k, C.c_void_p) for k in ("means", "eps", "std", "action", "env_action")]
 
 
+QMIX_PTRS = ("agent_qs", "state", "w1_0_w", "w1_0_b", "w1_2_w", "w1_2_b", "wf_0_w", "wf_0_b", "wf_2_w", "wf_2_b",
+             "b1_w", "b1_b", "v_0_w", "v_0_b", "v_2_w", "v_2_b", "q_tot", "h1", "d_q_tot", "d_agent_qs", "d_w1", "d_wf",
+             "d_pre1")
+FLEXNET_QMIX_EMBED = 64
+FLEXNET_QMIX_MAX_STATE = 1024
+
+
+class FlexQmixArgs(C.Structure):
+    """include/flexnet.h"""
+    _fields_ = [("batch", C.c_int64), ("ld_state", C.c_int64), ("n_agents", C.c_int32), ("state_dim", C.c_int32),
+                ("want_param_grads", C.c_int32), ("pad0", C.c_int32)] + [(k, C.c_void_p) for k in QMIX_PTRS]
+
+
 class FlexSumArgs(C.Structure):
     """include/flexnet.h"""
     _fields_ = [("n", C.c_int64), ("scale", C.c_float), ("pad0", C.c_int32), ("x", C.c_void_p), ("out", C.c_void_p),
@@ -335,6 +349,9 @@ def load():
     lib.flexnet_td_loss.restype = C.c_int
     lib.flexnet_td_stats.argtypes = [C.POINTER(FlexTdLossArgs), vp]
     lib.flexnet_td_stats.restype = C.c_int
+    for fn in (lib.flexnet_qmix_forward, lib.flexnet_qmix_backward):
+        fn.argtypes = [C.POINTER(FlexQmixArgs), vp]
+        fn.restype = C.c_int
     lib.flexnet_agent_sum_explore.argtypes = [C.POINTER(FlexAgentSumArgs), vp]
     lib.flexnet_agent_sum_explore.restype = C.c_int
     lib.flexnet_scaled_sum.argtypes = [C.POINTER(FlexSumArgs), vp]

@@ -24,7 +24,7 @@ import torch.nn as nn
 from .nets import (WGRAD_MIN_ROWS, CriticTail, critic_first_layer, critic_td_loss, critic_td_loss_supported, critic_policy_loss,
                    critic_policy_loss_supported, expand_agents, MLPAgent, MLPCritic, RNNAgent, critic_policy_supported, critic_replayed_supported,
                    critic_tail_supported, fused_actor_forward, tall_linear, td_loss, td_loss_supported, wide_batch_linear,
-                   batchnorm_stats_supported, batchnorm_update_running_stats, sync_batchnorm)
+                   batchnorm_stats_supported, batchnorm_update_running_stats, sync_batchnorm, QMixer)
 from .replay_buffer import Transition
 from .util import graph_capture, prep_obs, scale_action, select_action, translate_action, mean_all
 
@@ -70,7 +70,7 @@ class RolloutGraph:
         # MATD3 / IDDPG with the bound enforced: their agent-summed action selection (matd3.py:92-97, iddpg.py:66-71 over
         # util.py:57-64) and translate_action as ONE launch behind the fused policy — bit-identical to get_actions +
         # env_action (same draws from torch's generator, every fp32 rounding in the same place), ~40 launches fewer per step
-        self.summed = (type(model).__name__ in ("MATD3", "IDDPG")
+        self.summed = (type(model).__name__ in ("MATD3", "IDDPG", "FACMADDPG")
                        and type(model).get_actions in (MATD3.get_actions, IDDPG.get_actions)
                        and bool(model.args.action_enforcebound) and bool(model.args.continuous) and a > 1
                        and env.obs.is_cuda and model.fused_inference and model.args.shared_params)
@@ -500,17 +500,19 @@ class Model(nn.Module):
                 nn.init.orthogonal_(m.weight, gain=nn.init.calculate_gain(self.args.hid_activation))
 
     def reload_params_to_target(self):
-        """model.py:22-26"""
+        """model.py:22-26 (+ the mixer where the algorithm has one)"""
         self.target_net.policy_dicts.load_state_dict(self.policy_dicts.state_dict())
         self.target_net.value_dicts.load_state_dict(self.value_dicts.state_dict())
+        if getattr(self.args, "mixer", False):
+            self.target_net.mixer.load_state_dict(self.mixer.state_dict())
 
     def update_target(self):
         """model.py:28-38: theta' <- (1 - target_lr) theta' + target_lr theta over every state_dict entry
-        of the policy and value nets (floating entries; the nets hold no buffers)."""
+        of the policy and value nets and, with args.mixer, the mixer (floating entries; the nets hold no buffers)."""
         with th.no_grad():
-            tgt = list(self.target_net.policy_dicts.state_dict().values()) + \
-                list(self.target_net.value_dicts.state_dict().values())
-            src = list(self.policy_dicts.state_dict().values()) + list(self.value_dicts.state_dict().values())
+            nets = ["policy_dicts", "value_dicts"] + (["mixer"] if getattr(self.args, "mixer", False) else [])
+            tgt = [t for k in nets for t in getattr(self.target_net, k).state_dict().values()]
+            src = [t for k in nets for t in getattr(self, k).state_dict().values()]
             th._foreach_mul_(tgt, 1 - self.args.target_lr)
             th._foreach_add_(tgt, src, alpha=self.args.target_lr)
 
@@ -577,6 +579,9 @@ class Model(nn.Module):
                         trainer.value_replay_process(stat)
                     for _ in range(self.args.policy_update_epochs):
                         trainer.policy_replay_process(stat)
+                if getattr(self.args, "mixer", False):              # model.py:51-53: after the value and policy steps
+                    for _ in range(self.args.mixer_update_epochs):
+                        trainer.mixer_replay_process(stat)
         else:
             raise NotImplementedError("the MADDPG path always replays (default.yaml:22)")
         if self.args.target and trainer.steps % self.args.target_update_freq == 0:
@@ -1489,3 +1494,54 @@ class SAFEMADDPG(MADDPG):
             return action.detach().reshape(-1, self.act_dim, self.n_).transpose(1, 2).to(th.float32).contiguous()
         # the type-major flat vector is re-read agent-major by env.step (safemaddpg.py:297 vs env:268-274, A13)
         return scale_action(self.args, action.detach()).reshape(-1, self.n_, self.act_dim)
+
+
+class FACMADDPG(IDDPG):
+    """madrl/models/facmaddpg.py:9-114: IDDPG's per-agent critic Q_i(o_i, a_i) and agent-summed action selection
+    (facmaddpg.py:36-83, inherited unchanged), mixed into Q_tot(s, Q_1..Q_n) by a QMIX mixer over the global state
+    (madrl/critics/qmix.py; nets.QMixer, csrc/qmix.hip on the GPU).  The value loss is on Q_tot against the reward of
+    agent 0 (facmaddpg.py:106); the policy loss is IDDPG's, without the mixer.  The mixer has an optimiser of its own
+    (trainer.mixer_replay_process, args.mixer)."""
+
+    graph_safe_updates = False       # sub-updates run eagerly (the mixer's losses are not audited for graph capture)
+    bootstrap_cacheable = False      # own get_loss: the bootstrap target is Q_tot', not per-agent values
+
+    def construct_value_net(self):
+        """facmaddpg.py:19-30"""
+        super().construct_value_net()
+        self.mixer = QMixer(self.args)
+
+    def get_loss(self, batch, need="both"):
+        """facmaddpg.py:85-114.  ``need`` = "value" (gradients for the critic: the mixer is differentiated w.r.t. its input
+        only), "mixer" (gradients for the mixer: the critic's values enter as data), "policy", or "both" (the reference's
+        call).  The value and mixer sub-updates step on the same loss."""
+        state, actions, _, _, _, rewards, next_state, done, _, actions_avail, last_hids, hids = self.unpack_data(batch)
+        b, n = state.size(0), self.n_
+        policy_loss = value_loss = action_out = None
+        if need in ("both", "policy"):
+            _, actions_pol, _, action_out, _ = self.get_actions(state, status="train", exploration=False,
+                                                                actions_avail=actions_avail, target=False,
+                                                                last_hid=last_hids)
+            advantages = self.value(state, actions_pol).contiguous().view(-1, n)
+            if self.args.normalize_advantages:
+                advantages = self.batchnorm(advantages)
+            policy_loss = mean_all(advantages, sign=-1.0)
+        if need in ("both", "value", "mixer"):
+            with th.no_grad():
+                # double_q: the next actions from the behaviour policy (facmaddpg.py:90-93), valued by the target critic
+                # and mixed by the target mixer on s' (facmaddpg.py:99-102)
+                _, next_actions, _, _, _ = self.get_actions(next_state, status="train", exploration=False,
+                                                            actions_avail=actions_avail, target=not self.args.double_q,
+                                                            last_hid=hids)
+                next_values = self.target_net.value(next_state, next_actions).contiguous().view(-1, n)
+                next_q_tot = self.target_net.mixer(next_values, next_state.reshape(b, n * self.obs_dim)).view(-1, 1)
+            if need == "mixer":
+                with th.no_grad():
+                    values = self.value(state, actions).contiguous().view(-1, n)
+            else:
+                values = self.value(state, actions).contiguous().view(-1, n)
+            q_tot = self.mixer(values, state.reshape(b, n * self.obs_dim), param_grads=(need != "value")).view(-1, 1)
+            returns = rewards[:, 0:1] + self.args.gamma * (1 - done) * next_q_tot
+            assert returns.size() == q_tot.size()
+            value_loss = mean_all((returns - q_tot).pow(2))
+        return policy_loss, value_loss, action_out

@@ -1542,3 +1542,198 @@ class CriticTail:
         return _CriticTailFn.apply(z1, None if ln is None else ln.weight, None if ln is None else ln.bias,
                                    critic.fc2.weight, critic.fc2.bias, critic.fc3.weight, critic.fc3.bias,
                                    1e-5 if ln is None else ln.eps)
+
+
+# ---- QMIX mixer of FACMADDPG (madrl/critics/qmix.py) ---------------------------------------------------------------------
+QMIX_PARAMS = ("hyper_w_1.0.weight", "hyper_w_1.0.bias", "hyper_w_1.2.weight", "hyper_w_1.2.bias",
+               "hyper_w_final.0.weight", "hyper_w_final.0.bias", "hyper_w_final.2.weight", "hyper_w_final.2.bias",
+               "hyper_b_1.weight", "hyper_b_1.bias", "V.0.weight", "V.0.bias", "V.2.weight", "V.2.bias")
+
+
+class QMixer(nn.Module):
+    """madrl/critics/qmix.py:6-81, same parameter names and shapes (a reference state_dict loads).  On the GPU, in the shipped
+    configuration (two-layer hypernetworks of width 64, mixing_embed_dim 64, q_embed_dim 1, not gated, no skip connections),
+    forward and backward are csrc/qmix.hip plus flexnet_wgrad reductions (one autograd node, _QmixFn); elsewhere the
+    reference's PyTorch composition (``forward_torch``)."""
+
+    def __init__(self, args):
+        super().__init__()
+        self.args = args
+        self.n_agents = args.agent_num
+        self.state_dim = args.obs_size * args.agent_num
+        self.embed_dim = args.mixing_embed_dim
+        self.q_embed_dim = getattr(args, "q_embed_dim", 1)
+        out1 = self.embed_dim * self.n_agents * self.q_embed_dim
+        self.hyper_w_1 = nn.Linear(self.state_dim, out1)
+        self.hyper_w_final = nn.Linear(self.state_dim, self.embed_dim)
+        if getattr(args, "hypernet_layers", 1) > 1:
+            assert args.hypernet_layers == 2, "Only 1 or 2 hypernet_layers is supported atm!"
+            he = args.hypernet_embed
+            self.hyper_w_1 = nn.Sequential(nn.Linear(self.state_dim, he), nn.ReLU(), nn.Linear(he, out1))
+            self.hyper_w_final = nn.Sequential(nn.Linear(self.state_dim, he), nn.ReLU(), nn.Linear(he, self.embed_dim))
+        if getattr(args, "hyper_initialization_nonzeros", 0) > 0:          # qmix.py:35-40, as written there
+            std = args.hyper_initialization_nonzeros ** -0.5
+            self.hyper_w_1.weight.data.normal_(std=std)
+            self.hyper_w_1.bias.data.normal_(std=std)
+            self.hyper_w_final.weight.data.normal_(std=std)
+            self.hyper_w_final.bias.data.normal_(std=std)
+        self.hyper_b_1 = nn.Linear(self.state_dim, self.embed_dim)
+        self.V = nn.Sequential(nn.Linear(self.state_dim, self.embed_dim), nn.ReLU(), nn.Linear(self.embed_dim, 1))
+        if getattr(args, "gated", False):
+            self.gate = nn.Parameter(th.ones(size=(1,)) * 0.5)
+
+    def fused_config(self):
+        """The configuration csrc/qmix.hip implements (include/flexnet.h: flexnet_qmix_forward)."""
+        a = self.args
+        return (getattr(a, "hypernet_layers", 1) == 2 and a.hypernet_embed == 64 and self.embed_dim == 64
+                and self.q_embed_dim == 1 and not getattr(a, "gated", False) and not getattr(a, "skip_connections", False)
+                and 1 <= self.n_agents <= 8 and self.state_dim % 16 == 0 and 16 <= self.state_dim <= 1024)
+
+    def fused_supported(self, agent_qs, states):
+        if not (agent_qs.is_cuda and states.is_cuda):
+            return False
+        ok = (self.fused_config() and agent_qs.dtype == th.float32 and states.dtype == th.float32
+              and not states.requires_grad and all(p.dtype == th.float32 and p.is_cuda for p in self.parameters()))
+        if not ok:
+            note_fallback("qmix", f"hypernet_layers {getattr(self.args, 'hypernet_layers', 1)}, state {self.state_dim}, "
+                                  f"agents {self.n_agents}, gated {getattr(self.args, 'gated', False)}, "
+                                  f"skip {getattr(self.args, 'skip_connections', False)}")
+        return ok
+
+    def forward(self, agent_qs, states, param_grads=True):
+        """q_tot [bs, 1, 1] (qmix.py:53-81).  ``param_grads=False``: the caller differentiates w.r.t. ``agent_qs`` only (a value
+        sub-update, whose optimiser holds the critic): the mixer's parameters take no gradient from this call."""
+        bs = agent_qs.size(0)
+        if self.fused_supported(agent_qs, states):
+            q = agent_qs.reshape(bs, self.n_agents)
+            x = states.reshape(bs, self.state_dim)
+            params = dict(self.named_parameters())
+            ws = [params[k] if param_grads else params[k].detach() for k in QMIX_PARAMS]
+            save = th.is_grad_enabled() and (q.requires_grad or any(w.requires_grad for w in ws))
+            return _QmixFn.apply(q, x, save, *ws).view(bs, 1, 1)
+        return self.forward_torch(agent_qs, states, param_grads)
+
+    def forward_torch(self, agent_qs, states, param_grads=True):
+        """qmix.py:53-81 as written there."""
+        params = {k: (v if param_grads else v.detach()) for k, v in self.named_parameters()}
+        return self._forward_torch_with(agent_qs, states, params)
+
+    def _forward_torch_with(self, agent_qs, states, p):
+        bs = agent_qs.size(0)
+        states = states.reshape(-1, self.state_dim)
+        agent_qs = agent_qs.reshape(-1, 1, self.n_agents * self.q_embed_dim)
+
+        def lin(x, name):
+            return F.linear(x, p[name + ".weight"], p[name + ".bias"])
+
+        def head(x, name):
+            if isinstance(getattr(self, name), nn.Sequential):
+                return lin(F.relu(lin(x, name + ".0")), name + ".2")
+            return lin(x, name)
+
+        w1 = th.abs(head(states, "hyper_w_1"))
+        b1 = lin(states, "hyper_b_1")
+        w1 = w1.view(-1, self.n_agents * self.q_embed_dim, self.embed_dim)
+        b1 = b1.view(-1, 1, self.embed_dim)
+        hidden = F.elu(th.bmm(agent_qs, w1) + b1)
+        w_final = th.abs(head(states, "hyper_w_final")).view(-1, self.embed_dim, 1)
+        v = head(states, "V").view(-1, 1, 1)
+        s = agent_qs.sum(dim=2, keepdim=True) if getattr(self.args, "skip_connections", False) else 0
+        if getattr(self.args, "gated", False):
+            y = th.bmm(hidden, w_final) * p["gate"] + v + s
+        else:
+            y = th.bmm(hidden, w_final) + v + s
+        return y.view(bs, -1, 1)
+
+
+def _qmix_args(q, x, ws):
+    from . import _lib
+    a = _lib.FlexQmixArgs()
+    a.batch, a.n_agents, a.state_dim = q.shape[0], q.shape[1], x.shape[1]
+    a.ld_state = x.stride(0) if x.shape[0] > 1 else x.shape[1]
+    a.agent_qs, a.state = q.data_ptr(), x.data_ptr()
+    names = ("w1_0_w", "w1_0_b", "w1_2_w", "w1_2_b", "wf_0_w", "wf_0_b", "wf_2_w", "wf_2_b", "b1_w", "b1_b", "v_0_w",
+             "v_0_b", "v_2_w", "v_2_b")
+    for name, w in zip(names, ws):
+        setattr(a, name, w.data_ptr())
+    return a
+
+
+def _wgrad_into(dy, x, out, colsum):
+    """out = dy^T x, colsum = sum over rows of dy: csrc/wgrad.hip (fixed order) where it applies."""
+    if tall_wgrad_supported(dy, x):
+        tall_wgrad(dy, x, out=out, colsum=colsum)
+    else:
+        out.copy_(dy.t() @ x)
+        colsum.copy_(dy.sum(0))
+
+
+class _QmixFn(th.autograd.Function):
+    """QMixer.forward in the shipped configuration: flexnet_qmix_forward (saving the first-layer outputs h1 [B, 256]),
+    flexnet_qmix_backward (d agent_qs, and the per-sample gradients of the second-layer outputs and first-layer
+    pre-activations when a mixer parameter needs its gradient) and the batch reductions dW = dY^T X of csrc/wgrad.hip."""
+
+    @staticmethod
+    def forward(ctx, q, x, save, *ws):
+        import ctypes as C
+        from . import _lib
+        q = q.contiguous()
+        if x.stride(-1) != 1 or (x.shape[0] > 1 and x.stride(0) % 4 != 0) or x.data_ptr() % 16 != 0:
+            x = x.contiguous()
+        ws = [w.contiguous() for w in ws]
+        B = q.shape[0]
+        out = th.empty(B, dtype=th.float32, device=q.device)
+        h1 = th.empty(B, 4 * _lib.FLEXNET_QMIX_EMBED, dtype=th.float32, device=q.device) if save else None
+        a = _qmix_args(q, x, ws)
+        a.q_tot = out.data_ptr()
+        if h1 is not None:
+            a.h1 = h1.data_ptr()
+        _lib.check(_lib.load().flexnet_qmix_forward(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream)),
+                   "flexnet_qmix_forward")
+        if save:
+            ctx.save_for_backward(q, x, h1, *ws)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        import ctypes as C
+        from . import _lib
+        q, x, h1, *ws = ctx.saved_tensors
+        B, n = q.shape
+        E = _lib.FLEXNET_QMIX_EMBED
+        want_w = any(ctx.needs_input_grad[3:])
+        g = g.reshape(B).contiguous()
+        dq = th.empty(B, n, dtype=th.float32, device=q.device)
+        a = _qmix_args(q, x, ws)
+        a.h1, a.d_q_tot, a.d_agent_qs = h1.data_ptr(), g.data_ptr(), dq.data_ptr()
+        if want_w:
+            d_w1 = th.empty(B, E * n, dtype=th.float32, device=q.device)
+            d_wf = th.empty(B, E, dtype=th.float32, device=q.device)
+            d_pre1 = th.empty(B, 4 * E, dtype=th.float32, device=q.device)
+            a.want_param_grads, a.d_w1, a.d_wf, a.d_pre1 = 1, d_w1.data_ptr(), d_wf.data_ptr(), d_pre1.data_ptr()
+        _lib.check(_lib.load().flexnet_qmix_backward(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream)),
+                   "flexnet_qmix_backward")
+        grads = [None] * len(ws)
+        if want_w:
+            S = x.shape[1]
+            dev = q.device
+            d1w = th.empty(4 * E, S, dtype=th.float32, device=dev)            # the four first layers, h1's unit order
+            d1b = th.empty(4 * E, dtype=th.float32, device=dev)
+            for c0 in (0, 2 * E):                                             # flexnet_wgrad: m <= 192 per call
+                _wgrad_into(d_pre1[:, c0:c0 + 2 * E], x, d1w[c0:c0 + 2 * E], d1b[c0:c0 + 2 * E])
+            dw12 = th.empty(E * n, E, dtype=th.float32, device=dev)
+            db12 = th.empty(E * n, dtype=th.float32, device=dev)
+            for c0 in range(0, E * n, 160):
+                c1 = min(c0 + 160, E * n)
+                _wgrad_into(d_w1[:, c0:c1], h1[:, 0:E], dw12[c0:c1], db12[c0:c1])
+            dwf2 = th.empty(E, E, dtype=th.float32, device=dev)
+            dbf2 = th.empty(E, dtype=th.float32, device=dev)
+            _wgrad_into(d_wf, h1[:, E:2 * E], dwf2, dbf2)
+            dv2 = th.empty(1, E, dtype=th.float32, device=dev)
+            dbv2 = th.empty(1, dtype=th.float32, device=dev)
+            _wgrad_into(g.view(B, 1), h1[:, 3 * E:4 * E], dv2, dbv2)
+            # QMIX_PARAMS order: hyper_w_1.0, hyper_w_1.2, hyper_w_final.0, hyper_w_final.2, hyper_b_1, V.0, V.2
+            grads = [d1w[0:E], d1b[0:E], dw12, db12, d1w[E:2 * E], d1b[E:2 * E], dwf2, dbf2,
+                     d1w[2 * E:3 * E], d1b[2 * E:3 * E], d1w[3 * E:4 * E], d1b[3 * E:4 * E], dv2, dbv2]
+            grads = [gr if need else None for gr, need in zip(grads, ctx.needs_input_grad[3:])]
+        return (dq if ctx.needs_input_grad[0] else None, None, None, *grads)

@@ -97,6 +97,9 @@ class PGTrainer(object):
         cap = dict(capturable=True) if self.device.type == "cuda" else {}       # optimiser steps inside HIP graphs
         self.policy_optimizer = RMSprop(net.policy_dicts.parameters(), lr=args.policy_lrate, **_RMSPROP, **cap)
         self.value_optimizer = RMSprop(net.value_dicts.parameters(), lr=args.value_lrate, **_RMSPROP, **cap)
+        self.mixer_optimizer = None
+        if getattr(args, "mixer", False):           # trainer.py:36-37
+            self.mixer_optimizer = RMSprop(net.mixer.parameters(), lr=args.mixer_lrate, **_RMSPROP, **cap)
         self.init_action = th.zeros(1, args.agent_num, args.action_dim, device=self.device)
 
         # replay memory sized for the number of environments feeding it
@@ -123,6 +126,12 @@ class PGTrainer(object):
     def value_replay_process(self, stat):       # model.py:48
         if not self._graphed_sub_update("value", stat):
             self._sub_update("value", stat, self.replay_buffer.get_batch_tensors(self.effective_batch_size()))
+
+    def mixer_replay_process(self, stat):       # model.py:51-53 (eager: FACMADDPG's sub-updates are not graphed)
+        self._sub_update("mixer", stat, self.replay_buffer.get_batch_tensors(self.effective_batch_size()))
+
+    def _optimizer(self, which):
+        return {"policy": self.policy_optimizer, "value": self.value_optimizer, "mixer": self.mixer_optimizer}[which]
 
     # ---- a sub-update as one HIP graph -----------------------------------------------------------------------
     def _ensure_graph(self, which, slot=0):
@@ -781,6 +790,9 @@ class PGTrainer(object):
     def value_transition_process(self, stat, trans):
         self._sub_update("value", stat, trans)
 
+    def mixer_transition_process(self, stat, trans):
+        self._sub_update("mixer", stat, trans)
+
     # ---- one gradient step -----------------------------------------------------------------------
     def _sub_update(self, which, stat, batch, fresh_leaves=False, flat=None):
         """zero_grad -> loss -> backward -> (all-reduce) -> clip_grad_norm_(1.0) -> RMSprop (trainer.py:81-108).
@@ -791,8 +803,7 @@ class PGTrainer(object):
             if flat is not None:
                 fdist.allreduce_flat(flat)
             else:
-                opt = self.policy_optimizer if which == "policy" else self.value_optimizer
-                fdist.allreduce_grads(opt.param_groups[0]["params"])
+                fdist.allreduce_grads(self._optimizer(which).param_groups[0]["params"])
         self._apply_grads(which, stat, flat=flat)
 
     def _loss_and_grads(self, which, stat, batch, fresh_leaves=False, flat=None):
@@ -803,8 +814,9 @@ class PGTrainer(object):
         gradient accumulator per parameter, bound to the stream it was first used on; if the caller still holds a
         graph built eagerly on the default stream (an evaluated policy output, say), backward would synchronise the
         capturing stream with the default stream — illegal during capture, and fatal in the HIP runtime.  Aliases are
-        new leaves with accumulators of their own; their gradients ARE the parameters' gradients."""
-        opt = self.policy_optimizer if which == "policy" else self.value_optimizer
+        new leaves with accumulators of their own; their gradients ARE the parameters' gradients.
+        ``which`` = "mixer" (FACMADDPG): the value loss, differentiated w.r.t. the mixer's parameters only."""
+        opt = self._optimizer(which)
         params = opt.param_groups[0]["params"]
         leaves = params
         if fresh_leaves:
@@ -860,7 +872,7 @@ class PGTrainer(object):
 
     def _apply_grads(self, which, stat, flat=None):
         """clip_grad_norm_ + RMSprop step (trainer.py:86-90,103-107), after the all-reduce; one HIP launch on the GPU."""
-        opt = self.policy_optimizer if which == "policy" else self.value_optimizer
+        opt = self._optimizer(which)
         params = opt.param_groups[0]["params"]
         if flat is not None and self.world > 1:
             flat.mul_(1.0 / self.world)               # the bucket holds the SUM over ranks
