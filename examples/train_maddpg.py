@@ -40,10 +40,14 @@ FACMADDPG_ALG_ARGS = dict(
     target_update_freq=4800,
 )
 
+# alg_args/sqddpg.yaml over the defaults above
+SQDDPG_ALG_ARGS = dict(policy_lrate=1.0e-4, value_lrate=1.0e-4, sample_size=10, gaussian_policy=False,
+                       action_enforcebound=True)
+
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--alg", choices=["maddpg", "safemaddpg", "matd3", "iddpg", "facmaddpg"], default="maddpg")
+    ap.add_argument("--alg", choices=["maddpg", "safemaddpg", "matd3", "iddpg", "facmaddpg", "sqddpg"], default="maddpg")
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--episodes", type=int, default=3)
     ap.add_argument("--agents", type=int, default=5, choices=[3, 5])
@@ -53,7 +57,7 @@ def main():
     import torch
     import safe_marl_amd  # noqa: F401
     from safe_marl_amd.flex_env import VecFlexProvisionEnv
-    from safe_marl_amd.learner import FACMADDPG, IDDPG, MADDPG, MATD3, SAFEMADDPG
+    from safe_marl_amd.learner import FACMADDPG, IDDPG, MADDPG, MATD3, SAFEMADDPG, SQDDPG
     from safe_marl_amd.network import create_network
     from safe_marl_amd.series import make_synthetic_series
     from safe_marl_amd.trainer import PGTrainer
@@ -79,12 +83,14 @@ def main():
     alg = dict(DEFAULT_ALG_ARGS)
     if a.alg == "facmaddpg":
         alg.update(FACMADDPG_ALG_ARGS)
+    if a.alg == "sqddpg":
+        alg.update(SQDDPG_ALG_ARGS)
     alg.update(alg=a.alg, agent_num=env.n_agents, obs_size=env.obs_size, state_size=env.state_size,
                action_dim=4, v_min=0.9, v_max=1.1)
     args = convert(alg)
     torch.manual_seed(0)
     trainer = PGTrainer(args, {"maddpg": MADDPG, "safemaddpg": SAFEMADDPG, "matd3": MATD3, "iddpg": IDDPG,
-                                 "facmaddpg": FACMADDPG}[a.alg], env, None,
+                                 "facmaddpg": FACMADDPG, "sqddpg": SQDDPG}[a.alg], env, None,
                         batch_scale=a.batch_scale, replay_capacity=a.envs * 96 * 2)
     stat = {}
     trainer.behaviour_net.train_process(stat, trainer)          # warm-up episode (allocations, rocBLAS plans)

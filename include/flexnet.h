@@ -572,6 +572,71 @@ typedef struct {
 int flexnet_qmix_forward(const FlexQmixArgs* args, void* stream);
 int flexnet_qmix_backward(const FlexQmixArgs* args, void* stream);
 
+/* SQDDPG's Shapley-value critic (madrl/models/sqddpg.py:35-104) with a shared MLPCritic, agent_id, hid 64, ReLU.
+ * Group g = b * sample_size + s holds a permutation of the agents: pos[g, i] = position of agent i.  Critic row (b, s, i)
+ * has first layer z1 = z_shared[b] + z_id[i] + sum over agents j with pos[g, j] <= pos[g, i] of
+ * W_act[:, block pos[g, j]] act[b, j] (the reference's coalition-ordered action blocks), then the MLPCritic tail.
+ * draw:     one uniform permutation per group from the counter-based stream rng_state = [seed, step] (int64, device);
+ *           the caller advances step.  No host synchronisation.
+ * forward:  phi [b, n] = mean over s of q, s [b] = sum_i phi (agent order), q [b, ns, n] (each optional, not all NULL).
+ * backward: from d_phi [b, n] (and optionally d_q [b, ns, n]) recomputes the forward and writes d_z_shared [b, 64] and
+ *           d_act_own [b, n, a] (agent i's own action, the other agents' actions detached) where non-NULL; with
+ *           want_param_grads the gradients of z_id, W_act, the LayerNorm, fc2 and fc3, through `workspace`
+ *           (FLEXNET_SQDDPG_BWD_GRID * FLEXNET_SQDDPG_WS_ROW floats) and a fixed-order reduction.
+ * No atomics: bit-reproducible.  n_agents 1..FLEXNET_MAX_AGENTS, act_dim 1..8 with n * act_dim <= 32, sample_size >= 1
+ * with sample_size * n <= 4096, z_shared / z_id / fc2_w 16-byte aligned; else FLEXNET_EUNSUPPORTED.  Missing tensors:
+ * FLEXNET_EINVAL.  Both before any HIP call. */
+#define FLEXNET_SQDDPG_WS_ROW 6976
+#define FLEXNET_SQDDPG_BWD_GRID 1024
+typedef struct {
+    int64_t groups;            /* b * sample_size */
+    int32_t n_agents;
+    int32_t pad0;
+    const int64_t* rng_state;  /* [seed, step] */
+    int32_t* pos;              /* out [groups, n] */
+} FlexSqddpgDrawArgs;
+
+typedef struct {
+    int64_t batch;             /* b */
+    int32_t n_agents;
+    int32_t act_dim;
+    int32_t sample_size;       /* ns */
+    int32_t layernorm;
+    float ln_eps;
+    int32_t want_param_grads;  /* backward */
+    const float* z_shared;     /* [b, 64]: W_obs obs_all + fc1.bias */
+    const float* z_id;         /* [n, 64]: the id columns of fc1.weight, transposed */
+    const float* w_act;        /* [64, n a]: the action columns of fc1.weight */
+    const float* act;          /* [b, n, a] */
+    const int32_t* pos;        /* [b ns, n] */
+    const float* ln_w;         /* [64], [64] (layernorm) */
+    const float* ln_b;
+    const float* fc2_w;        /* [64, 64], [64] */
+    const float* fc2_b;
+    const float* fc3_w;        /* [1, 64], [1] */
+    const float* fc3_b;
+    float* q;                  /* forward out [b, ns, n] (optional) */
+    float* phi;                /* forward out [b, n] (optional) */
+    float* s;                  /* forward out [b] (optional) */
+    const float* d_phi;        /* backward in [b, n] */
+    const float* d_q;          /* backward in [b, ns, n] (optional) */
+    float* d_z_shared;         /* backward out [b, 64] (optional) */
+    float* d_act_own;          /* backward out [b, n, a] (optional) */
+    float* d_z_id;             /* backward out, want_param_grads: [n, 64] */
+    float* d_w_act;            /* [64, n a] */
+    float* d_ln_w;             /* [64], [64] (layernorm) */
+    float* d_ln_b;
+    float* d_fc2_w;            /* [64, 64], [64] */
+    float* d_fc2_b;
+    float* d_fc3_w;            /* [64], [1] */
+    float* d_fc3_b;
+    float* workspace;          /* FLEXNET_SQDDPG_BWD_GRID * FLEXNET_SQDDPG_WS_ROW floats */
+} FlexSqddpgArgs;
+
+int flexnet_sqddpg_draw(const FlexSqddpgDrawArgs* args, void* stream);
+int flexnet_sqddpg_forward(const FlexSqddpgArgs* args, void* stream);
+int flexnet_sqddpg_backward(const FlexSqddpgArgs* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

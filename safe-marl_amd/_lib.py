@@ -78,6 +78,7 @@ SYMBOLS = (
     "flexnet_actor_forward", "flexnet_critic_tail_forward", "flexnet_critic_tail_backward", "flexnet_rollout_pack", "flexnet_wgrad", "flexnet_lnrelu_forward", "flexnet_lnrelu_backward", "flexnet_clip_rmsprop", "flexnet_clip_rmsprop_refresh", "flexnet_td_loss", "flexnet_td_stats", "flexnet_critic_td_backward", "flexnet_critic_td_backward_phases", "flexnet_wgrad_critic_finish",
     "flexnet_scaled_sum", "flexnet_agent_sum_explore", "flexnet_gather_rows", "flexnet_gather_rows_td", "flexnet_window_refresh", "flexnet_gather_window", "flexnet_linear2", "flexnet_gru_backward",
     "flexnet_qmix_forward", "flexnet_qmix_backward",
+    "flexnet_sqddpg_draw", "flexnet_sqddpg_forward", "flexnet_sqddpg_backward",
     "flexopf_qp_work_doubles", "flexopf_qp_solve",
 )
 
@@ -223,6 +224,26 @@ class FlexQmixArgs(C.Structure):
                 ("want_param_grads", C.c_int32), ("pad0", C.c_int32)] + [(k, C.c_void_p) for k in QMIX_PTRS]
 
 
+SQDDPG_PTRS = ("z_shared", "z_id", "w_act", "act", "pos", "ln_w", "ln_b", "fc2_w", "fc2_b", "fc3_w", "fc3_b", "q", "phi",
+               "s", "d_phi", "d_q", "d_z_shared", "d_act_own", "d_z_id", "d_w_act", "d_ln_w", "d_ln_b", "d_fc2_w",
+               "d_fc2_b", "d_fc3_w", "d_fc3_b", "workspace")
+FLEXNET_SQDDPG_WS_ROW = 6976
+FLEXNET_SQDDPG_BWD_GRID = 1024
+
+
+class FlexSqddpgDrawArgs(C.Structure):
+    """include/flexnet.h"""
+    _fields_ = [("groups", C.c_int64), ("n_agents", C.c_int32), ("pad0", C.c_int32), ("rng_state", C.c_void_p),
+                ("pos", C.c_void_p)]
+
+
+class FlexSqddpgArgs(C.Structure):
+    """include/flexnet.h"""
+    _fields_ = [("batch", C.c_int64), ("n_agents", C.c_int32), ("act_dim", C.c_int32), ("sample_size", C.c_int32),
+                ("layernorm", C.c_int32), ("ln_eps", C.c_float), ("want_param_grads", C.c_int32)] + \
+               [(k, C.c_void_p) for k in SQDDPG_PTRS]
+
+
 class FlexSumArgs(C.Structure):
     """include/flexnet.h"""
     _fields_ = [("n", C.c_int64), ("scale", C.c_float), ("pad0", C.c_int32), ("x", C.c_void_p), ("out", C.c_void_p),
@@ -351,6 +372,11 @@ def load():
     lib.flexnet_td_stats.restype = C.c_int
     for fn in (lib.flexnet_qmix_forward, lib.flexnet_qmix_backward):
         fn.argtypes = [C.POINTER(FlexQmixArgs), vp]
+        fn.restype = C.c_int
+    lib.flexnet_sqddpg_draw.argtypes = [C.POINTER(FlexSqddpgDrawArgs), vp]
+    lib.flexnet_sqddpg_draw.restype = C.c_int
+    for fn in (lib.flexnet_sqddpg_forward, lib.flexnet_sqddpg_backward):
+        fn.argtypes = [C.POINTER(FlexSqddpgArgs), vp]
         fn.restype = C.c_int
     lib.flexnet_agent_sum_explore.argtypes = [C.POINTER(FlexAgentSumArgs), vp]
     lib.flexnet_agent_sum_explore.restype = C.c_int

@@ -24,9 +24,10 @@ import torch.nn as nn
 from .nets import (WGRAD_MIN_ROWS, CriticTail, critic_first_layer, critic_td_loss, critic_td_loss_supported, critic_policy_loss,
                    critic_policy_loss_supported, expand_agents, MLPAgent, MLPCritic, RNNAgent, critic_policy_supported, critic_replayed_supported,
                    critic_tail_supported, fused_actor_forward, tall_linear, td_loss, td_loss_supported, wide_batch_linear,
-                   batchnorm_stats_supported, batchnorm_update_running_stats, sync_batchnorm, QMixer)
+                   batchnorm_stats_supported, batchnorm_update_running_stats, sync_batchnorm, QMixer,
+                   sqddpg_draw, sqddpg_fused_config, sqddpg_shapley_fused)
 from .replay_buffer import Transition
-from .util import graph_capture, prep_obs, scale_action, select_action, translate_action, mean_all
+from .util import graph_capture, prep_obs, scale_action, select_action, translate_action, mean_all, note_fallback
 
 
 class RolloutGraph:
@@ -70,7 +71,7 @@ class RolloutGraph:
         # MATD3 / IDDPG with the bound enforced: their agent-summed action selection (matd3.py:92-97, iddpg.py:66-71 over
         # util.py:57-64) and translate_action as ONE launch behind the fused policy — bit-identical to get_actions +
         # env_action (same draws from torch's generator, every fp32 rounding in the same place), ~40 launches fewer per step
-        self.summed = (type(model).__name__ in ("MATD3", "IDDPG", "FACMADDPG")
+        self.summed = (type(model).__name__ in ("MATD3", "IDDPG", "FACMADDPG", "SQDDPG")
                        and type(model).get_actions in (MATD3.get_actions, IDDPG.get_actions)
                        and bool(model.args.action_enforcebound) and bool(model.args.continuous) and a > 1
                        and env.obs.is_cuda and model.fused_inference and model.args.shared_params)
@@ -1544,4 +1545,132 @@ class FACMADDPG(IDDPG):
             returns = rewards[:, 0:1] + self.args.gamma * (1 - done) * next_q_tot
             assert returns.size() == q_tot.size()
             value_loss = mean_all((returns - q_tot).pow(2))
+        return policy_loss, value_loss, action_out
+
+
+class SQDDPG(MADDPG):
+    """madrl/models/sqddpg.py:8-158: MADDPG's centralised critic (same construction and state_dict keys) valued on sampled
+    coalitions.  For each of ``sample_size`` uniformly random agent orders per sample, row (b, s, i) of the critic holds every
+    observation, the actions of the agents placed at or before agent i (in coalition order; the others' actions detached)
+    and onehot(i); phi[b, i] = mean over s is agent i's Shapley estimate.  The policy loss is -mean(phi), the value loss is
+    on S = sum_i phi with the target S' of the target critic, every term on FRESH coalitions.  Action selection is IDDPG's
+    agent-summed one (sqddpg.py:109-129).  On the GPU, csrc/sqddpg.hip draws the coalitions and runs the critic without
+    materialising the [b ns n, 745] rows (nets.sqddpg_shapley_fused); elsewhere the reference's composition
+    (``marginal_contribution_torch``)."""
+
+    graph_safe_updates = False       # sub-updates run eagerly (fresh coalitions per call; not audited for graph capture)
+    bootstrap_cacheable = False      # own get_loss: the target term draws its own coalitions in every value sub-update
+    get_actions = IDDPG.get_actions  # the same function object (RolloutGraph.summed checks identity)
+    coalition_source = None          # tests: callable(role, groups) -> pos [groups, n], role "policy" / "value" / "target"
+
+    def __init__(self, args, target_net=None):
+        super().__init__(args, target_net)
+        self.sample_size = int(args.sample_size)
+        self._coalition_rng = None
+
+    # -- coalitions ------------------------------------------------------------------------------------
+    def draw_coalitions(self, role, batch_size, device):
+        """pos [b ns, n]: pos[g, i] is the position of agent i in coalition group g = b ns + s (the raw th.multinomial
+        output of sqddpg.py:35-40).  ``coalition_source`` when set; on the GPU the device draw of csrc/sqddpg.hip from a
+        [seed, step] stream seeded from torch's generator (no host synchronisation after the first call); else
+        th.multinomial as the reference."""
+        groups = batch_size * self.sample_size
+        n = self.n_
+        if self.coalition_source is not None:
+            return self.coalition_source(role, groups).to(device)
+        if device.type == "cuda" and self.fused_inference:
+            if self._coalition_rng is None or self._coalition_rng.device != device:
+                seed = int(th.randint(0, 2 ** 62, (1,)).item())
+                self._coalition_rng = th.tensor([seed, 0], dtype=th.int64, device=device)
+            return sqddpg_draw(groups, n, self._coalition_rng)
+        weights = th.full((groups, n), 1.0 / n, dtype=th.float64, device=device)
+        return th.multinomial(weights, n, replacement=False)
+
+    def coalition_maps(self, pos, batch_size):
+        """sqddpg.py:35-61 from the drawn positions: (subcoalition map, grand coalitions, individual map), each
+        [b, ns, n, n].  individual[.., i, p] = 1 at p = pos[g, i]; subcoalition[.., i, p] = 1 for p <= pos[g, i];
+        grand[.., i, p] = the agent at position p (the same for every i)."""
+        b, ns, n = batch_size, self.sample_size, self.n_
+        pos = pos.long().reshape(b * ns, n)
+        individual = th.zeros(b * ns * n, n, device=pos.device).scatter_(1, pos.reshape(-1, 1), 1.0).view(b, ns, n, n)
+        subcoalition = th.matmul(individual, th.tril(th.ones(n, n, device=pos.device)))
+        grand = th.empty_like(pos).scatter_(1, pos, th.arange(n, device=pos.device).expand(b * ns, n))
+        grand = grand.view(b, ns, 1, n).expand(b, ns, n, n)
+        return subcoalition, grand, individual
+
+    def marginal_contribution_torch(self, obs, act, pos):
+        """sqddpg.py:63-104 on given coalitions: the critic's values [b, ns, n, 1] of the materialised rows
+        [obs_0 .. obs_{n-1} | block p = act of the agent at position p if p <= pos[g, i] else 0 | onehot(i)]."""
+        b, ns, n, o, a = obs.size(0), self.sample_size, self.n_, self.obs_dim, self.act_dim
+        subcoalition, grand, individual = self.coalition_maps(pos, b)
+        acts = act.view(b, 1, 1, n, a).expand(b, ns, n, n, a).gather(3, grand.unsqueeze(-1).expand(b, ns, n, n, a))
+        others = (subcoalition - individual).unsqueeze(-1)
+        acts = (acts * others).detach() + acts * individual.unsqueeze(-1)          # only agent i's own action keeps its gradient
+        rows = th.cat((obs.reshape(b, 1, 1, n * o).expand(b, ns, n, n * o), acts.reshape(b, ns, n, n * a)), dim=-1)
+        rows = rows.reshape(b * ns, n, -1)
+        if self.args.agent_id:
+            ids = th.eye(n, device=obs.device, dtype=rows.dtype).unsqueeze(0).expand(b * ns, n, n)
+            rows = th.cat((rows, ids), dim=-1)
+        if self.args.shared_params:
+            values, _ = self.value_dicts[0](rows.reshape(b * ns * n, -1), None)
+        else:
+            values = th.stack([net(rows[:, i, :], None)[0] for i, net in enumerate(self.value_dicts)], dim=1)
+        return values.reshape(b, ns, n, 1)
+
+    def _fused(self, act):
+        if not act.is_cuda:
+            return False
+        ok = (self.args.shared_params and self.fused_inference and act.dtype == th.float32
+              and sqddpg_fused_config(self.value_dicts[0], self.n_, self.act_dim, self.sample_size))
+        if not ok:
+            note_fallback("sqddpg", f"shared_params {self.args.shared_params}, agent_id {self.args.agent_id}, "
+                                    f"hid {self.args.hid_size}, agents {self.n_}, act_dim {self.act_dim}")
+        return ok
+
+    def shapley_values(self, obs, act, pos, want_q=False, frozen=False):
+        """(phi [b, n], values [b, ns, n, 1] or None) on the coalitions ``pos``; ``frozen``: no critic-parameter gradients."""
+        b, n = obs.size(0), self.n_
+        if self._fused(act):
+            phi, q = sqddpg_shapley_fused(self.value_dicts[0], obs.reshape(b, n * self.obs_dim), act.to(th.float32),
+                                          pos, self.sample_size, want_q=want_q, frozen=frozen)
+            return phi, (q.unsqueeze(-1) if want_q else None)
+        values = self.marginal_contribution_torch(obs, act, pos)
+        return values.mean(dim=1).reshape(b, n), values
+
+    def value(self, obs, act, critic_frozen=False):
+        """sqddpg.py:106-107: the critic's values [b, ns, n, 1] on fresh coalitions."""
+        pos = self.draw_coalitions("value", obs.size(0), obs.device)
+        return self.shapley_values(obs, act, pos, want_q=True, frozen=critic_frozen)[1]
+
+    marginal_contribution = value
+
+    def get_loss(self, batch, need="both"):
+        """sqddpg.py:131-158.  ``need`` = "value" (the value and target terms), "policy" (the policy term, critic frozen) or
+        "both" (the reference's call: policy, value and target coalitions drawn in that order)."""
+        state, actions, _, _, _, rewards, next_state, done, _, actions_avail, last_hids, hids = self.unpack_data(batch)
+        b, dev = state.size(0), state.device
+        policy_loss = value_loss = action_out = None
+        if need in ("both", "policy"):
+            _, actions_pol, _, action_out, _ = self.get_actions(state, status="train", exploration=False,
+                                                                actions_avail=actions_avail, target=False,
+                                                                last_hid=last_hids)
+            pos = self.draw_coalitions("policy", b, dev)
+            advantages, _ = self.shapley_values(state, actions_pol, pos, frozen=(need == "policy"))
+            if self.args.normalize_advantages:
+                advantages = self.batchnorm(advantages)
+            policy_loss = mean_all(advantages, sign=-1.0)
+        if need in ("both", "value"):
+            pos = self.draw_coalitions("value", b, dev)
+            pos_next = self.draw_coalitions("target", b, dev)
+            tgt = self.target_net if self.args.target else self
+            with th.no_grad():
+                # double_q: the next actions from the behaviour policy (sqddpg.py:136-139)
+                _, next_actions, _, _, _ = self.get_actions(next_state, status="train", exploration=False,
+                                                            actions_avail=actions_avail, target=not self.args.double_q,
+                                                            last_hid=hids)
+                next_phi, _ = tgt.shapley_values(next_state, next_actions, pos_next)
+                next_sum = next_phi.sum(dim=-1, keepdim=True)
+            phi, _ = self.shapley_values(state, actions, pos)
+            returns = rewards + self.args.gamma * (1 - done) * next_sum
+            value_loss = mean_all((returns - phi.sum(dim=-1, keepdim=True)).pow(2))
         return policy_loss, value_loss, action_out

@@ -1737,3 +1737,136 @@ class _QmixFn(th.autograd.Function):
                      d1w[2 * E:3 * E], d1b[2 * E:3 * E], d1w[3 * E:4 * E], d1b[3 * E:4 * E], dv2, dbv2]
             grads = [gr if need else None for gr, need in zip(grads, ctx.needs_input_grad[3:])]
         return (dq if ctx.needs_input_grad[0] else None, None, None, *grads)
+
+
+# ---- SQDDPG's Shapley-value critic (madrl/models/sqddpg.py:35-104) -------------------------------------------------------
+_SQDDPG_WS = {}
+
+
+def sqddpg_fused_config(critic, n_agents, act_dim, sample_size):
+    """The configuration csrc/sqddpg.hip implements (include/flexnet.h: flexnet_sqddpg_forward): a shared MLPCritic with hid
+    64, ReLU and one output, the agent id columns, n <= 8 agents, act_dim <= 8 with n * act_dim <= 32."""
+    a = critic.args
+    return (a.hid_size == 64 and a.hid_activation == "relu" and critic.fc3.weight.shape[0] == 1 and bool(a.agent_id)
+            and 1 <= n_agents <= 8 and 1 <= act_dim <= 8 and n_agents * act_dim <= 32 and sample_size >= 1
+            and sample_size * n_agents <= 4096)
+
+
+def sqddpg_draw(groups, n_agents, rng_state):
+    """One uniform random permutation per coalition group on the device: pos [groups, n] (int32), pos[g, i] = position of
+    agent i.  The stream is rng_state = [seed, step] (int64, device); the step advances on the device after the draw."""
+    import ctypes as C
+    from . import _lib
+    pos = th.empty(groups, n_agents, dtype=th.int32, device=rng_state.device)
+    a = _lib.FlexSqddpgDrawArgs()
+    a.groups, a.n_agents, a.rng_state, a.pos = groups, n_agents, rng_state.data_ptr(), pos.data_ptr()
+    _lib.check(_lib.load().flexnet_sqddpg_draw(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream)),
+               "flexnet_sqddpg_draw")
+    rng_state[1:2].add_(1)
+    return pos
+
+
+def _sqddpg_args(z_shared, z_id, w_act, act, pos, ns, eps, layernorm, ps):
+    from . import _lib
+    a = _lib.FlexSqddpgArgs()
+    a.batch, a.n_agents, a.act_dim = act.shape
+    a.sample_size, a.layernorm, a.ln_eps = ns, int(layernorm), eps
+    a.z_shared, a.z_id, a.w_act, a.act, a.pos = (z_shared.data_ptr(), z_id.data_ptr(), w_act.data_ptr(), act.data_ptr(),
+                                                 pos.data_ptr())
+    ln_w, ln_b, fc2_w, fc2_b, fc3_w, fc3_b = ps
+    if layernorm:
+        a.ln_w, a.ln_b = ln_w.data_ptr(), ln_b.data_ptr()
+    a.fc2_w, a.fc2_b, a.fc3_w, a.fc3_b = fc2_w.data_ptr(), fc2_b.data_ptr(), fc3_w.data_ptr(), fc3_b.data_ptr()
+    return a
+
+
+class _SqddpgFn(th.autograd.Function):
+    """phi [b, n] = mean over the ns coalitions of the critic's value of each agent's coalition row, and (want_q) the rows'
+    values q [b, ns, n]: flexnet_sqddpg_forward / flexnet_sqddpg_backward.  Inputs: z_shared [b, 64] (fc1 of the
+    observations + bias), z_id [n, 64], w_act [64, n a], act [b, n, a] (only agent i's own action takes a gradient from row
+    (b, s, i)), pos [b ns, n]; then the tail's parameters."""
+
+    @staticmethod
+    def forward(ctx, z_shared, z_id, w_act, act, pos, ns, eps, layernorm, want_q, ln_w, ln_b, fc2_w, fc2_b, fc3_w, fc3_b):
+        import ctypes as C
+        from . import _lib
+        ctx.set_materialize_grads(False)
+        z_shared, z_id, w_act, act = z_shared.contiguous(), z_id.contiguous(), w_act.contiguous(), act.contiguous()
+        pos = pos.to(th.int32).contiguous()
+        ps = [None if p is None else p.contiguous() for p in (ln_w, ln_b, fc2_w, fc2_b, fc3_w, fc3_b)]
+        b, n, _ = act.shape
+        phi = th.empty(b, n, dtype=th.float32, device=act.device)
+        q = th.empty(b, ns, n, dtype=th.float32, device=act.device) if want_q else phi.new_empty(0)
+        k = _sqddpg_args(z_shared, z_id, w_act, act, pos, ns, eps, layernorm, ps)
+        k.phi = phi.data_ptr()
+        if want_q:
+            k.q = q.data_ptr()
+        _lib.check(_lib.load().flexnet_sqddpg_forward(C.byref(k), C.c_void_p(th.cuda.current_stream().cuda_stream)),
+                   "flexnet_sqddpg_forward")
+        ctx.ns, ctx.eps, ctx.layernorm = ns, eps, layernorm
+        ctx.save_for_backward(z_shared, z_id, w_act, act, pos, *[p if p is not None else phi.new_empty(0) for p in ps])
+        if not want_q:
+            ctx.mark_non_differentiable(q)
+        return phi, q
+
+    @staticmethod
+    def backward(ctx, d_phi, d_q):
+        import ctypes as C
+        from . import _lib
+        z_shared, z_id, w_act, act, pos, *ps = ctx.saved_tensors
+        if not ctx.layernorm:
+            ps[0] = ps[1] = None
+        b, n, ad = act.shape
+        dev = act.device
+        need = ctx.needs_input_grad
+        want_w = any(need[1:3]) or any(need[9:])
+        d_phi = th.zeros(b, n, dtype=th.float32, device=dev) if d_phi is None else d_phi.contiguous()
+        k = _sqddpg_args(z_shared, z_id, w_act, act, pos, ctx.ns, ctx.eps, ctx.layernorm, ps)
+        k.d_phi = d_phi.data_ptr()
+        if d_q is not None and d_q.numel() == b * ctx.ns * n:
+            d_q = d_q.contiguous()
+            k.d_q = d_q.data_ptr()
+        dz = th.empty(b, 64, dtype=th.float32, device=dev) if need[0] else None
+        da = th.empty(b, n, ad, dtype=th.float32, device=dev) if need[3] else None
+        if dz is not None:
+            k.d_z_shared = dz.data_ptr()
+        if da is not None:
+            k.d_act_own = da.data_ptr()
+        grads = [None] * 8
+        if want_w:
+            if dev not in _SQDDPG_WS:
+                _SQDDPG_WS[dev] = th.empty(_lib.FLEXNET_SQDDPG_BWD_GRID * _lib.FLEXNET_SQDDPG_WS_ROW, dtype=th.float32,
+                                           device=dev)
+            grads = [th.empty(n, 64, device=dev), th.empty(64, n * ad, device=dev), th.zeros(64, device=dev),
+                     th.zeros(64, device=dev), th.empty(64, 64, device=dev), th.empty(64, device=dev),
+                     th.empty(1, 64, device=dev), th.empty(1, device=dev)]
+            k.want_param_grads = 1
+            k.workspace = _SQDDPG_WS[dev].data_ptr()
+            for name, t in zip(("d_z_id", "d_w_act", "d_ln_w", "d_ln_b", "d_fc2_w", "d_fc2_b", "d_fc3_w", "d_fc3_b"), grads):
+                setattr(k, name, t.data_ptr())
+        _lib.check(_lib.load().flexnet_sqddpg_backward(C.byref(k), C.c_void_p(th.cuda.current_stream().cuda_stream)),
+                   "flexnet_sqddpg_backward")
+        gz_id, gw_act, *gp = [g if nd else None for g, nd in zip(grads, (need[1], need[2]) + tuple(need[9:]))]
+        return (dz, gz_id, gw_act, da, None, None, None, None, None, *gp)
+
+
+def sqddpg_shapley_fused(critic, obs2d, act, pos, ns, want_q=False, frozen=False):
+    """(phi [b, n], q [b, ns, n] or None) of madrl/models/sqddpg.py:63-104 through csrc/sqddpg.hip.  fc1's observation
+    block and bias form z_shared once per sample (tall_linear: flexnet_wgrad for dW_obs / db1); the reference's row layout
+    [obs | coalition actions | onehot(i)] fixes the column blocks.  ``frozen``: the critic's parameters take no gradient
+    (a policy sub-update)."""
+    b, n, ad = act.shape
+    W, bias = critic.fc1.weight, critic.fc1.bias
+    ln = critic.layernorm if critic.args.layernorm else None
+    tail = [None if ln is None else ln.weight, None if ln is None else ln.bias, critic.fc2.weight, critic.fc2.bias,
+            critic.fc3.weight, critic.fc3.bias]
+    if frozen:
+        W, bias = W.detach(), bias.detach()
+        tail = [None if p is None else p.detach() for p in tail]
+    no = obs2d.shape[1]
+    z_shared = tall_linear(obs2d, W[:, :no], bias)
+    w_act = W[:, no:no + n * ad]
+    z_id = W[:, no + n * ad:no + n * ad + n].t()
+    phi, q = _SqddpgFn.apply(z_shared, z_id, w_act, act, pos, ns, 1e-5 if ln is None else ln.eps, ln is not None,
+                             want_q, *tail)
+    return phi, (q if want_q else None)
