@@ -44,10 +44,16 @@ FACMADDPG_ALG_ARGS = dict(
 SQDDPG_ALG_ARGS = dict(policy_lrate=1.0e-4, value_lrate=1.0e-4, sample_size=10, gaussian_policy=False,
                        action_enforcebound=True)
 
+# alg_args/ippo.yaml and mappo.yaml (the same settings) over the defaults above: on-policy, an update event every 240
+# vector steps of ten value and ten policy sub-updates on pooled windows of 32 steps of every environment
+PPO_ALG_ARGS = dict(policy_lrate=1.0e-4, value_lrate=1.0e-4, value_update_epochs=10, policy_update_epochs=10, lambda_=0.95,
+                    eps_clip=0.6, value_loss_coef=2.0, reward_normalisation=True, normalize_advantages=True,
+                    gaussian_policy=False, action_enforcebound=True, behaviour_update_freq=240, target_update_freq=480)
+
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--alg", choices=["maddpg", "safemaddpg", "matd3", "iddpg", "facmaddpg", "sqddpg"], default="maddpg")
+    ap.add_argument("--alg", choices=["maddpg", "safemaddpg", "matd3", "iddpg", "facmaddpg", "sqddpg", "ippo", "mappo"], default="maddpg")
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--episodes", type=int, default=3)
     ap.add_argument("--agents", type=int, default=5, choices=[3, 5])
@@ -57,11 +63,11 @@ def main():
     import torch
     import safe_marl_amd  # noqa: F401
     from safe_marl_amd.flex_env import VecFlexProvisionEnv
-    from safe_marl_amd.learner import FACMADDPG, IDDPG, MADDPG, MATD3, SAFEMADDPG, SQDDPG
+    from safe_marl_amd.learner import FACMADDPG, IDDPG, IPPO, MADDPG, MAPPO, MATD3, SAFEMADDPG, SQDDPG
     from safe_marl_amd.network import create_network
     from safe_marl_amd.series import make_synthetic_series
     from safe_marl_amd.trainer import PGTrainer
-    from safe_marl_amd.util import convert
+    from safe_marl_amd.util import FALLBACKS, convert
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -85,13 +91,17 @@ def main():
         alg.update(FACMADDPG_ALG_ARGS)
     if a.alg == "sqddpg":
         alg.update(SQDDPG_ALG_ARGS)
+    if a.alg in ("ippo", "mappo"):
+        alg.update(PPO_ALG_ARGS)
     alg.update(alg=a.alg, agent_num=env.n_agents, obs_size=env.obs_size, state_size=env.state_size,
                action_dim=4, v_min=0.9, v_max=1.1)
     args = convert(alg)
     torch.manual_seed(0)
     trainer = PGTrainer(args, {"maddpg": MADDPG, "safemaddpg": SAFEMADDPG, "matd3": MATD3, "iddpg": IDDPG,
-                                 "facmaddpg": FACMADDPG, "sqddpg": SQDDPG}[a.alg], env, None,
-                        batch_scale=a.batch_scale, replay_capacity=a.envs * 96 * 2)
+                                 "facmaddpg": FACMADDPG, "sqddpg": SQDDPG, "ippo": IPPO, "mappo": MAPPO}[a.alg], env, None,
+                        batch_scale=a.batch_scale,
+                        # (on-policy: the trainer's default holds what is collected between two update events)
+                        replay_capacity=None if a.alg in ("ippo", "mappo") else a.envs * 96 * 2)
     stat = {}
     trainer.behaviour_net.train_process(stat, trainer)          # warm-up episode (allocations, rocBLAS plans)
     torch.cuda.synchronize()
@@ -112,7 +122,9 @@ def main():
                "batch": trainer.effective_batch_size(),
                "grad_steps": int(steps // args.behaviour_update_freq) * (args.value_update_epochs + args.policy_update_epochs
                                                                          + (args.mixer_update_epochs if args.mixer else 0)),
-               "stat": {k: (float(v) if not isinstance(v, float) else v) for k, v in stat.items()}}
+               "stat": {k: (float(v) if not isinstance(v, float) else v) for k, v in stat.items()},
+               # fused paths that declined a call and ran their PyTorch composition instead (util.note_fallback): none expected
+               "fallbacks": dict(FALLBACKS)}
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

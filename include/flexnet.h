@@ -637,6 +637,95 @@ int flexnet_sqddpg_draw(const FlexSqddpgDrawArgs* args, void* stream);
 int flexnet_sqddpg_forward(const FlexSqddpgArgs* args, void* stream);
 int flexnet_sqddpg_backward(const FlexSqddpgArgs* args, void* stream);
 
+/* ---- PPO (IPPO / MAPPO): madrl/learning_algorithms/ppo.py:14-69 around the networks (csrc/ppo.hip) ----------------
+ * [rows, n_agents] fp32 tensors, n_agents <= FLEXNET_MAX_AGENTS.  Fixed-order reductions, no atomics: bit-reproducible.
+ * gae:    reward_norm = BatchNorm(reward) (reward_bn.enabled, else a copy);
+ *         delta_i = reward_norm_i + gamma old_next_values_i m_i - old_values_i,  m_i = last_step_i ? 1 - done_i : 1;
+ *         advantages_i = delta_i + gamma lambda_ m_i advantages_{i + chain_stride} (0 past the last row): row i continues
+ *         into row i + chain_stride — 1: one chain over the batch; N: a time-major window of N environments, N chains.
+ *         With adv_bn.enabled also advantages_norm = BatchNorm(advantages).  An enabled module's running statistics
+ *         move as a training-mode nn.BatchNorm1d moves them (pointers may be NULL: no tracking).
+ *         One lane per chain for chains of up to 256 steps (or >= 16384 chains), else one wavefront per chain scanning
+ *         64 steps at a time; any rows / chain_stride >= 1.
+ * policy: mu = sum over agents of means;  log p[b, i] = sum_k log N(actions[b, i, k]; mu[b, k], exp(log_std[k]));
+ *         ratio = exp(log p - old) with old = old_log_prob[b, i], or sum_k actions[b, i, k] when old_log_prob is NULL
+ *         (model.py:313);  loss = -mean(min(ratio A, clamp(ratio, 1 - eps, 1 + eps) A));  d_means = d loss / d means.
+ * value:  ret = reward_norm + gamma (1 - done) next_values;  vc = old_values + clamp(values - old_values, -eps, eps);
+ *         loss = coef mean(max((values - ret)^2, (vc - ret)^2));  d_values = d loss / d values.
+ * Ties: min / max give half of the gradient to each argument where they are equal; clamp passes the gradient on
+ * [lo, hi], ends included (PyTorch's subgradients).
+ * Missing tensors, a short or misaligned workspace: FLEXNET_EINVAL; n_agents / act_dim beyond the maxima, rows >= 2^28:
+ * FLEXNET_EUNSUPPORTED.  Both before any HIP call. */
+#define FLEXNET_PPO_BLOCKS 256
+#define FLEXNET_PPO_WS_FLOATS (2 * FLEXNET_TD_WS_FLOATS + 2 * FLEXNET_PPO_BLOCKS)
+typedef struct {
+    int32_t enabled;           /* normalise with this module */
+    float eps, momentum;
+    int32_t pad0;
+    const float* weight;       /* [n] or NULL (1) */
+    const float* bias;         /* [n] or NULL (0) */
+    float* running_mean;       /* [n] updated in place, or NULL */
+    float* running_var;
+    int64_t* num_batches_tracked; /* += 1, or NULL */
+} FlexPpoBatchNorm;
+
+typedef struct {
+    int64_t rows;
+    int64_t chain_stride;      /* >= 1 */
+    int32_t n_agents;
+    float gamma, lambda_;
+    int32_t pad0;
+    const float* reward;       /* [rows, n] raw */
+    const float* old_values;   /* [rows, n] */
+    const float* old_next_values;
+    const float* done;         /* [rows] 0/1 */
+    const float* last_step;    /* [rows] 0/1 */
+    FlexPpoBatchNorm reward_bn;
+    FlexPpoBatchNorm adv_bn;
+    float* reward_norm;        /* out [rows, n] */
+    float* advantages;         /* out [rows, n] */
+    float* advantages_norm;    /* out [rows, n] (adv_bn.enabled) */
+    float* workspace;          /* 8-byte aligned */
+    int64_t workspace_floats;  /* >= FLEXNET_PPO_WS_FLOATS */
+} FlexPpoGaeArgs;
+
+typedef struct {
+    int64_t rows;
+    int32_t n_agents, act_dim; /* act_dim <= FLEXNET_MAX_ACT */
+    float eps_clip;
+    int32_t pad0;
+    const float* means;        /* [rows, n, a] */
+    const float* log_std;      /* [a]: the agent-summed log-std of the fixed-std policy */
+    const float* actions;      /* [rows, n, a] */
+    const float* old_log_prob; /* [rows, n] or NULL */
+    const float* advantages;   /* [rows, n] */
+    float* loss;               /* out [1] */
+    float* d_means;            /* out [rows, n, a] */
+    float* ratio;              /* out [rows, n] (optional) */
+    float* workspace;
+    int64_t workspace_floats;  /* >= FLEXNET_PPO_WS_FLOATS */
+} FlexPpoPolicyArgs;
+
+typedef struct {
+    int64_t rows;
+    int32_t n_agents;
+    float gamma, eps_clip, value_loss_coef;
+    const float* values;       /* [rows, n] */
+    const float* old_values;   /* [rows, n] */
+    const float* next_values;  /* [rows, n] V(s') of the current network, no gradient */
+    const float* reward_norm;  /* [rows, n] from flexnet_ppo_gae */
+    const float* done;         /* [rows] */
+    float* loss;               /* out [1] */
+    float* d_values;           /* out [rows, n] */
+    float* returns;            /* out [rows, n] (optional) */
+    float* workspace;
+    int64_t workspace_floats;  /* >= FLEXNET_PPO_WS_FLOATS */
+} FlexPpoValueArgs;
+
+int flexnet_ppo_gae(const FlexPpoGaeArgs* args, void* stream);
+int flexnet_ppo_policy_loss(const FlexPpoPolicyArgs* args, void* stream);
+int flexnet_ppo_value_loss(const FlexPpoValueArgs* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

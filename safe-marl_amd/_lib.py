@@ -79,6 +79,7 @@ SYMBOLS = (
     "flexnet_scaled_sum", "flexnet_agent_sum_explore", "flexnet_gather_rows", "flexnet_gather_rows_td", "flexnet_window_refresh", "flexnet_gather_window", "flexnet_linear2", "flexnet_gru_backward",
     "flexnet_qmix_forward", "flexnet_qmix_backward",
     "flexnet_sqddpg_draw", "flexnet_sqddpg_forward", "flexnet_sqddpg_backward",
+    "flexnet_ppo_gae", "flexnet_ppo_policy_loss", "flexnet_ppo_value_loss",
     "flexopf_qp_work_doubles", "flexopf_qp_solve",
 )
 
@@ -244,6 +245,44 @@ class FlexSqddpgArgs(C.Structure):
                [(k, C.c_void_p) for k in SQDDPG_PTRS]
 
 
+FLEXNET_PPO_BLOCKS = 256
+FLEXNET_PPO_WS_FLOATS = 2 * FLEXNET_TD_WS_FLOATS + 2 * FLEXNET_PPO_BLOCKS
+
+
+class FlexPpoBatchNorm(C.Structure):
+    """include/flexnet.h"""
+    _fields_ = [("enabled", C.c_int32), ("eps", C.c_float), ("momentum", C.c_float), ("pad0", C.c_int32)] + \
+               [(k, C.c_void_p) for k in ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")]
+
+
+class FlexPpoGaeArgs(C.Structure):
+    """include/flexnet.h"""
+    _fields_ = [("rows", C.c_int64), ("chain_stride", C.c_int64), ("n_agents", C.c_int32), ("gamma", C.c_float),
+                ("lambda_", C.c_float), ("pad0", C.c_int32)] + \
+               [(k, C.c_void_p) for k in ("reward", "old_values", "old_next_values", "done", "last_step")] + \
+               [("reward_bn", FlexPpoBatchNorm), ("adv_bn", FlexPpoBatchNorm)] + \
+               [(k, C.c_void_p) for k in ("reward_norm", "advantages", "advantages_norm", "workspace")] + \
+               [("workspace_floats", C.c_int64)]
+
+
+class FlexPpoPolicyArgs(C.Structure):
+    """include/flexnet.h"""
+    _fields_ = [("rows", C.c_int64), ("n_agents", C.c_int32), ("act_dim", C.c_int32), ("eps_clip", C.c_float),
+                ("pad0", C.c_int32)] + \
+               [(k, C.c_void_p) for k in ("means", "log_std", "actions", "old_log_prob", "advantages", "loss", "d_means",
+                                          "ratio", "workspace")] + \
+               [("workspace_floats", C.c_int64)]
+
+
+class FlexPpoValueArgs(C.Structure):
+    """include/flexnet.h"""
+    _fields_ = [("rows", C.c_int64), ("n_agents", C.c_int32), ("gamma", C.c_float), ("eps_clip", C.c_float),
+                ("value_loss_coef", C.c_float)] + \
+               [(k, C.c_void_p) for k in ("values", "old_values", "next_values", "reward_norm", "done", "loss", "d_values",
+                                          "returns", "workspace")] + \
+               [("workspace_floats", C.c_int64)]
+
+
 class FlexSumArgs(C.Structure):
     """include/flexnet.h"""
     _fields_ = [("n", C.c_int64), ("scale", C.c_float), ("pad0", C.c_int32), ("x", C.c_void_p), ("out", C.c_void_p),
@@ -375,6 +414,10 @@ def load():
         fn.restype = C.c_int
     lib.flexnet_sqddpg_draw.argtypes = [C.POINTER(FlexSqddpgDrawArgs), vp]
     lib.flexnet_sqddpg_draw.restype = C.c_int
+    for fn, st in ((lib.flexnet_ppo_gae, FlexPpoGaeArgs), (lib.flexnet_ppo_policy_loss, FlexPpoPolicyArgs),
+                   (lib.flexnet_ppo_value_loss, FlexPpoValueArgs)):
+        fn.argtypes = [C.POINTER(st), vp]
+        fn.restype = C.c_int
     for fn in (lib.flexnet_sqddpg_forward, lib.flexnet_sqddpg_backward):
         fn.argtypes = [C.POINTER(FlexSqddpgArgs), vp]
         fn.restype = C.c_int

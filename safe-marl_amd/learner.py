@@ -25,7 +25,7 @@ from .nets import (WGRAD_MIN_ROWS, CriticTail, critic_first_layer, critic_td_los
                    critic_policy_loss_supported, expand_agents, MLPAgent, MLPCritic, RNNAgent, critic_policy_supported, critic_replayed_supported,
                    critic_tail_supported, fused_actor_forward, tall_linear, td_loss, td_loss_supported, wide_batch_linear,
                    batchnorm_stats_supported, batchnorm_update_running_stats, sync_batchnorm, QMixer,
-                   sqddpg_draw, sqddpg_fused_config, sqddpg_shapley_fused)
+                   sqddpg_draw, sqddpg_fused_config, sqddpg_shapley_fused, ppo_gae, ppo_policy_loss, ppo_value_loss)
 from .replay_buffer import Transition
 from .util import graph_capture, prep_obs, scale_action, select_action, translate_action, mean_all, note_fallback
 
@@ -71,7 +71,7 @@ class RolloutGraph:
         # MATD3 / IDDPG with the bound enforced: their agent-summed action selection (matd3.py:92-97, iddpg.py:66-71 over
         # util.py:57-64) and translate_action as ONE launch behind the fused policy — bit-identical to get_actions +
         # env_action (same draws from torch's generator, every fp32 rounding in the same place), ~40 launches fewer per step
-        self.summed = (type(model).__name__ in ("MATD3", "IDDPG", "FACMADDPG", "SQDDPG")
+        self.summed = (type(model).__name__ in ("MATD3", "IDDPG", "FACMADDPG", "SQDDPG", "IPPO", "MAPPO")
                        and type(model).get_actions in (MATD3.get_actions, IDDPG.get_actions)
                        and bool(model.args.action_enforcebound) and bool(model.args.continuous) and a > 1
                        and env.obs.is_cuda and model.fused_inference and model.args.shared_params)
@@ -565,6 +565,12 @@ class Model(nn.Module):
         return out
 
     # -- update cadence (model.py:40-71) -----------------------------------------------------------
+    on_policy = False                # IPPO / MAPPO: the replay is cleared after every update event (model.py:54-57)
+
+    def _unfiled_columns(self, n_envs):
+        """What the vectorised rollout files for log_prob_a / value / next_value: constants nobody reads (the DDPG losses)."""
+        return dict(log_prob_a=0.0, value=0.0, next_value=0.0)
+
     def transition_update(self, trainer, trans, stat):
         if self.args.replay:
             if trans is not None:
@@ -573,6 +579,8 @@ class Model(nn.Module):
                 and len(trainer.replay_buffer.buffer) >= trainer.effective_batch_size() \
                 and trainer.steps % self.args.behaviour_update_freq == 0
             if replay_cond:
+                if self.on_policy:                        # old values of every transition the event's windows may read
+                    self.begin_update_event(trainer)
                 if hasattr(trainer, "replay_event"):      # same sub-updates in the same order, software-pipelined
                     trainer.replay_event(stat, self.args.value_update_epochs, self.args.policy_update_epochs)
                 else:
@@ -583,22 +591,29 @@ class Model(nn.Module):
                 if getattr(self.args, "mixer", False):              # model.py:51-53: after the value and policy steps
                     for _ in range(self.args.mixer_update_epochs):
                         trainer.mixer_replay_process(stat)
+                if self.on_policy:                        # model.py:54-57: the data of an on-policy update is used once
+                    trainer.replay_buffer.clear()
         else:
             raise NotImplementedError("the MADDPG path always replays (default.yaml:22)")
         if self.args.target and trainer.steps % self.args.target_update_freq == 0:
             self.update_target()
 
     # -- batches -----------------------------------------------------------------------------------------
-    def unpack_data(self, batch, normalise_reward=True):
-        """model.py:308-323.  ``batch`` is a Transition of device tensors (replay_buffer.window) or, for
-        callers written against the reference, a Transition of per-sample tuples (trainer.py:68).
-        ``normalise_reward=False`` hands the raw reward on: the caller applies the BatchNorm itself (the fused value
-        loss does, together with the running-statistics update — exactly once per get_loss call either way)."""
+    def _tensor_batch(self, batch):
+        """A Transition of per-sample tuples (trainer.py:68) as a Transition of device tensors; tensors pass through."""
         if not isinstance(batch.reward, th.Tensor):
             batch = Transition(*[th.stack([th.as_tensor(np.asarray(x), dtype=th.float32) for x in f]).to(self.device)
                                  for f in batch])
             # model.py:312-320 concatenates the [1, n, x] per-step arrays along axis 0
             batch = Transition(*[f.squeeze(1) if f.dim() == 4 else f for f in batch])
+        return batch
+
+    def unpack_data(self, batch, normalise_reward=True):
+        """model.py:308-323.  ``batch`` is a Transition of device tensors (replay_buffer.window) or, for
+        callers written against the reference, a Transition of per-sample tuples (trainer.py:68).
+        ``normalise_reward=False`` hands the raw reward on: the caller applies the BatchNorm itself (the fused value
+        loss does, together with the running-statistics update — exactly once per get_loss call either way)."""
+        batch = self._tensor_batch(batch)
         reward = batch.reward.float()
         if self.args.reward_normalisation and normalise_reward:
             # train-mode batch statistics (running stats still update).  The affine pair is in no optimiser
@@ -698,7 +713,7 @@ class Model(nn.Module):
             next_obs = env.obs
             donef = done.float()
             last_step = donef if t < horizon - 1 else th.ones_like(donef)       # model.py:229
-            buf.add_batch(state=obs, action=action_pol, log_prob_a=0.0, value=0.0, next_value=0.0,
+            buf.add_batch(state=obs, action=action_pol, **self._unfiled_columns(N),
                           reward=reward.float().unsqueeze(1).expand(N, self.n_), next_state=next_obs, done=donef,
                           last_step=last_step, action_avail=1.0, last_hid=last_hid, hid=hid)
             self.transition_update(trainer, None, stat)
@@ -1674,3 +1689,188 @@ class SQDDPG(MADDPG):
             returns = rewards + self.args.gamma * (1 - done) * next_sum
             value_loss = mean_all((returns - phi.sum(dim=-1, keepdim=True)).pow(2))
         return policy_loss, value_loss, action_out
+
+
+class _PPO:
+    """madrl/learning_algorithms/ppo.py:7-10: what the reference's ``self.rl`` holds beside the loss — the BatchNorm of the
+    advantages.  A plain object: the module stays outside the model's state_dict, as in the reference."""
+
+    def __init__(self, args, device):
+        self.args = args
+        self.batchnorm = nn.BatchNorm1d(args.agent_num).to(device)
+
+
+class IPPO(Model):
+    """madrl/models/ippo.py:9-83 with the loss of madrl/learning_algorithms/ppo.py:14-69: the fixed-std RNN policy with the
+    agent-summed action selection of IDDPG, independent state-value nets V_i(o_i) (plus the one-hot id), GAE on the values
+    filed with the data, the clipped surrogate and the clipped value loss.  On the GPU the loss around the networks is
+    csrc/ppo.hip (nets.ppo_gae / ppo_policy_loss / ppo_value_loss); elsewhere the tensor composition of the same formulas.
+
+    ``gae_chain_stride``: row i of a batch continues into row i + stride.  1 is the reference's layout (a batch is one
+    chain); the trainer sets it to the number of environments, whose pooled windows are whole vector steps, time-major.
+    ``args.ppo_consistent_ratio`` (off by default, NOT the reference): the old log-probability is the loss's own
+    log-density under the parameters that collected the data, instead of the action (model.py:313)."""
+
+    on_policy = True
+    graph_safe_updates = False       # sub-updates run eagerly
+    gae_chain_stride = 1
+    fused_ppo = True                 # (tests switch it off to compare with the tensor composition)
+    get_actions = IDDPG.get_actions  # ippo.py:61-79 (continuous branch): the same function object
+    FILE_ROWS = 131072               # rows per pass of begin_update_event
+
+    def __init__(self, args, target_net=None):
+        super().__init__(args)
+        if not args.continuous:
+            raise NotImplementedError("discrete control is outside the flexibility-provision hot path")
+        self.construct_model()
+        self.apply(self.init_weights)
+        if target_net is not None:
+            self.target_net = target_net
+            self.reload_params_to_target()
+        object.__setattr__(self, "rl", _PPO(self.args, self.device))
+        self.consistent_ratio = bool(getattr(args, "ppo_consistent_ratio", False))
+        self.last_terms = {}
+
+    def construct_value_net(self):
+        """ippo.py:19-28: a V(s), input obs + id."""
+        input_shape = self.obs_dim + (self.n_ if self.args.agent_id else 0)
+        count = 1 if self.args.shared_params else self.n_
+        self.value_dicts = nn.ModuleList([MLPCritic(input_shape, 1, self.args) for _ in range(count)])
+
+    def construct_model(self):
+        self.construct_value_net()
+        self.construct_policy_net()
+
+    def value(self, obs, act=None):
+        """ippo.py:34-59: rows [o_i | onehot(i)] -> [b, n, 1]; ``act`` is ignored."""
+        b = obs.size(0)
+        if self.args.agent_id:
+            ids = th.eye(self.n_, device=obs.device, dtype=obs.dtype).expand(b, -1, -1)
+            obs = th.cat((obs, ids), dim=-1)
+        if self.args.shared_params:
+            net = self.value_dicts[0]
+            rows = obs.reshape(b * self.n_, -1)
+            if rows.is_cuda and rows.shape[0] >= WGRAD_MIN_ROWS and self.fused_inference:
+                # update batches, as IDDPG.value: csrc/wgrad.hip behind the first layer, the fused tail kernels after it
+                v, _ = net.forward_from_hidden(tall_linear(rows, net.fc1.weight, net.fc1.bias), need_hidden=False)
+            else:
+                v, _ = net(rows, None)
+            return v.view(b, self.n_, -1)
+        return th.stack([net(obs[:, i, :], None)[0] for i, net in enumerate(self.value_dicts)], dim=1)
+
+    def _unfiled_columns(self, n_envs):
+        """Real columns: begin_update_event files the values (and the consistent log-probability) into them."""
+        z = th.zeros(n_envs, self.n_, 1, device=self.device)
+        out = dict(value=z, next_value=z, log_prob_a=0.0)
+        if self.consistent_ratio:
+            out["log_prob_a"] = th.zeros(n_envs, self.n_, self.act_dim, device=self.device)
+        return out
+
+    # -- old values --------------------------------------------------------------------------------------------------
+    def log_density(self, means, log_stds, actions):
+        """ppo.py:19-28: log N(actions; agent-summed means, exp(agent-summed log-stds)) [b, n, a]."""
+        from torch.distributions.normal import Normal
+        if means.size(-1) > 1:
+            means, log_stds = means.sum(dim=1, keepdim=True), log_stds.sum(dim=1, keepdim=True)
+        return Normal(means, log_stds.exp(), validate_args=False).log_prob(actions)
+
+    def begin_update_event(self, trainer):
+        """Files ``value`` = V(s) and ``next_value`` = V(s') of every transition in the replay, in tall passes, before the
+        first sub-update of an update event — for the vectorised rollouts, which do not value each step as model.py:218,226
+        does.  Nothing has trained since the replay was last cleared, so these are the values the per-step route would have
+        stored (tests/test_ppo_cpu.py).  With ``ppo_consistent_ratio`` the log-density column is filed the same way, on
+        either route."""
+        buf = trainer.replay_buffer
+        vec = getattr(trainer.env, "n_envs", 1) > 1 or buf.slab_mode
+        if not (vec or self.consistent_ratio):
+            return
+        if buf.slab_mode:
+            buf.enable_filed_columns(log_prob=self.consistent_ratio)
+        N = max(1, getattr(trainer.env, "n_envs", 1))
+        chunk = max(N, self.FILE_ROWS // (N * self.n_) * N)
+        with th.no_grad():
+            for start, count in buf.contiguous_runs():
+                for c in range(start, start + count, chunk):
+                    m = min(chunk, start + count - c)
+                    w = buf.window(c, m)
+                    cols = {}
+                    if vec:
+                        cols["value"] = self.value(w.state, None).reshape(m, self.n_, 1)
+                        cols["next_value"] = self.value(w.next_state, None).reshape(m, self.n_, 1)
+                    if self.consistent_ratio:
+                        means, log_stds, _ = self.policy(w.state, last_hid=w.last_hid)
+                        lp = self.log_density(means, log_stds, w.action)
+                        cols["log_prob_a"] = lp[:, :buf.field_rows("log_prob_a")]
+                    buf.file_columns(c, m, **cols)
+
+    # -- loss ----------------------------------------------------------------------------------------------------------
+    def get_loss(self, batch, need="both"):
+        """ppo.py:14-69 -> (policy_loss, value_loss, (means, log_stds)).  ``need`` = "value" / "policy" builds only that
+        loss's graph; the reward and advantage BatchNorms move once per call whichever it is, as in the reference, which
+        evaluates both losses every time."""
+        args, n = self.args, self.n_
+        batch = self._tensor_batch(batch)
+        state, actions, _, old_values, old_next_values, rewards, next_state, done, last_step, actions_avail, last_hids, _ = \
+            self.unpack_data(batch, normalise_reward=False)
+        fused = bool(self.fused_ppo and self.fused_inference)
+        reward_bn = self.batchnorm if args.reward_normalisation else None
+        adv_bn = self.rl.batchnorm if args.normalize_advantages else None
+        reward_norm, advantages, advantages_norm = ppo_gae(
+            rewards, old_values, old_next_values, done, last_step, args.gamma, args.lambda_, self.gae_chain_stride,
+            reward_bn, adv_bn, fused=fused)
+        terms = dict(advantages=advantages, advantages_norm=advantages_norm, reward_norm=reward_norm)
+        policy_loss = value_loss = action_out = None
+        if need in ("both", "policy"):
+            means, log_stds, _ = self.policy(state, last_hid=last_hids)
+            action_out = (means, log_stds)
+            old = batch.log_prob_a if self.consistent_ratio else None
+            policy_loss, terms["ratios"] = ppo_policy_loss(means, log_stds, actions, old, advantages_norm, args.eps_clip,
+                                                           actions_avail, fused=fused)
+        if need in ("both", "value"):
+            values = self.value(state, None).contiguous().view(-1, n)
+            with th.no_grad():
+                next_values = self.value(next_state, None).contiguous().view(-1, n)
+            value_loss, terms["returns"] = ppo_value_loss(values, old_values, next_values, reward_norm, done, args.gamma,
+                                                          args.eps_clip, args.value_loss_coef, fused=fused)
+        self.last_terms = terms          # (tests and tools read the intermediates of the last call)
+        return policy_loss, value_loss, action_out
+
+
+class MAPPO(IPPO):
+    """madrl/models/mappo.py:9-89: IPPO whose value nets see every agent's observation, V_i(o_1..o_n, onehot(i))."""
+
+    def construct_value_net(self):
+        """mappo.py:19-28"""
+        input_shape = self.obs_dim * self.n_ + (self.n_ if self.args.agent_id else 0)
+        count = 1 if self.args.shared_params else self.n_
+        self.value_dicts = nn.ModuleList([MLPCritic(input_shape, 1, self.args) for _ in range(count)])
+
+    def value(self, obs, act=None):
+        """mappo.py:34-62: rows [o_1 .. o_n | onehot(i)] -> [b, n, 1].  The n rows of a sample differ in the id column only,
+        so the shared net's first layer is formed ONCE per sample and the id column added per agent — on the GPU by the
+        critic's first-layer and tail kernels (as MADDPG.value on replayed actions)."""
+        b, n, o = obs.size(0), self.n_, self.obs_dim
+        obs_cols = obs.reshape(b, n * o)
+        if self.args.shared_params:
+            net = self.value_dicts[0]
+            W, bias = net.fc1.weight, net.fc1.bias
+            if obs.is_cuda and self.fused_inference and b * n >= WGRAD_MIN_ROWS:
+                if th.is_grad_enabled() and W.requires_grad:
+                    shared = wide_batch_linear(obs_cols, W[:, :n * o]) + bias
+                else:
+                    shared = th.addmm(bias, obs_cols, W[:, :n * o].t())
+                if self.args.agent_id and critic_tail_supported(net, shared):
+                    return CriticTail.apply_composed(shared, W[:, n * o:n * o + n].t(), net).view(b, n, 1)
+                h = shared.unsqueeze(1).expand(b, n, -1)
+                if self.args.agent_id:
+                    h = h + W[:, n * o:n * o + n].t().unsqueeze(0)
+                v, _ = net.forward_from_hidden(h.reshape(b * n, -1), need_hidden=False)
+                return v.view(b, n, 1)
+        inp = obs_cols.unsqueeze(1).expand(b, n, n * o)
+        if self.args.agent_id:
+            ids = th.eye(n, device=obs.device, dtype=obs.dtype).expand(b, -1, -1)
+            inp = th.cat((inp, ids), dim=-1)
+        if self.args.shared_params:
+            v, _ = self.value_dicts[0](inp.reshape(b * n, -1), None)
+            return v.view(b, n, -1)
+        return th.stack([net(inp[:, i, :], None)[0] for i, net in enumerate(self.value_dicts)], dim=1)

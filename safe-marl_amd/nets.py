@@ -1870,3 +1870,211 @@ def sqddpg_shapley_fused(critic, obs2d, act, pos, ns, want_q=False, frozen=False
     phi, q = _SqddpgFn.apply(z_shared, z_id, w_act, act, pos, ns, 1e-5 if ln is None else ln.eps, ln is not None,
                              want_q, *tail)
     return phi, (q if want_q else None)
+
+
+# ---- PPO (IPPO / MAPPO): madrl/learning_algorithms/ppo.py:14-69 around the networks ---------------------------------------
+# Three pieces, each as a fused launch sequence of csrc/ppo.hip on the GPU and as the tensor composition of the same
+# formulas everywhere else (CPU, fp64, more than 8 agents, a masked action_avail, cross-rank BatchNorm statistics): the
+# composition is also what the GPU tests compare the kernels with.
+_PPO_WS = {}
+
+
+def _ppo_workspace(device):
+    """The statistics and loss partials of one call, read by that call's own finish launch: one workspace per (device,
+    stream), so calls on different streams never share one (calls on one stream run in order)."""
+    from . import _lib
+    key = (device, th.cuda.current_stream(device).cuda_stream)
+    if key not in _PPO_WS:
+        _PPO_WS[key] = th.empty(_lib.FLEXNET_PPO_WS_FLOATS // 2, dtype=th.float64, device=device)
+    return _PPO_WS[key]
+
+
+def ppo_gae_torch(reward_norm, old_values, old_next_values, done, last_step, gamma, lambda_, chain_stride=1):
+    """ppo.py:44-52 on chains: row i continues into row i + chain_stride.  The loop runs over the steps of a chain, every
+    chain of the batch at once (stride 1: the reference's literal loop over the rows); each chain sees the literal loop's
+    operations in the literal loop's order."""
+    rows, n = reward_norm.shape
+    stride = int(chain_stride)
+    if stride < 1 or rows % stride != 0:
+        raise ValueError(f"a batch of {rows} rows is not a whole number of steps of {stride} chains")
+    steps = rows // stride
+    done, last_step = done.reshape(steps, stride, 1), last_step.reshape(steps, stride, 1)
+    mask = th.where(last_step != 0, 1.0 - done, th.ones_like(done))
+    r, v, nv = (x.reshape(steps, stride, n) for x in (reward_norm, old_values, old_next_values))
+    out = th.empty_like(r)
+    last = 0
+    for t in reversed(range(steps)):
+        deltas = r[t] + gamma * nv[t] * mask[t] - v[t]
+        last = deltas + gamma * lambda_ * last * mask[t]
+        out[t] = last
+    return out.reshape(rows, n)
+
+
+def ppo_fused_supported(bns, *tensors):
+    """csrc/ppo.hip covers fp32 CUDA tensors of up to 8 agents and training-mode BatchNorm1d modules with a momentum whose
+    statistics are this rank's own (cross-rank statistics take the composition: sync_batchnorm)."""
+    ok = all(t is None or (t.is_cuda and t.dtype == th.float32) for t in tensors)
+    for bn in bns:
+        if bn is not None:
+            ok = ok and isinstance(bn, nn.BatchNorm1d) and bn.training and bn.momentum is not None and not _sync_active(bn) \
+                and bn.num_features <= 8 and (not bn.track_running_stats or bn.running_mean.dtype == th.float32)
+    return bool(ok)
+
+
+def _ppo_bn_args(dst, bn):
+    if bn is None:
+        return
+    dst.enabled, dst.eps, dst.momentum = 1, float(bn.eps), float(bn.momentum)
+    if bn.affine:
+        dst.weight, dst.bias = bn.weight.data_ptr(), bn.bias.data_ptr()
+    if bn.track_running_stats:
+        dst.running_mean, dst.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
+        dst.num_batches_tracked = bn.num_batches_tracked.data_ptr()
+
+
+def ppo_gae(reward, old_values, old_next_values, done, last_step, gamma, lambda_, chain_stride=1, reward_bn=None, adv_bn=None,
+            fused=True):
+    """(reward_norm, advantages, advantages_norm) [rows, n], no gradient: the reward through ``reward_bn`` (None: as it is),
+    GAE along the chains, the advantages through ``adv_bn`` (None: advantages_norm is advantages).  Both modules' running
+    statistics move once, as their training-mode forward moves them."""
+    rows, n = reward.shape
+    stride = int(chain_stride)
+    if stride < 1 or rows % stride != 0:
+        raise ValueError(f"a batch of {rows} rows is not a whole number of steps of {stride} chains")
+    old_values, old_next_values = old_values.reshape(rows, n), old_next_values.reshape(rows, n)
+    done, last_step = done.reshape(rows), last_step.reshape(rows)
+    with th.no_grad():
+        if fused and n <= 8 and ppo_fused_supported((reward_bn, adv_bn), reward, old_values, old_next_values, done, last_step):
+            import ctypes as C
+            from . import _lib
+            r, v, nv, d, ls = (x.contiguous() for x in (reward, old_values, old_next_values, done, last_step))
+            rn, adv = th.empty_like(r), th.empty_like(r)
+            advn = th.empty_like(r) if adv_bn is not None else adv
+            ws = _ppo_workspace(r.device)
+            a = _lib.FlexPpoGaeArgs()
+            a.rows, a.chain_stride, a.n_agents, a.gamma, a.lambda_ = rows, stride, n, float(gamma), float(lambda_)
+            a.reward, a.old_values, a.old_next_values, a.done, a.last_step = (x.data_ptr() for x in (r, v, nv, d, ls))
+            _ppo_bn_args(a.reward_bn, reward_bn)
+            _ppo_bn_args(a.adv_bn, adv_bn)
+            a.reward_norm, a.advantages, a.advantages_norm = rn.data_ptr(), adv.data_ptr(), advn.data_ptr()
+            a.workspace, a.workspace_floats = ws.data_ptr(), 2 * ws.numel()
+            rc = _lib.load().flexnet_ppo_gae(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream))
+            if rc == 0:
+                return rn, adv, advn
+            if rc != _lib.FLEXNET_EUNSUPPORTED:
+                _lib.check(rc, "flexnet_ppo_gae")
+        if fused and reward.is_cuda:
+            note_fallback("ppo_gae", f"agents {n}, dtype {reward.dtype}, cross-rank statistics or an evaluation-mode BatchNorm")
+        rn = sync_batchnorm(reward_bn, reward.contiguous()) if reward_bn is not None else reward
+        adv = ppo_gae_torch(rn, old_values, old_next_values, done, last_step, gamma, lambda_, stride)
+        advn = sync_batchnorm(adv_bn, adv) if adv_bn is not None else adv
+        return rn, adv, advn
+
+
+def ppo_policy_loss_torch(means, log_stds, actions, old_log_prob, advantages, eps_clip, actions_avail=None):
+    """ppo.py:19-33,36,57-61: (loss, ratios [rows, n]).  ``old_log_prob`` [rows, n, a] is summed over the action dimension
+    here, as the reference sums it (model.py:313 hands the ACTION over in its place)."""
+    from torch.distributions.normal import Normal
+    if means.size(-1) > 1:
+        means_, log_stds_ = means.sum(dim=1, keepdim=True), log_stds.sum(dim=1, keepdim=True)
+    else:
+        means_, log_stds_ = means, log_stds
+    log_prob_a = Normal(means_, log_stds_.exp(), validate_args=False).log_prob(actions)
+    if actions_avail is not None and getattr(actions_avail, "_flex_const", None) != 1.0:
+        restore_mask = 1.0 - (actions_avail == 0).to(means.dtype)
+        log_prob_a, old_log_prob = restore_mask * log_prob_a, restore_mask * old_log_prob
+    log_prob_a, old_log_prob = log_prob_a.sum(dim=-1), old_log_prob.sum(dim=-1)
+    ratios = th.exp(log_prob_a - old_log_prob.detach())
+    assert ratios.size() == advantages.size()
+    surr1 = ratios * advantages.detach()
+    surr2 = th.clamp(ratios, 1 - eps_clip, 1 + eps_clip) * advantages.detach()
+    return -th.min(surr1, surr2).mean(), ratios
+
+
+def ppo_value_loss_torch(values, old_values, next_values, reward_norm, done, gamma, eps_clip, value_loss_coef):
+    """ppo.py:53,63-68: (loss, returns [rows, n])."""
+    returns = reward_norm + gamma * (1 - done.reshape(-1, 1)) * next_values.detach()
+    assert old_values.size() == values.size()
+    values_clipped = old_values + th.clamp(values - old_values, -eps_clip, eps_clip)
+    surr1 = (values - returns).pow(2)
+    surr2 = (values_clipped - returns).pow(2)
+    return value_loss_coef * th.max(surr1, surr2).mean(), returns
+
+
+class _PpoLossFn(th.autograd.Function):
+    """A loss of csrc/ppo.hip whose gradient w.r.t. its one differentiable input came out of the forward launch."""
+
+    @staticmethod
+    def forward(ctx, x, loss, dx):
+        ctx.save_for_backward(dx)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        (dx,) = ctx.saved_tensors
+        from .util import is_unit_seed
+        return (dx if is_unit_seed(g) else dx * g), None, None
+
+
+def ppo_policy_loss(means, log_stds, actions, old_log_prob, advantages, eps_clip, actions_avail=None, fused=True):
+    """(loss, ratios [rows, n] detached) of ppo.py:19-36,57-61.  ``old_log_prob``: [rows, n, a] as stored (summed here), or
+    None for the reference's own choice, the action (model.py:313)."""
+    rows, n, na = means.shape
+    every = actions_avail is None or getattr(actions_avail, "_flex_const", None) == 1.0
+    if (fused and every and n <= 8 and na <= 8 and na > 1 and means.is_cuda and actions.shape == means.shape
+            and ppo_fused_supported((), means, actions, advantages, old_log_prob)
+            and getattr(log_stds, "_flex_entropy", None) is not None):
+        import ctypes as C
+        from . import _lib
+        with th.no_grad():
+            m, act, adv = means.detach().contiguous(), actions.contiguous(), advantages.reshape(rows, n).contiguous()
+            ls = log_stds.detach()[:1].sum(dim=1).reshape(na).contiguous()        # the agent-summed log-std of one row
+            old = old_log_prob.sum(dim=-1).expand(rows, n).contiguous() if old_log_prob is not None else None
+            loss = th.empty((), dtype=th.float32, device=m.device)
+            d_means, ratio = th.empty_like(m), th.empty(rows, n, dtype=th.float32, device=m.device)
+            ws = _ppo_workspace(m.device)
+            a = _lib.FlexPpoPolicyArgs()
+            a.rows, a.n_agents, a.act_dim, a.eps_clip = rows, n, na, float(eps_clip)
+            a.means, a.log_std, a.actions, a.advantages = m.data_ptr(), ls.data_ptr(), act.data_ptr(), adv.data_ptr()
+            if old is not None:
+                a.old_log_prob = old.data_ptr()
+            a.loss, a.d_means, a.ratio = loss.data_ptr(), d_means.data_ptr(), ratio.data_ptr()
+            a.workspace, a.workspace_floats = ws.data_ptr(), 2 * ws.numel()
+            rc = _lib.load().flexnet_ppo_policy_loss(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream))
+        if rc == 0:
+            return _PpoLossFn.apply(means, loss, d_means), ratio
+        if rc != _lib.FLEXNET_EUNSUPPORTED:
+            _lib.check(rc, "flexnet_ppo_policy_loss")
+    if fused and means.is_cuda:
+        note_fallback("ppo_policy_loss", f"agents {n}, act_dim {na}, dtype {means.dtype}, every action available: {every}")
+    loss, ratios = ppo_policy_loss_torch(means, log_stds, actions, actions if old_log_prob is None else old_log_prob,
+                                         advantages, eps_clip, actions_avail)
+    return loss, ratios.detach()
+
+
+def ppo_value_loss(values, old_values, next_values, reward_norm, done, gamma, eps_clip, value_loss_coef, fused=True):
+    """(loss, returns [rows, n]) of ppo.py:53,63-68; gradient w.r.t. ``values`` only."""
+    rows, n = reward_norm.shape
+    values2, old_values, next_values = values.reshape(rows, n), old_values.reshape(rows, n), next_values.reshape(rows, n).detach()
+    if fused and n <= 8 and values.is_cuda and ppo_fused_supported((), values2, old_values, next_values, reward_norm, done):
+        import ctypes as C
+        from . import _lib
+        with th.no_grad():
+            v, ov, nv, rn, d = (x.detach().contiguous() for x in (values2, old_values, next_values, reward_norm, done.reshape(rows)))
+            loss = th.empty((), dtype=th.float32, device=v.device)
+            d_values, returns = th.empty_like(v), th.empty_like(v)
+            ws = _ppo_workspace(v.device)
+            a = _lib.FlexPpoValueArgs()
+            a.rows, a.n_agents, a.gamma, a.eps_clip, a.value_loss_coef = rows, n, float(gamma), float(eps_clip), float(value_loss_coef)
+            a.values, a.old_values, a.next_values, a.reward_norm, a.done = (x.data_ptr() for x in (v, ov, nv, rn, d))
+            a.loss, a.d_values, a.returns = loss.data_ptr(), d_values.data_ptr(), returns.data_ptr()
+            a.workspace, a.workspace_floats = ws.data_ptr(), 2 * ws.numel()
+            rc = _lib.load().flexnet_ppo_value_loss(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream))
+        if rc == 0:
+            return _PpoLossFn.apply(values, loss, d_values.view(values.shape)), returns
+        if rc != _lib.FLEXNET_EUNSUPPORTED:
+            _lib.check(rc, "flexnet_ppo_value_loss")
+    if fused and values.is_cuda:
+        note_fallback("ppo_value_loss", f"agents {n}, dtype {values.dtype}")
+    loss, returns = ppo_value_loss_torch(values2, old_values, next_values, reward_norm, done, gamma, eps_clip, value_loss_coef)
+    return loss, returns.detach()

@@ -48,6 +48,8 @@ class DeviceReplayBuffer:
         self.buffer = _LenView(self)
         self.consts = {}           # field -> python float, for fields that are never stored
         self.const_shapes = {}     # field -> trailing shape of the broadcast view
+        self.v_ring = self.nv_ring = self.lp_ring = None       # slab mode: value / next_value / log_prob_a columns
+        self.filed = ()            # ... of them, the ones an on-policy learner files (enable_filed_columns)
 
     # -- allocation on first use (shapes come from the first transition) ---------------------
     def _alloc(self, shapes):
@@ -111,6 +113,8 @@ class DeviceReplayBuffer:
         self.store = None
         self.head = 0
         self.length = 0
+        self.v_ring = self.lp_ring = None      # enable_filed_columns
+        self.filed = ()
 
     @property
     def slab_mode(self):
@@ -125,6 +129,8 @@ class DeviceReplayBuffer:
         ``add_batch`` allocates its own store on the next call.  Transitions the ring held are dropped."""
         self.obs_ring = self.row_ring = self.hid_ring = self.hid_store = self.small_ring = self.nv_ring = self.cursor = None
         self.stack_ring = None
+        self.v_ring = self.lp_ring = None
+        self.filed = ()
         self.k = self.first = 0
         self.gaps = []
         self.consts, self.const_shapes = {}, {}
@@ -235,7 +241,102 @@ class DeviceReplayBuffer:
             shape = self.const_shapes.get(k, ())
             out[k] = th.full((1,) + tuple(1 for _ in shape), float(c), device=self.device).expand((batch_size,) + tuple(shape))
             out[k]._flex_const = float(c)
+        for k, ring in self._filed_rings().items():           # columns an on-policy learner filed (enable_filed_columns)
+            out[k] = take(ring, slot, batch_size).view((batch_size,) + tuple(self.const_shapes[k]))
         return Transition(**out)
+
+    # -- columns filed after the fact (on-policy learners: learner.IPPO.begin_update_event) -------------------------------
+    def enable_filed_columns(self, log_prob=False):
+        """Slab mode: ``value`` / ``next_value`` (and ``log_prob_a``) become real columns — rings beside ``small_ring``
+        that ``file_columns`` writes and ``slab_window`` hands out — instead of the constants the DDPG losses never read."""
+        dev, n = self.device, self.n_agents
+        if self.v_ring is None:
+            self.v_ring = th.zeros(self.slabs, self.n_envs, n, dtype=th.float32, device=dev)
+        if log_prob and self.lp_ring is None:
+            self.lp_ring = th.zeros(self.slabs, self.n_envs, n * self.act_dim, dtype=th.float32, device=dev)
+        self.filed = ("value", "next_value") + (("log_prob_a",) if log_prob else ())
+        for k in self.filed:
+            self.consts.pop(k, None)
+
+    def _filed_rings(self):
+        rings = {"value": self.v_ring, "next_value": self.nv_ring, "log_prob_a": self.lp_ring}
+        return {k: rings[k] for k in self.filed}
+
+    def contiguous_runs(self):
+        """[(first logical transition, count)] of the runs of consecutive transitions (slab mode: between the gaps)."""
+        if not self.slab_mode:
+            return [(0, self.length)] if self.length else []
+        out, at = [], 0
+        for a, b in self._runs():
+            out.append((at, (b - a) * self.n_envs))
+            at += (b - a) * self.n_envs
+        return out
+
+    def field_rows(self, name):
+        """Rows per transition of a stored field (the reference's single-env rollout stores [1, a] log-probabilities)."""
+        if self.slab_mode:
+            return self.const_shapes[name][0]
+        return self.store[name].shape[1]
+
+    def file_columns(self, start, rows, **cols):
+        """Writes ``cols`` (field -> [rows, ...]) over the logical transitions [start, start + rows)."""
+        if self.slab_mode:
+            slot = self._logical_to_slot(start)
+            rings = self._filed_rings()
+            for k, v in cols.items():
+                flat, v, off = rings[k].view(self.slabs * self.n_envs, -1), v.reshape(rows, -1), 0
+                for p, c in self.segments(slot, rows):
+                    flat[p:p + c].copy_(v[off:off + c])
+                    off += c
+            return
+        p0 = (self.head + start) % self.size
+        for k, v in cols.items():
+            dst = self.store[k]
+            if p0 + rows <= self.size:
+                dst[p0:p0 + rows].copy_(v.reshape((rows,) + dst.shape[1:]))
+            else:
+                idx = (p0 + th.arange(rows, device=self.device)) % self.size
+                dst.index_copy_(0, idx, v.reshape((rows,) + dst.shape[1:]).to(dst.dtype))
+
+    def aligned_window(self, step, batch_size, n_envs):
+        """The window of ``batch_size`` transitions that starts at vector step ``step`` (0 = the oldest) of a time-major
+        replay of ``n_envs`` environments: whole vector steps, row = t * n_envs + env.  ValueError where the batch is not a
+        whole number of steps, the replay is not step-aligned, or the window would cross a gap of the ring."""
+        self._check_aligned(batch_size, n_envs)
+        return self.window(step * n_envs, batch_size)
+
+    def _check_aligned(self, batch_size, n_envs):
+        if batch_size % n_envs != 0 or batch_size < n_envs:
+            raise ValueError(f"a pooled window of {batch_size} transitions is not a whole number of steps of {n_envs} environments")
+        if self.slab_mode:
+            if n_envs != self.n_envs:
+                raise ValueError("the slab ring was allocated for another number of environments")
+        elif self.length % n_envs != 0 or self.head % n_envs != 0:
+            raise ValueError("the replay does not hold whole vector steps")
+
+    def sample_aligned(self, batch_size, n_envs):
+        """utils/replay_buffer.py:17-21 over step-aligned windows: a uniformly random start among the windows of
+        ``batch_size // n_envs`` consecutive whole vector steps (none spans a gap).  Returns the start's vector step."""
+        self._check_aligned(batch_size, n_envs)
+        w = batch_size // n_envs
+        spans, at = [], 0
+        for _, count in self.contiguous_runs():
+            steps = count // n_envs
+            if steps >= w:
+                spans.append((at, steps - w + 1))
+            at += steps
+        total = sum(c for _, c in spans)
+        if total < 1:
+            raise ValueError("not enough transitions for a batch")
+        r = int(np.random.randint(total))
+        for base, c in spans:
+            if r < c:
+                return base + r
+            r -= c
+        raise AssertionError
+
+    def get_window_aligned(self, batch_size, n_envs):
+        return self.aligned_window(self.sample_aligned(batch_size, n_envs), batch_size, n_envs)
 
     def stacked_obs(self, slot, rows, out=None):
         """Row mode: the stacked observations [rows, n_agents * obs_dim] of the global slot range [slot, slot + rows), formed

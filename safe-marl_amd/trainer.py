@@ -94,6 +94,7 @@ class PGTrainer(object):
         from .nets import set_reward_bn_sync
         for m in (net, getattr(net, "target_net", None)):          # the flag lives on THIS trainer's BatchNorm modules
             set_reward_bn_sync(getattr(m, "batchnorm", None), self.sync_reward_bn)
+            set_reward_bn_sync(getattr(getattr(m, "rl", None), "batchnorm", None), self.sync_reward_bn)   # PPO's advantages
         cap = dict(capturable=True) if self.device.type == "cuda" else {}       # optimiser steps inside HIP graphs
         self.policy_optimizer = RMSprop(net.policy_dicts.parameters(), lr=args.policy_lrate, **_RMSPROP, **cap)
         self.value_optimizer = RMSprop(net.value_dicts.parameters(), lr=args.value_lrate, **_RMSPROP, **cap)
@@ -104,12 +105,25 @@ class PGTrainer(object):
 
         # replay memory sized for the number of environments feeding it
         n_envs = getattr(env, "n_envs", 1)
+        self.n_envs = n_envs
+        # IPPO / MAPPO: a pooled batch is whole vector steps — every environment contributes the reference's batch_size-step
+        # truncated episode, and GAE runs along n_envs chains (row i continues into row i + n_envs)
+        self.on_policy = bool(getattr(net, "on_policy", False))
         if batch_scale is None:
-            batch_scale = 1 if n_envs == 1 else max(1, n_envs // 4)
+            batch_scale = 1 if n_envs == 1 else (n_envs if self.on_policy else max(1, n_envs // 4))
         self.batch_scale = batch_scale
+        if self.on_policy and n_envs > 1:
+            if self.effective_batch_size() % n_envs != 0:
+                raise ValueError(f"an on-policy batch of {self.effective_batch_size()} transitions is not a whole number of "
+                                 f"steps of {n_envs} environments")
+            net.gae_chain_stride = n_envs
         if args.replay:
             if replay_capacity is None:
                 replay_capacity = int(args.replay_buffer_size) * max(1, min(n_envs, 64))
+                if self.on_policy and n_envs > 1:
+                    # everything collected between two update events, plus the two slabs the ring keeps back for the
+                    # step in flight (the rows an observation reaches back into come on top: alloc_slabs' keep_back)
+                    replay_capacity = max(replay_capacity, (int(args.behaviour_update_freq) + 4) * n_envs)
             self.replay_buffer = TransReplayBuffer(replay_capacity, device=self.device)
 
     # ---- sampling ----------------------------------------------------------------------------
@@ -119,16 +133,22 @@ class PGTrainer(object):
     def get_loss(self, batch, need="both"):
         return self.behaviour_net.get_loss(batch, need=need)
 
+    def _sample_batch(self):
+        """The eager sub-updates' batch: utils/replay_buffer.py:17-21, step-aligned for the pooled on-policy windows."""
+        if self.on_policy and self.n_envs > 1:
+            return self.replay_buffer.get_window_aligned(self.effective_batch_size(), self.n_envs)
+        return self.replay_buffer.get_batch_tensors(self.effective_batch_size())
+
     def policy_replay_process(self, stat):      # model.py:50
         if not self._graphed_sub_update("policy", stat):
-            self._sub_update("policy", stat, self.replay_buffer.get_batch_tensors(self.effective_batch_size()))
+            self._sub_update("policy", stat, self._sample_batch())
 
     def value_replay_process(self, stat):       # model.py:48
         if not self._graphed_sub_update("value", stat):
-            self._sub_update("value", stat, self.replay_buffer.get_batch_tensors(self.effective_batch_size()))
+            self._sub_update("value", stat, self._sample_batch())
 
     def mixer_replay_process(self, stat):       # model.py:51-53 (eager: FACMADDPG's sub-updates are not graphed)
-        self._sub_update("mixer", stat, self.replay_buffer.get_batch_tensors(self.effective_batch_size()))
+        self._sub_update("mixer", stat, self._sample_batch())
 
     def _optimizer(self, which):
         return {"policy": self.policy_optimizer, "value": self.value_optimizer, "mixer": self.mixer_optimizer}[which]
