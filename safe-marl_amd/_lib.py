@@ -483,3 +483,22 @@ def load():
 def check(rc, what):
     if rc != 0:
         raise FlexLibraryError(f"{what} failed with code {rc}")
+
+
+def try_launch(name, *args, stream=None):
+    """Call the entry point ``name`` as name(args..., stream): every ctypes.Structure goes by reference, anything else (an
+    integer phase, None for an absent structure) as it is; ``stream`` is a torch stream, default the current one of the current
+    device.  False if the library answers FLEXNET_EUNSUPPORTED (the caller falls back), FlexLibraryError on any other error."""
+    import torch
+    stream = torch.cuda.current_stream() if stream is None else stream
+    rc = getattr(load(), name)(*[C.byref(a) if isinstance(a, C.Structure) else a for a in args], C.c_void_p(stream.cuda_stream))
+    if rc == FLEXNET_EUNSUPPORTED:
+        return False
+    check(rc, name)
+    return True
+
+
+def launch(name, *args, stream=None):
+    """``try_launch`` for a call the library must accept: FLEXNET_EUNSUPPORTED raises like every other error."""
+    if not try_launch(name, *args, stream=stream):
+        check(FLEXNET_EUNSUPPORTED, name)

@@ -225,7 +225,6 @@ class RolloutGraph:
 
     def _pack(self, action, hid):
         """model.py:230-262 for every environment in one launch (include/flexnet.h: flexnet_rollout_pack)."""
-        import ctypes as C
         from . import _lib
         m, env, buf = self.model, self.env, self.buf
         a = _lib.FlexRolloutPackArgs()
@@ -242,8 +241,7 @@ class RolloutGraph:
                 setattr(a, name, t.data_ptr())
         if not self.torch_noise:
             a.rng_state = self.rng_state.data_ptr()       # next step of the actor kernel's noise stream
-        _lib.check(_lib.load().flexnet_rollout_pack(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                   "flexnet_rollout_pack")
+        _lib.launch("flexnet_rollout_pack", a)
 
     def last_transition(self):
         """Views of the transition the last step wrote (tests, debugging): the slab before the cursor."""
@@ -1121,6 +1119,13 @@ def _maddpg_critic_policy_loss(self, state, actions_pol):
     return critic_policy_loss(obs_cols, actions_pol, net, sign=-1.0)
 
 
+def _fc1_reads_in_place(self, net):
+    """``net``'s first layer is the [64, obs | act | ids] one whose product flexnet_linear2 forms from the ring in place."""
+    n, fc1 = self.n_, getattr(net, "fc1", None)
+    return ((n * self.obs_dim) % 8 == 0 and (n * self.act_dim) % 4 == 0 and n * (self.obs_dim + self.act_dim) <= 768
+            and fc1 is not None and fc1.weight.shape == (64, n * (self.obs_dim + self.act_dim) + n))
+
+
 def _maddpg_reads_state_in_place(self, bs):
     """True iff a value sub-update on filed bootstrap values ("value_cached") touches ``batch.state`` ONLY through
     nets._CriticTdLossFn — whose first layer (flexnet_linear2) and weight gradient (flexnet_wgrad) can read the window in place
@@ -1129,15 +1134,11 @@ def _maddpg_reads_state_in_place(self, bs):
     the batch's values; a subclass with its own get_loss / value / critic input layout (MATD3, IDDPG) answers False."""
     from .nets import CRITIC_TD_MIN_ROWS, CRITIC_VARIANT
     import safe_marl_amd.nets as _nets
-    n = self.n_
-    net = self.value_dicts[0]
-    fc1 = getattr(net, "fc1", None)
     return bool(type(self).get_loss is MADDPG.get_loss and type(self)._critic_td_loss is _maddpg_critic_td_loss
                 and type(self).value is MADDPG.value and self.args.shared_params and self.args.agent_id
                 and self.fused_td_backward and self.fused_inference and _nets.CRITIC_FC1_FUSED
-                and bs * n >= CRITIC_TD_MIN_ROWS and CRITIC_VARIANT == 0 and _nets.CRITIC_PGRAD32 == 0
-                and (n * self.obs_dim) % 8 == 0 and (n * self.act_dim) % 4 == 0 and n * (self.obs_dim + self.act_dim) <= 768
-                and fc1 is not None and fc1.weight.shape == (64, n * (self.obs_dim + self.act_dim) + n))
+                and bs * self.n_ >= CRITIC_TD_MIN_ROWS and CRITIC_VARIANT == 0 and _nets.CRITIC_PGRAD32 == 0
+                and _fc1_reads_in_place(self, self.value_dicts[0]))
 
 
 def _maddpg_reads_next_state_in_place(self, bs):
@@ -1149,16 +1150,13 @@ def _maddpg_reads_next_state_in_place(self, bs):
     tgt = getattr(self, "target_net", None)
     if tgt is None or type(self).bootstrap_values is not MADDPG.bootstrap_values or type(self).policy is not Model.policy:
         return False
-    agent, net = self.policy_dicts[0], tgt.value_dicts[0]
-    fc1 = getattr(net, "fc1", None)
+    agent = self.policy_dicts[0]
     a = agent.args
     return bool(type(self).get_actions is MADDPG.get_actions and type(tgt).value is MADDPG.value and self.args.shared_params
                 and self.args.agent_id and self.fused_inference and tgt.fused_inference and _nets.CRITIC_FC1_FUSED
                 and isinstance(agent, _nets.RNNAgent) and a.hid_size == 64 and a.hid_activation == "relu"
                 and self.obs_dim <= 144 and n <= 8 and a.action_dim <= 8
-                and (n * self.obs_dim) % 8 == 0 and (n * self.act_dim) % 4 == 0 and n * (self.obs_dim + self.act_dim) <= 768
-                and fc1 is not None and fc1.weight.shape == (64, n * (self.obs_dim + self.act_dim) + n)
-                and bs * n >= 65536)
+                and _fc1_reads_in_place(self, tgt.value_dicts[0]) and bs * n >= 65536)
 
 
 MADDPG.reads_state_in_place = _maddpg_reads_state_in_place
@@ -1173,7 +1171,6 @@ def summed_exploration(model, means, env_action=None, action_out=None):
     """tanh(sum over agents of the means + exp(sum of log-stds) * eps), the ONE action of matd3.py:92-97 / iddpg.py:66-71
     under util.py:57-64, handed to every agent: [b, n, a] (and, with ``env_action``, translate_action of it) from one launch
     of flexnet_agent_sum_explore.  eps is Normal.rsample's own draw; every fp32 rounding sits where the tensor ops have it."""
-    import ctypes as C
     import torch.distributions.normal as tdn      # (looked up at call time: the very function Normal.rsample calls)
     from . import _lib
     b, n, a = means.shape
@@ -1191,8 +1188,7 @@ def summed_exploration(model, means, env_action=None, action_out=None):
     k.means, k.eps, k.std, k.action = means.data_ptr(), eps.data_ptr(), cache[means.device].data_ptr(), out.data_ptr()
     if env_action is not None:
         k.env_action = env_action.data_ptr()
-    _lib.check(_lib.load().flexnet_agent_sum_explore(C.byref(k), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-               "flexnet_agent_sum_explore")
+    _lib.launch("flexnet_agent_sum_explore", k)
     return out
 
 
@@ -1212,7 +1208,6 @@ class _SumBroadcastAgentsFn(th.autograd.Function):
 
 
 def _sum_broadcast(model, x):
-    import ctypes as C
     from . import _lib
     b, n, a = x.shape
     x = x.contiguous()
@@ -1220,8 +1215,7 @@ def _sum_broadcast(model, x):
     k = _lib.FlexAgentSumArgs()
     k.n_envs, k.n_agents, k.act_dim = b, n, a
     k.means, k.action = x.data_ptr(), out.data_ptr()
-    _lib.check(_lib.load().flexnet_agent_sum_explore(C.byref(k), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-               "flexnet_agent_sum_explore")
+    _lib.launch("flexnet_agent_sum_explore", k)
     return out
 
 

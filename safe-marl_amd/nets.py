@@ -4,11 +4,13 @@ Training (autograd) runs through PyTorch-ROCm; the actor's INFERENCE pass — ev
 bootstrap target — is one fused HIP launch (csrc/actor.hip, include/flexnet.h) through ``fused_actor_forward``."""
 from __future__ import annotations
 
+import math
 import os
 import torch as th
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _lib
 from .util import note_fallback
 
 
@@ -187,8 +189,6 @@ def fused_actor_forward(agent, obs, hidden, n_agents, agent_id, noise=None, std=
     burst, which runs this policy evaluation inside the environment's persistent launch (flex_env.rollout_burst).
     ``obs_source`` (a ``_lib.FlexObsSource``, VecFlexProvisionEnv.obs_source()): the observations are read IN PLACE from
     the environment's history (``obs`` then only gives the shape [b, n, obs_dim]; it is not read)."""
-    import ctypes as C
-    from . import _lib
     a = agent.args
     if not (isinstance(agent, RNNAgent) and a.hid_size == 64 and a.hid_activation == "relu" and obs.is_cuda
             and obs.dtype == th.float32 and obs.shape[-1] <= 144 and n_agents <= 8 and a.action_dim <= 8):
@@ -196,7 +196,6 @@ def fused_actor_forward(agent, obs, hidden, n_agents, agent_id, noise=None, std=
             note_fallback("actor_forward", f"{type(agent).__name__}, hid {a.hid_size}, act {a.hid_activation}, obs "
                                            f"{obs.shape[-1]}, agents {n_agents}, dtype {obs.dtype}")
         return None
-    lib = _lib.load()
     rows = obs.shape[0] * obs.shape[1]
     obs_dim = obs.shape[-1]
     obs = obs.contiguous()
@@ -266,11 +265,9 @@ def fused_actor_forward(agent, obs, hidden, n_agents, agent_id, noise=None, std=
     if launch is not None:
         launch(args)
         return (means, hid_out, action, env_action) if explore else (means, hid_out)
-    rc = lib.flexnet_actor_forward(C.byref(args), C.c_void_p(th.cuda.current_stream().cuda_stream))
-    if rc == _lib.FLEXNET_EUNSUPPORTED:
+    if not _lib.try_launch("flexnet_actor_forward", args):
         note_fallback("actor_forward", "FLEXNET_EUNSUPPORTED from flexnet_actor_forward")
         return None
-    _lib.check(rc, "flexnet_actor_forward")
     return (means, hid_out, action, env_action) if explore else (means, hid_out)
 
 
@@ -298,9 +295,6 @@ def tall_wgrad(dy, x, out=None, accumulate=False, colsum=None, x2=None, out2=Non
     takes [x | x2] as one operand (64 output rows, x wider than 64 columns and a multiple of 5), else a second call.
     ``critic_finish`` = (FlexCriticTailArgs, FlexTdLossArgs): phase 2 of flexnet_critic_td_backward_phases rides in this
     call's second-stage launch (flexnet_wgrad_critic_finish) — or is launched on its own first where the rider does not apply."""
-    import ctypes as C
-    from . import _lib
-    lib = _lib.load()
     k, m = dy.shape
     n = x.shape[1]
     if x2 is not None and not (32 < m <= 64 and n > 64 and n % 5 == 0 and k > 1 and tall_wgrad_supported(dy, x2)
@@ -331,16 +325,11 @@ def tall_wgrad(dy, x, out=None, accumulate=False, colsum=None, x2=None, out2=Non
         a.colsum = colsum.data_ptr()
     if x2 is not None:
         a.b2, a.c2, a.ldb2, a.n2, a.ldc2 = x2.data_ptr(), out2.data_ptr(), x2.stride(0), x2.shape[1], out2.stride(0)
-    stream = C.c_void_p(th.cuda.current_stream().cuda_stream)
     if critic_finish is not None:
-        cargs, targs = critic_finish
-        rc = lib.flexnet_wgrad_critic_finish(C.byref(a), C.byref(cargs), C.byref(targs), stream) if WGRAD_FINISH_RIDER else _lib.FLEXNET_EUNSUPPORTED
-        if rc == 0:
+        if WGRAD_FINISH_RIDER and _lib.try_launch("flexnet_wgrad_critic_finish", a, *critic_finish):
             return out
-        if rc != _lib.FLEXNET_EUNSUPPORTED:
-            _lib.check(rc, "flexnet_wgrad_critic_finish")
-        _lib.check(lib.flexnet_critic_td_backward_phases(C.byref(cargs), C.byref(targs), 2, stream), "flexnet_critic_td_backward")
-    _lib.check(lib.flexnet_wgrad(C.byref(a), stream), "flexnet_wgrad")
+        _lib.launch("flexnet_critic_td_backward_phases", *critic_finish, 2)
+    _lib.launch("flexnet_wgrad", a)
     return out
 
 
@@ -437,8 +426,6 @@ def critic_first_layer(bias, obs2d, act2d, W, c_act):
           and obs2d.stride(1) == 1 and act2d.stride(1) == 1 and W.stride(1) == 1 and bias.is_contiguous()
           and not th.is_grad_enabled())
     if ok:
-        import ctypes as C
-        from . import _lib
         out = th.empty(obs2d.shape[0], 64, dtype=th.float32, device=obs2d.device)
         a = _lib.FlexLinear2Args()
         a.rows, a.k1, a.k2 = obs2d.shape[0], no, na_
@@ -446,13 +433,10 @@ def critic_first_layer(bias, obs2d, act2d, W, c_act):
         a.x1, a.x2, a.w, a.bias, a.out = obs2d.data_ptr(), act2d.data_ptr(), W.data_ptr(), bias.data_ptr(), out.data_ptr()
         if rv is not None:
             a.x1, a.x1_row_cell = rv[0].data_ptr(), rv[1].data_ptr()
-        rc = _lib.load().flexnet_linear2(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream))
-        if rc == 0:
+        if _lib.try_launch("flexnet_linear2", a):
             return out
         if rv is not None:
-            raise RuntimeError(f"flexnet_linear2 declined an in-place window of the stacked-observation ring (code {rc})")
-        if rc != _lib.FLEXNET_EUNSUPPORTED:
-            _lib.check(rc, "flexnet_linear2")
+            raise RuntimeError("flexnet_linear2 declined an in-place window of the stacked-observation ring (FLEXNET_EUNSUPPORTED)")
         note_fallback("critic_fc1", "FLEXNET_EUNSUPPORTED from flexnet_linear2")
     if rv is not None:
         raise RuntimeError("critic_first_layer: an in-place window of the stacked-observation ring needs the fused kernel")
@@ -462,6 +446,13 @@ def critic_first_layer(bias, obs2d, act2d, W, c_act):
 
 
 _TD_WS = {}
+
+
+def _td_workspace(device):
+    """Per-device fp64 scratch of csrc/tdloss.hip (statistics partials)."""
+    if device not in _TD_WS:
+        _TD_WS[device] = th.empty(_lib.FLEXNET_TD_WS_FLOATS // 2, dtype=th.float64, device=device)
+    return _TD_WS[device]
 
 
 # Cross-rank reward statistics (SURVEY.md 8e: "or all-reduce 2 x 5 moments"; off unless the trainer switches it on):
@@ -497,15 +488,12 @@ TD_OFFERS = {}              # data_ptr of a static [rows, n] reward tensor -> {"
 def offer_td_stats(reward):
     """Offer to file the reward statistics of ``reward`` (a static batch tensor) with every refresh of it.  Returns
     (record, FlexTdLossArgs for the rider); record["taken"] says after a loss has run whether the fused value loss used them."""
-    from . import _lib
     import weakref
     r2 = reward.reshape(reward.shape[0], -1)
     rec = {"taken": False, "ref": weakref.ref(reward)}        # (a dead tensor's address may be handed out again: checked on use)
     TD_OFFERS[r2.data_ptr()] = rec
     rows, n = r2.shape
-    if r2.device not in _TD_WS:
-        _TD_WS[r2.device] = th.empty(_lib.FLEXNET_TD_WS_FLOATS // 2, dtype=th.float64, device=r2.device)
-    ws = _TD_WS[r2.device]
+    ws = _td_workspace(r2.device)
     a = _lib.FlexTdLossArgs()
     a.rows, a.n_agents, a.normalise, a.reward = rows, n, 1, r2.data_ptr()
     a.workspace, a.workspace_floats = ws.data_ptr(), 2 * ws.numel()
@@ -522,10 +510,8 @@ def _td_sync_stats(a, ws, bn):
     tensor of ``a``."""
     if not (a.normalise and _sync_active(bn)):
         return
-    import ctypes as C
     import torch.distributed as dist
-    from . import _lib
-    _lib.check(_lib.load().flexnet_td_stats(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream)), "flexnet_td_stats")
+    _lib.launch("flexnet_td_stats", a)
     dist.all_reduce(ws[:_lib.FLEXNET_TD_STAT_DOUBLES], op=dist.ReduceOp.SUM)
     a.stats_ready, a.stat_rows = 1, int(a.rows) * dist.get_world_size()
 
@@ -564,17 +550,12 @@ class _TdLossFn(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, next_q, reward, done, gamma, bn, update_stats=True):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
         rows, n = reward.shape
         q2, nq, r, d = q.reshape(rows, n).contiguous(), next_q.reshape(rows, n).contiguous(), reward.contiguous(), \
             done.reshape(rows).contiguous()
         dq = th.empty_like(q2)
         loss = th.empty((), dtype=th.float32, device=q.device)
-        if q.device not in _TD_WS:
-            _TD_WS[q.device] = th.empty(_lib.FLEXNET_TD_WS_FLOATS // 2, dtype=th.float64, device=q.device)
-        ws = _TD_WS[q.device]
+        ws = _td_workspace(q.device)
         a = _lib.FlexTdLossArgs()
         a.rows, a.n_agents, a.normalise, a.gamma = rows, n, int(bn is not None), float(gamma)
         a.reward, a.done, a.next_q, a.q = r.data_ptr(), d.data_ptr(), nq.data_ptr(), q2.data_ptr()
@@ -588,7 +569,7 @@ class _TdLossFn(th.autograd.Function):
         a.dq, a.loss = dq.data_ptr(), loss.data_ptr()
         a.workspace, a.workspace_floats = ws.data_ptr(), 2 * ws.numel()
         _td_sync_stats(a, ws, bn)
-        _lib.check(lib.flexnet_td_loss(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream)), "flexnet_td_loss")
+        _lib.launch("flexnet_td_loss", a)
         ctx.save_for_backward(dq)
         ctx.q_shape = q.shape
         return loss
@@ -619,14 +600,9 @@ def batchnorm_update_running_stats(bn, x):
     """What a training-mode ``bn(x)`` does to ``running_mean`` / ``running_var`` / ``num_batches_tracked``, without the
     normalised output (csrc/tdloss.hip statistics pass): for get_loss calls that normalise the reward only for the
     module's bookkeeping (the policy loss never reads it, model.py:308-323)."""
-    import ctypes as C
-    from . import _lib
-    lib = _lib.load()
     rows, n = x.shape
     x = x.contiguous()
-    if x.device not in _TD_WS:
-        _TD_WS[x.device] = th.empty(_lib.FLEXNET_TD_WS_FLOATS // 2, dtype=th.float64, device=x.device)
-    ws = _TD_WS[x.device]
+    ws = _td_workspace(x.device)
     a = _lib.FlexTdLossArgs()
     a.rows, a.n_agents, a.normalise = rows, n, 1
     a.bn_eps, a.bn_momentum = float(bn.eps), float(bn.momentum)
@@ -635,7 +611,7 @@ def batchnorm_update_running_stats(bn, x):
     a.num_batches_tracked = bn.num_batches_tracked.data_ptr()
     a.workspace, a.workspace_floats = ws.data_ptr(), 2 * ws.numel()
     _td_sync_stats(a, ws, bn)
-    _lib.check(lib.flexnet_td_loss(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream)), "flexnet_td_loss")
+    _lib.launch("flexnet_td_loss", a)
 
 
 def batchnorm_stats_supported(bn, x):
@@ -654,7 +630,6 @@ _LNRELU_WS = {}
 
 
 def _lnrelu_args(z, bias, id_cols, ln_w, ln_b, eps, n_agents):
-    from . import _lib
     a = _lib.FlexLnReluArgs()
     a.rows, a.n_agents, a.layernorm, a.ln_eps = z.shape[0], n_agents, int(ln_w is not None), float(eps)
     a.z = z.data_ptr()
@@ -671,25 +646,18 @@ class _LnReluFn(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, bias, id_cols, ln_w, ln_b, eps, n_agents):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
         z = z.contiguous()
         id_cols = None if id_cols is None else id_cols.contiguous()
         out = th.empty_like(z)
         a = _lnrelu_args(z, bias, id_cols, ln_w, ln_b, eps, n_agents)
         a.out = out.data_ptr()
-        _lib.check(lib.flexnet_lnrelu_forward(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                   "flexnet_lnrelu_forward")
+        _lib.launch("flexnet_lnrelu_forward", a)
         ctx.eps, ctx.n_agents = eps, n_agents
         ctx.save_for_backward(z, bias, id_cols, ln_w, ln_b)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
         z, bias, id_cols, ln_w, ln_b = ctx.saved_tensors
         dout = dout.contiguous()
         dz = th.empty_like(z)
@@ -706,8 +674,7 @@ class _LnReluFn(th.autograd.Function):
             _LNRELU_WS[z.device] = th.empty(_lib.FLEXNET_LNRELU_WS_FLOATS, dtype=th.float32, device=z.device)
         ws = _LNRELU_WS[z.device]
         a.workspace, a.workspace_floats = ws.data_ptr(), ws.numel()
-        _lib.check(lib.flexnet_lnrelu_backward(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                   "flexnet_lnrelu_backward")
+        _lib.launch("flexnet_lnrelu_backward", a)
         return (dz, None if bias is None else small[2], None if id_cols is None else small[3:],
                 None if ln_w is None else small[0], None if ln_w is None else small[1], None, None)
 
@@ -728,9 +695,6 @@ class _ActorTrainFn(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, obs, hidden, n_agents, agent_id, fc1_w, fc1_b, ln_w, ln_b, ln_eps, w_ih, w_hh, b_ih, b_hh, fc2_w, fc2_b):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
         rows, o = obs.shape
         act_dim = fc2_w.shape[0]
         obs, hidden = obs.contiguous(), hidden.contiguous()
@@ -748,8 +712,7 @@ class _ActorTrainFn(th.autograd.Function):
                 if not t.is_contiguous():
                     raise ValueError(f"actor training forward: {name} must be contiguous")
                 setattr(a, name, t.data_ptr())
-        _lib.check(lib.flexnet_actor_forward(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                   "flexnet_actor_forward")
+        _lib.launch("flexnet_actor_forward", a)
         ctx.n_agents, ctx.agent_id, ctx.ln_eps = n_agents, bool(agent_id), float(ln_eps)
         ctx.save_for_backward(obs, hidden, hid_out, saved, fc1_w, fc1_b, ln_w, ln_b, w_ih, fc2_w)
         ctx.mark_non_differentiable(hid_out)          # the new hidden state is returned for the caller's bookkeeping only
@@ -758,13 +721,9 @@ class _ActorTrainFn(th.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_means, _d_hid):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
         obs, hidden, hid_out, saved, fc1_w, fc1_b, ln_w, ln_b, w_ih, fc2_w = ctx.saved_tensors
         rows, o = obs.shape
         n, dev = ctx.n_agents, obs.device
-        stream = C.c_void_p(th.cuda.current_stream().cuda_stream)
         d_means = d_means.contiguous()
         d_gi = th.empty(rows, 192, dtype=th.float32, device=dev)
         d_gh = th.empty(rows, 192, dtype=th.float32, device=dev)
@@ -795,7 +754,7 @@ class _ActorTrainFn(th.autograd.Function):
                 g.d_id = d_fc1_w.data_ptr() + 4 * o
                 g.d_id_agent_stride, g.d_id_unit_stride = 1, fc1_w.shape[1]
             g.workspace, g.workspace_floats = ws.data_ptr(), ws.numel()
-        _lib.check(lib.flexnet_gru_backward(C.byref(g), stream), "flexnet_gru_backward")
+        _lib.launch("flexnet_gru_backward", g)
         # fc2: weight and bias gradients from one pass over d_means
         d_fc2_b = th.empty(fc2_w.shape[0], dtype=th.float32, device=dev)
         d_fc2_w = tall_wgrad(d_means, hid_out, colsum=d_fc2_b)
@@ -827,7 +786,7 @@ class _ActorTrainFn(th.autograd.Function):
             _LNRELU_WS[dev] = th.empty(_lib.FLEXNET_LNRELU_WS_FLOATS, dtype=th.float32, device=dev)
         ws = _LNRELU_WS[dev]
         la.workspace, la.workspace_floats = ws.data_ptr(), ws.numel()
-        _lib.check(lib.flexnet_lnrelu_backward(C.byref(la), stream), "flexnet_lnrelu_backward")
+        _lib.launch("flexnet_lnrelu_backward", la)
         if _DEBUG_KEEP is not None:
             _DEBUG_KEEP["dz"] = dz
         d_fc1_w = th.empty_like(fc1_w)
@@ -892,10 +851,17 @@ def wide_batch_linear(x, w):
     return _WideBatchLinear.apply(x, w)
 
 
+def _critic_config_ok(critic):
+    """The MLPCritic configuration csrc/critic.hip (and the tail inside csrc/sqddpg.hip) implements: 64 hidden units, ReLU,
+    one output."""
+    a = critic.args
+    return a.hid_size == 64 and a.hid_activation == "relu" and critic.fc3.out_features == 1
+
+
 def critic_tail_supported(critic, x):
     a = critic.args
-    ok = (x.is_cuda and x.dtype == th.float32 and x.dim() == 2 and x.shape[1] == 64 and a.hid_size == 64
-          and a.hid_activation == "relu" and critic.fc3.out_features == 1 and getattr(critic, "fused_tail", True))
+    ok = (x.is_cuda and x.dtype == th.float32 and x.dim() == 2 and x.shape[1] == 64 and _critic_config_ok(critic)
+          and getattr(critic, "fused_tail", True))
     if x.is_cuda and not ok and getattr(critic, "fused_tail", True):
         note_fallback("critic_tail", f"hid {a.hid_size}, act {a.hid_activation}, out {critic.fc3.out_features}, dtype {x.dtype}")
     return ok
@@ -906,8 +872,14 @@ CRITIC_PGRAD32 = 0              # matrix-core backward WITH parameter gradients:
 #                                 1 = the 32-row kernel it replaced (tests and tools/critic_bench.py compare the two)
 
 
+def _tail_params(critic):
+    """(ln_w, ln_b, w2, b2, w3, b3, eps) of an MLPCritic: the tail's arguments, in the order every critic node takes them."""
+    ln = critic.layernorm if critic.args.layernorm else None
+    return (None if ln is None else ln.weight, None if ln is None else ln.bias, critic.fc2.weight, critic.fc2.bias,
+            critic.fc3.weight, critic.fc3.bias, 1e-5 if ln is None else ln.eps)
+
+
 def _critic_args(z1, ln_w, ln_b, w2, b2, w3, b3, eps):
-    from . import _lib
     a = _lib.FlexCriticTailArgs()
     a.rows, a.layernorm, a.ln_eps, a.variant = z1.shape[0], int(ln_w is not None), float(eps), CRITIC_VARIANT
     a.variant_pgrad32 = CRITIC_PGRAD32
@@ -918,25 +890,100 @@ def _critic_args(z1, ln_w, ln_b, w2, b2, w3, b3, eps):
     return a
 
 
-_CRITIC_WS = {}
-
-
-def _set_critic_ids(args, W, col0, n, dense=None):
-    """The composed input's id-column table: ``dense`` [n, 64] if given, else columns col0 .. col0 + n - 1 of fc1.weight
-    read where they are (the kernels stage the table in LDS through the two strides: no transposed copy per call)."""
-    if dense is not None:
-        args.z_id = dense.data_ptr()
+def _composed_args(shared, n, W, no, tail, dense_ids=None):
+    """``_critic_args`` for the composed input z1[b, i] = shared[b] + id column i (``tail``: _tail_params' tuple).  The
+    id-column table is ``dense_ids`` [n, 64] if given, else columns no .. no + n - 1 of fc1.weight ``W`` read where they are
+    (the kernels stage the table in LDS through the two strides: no transposed copy per call)."""
+    args = _critic_args(shared, *tail)
+    args.rows, args.z1, args.z_shared, args.n_agents = shared.shape[0] * n, None, shared.data_ptr(), n
+    if dense_ids is not None:
+        args.z_id = dense_ids.data_ptr()
     else:
-        args.z_id = W[:, col0:col0 + n].data_ptr()
+        args.z_id = W[:, no:no + n].data_ptr()
         args.z_id_agent_stride, args.z_id_unit_stride = 1, W.stride(0)
+    return args
+
+
+_CRITIC_WS = {}
 
 
 def _critic_workspace(device):
     """Per-device scratch for the backward kernel's per-block partial sums (18 MB, allocated once)."""
-    from . import _lib
     if device not in _CRITIC_WS:
         _CRITIC_WS[device] = th.empty(_lib.FLEXNET_CRITIC_WS_FLOATS, dtype=th.float32, device=device)
     return _CRITIC_WS[device]
+
+
+def _bind_workspace(args, device, overwrite=False):
+    """With the workspace the backward kernel reduces the parameter gradients in a fixed-order second stage; ``overwrite``:
+    that stage STORES them (no zero fill of the slab needed) instead of adding to what is there."""
+    ws = _critic_workspace(device)
+    args.workspace, args.workspace_floats, args.overwrite_grads = ws.data_ptr(), ws.numel(), int(overwrite)
+
+
+# The tail's six parameter gradients are written into ONE slab (one allocation, one zero fill where they are accumulated):
+# FlexCriticTailArgs field -> (first float, shape), in the order fc2.weight, fc2.bias, fc3.weight, LayerNorm weight and
+# bias, fc3.bias
+_TAIL_GRADS = {}
+_TAIL_FLOATS = 0
+for _name, _shape in (("d_fc2_w", (64, 64)), ("d_fc2_b", (64,)), ("d_fc3_w", (1, 64)), ("d_ln_w", (64,)), ("d_ln_b", (64,)),
+                      ("d_fc3_b", (1,))):
+    _TAIL_GRADS[_name] = (_TAIL_FLOATS, _shape)
+    _TAIL_FLOATS += math.prod(_shape)
+
+
+def _new_tail_grads(device, zero=False, heads=None):
+    """An empty slab ([heads, floats] with ``heads``); ``zero``: zero-filled, for the kernels that accumulate into it."""
+    shape = (_TAIL_FLOATS,) if heads is None else (heads, _TAIL_FLOATS)
+    return (th.zeros if zero else th.empty)(shape, dtype=th.float32, device=device)
+
+
+def _bind_tail_grads(args, slab):
+    """Point the d_* fields of ``args`` into ``slab`` (one head's); the LayerNorm pair only where there is a LayerNorm."""
+    base = slab.data_ptr()
+    for name, (first, _) in _TAIL_GRADS.items():
+        if args.layernorm or name not in ("d_ln_w", "d_ln_b"):
+            setattr(args, name, base + 4 * first)
+
+
+def _split_tail_grads(slab, has_ln):
+    """The six gradients of a slab in autograd-return order (ln_w, ln_b, w2, b2, w3, b3), None for an absent LayerNorm."""
+    def part(name):
+        first, shape = _TAIL_GRADS[name]
+        g = slab[first:first + math.prod(shape)]
+        return g.view(shape) if len(shape) > 1 else g
+    return ((part("d_ln_w") if has_ln else None), (part("d_ln_b") if has_ln else None), part("d_fc2_w"), part("d_fc2_b"),
+            part("d_fc3_w"), part("d_fc3_b"))
+
+
+def _sum_rows(x):
+    """x[0] + ... + x[n - 1] with n - 1 pointwise adds: no ATen reduction in a captured graph."""
+    tot = x[0]
+    for i in range(1, x.shape[0]):
+        tot = tot + x[i]
+    return tot
+
+
+def _fc1_grad(dW, d_shared, obs2d, act2d, n, d_id=None, flag_rows=None, critic_finish=None):
+    """Fill fc1's weight gradient ``dW`` [64, obs | n id columns | act | trailing columns] from ``d_shared`` [b, 64] and
+    return its bias gradient (the column sum from the same pass).  ``d_id`` [n, 64]: the id-column sums, transposed into the
+    id block (None: the tail's backward wrote them there through its strides).  Trailing columns see no input: zero —
+    except, with ``flag_rows`` [n, 64] (both heads of the twin critic), the last one: the flag column sees every agent's row
+    of the second head, the sum of its id-column gradients.  ``critic_finish``: tall_wgrad's rider."""
+    no, na_ = obs2d.shape[1], act2d.shape[1]
+    end = no + n + na_
+    d_bias = th.empty(64, dtype=th.float32, device=dW.device)
+    # the observation block and the action block of dW from one launch (the action block rides in the last column chunk)
+    tall_wgrad(d_shared, obs2d, out=dW[:, :no], colsum=d_bias, x2=act2d, out2=dW[:, no + n:end], critic_finish=critic_finish)
+    if d_id is not None:
+        dW[:, no:no + n] = d_id.t()
+    if flag_rows is not None:
+        dW[:, -1] = _sum_rows(flag_rows)
+        if dW.shape[1] > end + 1:
+            dW[:, end:-1] = 0.0
+    elif dW.shape[1] > end:
+        dW[:, end:] = 0.0
+    return d_bias
 
 
 class _CriticTailFn(th.autograd.Function):
@@ -944,47 +991,32 @@ class _CriticTailFn(th.autograd.Function):
     for the six parameter tensors of the tail."""
 
     @staticmethod
-    def forward(ctx, z1, ln_w, ln_b, w2, b2, w3, b3, eps):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
+    def forward(ctx, z1, *tail):
         z1 = z1.contiguous()
         q = th.empty(z1.shape[0], 1, dtype=th.float32, device=z1.device)
-        args = _critic_args(z1, ln_w, ln_b, w2, b2, w3, b3, eps)
+        args = _critic_args(z1, *tail)
         args.q = q.data_ptr()
-        _lib.check(lib.flexnet_critic_tail_forward(C.byref(args), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                   "flexnet_critic_tail_forward")
-        ctx.eps = eps
-        ctx.save_for_backward(z1, ln_w, ln_b, w2, b2, w3, b3)
+        _lib.launch("flexnet_critic_tail_forward", args)
+        ctx.eps = tail[6]
+        ctx.save_for_backward(z1, *tail[:6])
         return q
 
     @staticmethod
     def backward(ctx, dq):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
-        z1, ln_w, ln_b, w2, b2, w3, b3 = ctx.saved_tensors
+        z1, *tail = ctx.saved_tensors
         dq = dq.contiguous()
         dz1 = th.empty_like(z1)
-        args = _critic_args(z1, ln_w, ln_b, w2, b2, w3, b3, ctx.eps)
+        args = _critic_args(z1, *tail, ctx.eps)
         args.dq, args.dz1 = dq.data_ptr(), dz1.data_ptr()
         if not any(ctx.needs_input_grad[1:7]):
             # the policy loss differentiates through a critic whose parameters take no step: dz1 only
-            _lib.check(lib.flexnet_critic_tail_backward(C.byref(args), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                       "flexnet_critic_tail_backward")
+            _lib.launch("flexnet_critic_tail_backward", args)
             return (dz1,) + (None,) * 7
-        grads = th.zeros(64 * 64 + 64 * 4 + 1, dtype=th.float32, device=z1.device)      # one zero-fill for all six
-        d_w2, d_b2, d_w3 = grads[:4096].view(64, 64), grads[4096:4160], grads[4160:4224].view(1, 64)
-        d_g, d_b, d_b3 = grads[4224:4288], grads[4288:4352], grads[4352:4353]
-        args.d_fc2_w, args.d_fc2_b, args.d_fc3_w, args.d_fc3_b = d_w2.data_ptr(), d_b2.data_ptr(), d_w3.data_ptr(), d_b3.data_ptr()
-        if ln_w is not None:
-            args.d_ln_w, args.d_ln_b = d_g.data_ptr(), d_b.data_ptr()
-        ws = _critic_workspace(z1.device)
-        args.workspace, args.workspace_floats = ws.data_ptr(), ws.numel()
-        _lib.check(lib.flexnet_critic_tail_backward(C.byref(args), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                   "flexnet_critic_tail_backward")
-        has_ln = ln_w is not None
-        return dz1, (d_g if has_ln else None), (d_b if has_ln else None), d_w2, d_b2, d_w3, d_b3, None
+        grads = _new_tail_grads(z1.device, zero=True)      # one zero-fill for all six
+        _bind_tail_grads(args, grads)
+        _bind_workspace(args, z1.device)
+        _lib.launch("flexnet_critic_tail_backward", args)
+        return (dz1, *_split_tail_grads(grads, tail[0] is not None), None)
 
 
 class _CriticTailComposedFn(th.autograd.Function):
@@ -992,54 +1024,37 @@ class _CriticTailComposedFn(th.autograd.Function):
     gradient is needed, maddpg.py:38-54) without materialising the [b * n, 64] tensor on the way in."""
 
     @staticmethod
-    def forward(ctx, shared, id_cols, ln_w, ln_b, w2, b2, w3, b3, eps):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
+    def forward(ctx, shared, id_cols, *tail):
         shared = shared.contiguous()
         n = id_cols.shape[0]
-        rows = shared.shape[0] * n
-        q = th.empty(rows, 1, dtype=th.float32, device=shared.device)
-        args = _critic_args(shared, ln_w, ln_b, w2, b2, w3, b3, eps)
-        args.rows, args.z1, args.z_shared, args.z_id, args.n_agents = rows, None, shared.data_ptr(), id_cols.data_ptr(), n
+        q = th.empty(shared.shape[0] * n, 1, dtype=th.float32, device=shared.device)
+        args = _composed_args(shared, n, None, 0, tail, dense_ids=id_cols)
         if not id_cols.is_contiguous():          # fc1.weight's id columns, transposed view: read in place through strides
             args.z_id_agent_stride, args.z_id_unit_stride = id_cols.stride(0), id_cols.stride(1)
         args.q = q.data_ptr()
-        _lib.check(lib.flexnet_critic_tail_forward(C.byref(args), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                   "flexnet_critic_tail_forward")
-        ctx.eps = eps
-        ctx.save_for_backward(shared, id_cols, ln_w, ln_b, w2, b2, w3, b3)
+        _lib.launch("flexnet_critic_tail_forward", args)
+        ctx.eps = tail[6]
+        ctx.save_for_backward(shared, id_cols, *tail[:6])
         return q
 
     @staticmethod
     def backward(ctx, dq):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
-        shared, id_cols, ln_w, ln_b, w2, b2, w3, b3 = ctx.saved_tensors
+        shared, id_cols, *tail = ctx.saved_tensors
         id_cols = id_cols.contiguous()
         n = id_cols.shape[0]
-        rows = shared.shape[0] * n
+        dev = shared.device
         dq = dq.contiguous()
-        dz1 = th.empty(rows, 64, dtype=th.float32, device=shared.device)
-        grads = th.zeros(64 * 64 + 64 * 4 + 1, dtype=th.float32, device=shared.device)
-        d_w2, d_b2, d_w3 = grads[:4096].view(64, 64), grads[4096:4160], grads[4160:4224].view(1, 64)
-        d_g, d_b, d_b3 = grads[4224:4288], grads[4288:4352], grads[4352:4353]
-        args = _critic_args(shared, ln_w, ln_b, w2, b2, w3, b3, ctx.eps)
-        args.rows, args.z1, args.z_shared, args.z_id, args.n_agents = rows, None, shared.data_ptr(), id_cols.data_ptr(), n
+        dz1 = th.empty(shared.shape[0] * n, 64, dtype=th.float32, device=dev)
+        grads = _new_tail_grads(dev, zero=True)
+        args = _composed_args(shared, n, None, 0, (*tail, ctx.eps), dense_ids=id_cols)
         args.dq, args.dz1 = dq.data_ptr(), dz1.data_ptr()
-        args.d_fc2_w, args.d_fc2_b, args.d_fc3_w, args.d_fc3_b = d_w2.data_ptr(), d_b2.data_ptr(), d_w3.data_ptr(), d_b3.data_ptr()
-        if ln_w is not None:
-            args.d_ln_w, args.d_ln_b = d_g.data_ptr(), d_b.data_ptr()
-        ws = _critic_workspace(shared.device)
-        args.workspace, args.workspace_floats = ws.data_ptr(), ws.numel()
+        _bind_tail_grads(args, grads)
+        _bind_workspace(args, dev)
         d_shared = th.empty_like(shared)
-        d_id = th.empty(n, 64, dtype=th.float32, device=shared.device)
+        d_id = th.empty(n, 64, dtype=th.float32, device=dev)
         args.d_z_shared, args.d_z_id = d_shared.data_ptr(), d_id.data_ptr()
-        _lib.check(lib.flexnet_critic_tail_backward(C.byref(args), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                   "flexnet_critic_tail_backward")
-        has_ln = ln_w is not None
-        return (d_shared, d_id, (d_g if has_ln else None), (d_b if has_ln else None), d_w2, d_b2, d_w3, d_b3, None)
+        _lib.launch("flexnet_critic_tail_backward", args)
+        return (d_shared, d_id, *_split_tail_grads(grads, tail[0] is not None), None)
 
 
 class _CriticReplayedFn(th.autograd.Function):
@@ -1052,76 +1067,47 @@ class _CriticReplayedFn(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, obs2d, act2d, n_agents, W, bias, ln_w, ln_b, w2, b2, w3, b3, eps, twin=False):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
-        no, na_ = obs2d.shape[1], act2d.shape[1]
+        no = obs2d.shape[1]
         shared = critic_first_layer(bias, obs2d, act2d, W, no + n_agents)
         # twin (matd3.py:64-67): the second head is the same network with the trailing 0/1 input flag set — fc1's last
         # column joins every agent's id column
         id_cols = (W[:, no:no + n_agents] + W[:, -1:]).t().contiguous() if twin else None
         ctx.twin = bool(twin)
-        rows = shared.shape[0] * n_agents
-        q = th.empty(rows, 1, dtype=th.float32, device=shared.device)
-        args = _critic_args(shared, ln_w, ln_b, w2, b2, w3, b3, eps)
-        args.rows, args.z1, args.z_shared, args.n_agents = rows, None, shared.data_ptr(), n_agents
-        _set_critic_ids(args, W, no, n_agents, dense=id_cols)
+        q = th.empty(shared.shape[0] * n_agents, 1, dtype=th.float32, device=shared.device)
+        args = _composed_args(shared, n_agents, W, no, (ln_w, ln_b, w2, b2, w3, b3, eps), dense_ids=id_cols)
         args.q = q.data_ptr()
-        _lib.check(lib.flexnet_critic_tail_forward(C.byref(args), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                   "flexnet_critic_tail_forward")
+        _lib.launch("flexnet_critic_tail_forward", args)
         ctx.eps, ctx.n_agents = eps, n_agents
         ctx.save_for_backward(obs2d, act2d, shared, id_cols, W, ln_w, ln_b, w2, b2, w3, b3)
         return q
 
     @staticmethod
     def backward(ctx, dq):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
-        obs2d, act2d, shared, id_cols, W, ln_w, ln_b, w2, b2, w3, b3 = ctx.saved_tensors      # (id_cols: twin only)
+        obs2d, act2d, shared, id_cols, W, *tail = ctx.saved_tensors      # (id_cols: twin only)
         n = ctx.n_agents
-        no, na_ = obs2d.shape[1], act2d.shape[1]
-        rows = shared.shape[0] * n
+        no = obs2d.shape[1]
+        dev = shared.device
         dq = dq.contiguous()
-        dz1 = th.empty(rows, 64, dtype=th.float32, device=shared.device)
+        dz1 = th.empty(shared.shape[0] * n, 64, dtype=th.float32, device=dev)
         # the six tail gradients are STORED by the fixed-order second stage (overwrite_grads): no zero fill
-        grads = th.empty(64 * 64 + 64 * 4 + 1, dtype=th.float32, device=shared.device)
-        d_w2, d_b2, d_w3 = grads[:4096].view(64, 64), grads[4096:4160], grads[4160:4224].view(1, 64)
-        d_g, d_b, d_b3 = grads[4224:4288], grads[4288:4352], grads[4352:4353]
-        args = _critic_args(shared, ln_w, ln_b, w2, b2, w3, b3, ctx.eps)
-        args.rows, args.z1, args.z_shared, args.n_agents = rows, None, shared.data_ptr(), n
-        _set_critic_ids(args, W, no, n, dense=id_cols)
+        grads = _new_tail_grads(dev)
+        args = _composed_args(shared, n, W, no, (*tail, ctx.eps), dense_ids=id_cols)
         args.dq, args.dz1 = dq.data_ptr(), dz1.data_ptr()
-        args.d_fc2_w, args.d_fc2_b, args.d_fc3_w, args.d_fc3_b = d_w2.data_ptr(), d_b2.data_ptr(), d_w3.data_ptr(), d_b3.data_ptr()
-        if ln_w is not None:
-            args.d_ln_w, args.d_ln_b = d_g.data_ptr(), d_b.data_ptr()
-        ws = _critic_workspace(shared.device)
-        args.workspace, args.workspace_floats, args.overwrite_grads = ws.data_ptr(), ws.numel(), 1
+        _bind_tail_grads(args, grads)
+        _bind_workspace(args, dev, overwrite=True)
         d_shared = th.empty_like(shared)                    # dz1 folded onto its two sources by the same call
         dW = th.empty_like(W)
         if ctx.twin:
-            d_id = th.empty(n, 64, dtype=th.float32, device=shared.device)
+            d_id = th.empty(n, 64, dtype=th.float32, device=dev)
         else:                                               # ... the id-column sums straight into dW[:, no:no + n]
             d_id = dW[:, no:no + n]
             args.d_z_id_agent_stride, args.d_z_id_unit_stride = 1, W.shape[1]
         args.d_z_shared, args.d_z_id = d_shared.data_ptr(), d_id.data_ptr()
-        _lib.check(lib.flexnet_critic_tail_backward(C.byref(args), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                   "flexnet_critic_tail_backward")
-        d_bias = th.empty(64, dtype=th.float32, device=W.device)
-        # fc1: the observation block and the action block of dW from one launch (the action block rides in the last column chunk)
-        tall_wgrad(d_shared, obs2d, out=dW[:, :no], colsum=d_bias, x2=act2d, out2=dW[:, no + n:no + n + na_])
-        if ctx.twin:
-            dW[:, no:no + n] = d_id.t()
-        if W.shape[1] > no + n + na_:
-            dW[:, no + n + na_:] = 0.0
-            if ctx.twin:                 # the flag column sees every agent's row: the sum of the id-column gradients
-                tot = d_id[0]
-                for i in range(1, n):
-                    tot = tot + d_id[i]      # (n - 1 pointwise adds: no ATen reduction in a captured graph)
-                dW[:, -1] = tot
-        has_ln = ln_w is not None
-        return (None, None, None, dW, d_bias, (d_g if has_ln else None), (d_b if has_ln else None), d_w2, d_b2, d_w3, d_b3,
-                None, None)
+        _lib.launch("flexnet_critic_tail_backward", args)
+        d_bias = _fc1_grad(dW, d_shared, obs2d, act2d, n, d_id=d_id if ctx.twin else None)
+        if ctx.twin and W.shape[1] > no + n + act2d.shape[1]:
+            dW[:, -1] = _sum_rows(d_id)      # the flag column sees every agent's row: the sum of the id-column gradients
+        return (None, None, None, dW, d_bias, *_split_tail_grads(grads, tail[0] is not None), None, None)
 
 
 class _CriticReplayedTwinFn(th.autograd.Function):
@@ -1131,74 +1117,46 @@ class _CriticReplayedTwinFn(th.autograd.Function):
     gradient is taken ONCE on the sum of the two heads' input gradients.  Returns cat([Q1, Q2]) as [2 rows, 1]."""
 
     @staticmethod
-    def forward(ctx, obs2d, act2d, n_agents, W, bias, ln_w, ln_b, w2, b2, w3, b3, eps):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
-        stream = C.c_void_p(th.cuda.current_stream().cuda_stream)
+    def forward(ctx, obs2d, act2d, n_agents, W, bias, *tail):
         n = n_agents
-        no, na_ = obs2d.shape[1], act2d.shape[1]
+        no = obs2d.shape[1]
         shared = critic_first_layer(bias, obs2d, act2d, W, no + n)
         id2 = (W[:, no:no + n] + W[:, -1:]).t().contiguous()
         rows = shared.shape[0] * n
         q = th.empty(2 * rows, 1, dtype=th.float32, device=shared.device)
         for h in range(2):
-            args = _critic_args(shared, ln_w, ln_b, w2, b2, w3, b3, eps)
-            args.rows, args.z1, args.z_shared, args.n_agents = rows, None, shared.data_ptr(), n
-            _set_critic_ids(args, W, no, n, dense=id2 if h else None)
+            args = _composed_args(shared, n, W, no, tail, dense_ids=id2 if h else None)
             args.q = q[h * rows:].data_ptr()
-            _lib.check(lib.flexnet_critic_tail_forward(C.byref(args), stream), "flexnet_critic_tail_forward")
-        ctx.eps, ctx.n_agents = eps, n
-        ctx.save_for_backward(obs2d, act2d, shared, id2, W, ln_w, ln_b, w2, b2, w3, b3)
+            _lib.launch("flexnet_critic_tail_forward", args)
+        ctx.eps, ctx.n_agents = tail[6], n
+        ctx.save_for_backward(obs2d, act2d, shared, id2, W, *tail[:6])
         return q
 
     @staticmethod
     def backward(ctx, dq):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
-        stream = C.c_void_p(th.cuda.current_stream().cuda_stream)
-        obs2d, act2d, shared, id2, W, ln_w, ln_b, w2, b2, w3, b3 = ctx.saved_tensors
+        obs2d, act2d, shared, id2, W, *tail = ctx.saved_tensors
         n = ctx.n_agents
-        no, na_ = obs2d.shape[1], act2d.shape[1]
+        no = obs2d.shape[1]
         rows = shared.shape[0] * n
         dev = shared.device
         dq = dq.contiguous()
         dz1 = th.empty(rows, 64, dtype=th.float32, device=dev)                 # (per head, consumed inside its call)
-        grads = th.empty(2, 64 * 64 + 64 * 4 + 1, dtype=th.float32, device=dev)
+        grads = _new_tail_grads(dev, heads=2)
         d_shared = th.empty((2,) + tuple(shared.shape), dtype=th.float32, device=dev)
         d_id = th.empty(2, n, 64, dtype=th.float32, device=dev)
-        ws = _critic_workspace(dev)
         for h in range(2):
-            g = grads[h]
-            args = _critic_args(shared, ln_w, ln_b, w2, b2, w3, b3, ctx.eps)
-            args.rows, args.z1, args.z_shared, args.n_agents = rows, None, shared.data_ptr(), n
-            _set_critic_ids(args, W, no, n, dense=id2 if h else None)
+            args = _composed_args(shared, n, W, no, (*tail, ctx.eps), dense_ids=id2 if h else None)
             args.dq, args.dz1 = dq[h * rows:].data_ptr(), dz1.data_ptr()
-            args.d_fc2_w, args.d_fc2_b, args.d_fc3_w = g.data_ptr(), g[4096:].data_ptr(), g[4160:].data_ptr()
-            args.d_fc3_b = g[4352:].data_ptr()
-            if ln_w is not None:
-                args.d_ln_w, args.d_ln_b = g[4224:].data_ptr(), g[4288:].data_ptr()
-            args.workspace, args.workspace_floats, args.overwrite_grads = ws.data_ptr(), ws.numel(), 1
+            _bind_tail_grads(args, grads[h])
+            _bind_workspace(args, dev, overwrite=True)
             args.d_z_shared, args.d_z_id = d_shared[h].data_ptr(), d_id[h].data_ptr()
-            _lib.check(lib.flexnet_critic_tail_backward(C.byref(args), stream), "flexnet_critic_tail_backward")
+            _lib.launch("flexnet_critic_tail_backward", args)
         gsum = grads[0] + grads[1]
         dsum = d_shared[0] + d_shared[1]
         isum = d_id[0] + d_id[1]
         dW = th.empty_like(W)
-        d_bias = th.empty(64, dtype=th.float32, device=dev)
-        tall_wgrad(dsum, obs2d, out=dW[:, :no], colsum=d_bias, x2=act2d, out2=dW[:, no + n:no + n + na_])
-        dW[:, no:no + n] = isum.t()
-        tot = d_id[1, 0]                       # the flag column sees every agent's row of the second head
-        for i in range(1, n):
-            tot = tot + d_id[1, i]             # (n - 1 pointwise adds: no ATen reduction in a captured graph)
-        dW[:, -1] = tot
-        if W.shape[1] > no + n + na_ + 1:
-            dW[:, no + n + na_:-1] = 0.0
-        d_w2, d_b2, d_w3 = gsum[:4096].view(64, 64), gsum[4096:4160], gsum[4160:4224].view(1, 64)
-        d_g, d_b, d_b3 = gsum[4224:4288], gsum[4288:4352], gsum[4352:4353]
-        has_ln = ln_w is not None
-        return (None, None, None, dW, d_bias, (d_g if has_ln else None), (d_b if has_ln else None), d_w2, d_b2, d_w3, d_b3, None)
+        d_bias = _fc1_grad(dW, dsum, obs2d, act2d, n, d_id=isum, flag_rows=d_id[1])
+        return (None, None, None, dW, d_bias, *_split_tail_grads(gsum, tail[0] is not None), None)
 
 
 # Measured and NOT adopted (round 5; VERDICT r04 item 1b asked for the small launches to be folded into their neighbours): the
@@ -1231,12 +1189,8 @@ class _CriticTdLossFn(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, obs2d, act2d, n_agents, W, bias, ln_w, ln_b, w2, b2, w3, b3, eps, next_q, reward, done, gamma, bn):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
-        stream = C.c_void_p(th.cuda.current_stream().cuda_stream)
         n = n_agents
-        no, na_ = obs2d.shape[1], act2d.shape[1]
+        no = obs2d.shape[1]
         dev = obs2d.device
         nq, r, d = next_q.reshape(-1, n).contiguous(), reward.contiguous(), done.reshape(-1).contiguous()
         t = _td_args(r, d, nq, gamma, bn, update_stats=True)
@@ -1253,52 +1207,38 @@ class _CriticTdLossFn(th.autograd.Function):
         if fork and t.normalise and not t.stats_ready:
             # the statistics pass beside the first-layer product (it needs the rewards only)
             side.wait_stream(main)
-            _lib.check(lib.flexnet_td_stats(C.byref(t), C.c_void_p(side.cuda_stream)), "flexnet_td_stats")
+            _lib.launch("flexnet_td_stats", t, stream=side)
             t.stats_ready = 1
         shared = critic_first_layer(bias, obs2d, act2d, W, no + n)
         if fork:
             main.wait_stream(side)
-        rows = shared.shape[0] * n
-        dz1 = th.empty(rows, 64, dtype=th.float32, device=dev)
-        grads = th.empty(64 * 64 + 64 * 4 + 1, dtype=th.float32, device=dev)
-        d_w2, d_b2, d_w3 = grads[:4096].view(64, 64), grads[4096:4160], grads[4160:4224].view(1, 64)
-        d_g, d_b, d_b3 = grads[4224:4288], grads[4288:4352], grads[4352:4353]
-        args = _critic_args(shared, ln_w, ln_b, w2, b2, w3, b3, eps)
-        args.rows, args.z1, args.z_shared, args.n_agents = rows, None, shared.data_ptr(), n
-        _set_critic_ids(args, W, no, n)
+        dz1 = th.empty(shared.shape[0] * n, 64, dtype=th.float32, device=dev)
+        grads = _new_tail_grads(dev)
+        args = _composed_args(shared, n, W, no, (ln_w, ln_b, w2, b2, w3, b3, eps))
         args.dz1 = dz1.data_ptr()
-        args.d_fc2_w, args.d_fc2_b, args.d_fc3_w, args.d_fc3_b = d_w2.data_ptr(), d_b2.data_ptr(), d_w3.data_ptr(), d_b3.data_ptr()
-        if ln_w is not None:
-            args.d_ln_w, args.d_ln_b = d_g.data_ptr(), d_b.data_ptr()
-        ws = _critic_workspace(dev)
-        args.workspace, args.workspace_floats, args.overwrite_grads = ws.data_ptr(), ws.numel(), 1
+        _bind_tail_grads(args, grads)
+        _bind_workspace(args, dev, overwrite=True)
         d_shared = th.empty_like(shared)
         dW = th.empty_like(W)
         args.d_z_shared, args.d_z_id = d_shared.data_ptr(), dW[:, no:no + n].data_ptr()
         args.d_z_id_agent_stride, args.d_z_id_unit_stride = 1, W.shape[1]
         loss = th.empty((), dtype=th.float32, device=dev)
         t.loss = loss.data_ptr()
-        d_bias = th.empty(64, dtype=th.float32, device=dev)
         sm = args.variant_pgrad32 == 0          # (the 16-row kernel writes d_z_shared itself: the finish does not feed the weight gradient)
         if fork and sm:
-            _lib.check(lib.flexnet_critic_td_backward_phases(C.byref(args), C.byref(t), 1, stream), "flexnet_critic_td_backward")
+            _lib.launch("flexnet_critic_td_backward_phases", args, t, 1)
             side.wait_stream(main)
-            _lib.check(lib.flexnet_critic_td_backward_phases(C.byref(args), C.byref(t), 2, C.c_void_p(side.cuda_stream)),
-                       "flexnet_critic_td_backward")
-            tall_wgrad(d_shared, obs2d, out=dW[:, :no], colsum=d_bias, x2=act2d, out2=dW[:, no + n:no + n + na_])
+            _lib.launch("flexnet_critic_td_backward_phases", args, t, 2, stream=side)
+            d_bias = _fc1_grad(dW, d_shared, obs2d, act2d, n)
             main.wait_stream(side)
         elif sm:
             # the finish (phase 2) depends on the backward kernel alone: it rides in the weight gradient's second-stage launch
-            _lib.check(lib.flexnet_critic_td_backward_phases(C.byref(args), C.byref(t), 1, stream), "flexnet_critic_td_backward")
-            tall_wgrad(d_shared, obs2d, out=dW[:, :no], colsum=d_bias, x2=act2d, out2=dW[:, no + n:no + n + na_],
-                       critic_finish=(args, t))
+            _lib.launch("flexnet_critic_td_backward_phases", args, t, 1)
+            d_bias = _fc1_grad(dW, d_shared, obs2d, act2d, n, critic_finish=(args, t))
         else:
-            _lib.check(lib.flexnet_critic_td_backward(C.byref(args), C.byref(t), stream), "flexnet_critic_td_backward")
-            tall_wgrad(d_shared, obs2d, out=dW[:, :no], colsum=d_bias, x2=act2d, out2=dW[:, no + n:no + n + na_])
-        if W.shape[1] > no + n + na_:
-            dW[:, no + n + na_:] = 0.0
-        has_ln = ln_w is not None
-        ctx.has_ln = has_ln
+            _lib.launch("flexnet_critic_td_backward", args, t)
+            d_bias = _fc1_grad(dW, d_shared, obs2d, act2d, n)
+        ctx.has_ln = ln_w is not None
         ctx.save_for_backward(dW, d_bias, grads)
         return loss
 
@@ -1308,19 +1248,13 @@ class _CriticTdLossFn(th.autograd.Function):
         dW, d_bias, grads = ctx.saved_tensors
         if not is_unit_seed(g):
             dW, d_bias, grads = dW * g, d_bias * g, grads * g
-        d_w2, d_b2, d_w3 = grads[:4096].view(64, 64), grads[4096:4160], grads[4160:4224].view(1, 64)
-        d_g, d_b, d_b3 = grads[4224:4288], grads[4288:4352], grads[4352:4353]
-        return (None, None, None, dW, d_bias, (d_g if ctx.has_ln else None), (d_b if ctx.has_ln else None), d_w2, d_b2, d_w3,
-                d_b3) + (None,) * 6
+        return (None, None, None, dW, d_bias, *_split_tail_grads(grads, ctx.has_ln)) + (None,) * 6
 
 
 def _td_args(reward, done, next_q, gamma, bn, update_stats=True):
     """FlexTdLossArgs for [rows, n] tensors (q / dq / loss left to the caller); the workspace is per device."""
-    from . import _lib
     rows, n = reward.shape
-    if reward.device not in _TD_WS:
-        _TD_WS[reward.device] = th.empty(_lib.FLEXNET_TD_WS_FLOATS // 2, dtype=th.float64, device=reward.device)
-    ws = _TD_WS[reward.device]
+    ws = _td_workspace(reward.device)
     a = _lib.FlexTdLossArgs()
     a.rows, a.n_agents, a.normalise, a.gamma = rows, n, int(bn is not None), float(gamma)
     a.reward, a.done, a.next_q = reward.data_ptr(), done.data_ptr(), next_q.data_ptr()
@@ -1350,11 +1284,8 @@ def critic_td_loss_supported(critic, obs2d, act2d, n_agents, next_q, reward, don
 
 
 def critic_td_loss(obs2d, act2d, n_agents, critic, next_q, reward, done, gamma, bn):
-    ln = critic.layernorm if critic.args.layernorm else None
-    return _CriticTdLossFn.apply(obs2d, act2d, n_agents, critic.fc1.weight, critic.fc1.bias,
-                                 None if ln is None else ln.weight, None if ln is None else ln.bias,
-                                 critic.fc2.weight, critic.fc2.bias, critic.fc3.weight, critic.fc3.bias,
-                                 1e-5 if ln is None else ln.eps, next_q, reward, done, gamma, bn)
+    return _CriticTdLossFn.apply(obs2d, act2d, n_agents, critic.fc1.weight, critic.fc1.bias, *_tail_params(critic),
+                                 next_q, reward, done, gamma, bn)
 
 
 class _ExpandAgentsFn(th.autograd.Function):
@@ -1380,6 +1311,22 @@ def expand_agents(x, n):
     return _ExpandAgentsFn.apply(x, n) if x.requires_grad else x.expand(-1, n, -1)
 
 
+def _policy_args(obs2d, act, W, bias, tail):
+    """The forward set-up of the two policy-loss nodes: fc1 on [obs | the policy's own actions] — value-wise every row is
+    shared[b] + W_id[:, i], the own-action term is zero-valued — and the composed tail's arguments on it."""
+    b, n, na_ = act.shape
+    no = obs2d.shape[1]
+    shared = critic_first_layer(bias, obs2d, act.reshape(b, n * na_), W, no + n)
+    return shared, _composed_args(shared, n, W, no, tail)
+
+
+def _policy_d_act(dz1, W, dims):
+    """d act[b, i] = dz1[b, i] @ W_act[:, block i]: row i of a sample carries agent i's own action block only."""
+    b, n, na_, no = dims
+    W_act = W[:, no + n:no + n + n * na_].reshape(64, n, na_)
+    return th.einsum("bih,hia->bia", dz1.view(b, n, 64), W_act)
+
+
 class _CriticPolicyFn(th.autograd.Function):
     """The shared-parameter critic inside the POLICY loss, maddpg.py:33-76 + maddpg.py:104-107: q[b, i] on the policy's own
     actions, differentiated w.r.t. those actions only (row i of a sample carries agent i's own action block; the other
@@ -1389,45 +1336,25 @@ class _CriticPolicyFn(th.autograd.Function):
     is used where only the policy optimiser steps (utils/trainer.py:99-108 steps the policy on the policy loss)."""
 
     @staticmethod
-    def forward(ctx, obs2d, act, W, bias, ln_w, ln_b, w2, b2, w3, b3, eps):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
-        b, n, na_ = act.shape
-        no = obs2d.shape[1]
-        act2d = act.reshape(b, n * na_)
-        shared = critic_first_layer(bias, obs2d, act2d, W, no + n)
-        rows = b * n
-        q = th.empty(rows, 1, dtype=th.float32, device=shared.device)
-        args = _critic_args(shared, ln_w, ln_b, w2, b2, w3, b3, eps)
-        args.rows, args.z1, args.z_shared, args.n_agents = rows, None, shared.data_ptr(), n
-        _set_critic_ids(args, W, no, n)
+    def forward(ctx, obs2d, act, W, bias, *tail):
+        shared, args = _policy_args(obs2d, act, W, bias, tail)
+        q = th.empty(args.rows, 1, dtype=th.float32, device=shared.device)
         args.q = q.data_ptr()
-        _lib.check(lib.flexnet_critic_tail_forward(C.byref(args), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                   "flexnet_critic_tail_forward")
-        ctx.eps, ctx.dims = eps, (b, n, na_, no)
-        ctx.save_for_backward(shared, W, ln_w, ln_b, w2, b2, w3, b3)
+        _lib.launch("flexnet_critic_tail_forward", args)
+        ctx.eps, ctx.dims = tail[6], (*act.shape, obs2d.shape[1])
+        ctx.save_for_backward(shared, W, *tail[:6])
         return q
 
     @staticmethod
     def backward(ctx, dq):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
-        shared, W, ln_w, ln_b, w2, b2, w3, b3 = ctx.saved_tensors
+        shared, W, *tail = ctx.saved_tensors
         b, n, na_, no = ctx.dims
-        rows = b * n
         dq = dq.contiguous()
-        dz1 = th.empty(rows, 64, dtype=th.float32, device=shared.device)
-        args = _critic_args(shared, ln_w, ln_b, w2, b2, w3, b3, ctx.eps)
-        args.rows, args.z1, args.z_shared, args.n_agents = rows, None, shared.data_ptr(), n
-        _set_critic_ids(args, W, no, n)
+        dz1 = th.empty(b * n, 64, dtype=th.float32, device=shared.device)
+        args = _composed_args(shared, n, W, no, (*tail, ctx.eps))
         args.dq, args.dz1 = dq.data_ptr(), dz1.data_ptr()
-        _lib.check(lib.flexnet_critic_tail_backward(C.byref(args), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                   "flexnet_critic_tail_backward")
-        W_act = W[:, no + n:no + n + n * na_].reshape(64, n, na_)
-        d_act = th.einsum("bih,hia->bia", dz1.view(b, n, 64), W_act)
-        return (None, d_act) + (None,) * 9
+        _lib.launch("flexnet_critic_tail_backward", args)
+        return (None, _policy_d_act(dz1, W, ctx.dims)) + (None,) * 9
 
 
 class _CriticPolicyLossFn(th.autograd.Function):
@@ -1439,28 +1366,15 @@ class _CriticPolicyLossFn(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, obs2d, act, W, bias, ln_w, ln_b, w2, b2, w3, b3, eps, sign):
-        import ctypes as C
-        from . import _lib
-        lib = _lib.load()
-        b, n, na_ = act.shape
-        no = obs2d.shape[1]
-        act2d = act.reshape(b, n * na_)
-        shared = critic_first_layer(bias, obs2d, act2d, W, no + n)
-        rows = b * n
+        shared, args = _policy_args(obs2d, act, W, bias, (ln_w, ln_b, w2, b2, w3, b3, eps))
+        rows = args.rows
         dz1 = th.empty(rows, 64, dtype=th.float32, device=shared.device)
         loss = th.empty((), dtype=th.float32, device=shared.device)
-        args = _critic_args(shared, ln_w, ln_b, w2, b2, w3, b3, eps)
-        args.rows, args.z1, args.z_shared, args.n_agents = rows, None, shared.data_ptr(), n
-        _set_critic_ids(args, W, no, n)
         args.dz1 = dz1.data_ptr()
         args.dq_uniform, args.dq_value, args.q_mean_scale, args.q_mean_out = 1, sign / rows, sign / rows, loss.data_ptr()
-        ws = _critic_workspace(shared.device)
-        args.workspace, args.workspace_floats = ws.data_ptr(), ws.numel()
-        _lib.check(lib.flexnet_critic_tail_backward(C.byref(args), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                   "flexnet_critic_tail_backward")
-        W_act = W[:, no + n:no + n + n * na_].reshape(64, n, na_)
-        d_act = th.einsum("bih,hia->bia", dz1.view(b, n, 64), W_act)
-        ctx.save_for_backward(d_act)
+        _bind_workspace(args, shared.device)
+        _lib.launch("flexnet_critic_tail_backward", args)
+        ctx.save_for_backward(_policy_d_act(dz1, W, (*act.shape, obs2d.shape[1])))
         return loss
 
     @staticmethod
@@ -1476,28 +1390,22 @@ def critic_policy_loss_supported(critic, obs2d, act, n_agents):
 
 
 def critic_policy_loss(obs2d, act, critic, sign=-1.0):
-    ln = critic.layernorm if critic.args.layernorm else None
-    return _CriticPolicyLossFn.apply(obs2d, act, critic.fc1.weight, critic.fc1.bias,
-                                     None if ln is None else ln.weight, None if ln is None else ln.bias,
-                                     critic.fc2.weight, critic.fc2.bias, critic.fc3.weight, critic.fc3.bias,
-                                     1e-5 if ln is None else ln.eps, float(sign))
+    return _CriticPolicyLossFn.apply(obs2d, act, critic.fc1.weight, critic.fc1.bias, *_tail_params(critic), float(sign))
 
 
 def critic_policy_supported(critic, obs2d, act, n_agents):
-    a = critic.args
     W = critic.fc1.weight
-    return (obs2d.is_cuda and obs2d.dtype == th.float32 and act.dtype == th.float32 and act.dim() == 3 and a.hid_size == 64
-            and a.hid_activation == "relu" and critic.fc3.out_features == 1 and getattr(critic, "fused_tail", True)
+    return (obs2d.is_cuda and obs2d.dtype == th.float32 and act.dtype == th.float32 and act.dim() == 3
+            and _critic_config_ok(critic) and getattr(critic, "fused_tail", True)
             and 1 <= n_agents <= 8 and not obs2d.requires_grad and act.shape[1] == n_agents
             and W.shape[1] in (obs2d.shape[1] + n_agents + n_agents * act.shape[2],
                                obs2d.shape[1] + n_agents + n_agents * act.shape[2] + 1))      # + MATD3's twin flag column
 
 
 def critic_replayed_supported(critic, obs2d, act2d, n_agents):
-    a = critic.args
     W = critic.fc1.weight
-    return (obs2d.is_cuda and obs2d.dtype == th.float32 and act2d.dtype == th.float32 and a.hid_size == 64
-            and a.hid_activation == "relu" and critic.fc3.out_features == 1 and getattr(critic, "fused_tail", True)
+    return (obs2d.is_cuda and obs2d.dtype == th.float32 and act2d.dtype == th.float32
+            and _critic_config_ok(critic) and getattr(critic, "fused_tail", True)
             and 1 <= n_agents <= 8 and not obs2d.requires_grad and not act2d.requires_grad
             and obs2d.shape[0] >= WGRAD_MIN_ROWS and W.shape[1] in (obs2d.shape[1] + n_agents + act2d.shape[1],
                                                                     obs2d.shape[1] + n_agents + act2d.shape[1] + 1)
@@ -1507,41 +1415,23 @@ def critic_replayed_supported(critic, obs2d, act2d, n_agents):
 class CriticTail:
     @staticmethod
     def apply_policy(obs2d, act, critic):
-        ln = critic.layernorm if critic.args.layernorm else None
-        return _CriticPolicyFn.apply(obs2d, act, critic.fc1.weight, critic.fc1.bias,
-                                     None if ln is None else ln.weight, None if ln is None else ln.bias,
-                                     critic.fc2.weight, critic.fc2.bias, critic.fc3.weight, critic.fc3.bias,
-                                     1e-5 if ln is None else ln.eps)
+        return _CriticPolicyFn.apply(obs2d, act, critic.fc1.weight, critic.fc1.bias, *_tail_params(critic))
 
     @staticmethod
     def apply_replayed_twin(obs2d, act2d, n_agents, critic):
-        ln = critic.layernorm if critic.args.layernorm else None
-        return _CriticReplayedTwinFn.apply(obs2d, act2d, n_agents, critic.fc1.weight, critic.fc1.bias,
-                                           None if ln is None else ln.weight, None if ln is None else ln.bias,
-                                           critic.fc2.weight, critic.fc2.bias, critic.fc3.weight, critic.fc3.bias,
-                                           1e-5 if ln is None else ln.eps)
+        return _CriticReplayedTwinFn.apply(obs2d, act2d, n_agents, critic.fc1.weight, critic.fc1.bias, *_tail_params(critic))
 
     @staticmethod
     def apply_replayed(obs2d, act2d, n_agents, critic, twin=False):
-        ln = critic.layernorm if critic.args.layernorm else None
-        return _CriticReplayedFn.apply(obs2d, act2d, n_agents, critic.fc1.weight, critic.fc1.bias,
-                                       None if ln is None else ln.weight, None if ln is None else ln.bias,
-                                       critic.fc2.weight, critic.fc2.bias, critic.fc3.weight, critic.fc3.bias,
-                                       1e-5 if ln is None else ln.eps, twin)
+        return _CriticReplayedFn.apply(obs2d, act2d, n_agents, critic.fc1.weight, critic.fc1.bias, *_tail_params(critic), twin)
 
     @staticmethod
     def apply_composed(shared, id_cols, critic):
-        ln = critic.layernorm if critic.args.layernorm else None
-        return _CriticTailComposedFn.apply(shared, id_cols, None if ln is None else ln.weight,
-                                           None if ln is None else ln.bias, critic.fc2.weight, critic.fc2.bias,
-                                           critic.fc3.weight, critic.fc3.bias, 1e-5 if ln is None else ln.eps)
+        return _CriticTailComposedFn.apply(shared, id_cols, *_tail_params(critic))
 
     @staticmethod
     def apply(z1, critic):
-        ln = critic.layernorm if critic.args.layernorm else None
-        return _CriticTailFn.apply(z1, None if ln is None else ln.weight, None if ln is None else ln.bias,
-                                   critic.fc2.weight, critic.fc2.bias, critic.fc3.weight, critic.fc3.bias,
-                                   1e-5 if ln is None else ln.eps)
+        return _CriticTailFn.apply(z1, *_tail_params(critic))
 
 
 # ---- QMIX mixer of FACMADDPG (madrl/critics/qmix.py) ---------------------------------------------------------------------
@@ -1647,7 +1537,6 @@ class QMixer(nn.Module):
 
 
 def _qmix_args(q, x, ws):
-    from . import _lib
     a = _lib.FlexQmixArgs()
     a.batch, a.n_agents, a.state_dim = q.shape[0], q.shape[1], x.shape[1]
     a.ld_state = x.stride(0) if x.shape[0] > 1 else x.shape[1]
@@ -1675,8 +1564,6 @@ class _QmixFn(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, x, save, *ws):
-        import ctypes as C
-        from . import _lib
         q = q.contiguous()
         if x.stride(-1) != 1 or (x.shape[0] > 1 and x.stride(0) % 4 != 0) or x.data_ptr() % 16 != 0:
             x = x.contiguous()
@@ -1688,16 +1575,13 @@ class _QmixFn(th.autograd.Function):
         a.q_tot = out.data_ptr()
         if h1 is not None:
             a.h1 = h1.data_ptr()
-        _lib.check(_lib.load().flexnet_qmix_forward(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                   "flexnet_qmix_forward")
+        _lib.launch("flexnet_qmix_forward", a)
         if save:
             ctx.save_for_backward(q, x, h1, *ws)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        import ctypes as C
-        from . import _lib
         q, x, h1, *ws = ctx.saved_tensors
         B, n = q.shape
         E = _lib.FLEXNET_QMIX_EMBED
@@ -1711,8 +1595,7 @@ class _QmixFn(th.autograd.Function):
             d_wf = th.empty(B, E, dtype=th.float32, device=q.device)
             d_pre1 = th.empty(B, 4 * E, dtype=th.float32, device=q.device)
             a.want_param_grads, a.d_w1, a.d_wf, a.d_pre1 = 1, d_w1.data_ptr(), d_wf.data_ptr(), d_pre1.data_ptr()
-        _lib.check(_lib.load().flexnet_qmix_backward(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                   "flexnet_qmix_backward")
+        _lib.launch("flexnet_qmix_backward", a)
         grads = [None] * len(ws)
         if want_w:
             S = x.shape[1]
@@ -1746,8 +1629,7 @@ _SQDDPG_WS = {}
 def sqddpg_fused_config(critic, n_agents, act_dim, sample_size):
     """The configuration csrc/sqddpg.hip implements (include/flexnet.h: flexnet_sqddpg_forward): a shared MLPCritic with hid
     64, ReLU and one output, the agent id columns, n <= 8 agents, act_dim <= 8 with n * act_dim <= 32."""
-    a = critic.args
-    return (a.hid_size == 64 and a.hid_activation == "relu" and critic.fc3.weight.shape[0] == 1 and bool(a.agent_id)
+    return (_critic_config_ok(critic) and bool(critic.args.agent_id)
             and 1 <= n_agents <= 8 and 1 <= act_dim <= 8 and n_agents * act_dim <= 32 and sample_size >= 1
             and sample_size * n_agents <= 4096)
 
@@ -1755,19 +1637,15 @@ def sqddpg_fused_config(critic, n_agents, act_dim, sample_size):
 def sqddpg_draw(groups, n_agents, rng_state):
     """One uniform random permutation per coalition group on the device: pos [groups, n] (int32), pos[g, i] = position of
     agent i.  The stream is rng_state = [seed, step] (int64, device); the step advances on the device after the draw."""
-    import ctypes as C
-    from . import _lib
     pos = th.empty(groups, n_agents, dtype=th.int32, device=rng_state.device)
     a = _lib.FlexSqddpgDrawArgs()
     a.groups, a.n_agents, a.rng_state, a.pos = groups, n_agents, rng_state.data_ptr(), pos.data_ptr()
-    _lib.check(_lib.load().flexnet_sqddpg_draw(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-               "flexnet_sqddpg_draw")
+    _lib.launch("flexnet_sqddpg_draw", a)
     rng_state[1:2].add_(1)
     return pos
 
 
 def _sqddpg_args(z_shared, z_id, w_act, act, pos, ns, eps, layernorm, ps):
-    from . import _lib
     a = _lib.FlexSqddpgArgs()
     a.batch, a.n_agents, a.act_dim = act.shape
     a.sample_size, a.layernorm, a.ln_eps = ns, int(layernorm), eps
@@ -1788,8 +1666,6 @@ class _SqddpgFn(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, z_shared, z_id, w_act, act, pos, ns, eps, layernorm, want_q, ln_w, ln_b, fc2_w, fc2_b, fc3_w, fc3_b):
-        import ctypes as C
-        from . import _lib
         ctx.set_materialize_grads(False)
         z_shared, z_id, w_act, act = z_shared.contiguous(), z_id.contiguous(), w_act.contiguous(), act.contiguous()
         pos = pos.to(th.int32).contiguous()
@@ -1801,8 +1677,7 @@ class _SqddpgFn(th.autograd.Function):
         k.phi = phi.data_ptr()
         if want_q:
             k.q = q.data_ptr()
-        _lib.check(_lib.load().flexnet_sqddpg_forward(C.byref(k), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                   "flexnet_sqddpg_forward")
+        _lib.launch("flexnet_sqddpg_forward", k)
         ctx.ns, ctx.eps, ctx.layernorm = ns, eps, layernorm
         ctx.save_for_backward(z_shared, z_id, w_act, act, pos, *[p if p is not None else phi.new_empty(0) for p in ps])
         if not want_q:
@@ -1811,8 +1686,6 @@ class _SqddpgFn(th.autograd.Function):
 
     @staticmethod
     def backward(ctx, d_phi, d_q):
-        import ctypes as C
-        from . import _lib
         z_shared, z_id, w_act, act, pos, *ps = ctx.saved_tensors
         if not ctx.layernorm:
             ps[0] = ps[1] = None
@@ -1844,8 +1717,7 @@ class _SqddpgFn(th.autograd.Function):
             k.workspace = _SQDDPG_WS[dev].data_ptr()
             for name, t in zip(("d_z_id", "d_w_act", "d_ln_w", "d_ln_b", "d_fc2_w", "d_fc2_b", "d_fc3_w", "d_fc3_b"), grads):
                 setattr(k, name, t.data_ptr())
-        _lib.check(_lib.load().flexnet_sqddpg_backward(C.byref(k), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                   "flexnet_sqddpg_backward")
+        _lib.launch("flexnet_sqddpg_backward", k)
         gz_id, gw_act, *gp = [g if nd else None for g, nd in zip(grads, (need[1], need[2]) + tuple(need[9:]))]
         return (dz, gz_id, gw_act, da, None, None, None, None, None, *gp)
 
@@ -1857,9 +1729,7 @@ def sqddpg_shapley_fused(critic, obs2d, act, pos, ns, want_q=False, frozen=False
     (a policy sub-update)."""
     b, n, ad = act.shape
     W, bias = critic.fc1.weight, critic.fc1.bias
-    ln = critic.layernorm if critic.args.layernorm else None
-    tail = [None if ln is None else ln.weight, None if ln is None else ln.bias, critic.fc2.weight, critic.fc2.bias,
-            critic.fc3.weight, critic.fc3.bias]
+    *tail, eps = _tail_params(critic)
     if frozen:
         W, bias = W.detach(), bias.detach()
         tail = [None if p is None else p.detach() for p in tail]
@@ -1867,8 +1737,7 @@ def sqddpg_shapley_fused(critic, obs2d, act, pos, ns, want_q=False, frozen=False
     z_shared = tall_linear(obs2d, W[:, :no], bias)
     w_act = W[:, no:no + n * ad]
     z_id = W[:, no + n * ad:no + n * ad + n].t()
-    phi, q = _SqddpgFn.apply(z_shared, z_id, w_act, act, pos, ns, 1e-5 if ln is None else ln.eps, ln is not None,
-                             want_q, *tail)
+    phi, q = _SqddpgFn.apply(z_shared, z_id, w_act, act, pos, ns, eps, tail[0] is not None, want_q, *tail)
     return phi, (q if want_q else None)
 
 
@@ -1882,7 +1751,6 @@ _PPO_WS = {}
 def _ppo_workspace(device):
     """The statistics and loss partials of one call, read by that call's own finish launch: one workspace per (device,
     stream), so calls on different streams never share one (calls on one stream run in order)."""
-    from . import _lib
     key = (device, th.cuda.current_stream(device).cuda_stream)
     if key not in _PPO_WS:
         _PPO_WS[key] = th.empty(_lib.FLEXNET_PPO_WS_FLOATS // 2, dtype=th.float64, device=device)
@@ -1945,8 +1813,6 @@ def ppo_gae(reward, old_values, old_next_values, done, last_step, gamma, lambda_
     done, last_step = done.reshape(rows), last_step.reshape(rows)
     with th.no_grad():
         if fused and n <= 8 and ppo_fused_supported((reward_bn, adv_bn), reward, old_values, old_next_values, done, last_step):
-            import ctypes as C
-            from . import _lib
             r, v, nv, d, ls = (x.contiguous() for x in (reward, old_values, old_next_values, done, last_step))
             rn, adv = th.empty_like(r), th.empty_like(r)
             advn = th.empty_like(r) if adv_bn is not None else adv
@@ -1958,11 +1824,8 @@ def ppo_gae(reward, old_values, old_next_values, done, last_step, gamma, lambda_
             _ppo_bn_args(a.adv_bn, adv_bn)
             a.reward_norm, a.advantages, a.advantages_norm = rn.data_ptr(), adv.data_ptr(), advn.data_ptr()
             a.workspace, a.workspace_floats = ws.data_ptr(), 2 * ws.numel()
-            rc = _lib.load().flexnet_ppo_gae(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream))
-            if rc == 0:
+            if _lib.try_launch("flexnet_ppo_gae", a):
                 return rn, adv, advn
-            if rc != _lib.FLEXNET_EUNSUPPORTED:
-                _lib.check(rc, "flexnet_ppo_gae")
         if fused and reward.is_cuda:
             note_fallback("ppo_gae", f"agents {n}, dtype {reward.dtype}, cross-rank statistics or an evaluation-mode BatchNorm")
         rn = sync_batchnorm(reward_bn, reward.contiguous()) if reward_bn is not None else reward
@@ -2024,8 +1887,6 @@ def ppo_policy_loss(means, log_stds, actions, old_log_prob, advantages, eps_clip
     if (fused and every and n <= 8 and na <= 8 and na > 1 and means.is_cuda and actions.shape == means.shape
             and ppo_fused_supported((), means, actions, advantages, old_log_prob)
             and getattr(log_stds, "_flex_entropy", None) is not None):
-        import ctypes as C
-        from . import _lib
         with th.no_grad():
             m, act, adv = means.detach().contiguous(), actions.contiguous(), advantages.reshape(rows, n).contiguous()
             ls = log_stds.detach()[:1].sum(dim=1).reshape(na).contiguous()        # the agent-summed log-std of one row
@@ -2040,11 +1901,9 @@ def ppo_policy_loss(means, log_stds, actions, old_log_prob, advantages, eps_clip
                 a.old_log_prob = old.data_ptr()
             a.loss, a.d_means, a.ratio = loss.data_ptr(), d_means.data_ptr(), ratio.data_ptr()
             a.workspace, a.workspace_floats = ws.data_ptr(), 2 * ws.numel()
-            rc = _lib.load().flexnet_ppo_policy_loss(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream))
-        if rc == 0:
+            ran = _lib.try_launch("flexnet_ppo_policy_loss", a)
+        if ran:
             return _PpoLossFn.apply(means, loss, d_means), ratio
-        if rc != _lib.FLEXNET_EUNSUPPORTED:
-            _lib.check(rc, "flexnet_ppo_policy_loss")
     if fused and means.is_cuda:
         note_fallback("ppo_policy_loss", f"agents {n}, act_dim {na}, dtype {means.dtype}, every action available: {every}")
     loss, ratios = ppo_policy_loss_torch(means, log_stds, actions, actions if old_log_prob is None else old_log_prob,
@@ -2057,8 +1916,6 @@ def ppo_value_loss(values, old_values, next_values, reward_norm, done, gamma, ep
     rows, n = reward_norm.shape
     values2, old_values, next_values = values.reshape(rows, n), old_values.reshape(rows, n), next_values.reshape(rows, n).detach()
     if fused and n <= 8 and values.is_cuda and ppo_fused_supported((), values2, old_values, next_values, reward_norm, done):
-        import ctypes as C
-        from . import _lib
         with th.no_grad():
             v, ov, nv, rn, d = (x.detach().contiguous() for x in (values2, old_values, next_values, reward_norm, done.reshape(rows)))
             loss = th.empty((), dtype=th.float32, device=v.device)
@@ -2069,11 +1926,9 @@ def ppo_value_loss(values, old_values, next_values, reward_norm, done, gamma, ep
             a.values, a.old_values, a.next_values, a.reward_norm, a.done = (x.data_ptr() for x in (v, ov, nv, rn, d))
             a.loss, a.d_values, a.returns = loss.data_ptr(), d_values.data_ptr(), returns.data_ptr()
             a.workspace, a.workspace_floats = ws.data_ptr(), 2 * ws.numel()
-            rc = _lib.load().flexnet_ppo_value_loss(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream))
-        if rc == 0:
+            ran = _lib.try_launch("flexnet_ppo_value_loss", a)
+        if ran:
             return _PpoLossFn.apply(values, loss, d_values.view(values.shape)), returns
-        if rc != _lib.FLEXNET_EUNSUPPORTED:
-            _lib.check(rc, "flexnet_ppo_value_loss")
     if fused and values.is_cuda:
         note_fallback("ppo_value_loss", f"agents {n}, dtype {values.dtype}")
     loss, returns = ppo_value_loss_torch(values2, old_values, next_values, reward_norm, done, gamma, eps_clip, value_loss_coef)

@@ -428,7 +428,6 @@ def qp_ipm_native(Qblk, c, lo, hi, free, jv, v_lo, v_hi, ji, i_hi, chain_a, chai
     Riccati recursion over the periods instead of a dense factorisation.  Qblk [B, T, w, w]; c, lo, hi, x0 [B, T w]; free
     [B, T w] bool; jv, ji [B, T, R, w]; v_lo, v_hi, i_hi [B, T R]; e_lo, e_hi [B, T na].  Returns (x, info) like qp_ipm;
     ``info["duals"]`` in qp_ipm's order (upper, lower of every block that has them)."""
-    import ctypes as C
     from . import _lib
     B, T, w, _ = Qblk.shape
     R, na = jv.shape[2], w // 4
@@ -452,7 +451,7 @@ def qp_ipm_native(Qblk, c, lo, hi, free, jv, v_lo, v_hi, ji, i_hi, chain_a, chai
     a.tol, a.reg, a.chain_a, a.chain_b = float(tol), float(reg), float(chain_a), float(chain_b)
     (a.q, a.c, a.lo, a.hi, a.jv, a.v_lo, a.v_hi, a.ji, a.i_hi, a.e_lo, a.e_hi, a.x0) = [t.data_ptr() for t in keep]
     a.free_mask, a.x, a.duals, a.info, a.work = fm.data_ptr(), x.data_ptr(), duals.data_ptr(), info.data_ptr(), work.data_ptr()
-    _lib.check(lib.flexopf_qp_solve(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream)), "flexopf_qp_solve")
+    _lib.launch("flexopf_qp_solve", a)
     res = info.cpu()                                      # (synchronises: the scratch and the inputs outlive the launch)
     conv = res[:, 4] > 0.5
     out = dict(iters=int(res[:, 0].max().item()), mu=res[:, 1].to(dev), res_d=res[:, 2].to(dev), res_p=res[:, 3].to(dev),

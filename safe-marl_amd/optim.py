@@ -6,8 +6,6 @@ PyTorch creates it and updated in place, so ``state_dict()`` round-trips and a l
 from it.  Configurations the kernel does not cover fall back to the two PyTorch calls."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch as th
 
 
@@ -44,7 +42,6 @@ def clip_and_step(opt, params, max_norm, refresh=None):
             _launch_refresh(refresh)
         return norm
     from . import _lib
-    lib = _lib.load()
     g = opt.param_groups[0]
     a = _lib.FlexClipRmspropArgs()
     a.lr, a.alpha, a.eps, a.max_norm = float(g["lr"]), float(g["alpha"]), float(g["eps"]), float(max_norm)
@@ -63,13 +60,10 @@ def clip_and_step(opt, params, max_norm, refresh=None):
         a.square_avg[k], a.step[k] = st["square_avg"].data_ptr(), st["step"].data_ptr()
         k += 1
     a.n_tensors = k
-    stream = C.c_void_p(th.cuda.current_stream().cuda_stream)
     if refresh is not None and k > 0:
-        ra, td = refresh
-        _lib.check(lib.flexnet_clip_rmsprop_refresh(C.byref(a), C.byref(ra), C.byref(td) if td is not None else None, stream),
-                   "flexnet_clip_rmsprop_refresh")
+        _lib.launch("flexnet_clip_rmsprop_refresh", a, *refresh)
         return norm
-    _lib.check(lib.flexnet_clip_rmsprop(C.byref(a), stream), "flexnet_clip_rmsprop")
+    _lib.launch("flexnet_clip_rmsprop", a)
     if refresh is not None:
         _launch_refresh(refresh)
     return norm
@@ -77,6 +71,4 @@ def clip_and_step(opt, params, max_norm, refresh=None):
 
 def _launch_refresh(refresh):
     from . import _lib
-    ra, td = refresh
-    _lib.check(_lib.load().flexnet_window_refresh(C.byref(ra), C.byref(td) if td is not None else None,
-                                                  C.c_void_p(th.cuda.current_stream().cuda_stream)), "flexnet_window_refresh")
+    _lib.launch("flexnet_window_refresh", *refresh)

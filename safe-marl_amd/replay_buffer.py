@@ -341,15 +341,13 @@ class DeviceReplayBuffer:
     def stacked_obs(self, slot, rows, out=None):
         """Row mode: the stacked observations [rows, n_agents * obs_dim] of the global slot range [slot, slot + rows), formed
         from the row ring by ONE launch of flexnet_gather_window (include/flexnet.h); the ring's seam is the kernel's business."""
-        import ctypes as C
         from . import _lib
         if out is None:
             out = th.empty(rows, self.n_agents * self.obs_dim, dtype=th.float32, device=self.device)
         a = _lib.FlexWindowArgs()
         a.row_ring, a.dst, a.rows, a.first_slot = self.row_ring.data_ptr(), out.data_ptr(), rows, int(slot)
         a.n_envs, a.n_agents, a.history, a.slabs = self.n_envs, self.n_agents, self.history, self.slabs
-        _lib.check(_lib.load().flexnet_gather_window(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                   "flexnet_gather_window")
+        _lib.launch("flexnet_gather_window", a)
         return out
 
     # -- stacked-observation ring (row mode, round 5): every slab's stacked observations formed ONCE ------------------------
@@ -442,7 +440,6 @@ class DeviceReplayBuffer:
         flexnet_gather_rows (include/flexnet.h).  ``plan`` = [(ring name, first column, width, row offset, rows, dst)],
         dst a contiguous [rows, width] fp32 tensor.  ``td`` = (reward tensor of the plan, FlexTdLossArgs): the value loss's
         reward-statistics pass rides in the same launch (flexnet_gather_rows_td; nets.offer_td_stats)."""
-        import ctypes as C
         from . import _lib
         jobs = []
         td_first = td_count = None
@@ -471,7 +468,6 @@ class DeviceReplayBuffer:
                 td_count = len(jobs) - td_first
         # a window that wraps the ring's seam splits every field in two: up to 2 x 8 stored fields = 16 jobs against the
         # launch's FLEXNET_GATHER_MAX_JOBS (12) — the rest goes out as a second launch instead of an intermittent error
-        stream = C.c_void_p(th.cuda.current_stream().cuda_stream)
         for lo in range(0, len(jobs), _lib.FLEXNET_GATHER_MAX_JOBS):
             a = _lib.FlexGatherArgs()
             chunk = jobs[lo:lo + _lib.FLEXNET_GATHER_MAX_JOBS]
@@ -480,14 +476,13 @@ class DeviceReplayBuffer:
                 a.rows[j], a.width[j], a.src_stride[j], a.dst_stride[j] = c, width, stride, width
             a.n_jobs = len(chunk)
             if td_count and lo <= td_first and td_first + td_count <= lo + len(chunk):
-                _lib.check(_lib.load().flexnet_gather_rows_td(C.byref(a), td_first - lo, td_count, C.byref(td[1]), stream),
-                           "flexnet_gather_rows_td")
+                _lib.launch("flexnet_gather_rows_td", a, td_first - lo, td_count, td[1])
                 td_count = 0
             else:
-                _lib.check(_lib.load().flexnet_gather_rows(C.byref(a), stream), "flexnet_gather_rows")
+                _lib.launch("flexnet_gather_rows", a)
         if td is not None and td_count != 0:
             # (the reward's copies fell across two launches, or the plan does not gather the tensor: the pass on its own)
-            _lib.check(_lib.load().flexnet_td_stats(C.byref(td[1]), stream), "flexnet_td_stats")
+            _lib.launch("flexnet_td_stats", td[1])
 
     def window_refresh_args(self, plan, start_cell, td=None):
         """``plan`` as FlexWindowRefreshArgs with the window's first slot read from the device cell ``start_cell`` (int64, a
@@ -525,16 +520,12 @@ class DeviceReplayBuffer:
 
     def window_refresh(self, args):
         """Launch a refresh prepared by window_refresh_args on the current stream (capturable)."""
-        import ctypes as C
         from . import _lib
-        a, td_args = args
-        _lib.check(_lib.load().flexnet_window_refresh(C.byref(a), C.byref(td_args) if td_args is not None else None,
-                                                      C.c_void_p(th.cuda.current_stream().cuda_stream)), "flexnet_window_refresh")
+        _lib.launch("flexnet_window_refresh", *args)
 
     def scatter(self, ring_name, src, slot, rows):
         """The reverse of one gather job: rows of the contiguous [rows, width] tensor ``src`` into the ring's slots of the
         global slot range [slot, slot + rows) (two pieces at the seam): one launch of flexnet_gather_rows."""
-        import ctypes as C
         from . import _lib
         ring = getattr(self, ring_name)
         stride = ring.shape[2]
@@ -547,8 +538,7 @@ class DeviceReplayBuffer:
             a.rows[j], a.width[j], a.src_stride[j], a.dst_stride[j] = c, stride, stride, stride
             done_rows += c
             a.n_jobs = j + 1
-        _lib.check(_lib.load().flexnet_gather_rows(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream)),
-                   "flexnet_gather_rows")
+        _lib.launch("flexnet_gather_rows", a)
 
     def _logical_to_slot(self, index):
         """Global slot of logical transition ``index`` (0 = oldest), skipping gaps."""

@@ -137,9 +137,7 @@ class _MeanAllFn(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, sign):
-        import ctypes as C
         from . import _lib
-        lib = _lib.load()
         flat = x.contiguous().view(-1)
         out = th.empty((), dtype=th.float32, device=x.device)
         if x.device not in _SUM_WS:
@@ -148,7 +146,7 @@ class _MeanAllFn(th.autograd.Function):
         a = _lib.FlexSumArgs()
         a.n, a.scale = flat.numel(), sign / flat.numel()
         a.x, a.out, a.workspace, a.workspace_floats = flat.data_ptr(), out.data_ptr(), ws.data_ptr(), 2 * ws.numel()
-        _lib.check(lib.flexnet_scaled_sum(C.byref(a), C.c_void_p(th.cuda.current_stream().cuda_stream)), "flexnet_scaled_sum")
+        _lib.launch("flexnet_scaled_sum", a)
         ctx.shape, ctx.scale = x.shape, sign / flat.numel()
         return out
 
