@@ -50,10 +50,16 @@ PPO_ALG_ARGS = dict(policy_lrate=1.0e-4, value_lrate=1.0e-4, value_update_epochs
                     eps_clip=0.6, value_loss_coef=2.0, reward_normalisation=True, normalize_advantages=True,
                     gaussian_policy=False, action_enforcebound=True, behaviour_update_freq=240, target_update_freq=480)
 
+# alg_args/coma.yaml over the defaults above: on-policy, an update event every 60 vector steps of ten value sub-updates and
+# one policy sub-update on pooled windows of 32 steps of every environment; ten draws per agent for the baseline
+COMA_ALG_ARGS = dict(policy_lrate=1.0e-4, value_lrate=1.0e-4, sample_size=10, gaussian_policy=False,
+                     action_enforcebound=True)
+
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--alg", choices=["maddpg", "safemaddpg", "matd3", "iddpg", "facmaddpg", "sqddpg", "ippo", "mappo"], default="maddpg")
+    ap.add_argument("--alg", choices=["maddpg", "safemaddpg", "matd3", "iddpg", "facmaddpg", "sqddpg", "ippo", "mappo", "coma"],
+                    default="maddpg")
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--episodes", type=int, default=3)
     ap.add_argument("--agents", type=int, default=5, choices=[3, 5])
@@ -63,7 +69,7 @@ def main():
     import torch
     import safe_marl_amd  # noqa: F401
     from safe_marl_amd.flex_env import VecFlexProvisionEnv
-    from safe_marl_amd.learner import FACMADDPG, IDDPG, IPPO, MADDPG, MAPPO, MATD3, SAFEMADDPG, SQDDPG
+    from safe_marl_amd.learner import COMA, FACMADDPG, IDDPG, IPPO, MADDPG, MAPPO, MATD3, SAFEMADDPG, SQDDPG
     from safe_marl_amd.network import create_network
     from safe_marl_amd.series import make_synthetic_series
     from safe_marl_amd.trainer import PGTrainer
@@ -93,15 +99,18 @@ def main():
         alg.update(SQDDPG_ALG_ARGS)
     if a.alg in ("ippo", "mappo"):
         alg.update(PPO_ALG_ARGS)
+    if a.alg == "coma":
+        alg.update(COMA_ALG_ARGS)
     alg.update(alg=a.alg, agent_num=env.n_agents, obs_size=env.obs_size, state_size=env.state_size,
                action_dim=4, v_min=0.9, v_max=1.1)
     args = convert(alg)
     torch.manual_seed(0)
     trainer = PGTrainer(args, {"maddpg": MADDPG, "safemaddpg": SAFEMADDPG, "matd3": MATD3, "iddpg": IDDPG,
-                                 "facmaddpg": FACMADDPG, "sqddpg": SQDDPG, "ippo": IPPO, "mappo": MAPPO}[a.alg], env, None,
+                                 "facmaddpg": FACMADDPG, "sqddpg": SQDDPG, "ippo": IPPO, "mappo": MAPPO,
+                                 "coma": COMA}[a.alg], env, None,
                         batch_scale=a.batch_scale,
                         # (on-policy: the trainer's default holds what is collected between two update events)
-                        replay_capacity=None if a.alg in ("ippo", "mappo") else a.envs * 96 * 2)
+                        replay_capacity=None if a.alg in ("ippo", "mappo", "coma") else a.envs * 96 * 2)
     stat = {}
     trainer.behaviour_net.train_process(stat, trainer)          # warm-up episode (allocations, rocBLAS plans)
     torch.cuda.synchronize()

@@ -726,6 +726,69 @@ int flexnet_ppo_gae(const FlexPpoGaeArgs* args, void* stream);
 int flexnet_ppo_policy_loss(const FlexPpoPolicyArgs* args, void* stream);
 int flexnet_ppo_value_loss(const FlexPpoValueArgs* args, void* stream);
 
+/* ---- COMA (madrl/models/coma.py:126-189, continuous branch; csrc/coma.hip) -----------------------------------------
+ * baseline: the counterfactual baseline of coma.py:137-149 with a shared MLPCritic, agent_id, hid 64, ReLU.  Critic row
+ *         (b, i) is [o_1 .. o_n | o_i | onehot(i) | a_1 .. a_n]; z1 [b n, 64] is its fc1 pre-activation (before the
+ *         LayerNorm) on the actions taken.  Row (s, b, i) of the baseline replaces agent i's own action by the draw
+ *         sampled[s, b, i], so its pre-activation is z1[b, i] + w_act[:, i a : (i + 1) a] (sampled[s, b, i] - act[b, i]):
+ *         a rank-act_dim update, then the MLPCritic tail.  baseline [b, n] = mean over s (summed in the order s = 0, 1, ..:
+ *         bit-reproducible); q_sampled [s, b, n] and q [b, n] (the tail of the unmodified z1, from the same pass) are
+ *         optional.  Forward only: the baseline enters the loss detached (coma.py:180).
+ *         n_agents 1..FLEXNET_MAX_AGENTS, act_dim 1..8 with n * act_dim <= 32, sample_size >= 1, z1 / fc2_w 16-byte
+ *         aligned, batch * n < 2^31; else FLEXNET_EUNSUPPORTED.  Missing tensors: FLEXNET_EINVAL.  Both before any HIP call.
+ * policy: adv = advantages[b, i] when given, else q[b, i] - baseline[b, i];
+ *         log p[b, i] = sum_k avail[b, i, k] log N(actions[b, i, k]; means[b, i, k], exp(log_stds[b, i, k])) (per-agent
+ *         means, util.py:42-44 and coma.py:183-185; avail NULL: every action available; log_std_uniform: log_stds is ONE
+ *         element);  loss = -mean(adv log p);  d_means = d loss / d means and, where non-NULL, d_log_stds.  Sums in fp64 in
+ *         a fixed order.  n_agents <= FLEXNET_MAX_AGENTS, act_dim <= FLEXNET_MAX_ACT. */
+#define FLEXNET_COMA_BLOCKS 256
+#define FLEXNET_COMA_WS_FLOATS (2 * FLEXNET_COMA_BLOCKS)
+typedef struct {
+    int64_t batch;             /* b */
+    int32_t n_agents;
+    int32_t act_dim;
+    int32_t sample_size;       /* s */
+    int32_t layernorm;
+    float ln_eps;
+    int32_t pad0;
+    const float* z1;           /* [b n, 64] */
+    const float* w_act;        /* [64, n a]: the action columns of fc1.weight */
+    const float* act;          /* [b, n, a] */
+    const float* sampled;      /* [s, b, n, a] */
+    const float* ln_w;         /* [64], [64] (layernorm) */
+    const float* ln_b;
+    const float* fc2_w;        /* [64, 64], [64] */
+    const float* fc2_b;
+    const float* fc3_w;        /* [1, 64], [1] */
+    const float* fc3_b;
+    float* baseline;           /* out [b, n] */
+    float* q_sampled;          /* out [s, b, n] (optional) */
+    float* q;                  /* out [b, n] (optional) */
+} FlexComaBaselineArgs;
+
+typedef struct {
+    int64_t rows;              /* b */
+    int32_t n_agents, act_dim;
+    int32_t log_std_uniform;
+    int32_t pad0;
+    const float* means;        /* [rows, n, a] */
+    const float* log_stds;     /* [rows, n, a], or one element (log_std_uniform) */
+    const float* actions;      /* [rows, n, a] */
+    const float* avail;        /* [rows, n, a] or NULL */
+    const float* q;            /* [rows, n] */
+    const float* baseline;     /* [rows, n] */
+    const float* advantages;   /* [rows, n] or NULL (q - baseline) */
+    float* loss;               /* out [1] */
+    float* d_means;            /* out [rows, n, a] */
+    float* d_log_stds;         /* out [rows, n, a] (optional) */
+    float* log_prob;           /* out [rows, n] (optional) */
+    float* workspace;          /* 8-byte aligned */
+    int64_t workspace_floats;  /* >= FLEXNET_COMA_WS_FLOATS */
+} FlexComaPolicyArgs;
+
+int flexnet_coma_baseline(const FlexComaBaselineArgs* args, void* stream);
+int flexnet_coma_policy_loss(const FlexComaPolicyArgs* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

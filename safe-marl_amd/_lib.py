@@ -80,6 +80,7 @@ SYMBOLS = (
     "flexnet_qmix_forward", "flexnet_qmix_backward",
     "flexnet_sqddpg_draw", "flexnet_sqddpg_forward", "flexnet_sqddpg_backward",
     "flexnet_ppo_gae", "flexnet_ppo_policy_loss", "flexnet_ppo_value_loss",
+    "flexnet_coma_baseline", "flexnet_coma_policy_loss",
     "flexopf_qp_work_doubles", "flexopf_qp_solve",
 )
 
@@ -283,6 +284,27 @@ class FlexPpoValueArgs(C.Structure):
                [("workspace_floats", C.c_int64)]
 
 
+FLEXNET_COMA_BLOCKS = 256
+FLEXNET_COMA_WS_FLOATS = 2 * FLEXNET_COMA_BLOCKS
+
+
+class FlexComaBaselineArgs(C.Structure):
+    """include/flexnet.h"""
+    _fields_ = [("batch", C.c_int64), ("n_agents", C.c_int32), ("act_dim", C.c_int32), ("sample_size", C.c_int32),
+                ("layernorm", C.c_int32), ("ln_eps", C.c_float), ("pad0", C.c_int32)] + \
+               [(k, C.c_void_p) for k in ("z1", "w_act", "act", "sampled", "ln_w", "ln_b", "fc2_w", "fc2_b", "fc3_w", "fc3_b",
+                                          "baseline", "q_sampled", "q")]
+
+
+class FlexComaPolicyArgs(C.Structure):
+    """include/flexnet.h"""
+    _fields_ = [("rows", C.c_int64), ("n_agents", C.c_int32), ("act_dim", C.c_int32), ("log_std_uniform", C.c_int32),
+                ("pad0", C.c_int32)] + \
+               [(k, C.c_void_p) for k in ("means", "log_stds", "actions", "avail", "q", "baseline", "advantages", "loss",
+                                          "d_means", "d_log_stds", "log_prob", "workspace")] + \
+               [("workspace_floats", C.c_int64)]
+
+
 class FlexSumArgs(C.Structure):
     """include/flexnet.h"""
     _fields_ = [("n", C.c_int64), ("scale", C.c_float), ("pad0", C.c_int32), ("x", C.c_void_p), ("out", C.c_void_p),
@@ -420,6 +442,9 @@ def load():
         fn.restype = C.c_int
     for fn in (lib.flexnet_sqddpg_forward, lib.flexnet_sqddpg_backward):
         fn.argtypes = [C.POINTER(FlexSqddpgArgs), vp]
+        fn.restype = C.c_int
+    for fn, st in ((lib.flexnet_coma_baseline, FlexComaBaselineArgs), (lib.flexnet_coma_policy_loss, FlexComaPolicyArgs)):
+        fn.argtypes = [C.POINTER(st), vp]
         fn.restype = C.c_int
     lib.flexnet_agent_sum_explore.argtypes = [C.POINTER(FlexAgentSumArgs), vp]
     lib.flexnet_agent_sum_explore.restype = C.c_int

@@ -20,16 +20,11 @@
 #include <stdint.h>
 #include "flexnet.h"
 #include "flex_reduce.h"
+#include "critic_mfma.h"
 
-typedef float sv16 __attribute__((ext_vector_type(16)));
-typedef float sv4 __attribute__((ext_vector_type(4)));
-
-#define SH FLEXNET_HID                                      // 64
 #define SQ_LP 68                                            // LDS row pitch (floats) of the [row][unit] stages
 #define SQ_XP 33                                            // LDS row pitch of the action stage [row][k]
 #define SQ_MAXK 32                                          // n a <= 32: one MFMA k tile for dW_act
-#define SQMFMA(a_, b_, c_) __builtin_amdgcn_mfma_f32_32x32x2f32((a_), (b_), (c_), 0, 0, 0)
-#define SU(r, h) (8 * ((r) >> 2) + 4 * (h) + ((r) & 3))     // unit of accumulator register r in lane half h
 
 // workspace row of one wavefront's parameter-gradient partials (floats)
 #define SQW_W2 0                                            // dW2 [64][64]
@@ -41,30 +36,6 @@ typedef float sv4 __attribute__((ext_vector_type(4)));
 #define SQW_ID 4416                                         // d z_id [8][64]
 #define SQW_WA 4928                                         // dW_act [64][32]
 static_assert(SQW_WA + SH * SQ_MAXK == FLEXNET_SQDDPG_WS_ROW, "workspace row layout");
-
-__device__ __forceinline__ sv4 ld4(const float* p) { return *reinterpret_cast<const sv4*>(p); }
-__device__ __forceinline__ float other_half(float v) { return __shfl_xor(v, 32, 64); }
-
-__device__ __forceinline__ sv16 bias_tile(const float* b, int h) {
-    sv16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = b[SU(r, h)];
-    return acc;
-}
-
-// out[o][s] = acc + sum_k W[o][k] in[k][s], 32 outputs o, k over 64 inputs as two accumulator-layout tiles
-__device__ __forceinline__ sv16 layer_tile(const float* wrow, sv16 acc, const sv16& in0, const sv16& in1) {
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const sv4 w = ld4(wrow + 32 * kt + 8 * q);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc = SQMFMA(w[j], kt ? in1[4 * q + j] : in0[4 * q + j], acc);
-        }
-    }
-    return acc;
-}
 
 // acc[k][s] += sum_o W[o][k] d[o][s] over the 32 outputs of tile d; wcol = W + obase * ld + kbase + i
 __device__ __forceinline__ sv16 transposed_tile(const float* wcol, int ld, int h, sv16 acc, const sv16& d) {

@@ -25,7 +25,8 @@ from .nets import (WGRAD_MIN_ROWS, CriticTail, critic_first_layer, critic_td_los
                    critic_policy_loss_supported, expand_agents, MLPAgent, MLPCritic, RNNAgent, critic_policy_supported, critic_replayed_supported,
                    critic_tail_supported, fused_actor_forward, tall_linear, td_loss, td_loss_supported, wide_batch_linear,
                    batchnorm_stats_supported, batchnorm_update_running_stats, sync_batchnorm, QMixer,
-                   sqddpg_draw, sqddpg_fused_config, sqddpg_shapley_fused, ppo_gae, ppo_policy_loss, ppo_value_loss)
+                   sqddpg_draw, sqddpg_fused_config, sqddpg_shapley_fused, ppo_gae, ppo_policy_loss, ppo_value_loss,
+                   coma_baseline, coma_baseline_torch, coma_fused_config, coma_policy_loss, coma_rows)
 from .replay_buffer import Transition
 from .util import graph_capture, prep_obs, scale_action, select_action, translate_action, mean_all, note_fallback
 
@@ -71,7 +72,7 @@ class RolloutGraph:
         # MATD3 / IDDPG with the bound enforced: their agent-summed action selection (matd3.py:92-97, iddpg.py:66-71 over
         # util.py:57-64) and translate_action as ONE launch behind the fused policy — bit-identical to get_actions +
         # env_action (same draws from torch's generator, every fp32 rounding in the same place), ~40 launches fewer per step
-        self.summed = (type(model).__name__ in ("MATD3", "IDDPG", "FACMADDPG", "SQDDPG", "IPPO", "MAPPO")
+        self.summed = (type(model).__name__ in ("MATD3", "IDDPG", "FACMADDPG", "SQDDPG", "IPPO", "MAPPO", "COMA")
                        and type(model).get_actions in (MATD3.get_actions, IDDPG.get_actions)
                        and bool(model.args.action_enforcebound) and bool(model.args.continuous) and a > 1
                        and env.obs.is_cuda and model.fused_inference and model.args.shared_params)
@@ -563,7 +564,7 @@ class Model(nn.Module):
         return out
 
     # -- update cadence (model.py:40-71) -----------------------------------------------------------
-    on_policy = False                # IPPO / MAPPO: the replay is cleared after every update event (model.py:54-57)
+    on_policy = False                # IPPO / MAPPO / COMA: the replay is cleared after every update event (model.py:54-57)
 
     def _unfiled_columns(self, n_envs):
         """What the vectorised rollout files for log_prob_a / value / next_value: constants nobody reads (the DDPG losses)."""
@@ -1868,3 +1869,156 @@ class MAPPO(IPPO):
             v, _ = self.value_dicts[0](inp.reshape(b * n, -1), None)
             return v.view(b, n, -1)
         return th.stack([net(inp[:, i, :], None)[0] for i, net in enumerate(self.value_dicts)], dim=1)
+
+
+class COMA(Model):
+    """madrl/models/coma.py:9-189 (continuous branch): a centralised critic Q_i on rows [o_1 .. o_n | o_i | onehot(i) |
+    a_1 .. a_n] and the counterfactual baseline — for every sample and agent the mean of the critic over ``sample_size``
+    draws of that agent's action from its own policy, everybody else's action kept.  The policy loss is
+    -mean((Q - baseline).detach() log p) with the per-agent log-density, the value loss the one-step TD error against the
+    target critic.  Action selection is IDDPG's agent-summed one (coma.py:104-124).  On-policy: the replay is cleared after
+    every update event (model.py:56).
+
+    On the GPU the first layer is assembled from fc1's column blocks (the all-observation and action blocks once per sample,
+    the own-observation block per row, the id column per agent), the baseline is one launch of csrc/coma.hip on that
+    pre-activation (nets.coma_baseline: nothing of [s b n, 889] is formed) and the policy loss another
+    (nets.coma_policy_loss); elsewhere the reference's composition on materialised rows."""
+
+    on_policy = True
+    graph_safe_updates = False       # sub-updates run eagerly
+    get_actions = IDDPG.get_actions  # coma.py:104-124 (continuous branch): the same function object
+    sample_source = None             # tests: callable(means, std, s) -> the draws [s, b, n, a] of coma.py:141
+
+    def __init__(self, args, target_net=None):
+        super().__init__(args)
+        if not args.continuous:
+            raise NotImplementedError("discrete control is outside the flexibility-provision hot path")
+        self.construct_model()
+        self.apply(self.init_weights)
+        if target_net is not None:
+            self.target_net = target_net
+            self.reload_params_to_target()
+        # coma.py:17: ONE module for the reward normalisation of unpack_data and (normalize_advantages) the advantages
+        self.batchnorm = nn.BatchNorm1d(self.args.agent_num).to(self.device)
+        self.sample_size = int(args.sample_size)
+        self.last_terms = {}
+
+    def construct_value_net(self):
+        """coma.py:19-35"""
+        input_shape = (self.n_ + 1) * self.obs_dim + self.n_ * self.act_dim + (self.n_ if self.args.agent_id else 0)
+        count = 1 if self.args.shared_params else self.n_
+        self.value_dicts = nn.ModuleList([MLPCritic(input_shape, 1, self.args) for _ in range(count)])
+
+    def construct_model(self):
+        self.construct_value_net()
+        self.construct_policy_net()
+
+    def begin_update_event(self, trainer):
+        """Nothing to file: COMA reads no stored value / log-probability column."""
+
+    # -- critic --------------------------------------------------------------------------------------------------------
+    def first_layer(self, obs, act):
+        """fc1 of the shared critic on the rows of coma.py:41-78, [b n, hid], from fc1.weight's column blocks: the
+        all-observation and action blocks once per sample, the own-observation block per row, the id column per agent — the
+        same affine map up to fp32 summation order, without the [b n, 889] input."""
+        b, n, o, a = obs.size(0), self.n_, self.obs_dim, self.act_dim
+        net = self.value_dicts[0]
+        W, bias = net.fc1.weight, net.fc1.bias
+        c_act = (n + 1) * o + (n if self.args.agent_id else 0)
+        obs_cols, act_cols = obs.reshape(b, n * o), act.detach().reshape(b, n * a)
+        if not th.is_grad_enabled() or not W.requires_grad:
+            with th.no_grad():
+                shared = critic_first_layer(bias, obs_cols, act_cols, W, c_act)
+        else:
+            shared = wide_batch_linear(obs_cols, W[:, :n * o]) + wide_batch_linear(act_cols, W[:, c_act:c_act + n * a]) + bias
+        z = shared.unsqueeze(1) + tall_linear(obs.reshape(b * n, o), W[:, n * o:(n + 1) * o]).view(b, n, -1)
+        if self.args.agent_id:
+            z = z + W[:, (n + 1) * o:(n + 1) * o + n].t().unsqueeze(0)
+        return z.reshape(b * n, -1)
+
+    def _composed(self, t):
+        return bool(self.args.shared_params and t.is_cuda and t.dtype == th.float32 and self.fused_inference)
+
+    def value(self, obs, act):
+        """coma.py:41-102 (continuous branch): ``act`` [b, n, a] -> [b, n, 1]; the baseline's form, ``act`` [s b, n, n a]
+        with row-specific actions -> [s b, n, 1] (the reference's view of the same values in the same order)."""
+        per_row = obs.size(0) != act.size(0)
+        b, n = obs.size(0), self.n_
+        if not per_row and self._composed(obs) and b * n >= WGRAD_MIN_ROWS:
+            v, _ = self.value_dicts[0].forward_from_hidden(self.first_layer(obs, act), need_hidden=False)
+            return v.view(b, n, 1)
+        rows = coma_rows(obs, act, self.args.agent_id, per_row)
+        if self.args.shared_params:
+            v, _ = self.value_dicts[0](rows.reshape(-1, rows.size(-1)), None)
+            return v.view(rows.size(0), n, -1)
+        return th.stack([net(rows[:, i, :], None)[0] for i, net in enumerate(self.value_dicts)], dim=1)
+
+    def draw_samples(self, means, std):
+        """coma.py:139-141: ``sample_size`` draws of every agent's action from its own policy, [s, b, n, a]."""
+        s = self.sample_size
+        if self.sample_source is not None:
+            return self.sample_source(means, std, s).to(means.device)
+        return th.normal(means.unsqueeze(0).expand(s, *means.shape), std.unsqueeze(0).expand(s, *means.shape))
+
+    def _fused(self, state):
+        if not (state.is_cuda and self.fused_inference):
+            return False
+        ok = (self.args.shared_params and state.dtype == th.float32
+              and coma_fused_config(self.value_dicts[0], self.n_, self.act_dim))
+        if not ok:
+            note_fallback("coma", f"shared_params {self.args.shared_params}, agent_id {self.args.agent_id}, "
+                                  f"hid {self.args.hid_size}, agents {self.n_}, act_dim {self.act_dim}")
+        return ok
+
+    # -- loss ----------------------------------------------------------------------------------------------------------
+    def get_loss(self, batch, need="both"):
+        """coma.py:126-189 -> (policy_loss, value_loss, (means, log_stds)).  ``need`` = "value": the value loss alone (no
+        draws, no baseline); "policy": the policy loss with the critic frozen; "both": the reference's call."""
+        args, n = self.args, self.n_
+        batch = self._tensor_batch(batch)
+        state, actions, _, _, _, rewards, next_state, done, _, actions_avail, last_hids, hids = self.unpack_data(batch)
+        fused = self._fused(state)
+        net = self.value_dicts[0]
+        terms = {}
+        policy_loss = value_loss = action_out = None
+        values = z1 = None
+        if fused:
+            with th.set_grad_enabled(th.is_grad_enabled() and need != "policy"):
+                z1 = self.first_layer(state, actions)
+        if need in ("both", "value"):
+            if fused:
+                values = net.forward_from_hidden(z1, need_hidden=False)[0].view(-1, n)
+            else:
+                values = self.value(state, actions).view(-1, n)
+        if need in ("both", "policy"):
+            means, log_stds, _ = self.policy(state, last_hid=last_hids)
+            action_out = (means, log_stds)
+            with th.no_grad():
+                sampled = self.draw_samples(means.detach(), log_stds.detach().exp())
+                if fused:
+                    baselines, _, q = coma_baseline(net, z1.detach(), actions, sampled, want_values=values is None)
+                    q = values.detach() if values is not None else q
+                else:
+                    nets = net if args.shared_params else self.value_dicts
+                    baselines, _ = coma_baseline_torch(nets, state, actions, sampled, args.agent_id)
+                    q = values.detach() if values is not None else self.value(state, actions).view(-1, n)
+                advantages = None
+                if args.normalize_advantages:
+                    advantages = self.batchnorm(q - baselines)
+            policy_loss, terms["log_prob_a"] = coma_policy_loss(means, log_stds, actions, actions_avail, q, baselines,
+                                                                advantages, fused=fused)
+            terms.update(sampled=sampled, baselines=baselines, values=q)
+        if need in ("both", "value"):
+            with th.no_grad():
+                # double_q: the next actions from the behaviour policy (coma.py:133-136), valued by the target critic
+                _, next_actions, _, _, _ = self.get_actions(next_state, status="train", exploration=False,
+                                                            actions_avail=actions_avail, target=not args.double_q,
+                                                            last_hid=hids)
+                tgt = self.target_net if args.target else self
+                next_values = tgt.value(next_state, next_actions).view(-1, n)
+            returns = rewards + args.gamma * (1 - done) * next_values
+            assert returns.size() == values.size()
+            value_loss = mean_all((returns - values).pow(2))
+            terms.update(values=values.detach(), next_values=next_values, returns=returns)
+        self.last_terms = terms          # (tests and tools read the intermediates of the last call)
+        return policy_loss, value_loss, action_out

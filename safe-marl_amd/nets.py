@@ -1933,3 +1933,184 @@ def ppo_value_loss(values, old_values, next_values, reward_norm, done, gamma, ep
         note_fallback("ppo_value_loss", f"agents {n}, dtype {values.dtype}")
     loss, returns = ppo_value_loss_torch(values2, old_values, next_values, reward_norm, done, gamma, eps_clip, value_loss_coef)
     return loss, returns.detach()
+
+
+# ---- COMA (madrl/models/coma.py:126-189): the counterfactual baseline and the policy loss -----------------------------------
+# The baseline as the launch of csrc/coma.hip on the GPU (from the first-layer pre-activation of the rows on the actions
+# taken: no [s b n, width] input exists) and as the reference's materialising composition everywhere else (CPU, fp64,
+# configurations the kernel does not cover); the composition is also what the GPU tests compare the kernel with.
+_COMA_WS = {}
+
+
+def coma_rows(obs, act, agent_id=True, per_row=False):
+    """coma.py:41-78 (continuous branch): the critic's input rows [.., n, (n + 1) o + n + n a] =
+    [o_1 .. o_n | o_i | onehot(i) | actions].  ``obs`` [b, n, o]; ``act`` [b, n, a] (every row of a sample sees the same n
+    actions) or, with ``per_row``, [m b, n, n a] (row-specific actions, the observations repeated m times: the baseline's
+    merged actions)."""
+    b, n, o = obs.shape
+    m = act.size(0) // b
+    parts = [obs.reshape(b, 1, n * o).expand(b, n, n * o), obs]
+    if agent_id:
+        parts.append(th.eye(n, device=obs.device, dtype=obs.dtype).expand(b, n, n))
+    inp = th.cat(parts, dim=-1)
+    if per_row:
+        inp = inp.unsqueeze(0).expand(m, b, n, inp.size(-1)).reshape(m * b, n, -1)
+        acts = act.reshape(m * b, n, -1)
+    else:
+        acts = act.reshape(b, 1, -1).expand(b, n, act[0].numel())
+    return th.cat((inp, acts), dim=-1)
+
+
+def coma_merged_actions(act, sampled):
+    """coma.py:142-147: [s b, n, n a] — row (s, b, i) holds the actions taken with agent i's own replaced by its draw."""
+    s, b, n, a = sampled.shape
+    mask = th.eye(n, device=act.device, dtype=act.dtype).view(1, 1, n, n, 1)
+    merged = act.view(1, b, 1, n, a) * (1.0 - mask) + sampled.view(s, b, 1, n, a) * mask
+    return merged.reshape(s * b, n, n * a)
+
+
+def coma_baseline_torch(critics, obs, act, sampled, agent_id=True, s_chunk=None):
+    """(baseline [b, n], q_sampled [s, b, n]) of coma.py:139-149 as the reference forms them: the [s b n, width] rows are
+    materialised and handed to the critic (``critics``: the shared MLPCritic, or one per agent).  ``s_chunk``: that many
+    draws at a time (the full set is 23 GB at the trainer's batch)."""
+    s, b, n, _ = sampled.shape
+    out = []
+    step = s if s_chunk is None else int(s_chunk)
+    for s0 in range(0, s, step):
+        rows = coma_rows(obs, coma_merged_actions(act, sampled[s0:s0 + step]), agent_id, per_row=True)
+        if isinstance(critics, nn.Module) and not isinstance(critics, nn.ModuleList):
+            v = critics(rows.reshape(-1, rows.size(-1)), None)[0]
+        else:
+            v = th.stack([net(rows[:, i, :], None)[0] for i, net in enumerate(critics)], dim=1)
+        out.append(v.reshape(-1, b, n))
+    q_sampled = th.cat(out, dim=0)
+    return q_sampled.mean(dim=0), q_sampled
+
+
+def coma_fused_config(critic, n_agents, act_dim):
+    """The configuration csrc/coma.hip implements (sqddpg_fused_config's): a shared MLPCritic with hid 64, ReLU and one
+    output, the agent id columns, n <= 8 agents, act_dim <= 8 with n * act_dim <= 32."""
+    return sqddpg_fused_config(critic, n_agents, act_dim, 1)
+
+
+def coma_act_columns(critic, n_agents, act_dim):
+    """The action columns [64, n a] of fc1.weight in COMA's row layout (the last n a columns)."""
+    return critic.fc1.weight[:, critic.fc1.in_features - n_agents * act_dim:]
+
+
+def coma_baseline(critic, z1, act, sampled, want_q=False, want_values=False, fused=True):
+    """(baseline [b, n], q_sampled [s, b, n] or None, values [b, n] or None), no gradient, from ``z1`` [b n, hid] — fc1's
+    pre-activation of the rows on the actions taken: row (s, b, i) is the tail of z1[b, i] + W_act,i (sampled[s, b, i] -
+    act[b, i]).  ``values`` is the tail of z1 itself.  On the GPU one launch of csrc/coma.hip; otherwise (and with
+    ``fused=False``) the same update as tensor operations."""
+    s, b, n, a = sampled.shape
+    with th.no_grad():
+        w_act = coma_act_columns(critic, n, a)
+        *tail, eps = _tail_params(critic)
+        if fused and z1.is_cuda:
+            if z1.dtype == th.float32 and sampled.dtype == th.float32 and coma_fused_config(critic, n, a):
+                z1c, actc, smp, wa = z1.contiguous(), act.to(th.float32).contiguous(), sampled.contiguous(), w_act.contiguous()
+                ps = [None if p is None else p.detach().contiguous() for p in tail]
+                base = th.empty(b, n, dtype=th.float32, device=z1.device)
+                qs = th.empty(s, b, n, dtype=th.float32, device=z1.device) if want_q else None
+                q = th.empty(b, n, dtype=th.float32, device=z1.device) if want_values else None
+                k = _lib.FlexComaBaselineArgs()
+                k.batch, k.n_agents, k.act_dim, k.sample_size = b, n, a, s
+                k.layernorm, k.ln_eps = int(ps[0] is not None), float(eps)
+                k.z1, k.w_act, k.act, k.sampled = z1c.data_ptr(), wa.data_ptr(), actc.data_ptr(), smp.data_ptr()
+                if ps[0] is not None:
+                    k.ln_w, k.ln_b = ps[0].data_ptr(), ps[1].data_ptr()
+                k.fc2_w, k.fc2_b, k.fc3_w, k.fc3_b = (p.data_ptr() for p in ps[2:])
+                k.baseline = base.data_ptr()
+                if qs is not None:
+                    k.q_sampled = qs.data_ptr()
+                if q is not None:
+                    k.q = q.data_ptr()
+                if _lib.try_launch("flexnet_coma_baseline", k):
+                    return base, qs, q
+            note_fallback("coma", f"hid {critic.args.hid_size}, act {critic.args.hid_activation}, agent_id "
+                                  f"{critic.args.agent_id}, agents {n}, act_dim {a}, dtype {z1.dtype}")
+        delta = (sampled - act.unsqueeze(0)).to(z1.dtype)                                   # [s, b, n, a]
+        z = z1.view(1, b, n, -1) + th.einsum("sbia,hia->sbih", delta, w_act.reshape(-1, n, a))
+        qs = critic.forward_from_hidden(z.reshape(s * b * n, -1), need_hidden=False)[0].reshape(s, b, n)
+        q = critic.forward_from_hidden(z1, need_hidden=False)[0].reshape(b, n) if want_values else None
+        return qs.mean(dim=0), (qs if want_q else None), q
+
+
+def coma_policy_loss_torch(means, log_stds, actions, actions_avail, advantages):
+    """coma.py:132,183-188: (loss, log_prob_a [b, n] after the mask and the sum over the action dimension)."""
+    from torch.distributions.normal import Normal
+    log_prob_a = Normal(means, log_stds.exp(), validate_args=False).log_prob(actions)
+    if actions_avail is not None and getattr(actions_avail, "_flex_const", None) != 1.0:
+        log_prob_a = (1.0 - (actions_avail == 0).to(means.dtype)) * log_prob_a
+    log_prob_a = log_prob_a.sum(dim=-1)
+    assert log_prob_a.size() == advantages.size()
+    return (-advantages.detach() * log_prob_a).mean(), log_prob_a
+
+
+class _ComaLossFn(th.autograd.Function):
+    """The policy loss of csrc/coma.hip: its gradients w.r.t. the means and the log-stds came out of the forward launch."""
+
+    @staticmethod
+    def forward(ctx, means, log_stds, loss, d_means, d_log_stds):
+        ctx.save_for_backward(d_means, d_log_stds)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        d_means, d_log_stds = ctx.saved_tensors
+        from .util import is_unit_seed
+        unit = is_unit_seed(g)
+        dl = None
+        if ctx.needs_input_grad[1]:
+            dl = d_log_stds if unit else d_log_stds * g
+        return (d_means if unit else d_means * g), dl, None, None, None
+
+
+def coma_policy_loss(means, log_stds, actions, actions_avail, values=None, baseline=None, advantages=None, fused=True):
+    """(loss, log_prob_a [b, n] detached) of coma.py:180-188: -mean(adv log p) with adv = ``advantages`` when given (the
+    normalised ones), else ``values`` - ``baseline``; nothing but the means and the log-stds takes a gradient."""
+    rows, n, na = means.shape
+    every = actions_avail is None or getattr(actions_avail, "_flex_const", None) == 1.0
+    uniform = getattr(log_stds, "_flex_entropy", None) is not None
+    given = [t for t in (values, baseline, advantages) if t is not None]
+    if (fused and means.is_cuda and n <= 8 and na <= 8 and actions.shape == means.shape
+            and all(t.is_cuda and t.dtype == th.float32 for t in [means, actions, log_stds] + given)
+            and (every or (actions_avail.is_cuda and actions_avail.shape == means.shape))):
+        with th.no_grad():
+            m, act = means.detach().contiguous(), actions.contiguous()
+            ls = log_stds.detach() if uniform else log_stds.detach().expand_as(m).contiguous()
+            loss = th.empty((), dtype=th.float32, device=m.device)
+            d_means = th.empty_like(m)
+            want_dl = log_stds.requires_grad and not uniform
+            d_log_stds = th.empty_like(m) if want_dl else m.new_empty(0)
+            logp = th.empty(rows, n, dtype=th.float32, device=m.device)
+            key = (m.device, th.cuda.current_stream(m.device).cuda_stream)
+            if key not in _COMA_WS:
+                _COMA_WS[key] = th.empty(_lib.FLEXNET_COMA_WS_FLOATS // 2, dtype=th.float64, device=m.device)
+            ws = _COMA_WS[key]
+            k = _lib.FlexComaPolicyArgs()
+            k.rows, k.n_agents, k.act_dim, k.log_std_uniform = rows, n, na, int(uniform)
+            k.means, k.log_stds, k.actions = m.data_ptr(), ls.data_ptr(), act.data_ptr()
+            keep = []
+            if not every:
+                keep.append(actions_avail.to(th.float32).contiguous())
+                k.avail = keep[-1].data_ptr()
+            if advantages is not None:
+                keep.append(advantages.detach().reshape(rows, n).contiguous())
+                k.advantages = keep[-1].data_ptr()
+            else:
+                keep += [values.detach().reshape(rows, n).contiguous(), baseline.detach().reshape(rows, n).contiguous()]
+                k.q, k.baseline = keep[-2].data_ptr(), keep[-1].data_ptr()
+            k.loss, k.d_means, k.log_prob = loss.data_ptr(), d_means.data_ptr(), logp.data_ptr()
+            if want_dl:
+                k.d_log_stds = d_log_stds.data_ptr()
+            k.workspace, k.workspace_floats = ws.data_ptr(), 2 * ws.numel()
+            ran = _lib.try_launch("flexnet_coma_policy_loss", k)
+        if ran:
+            return _ComaLossFn.apply(means, log_stds, loss, d_means, d_log_stds), logp
+    if fused and means.is_cuda:
+        note_fallback("coma_policy_loss", f"agents {n}, act_dim {na}, dtype {means.dtype}")
+    adv = advantages if advantages is not None else values - baseline
+    loss, logp = coma_policy_loss_torch(means, log_stds, actions, actions_avail, adv.reshape(rows, n))
+    return loss, logp.detach()
