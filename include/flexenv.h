@@ -190,7 +190,9 @@ int flexenv_step(FlexEnv* env, const void* actions, int32_t act_dtype,
  * `steps` calls of flexenv_step with the same flags.  get_obs() is the row push: FLEX_STEP_OBS_ROWS is required
  * (FLEX_STEP_AUTORESET optional), FLEX_EINVAL otherwise and while a row ring is registered (flexenv_set_obs_ring: the
  * closed-loop forms own its cursor).  Environments are independent, so a wavefront walks its own environments through the
- * whole sequence without a launch boundary per step.  FLEX_STEP_MANY_NO_CARRY (diagnostic): every step re-loads its integer
+ * whole sequence without a launch boundary per step.  All `act_period` slabs must be readable whatever `steps` is: the kernel
+ * requests the slab after the one a step uses ahead of that step's solve (slab (k + 1) mod act_period, slab 0 before the first
+ * step), also where no later step consumes it.  FLEX_STEP_MANY_NO_CARRY (diagnostic): every step re-loads its integer
  * record from memory instead of carrying it in registers. */
 #define FLEX_STEP_MANY_NO_CARRY 32
 int flexenv_step_many(FlexEnv* env, const void* actions, int32_t act_dtype, int32_t act_period, int32_t steps,

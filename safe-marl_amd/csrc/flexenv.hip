@@ -76,6 +76,17 @@ struct FlexEnv {
 #define FLEX_STAMP(slot) do { } while (0)
 #define FLEX_STAMP_RT(slot) do { } while (0)
 #endif
+// Diagnostic build only (-DFLEX_MANY_STAMPS, tools/many_stamps.py): segments of a step of flex_step_many_kernel's loop.  These
+// stamps do NOT drain the vector-memory counter (FLEX_STAMP's s_waitcnt vmcnt(0) would serialise exactly the overlaps the
+// loop is built for): each adds the cycles since the stamp before it into a wavefront-uniform (scalar) sum, and lane 0 stores
+// the sums after the loop.  Segment s ends at FLEX_MANY_STAMP(s): 0 loop top -> solve, 1 solve, 2 epilogue, 3 fence.
+#ifdef FLEX_MANY_STAMPS
+#define FLEX_MANY_STAMP(mcp, seg) do { unsigned long long _t; __builtin_amdgcn_sched_barrier(0); \
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(_t) :: "memory"); __builtin_amdgcn_sched_barrier(0); \
+    const uint32_t _n = (uint32_t)_t; if ((seg) >= 0) (mcp)->st_acc[(seg) < 0 ? 0 : (seg)] += _n - (mcp)->st_prev; (mcp)->st_prev = _n; } while (0)
+#else
+#define FLEX_MANY_STAMP(mcp, seg) do { } while (0)
+#endif
 
 struct KArgs {
     unsigned long long* stamps;
@@ -539,10 +550,29 @@ void flex_reset_kernel(KArgs a, const uint8_t* __restrict__ mask, DevResetSpec i
 #ifndef FLEX_MANY_CARRY_NET
 #define FLEX_MANY_CARRY_NET 1
 #endif
+// What the loop of flex_step_many_kernel waits for (each can be built out with -D...=0 for an A/B):
+// FLEX_MANY_PREFETCH_ACT: the actions are an argument of the launch, so step k requests step k+1's slab before its own solve and
+//   hands it over in StepCarry — a step's prologue then waits for nothing from memory while the carry holds.
+// FLEX_MANY_EARLY_HEAD: the launch's first step requests its integer record (the head of the ienv -> series row chain) before
+//   the 19 loads of the network rows, not behind them.
+#ifndef FLEX_MANY_PREFETCH_ACT
+#define FLEX_MANY_PREFETCH_ACT 1
+#endif
+#ifndef FLEX_MANY_EARLY_HEAD
+#define FLEX_MANY_EARLY_HEAD 1
+#endif
 struct StepCarry {
     flex_v4i iv;                 // steps, start, row, pushes: the 16 bytes the step wrote to ienv
     bool have;                   // wavefront-uniform: everything below is current
+    bool have_iv;                // wavefront-uniform: `iv` is current although the rest is not (the launch's first step)
     LaneNet ln;
+    // FLEX_MANY_PREFETCH_ACT: this step's actions, requested by the step before (by the kernel for the first step); the
+    // actions are never written by the launch, so they hold whatever `have` says
+    float4 af;
+    double2 ad0, ad1;
+#ifdef FLEX_MANY_STAMPS
+    uint32_t st_prev, st_acc[4]; // diagnostic build: the last stamp and the cycles of the four segments of a step, summed
+#endif
     // the lane's inputs of the NEXT step, as that step would load them: its bus's cells of the series row the step advanced to
     // (read by every lane for get_obs() anyway: env:340 / env:377-382), the ESS state, the warm-start word, the running return
     double pd, qd, ppv, price, e_cur, e_init, cum;
@@ -553,7 +583,7 @@ __device__ __forceinline__ void flex_step_body(const KArgs& a, const int wave, c
                                                double* __restrict__ reward, uint8_t* __restrict__ done, double* __restrict__ info,
                                                uint8_t* __restrict__ failed, ObsT* __restrict__ obs, int want_obs, int auto_reset,
                                                const int64_t slab, const bool cells, const unsigned long long kbase,
-                                               StepCarry* mc = nullptr) {
+                                               StepCarry* mc = nullptr, const ActT* __restrict__ next_actions = nullptr) {
     constexpr int LW = FLEX_WAVE / EPW;
     const int lane = threadIdx.x & 63;
     const int env0 = wave * EPW;                               // first environment of this wavefront
@@ -582,7 +612,7 @@ __device__ __forceinline__ void flex_step_body(const KArgs& a, const int wave, c
     int4 iv;                                                      // steps, start, row, obs_cnt in one load
     LaneNet ln;
     if constexpr (MANY) {
-        if (mc->have) iv = int4{mc->iv.x, mc->iv.y, mc->iv.z, mc->iv.w};
+        if (mc->have || mc->have_iv) iv = int4{mc->iv.x, mc->iv.y, mc->iv.z, mc->iv.w};
         else iv = ld_at<int4>(b_ienv, o_ienv);
 #if FLEX_MANY_CARRY_NET
         ln = mc->ln;
@@ -620,7 +650,11 @@ __device__ __forceinline__ void flex_step_body(const KArgs& a, const int wave, c
     const bool from_regs = MANY && mc->have;
     const uint32_t o_act = (g * na + ag) * (4 * (uint32_t)sizeof(ActT));
     ActT av[4];
-    if constexpr (sizeof(ActT) == 4) {
+    if constexpr (MANY && FLEX_MANY_PREFETCH_ACT) {
+        // (requested underneath the step before: nothing here waits for memory while the carry holds)
+        if constexpr (sizeof(ActT) == 4) { av[0] = mc->af.x; av[1] = mc->af.y; av[2] = mc->af.z; av[3] = mc->af.w; }
+        else { av[0] = mc->ad0.x; av[1] = mc->ad0.y; av[2] = mc->ad1.x; av[3] = mc->ad1.y; }
+    } else if constexpr (sizeof(ActT) == 4) {
         const float4 t = ld_at<float4>(b_act, o_act);
         av[0] = t.x; av[1] = t.y; av[2] = t.z; av[3] = t.w;
     } else {
@@ -651,6 +685,14 @@ __device__ __forceinline__ void flex_step_body(const KArgs& a, const int wave, c
     // (only building lanes use the next row's Pd / Qd / Ppv: every other lane reads the price cell instead — an address this
     //  wavefront fetches anyway — so the observation touches 5 + 5 + 2 sectors of the next row, not all 18)
     // (MANY: every lane reads its OWN bus's cells — they are its inputs of the launch's next step, StepCarry)
+    if constexpr (MANY && FLEX_MANY_PREFETCH_ACT) {
+        // the NEXT step's actions (the caller hands in a slab that exists: the sequence wraps at its period): they land underneath
+        // the solve.  Unconditional per lane, like every load of the prologue, and AHEAD of the next row's cells: loads return
+        // in order, so the epilogue's wait for those cells also covers these, and the next step's prologue waits for nothing.
+        const ActT* const b_nact = next_actions + (int64_t)env0 * (na * 4);
+        if constexpr (sizeof(ActT) == 4) mc->af = ld_at<float4>(b_nact, o_act);
+        else { mc->ad0 = ld_at<double2>(b_nact, o_act); mc->ad1 = ld_at<double2>(b_nact, o_act + 16); }
+    }
     double n_pd = ld_at<double>(a.series, nrow_off + (is_bld || MANY ? o_bus : o_price));
     double n_qd = ld_at<double>(a.series, nrow_off + (is_bld || MANY ? o_qbus : o_price));
     double n_ppv = ld_at<double>(a.series, nrow_off + (is_bld || MANY ? o_pv : o_price));
@@ -697,11 +739,17 @@ __device__ __forceinline__ void flex_step_body(const KArgs& a, const int wave, c
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
     FLEX_STAMP(1);
+#ifdef FLEX_MANY_STAMPS
+    if constexpr (MANY) { asm volatile("" :: "v"(pnet), "v"(qnet), "v"(e), "v"(f)); FLEX_MANY_STAMP(mc, 0); }
+#endif
     bool ok = pf_solve<EPW>(a.net, ln, c.solver, pnet, qnet, e, f, c.pf_tol, c.pf_max_iter, iters, sweeps);
 #ifdef FLEX_STAMPS
     asm volatile("" :: "v"(e), "v"(f));
 #endif
     FLEX_STAMP(2);
+#ifdef FLEX_MANY_STAMPS
+    if constexpr (MANY) { asm volatile("" :: "v"(e), "v"(f)); FLEX_MANY_STAMP(mc, 1); }
+#endif
 
     // the epilogue re-reads its configuration and rebuilds its bases from fresh kernarg loads (see relaunder_kernarg)
     const KArgs& z = *relaunder_kernarg<KArgs>(kbase);
@@ -779,6 +827,7 @@ __device__ __forceinline__ void flex_step_body(const KArgs& a, const int wave, c
         // (a restart rewrites all of this in memory behind here: the next step of the launch then loads it)
         mc->iv = flex_v4i{new_steps, start, new_row, cnt_after};
         mc->have = !(auto_reset && __ballot(restart) != 0ull);
+        mc->have_iv = false;
         mc->pd = n_pd; mc->qd = n_qd; mc->ppv = n_ppv; mc->price = n_price;
         mc->e_cur = e_new; mc->e_init = e_init_r; mc->cum = cum_before + rwd;
         mc->vw = (ok && ln.bus >= 0) ? pack_warm(e, f) : vw_word;        // (the spare group of an odd batch mirrors environment 0)
@@ -904,26 +953,82 @@ void flex_step_many_kernel(ManyArgs m) {
     if (wave * EPW >= m.k.n_envs) return;
     StepCarry mc;
     mc.have = false;
+    mc.have_iv = false;
     mc.iv = flex_v4i{0, 0, 0, 0};
-    load_lane_net<EPW>(m.k.net, threadIdx.x & 63, mc.ln);
+    const int lane = threadIdx.x & 63;
+#if FLEX_MANY_EARLY_HEAD || FLEX_MANY_PREFETCH_ACT
+    constexpr int LW = FLEX_WAVE / EPW;
+    const int g0 = wave * EPW + lane / LW < m.k.n_envs ? lane / LW : 0;          // (flex_step_body's `g`)
+#endif
+#if FLEX_MANY_EARLY_HEAD
+    // the first step's integer record — the head of the only two-level chain (ienv -> series row) — goes out before the 19
+    // table loads, as in flex_step_body for the one-step kernel: loads return in order
+    mc.iv = ld_at<flex_v4i>(m.k.st.ienv + (int64_t)wave * EPW * IF_COUNT, g0 * (IF_COUNT * 4));
+    mc.have_iv = true;
+#endif
+#if FLEX_MANY_PREFETCH_ACT
+    // ... and the row the first step's action address hangs on (load_lane_net reads it again: one load, same line)
+    const int agent0 = m.k.net->agent_of_lane[lane & (LW - 1)];
+#endif
+    load_lane_net<EPW>(m.k.net, lane, mc.ln);
+#if FLEX_MANY_PREFETCH_ACT
+    {   // the first step's actions (slab 0), as flex_step_body requests every later step's
+        const int na = m.k.cfg.n_agents;
+        const ActT* const b_act = reinterpret_cast<const ActT*>(m.actions) + (int64_t)wave * EPW * (na * 4);
+        const uint32_t o_act = (g0 * na + (agent0 >= 0 ? agent0 : 0)) * (4 * (uint32_t)sizeof(ActT));
+        if constexpr (sizeof(ActT) == 4) mc.af = ld_at<float4>(b_act, o_act);
+        else { mc.ad0 = ld_at<double2>(b_act, o_act); mc.ad1 = ld_at<double2>(b_act, o_act + 16); }
+    }
+#endif
+#ifdef FLEX_MANY_STAMPS
+    mc.st_acc[0] = mc.st_acc[1] = mc.st_acc[2] = mc.st_acc[3] = 0;
+    uint32_t st_first[4] = {0, 0, 0, 0};
+    FLEX_MANY_STAMP(&mc, -1);
+    const uint32_t st_begin = mc.st_prev;
+#endif
     const int n_steps = m.n_steps;
+    const bool carry = m.carry != 0;            // (one bit, kept like n_steps: a scalar load and its wait less at every loop top)
     int slot = 0;
     for (int k = 0; k < n_steps; ++k) {
         // (every step reads its arguments through a freshly derived kernarg pointer, as the step body's epilogue does:
         //  nothing of them is carried — spilled — across the solve)
         const ManyArgs& b = *relaunder_kernarg<ManyArgs>(kb);
         const int64_t ne = b.k.n_envs;
-        const ActT* act = reinterpret_cast<const ActT*>(b.actions) + (int64_t)slot * ne * (b.k.cfg.n_agents * 4);
-        if (!b.carry) mc.have = false;
+        const int64_t slab_elems = ne * (b.k.cfg.n_agents * 4);
+        const ActT* act = reinterpret_cast<const ActT*>(b.actions) + (int64_t)slot * slab_elems;
+        slot = slot + 1 == b.act_period ? 0 : slot + 1;
+        // (the slab after this one; behind the launch's last step it is a slab of the period all the same: a valid address,
+        //  a load nobody uses)
+        const ActT* act_next = reinterpret_cast<const ActT*>(b.actions) + (int64_t)slot * slab_elems;
+        if (!carry) mc.have = false;
         flex_step_body<EPW, float, ActT, FLEX_OBS_AGENTS_SMALL, false, true, true>(
             b.k, wave, act, b.reward + k * ne, b.done + k * ne, b.info ? b.info + k * ne * FLEX_INFO_W : nullptr,
-            b.failed ? b.failed + k * ne : nullptr, nullptr, 1, b.auto_reset, -1, false, kb, &mc);
-        slot = slot + 1 == b.act_period ? 0 : slot + 1;
+            b.failed ? b.failed + k * ne : nullptr, nullptr, 1, b.auto_reset, -1, false, kb, &mc, act_next);
+        FLEX_MANY_STAMP(&mc, 2);
         // this wavefront's own stores (state, history; a restart's) are what its next step loads: complete and visible
         // within the CU before those loads go out (work-group scope: one vector L1, write-through)
+        // (about 90 of a step's 14.7 k cycles in the stamp build; making the pair conditional on what the next step loads
+        //  measured nothing — DESIGN §4.2a — so it stays unconditional)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        FLEX_MANY_STAMP(&mc, 3);
+#ifdef FLEX_MANY_STAMPS
+        if (k == 0) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { st_first[i] = mc.st_acc[i]; mc.st_acc[i] = 0; }
+        }
+#endif
     }
+#ifdef FLEX_MANY_STAMPS
+    // slots 0-3: the segments of step 0; 4-7: their sums over steps 1 .. n-1; 8: n_steps; 9: cycles of the whole loop
+    if (m.k.stamps && lane == 0) {
+        unsigned long long* const o = m.k.stamps + (int64_t)wave * EPW * 16;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { o[i] = st_first[i]; o[4 + i] = mc.st_acc[i]; }
+        o[8] = (unsigned long long)n_steps;
+        o[9] = mc.st_prev - st_begin;
+    }
+#endif
     if (blockIdx.x == 0 && threadIdx.x == 0) {                 // the launch counter, as n_steps single launches leave it
         const ManyArgs& b = *relaunder_kernarg<ManyArgs>(kb);
         int64_t* const sc = b.k.step_counter;
