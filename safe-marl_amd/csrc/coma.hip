@@ -10,13 +10,15 @@
 // update is act_dim / 2 steps of v_mfma_f32_32x32x2_f32 per 32 units (A = the block's columns, B = the rows' differences,
 // C = z1) against the 64 steps of fc2.  z1, the block's columns and fc2's weights (64 registers per lane: the whole
 // matrix over the wavefront) stay in registers while the wavefront walks its rows through the s draws; LayerNorm's
-// parameters, fc2's bias and fc3 sit in LDS.  The tail is critic_mfma.h's transposed scheme, as in sqddpg.hip.  Lane
+// parameters, fc2's bias and fc3 sit in LDS.  The tail is flex_mfma_tile.h's transposed scheme, as in sqddpg.hip.  Lane
 // (row, half 0) sums its row's values over s = 0, 1, .. in that order: no atomics, bit-reproducible.  Forward only — the
 // baseline enters the loss detached (coma.py:180).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "flexnet.h"
-#include "critic_mfma.h"
+#include "flex_launch.h"
+#include "flex_mfma_tile.h"
+#include "flex_reduce.h"
 
 #define CM_THREADS 256
 #define CM_BLOCKS FLEXNET_COMA_BLOCKS
@@ -48,8 +50,8 @@ __global__ __launch_bounds__(64) void coma_baseline_kernel(FlexComaBaselineArgs 
     s_w3[lane] = a.fc3_w[lane];
 
     // resident: z1 of the row, fc2 as the A operand, the agent's action block of W_act, the action taken
-    sv16 z[2];
-    sv4 w2[2][2][4];
+    tv16 z[2];
+    tv4 w2[2][2][4];
     float wa[2][4], own[4];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
@@ -57,7 +59,7 @@ __global__ __launch_bounds__(64) void coma_baseline_kernel(FlexComaBaselineArgs 
         const float* wr = a.fc2_w + (32 * t + i) * SH + 4 * h;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const sv4 u = ld4(zp + 8 * q);
+            const tv4 u = ld4(zp + 8 * q);
 #pragma unroll
             for (int j = 0; j < 4; ++j) z[t][4 * q + j] = u[j];
             w2[t][0][q] = ld4(wr + 8 * q);
@@ -83,13 +85,13 @@ __global__ __launch_bounds__(64) void coma_baseline_kernel(FlexComaBaselineArgs 
     float acc = 0.0f;
     for (int s = first; s < ns; ++s) {
         if (s + 1 < ns) cm_load_delta(a, s + 1, row, h, own, dn);          // in flight behind this pass's arithmetic
-        sv16 zs[2] = {z[0], z[1]};
+        tv16 zs[2] = {z[0], z[1]};
         if (s >= 0) {
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
                 if (2 * kk < ad) {
-                    zs[0] = SQMFMA(wa[0][kk], d[kk], zs[0]);
-                    zs[1] = SQMFMA(wa[1][kk], d[kk], zs[1]);
+                    zs[0] = TILE_MFMA(wa[0][kk], d[kk], zs[0]);
+                    zs[1] = TILE_MFMA(wa[1][kk], d[kk], zs[1]);
                 }
             }
         }
@@ -99,7 +101,7 @@ __global__ __launch_bounds__(64) void coma_baseline_kernel(FlexComaBaselineArgs 
         for (int t = 0; t < 2; ++t) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const sv4 g = ld4(s_lnw + 32 * t + 8 * q + 4 * h), be = ld4(s_lnb + 32 * t + 8 * q + 4 * h);
+                const tv4 g = ld4(s_lnw + 32 * t + 8 * q + 4 * h), be = ld4(s_lnb + 32 * t + 8 * q + 4 * h);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const float v = zs[t][4 * q + j];
@@ -108,15 +110,15 @@ __global__ __launch_bounds__(64) void coma_baseline_kernel(FlexComaBaselineArgs 
                 }
             }
         }
-        sv16 z2[2] = {bias_tile(s_b2, h), bias_tile(s_b2 + 32, h)};
+        tv16 z2[2] = {bias_tile(s_b2, h), bias_tile(s_b2 + 32, h)};
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    z2[0] = SQMFMA(w2[0][kt][q][j], zs[kt][4 * q + j], z2[0]);
-                    z2[1] = SQMFMA(w2[1][kt][q][j], zs[kt][4 * q + j], z2[1]);
+                    z2[0] = TILE_MFMA(w2[0][kt][q][j], zs[kt][4 * q + j], z2[0]);
+                    z2[1] = TILE_MFMA(w2[1][kt][q][j], zs[kt][4 * q + j], z2[1]);
                 }
             }
         }
@@ -124,7 +126,7 @@ __global__ __launch_bounds__(64) void coma_baseline_kernel(FlexComaBaselineArgs 
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
 #pragma unroll
-            for (int r2 = 0; r2 < 16; ++r2) p += s_w3[32 * t + SU(r2, h)] * fmaxf(z2[t][r2], 0.0f);
+            for (int r2 = 0; r2 < 16; ++r2) p += s_w3[32 * t + TILE_U(r2, h)] * fmaxf(z2[t][r2], 0.0f);
         }
         const float q = (p + other_half(p)) + b3;
         if (s >= 0) {
@@ -141,7 +143,6 @@ __global__ __launch_bounds__(64) void coma_baseline_kernel(FlexComaBaselineArgs 
 
 // ---- policy loss: one thread per (sample, agent), per-block partial sums (fp64, fixed tree), a one-wavefront finish ------
 __global__ __launch_bounds__(CM_THREADS) void coma_policy_kernel(FlexComaPolicyArgs a) {
-    __shared__ double red[CM_THREADS];
     const int na = a.act_dim, tid = threadIdx.x;
     const int64_t total = a.rows * a.n_agents;
     const float inv = 1.0f / (float)total;
@@ -164,27 +165,14 @@ __global__ __launch_bounds__(CM_THREADS) void coma_policy_kernel(FlexComaPolicyA
         if (a.log_prob) a.log_prob[r] = logp;
         acc += (double)(adv * logp);
     }
-    red[tid] = acc;
-    __syncthreads();
-    for (int sft = CM_THREADS / 2; sft > 0; sft >>= 1) {
-        if (tid < sft) red[tid] += red[tid + sft];
-        __syncthreads();
-    }
-    if (tid == 0) reinterpret_cast<double*>(a.workspace)[blockIdx.x] = red[0];
+    flex_block_sum_f64<CM_THREADS>(acc, reinterpret_cast<double*>(a.workspace));
 }
 
 __global__ __launch_bounds__(64) void coma_loss_finish_kernel(const double* partial, double scale, float* loss) {
-    const int lane = threadIdx.x;
-    double t = 0.0;
-    for (int b = lane; b < CM_BLOCKS; b += 64) t += partial[b];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
-    if (lane == 0) *loss = (float)(t * scale);
+    flex_loss_finish(partial, CM_BLOCKS, scale, loss);
 }
 
 // ---- entry points -----------------------------------------------------------------------------------------------------
-static inline bool cm_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 extern "C" int flexnet_coma_baseline(const FlexComaBaselineArgs* a, void* stream) {
     if (!a || a->batch < 0 || !a->z1 || !a->w_act || !a->act || !a->sampled || !a->fc2_w || !a->fc2_b || !a->fc3_w ||
         !a->fc3_b || !a->baseline)
@@ -193,22 +181,22 @@ extern "C" int flexnet_coma_baseline(const FlexComaBaselineArgs* a, void* stream
     if (a->n_agents < 1 || a->n_agents > FLEXNET_MAX_AGENTS || a->act_dim < 1 || a->act_dim > 8 ||
         a->n_agents * a->act_dim > 32 || a->sample_size < 1 || a->batch * a->n_agents > (int64_t)INT32_MAX)
         return FLEXNET_EUNSUPPORTED;
-    if (!cm_al16(a->z1) || !cm_al16(a->fc2_w)) return FLEXNET_EUNSUPPORTED;
+    if (!flex_aligned(a->z1, 16) || !flex_aligned(a->fc2_w, 16)) return FLEXNET_EUNSUPPORTED;
     if (a->batch == 0) return FLEXNET_OK;
     const int64_t tiles = (a->batch + 31) / 32 * a->n_agents;
     hipLaunchKernelGGL(coma_baseline_kernel, dim3((unsigned)tiles), dim3(64), 0, (hipStream_t)stream, *a);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }
 
 extern "C" int flexnet_coma_policy_loss(const FlexComaPolicyArgs* a, void* stream) {
     if (!a || a->rows < 1 || a->n_agents < 1 || a->act_dim < 1 || !a->means || !a->log_stds || !a->actions ||
         (!a->advantages && (!a->q || !a->baseline)) || !a->loss || !a->d_means || !a->workspace ||
-        a->workspace_floats < FLEXNET_COMA_WS_FLOATS || (reinterpret_cast<uintptr_t>(a->workspace) & 7) != 0)
+        a->workspace_floats < FLEXNET_COMA_WS_FLOATS || !flex_aligned(a->workspace, 8))
         return FLEXNET_EINVAL;
     if (a->n_agents > FLEXNET_MAX_AGENTS || a->act_dim > FLEXNET_MAX_ACT) return FLEXNET_EUNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(coma_policy_kernel, dim3(CM_BLOCKS), dim3(CM_THREADS), 0, s, *a);
     hipLaunchKernelGGL(coma_loss_finish_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<const double*>(a->workspace),
                        -1.0 / ((double)a->rows * a->n_agents), a->loss);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }

@@ -1292,7 +1292,7 @@ static int critic_dz_fold(const FlexCriticTailArgs& k, hipStream_t stream) {
     if ((int64_t)blocks * DZF_PITCH > k.workspace_floats) return FLEXNET_EINVAL;
     hipLaunchKernelGGL(critic_dz_fold_kernel, dim3(blocks), dim3(64 * DZF_W), 0, stream, k, (int64_t)0);
     hipLaunchKernelGGL(critic_dz_reduce_kernel, dim3(k.n_agents), dim3(64 * RED_G), 0, stream, k, blocks);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }
 
 // Everything that follows the two first-stage kernels of flexnet_critic_td_backward in ONE launch: the parameter gradients'
@@ -1337,12 +1337,12 @@ extern "C" int flexnet_critic_tail_forward(const FlexCriticTailArgs* a, void* st
         const int nb = critic_mfma_grid(a->rows);
         if (nb < 1) return FLEXNET_EHIP;
         hipLaunchKernelGGL(critic_tail_mfma_kernel<false>, dim3(nb), dim3(64 * CMW), 0, (hipStream_t)stream, *a);
-        return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+        return flex_launch_status();
     }
     const int blocks = critic_grid(a->rows, 8);
     if (blocks < 1) return FLEXNET_EHIP;
     hipLaunchKernelGGL(critic_tail_fwd_kernel, dim3(blocks), dim3(64 * CW), 0, (hipStream_t)stream, *a);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }
 
 static int critic_tail_backward_main(const FlexCriticTailArgs* a, void* stream);
@@ -1366,7 +1366,7 @@ extern "C" int flexnet_critic_tail_backward(const FlexCriticTailArgs* a, void* s
         FlexCriticTailArgs k = *a;
         k.workspace = a->workspace + (int64_t)nb * CRITIC_WS_PITCH;
         hipLaunchKernelGGL(critic_dz_reduce_kernel, dim3(k.n_agents), dim3(64 * RED_G), 0, (hipStream_t)stream, k, nb);
-        return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+        return flex_launch_status();
     }
     return critic_dz_fold(*a, (hipStream_t)stream);        // after the main launches: it reuses their workspace
 }
@@ -1376,7 +1376,7 @@ int critic_finish_prepare(const FlexCriticTailArgs* a, const FlexTdLossArgs* t, 
     const int rc = critic_check(a, true, false);
     if (rc != FLEXNET_OK) return rc;
     if (!t || t->rows < 1 || t->n_agents < 1 || !t->reward || !t->done || !t->next_q || !t->loss || !t->workspace ||
-        t->workspace_floats < FLEXNET_TD_WS_FLOATS || (reinterpret_cast<uintptr_t>(t->workspace) & 7) != 0)
+        t->workspace_floats < FLEXNET_TD_WS_FLOATS || !flex_aligned(t->workspace, 8))
         return FLEXNET_EINVAL;
     if ((int64_t)t->rows * t->n_agents != a->rows) return FLEXNET_EINVAL;
     if (t->n_agents > TD_NA) return FLEXNET_EUNSUPPORTED;
@@ -1426,7 +1426,7 @@ extern "C" int flexnet_critic_td_backward_phases(const FlexCriticTailArgs* a, co
     }
     if (phases & 2)
         hipLaunchKernelGGL(critic_td_finish_kernel, dim3(k.blocks), dim3(64 * RED_G), 0, s, k);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }
 
 extern "C" int flexnet_critic_td_backward(const FlexCriticTailArgs* a, const FlexTdLossArgs* t, void* stream) {
@@ -1439,7 +1439,7 @@ static int critic_tail_backward_main(const FlexCriticTailArgs* a, void* stream) 
         const int nb = critic_mfma_grid(k.rows);
         if (nb < 1) return FLEXNET_EHIP;
         if (k.q_mean_out && (!k.workspace || k.workspace_floats < 2 * (int64_t)nb ||
-                             (reinterpret_cast<uintptr_t>(k.workspace) & 7) != 0)) return FLEXNET_EINVAL;
+                             !flex_aligned(k.workspace, 8))) return FLEXNET_EINVAL;
         if (k.dq_uniform != (k.q_mean_out != nullptr)) return FLEXNET_EUNSUPPORTED;      // (the two come together)
         if (k.q_mean_out) {
             hipLaunchKernelGGL((critic_tail_mfma_kernel<true, true>), dim3(nb), dim3(64 * CMW), 0, (hipStream_t)stream, k);
@@ -1447,14 +1447,14 @@ static int critic_tail_backward_main(const FlexCriticTailArgs* a, void* stream) 
         } else {
             hipLaunchKernelGGL(critic_tail_mfma_kernel<true>, dim3(nb), dim3(64 * CMW), 0, (hipStream_t)stream, k);
         }
-        return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+        return flex_launch_status();
     }
     if (k.dq_uniform || k.q_mean_out) return FLEXNET_EUNSUPPORTED;       // the matrix-core dz1-only backward's extras
     if (!k.d_fc2_w) {
         const int nb = critic_grid(k.rows, 4);
         if (nb < 1) return FLEXNET_EHIP;
         hipLaunchKernelGGL(critic_tail_bwd_kernel<false>, dim3(nb), dim3(64 * CW), 0, (hipStream_t)stream, k);
-        return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+        return flex_launch_status();
     }
     const bool two_stage = k.workspace && k.workspace_floats >= FLEXNET_CRITIC_WS_FLOATS;
     if (k.overwrite_grads && !two_stage) return FLEXNET_EINVAL;
@@ -1469,7 +1469,7 @@ static int critic_tail_backward_main(const FlexCriticTailArgs* a, void* stream) 
         else
             critic_launch_pgrad16<false>(nb, sm, k, FlexTdLossArgs{}, dz_off, (hipStream_t)stream);
         hipLaunchKernelGGL(critic_reduce_kernel, dim3((HID * HID + 4 * HID + 1 + 63) / 64), dim3(64 * RED_G), 0, (hipStream_t)stream, k, nb);
-        return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+        return flex_launch_status();
     }
     if (!two_stage) k.workspace = nullptr;
     // deterministic path: up to 1024 blocks of partial sums; atomic path: one block per CU (each ends with 4 k atomics)
@@ -1478,5 +1478,5 @@ static int critic_tail_backward_main(const FlexCriticTailArgs* a, void* stream) 
     hipLaunchKernelGGL(critic_tail_bwd_kernel<true>, dim3(blocks), dim3(64 * CW), 0, (hipStream_t)stream, k);
     if (two_stage)
         hipLaunchKernelGGL(critic_reduce_kernel, dim3((HID * HID + 4 * HID + 1 + 63) / 64), dim3(64 * RED_G), 0, (hipStream_t)stream, k, blocks);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }

@@ -1,7 +1,15 @@
-// flex_launch.h — host-side helper shared by the learner kernels' entry points, and the wavefront sum they share.
+// flex_launch.h — host-side helpers shared by the learner kernels' entry points, and the wavefront sum they share.
 #ifndef FLEX_LAUNCH_H
 #define FLEX_LAUNCH_H
 #include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "flexnet.h"
+
+// `p` is a multiple of `bytes` (a power of two): 16 for what the kernels read with 16-byte loads, 8 for workspaces of doubles
+static inline bool flex_aligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+
+// what an entry point returns after its launches
+static inline int flex_launch_status() { return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP; }
 
 // Compute units of the current device (one process drives one GPU: cached after the first query); -1 on a HIP error.
 static inline int flex_cu_count() {

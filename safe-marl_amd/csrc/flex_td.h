@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "flexnet.h"
+#include "flex_reduce.h"
 
 #define TD_THREADS 256
 #define TD_BLOCKS 64
@@ -43,10 +44,7 @@ __device__ __forceinline__ void td_column_affine(const FlexTdLossArgs& a, int j,
 // mode) moves them: momentum weighting, unbiased variance, num_batches_tracked += 1.
 __device__ __forceinline__ void td_finish(const FlexTdLossArgs& a, int sq_blocks, int lane) {
     const double* ws = reinterpret_cast<const double*>(a.workspace);
-    double t = 0.0;
-    for (int b = lane; b < sq_blocks; b += 64) t += ws[TD_WS_SQ + b];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
+    const double t = flex_partials_sum_f64(ws + TD_WS_SQ, sq_blocks, lane);
     if (lane == 0) {
         if (a.loss) *a.loss = (float)(t / ((double)a.rows * a.n_agents));
         if (a.normalise && a.num_batches_tracked) *a.num_batches_tracked += 1;

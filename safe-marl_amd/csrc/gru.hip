@@ -342,7 +342,7 @@ static int gru_backward_fused(const FlexGruBwdArgs* a, hipStream_t s) {
     if (a->act_dim <= 4) hipLaunchKernelGGL(gru_backward_fused_kernel<4>, dim3(blocks), dim3(64 * GF_W), 0, s, *a);
     else hipLaunchKernelGGL(gru_backward_fused_kernel<FLEXNET_MAX_ACT>, dim3(blocks), dim3(64 * GF_W), 0, s, *a);
     hipLaunchKernelGGL(gru_fused_reduce_kernel, dim3(GF_VECS), dim3(64 * FLEX_RED_G), 0, s, *a, blocks);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }
 
 extern "C" int flexnet_gru_backward(const FlexGruBwdArgs* a, void* stream) {
@@ -356,5 +356,5 @@ extern "C" int flexnet_gru_backward(const FlexGruBwdArgs* a, void* stream) {
     int64_t blocks = (passes + GRU_THREADS / 64 - 1) / (GRU_THREADS / 64);
     if (blocks > 8192) blocks = 8192;                                         // grid-stride beyond 32 rows per CU slot
     hipLaunchKernelGGL(gru_backward_kernel, dim3((unsigned)blocks), dim3(GRU_THREADS), 0, (hipStream_t)stream, *a);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }

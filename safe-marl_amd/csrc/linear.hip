@@ -236,5 +236,5 @@ extern "C" int flexnet_linear2(const FlexLinear2Args* a, void* stream) {
         case 3: hipLaunchKernelGGL(linear2_wreg_kernel<3>, dim3(grid), dim3(64 * L2_WAVES), 0, s, p); break;
         default: return FLEXNET_EUNSUPPORTED;                  // more than 768 input columns: the weights no longer fit the registers of eight wavefronts
     }
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }

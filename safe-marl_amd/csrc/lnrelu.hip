@@ -163,7 +163,7 @@ extern "C" int flexnet_lnrelu_forward(const FlexLnReluArgs* a, void* stream) {
     const int blocks = lnrelu_grid(a->rows, 8, 1 << 20);
     if (blocks < 1) return FLEXNET_EHIP;
     hipLaunchKernelGGL(lnrelu_fwd_kernel, dim3(blocks), dim3(64 * LW), 0, (hipStream_t)stream, *a);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }
 
 extern "C" int flexnet_lnrelu_backward(const FlexLnReluArgs* a, void* stream) {
@@ -176,5 +176,5 @@ extern "C" int flexnet_lnrelu_backward(const FlexLnReluArgs* a, void* stream) {
     }
     hipLaunchKernelGGL(lnrelu_bwd_kernel, dim3(blocks), dim3(64 * LW), 0, (hipStream_t)stream, *a);
     hipLaunchKernelGGL(lnrelu_reduce_kernel, dim3(LN_VECS), dim3(64 * LRED), 0, (hipStream_t)stream, *a, blocks);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "flexnet.h"
+#include "flex_launch.h"
 #include "window_refresh.h"
 
 #define OPT_THREADS 256
@@ -167,7 +168,7 @@ static int clip_rmsprop_run(const FlexClipRmspropArgs* a, const WindowRider* r, 
         hipLaunchKernelGGL(clip_norm_kernel<false>, dim3(OPT_BLOCKS), dim3(OPT_THREADS), 0, s, *a, a->workspace, none);
         hipLaunchKernelGGL(clip_rmsprop_kernel<false>, dim3(OPT_BLOCKS), dim3(OPT_THREADS), 0, s, *a, a->workspace, none);
     }
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }
 
 extern "C" int flexnet_clip_rmsprop(const FlexClipRmspropArgs* a, void* stream) { return clip_rmsprop_run(a, nullptr, stream); }

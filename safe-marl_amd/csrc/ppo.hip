@@ -21,6 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "flexnet.h"
+#include "flex_launch.h"
+#include "flex_reduce.h"
 #include "flex_td.h"
 
 #define PPO_THREADS 256
@@ -138,7 +140,7 @@ static bool ppo_bn_ok(const FlexPpoBatchNorm& bn) {
 extern "C" int flexnet_ppo_gae(const FlexPpoGaeArgs* a, void* stream) {
     if (!a || a->rows < 1 || a->n_agents < 1 || a->chain_stride < 1 || !a->reward || !a->old_values || !a->old_next_values ||
         !a->done || !a->last_step || !a->reward_norm || !a->advantages || !a->workspace ||
-        a->workspace_floats < FLEXNET_PPO_WS_FLOATS || (reinterpret_cast<uintptr_t>(a->workspace) & 7) != 0 ||
+        a->workspace_floats < FLEXNET_PPO_WS_FLOATS || !flex_aligned(a->workspace, 8) ||
         (a->adv_bn.enabled && !a->advantages_norm) || !ppo_bn_ok(a->reward_bn) || !ppo_bn_ok(a->adv_bn))
         return FLEXNET_EINVAL;
     if (a->n_agents > TD_NA || a->rows > (int64_t)INT32_MAX / TD_NA) return FLEXNET_EUNSUPPORTED;
@@ -159,7 +161,7 @@ extern "C" int flexnet_ppo_gae(const FlexPpoGaeArgs* a, void* stream) {
         if (blocks > 1024) blocks = 1024;
         hipLaunchKernelGGL(ppo_gae_finish_kernel, dim3((unsigned)blocks), dim3(PPO_THREADS), 0, s, *a);
     }
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }
 
 
@@ -169,25 +171,8 @@ __device__ __forceinline__ float ppo_maxf(float a, float b) { return (a > b || a
 __device__ __forceinline__ float ppo_clampf(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
 
 // ---- the two losses: one thread per row, per-block partial sums (fp64, fixed tree), a one-wavefront finish ---------------
-__device__ __forceinline__ void ppo_block_sum(double v, double* partial) {
-    __shared__ double red[PPO_THREADS];
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int sft = PPO_THREADS / 2; sft > 0; sft >>= 1) {
-        if (tid < sft) red[tid] += red[tid + sft];
-        __syncthreads();
-    }
-    if (tid == 0) partial[blockIdx.x] = red[0];
-}
-
 __global__ __launch_bounds__(64) void ppo_loss_finish_kernel(const double* partial, double scale, float* loss) {
-    const int lane = threadIdx.x;
-    double t = 0.0;
-    for (int b = lane; b < PPO_BLOCKS; b += 64) t += partial[b];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
-    if (lane == 0) *loss = (float)(t * scale);
+    flex_loss_finish(partial, PPO_BLOCKS, scale, loss);
 }
 
 __global__ __launch_bounds__(PPO_THREADS) void ppo_policy_kernel(FlexPpoPolicyArgs a) {
@@ -248,20 +233,20 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_policy_kernel(FlexPpoPolicyAr
             for (int k = 0; k < FLEXNET_MAX_ACT; ++k)
                 if (k < na) dp[i * na + k] = g[k];                     // the sum over agents hands it to every agent
     }
-    ppo_block_sum(acc, reinterpret_cast<double*>(a.workspace) + PPO_WS_LOSS);
+    flex_block_sum_f64<PPO_THREADS>(acc, reinterpret_cast<double*>(a.workspace) + PPO_WS_LOSS);
 }
 
 extern "C" int flexnet_ppo_policy_loss(const FlexPpoPolicyArgs* a, void* stream) {
     if (!a || a->rows < 1 || a->n_agents < 1 || a->act_dim < 1 || !a->means || !a->log_std || !a->actions || !a->advantages ||
         !a->loss || !a->d_means || !a->workspace || a->workspace_floats < FLEXNET_PPO_WS_FLOATS ||
-        (reinterpret_cast<uintptr_t>(a->workspace) & 7) != 0)
+        !flex_aligned(a->workspace, 8))
         return FLEXNET_EINVAL;
     if (a->n_agents > FLEXNET_MAX_AGENTS || a->act_dim > FLEXNET_MAX_ACT) return FLEXNET_EUNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(ppo_policy_kernel, dim3(PPO_BLOCKS), dim3(PPO_THREADS), 0, s, *a);
     hipLaunchKernelGGL(ppo_loss_finish_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<const double*>(a->workspace) + PPO_WS_LOSS,
                        -1.0 / ((double)a->rows * a->n_agents), a->loss);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }
 
 __global__ __launch_bounds__(PPO_THREADS) void ppo_value_kernel(FlexPpoValueArgs a) {
@@ -285,18 +270,18 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_value_kernel(FlexPpoValueArgs
         a.d_values[idx] = c2 * (w1 * e1 + w2 * e2);
         if (a.returns) a.returns[idx] = ret;
     }
-    ppo_block_sum(acc, reinterpret_cast<double*>(a.workspace) + PPO_WS_LOSS);
+    flex_block_sum_f64<PPO_THREADS>(acc, reinterpret_cast<double*>(a.workspace) + PPO_WS_LOSS);
 }
 
 extern "C" int flexnet_ppo_value_loss(const FlexPpoValueArgs* a, void* stream) {
     if (!a || a->rows < 1 || a->n_agents < 1 || !a->values || !a->old_values || !a->next_values || !a->reward_norm || !a->done ||
         !a->loss || !a->d_values || !a->workspace || a->workspace_floats < FLEXNET_PPO_WS_FLOATS ||
-        (reinterpret_cast<uintptr_t>(a->workspace) & 7) != 0)
+        !flex_aligned(a->workspace, 8))
         return FLEXNET_EINVAL;
     if (a->n_agents > FLEXNET_MAX_AGENTS) return FLEXNET_EUNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(ppo_value_kernel, dim3(PPO_BLOCKS), dim3(PPO_THREADS), 0, s, *a);
     hipLaunchKernelGGL(ppo_loss_finish_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<const double*>(a->workspace) + PPO_WS_LOSS,
                        (double)a->value_loss_coef / ((double)a->rows * a->n_agents), a->loss);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }

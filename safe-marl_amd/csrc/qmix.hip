@@ -7,10 +7,10 @@
 //     w1 = |Ww1_2 h1[0:64] + b| (64 n), wf = |Wwf_2 h1[64:128] + b| (64), v = WV_2 h1[192:256] + b
 //     hidden[e] = elu(sum_i q_i w1[i, e] + h1[128 + e]);  q_tot = sum_e hidden[e] wf[e] + v
 //
-// One wavefront owns 32 samples end to end.  Every layer is evaluated transposed on v_mfma_f32_32x32x2_f32 (exact fp32):
-// A = weights (rows = output units), B = activations (columns = the wavefront's 32 samples), so lane (sample s, half h)
-// ends a layer holding units 8 q + 4 h + j of its sample in accumulator register 4 q + j — exactly what the next layer's
-// B operand wants when MFMA step (q, j) takes the k-pair (8 q + j, 8 q + 4 + j) (the scheme of actor.hip / critic.hip).
+// One wavefront owns 32 samples end to end.  Every layer is evaluated in flex_mfma_tile.h's transposed scheme on
+// v_mfma_f32_32x32x2_f32 (exact fp32): A = weights (rows = output units), B = activations (columns = the wavefront's 32
+// samples), so lane (sample s, half h) ends a layer holding units 8 q + 4 h + j of its sample in accumulator register
+// 4 q + j — exactly what the next layer's B operand wants.
 // The first layer reads the state rows and the weight rows with one 16-byte load per lane and group of eight inputs;
 // the weights (4 x 64 x S floats, 737 KB at S = 720) are shared by every wavefront and served from L2 / L1.  The
 // per-sample hypernetwork outputs w1 [64 n] and wf [64] never leave the registers: the mixing is done on the
@@ -24,70 +24,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "flexnet.h"
-
-typedef float qv16 __attribute__((ext_vector_type(16)));
-typedef float qv4 __attribute__((ext_vector_type(4)));
+#include "flex_launch.h"
+#include "flex_mfma_tile.h"
 
 #define QM_WAVES 4                                   // wavefronts per block: 128 samples
 #define QM_E FLEXNET_QMIX_EMBED                      // 64
-#define QMFMA(a_, b_, c_) __builtin_amdgcn_mfma_f32_32x32x2f32((a_), (b_), (c_), 0, 0, 0)
-#define QU(r, h) (8 * ((r) >> 2) + 4 * (h) + ((r) & 3))     // unit of accumulator register r in lane half h
 
-__device__ __forceinline__ qv4 ld4(const float* p) { return *reinterpret_cast<const qv4*>(p); }
-__device__ __forceinline__ void st4(float* p, qv4 v) { *reinterpret_cast<qv4*>(p) = v; }
 __device__ __forceinline__ float sgnf(float x) { return x > 0.0f ? 1.0f : (x < 0.0f ? -1.0f : 0.0f); }  // torch.sign
-__device__ __forceinline__ float other_half(float v) { return __shfl_xor(v, 32, 64); }
-
-// accumulators start from the bias of their units (NULL: zero)
-__device__ __forceinline__ qv16 bias_tile(const float* b, int h) {
-    qv16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = b ? b[QU(r, h)] : 0.0f;
-    return acc;
-}
-
-// out[o][s] = bias + sum_k W[o][k] in[k][s] for the 32 outputs o = obase + lane row and k over 64 inputs held as two
-// tiles of accumulator layout (in0: inputs 0..31, in1: 32..63).  `wrow` = W + (obase + i) * 64 + 4 h.
-__device__ __forceinline__ qv16 second_layer_tile(const float* wrow, qv16 acc, const qv16& in0, const qv16& in1) {
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const qv4 w = ld4(wrow + 32 * kt + 8 * q);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc = QMFMA(w[j], kt ? in1[4 * q + j] : in0[4 * q + j], acc);
-        }
-    }
-    return acc;
-}
-
-// The transposed product: acc[k][s] += sum_o W[o][k] d[o][s] for k = kbase + lane row and o over the 32 outputs of the
-// tile `d` (accumulator layout).  `wcol` = W + obase * ld + kbase + i.
-__device__ __forceinline__ qv16 transposed_tile(const float* wcol, int ld, int h, qv16 acc, const qv16& d) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = QMFMA(wcol[(8 * q + 4 * h + j) * ld], d[4 * q + j], acc);
-    }
-    return acc;
-}
-
-__device__ __forceinline__ void store_tile(float* row, const qv16& t, bool ok) {      // row = base + unit offset + 4 h
-    if (!ok) return;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) st4(row + 8 * q, qv4{t[4 * q], t[4 * q + 1], t[4 * q + 2], t[4 * q + 3]});
-}
-
-__device__ __forceinline__ qv16 load_tile(const float* row) {
-    qv16 t;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const qv4 v = ld4(row + 8 * q);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) t[4 * q + j] = v[j];
-    }
-    return t;
-}
 
 // ---- forward ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64 * QM_WAVES, 1) void qmix_forward_kernel(FlexQmixArgs a) {
@@ -103,28 +46,28 @@ __global__ __launch_bounds__(64 * QM_WAVES, 1) void qmix_forward_kernel(FlexQmix
     // first layer: four S -> 64 heads as one S -> 256 product; tile t = head t / 2, units 32 (t & 1) .. + 31
     const float* wm[4] = {a.w1_0_w, a.wf_0_w, a.b1_w, a.v_0_w};
     const float* bm[4] = {a.w1_0_b, a.wf_0_b, a.b1_b, a.v_0_b};
-    qv16 acc[8];
+    tv16 acc[8];
     const float* wr[8];
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
-        acc[t] = bias_tile(bm[t >> 1] + 32 * (t & 1), h);
+        acc[t] = bias_tile_or_zero(bm[t >> 1] + 32 * (t & 1), h);
         wr[t] = wm[t >> 1] + (int64_t)(32 * (t & 1) + i) * S + 4 * h;
     }
     const float* xr = a.state + row * a.ld_state + 4 * h;
-    qv4 xb = ld4(xr), wb[8];
+    tv4 xb = ld4(xr), wb[8];
 #pragma unroll
     for (int t = 0; t < 8; ++t) wb[t] = ld4(wr[t]);
     for (int k0 = 0; k0 < S; k0 += 8) {
         // next group's operands in flight while this group's 32 MFMAs issue
         const int kn = k0 + 8 < S ? k0 + 8 : k0;
-        const qv4 xn = ld4(xr + kn);
-        qv4 wn[8];
+        const tv4 xn = ld4(xr + kn);
+        tv4 wn[8];
 #pragma unroll
         for (int t = 0; t < 8; ++t) wn[t] = ld4(wr[t] + kn);
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[t] = QMFMA(wb[t][j], xb[j], acc[t]);
+            for (int j = 0; j < 4; ++j) acc[t] = TILE_MFMA(wb[t][j], xb[j], acc[t]);
         }
         xb = xn;
 #pragma unroll
@@ -144,14 +87,14 @@ __global__ __launch_bounds__(64 * QM_WAVES, 1) void qmix_forward_kernel(FlexQmix
     }
 
     // mixing: sum_i q_i |w1[i, e]| over the agents in order, then + b1, elu
-    qv16 hs[2];
+    tv16 hs[2];
 #pragma unroll
     for (int eh = 0; eh < 2; ++eh) {
-        hs[eh] = qv16{};
+        hs[eh] = tv16{};
         for (int ag = 0; ag < n; ++ag) {
             const float qa = a.agent_qs[row * n + ag];
             const int ob = ag * QM_E + 32 * eh;
-            const qv16 w = second_layer_tile(a.w1_2_w + (int64_t)(ob + i) * QM_E + 4 * h, bias_tile(a.w1_2_b + ob, h),
+            const tv16 w = layer_tile(a.w1_2_w + (int64_t)(ob + i) * QM_E + 4 * h, bias_tile_or_zero(a.w1_2_b + ob, h),
                                              acc[0], acc[1]);
 #pragma unroll
             for (int r = 0; r < 16; ++r) hs[eh][r] += qa * fabsf(w[r]);
@@ -160,7 +103,7 @@ __global__ __launch_bounds__(64 * QM_WAVES, 1) void qmix_forward_kernel(FlexQmix
     float part = 0.0f;
 #pragma unroll
     for (int eh = 0; eh < 2; ++eh) {
-        const qv16 wf = second_layer_tile(a.wf_2_w + (32 * eh + i) * QM_E + 4 * h, bias_tile(a.wf_2_b + 32 * eh, h),
+        const tv16 wf = layer_tile(a.wf_2_w + (32 * eh + i) * QM_E + 4 * h, bias_tile_or_zero(a.wf_2_b + 32 * eh, h),
                                           acc[2], acc[3]);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -173,7 +116,7 @@ __global__ __launch_bounds__(64 * QM_WAVES, 1) void qmix_forward_kernel(FlexQmix
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) vp += a.v_2_w[32 * t + QU(r, h)] * acc[6 + t][r];
+        for (int r = 0; r < 16; ++r) vp += a.v_2_w[32 * t + TILE_U(r, h)] * acc[6 + t][r];
     }
     const float part_o = other_half(part), vp_o = other_half(vp);
     if (h == 0 && ok) a.q_tot[smp] = (part + part_o) + ((vp + vp_o) + a.v_2_b[0]);
@@ -191,27 +134,27 @@ __global__ __launch_bounds__(64 * QM_WAVES, 1) void qmix_backward_kernel(FlexQmi
     const int n = a.n_agents;
     const bool pg = a.want_param_grads != 0;
     const float* hr = a.h1 + row * (4 * QM_E) + 4 * h;
-    const qv16 h0 = load_tile(hr), h1t = load_tile(hr + 32);
-    const qv16 h2 = load_tile(hr + 64), h3 = load_tile(hr + 96);
+    const tv16 h0 = load_tile(hr), h1t = load_tile(hr + 32);
+    const tv16 h2 = load_tile(hr + 64), h3 = load_tile(hr + 96);
     const float g = a.d_q_tot[row];
 
     // re-formed forward: wf (pre-abs) and the mixing's pre-activation
-    qv16 wf[2], dh[2];
+    tv16 wf[2], dh[2];
 #pragma unroll
     for (int eh = 0; eh < 2; ++eh)
-        wf[eh] = second_layer_tile(a.wf_2_w + (32 * eh + i) * QM_E + 4 * h, bias_tile(a.wf_2_b + 32 * eh, h), h2, h3);
+        wf[eh] = layer_tile(a.wf_2_w + (32 * eh + i) * QM_E + 4 * h, bias_tile_or_zero(a.wf_2_b + 32 * eh, h), h2, h3);
 #pragma unroll
     for (int eh = 0; eh < 2; ++eh) {
-        qv16 hs = qv16{};
+        tv16 hs = tv16{};
         for (int ag = 0; ag < n; ++ag) {
             const float qa = a.agent_qs[row * n + ag];
             const int ob = ag * QM_E + 32 * eh;
-            const qv16 w = second_layer_tile(a.w1_2_w + (int64_t)(ob + i) * QM_E + 4 * h, bias_tile(a.w1_2_b + ob, h), h0, h1t);
+            const tv16 w = layer_tile(a.w1_2_w + (int64_t)(ob + i) * QM_E + 4 * h, bias_tile_or_zero(a.w1_2_b + ob, h), h0, h1t);
 #pragma unroll
             for (int r = 0; r < 16; ++r) hs[r] += qa * fabsf(w[r]);
         }
-        const qv16 b1 = load_tile(hr + 128 + 32 * eh);
-        qv16 dwf;
+        const tv16 b1 = load_tile(hr + 128 + 32 * eh);
+        tv16 dwf;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const float x = hs[r] + b1[r];
@@ -230,15 +173,15 @@ __global__ __launch_bounds__(64 * QM_WAVES, 1) void qmix_backward_kernel(FlexQmi
     }
 
     // d agent_qs, d(w1 pre-abs) and its input gradient into h1[0:64]
-    qv16 dx0 = qv16{}, dx1 = qv16{};
+    tv16 dx0 = tv16{}, dx1 = tv16{};
     for (int ag = 0; ag < n; ++ag) {
         const float qa = a.agent_qs[row * n + ag];
         float dqp = 0.0f;
 #pragma unroll
         for (int eh = 0; eh < 2; ++eh) {
             const int ob = ag * QM_E + 32 * eh;
-            const qv16 w = second_layer_tile(a.w1_2_w + (int64_t)(ob + i) * QM_E + 4 * h, bias_tile(a.w1_2_b + ob, h), h0, h1t);
-            qv16 dw;
+            const tv16 w = layer_tile(a.w1_2_w + (int64_t)(ob + i) * QM_E + 4 * h, bias_tile_or_zero(a.w1_2_b + ob, h), h0, h1t);
+            tv16 dw;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 dqp += dh[eh][r] * fabsf(w[r]);
@@ -255,7 +198,7 @@ __global__ __launch_bounds__(64 * QM_WAVES, 1) void qmix_backward_kernel(FlexQmi
     }
     if (!pg) return;
     // ReLU masks; hyper_w_final's input gradient; V: d h1[192 + u] = g V2[u]
-    qv16 d2 = qv16{}, d3 = qv16{};
+    tv16 d2 = tv16{}, d3 = tv16{};
 #pragma unroll
     for (int eh = 0; eh < 2; ++eh) {
         d2 = transposed_tile(a.wf_2_w + (32 * eh) * QM_E + i, QM_E, h, d2, wf[eh]);
@@ -274,17 +217,15 @@ __global__ __launch_bounds__(64 * QM_WAVES, 1) void qmix_backward_kernel(FlexQmi
     store_tile(pr + 96, d3, ok);
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-        const qv16 hv = load_tile(hr + 192 + 32 * t);
-        qv16 dv;
+        const tv16 hv = load_tile(hr + 192 + 32 * t);
+        tv16 dv;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) dv[r] = hv[r] > 0.0f ? g * a.v_2_w[32 * t + QU(r, h)] : 0.0f;
+        for (int r = 0; r < 16; ++r) dv[r] = hv[r] > 0.0f ? g * a.v_2_w[32 * t + TILE_U(r, h)] : 0.0f;
         store_tile(pr + 192 + 32 * t, dv, ok);
     }
 }
 
 // ---- entry points -------------------------------------------------------------------------------------------------
-static inline bool qm_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // FLEXNET_EINVAL for missing tensors, FLEXNET_EUNSUPPORTED for shapes / layouts outside the kernel; both before any HIP call
 static int qmix_check(const FlexQmixArgs* a, bool backward) {
     if (!a || a->batch < 0) return FLEXNET_EINVAL;
@@ -299,12 +240,13 @@ static int qmix_check(const FlexQmixArgs* a, bool backward) {
     const int S = a->state_dim;
     if (a->n_agents < 1 || a->n_agents > FLEXNET_MAX_AGENTS || S < 16 || S > FLEXNET_QMIX_MAX_STATE || S % 16 != 0)
         return FLEXNET_EUNSUPPORTED;
-    if (!backward && (a->ld_state < S || a->ld_state % 4 != 0 || !qm_al16(a->state) || !qm_al16(a->w1_0_w) ||
-                      !qm_al16(a->wf_0_w) || !qm_al16(a->b1_w) || !qm_al16(a->v_0_w)))
+    if (!backward && (a->ld_state < S || a->ld_state % 4 != 0 || !flex_aligned(a->state, 16) || !flex_aligned(a->w1_0_w, 16) ||
+                      !flex_aligned(a->wf_0_w, 16) || !flex_aligned(a->b1_w, 16) || !flex_aligned(a->v_0_w, 16)))
         return FLEXNET_EUNSUPPORTED;
-    if (!qm_al16(a->w1_2_w) || !qm_al16(a->wf_2_w) || (a->h1 && !qm_al16(a->h1)))
+    if (!flex_aligned(a->w1_2_w, 16) || !flex_aligned(a->wf_2_w, 16) || (a->h1 && !flex_aligned(a->h1, 16)))
         return FLEXNET_EUNSUPPORTED;
-    if (backward && a->want_param_grads && (!qm_al16(a->d_w1) || !qm_al16(a->d_wf) || !qm_al16(a->d_pre1)))
+    if (backward && a->want_param_grads &&
+        (!flex_aligned(a->d_w1, 16) || !flex_aligned(a->d_wf, 16) || !flex_aligned(a->d_pre1, 16)))
         return FLEXNET_EUNSUPPORTED;
     return FLEXNET_OK;
 }
@@ -315,12 +257,12 @@ extern "C" int flexnet_qmix_forward(const FlexQmixArgs* a, void* stream) {
     const int rc = qmix_check(a, false);
     if (rc != FLEXNET_OK || a->batch == 0) return rc;
     hipLaunchKernelGGL(qmix_forward_kernel, dim3(qm_blocks(a->batch)), dim3(64 * QM_WAVES), 0, (hipStream_t)stream, *a);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }
 
 extern "C" int flexnet_qmix_backward(const FlexQmixArgs* a, void* stream) {
     const int rc = qmix_check(a, true);
     if (rc != FLEXNET_OK || a->batch == 0) return rc;
     hipLaunchKernelGGL(qmix_backward_kernel, dim3(qm_blocks(a->batch)), dim3(64 * QM_WAVES), 0, (hipStream_t)stream, *a);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }

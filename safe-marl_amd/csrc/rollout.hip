@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "flexnet.h"
+#include "flex_launch.h"
 #include "flex_td.h"
 #include "window_refresh.h"
 
@@ -146,7 +147,7 @@ extern "C" int flexnet_rollout_pack(const FlexRolloutPackArgs* a, void* stream) 
     const int blocks = (a->n_envs + PACK_ENVS - 1) / PACK_ENVS + PACK_STATS;
     hipLaunchKernelGGL(rollout_pack_kernel, dim3(blocks), dim3(PACK_THREADS), 0, (hipStream_t)stream, *a);
     if (!a->cursor_stepped) hipLaunchKernelGGL(rollout_cursor_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, a->cursor, a->slabs);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }
 
 // ---- replay-window refresh ------------------------------------------------------------------------------------------------
@@ -183,7 +184,7 @@ extern "C" int flexnet_agent_sum_explore(const FlexAgentSumArgs* a, void* stream
     const int64_t tot = (int64_t)a->n_envs * a->act_dim;
     if (tot > 0x7fffffff) return FLEXNET_EUNSUPPORTED;
     hipLaunchKernelGGL(agent_sum_explore_kernel, dim3((int)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *a);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }
 
 // ---- stacked observations of a replay window from the row ring (flexnet_gather_window) -------------------------------------
@@ -279,7 +280,7 @@ extern "C" int flexnet_gather_window(const FlexWindowArgs* a, void* stream) {
     if (bx > 0x7fffffffll || by > 65535) return FLEXNET_EUNSUPPORTED;
     if (a->history == 24) hipLaunchKernelGGL(gather_window_kernel<24>, dim3((unsigned)bx, (unsigned)by), dim3(WINDOW_THREADS), 0, (hipStream_t)stream, *a);
     else hipLaunchKernelGGL(gather_window_kernel<0>, dim3((unsigned)bx, (unsigned)by), dim3(WINDOW_THREADS), 0, (hipStream_t)stream, *a);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }
 
 #define GATHER_THREADS 256
@@ -366,7 +367,7 @@ static int gather_rows_run(const FlexGatherArgs* a, const GatherTd* t, void* str
         none.job = none.jobs = 0;                                // (never read without TD)
         hipLaunchKernelGGL(gather_rows_kernel<false>, dim3(blocks), dim3(GATHER_THREADS), 0, (hipStream_t)stream, *a, p, none);
     }
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }
 
 extern "C" int flexnet_gather_rows(const FlexGatherArgs* a, void* stream) { return gather_rows_run(a, nullptr, stream); }
@@ -380,7 +381,7 @@ extern "C" int flexnet_gather_rows_td(const FlexGatherArgs* a, int32_t reward_jo
     if (!a || !td || reward_jobs < 1 || reward_jobs > 2 || reward_job < 0 || reward_job + reward_jobs > a->n_jobs)
         return FLEXNET_EINVAL;
     if (td->rows < 1 || td->n_agents < 1 || td->n_agents > TD_NA || !td->workspace || td->workspace_floats < FLEXNET_TD_WS_FLOATS ||
-        (reinterpret_cast<uintptr_t>(td->workspace) & 7) != 0)
+        !flex_aligned(td->workspace, 8))
         return FLEXNET_EINVAL;
     int64_t rows = 0;
     for (int j = reward_job; j < reward_job + reward_jobs; ++j) {
@@ -412,5 +413,5 @@ extern "C" int flexnet_window_refresh(const FlexWindowRefreshArgs* a, const Flex
     hipStream_t s = (hipStream_t)stream;
     if (td) hipLaunchKernelGGL(window_refresh_kernel<true>, dim3(blocks + TD_BLOCKS), dim3(WINDOW_THREADS), 0, s, *a, p, *td);
     else hipLaunchKernelGGL(window_refresh_kernel<false>, dim3(blocks), dim3(WINDOW_THREADS), 0, s, *a, p, FlexTdLossArgs{});
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }

@@ -6,7 +6,7 @@
 //     z1 = z_shared[b] + z_id[i] + W_act x,     x[p a + k] = act[b, gc[g, p], k] for p <= pos[g, i], else 0
 // with z_shared = W_obs obs + b1 formed once per sample by the caller.  The kernel never materialises the 745-wide rows:
 // each row's z1 starts from z_shared + z_id and takes the coalition-masked action block (n a <= 32 columns) as up to 16
-// steps of v_mfma_f32_32x32x2_f32; LayerNorm, ReLU, fc2 (fp32 MFMA), ReLU and fc3 follow as in qmix.hip's transposed
+// steps of v_mfma_f32_32x32x2_f32; LayerNorm, ReLU, fc2 (fp32 MFMA), ReLU and fc3 follow in flex_mfma_tile.h's transposed
 // scheme (A = weights, B = the wavefront's 32 rows; lane (row i, half h) ends a layer holding units 8 q + 4 h + j).
 //
 // One wavefront (one work-group) owns a chunk of whole samples (`spc` of them, <= 64 / n and about 256 rows): it walks the
@@ -20,7 +20,8 @@
 #include <stdint.h>
 #include "flexnet.h"
 #include "flex_reduce.h"
-#include "critic_mfma.h"
+#include "flex_launch.h"
+#include "flex_mfma_tile.h"
 
 #define SQ_LP 68                                            // LDS row pitch (floats) of the [row][unit] stages
 #define SQ_XP 33                                            // LDS row pitch of the action stage [row][k]
@@ -36,16 +37,6 @@
 #define SQW_ID 4416                                         // d z_id [8][64]
 #define SQW_WA 4928                                         // dW_act [64][32]
 static_assert(SQW_WA + SH * SQ_MAXK == FLEXNET_SQDDPG_WS_ROW, "workspace row layout");
-
-// acc[k][s] += sum_o W[o][k] d[o][s] over the 32 outputs of tile d; wcol = W + obase * ld + kbase + i
-__device__ __forceinline__ sv16 transposed_tile(const float* wcol, int ld, int h, sv16 acc, const sv16& d) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = SQMFMA(wcol[(8 * q + 4 * h + j) * ld], d[4 * q + j], acc);
-    }
-    return acc;
-}
 
 struct SqRow {            // one row of the tile, as lane (i, h) sees it
     int64_t b;            // sample
@@ -81,7 +72,7 @@ __device__ __forceinline__ float sq_x(const FlexSqddpgArgs& a, const SqRow& r, i
     return a.act[(r.b * n + who) * ad + c];
 }
 
-struct SqFwd { sv16 z[2], xh[2], a1[2], z2[2]; float rstd; };
+struct SqFwd { tv16 z[2], xh[2], a1[2], z2[2]; float rstd; };
 
 // z1 -> LayerNorm -> ReLU -> fc2 of the lane's row; returns the pre-activation z2 (and what the backward needs)
 __device__ __forceinline__ void sq_forward_row(const FlexSqddpgArgs& a, const SqRow& r, int i, int h, float* xs, SqFwd& f) {
@@ -92,7 +83,7 @@ __device__ __forceinline__ void sq_forward_row(const FlexSqddpgArgs& a, const Sq
         const float* zi = a.z_id + r.ag * SH + 32 * t + 4 * h;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const sv4 u = ld4(zs + 8 * q), v = ld4(zi + 8 * q);
+            const tv4 u = ld4(zs + 8 * q), v = ld4(zi + 8 * q);
 #pragma unroll
             for (int j = 0; j < 4; ++j) f.z[t][4 * q + j] = u[j] + v[j];
         }
@@ -105,7 +96,7 @@ __device__ __forceinline__ void sq_forward_row(const FlexSqddpgArgs& a, const Sq
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             const float w = k < nka ? a.w_act[(32 * t + i) * nka + k] : 0.0f;
-            f.z[t] = SQMFMA(w, xv, f.z[t]);
+            f.z[t] = TILE_MFMA(w, xv, f.z[t]);
         }
     }
     float mean = 0.0f, rstd = 1.0f;
@@ -127,7 +118,7 @@ __device__ __forceinline__ void sq_forward_row(const FlexSqddpgArgs& a, const Sq
     for (int t = 0; t < 2; ++t) {
 #pragma unroll
         for (int r2 = 0; r2 < 16; ++r2) {
-            const int u = 32 * t + SU(r2, h);
+            const int u = 32 * t + TILE_U(r2, h);
             const float xh = a.layernorm ? (f.z[t][r2] - mean) * rstd : f.z[t][r2];
             const float y = a.layernorm ? xh * a.ln_w[u] + a.ln_b[u] : xh;
             f.xh[t][r2] = xh;
@@ -200,7 +191,7 @@ __global__ __launch_bounds__(64, 1) void sqddpg_forward_kernel(FlexSqddpgArgs a,
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
 #pragma unroll
-            for (int r2 = 0; r2 < 16; ++r2) p += a.fc3_w[32 * t + SU(r2, h)] * fmaxf(f.z2[t][r2], 0.0f);
+            for (int r2 = 0; r2 < 16; ++r2) p += a.fc3_w[32 * t + TILE_U(r2, h)] * fmaxf(f.z2[t][r2], 0.0f);
         }
         const float q = (p + other_half(p)) + a.fc3_b[0];
         if (h == 0) {
@@ -241,11 +232,11 @@ __global__ __launch_bounds__(64, 1) void sqddpg_backward_kernel(FlexSqddpgArgs a
     const int n = a.n_agents, ns = a.sample_size, R = ns * n, ad = a.act_dim, nka = n * ad;
     const bool pg = a.want_param_grads != 0;
     const float inv_ns = 1.0f / (float)ns;
-    sv16 dw2[4], dwa[2];
+    tv16 dw2[4], dwa[2];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) dw2[t] = sv16{};
-    dwa[0] = sv16{};
-    dwa[1] = sv16{};
+    for (int t = 0; t < 4; ++t) dw2[t] = tv16{};
+    dwa[0] = tv16{};
+    dwa[1] = tv16{};
     float c_b2 = 0.0f, c_w3 = 0.0f, c_g = 0.0f, c_be = 0.0f, c_b3 = 0.0f;   // lane = unit
     float c_id[FLEXNET_MAX_AGENTS];
 #pragma unroll
@@ -272,15 +263,15 @@ __global__ __launch_bounds__(64, 1) void sqddpg_backward_kernel(FlexSqddpgArgs a
                 if (a.d_q) dq += a.d_q[b0 * R + t0 + i];
             }
             // fc3, ReLU, fc2^T
-            sv16 dz2[2], da1[2];
+            tv16 dz2[2], da1[2];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
 #pragma unroll
                 for (int r2 = 0; r2 < 16; ++r2)
-                    dz2[t][r2] = f.z2[t][r2] > 0.0f ? dq * a.fc3_w[32 * t + SU(r2, h)] : 0.0f;
+                    dz2[t][r2] = f.z2[t][r2] > 0.0f ? dq * a.fc3_w[32 * t + TILE_U(r2, h)] : 0.0f;
             }
-            da1[0] = sv16{};
-            da1[1] = sv16{};
+            da1[0] = tv16{};
+            da1[1] = tv16{};
 #pragma unroll
             for (int ot = 0; ot < 2; ++ot) {
 #pragma unroll
@@ -292,7 +283,7 @@ __global__ __launch_bounds__(64, 1) void sqddpg_backward_kernel(FlexSqddpgArgs a
                 for (int t = 0; t < 2; ++t) {
 #pragma unroll
                     for (int r2 = 0; r2 < 16; ++r2) {
-                        const int u = 32 * t + SU(r2, h);
+                        const int u = 32 * t + TILE_U(r2, h);
                         s_a1[i * SQ_LP + u] = f.a1[t][r2];
                         s_dz2[i * SQ_LP + u] = dz2[t][r2];
                         s_dz1[i * SQ_LP + u] = dq * fmaxf(f.z2[t][r2], 0.0f);
@@ -306,7 +297,7 @@ __global__ __launch_bounds__(64, 1) void sqddpg_backward_kernel(FlexSqddpgArgs a
             for (int t = 0; t < 2; ++t) {
 #pragma unroll
                 for (int r2 = 0; r2 < 16; ++r2) {
-                    const int u = 32 * t + SU(r2, h);
+                    const int u = 32 * t + TILE_U(r2, h);
                     const float dy = f.a1[t][r2] > 0.0f ? da1[t][r2] : 0.0f;
                     da1[t][r2] = dy;
                     if (a.layernorm) {
@@ -331,7 +322,7 @@ __global__ __launch_bounds__(64, 1) void sqddpg_backward_kernel(FlexSqddpgArgs a
                         const float av = s_dz2[row * SQ_LP + 32 * ot + i];
 #pragma unroll
                         for (int kt = 0; kt < 2; ++kt)
-                            dw2[2 * ot + kt] = SQMFMA(av, s_a1[row * SQ_LP + 32 * kt + i], dw2[2 * ot + kt]);
+                            dw2[2 * ot + kt] = TILE_MFMA(av, s_a1[row * SQ_LP + 32 * kt + i], dw2[2 * ot + kt]);
                     }
                 }
                 for (int row = 0; row < 32; ++row) {
@@ -346,7 +337,7 @@ __global__ __launch_bounds__(64, 1) void sqddpg_backward_kernel(FlexSqddpgArgs a
             for (int t = 0; t < 2; ++t) {
 #pragma unroll
                 for (int r2 = 0; r2 < 16; ++r2) {
-                    const int u = 32 * t + SU(r2, h);
+                    const int u = 32 * t + TILE_U(r2, h);
                     const float dy = da1[t][r2];
                     float dz1 = dy;
                     if (a.layernorm) dz1 = f.rstd * (dy * a.ln_w[u] - m1 - f.xh[t][r2] * m2);
@@ -365,7 +356,7 @@ __global__ __launch_bounds__(64, 1) void sqddpg_backward_kernel(FlexSqddpgArgs a
                     const int row = 2 * st + h;
                     const float xv = i < nka ? s_x[row * SQ_XP + i] : 0.0f;
 #pragma unroll
-                    for (int ot = 0; ot < 2; ++ot) dwa[ot] = SQMFMA(s_dz1[row * SQ_LP + 32 * ot + i], xv, dwa[ot]);
+                    for (int ot = 0; ot < 2; ++ot) dwa[ot] = TILE_MFMA(s_dz1[row * SQ_LP + 32 * ot + i], xv, dwa[ot]);
                 }
             }
             for (int row = 0; row < 32; ++row) {           // lane = unit: the rows in order
@@ -428,10 +419,10 @@ __global__ __launch_bounds__(64, 1) void sqddpg_backward_kernel(FlexSqddpgArgs a
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
 #pragma unroll
-            for (int r2 = 0; r2 < 16; ++r2) w[SQW_W2 + (32 * ot + SU(r2, h)) * SH + 32 * kt + i] = dw2[2 * ot + kt][r2];
+            for (int r2 = 0; r2 < 16; ++r2) w[SQW_W2 + (32 * ot + TILE_U(r2, h)) * SH + 32 * kt + i] = dw2[2 * ot + kt][r2];
         }
 #pragma unroll
-        for (int r2 = 0; r2 < 16; ++r2) w[SQW_WA + (32 * ot + SU(r2, h)) * SQ_MAXK + i] = dwa[ot][r2];
+        for (int r2 = 0; r2 < 16; ++r2) w[SQW_WA + (32 * ot + TILE_U(r2, h)) * SQ_MAXK + i] = dwa[ot][r2];
     }
     w[SQW_B2 + lane] = c_b2;
     w[SQW_G + lane] = c_g;
@@ -462,8 +453,6 @@ __global__ __launch_bounds__(64 * FLEX_RED_G) void sqddpg_reduce_kernel(FlexSqdd
 }
 
 // ---- entry points -----------------------------------------------------------------------------------------------------
-static inline bool sq_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // samples per wavefront chunk: about 256 rows, at most 64 / n samples (one lane per (sample, agent))
 static inline int sq_spc(const FlexSqddpgArgs* a) {
     const int R = a->sample_size * a->n_agents;
@@ -485,7 +474,7 @@ static int sqddpg_check(const FlexSqddpgArgs* a, bool backward) {
     if (a->n_agents < 1 || a->n_agents > FLEXNET_MAX_AGENTS || a->act_dim < 1 || a->act_dim > 8 ||
         a->n_agents * a->act_dim > SQ_MAXK || a->sample_size < 1 || a->sample_size * a->n_agents > 4096)
         return FLEXNET_EUNSUPPORTED;
-    if (!sq_al16(a->z_shared) || !sq_al16(a->z_id) || !sq_al16(a->fc2_w)) return FLEXNET_EUNSUPPORTED;
+    if (!flex_aligned(a->z_shared, 16) || !flex_aligned(a->z_id, 16) || !flex_aligned(a->fc2_w, 16)) return FLEXNET_EUNSUPPORTED;
     return FLEXNET_OK;
 }
 
@@ -494,7 +483,7 @@ extern "C" int flexnet_sqddpg_draw(const FlexSqddpgDrawArgs* a, void* stream) {
     if (a->n_agents < 1 || a->n_agents > FLEXNET_MAX_AGENTS) return FLEXNET_EUNSUPPORTED;
     if (a->groups == 0) return FLEXNET_OK;
     hipLaunchKernelGGL(sqddpg_draw_kernel, dim3((unsigned)((a->groups + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *a);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }
 
 extern "C" int flexnet_sqddpg_forward(const FlexSqddpgArgs* a, void* stream) {
@@ -503,7 +492,7 @@ extern "C" int flexnet_sqddpg_forward(const FlexSqddpgArgs* a, void* stream) {
     const int spc = sq_spc(a);
     const int64_t chunks = (a->batch + spc - 1) / spc;
     hipLaunchKernelGGL(sqddpg_forward_kernel, dim3((unsigned)chunks), dim3(64), 0, (hipStream_t)stream, *a, spc);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }
 
 extern "C" int flexnet_sqddpg_backward(const FlexSqddpgArgs* a, void* stream) {

@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "flexnet.h"
+#include "flex_launch.h"
+#include "flex_reduce.h"
 #include "flex_td.h"
 
 __global__ __launch_bounds__(TD_THREADS) void td_stats_kernel(FlexTdLossArgs a) {
@@ -64,11 +66,11 @@ void flex_td_launch_finish(const FlexTdLossArgs& a, int sq_blocks, hipStream_t s
 
 extern "C" int flexnet_td_stats(const FlexTdLossArgs* a, void* stream) {
     if (!a || a->rows < 1 || a->n_agents < 1 || !a->reward || !a->workspace || a->workspace_floats < FLEXNET_TD_WS_FLOATS ||
-        (reinterpret_cast<uintptr_t>(a->workspace) & 7) != 0)
+        !flex_aligned(a->workspace, 8))
         return FLEXNET_EINVAL;
     if (a->n_agents > TD_NA) return FLEXNET_EUNSUPPORTED;
     flex_td_launch_stats(*a, (hipStream_t)stream);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }
 
 extern "C" int flexnet_td_loss(const FlexTdLossArgs* a, void* stream) {
@@ -80,33 +82,27 @@ extern "C" int flexnet_td_loss(const FlexTdLossArgs* a, void* stream) {
     if (stats_only && (!a->normalise || a->next_q || a->dq || a->loss)) return FLEXNET_EINVAL;
     if (!stats_only && (!a->done || !a->next_q || !a->dq || !a->loss)) return FLEXNET_EINVAL;
     if (a->n_agents > TD_NA) return FLEXNET_EUNSUPPORTED;
-    if ((reinterpret_cast<uintptr_t>(a->workspace) & 7) != 0) return FLEXNET_EINVAL;         // holds doubles
+    if (!flex_aligned(a->workspace, 8)) return FLEXNET_EINVAL;         // holds doubles
     hipStream_t s = (hipStream_t)stream;
     if (a->normalise && !a->stats_ready) flex_td_launch_stats(*a, s);
     if (!stats_only) hipLaunchKernelGGL(td_apply_kernel, dim3(TD_BLOCKS), dim3(TD_THREADS), 0, s, *a);
     flex_td_launch_finish(*a, stats_only ? 0 : TD_BLOCKS, s);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }
 
 
 // ---- fixed-order scalar sum (flexnet_scaled_sum): the reported means of the losses, graph-replay safe -------------------
 __global__ __launch_bounds__(TD_THREADS) void sum_partial_kernel(FlexSumArgs a) {
-    __shared__ double red[TD_THREADS];
     const int tid = threadIdx.x;
     double s0 = 0.0, s1 = 0.0;
     int64_t i = (int64_t)blockIdx.x * TD_THREADS + tid;
     const int64_t stride = (int64_t)TD_BLOCKS * TD_THREADS;
     for (; i + stride < a.n; i += 2 * stride) { s0 += (double)a.x[i]; s1 += (double)a.x[i + stride]; }
     if (i < a.n) s0 += (double)a.x[i];
-    red[tid] = s0 + s1;
-    __syncthreads();
-    for (int sft = TD_THREADS / 2; sft > 0; sft >>= 1) {
-        if (tid < sft) red[tid] += red[tid + sft];
-        __syncthreads();
-    }
-    if (tid == 0) reinterpret_cast<double*>(a.workspace)[blockIdx.x] = red[0];
+    flex_block_sum_f64<TD_THREADS>(s0 + s1, reinterpret_cast<double*>(a.workspace));
 }
 
+// NOT flex_loss_finish: one lane adds the partials serially, in block order — another summation order, other bits
 __global__ __launch_bounds__(64) void sum_finish_kernel(FlexSumArgs a) {
     if (threadIdx.x != 0) return;
     const double* ws = reinterpret_cast<const double*>(a.workspace);
@@ -117,10 +113,10 @@ __global__ __launch_bounds__(64) void sum_finish_kernel(FlexSumArgs a) {
 
 extern "C" int flexnet_scaled_sum(const FlexSumArgs* a, void* stream) {
     if (!a || a->n < 1 || !a->x || !a->out || !a->workspace || a->workspace_floats < FLEXNET_SUM_WS_FLOATS ||
-        (reinterpret_cast<uintptr_t>(a->workspace) & 7) != 0)
+        !flex_aligned(a->workspace, 8))
         return FLEXNET_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(sum_partial_kernel, dim3(TD_BLOCKS), dim3(TD_THREADS), 0, s, *a);
     hipLaunchKernelGGL(sum_finish_kernel, dim3(1), dim3(64), 0, s, *a);
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "flexnet.h"
+#include "flex_launch.h"
 #include "flex_reduce.h"
 #include "critic_finish.h"
 
@@ -309,7 +310,7 @@ static int wgrad_launch(WgradK p, int chunks, hipStream_t s, const CriticFinishK
         none.blocks = 0;                                          // (never read without RIDER)
         hipLaunchKernelGGL((wgrad_reduce_kernel<MT, NT>), dim3(WG_IMG(MT, NT) / 64 + cs_blocks, chunks), dim3(64 * WG_RED), 0, s, p, none);
     }
-    return hipGetLastError() == hipSuccess ? FLEXNET_OK : FLEXNET_EHIP;
+    return flex_launch_status();
 }
 
 static int wgrad_run(const FlexWgradArgs* a, void* stream, const CriticFinishK* rider) {

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "flexnet.h"
+#include "flex_launch.h"
 #include "flex_td.h"
 
 #define WINDOW_THREADS 256
@@ -98,7 +99,7 @@ static inline int window_refresh_prepare(const FlexWindowRefreshArgs* a, const F
         const int j = a->reward_job;
         if (j < 0 || j >= a->n_jobs || a->width[j] != td->n_agents || a->rows[j] != td->rows || td->rows < 1 || td->n_agents < 1 ||
             td->n_agents > TD_NA || !td->workspace || td->workspace_floats < FLEXNET_TD_WS_FLOATS ||
-            (reinterpret_cast<uintptr_t>(td->workspace) & 7) != 0)
+            !flex_aligned(td->workspace, 8))
             return FLEXNET_EINVAL;
     }
     *copy_blocks = blocks;
