@@ -77,9 +77,7 @@ class RolloutGraph:
                        and bool(model.args.action_enforcebound) and bool(model.args.continuous) and a > 1
                        and env.obs.is_cuda and model.fused_inference and model.args.shared_params)
         if self.summed:
-            with th.no_grad():                  # exp(sum over agents of the fixed log-std): the tensor ops' own arithmetic
-                ls = model._log_stds_like(th.zeros(1, n, a, device=dev))
-                self.std_sum = _sum_agents(ls.expand(1, n, a)).exp().reshape(a).to(th.float32).contiguous()
+            self.std_sum = model.summed_std(self.avail.device)
             self.act_pol_buf = th.zeros(N, n, a, device=dev)
             self.env_act_buf = th.zeros(N, n, a, device=dev)
         # plain MADDPG on the GPU: policy + exploration in one HIP launch, ring write + hand-over + statistics in another
@@ -482,6 +480,26 @@ class Model(nn.Module):
         self.fused_inference = True      # no-grad policy passes on the GPU go through csrc/actor.hip
 
     # -- construction ------------------------------------------------------------------------------
+    def construct_model(self):
+        """Critic first, then policy: the order of the draws from torch's generator."""
+        self.construct_value_net()
+        self.construct_policy_net()
+
+    def build_nets(self, target_net):
+        """What every algorithm's __init__ does: the nets, their initialisation, the target and its first reload."""
+        self.construct_model()
+        self.apply(self.init_weights)
+        if target_net is not None:
+            self.target_net = target_net
+            self.reload_params_to_target()
+
+    def build_value_dicts(self, input_shape):
+        """``value_dicts`` for critics of ``input_shape`` columns plus the id columns under agent_id: one critic under
+        shared_params, else one per agent."""
+        input_shape += self.n_ if self.args.agent_id else 0
+        count = 1 if self.args.shared_params else self.n_
+        self.value_dicts = nn.ModuleList([MLPCritic(input_shape, 1, self.args) for _ in range(count)])
+
     def construct_policy_net(self):
         """model.py:145-169"""
         input_shape = self.obs_dim + self.n_ if self.args.agent_id else self.obs_dim
@@ -535,9 +553,7 @@ class Model(nn.Module):
             if out is not None:
                 means, hiddens = out[0].view(b, self.n_, -1), out[2].view(b, self.n_, -1)
                 return means, self._log_stds_like(means), hiddens
-        if self.args.agent_id:
-            ids = th.eye(self.n_, device=obs.device, dtype=obs.dtype).expand(b, -1, -1)
-            obs = th.cat((obs, ids), dim=-1)
+        obs = self.with_ids(obs)
         if self.args.shared_params:
             means, _, hiddens = self.policy_dicts[0](obs.reshape(b * self.n_, -1), last_hid)
             means = means.view(b, self.n_, -1)
@@ -562,6 +578,55 @@ class Model(nn.Module):
         out = cache[means.device][0].expand_as(means)
         out._flex_entropy = cache[means.device][1]        # mean entropy of Normal(means, exp(out)) (util.py:35-36)
         return out
+
+    def summed_std(self, device):
+        """exp(sum over agents of the fixed log-std) [a], the standard deviation of the agent-summed action selection: the
+        tensor ops' own arithmetic, once per device."""
+        cache = self.__dict__.setdefault("_std_sum_cache", {})
+        if device not in cache:
+            n, a = self.n_, self.act_dim
+            with th.no_grad():
+                ls = self._log_stds_like(th.zeros(1, n, a, device=device))
+                cache[device] = _sum_agents(ls.expand(1, n, a)).exp().reshape(a).to(th.float32).contiguous()
+        return cache[device]
+
+    # -- pieces the algorithms' critics and losses share ---------------------------------------------------
+    def with_ids(self, rows):
+        """[b, n, w] -> [b, n, w + n]: onehot(i) behind agent i's columns (under agent_id)."""
+        if self.args.agent_id:
+            ids = th.eye(self.n_, device=rows.device, dtype=rows.dtype).expand(rows.size(0), -1, -1)
+            rows = th.cat((rows, ids), dim=-1)
+        return rows
+
+    def row_values(self, rows, tall):
+        """The critic on materialised rows [b, n, w] -> [b, n, 1]: the shared one on all of them, else agent i's on row i.
+        ``tall``: update batches on the GPU take the shared critic's first layer with the batch-reduced weight gradient of
+        csrc/wgrad.hip (the library's dW = dY^T X over 163 840 rows took 0.8 ms) and the rest in the fused tail kernels."""
+        if not self.args.shared_params:
+            return th.stack([net(rows[:, i, :], None)[0] for i, net in enumerate(self.value_dicts)], dim=1)
+        b, net = rows.size(0), self.value_dicts[0]
+        rows = rows.reshape(b * self.n_, -1)
+        if tall and rows.is_cuda and rows.shape[0] >= WGRAD_MIN_ROWS:
+            v, _ = net.forward_from_hidden(tall_linear(rows, net.fc1.weight, net.fc1.bias), need_hidden=False)
+        else:
+            v, _ = net(rows, None)
+        return v.view(b, self.n_, -1)
+
+    def policy_term(self, advantages):
+        """-mean of the (normalize_advantages: batch-normalised) advantages [b, n]."""
+        if self.args.normalize_advantages:
+            advantages = self.batchnorm(advantages)
+        return mean_all(advantages, sign=-1.0)
+
+    def next_actions(self, next_state, actions_avail, hids, exploration=False, **kw):
+        """The restored next actions of a TD target, for a caller under no_grad: from the behaviour policy (double_q) or
+        the target policy.  ``kw``: ``clip`` / ``need_log_prob`` where the algorithm's get_actions takes them."""
+        return self.get_actions(next_state, status="train", exploration=exploration, actions_avail=actions_avail,
+                                target=not self.args.double_q, last_hid=hids, **kw)[1]
+
+    def note_unfused(self, kernel):
+        note_fallback(kernel, f"shared_params {self.args.shared_params}, agent_id {self.args.agent_id}, "
+                              f"hid {self.args.hid_size}, agents {self.n_}, act_dim {self.act_dim}")
 
     # -- update cadence (model.py:40-71) -----------------------------------------------------------
     on_policy = False                # IPPO / MAPPO / COMA: the replay is cleared after every update event (model.py:54-57)
@@ -927,18 +992,12 @@ class MADDPG(Model):
 
     def __init__(self, args, target_net=None):
         super().__init__(args)
-        self.construct_model()
-        self.apply(self.init_weights)
-        if target_net is not None:
-            self.target_net = target_net
-            self.reload_params_to_target()
+        self.build_nets(target_net)
         self.batchnorm = nn.BatchNorm1d(self.args.agent_num).to(self.device)      # maddpg.py:16
 
     def construct_value_net(self):
         """maddpg.py:18-27: input (obs+act)*n + n."""
-        input_shape = (self.obs_dim + self.act_dim) * self.n_ + (self.n_ if self.args.agent_id else 0)
-        count = 1 if self.args.shared_params else self.n_
-        self.value_dicts = nn.ModuleList([MLPCritic(input_shape, 1, self.args) for _ in range(count)])
+        self.build_value_dicts((self.obs_dim + self.act_dim) * self.n_)
 
     # replay fields each loss reads (get_loss below; MATD3 and SAFEMADDPG read the same ones): a graphed sub-update
     # refreshes only these columns of its static batch
@@ -949,10 +1008,6 @@ class MADDPG(Model):
                      # trainer.replay_event with the bootstrap values filed per transition first (round 3)
                      "value_cached": ("state", "action", "reward", "done", "next_value"),
                      "bootstrap": ("next_state", "hid")}
-
-    def construct_model(self):
-        self.construct_value_net()
-        self.construct_policy_net()
 
     def value(self, obs, act, critic_frozen=False):
         """maddpg.py:33-76.  Row i of the reference's critic input is
@@ -1031,9 +1086,7 @@ class MADDPG(Model):
         """Q'(s', pi(s')) [b, n] of maddpg.py:108-111: the next action from the behaviour policy (double_q) or the target
         policy, valued by the target critic; no gradient (maddpg.py:110,115: .detach())."""
         with th.no_grad():
-            _, next_actions, _, _, _ = self.get_actions(next_state, status="train", exploration=False,
-                                                        actions_avail=actions_avail, target=not self.args.double_q,
-                                                        last_hid=hids)
+            next_actions = self.next_actions(next_state, actions_avail, hids)
             return self.target_net.value(next_state, next_actions).view(-1, self.n_)
 
     def get_loss(self, batch, need="both"):
@@ -1064,9 +1117,7 @@ class MADDPG(Model):
             policy_loss = self._critic_policy_loss(state, actions_pol) if need == "policy" else None
             if policy_loss is None:
                 advantages = self.value(state, actions_pol, critic_frozen=(need == "policy")).view(-1, self.n_)
-                if self.args.normalize_advantages:
-                    advantages = self.batchnorm(advantages)
-                policy_loss = mean_all(advantages, sign=-1.0)
+                policy_loss = self.policy_term(advantages)
         if need in ("both", "value"):
             if self.bootstrap_from_batch and need == "value":
                 # trainer.replay_event filed Q'(s', pi(s')) for this window already (bootstrap_values below, on the same
@@ -1175,18 +1226,14 @@ def summed_exploration(model, means, env_action=None, action_out=None):
     import torch.distributions.normal as tdn      # (looked up at call time: the very function Normal.rsample calls)
     from . import _lib
     b, n, a = means.shape
-    cache = model.__dict__.setdefault("_std_sum_cache", {})
-    if means.device not in cache:
-        with th.no_grad():
-            ls = model._log_stds_like(th.zeros(1, n, a, device=means.device))
-            cache[means.device] = _sum_agents(ls.expand(1, n, a)).exp().reshape(a).to(th.float32).contiguous()
+    std = model.summed_std(means.device)
     means = means.contiguous()
     eps = tdn._standard_normal((b, 1, a), means.dtype, means.device)
     out = action_out if action_out is not None else th.empty(b, n, a, dtype=th.float32, device=means.device)
     k = _lib.FlexAgentSumArgs()
     k.n_envs, k.n_agents, k.act_dim = b, n, a
     k.act_low, k.act_high = float(model.args.action_low), float(model.args.action_high)
-    k.means, k.eps, k.std, k.action = means.data_ptr(), eps.data_ptr(), cache[means.device].data_ptr(), out.data_ptr()
+    k.means, k.eps, k.std, k.action = means.data_ptr(), eps.data_ptr(), std.data_ptr(), out.data_ptr()
     if env_action is not None:
         k.env_action = env_action.data_ptr()
     _lib.launch("flexnet_agent_sum_explore", k)
@@ -1246,6 +1293,39 @@ def _sum_agents(x):
     return out.unsqueeze(1)
 
 
+def _summed_get_actions(self, obs, status, exploration, actions_avail, target, last_hid, need_log_prob, clip=False,
+                        mask_unavailable=False):
+    """The agent-summed action selection of matd3.py:88-111 and iddpg.py:61-83 (continuous branch): the means are summed over
+    the AGENT axis before sampling (matd3.py:94-97), and the one action goes to every agent.  ``need_log_prob=False`` (the
+    losses and the vectorised rollout never read it): exploration in one launch where ``_summed_exploration_applies``.
+    ``mask_unavailable``: MATD3 zeroes the means and log-stds of unavailable actions first; ``clip``: its target smoothing."""
+    pol = self.target_net.policy if (target and self.args.target) else self.policy
+    means, log_stds, hiddens = pol(obs, last_hid=last_hid)
+    if _summed_exploration_applies(self, means, status, exploration, actions_avail, need_log_prob):
+        restore_actions = summed_exploration(self, means)
+        return restore_actions[:, :1], restore_actions, None, (means, log_stds), hiddens
+    if _summed_mean_applies(self, means, status, exploration, actions_avail):
+        restore_actions = _SumBroadcastAgentsFn.apply(means, self)
+        return restore_actions[:, :1], restore_actions, None, (means, log_stds), hiddens
+    avail = actions_avail
+    if mask_unavailable:
+        avail = avail.to(means.device)
+        means = means.masked_fill(avail == 0, 0.0)
+        log_stds = log_stds.masked_fill(avail == 0, 0.0)
+    if means.size(-1) > 1:                                              # matd3.py:94-96: sum over dim=1 (agents)
+        means_, log_stds_ = _sum_agents(means), _sum_agents(log_stds)
+    else:
+        means_, log_stds_ = means, log_stds
+    actions, log_prob_a = select_action(self.args, means_, status=status, exploration=exploration,
+                                        info={"clip": clip, "log_std": log_stds_})
+    if getattr(actions_avail, "_flex_const", None) == 1.0 and actions.size(1) == 1:
+        # every action available (env:721-730): the mask is 1; the agent-summed action goes to every agent
+        restore_actions = expand_agents(actions, self.n_)
+    else:                               # (the mask reaches the device only here, unless MATD3 moved it above)
+        restore_actions = (1.0 - (avail.to(means.device) == 0).float()) * actions
+    return actions, restore_actions, log_prob_a, (means, log_stds), hiddens
+
+
 class MATD3(MADDPG):
     """madrl/models/matd3.py:8-149: twin centralised critics realised as ONE shared network with
     a trailing 0/1 input flag (matd3.py:64-67), clipped-double-Q target min(Q1', Q2') (matd3.py:139-140) and a
@@ -1259,9 +1339,7 @@ class MATD3(MADDPG):
 
     def construct_value_net(self):
         """matd3.py:18-27: the MADDPG critic input plus the twin flag."""
-        input_shape = (self.obs_dim + self.act_dim) * self.n_ + 1 + (self.n_ if self.args.agent_id else 0)
-        count = 1 if self.args.shared_params else self.n_
-        self.value_dicts = nn.ModuleList([MLPCritic(input_shape, 1, self.args) for _ in range(count)])
+        self.build_value_dicts((self.obs_dim + self.act_dim) * self.n_ + 1)
 
     def value(self, obs, act, critic_frozen=False, first_head_only=False):
         """matd3.py:33-86: returns cat([Q1, Q2], dim=0) of shape [2b, n, 1] (``first_head_only``: Q1 alone, [b, n, 1] — all
@@ -1315,31 +1393,9 @@ class MATD3(MADDPG):
         return th.cat([v1.view(b, n, 1), v2.view(b, n, 1)], dim=0)
 
     def get_actions(self, obs, status, exploration, actions_avail, target=False, last_hid=None, clip=False, need_log_prob=True):
-        """matd3.py:88-111 (continuous branch).  ``need_log_prob=False`` (the losses and the vectorised rollout never read
-        it): exploration in one launch where ``_summed_exploration_applies``."""
-        pol = self.target_net.policy if (target and self.args.target) else self.policy
-        means, log_stds, hiddens = pol(obs, last_hid=last_hid)
-        if _summed_exploration_applies(self, means, status, exploration, actions_avail, need_log_prob):
-            restore_actions = summed_exploration(self, means)
-            return restore_actions[:, :1], restore_actions, None, (means, log_stds), hiddens
-        if _summed_mean_applies(self, means, status, exploration, actions_avail):
-            restore_actions = _SumBroadcastAgentsFn.apply(means, self)
-            return restore_actions[:, :1], restore_actions, None, (means, log_stds), hiddens
-        avail = actions_avail.to(means.device)
-        means = means.masked_fill(avail == 0, 0.0)
-        log_stds = log_stds.masked_fill(avail == 0, 0.0)
-        if means.size(-1) > 1:                                              # matd3.py:94-96: sum over dim=1 (agents)
-            means_, log_stds_ = _sum_agents(means), _sum_agents(log_stds)
-        else:
-            means_, log_stds_ = means, log_stds
-        actions, log_prob_a = select_action(self.args, means_, status=status, exploration=exploration,
-                                            info={"clip": clip, "log_std": log_stds_})
-        if getattr(actions_avail, "_flex_const", None) == 1.0 and actions.size(1) == 1:
-            # every action available (env:721-730): the mask is 1; the agent-summed action goes to every agent
-            restore_actions = expand_agents(actions, self.n_)
-        else:
-            restore_actions = (1.0 - (avail == 0).float()) * actions
-        return actions, restore_actions, log_prob_a, (means, log_stds), hiddens
+        """matd3.py:88-111 (continuous branch): the agent-summed selection on means masked where unavailable."""
+        return _summed_get_actions(self, obs, status, exploration, actions_avail, target, last_hid, need_log_prob,
+                                   clip=clip, mask_unavailable=True)
 
     def get_loss(self, batch, need="both"):
         """matd3.py:113-149.  ``need`` = "value" / "policy" (what a sub-update asks for) on the GPU: the reward BatchNorm
@@ -1362,14 +1418,11 @@ class MATD3(MADDPG):
                 advantages = self.value(state, actions_pol, critic_frozen=True, first_head_only=True).reshape(-1, self.n_)
             else:
                 advantages = self.value(state, actions_pol)[:b].reshape(-1, self.n_)      # first head only
-            if self.args.normalize_advantages:
-                advantages = self.batchnorm(advantages)
-            policy_loss = mean_all(advantages, sign=-1.0)
+            policy_loss = self.policy_term(advantages)
         if need in ("both", "value"):
             with th.no_grad():
-                _, next_actions, _, _, _ = self.get_actions(next_state, status="train", exploration=True,
-                                                            actions_avail=actions_avail, target=not self.args.double_q,
-                                                            last_hid=hids, clip=True, need_log_prob=False)
+                next_actions = self.next_actions(next_state, actions_avail, hids, exploration=True, clip=True,
+                                                 need_log_prob=False)
                 nxt = self.target_net.value(next_state, next_actions)
                 next_min = th.min(nxt[:b].reshape(-1, self.n_), nxt[b:].reshape(-1, self.n_))
             cur = self.value(state, actions)
@@ -1402,50 +1455,15 @@ class IDDPG(MADDPG):
 
     def construct_value_net(self):
         """iddpg.py:17-26"""
-        input_shape = self.obs_dim + self.act_dim + (self.n_ if self.args.agent_id else 0)
-        count = 1 if self.args.shared_params else self.n_
-        self.value_dicts = nn.ModuleList([MLPCritic(input_shape, 1, self.args) for _ in range(count)])
+        self.build_value_dicts(self.obs_dim + self.act_dim)
 
     def value(self, obs, act, critic_frozen=False):
         """iddpg.py:32-59: rows [o_i | onehot(i) | a_i] -> [b, n, 1]."""
-        b = obs.size(0)
-        if self.args.agent_id:
-            ids = th.eye(self.n_, device=obs.device, dtype=obs.dtype).expand(b, -1, -1)
-            obs = th.cat((obs, ids), dim=-1)
-        inputs = th.cat((obs, act), dim=-1)
-        if self.args.shared_params:
-            net = self.value_dicts[0]
-            rows = inputs.reshape(b * self.n_, -1)
-            if rows.is_cuda and rows.shape[0] >= WGRAD_MIN_ROWS:
-                # update batches: first layer with the batch-reduced weight gradient of csrc/wgrad.hip (the library's
-                # dW = dY^T X over 163 840 rows took 0.8 ms), the rest of the critic in the fused tail kernels
-                v, _ = net.forward_from_hidden(tall_linear(rows, net.fc1.weight, net.fc1.bias), need_hidden=False)
-            else:
-                v, _ = net(rows, None)
-            return v.view(b, self.n_, -1)
-        return th.stack([net(inputs[:, i, :], None)[0] for i, net in enumerate(self.value_dicts)], dim=1)
+        return self.row_values(th.cat((self.with_ids(obs), act), dim=-1), True)
 
     def get_actions(self, state, status, exploration, actions_avail, target=False, last_hid=None, need_log_prob=True):
         """iddpg.py:61-83 (continuous branch): the means are summed over the agent axis before sampling."""
-        pol = self.target_net.policy if (target and self.args.target) else self.policy
-        means, log_stds, hiddens = pol(state, last_hid=last_hid)
-        if _summed_exploration_applies(self, means, status, exploration, actions_avail, need_log_prob):
-            restore_actions = summed_exploration(self, means)
-            return restore_actions[:, :1], restore_actions, None, (means, log_stds), hiddens
-        if _summed_mean_applies(self, means, status, exploration, actions_avail):
-            restore_actions = _SumBroadcastAgentsFn.apply(means, self)
-            return restore_actions[:, :1], restore_actions, None, (means, log_stds), hiddens
-        if means.size(-1) > 1:
-            means_, log_stds_ = _sum_agents(means), _sum_agents(log_stds)
-        else:
-            means_, log_stds_ = means, log_stds
-        actions, log_prob_a = select_action(self.args, means_, status=status, exploration=exploration,
-                                            info={"log_std": log_stds_})
-        if getattr(actions_avail, "_flex_const", None) == 1.0 and actions.size(1) == 1:
-            restore_actions = expand_agents(actions, self.n_)       # every action available: the mask is 1
-        else:
-            restore_actions = (1.0 - (actions_avail.to(means.device) == 0).float()) * actions
-        return actions, restore_actions, log_prob_a, (means, log_stds), hiddens
+        return _summed_get_actions(self, state, status, exploration, actions_avail, target, last_hid, need_log_prob)
 
 
 class SAFEMADDPG(MADDPG):
@@ -1533,17 +1551,12 @@ class FACMADDPG(IDDPG):
             _, actions_pol, _, action_out, _ = self.get_actions(state, status="train", exploration=False,
                                                                 actions_avail=actions_avail, target=False,
                                                                 last_hid=last_hids)
-            advantages = self.value(state, actions_pol).contiguous().view(-1, n)
-            if self.args.normalize_advantages:
-                advantages = self.batchnorm(advantages)
-            policy_loss = mean_all(advantages, sign=-1.0)
+            policy_loss = self.policy_term(self.value(state, actions_pol).contiguous().view(-1, n))
         if need in ("both", "value", "mixer"):
             with th.no_grad():
                 # double_q: the next actions from the behaviour policy (facmaddpg.py:90-93), valued by the target critic
                 # and mixed by the target mixer on s' (facmaddpg.py:99-102)
-                _, next_actions, _, _, _ = self.get_actions(next_state, status="train", exploration=False,
-                                                            actions_avail=actions_avail, target=not self.args.double_q,
-                                                            last_hid=hids)
+                next_actions = self.next_actions(next_state, actions_avail, hids)
                 next_values = self.target_net.value(next_state, next_actions).contiguous().view(-1, n)
                 next_q_tot = self.target_net.mixer(next_values, next_state.reshape(b, n * self.obs_dim)).view(-1, 1)
             if need == "mixer":
@@ -1617,15 +1630,7 @@ class SQDDPG(MADDPG):
         others = (subcoalition - individual).unsqueeze(-1)
         acts = (acts * others).detach() + acts * individual.unsqueeze(-1)          # only agent i's own action keeps its gradient
         rows = th.cat((obs.reshape(b, 1, 1, n * o).expand(b, ns, n, n * o), acts.reshape(b, ns, n, n * a)), dim=-1)
-        rows = rows.reshape(b * ns, n, -1)
-        if self.args.agent_id:
-            ids = th.eye(n, device=obs.device, dtype=rows.dtype).unsqueeze(0).expand(b * ns, n, n)
-            rows = th.cat((rows, ids), dim=-1)
-        if self.args.shared_params:
-            values, _ = self.value_dicts[0](rows.reshape(b * ns * n, -1), None)
-        else:
-            values = th.stack([net(rows[:, i, :], None)[0] for i, net in enumerate(self.value_dicts)], dim=1)
-        return values.reshape(b, ns, n, 1)
+        return self.row_values(self.with_ids(rows.reshape(b * ns, n, -1)), False).reshape(b, ns, n, 1)
 
     def _fused(self, act):
         if not act.is_cuda:
@@ -1633,8 +1638,7 @@ class SQDDPG(MADDPG):
         ok = (self.args.shared_params and self.fused_inference and act.dtype == th.float32
               and sqddpg_fused_config(self.value_dicts[0], self.n_, self.act_dim, self.sample_size))
         if not ok:
-            note_fallback("sqddpg", f"shared_params {self.args.shared_params}, agent_id {self.args.agent_id}, "
-                                    f"hid {self.args.hid_size}, agents {self.n_}, act_dim {self.act_dim}")
+            self.note_unfused("sqddpg")
         return ok
 
     def shapley_values(self, obs, act, pos, want_q=False, frozen=False):
@@ -1665,19 +1669,14 @@ class SQDDPG(MADDPG):
                                                                 actions_avail=actions_avail, target=False,
                                                                 last_hid=last_hids)
             pos = self.draw_coalitions("policy", b, dev)
-            advantages, _ = self.shapley_values(state, actions_pol, pos, frozen=(need == "policy"))
-            if self.args.normalize_advantages:
-                advantages = self.batchnorm(advantages)
-            policy_loss = mean_all(advantages, sign=-1.0)
+            policy_loss = self.policy_term(self.shapley_values(state, actions_pol, pos, frozen=(need == "policy"))[0])
         if need in ("both", "value"):
             pos = self.draw_coalitions("value", b, dev)
             pos_next = self.draw_coalitions("target", b, dev)
             tgt = self.target_net if self.args.target else self
             with th.no_grad():
                 # double_q: the next actions from the behaviour policy (sqddpg.py:136-139)
-                _, next_actions, _, _, _ = self.get_actions(next_state, status="train", exploration=False,
-                                                            actions_avail=actions_avail, target=not self.args.double_q,
-                                                            last_hid=hids)
+                next_actions = self.next_actions(next_state, actions_avail, hids)
                 next_phi, _ = tgt.shapley_values(next_state, next_actions, pos_next)
                 next_sum = next_phi.sum(dim=-1, keepdim=True)
             phi, _ = self.shapley_values(state, actions, pos)
@@ -1717,41 +1716,18 @@ class IPPO(Model):
         super().__init__(args)
         if not args.continuous:
             raise NotImplementedError("discrete control is outside the flexibility-provision hot path")
-        self.construct_model()
-        self.apply(self.init_weights)
-        if target_net is not None:
-            self.target_net = target_net
-            self.reload_params_to_target()
+        self.build_nets(target_net)
         object.__setattr__(self, "rl", _PPO(self.args, self.device))
         self.consistent_ratio = bool(getattr(args, "ppo_consistent_ratio", False))
         self.last_terms = {}
 
     def construct_value_net(self):
         """ippo.py:19-28: a V(s), input obs + id."""
-        input_shape = self.obs_dim + (self.n_ if self.args.agent_id else 0)
-        count = 1 if self.args.shared_params else self.n_
-        self.value_dicts = nn.ModuleList([MLPCritic(input_shape, 1, self.args) for _ in range(count)])
-
-    def construct_model(self):
-        self.construct_value_net()
-        self.construct_policy_net()
+        self.build_value_dicts(self.obs_dim)
 
     def value(self, obs, act=None):
         """ippo.py:34-59: rows [o_i | onehot(i)] -> [b, n, 1]; ``act`` is ignored."""
-        b = obs.size(0)
-        if self.args.agent_id:
-            ids = th.eye(self.n_, device=obs.device, dtype=obs.dtype).expand(b, -1, -1)
-            obs = th.cat((obs, ids), dim=-1)
-        if self.args.shared_params:
-            net = self.value_dicts[0]
-            rows = obs.reshape(b * self.n_, -1)
-            if rows.is_cuda and rows.shape[0] >= WGRAD_MIN_ROWS and self.fused_inference:
-                # update batches, as IDDPG.value: csrc/wgrad.hip behind the first layer, the fused tail kernels after it
-                v, _ = net.forward_from_hidden(tall_linear(rows, net.fc1.weight, net.fc1.bias), need_hidden=False)
-            else:
-                v, _ = net(rows, None)
-            return v.view(b, self.n_, -1)
-        return th.stack([net(obs[:, i, :], None)[0] for i, net in enumerate(self.value_dicts)], dim=1)
+        return self.row_values(self.with_ids(obs), self.fused_inference)
 
     def _unfiled_columns(self, n_envs):
         """Real columns: begin_update_event files the values (and the consistent log-probability) into them."""
@@ -1836,9 +1812,7 @@ class MAPPO(IPPO):
 
     def construct_value_net(self):
         """mappo.py:19-28"""
-        input_shape = self.obs_dim * self.n_ + (self.n_ if self.args.agent_id else 0)
-        count = 1 if self.args.shared_params else self.n_
-        self.value_dicts = nn.ModuleList([MLPCritic(input_shape, 1, self.args) for _ in range(count)])
+        self.build_value_dicts(self.obs_dim * self.n_)
 
     def value(self, obs, act=None):
         """mappo.py:34-62: rows [o_1 .. o_n | onehot(i)] -> [b, n, 1].  The n rows of a sample differ in the id column only,
@@ -1861,14 +1835,7 @@ class MAPPO(IPPO):
                     h = h + W[:, n * o:n * o + n].t().unsqueeze(0)
                 v, _ = net.forward_from_hidden(h.reshape(b * n, -1), need_hidden=False)
                 return v.view(b, n, 1)
-        inp = obs_cols.unsqueeze(1).expand(b, n, n * o)
-        if self.args.agent_id:
-            ids = th.eye(n, device=obs.device, dtype=obs.dtype).expand(b, -1, -1)
-            inp = th.cat((inp, ids), dim=-1)
-        if self.args.shared_params:
-            v, _ = self.value_dicts[0](inp.reshape(b * n, -1), None)
-            return v.view(b, n, -1)
-        return th.stack([net(inp[:, i, :], None)[0] for i, net in enumerate(self.value_dicts)], dim=1)
+        return self.row_values(self.with_ids(obs_cols.unsqueeze(1).expand(b, n, n * o)), False)
 
 
 class COMA(Model):
@@ -1893,11 +1860,7 @@ class COMA(Model):
         super().__init__(args)
         if not args.continuous:
             raise NotImplementedError("discrete control is outside the flexibility-provision hot path")
-        self.construct_model()
-        self.apply(self.init_weights)
-        if target_net is not None:
-            self.target_net = target_net
-            self.reload_params_to_target()
+        self.build_nets(target_net)
         # coma.py:17: ONE module for the reward normalisation of unpack_data and (normalize_advantages) the advantages
         self.batchnorm = nn.BatchNorm1d(self.args.agent_num).to(self.device)
         self.sample_size = int(args.sample_size)
@@ -1905,13 +1868,7 @@ class COMA(Model):
 
     def construct_value_net(self):
         """coma.py:19-35"""
-        input_shape = (self.n_ + 1) * self.obs_dim + self.n_ * self.act_dim + (self.n_ if self.args.agent_id else 0)
-        count = 1 if self.args.shared_params else self.n_
-        self.value_dicts = nn.ModuleList([MLPCritic(input_shape, 1, self.args) for _ in range(count)])
-
-    def construct_model(self):
-        self.construct_value_net()
-        self.construct_policy_net()
+        self.build_value_dicts((self.n_ + 1) * self.obs_dim + self.n_ * self.act_dim)
 
     def begin_update_event(self, trainer):
         """Nothing to file: COMA reads no stored value / log-probability column."""
@@ -1947,11 +1904,7 @@ class COMA(Model):
         if not per_row and self._composed(obs) and b * n >= WGRAD_MIN_ROWS:
             v, _ = self.value_dicts[0].forward_from_hidden(self.first_layer(obs, act), need_hidden=False)
             return v.view(b, n, 1)
-        rows = coma_rows(obs, act, self.args.agent_id, per_row)
-        if self.args.shared_params:
-            v, _ = self.value_dicts[0](rows.reshape(-1, rows.size(-1)), None)
-            return v.view(rows.size(0), n, -1)
-        return th.stack([net(rows[:, i, :], None)[0] for i, net in enumerate(self.value_dicts)], dim=1)
+        return self.row_values(coma_rows(obs, act, self.args.agent_id, per_row), False)
 
     def draw_samples(self, means, std):
         """coma.py:139-141: ``sample_size`` draws of every agent's action from its own policy, [s, b, n, a]."""
@@ -1966,8 +1919,7 @@ class COMA(Model):
         ok = (self.args.shared_params and state.dtype == th.float32
               and coma_fused_config(self.value_dicts[0], self.n_, self.act_dim))
         if not ok:
-            note_fallback("coma", f"shared_params {self.args.shared_params}, agent_id {self.args.agent_id}, "
-                                  f"hid {self.args.hid_size}, agents {self.n_}, act_dim {self.act_dim}")
+            self.note_unfused("coma")
         return ok
 
     # -- loss ----------------------------------------------------------------------------------------------------------
@@ -2011,9 +1963,7 @@ class COMA(Model):
         if need in ("both", "value"):
             with th.no_grad():
                 # double_q: the next actions from the behaviour policy (coma.py:133-136), valued by the target critic
-                _, next_actions, _, _, _ = self.get_actions(next_state, status="train", exploration=False,
-                                                            actions_avail=actions_avail, target=not args.double_q,
-                                                            last_hid=hids)
+                next_actions = self.next_actions(next_state, actions_avail, hids)
                 tgt = self.target_net if args.target else self
                 next_values = tgt.value(next_state, next_actions).view(-1, n)
             returns = rewards + args.gamma * (1 - done) * next_values

@@ -3,47 +3,15 @@
 ``sample_source``; the rank-act_dim identity the HIP kernel rests on; the need split; the baseline takes no gradient; the
 on-policy cadence on a vectorised CPU run; the C ABI; the cross-compiled kernels' resources."""
 import ctypes as C
-import json
 import os
 
 import numpy as np
 import pytest
 import torch as th
 
-G = os.path.join(os.path.dirname(__file__), "golden")
+from .golden_io import StubEnv, golden_args, golden_batch, golden_model, golden_tensors, golden_vectors
+
 CASES = ["coma", "coma3"]
-
-
-def _args(prefix, **over):
-    from safe_marl_amd.util import convert
-    d = json.load(open(os.path.join(G, prefix + "_args.json")))
-    d.update(over)
-    return convert(d)
-
-
-def _load(name):
-    z = np.load(os.path.join(G, name))
-    return {k: th.from_numpy(z[k]) for k in z.files}
-
-
-def _gold(prefix):
-    return dict(np.load(os.path.join(G, prefix + "_golden.npz")))
-
-
-def _batch(prefix, gold):
-    from safe_marl_amd.replay_buffer import Transition
-    z = dict(np.load(os.path.join(G, "learner3_batch.npz" if prefix.endswith("3") else "learner_batch.npz")))
-    z["action"] = gold["batch.action"]
-    return Transition(**{k: th.from_numpy(z[k]).float() for k in Transition._fields})
-
-
-def _model(prefix, **over):
-    from safe_marl_amd.learner import COMA
-    args = _args(prefix, **over)
-    model = COMA(args, COMA(args))
-    res = model.load_state_dict(_load(f"{prefix}_state_dict.npz"), strict=True)        # the reference's keys and shapes
-    assert not res.missing_keys and not res.unexpected_keys
-    return model, args
 
 
 def _recorded(draws):
@@ -55,27 +23,18 @@ def _recorded(draws):
     return source
 
 
-class StubEnv:
-    n_envs = 1
-
-    def __init__(self, n):
-        self.n = n
-
-    def get_num_of_agents(self):
-        return self.n
-
-
 @pytest.mark.parametrize("prefix", CASES)
 def test_golden_parity(prefix):
     from safe_marl_amd.learner import COMA
     from safe_marl_amd.trainer import PGTrainer
-    gold = _gold(prefix)
-    model, args = _model(prefix)
+    gold = golden_vectors(prefix)
+    args = golden_args(prefix)
+    model = golden_model("COMA", args, f"{prefix}_state_dict.npz")
     n = args.agent_num
     assert args.sample_size == 10 and not args.normalize_advantages
     assert "batchnorm.running_mean" in model.state_dict()
     assert model.value_dicts[0].fc1.in_features == (n + 1) * 144 + n * 4 + n
-    batch = _batch(prefix, gold)
+    batch = golden_batch(prefix, gold=gold, fields=("action",))
     assert all(th.equal(batch.action[:, i], batch.action[:, 0]) for i in range(n))
     model.sample_source = _recorded(gold["sampled"])
     pl, vl, (means, log_stds) = model.get_loss(batch)
@@ -105,7 +64,7 @@ def test_golden_parity(prefix):
     th.manual_seed(2468)
     trainer = PGTrainer(args, COMA, StubEnv(n), None)
     net = trainer.behaviour_net
-    sd0 = _load(f"{prefix}_state_dict.npz")
+    sd0 = golden_tensors(f"{prefix}_state_dict.npz")
     net.load_state_dict(sd0)
     net.target_net.load_state_dict({k[len("target_net."):]: v for k, v in sd0.items() if k.startswith("target_net.")})
     net.sample_source = _recorded(gold["step.sampled_policy"])       # the value step draws nothing here
@@ -117,14 +76,14 @@ def test_golden_parity(prefix):
                                  "mean_train_policy_grad_norm", "mean_train_entropy"}
     for k in keys:
         assert abs(float(stat[k]) - gold["stat." + k]) < 1e-4 * max(1.0, abs(gold["stat." + k])), k
-    after = _load(f"{prefix}_state_dict_after_step.npz")
+    after = golden_tensors(f"{prefix}_state_dict_after_step.npz")
     mine = net.state_dict()
     assert sorted(mine) == sorted(after)
     for k, ref in after.items():
         assert th.allclose(mine[k].float(), ref.float(), atol=3e-6, rtol=1e-5), k
     assert th.allclose(net.batchnorm.running_var, th.from_numpy(gold["after_step.reward_bn.running_var"]), atol=1e-6, rtol=1e-5)
     net.update_target()
-    tgt = _load(f"{prefix}_target_after_update.npz")
+    tgt = golden_tensors(f"{prefix}_target_after_update.npz")
     mine_t = net.target_net.state_dict()
     for k, ref in tgt.items():
         assert th.allclose(mine_t[k].float(), ref.float(), atol=3e-6, rtol=1e-5), k
@@ -136,16 +95,16 @@ def test_class_wiring():
     assert safe_marl_amd.COMA is COMA
     assert COMA.on_policy and COMA.graph_safe_updates is False and COMA.get_actions is IDDPG.get_actions
     assert COMA.sample_source is None and COMA._unfiled_columns is Model._unfiled_columns
-    args = _args("coma")
+    args = golden_args("coma")
     m = COMA(args)
     m.begin_update_event(None)                                     # a no-op
     n, o = args.agent_num, args.obs_size
-    assert COMA(_args("coma", agent_id=False)).value_dicts[0].fc1.in_features == (n + 1) * o + n * 4
-    assert len(COMA(_args("coma", shared_params=False)).value_dicts) == n
+    assert COMA(golden_args("coma", agent_id=False)).value_dicts[0].fc1.in_features == (n + 1) * o + n * 4
+    assert len(COMA(golden_args("coma", shared_params=False)).value_dicts) == n
     obs, act = th.randn(7, n, o), th.randn(7, n, 4)
     assert m.value(obs, act).shape == (7, n, 1)
     with pytest.raises(NotImplementedError):
-        COMA(_args("coma", continuous=False))
+        COMA(golden_args("coma", continuous=False))
 
 
 @pytest.mark.parametrize("prefix", CASES)
@@ -153,10 +112,12 @@ def test_class_wiring():
 def test_rank_update_identity_in_float64(prefix, layernorm):
     """The critic on the materialised rows of coma.py:139-149 equals the tail of z1 + W_act,i (draw - action)."""
     from safe_marl_amd.nets import coma_baseline, coma_baseline_torch
-    model, args = _model(prefix) if layernorm else (None, None)
-    if not layernorm:
+    if layernorm:
+        args = golden_args(prefix)
+        model = golden_model("COMA", args, f"{prefix}_state_dict.npz")
+    else:
         from safe_marl_amd.learner import COMA
-        args = _args(prefix, layernorm=False)
+        args = golden_args(prefix, layernorm=False)
         th.manual_seed(3)
         model = COMA(args)
     model = model.double()
@@ -181,16 +142,16 @@ def test_rank_update_identity_in_float64(prefix, layernorm):
 
 
 def test_need_value_draws_nothing_and_matches_both():
-    gold = _gold("coma")
-    batch = _batch("coma", gold)
-    both, _ = _model("coma")
+    gold = golden_vectors("coma")
+    batch = golden_batch("coma", gold=gold, fields=("action",))
+    both = golden_model("COMA", golden_args("coma"), "coma_state_dict.npz")
     both.sample_source = _recorded(gold["sampled"])
     pl, vl, _ = both.get_loss(batch)
 
     def never(*a):
         raise AssertionError("the value loss needs no draws")
 
-    m, _ = _model("coma")
+    m = golden_model("COMA", golden_args("coma"), "coma_state_dict.npz")
     m.sample_source = never
     p, v, out = m.get_loss(batch, need="value")
     assert p is None and out is None and v.item() == vl.item()
@@ -198,7 +159,7 @@ def test_need_value_draws_nothing_and_matches_both():
     ga = th.autograd.grad(v, list(m.value_dicts.parameters()))
     gb = th.autograd.grad(vl, list(both.value_dicts.parameters()), retain_graph=True)
     assert all(th.equal(x, y) for x, y in zip(ga, gb))
-    m2, _ = _model("coma")
+    m2 = golden_model("COMA", golden_args("coma"), "coma_state_dict.npz")
     m2.sample_source = _recorded(gold["sampled"])
     p2, v2, _ = m2.get_loss(batch, need="policy")
     assert v2 is None and p2.item() == pl.item()
@@ -206,9 +167,9 @@ def test_need_value_draws_nothing_and_matches_both():
 
 
 def test_the_baseline_takes_no_gradient():
-    gold = _gold("coma")
-    batch = _batch("coma", gold)
-    m, _ = _model("coma")
+    gold = golden_vectors("coma")
+    batch = golden_batch("coma", gold=gold, fields=("action",))
+    m = golden_model("COMA", golden_args("coma"), "coma_state_dict.npz")
     m.sample_source = _recorded(gold["sampled"])
     pl, vl, _ = m.get_loss(batch)
     for g in th.autograd.grad(pl, list(m.value_dicts.parameters()), allow_unused=True, retain_graph=True):
@@ -217,14 +178,15 @@ def test_the_baseline_takes_no_gradient():
         assert g is None or float(g.abs().max()) == 0.0
     assert any(float(g.abs().max()) > 0 for g in th.autograd.grad(pl, list(m.policy_dicts.parameters())))
     # other draws move the policy loss and leave the value loss alone
-    m2, _ = _model("coma")
+    m2 = golden_model("COMA", golden_args("coma"), "coma_state_dict.npz")
     m2.sample_source = _recorded(gold["sampled"] + 0.5)
     pl2, vl2, _ = m2.get_loss(batch)
     assert vl2.item() == vl.item() and pl2.item() != pl.item()
 
 
 def test_default_draws_are_torch_normal_in_the_reference_order():
-    m, args = _model("coma")
+    args = golden_args("coma")
+    m = golden_model("COMA", args, "coma_state_dict.npz")
     means, std = th.randn(6, args.agent_num, 4), th.full((6, args.agent_num, 4), 0.7)
     th.manual_seed(5)
     mine = m.draw_samples(means, std)
@@ -279,7 +241,7 @@ def test_vectorised_training_smoke_two_update_events():
     from safe_marl_amd.learner import COMA
     from safe_marl_amd.trainer import PGTrainer
     n_envs = 4
-    args = _args("coma3", behaviour_update_freq=20, max_steps=20, batch_size=8, target_update_freq=40)
+    args = golden_args("coma3", behaviour_update_freq=20, max_steps=20, batch_size=8, target_update_freq=40)
     env = FakeVecEnv(n_envs, args.agent_num, args.obs_size)
     th.manual_seed(0)
     trainer = PGTrainer(args, COMA, env, None, graph_rollout=False)

@@ -1,53 +1,20 @@
 """COMA on the GPU: csrc/coma.hip (the counterfactual baseline from the first-layer pre-activation, the policy loss) against
 the reference's own modules (tests/golden/coma*_*, make_coma_golden.py) and against the materialising composition, its
 determinism, the fallback, the first layer assembled from column blocks, and a short training run."""
-import json
-import os
 import warnings
 
 import numpy as np
 import pytest
 import torch as th
 
+from .golden_io import StubEnv, _np, golden_args, golden_batch, golden_model, golden_tensors, golden_vectors
+
 pytestmark = pytest.mark.gpu
-G = os.path.join(os.path.dirname(__file__), "golden")
-
-
-def _args(prefix="coma", **over):
-    from safe_marl_amd.util import convert
-    d = json.load(open(os.path.join(G, prefix + "_args.json")))
-    d.update(cuda=True)
-    d.update(over)
-    return convert(d)
-
-
-def _load(name):
-    z = np.load(os.path.join(G, name))
-    return {k: th.from_numpy(z[k]).cuda() for k in z.files}
-
-
-def _gold(prefix):
-    return dict(np.load(os.path.join(G, prefix + "_golden.npz")))
-
-
-def _batch(prefix, gold):
-    from safe_marl_amd.replay_buffer import Transition
-    z = dict(np.load(os.path.join(G, "learner3_batch.npz" if prefix.endswith("3") else "learner_batch.npz")))
-    z["action"] = gold["batch.action"]
-    return Transition(**{k: th.from_numpy(z[k]).float().cuda() for k in Transition._fields})
-
-
-def _model(prefix, args):
-    from safe_marl_amd.learner import COMA
-    m = COMA(args, COMA(args).cuda()).cuda()
-    res = m.load_state_dict(_load(prefix + "_state_dict.npz"), strict=True)
-    assert not res.missing_keys and not res.unexpected_keys
-    return m
 
 
 def _random_model(n, layernorm, seed=0):
     from safe_marl_amd.learner import COMA
-    args = _args("coma" if n == 5 else "coma3", layernorm=layernorm)
+    args = golden_args("coma" if n == 5 else "coma3", cuda=True, layernorm=layernorm)
     th.manual_seed(seed)
     return COMA(args).cuda(), args
 
@@ -61,27 +28,13 @@ def _recorded(draws):
     return source
 
 
-def _np(t):
-    return t.detach().float().cpu().numpy()
-
-
-class StubEnv:
-    n_envs = 1
-
-    def __init__(self, n):
-        self.n = n
-
-    def get_num_of_agents(self):
-        return self.n
-
-
 @pytest.mark.parametrize("prefix", ["coma", "coma3"])
 def test_fused_baseline_matches_the_reference(prefix):
     """The kernel on the golden batch, draws and weights: q_sampled, baseline and the values of the unmodified rows."""
     from safe_marl_amd.nets import coma_baseline
-    args, gold = _args(prefix), _gold(prefix)
-    m = _model(prefix, args)
-    b = _batch(prefix, gold)
+    args, gold = golden_args(prefix, cuda=True), golden_vectors(prefix)
+    m = golden_model("COMA", args, prefix + "_state_dict.npz", "cuda")
+    b = golden_batch(prefix, "cuda", gold=gold, fields=("action",))
     sampled = th.from_numpy(gold["sampled"]).cuda()
     with th.no_grad():
         z1 = m.first_layer(b.state, b.action)
@@ -181,9 +134,9 @@ def test_golden_losses_and_steps_on_the_device(prefix):
     from safe_marl_amd.trainer import PGTrainer
     util.FALLBACKS.pop("coma", None)
     util.FALLBACKS.pop("coma_policy_loss", None)
-    args, gold = _args(prefix), _gold(prefix)
-    m = _model(prefix, args)
-    batch = _batch(prefix, gold)
+    args, gold = golden_args(prefix, cuda=True), golden_vectors(prefix)
+    m = golden_model("COMA", args, prefix + "_state_dict.npz", "cuda")
+    batch = golden_batch(prefix, "cuda", gold=gold, fields=("action",))
     assert m._fused(batch.state)                                       # the HIP path is the one under test
     m.sample_source = _recorded(gold["sampled"])
     pl, vl, (means, _) = m.get_loss(batch)
@@ -202,28 +155,28 @@ def test_golden_losses_and_steps_on_the_device(prefix):
         r = gold["pgrad." + k]
         assert np.allclose(_np(g), r, atol=2e-6 + 2e-4 * np.abs(r).max()), (k, np.abs(_np(g) - r).max())
     # the split forms the trainer uses: the same losses
-    m2 = _model(prefix, args)
+    m2 = golden_model("COMA", args, prefix + "_state_dict.npz", "cuda")
     m2.sample_source = _recorded(gold["sampled"])
     p2, _, _ = m2.get_loss(batch, need="policy")
-    _, v2, _ = _model(prefix, args).get_loss(batch, need="value")
+    _, v2, _ = golden_model("COMA", args, prefix + "_state_dict.npz", "cuda").get_loss(batch, need="value")
     assert abs(p2.item() - pl.item()) < 1e-6 and abs(v2.item() - vl.item()) < 1e-6 * max(1.0, abs(vl.item()))
     # one value and one policy step through the trainer, then the target update
     trainer = PGTrainer(args, COMA, StubEnv(args.agent_num), None)
     net = trainer.behaviour_net
-    sd0 = _load(f"{prefix}_state_dict.npz")
+    sd0 = golden_tensors(f"{prefix}_state_dict.npz", "cuda")
     net.load_state_dict(sd0)
     net.target_net.load_state_dict({k[len("target_net."):]: v for k, v in sd0.items() if k.startswith("target_net.")})
     net.sample_source = _recorded(gold["step.sampled_policy"])
     stat = {}
     trainer.value_transition_process(stat, batch)
     trainer.policy_transition_process(stat, batch)
-    after = _load(f"{prefix}_state_dict_after_step.npz")
+    after = golden_tensors(f"{prefix}_state_dict_after_step.npz", "cuda")
     cur = net.state_dict()
     for k, v in after.items():
         assert np.allclose(_np(cur[k]), _np(v), atol=5e-5), (k, np.abs(_np(cur[k]) - _np(v)).max())
     net.update_target()
     cur = net.target_net.state_dict()
-    for k, v in _load(f"{prefix}_target_after_update.npz").items():
+    for k, v in golden_tensors(f"{prefix}_target_after_update.npz", "cuda").items():
         assert np.allclose(_np(cur[k]), _np(v), atol=5e-5), k
     assert "coma" not in util.FALLBACKS and "coma_policy_loss" not in util.FALLBACKS, util.FALLBACKS
 
@@ -232,11 +185,11 @@ def test_unshared_critics_fall_back_and_are_counted():
     from safe_marl_amd import util
     from safe_marl_amd.learner import COMA
     util.FALLBACKS.pop("coma", None)
-    args = _args("coma", shared_params=False)
-    gold = _gold("coma")
+    args = golden_args("coma", cuda=True, shared_params=False)
+    gold = golden_vectors("coma")
     th.manual_seed(0)
     m = COMA(args, COMA(args).cuda()).cuda()
-    batch = _batch("coma", gold)
+    batch = golden_batch("coma", "cuda", gold=gold, fields=("action",))
     m.sample_source = _recorded(gold["sampled"])
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
@@ -289,7 +242,8 @@ def test_short_training_run_ends_with_finite_weights_and_an_emptied_replay():
     net = create_network(env_args)
     n_envs = 64
     env = VecFlexProvisionEnv(env_args, n_envs, net=net, series=make_synthetic_series(net, n_days=60), seed=3, warm_start=True)
-    args = _args("coma", agent_num=env.n_agents, obs_size=env.obs_size, state_size=env.state_size, v_min=0.9, v_max=1.1)
+    args = golden_args("coma", cuda=True, agent_num=env.n_agents, obs_size=env.obs_size, state_size=env.state_size,
+                       v_min=0.9, v_max=1.1)
     assert args.behaviour_update_freq == 60 and args.value_update_epochs == 10 and args.policy_update_epochs == 1
     th.manual_seed(0)
     np.random.seed(0)

@@ -2,62 +2,14 @@
 reference's own modules (tests/golden/make_facmaddpg_golden.py), the update cadence with the mixer, the C ABI's argument
 checks of flexnet_qmix_*, the kernels' resources and the two-rank path on gloo."""
 import ctypes as C
-import json
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch as th
 
-G = os.path.join(os.path.dirname(__file__), "golden")
-
-
-def _args(prefix="facmaddpg"):
-    from safe_marl_amd.util import convert
-    return convert(json.load(open(os.path.join(G, prefix + "_args.json"))))
-
-
-def _load(name):
-    z = np.load(os.path.join(G, name))
-    return {k: th.from_numpy(z[k]) for k in z.files}
-
-
-def _sd(prefix, name):
-    sd = _load(f"{prefix}_{name}.npz")
-    sd.update(_load(f"{prefix}_{name}_mixer.npz"))
-    return sd
-
-
-def _full_sd(prefix):
-    """The behaviour net's initial state_dict; its target replica's mixer is the initial mixer (reload_params_to_target)."""
-    sd = _sd(prefix, "state_dict")
-    sd.update({"target_net." + k: v for k, v in sd.items() if k.startswith("mixer.")})
-    return sd
-
-
-def _batch(prefix):
-    from safe_marl_amd.replay_buffer import Transition
-    z = np.load(os.path.join(G, "learner_batch.npz" if prefix == "facmaddpg" else "learner3_batch.npz"))
-    return Transition(**{k: th.from_numpy(z[k]).float() for k in Transition._fields})
-
-
-def _model(args, prefix):
-    from safe_marl_amd.learner import FACMADDPG
-    model = FACMADDPG(args, FACMADDPG(args))
-    res = model.load_state_dict(_full_sd(prefix), strict=True)      # the reference's keys and shapes, mixer included
-    assert not res.missing_keys and not res.unexpected_keys
-    return model
-
-
-class StubEnv:
-    n_envs = 1
-
-    def __init__(self, n):
-        self.n = n
-
-    def get_num_of_agents(self):
-        return self.n
+from .golden_io import (G, StubEnv, _free_port, facmaddpg_state_dict, golden_args, golden_batch, golden_model, golden_tensors,
+                        golden_vectors)
 
 
 PREFIXES = ["facmaddpg", "facmaddpg3"]
@@ -66,21 +18,21 @@ PREFIXES = ["facmaddpg", "facmaddpg3"]
 def test_mixer_state_dict_keys_match_the_reference():
     from safe_marl_amd.nets import QMIX_PARAMS
     for prefix in PREFIXES:
-        args = _args(prefix)
+        args = golden_args(prefix)
         from safe_marl_amd.nets import QMixer
         mixer = QMixer(args)
-        ref = _load(f"{prefix}_state_dict_mixer.npz")
+        ref = golden_tensors(f"{prefix}_state_dict_mixer.npz")
         assert sorted("mixer." + k for k in mixer.state_dict()) == sorted(ref)
         assert sorted(QMIX_PARAMS) == sorted(mixer.state_dict())
         for k, v in mixer.state_dict().items():
             assert tuple(v.shape) == tuple(ref["mixer." + k].shape)
-    n = sum(p.numel() for p in QMixer(_args()).parameters())
+    n = sum(p.numel() for p in QMixer(golden_args("facmaddpg")).parameters())
     assert n == 209601                                               # 5 agents, S = 720
 
 
 def test_init_weights_reach_the_mixer():
     from safe_marl_amd.learner import FACMADDPG
-    args = _args()
+    args = golden_args("facmaddpg")
     th.manual_seed(0)
     m = FACMADDPG(args)
     w = m.mixer.hyper_w_1[0].weight.detach()
@@ -89,11 +41,11 @@ def test_init_weights_reach_the_mixer():
 
 @pytest.mark.parametrize("prefix", PREFIXES)
 def test_value_qtot_losses_and_grads(prefix):
-    args = _args(prefix)
-    gold = dict(np.load(os.path.join(G, prefix + "_golden.npz")))
+    args = golden_args(prefix)
+    gold = golden_vectors(prefix)
     mgold = dict(np.load(os.path.join(G, prefix + "_golden_mixer_grads.npz")))
-    model = _model(args, prefix)
-    batch = _batch(prefix)
+    model = golden_model("FACMADDPG", args, facmaddpg_state_dict(prefix, target_mixer=True))
+    batch = golden_batch(prefix)
     n, o = args.agent_num, args.obs_size
     with th.no_grad():
         v = model.value(batch.state, batch.action)
@@ -106,7 +58,7 @@ def test_value_qtot_losses_and_grads(prefix):
         nv = model.target_net.value(batch.next_state, na).view(-1, n)
         nq = model.target_net.mixer(nv, batch.next_state.reshape(b, n * o)).view(-1, 1)
         assert np.allclose(nq.numpy(), gold["next_q_tot"], atol=1e-4, rtol=1e-5)
-    model = _model(args, prefix)
+    model = golden_model("FACMADDPG", args, facmaddpg_state_dict(prefix, target_mixer=True))
     pl, vl, _ = model.get_loss(batch)
     assert abs(vl.item() - float(gold["value_loss"])) < 1e-4 * max(1.0, abs(float(gold["value_loss"])))
     assert abs(pl.item() - float(gold["policy_loss"])) < 1e-5
@@ -126,11 +78,11 @@ def test_value_qtot_losses_and_grads(prefix):
 @pytest.mark.parametrize("prefix", PREFIXES)
 def test_split_losses_give_each_optimiser_the_reference_gradients(prefix):
     """need="value" differentiates the critic only, need="mixer" the mixer only: same loss, same gradients."""
-    args = _args(prefix)
+    args = golden_args(prefix)
     mgold = dict(np.load(os.path.join(G, prefix + "_golden_mixer_grads.npz")))
-    gold = dict(np.load(os.path.join(G, prefix + "_golden.npz")))
-    model = _model(args, prefix)
-    batch = _batch(prefix)
+    gold = golden_vectors(prefix)
+    model = golden_model("FACMADDPG", args, facmaddpg_state_dict(prefix, target_mixer=True))
+    batch = golden_batch(prefix)
     _, vl, _ = model.get_loss(batch, need="value")
     crit = list(model.value_dicts.parameters())
     mix = list(model.mixer.parameters())
@@ -149,16 +101,17 @@ def test_split_losses_give_each_optimiser_the_reference_gradients(prefix):
 def test_trainer_steps_value_policy_mixer_and_target_update(prefix):
     from safe_marl_amd.learner import FACMADDPG
     from safe_marl_amd.trainer import PGTrainer
-    args = _args(prefix)
-    gold = dict(np.load(os.path.join(G, prefix + "_golden.npz")))
+    args = golden_args(prefix)
+    gold = golden_vectors(prefix)
     trainer = PGTrainer(args, FACMADDPG, StubEnv(args.agent_num), None)
-    trainer.behaviour_net.load_state_dict(_full_sd(prefix))
-    trainer.behaviour_net.target_net.load_state_dict({k[len("target_net."):]: v for k, v in _full_sd(prefix).items()
+    sd = facmaddpg_state_dict(prefix, target_mixer=True)
+    trainer.behaviour_net.load_state_dict(sd)
+    trainer.behaviour_net.target_net.load_state_dict({k[len("target_net."):]: v for k, v in sd.items()
                                                        if k.startswith("target_net.")})
     assert trainer.mixer_optimizer.param_groups[0]["lr"] == args.mixer_lrate
     assert {id(p) for p in trainer.mixer_optimizer.param_groups[0]["params"]} == \
         {id(p) for p in trainer.behaviour_net.mixer.parameters()}
-    batch = _batch(prefix)
+    batch = golden_batch(prefix)
     stat = {}
     trainer.value_transition_process(stat, batch)
     trainer.policy_transition_process(stat, batch)
@@ -167,12 +120,12 @@ def test_trainer_steps_value_policy_mixer_and_target_update(prefix):
               "mean_train_policy_grad_norm", "mean_train_mixer_grad_norm"):
         ref = gold["stat." + k]
         assert abs(float(stat[k]) - ref) < 1e-4 * max(1.0, abs(ref)), k
-    after = _sd(prefix, "state_dict_after_step")
+    after = facmaddpg_state_dict(prefix, "state_dict_after_step")
     sd = trainer.behaviour_net.state_dict()
     for k, v in after.items():
         assert np.allclose(sd[k].numpy(), v.numpy(), atol=2e-5), k
     trainer.behaviour_net.update_target()
-    tgt = _sd(prefix, "target_after_update")
+    tgt = facmaddpg_state_dict(prefix, "target_after_update")
     tsd = trainer.behaviour_net.target_net.state_dict()
     for k, v in tgt.items():
         assert np.allclose(tsd[k].numpy(), v.numpy(), atol=2e-5), k
@@ -181,8 +134,8 @@ def test_trainer_steps_value_policy_mixer_and_target_update(prefix):
 
 def test_update_event_order_is_value_policy_mixer():
     from safe_marl_amd.learner import FACMADDPG
-    args = _args()._replace(value_update_epochs=2, policy_update_epochs=1, mixer_update_epochs=3, replay_warmup=0,
-                            behaviour_update_freq=1, target_update_freq=10 ** 9)
+    args = golden_args("facmaddpg")._replace(value_update_epochs=2, policy_update_epochs=1, mixer_update_epochs=3,
+                                             replay_warmup=0, behaviour_update_freq=1, target_update_freq=10 ** 9)
     model = FACMADDPG(args)
 
     class Buf:
@@ -256,12 +209,6 @@ def test_qmix_kernels_have_no_scratch():
         assert v.get("scratch_bytes_per_lane", 0) == 0 and v.get("vgpr_spills", 0) == 0
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 def _worker(rank, world, port, out):
     import torch.distributed as dist
     import safe_marl_amd  # noqa: F401
@@ -270,11 +217,11 @@ def _worker(rank, world, port, out):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    args = _args()
+    args = golden_args("facmaddpg")
     th.manual_seed(200 + rank)                    # different initial weights per rank: rank 0's are broadcast
     trainer = PGTrainer(args, FACMADDPG, StubEnv(5), None)
     w0 = th.cat([p.detach().reshape(-1) for p in trainer.behaviour_net.parameters()])
-    full = _batch("facmaddpg")
+    full = golden_batch("facmaddpg")
     lo, hi = (0, 16) if rank == 0 else (16, 32)
     batch = type(full)(*[f[lo:hi] for f in full])
     stat = {}

@@ -1,80 +1,27 @@
 """FACMADDPG on the GPU (csrc/qmix.hip for the mixer) against the reference's own modules (tests/golden/facmaddpg*_*,
 make_facmaddpg_golden.py), and a short vectorised training run with the mixer's sub-updates."""
-import json
 import os
 
 import numpy as np
 import pytest
 import torch as th
 
+from .golden_io import (G, StubEnv, _grads, _np, facmaddpg_state_dict, golden_args, golden_batch, golden_model,
+                        golden_vectors)
+
 pytestmark = pytest.mark.gpu
-G = os.path.join(os.path.dirname(__file__), "golden")
+
 PREFIXES = ["facmaddpg", "facmaddpg3"]
-
-
-def _args(prefix, **over):
-    from safe_marl_amd.util import convert
-    d = json.load(open(os.path.join(G, prefix + "_args.json")))
-    d.update(cuda=True)
-    d.update(over)
-    return convert(d)
-
-
-def _load(name):
-    z = np.load(os.path.join(G, name))
-    return {k: th.from_numpy(z[k]).cuda() for k in z.files}
-
-
-def _sd(prefix, name):
-    sd = _load(f"{prefix}_{name}.npz")
-    sd.update(_load(f"{prefix}_{name}_mixer.npz"))
-    return sd
-
-
-def _full_sd(prefix):
-    sd = _sd(prefix, "state_dict")
-    sd.update({"target_net." + k: v for k, v in sd.items() if k.startswith("mixer.")})
-    return sd
-
-
-def _batch(prefix, tile=1):
-    from safe_marl_amd.replay_buffer import Transition
-    z = np.load(os.path.join(G, "learner_batch.npz" if prefix == "facmaddpg" else "learner3_batch.npz"))
-    out = {}
-    for k in Transition._fields:
-        t = th.from_numpy(z[k]).float().cuda()
-        out[k] = t.repeat((tile,) + (1,) * (t.dim() - 1)).contiguous()
-    return Transition(**out)
-
-
-class StubEnv:
-    n_envs = 1
-
-    def __init__(self, n):
-        self.n = n
-
-    def get_num_of_agents(self):
-        return self.n
-
-
-def _np(t):
-    return t.detach().float().cpu().numpy()
-
-
-def _grads(loss, params):
-    return [_np(g) for g in th.autograd.grad(loss, list(params))]
 
 
 @pytest.mark.parametrize("prefix,tile", [("facmaddpg", 1), ("facmaddpg", 64), ("facmaddpg3", 64)])
 def test_losses_and_grads_match_the_reference(prefix, tile):
     from safe_marl_amd.learner import FACMADDPG
-    args = _args(prefix)
-    gold = dict(np.load(os.path.join(G, prefix + "_golden.npz")))
+    args = golden_args(prefix, cuda=True)
+    gold = golden_vectors(prefix)
     mgold = dict(np.load(os.path.join(G, prefix + "_golden_mixer_grads.npz")))
-    model = FACMADDPG(args, FACMADDPG(args).cuda()).cuda()
-    res = model.load_state_dict(_full_sd(prefix), strict=True)
-    assert not res.missing_keys and not res.unexpected_keys
-    b = _batch(prefix, tile)
+    model = golden_model(FACMADDPG, args, facmaddpg_state_dict(prefix, device="cuda", target_mixer=True), "cuda")
+    b = golden_batch(prefix, "cuda", tile)
     n, o = args.agent_num, args.obs_size
     assert model.mixer.fused_supported(b.reward, b.state.reshape(-1, n * o))         # the HIP path is the one under test
     with th.no_grad():
@@ -106,13 +53,13 @@ def test_losses_and_grads_match_the_reference(prefix, tile):
 def test_trainer_steps_and_target_update_match_the_reference(prefix):
     from safe_marl_amd.learner import FACMADDPG
     from safe_marl_amd.trainer import PGTrainer
-    args = _args(prefix)
-    gold = dict(np.load(os.path.join(G, prefix + "_golden.npz")))
+    args = golden_args(prefix, cuda=True)
+    gold = golden_vectors(prefix)
     tr = PGTrainer(args, FACMADDPG, StubEnv(args.agent_num), None)
-    sd = _full_sd(prefix)
+    sd = facmaddpg_state_dict(prefix, device="cuda", target_mixer=True)
     tr.behaviour_net.load_state_dict(sd)
     tr.behaviour_net.target_net.load_state_dict({k[len("target_net."):]: v for k, v in sd.items() if k.startswith("target_net.")})
-    b = _batch(prefix)
+    b = golden_batch(prefix, "cuda")
     stat = {}
     tr.value_transition_process(stat, b)
     tr.policy_transition_process(stat, b)
@@ -120,12 +67,12 @@ def test_trainer_steps_and_target_update_match_the_reference(prefix):
     for k in ("mean_train_value_loss", "mean_train_mixer_loss", "mean_train_value_grad_norm", "mean_train_mixer_grad_norm"):
         ref = gold["stat." + k]
         assert abs(float(stat[k]) - ref) < 2e-4 * max(1.0, abs(ref)), k
-    after = _sd(prefix, "state_dict_after_step")
+    after = facmaddpg_state_dict(prefix, "state_dict_after_step", "cuda")
     cur = tr.behaviour_net.state_dict()
     for k, v in after.items():
         assert np.allclose(_np(cur[k]), _np(v), atol=5e-5), (k, np.abs(_np(cur[k]) - _np(v)).max())
     tr.behaviour_net.update_target()
-    tgt = _sd(prefix, "target_after_update")
+    tgt = facmaddpg_state_dict(prefix, "target_after_update", "cuda")
     cur = tr.behaviour_net.target_net.state_dict()
     for k, v in tgt.items():
         assert np.allclose(_np(cur[k]), _np(v), atol=5e-5), k
@@ -141,8 +88,8 @@ def test_short_training_run_moves_the_mixer():
     env_args = {"buildings": blds, "pv_nodes": blds, "ess_nodes": blds}
     net = create_network(env_args)
     env = VecFlexProvisionEnv(env_args, 256, net=net, series=make_synthetic_series(net, n_days=60), seed=3, warm_start=True)
-    args = _args("facmaddpg", agent_num=env.n_agents, obs_size=env.obs_size, state_size=env.state_size, v_min=0.9,
-                 v_max=1.1, target_update_freq=60)
+    args = golden_args("facmaddpg", cuda=True, agent_num=env.n_agents, obs_size=env.obs_size, state_size=env.state_size,
+                       v_min=0.9, v_max=1.1, target_update_freq=60)
     th.manual_seed(0)
     np.random.seed(0)
     tr = PGTrainer(args, learner.FACMADDPG, env, None, batch_scale=64, replay_capacity=256 * 96 * 2)

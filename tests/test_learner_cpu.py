@@ -1,54 +1,26 @@
 """Learner parity against golden vectors captured by importing the reference's own torch modules
 (tests/golden/make_learner_golden.py).  fp32 arithmetic: tolerances are stated per check."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch as th
 
-from safe_marl_amd.util import convert, select_action, translate_action
+from safe_marl_amd.util import select_action, translate_action
 from safe_marl_amd.learner import MADDPG
 from safe_marl_amd.replay_buffer import DeviceReplayBuffer, Transition, TransReplayBuffer
 from safe_marl_amd.trainer import PGTrainer
 
-G = os.path.join(os.path.dirname(__file__), "golden")
+from .golden_io import (StubEnv, golden_args, golden_batch as _batch, golden_model, golden_tensors as _load_sd,
+                        golden_vectors)
 
 
 @pytest.fixture(scope="module")
 def gold():
-    return dict(np.load(os.path.join(G, "learner_golden.npz")))
+    return golden_vectors("learner")
 
 
 @pytest.fixture(scope="module")
 def args():
-    return convert(json.load(open(os.path.join(G, "learner_args.json"))))
-
-
-def _load_sd(name):
-    z = np.load(os.path.join(G, name))
-    return {k: th.from_numpy(z[k]) for k in z.files}
-
-
-def _batch(device="cpu"):
-    z = np.load(os.path.join(G, "learner_batch.npz"))
-    return Transition(**{k: th.from_numpy(z[k]).float().to(device) for k in Transition._fields})
-
-
-def _model(args):
-    target = MADDPG(args)
-    model = MADDPG(args, target)
-    sd = _load_sd("learner_state_dict.npz")
-    missing = model.load_state_dict(sd, strict=True)      # same keys and shapes as the reference's state_dict
-    assert not missing.missing_keys and not missing.unexpected_keys
-    return model
-
-
-class StubEnv:
-    n_envs = 1
-
-    def get_num_of_agents(self):
-        return 5
+    return golden_args()
 
 
 def test_select_and_translate_action(gold, args):
@@ -68,7 +40,7 @@ def test_select_and_translate_action(gold, args):
 
 
 def test_policy_value_loss_and_grads(gold, args):
-    model = _model(args)
+    model = golden_model(MADDPG, args, "learner_state_dict.npz")
     batch = _batch()
     unpacked = model.unpack_data(batch)
     assert np.allclose(unpacked[5].detach().numpy(), gold["unpack_reward_bn"], atol=2e-5)      # reward BatchNorm
@@ -77,7 +49,7 @@ def test_policy_value_loss_and_grads(gold, args):
     assert np.allclose(hiddens.detach().numpy(), gold["policy_hiddens"], atol=2e-6)
     v = model.value(batch.state, batch.action)
     assert np.allclose(v.detach().numpy(), gold["value_sa"], atol=1e-5)
-    model = _model(args)
+    model = golden_model(MADDPG, args, "learner_state_dict.npz")
     policy_loss, value_loss, _ = model.get_loss(batch)
     assert abs(policy_loss.item() - gold["policy_loss"]) < 2e-6
     assert abs(value_loss.item() - gold["value_loss"]) < 1e-5 * max(1.0, abs(gold["value_loss"]))
@@ -154,7 +126,7 @@ def test_add_experience_accepts_reference_transitions(args):
 def test_transition_update_schedule(gold, args):
     """model.py:40-71: 10 value + 1 policy sub-updates whenever steps % 60 == 0 (and steps > 0, buffer >= 32);
     target update whenever steps % 120 == 0 — including steps == 0, before the first increment."""
-    model = _model(args)
+    model = golden_model(MADDPG, args, "learner_state_dict.npz")
 
     class StubTrainer:
         def __init__(self):
@@ -186,7 +158,7 @@ def test_transition_update_schedule(gold, args):
 def test_critic_block_form_equals_explicit_input(args):
     """The critic's column-block evaluation equals fc1 applied to the explicit [obs_all | onehot | acts] rows of
     maddpg.py:33-76, values and own-action gradients alike."""
-    model = _model(args)
+    model = golden_model(MADDPG, args, "learner_state_dict.npz")
     th.manual_seed(0)
     b, n = 6, 5
     obs = th.randn(b, n, 144)
@@ -211,10 +183,7 @@ def test_critic_block_form_equals_explicit_input(args):
 def test_matd3_matches_reference(gold, args):
     """madrl/models/matd3.py: twin-flag critic, min-of-twins target, agent-summed action quirk."""
     from safe_marl_amd.learner import MATD3
-    target = MATD3(args)
-    model = MATD3(args, target)
-    res = model.load_state_dict(_load_sd("matd3_state_dict.npz"), strict=True)
-    assert not res.missing_keys and not res.unexpected_keys
+    model = golden_model(MATD3, args, "matd3_state_dict.npz")
     assert model.value_dicts[0].fc1.in_features == 746
     batch = _batch()
     v = model.value(batch.state, batch.action)
@@ -245,9 +214,7 @@ def test_matd3_matches_reference(gold, args):
 def test_iddpg_matches_reference(gold, args):
     """madrl/models/iddpg.py + learning_algorithms/ddpg.py: independent critics on (o_i, id_i, a_i)."""
     from safe_marl_amd.learner import IDDPG
-    model = IDDPG(args, IDDPG(args))
-    res = model.load_state_dict(_load_sd("iddpg_state_dict.npz"), strict=True)
-    assert not res.missing_keys and not res.unexpected_keys
+    model = golden_model(IDDPG, args, "iddpg_state_dict.npz")
     assert model.value_dicts[0].fc1.in_features == 144 + 4 + 5
     batch = _batch()
     v = model.value(batch.state, batch.action)
@@ -292,13 +259,8 @@ def test_run_lengths_cover_the_training_loops_schedule():
 def test_three_agent_maddpg_matches_the_reference():
     """BASELINE.json config 3 (3 agents: critic input (144 + 4) * 3 + 3, maddpg.py:18-27): the learner3_* fixtures
     (make_learner_golden.py --agents 3) — values, losses, every gradient, one value + one policy step, target update."""
-    gold = dict(np.load(os.path.join(G, "learner3_golden.npz")))
-    args = convert(json.load(open(os.path.join(G, "learner3_args.json"))))
-    z = np.load(os.path.join(G, "learner3_batch.npz"))
-    batch = Transition(**{k: th.from_numpy(z[k]).float() for k in Transition._fields})
-    model = MADDPG(args, MADDPG(args))
-    res = model.load_state_dict(_load_sd("learner3_state_dict.npz"), strict=True)
-    assert not res.missing_keys and not res.unexpected_keys
+    gold, args, batch = golden_vectors("learner3"), golden_args("learner3"), _batch("learner3")
+    model = golden_model(MADDPG, args, "learner3_state_dict.npz")
     assert tuple(model.value_dicts[0].fc1.weight.shape) == (64, 447)
     means, _, hiddens = model.policy(batch.state, last_hid=batch.last_hid)
     assert np.allclose(means.detach().numpy(), gold["policy_means"], atol=2e-6)
@@ -312,13 +274,7 @@ def test_three_agent_maddpg_matches_the_reference():
         ref = gold["vgrad." + k]
         assert np.allclose(p.grad.numpy(), ref, atol=2e-6 + 1e-4 * np.abs(ref).max()), k
 
-    class Env3:
-        n_envs = 1
-
-        def get_num_of_agents(self):
-            return 3
-
-    trainer = PGTrainer(args, MADDPG, Env3(), None)
+    trainer = PGTrainer(args, MADDPG, StubEnv(3), None)
     trainer.behaviour_net.load_state_dict(_load_sd("learner3_state_dict.npz"))
     stat = {}
     trainer.value_transition_process(stat, batch)

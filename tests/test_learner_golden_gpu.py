@@ -12,15 +12,13 @@ losses, gradients, the RMSprop step and the target update are invariant under ti
 running_var sees the unbiased n/(n-1) factor, which the test accounts for).  Tolerances are those of the CPU test
 (tests/test_learner_cpu.py): losses 1e-5, gradients 2e-6 + 1e-4 max|g|, post-step weights 3e-6 (+ the RMSprop
 sensitivity of near-zero gradients, stated below)."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch as th
 
+from .golden_io import StubEnv, _grads, _np, golden_args, golden_batch, golden_model, golden_tensors, golden_vectors
+
 pytestmark = pytest.mark.gpu
-G = os.path.join(os.path.dirname(__file__), "golden")
 
 # 1: 32 samples (small-batch kernels); 64: 2 048 samples = 10 240 actor rows (wgrad + lnrelu + VALU critic tail);
 # 2048: 65 536 samples = 327 680 rows (matrix-core critic tail / pgrad kernels, MFMA actor at full width)
@@ -29,57 +27,7 @@ TILES = [1, 64, 2048]
 
 @pytest.fixture(scope="module")
 def gold():
-    return dict(np.load(os.path.join(G, "learner_golden.npz")))
-
-
-def _args(prefix="learner", **over):
-    from safe_marl_amd.util import convert
-    d = json.load(open(os.path.join(G, prefix + "_args.json")))
-    d.update(cuda=True)
-    d.update(over)
-    return convert(d)
-
-
-def _load_sd(name):
-    z = np.load(os.path.join(G, name))
-    return {k: th.from_numpy(z[k]) for k in z.files}
-
-
-def _batch(tile=1, prefix="learner"):
-    from safe_marl_amd.replay_buffer import Transition
-    z = np.load(os.path.join(G, prefix + "_batch.npz"))
-    out = {}
-    for k in Transition._fields:
-        t = th.from_numpy(z[k]).float().cuda()
-        out[k] = t.repeat((tile,) + (1,) * (t.dim() - 1)).contiguous()
-    return Transition(**out)
-
-
-class StubEnv:
-    n_envs = 1
-
-    def __init__(self, n=5):
-        self.n = n
-
-    def get_num_of_agents(self):
-        return self.n
-
-
-def _model(cls, sd_name, prefix="learner"):
-    args = _args(prefix)
-    model = cls(args, cls(args).cuda()).cuda()
-    res = model.load_state_dict(_load_sd(sd_name), strict=True)
-    assert not res.missing_keys and not res.unexpected_keys
-    return model
-
-
-def _np(t):
-    return t.detach().float().cpu().numpy()
-
-
-def _grads(loss, params):
-    """what trainer._sub_update hands the optimiser: d loss / d (this optimiser's parameters)"""
-    return [_np(g) for g in th.autograd.grad(loss, list(params), allow_unused=False)]
+    return golden_vectors("learner")
 
 
 def _loaded_lib():
@@ -92,11 +40,11 @@ def test_maddpg_forward_losses_and_grads_match_the_reference(gold, tile):
     """maddpg.py:33-123 on the GPU: policy(), value(), both losses and every parameter gradient."""
     from safe_marl_amd.learner import MADDPG
     _loaded_lib()
-    b = _batch(tile)
-    model = _model(MADDPG, "learner_state_dict.npz")
+    b = golden_batch("learner", "cuda", tile)
+    model = golden_model(MADDPG, golden_args(cuda=True), "learner_state_dict.npz", "cuda")
     # reward BatchNorm of unpack_data (model.py:321-322): biased batch statistics -> tiling-invariant
     assert np.allclose(_np(model.unpack_data(b)[5])[:32], gold["unpack_reward_bn"], atol=2e-5)
-    model = _model(MADDPG, "learner_state_dict.npz")
+    model = golden_model(MADDPG, golden_args(cuda=True), "learner_state_dict.npz", "cuda")
     with th.no_grad():                                   # fused inference kernel (csrc/actor.hip)
         means, _, hid = model.policy(b.state, last_hid=b.last_hid)
     assert np.allclose(_np(means)[:32], gold["policy_means"], atol=5e-6)
@@ -111,11 +59,11 @@ def test_maddpg_forward_losses_and_grads_match_the_reference(gold, tile):
     assert np.allclose(_np(v_g)[:32], gold["value_sa"], atol=2e-5)
 
     # the reference's call (both losses), then the single-loss evaluations the trainer uses
-    model = _model(MADDPG, "learner_state_dict.npz")
+    model = golden_model(MADDPG, golden_args(cuda=True), "learner_state_dict.npz", "cuda")
     pl, vl, _ = model.get_loss(b)
     assert abs(pl.item() - gold["policy_loss"]) < 1e-5
     assert abs(vl.item() - gold["value_loss"]) < 1e-5 * max(1.0, abs(gold["value_loss"]))
-    model = _model(MADDPG, "learner_state_dict.npz")
+    model = golden_model(MADDPG, golden_args(cuda=True), "learner_state_dict.npz", "cuda")
     _, vl, _ = model.get_loss(b, need="value")           # csrc/tdloss.hip, critic kernels, fused bootstrap actor
     assert abs(vl.item() - gold["value_loss"]) < 1e-5 * max(1.0, abs(gold["value_loss"]))
     names = [k for k, _ in model.value_dicts.named_parameters()]
@@ -143,8 +91,8 @@ def _check_after_step(gold, trainer, stat, n_rows, label, fixtures="learner"):
     for k in ("mean_train_value_grad_norm", "mean_train_value_loss", "mean_train_policy_grad_norm",
               "mean_train_policy_loss", "mean_train_entropy"):
         assert abs(float(stat[k]) - gold["stat." + k]) < 1e-4 * max(1.0, abs(gold["stat." + k])), (label, k)
-    after = _load_sd(fixtures + "_state_dict_after_step.npz")
-    before = _load_sd(fixtures + "_state_dict.npz")
+    after = golden_tensors(fixtures + "_state_dict_after_step.npz")
+    before = golden_tensors(fixtures + "_state_dict.npz")
     mine = {k: v.detach().cpu() for k, v in trainer.behaviour_net.state_dict().items()}
     # RMSprop's first step is lr * g / (0.1 |g| + eps): for |g| >> 10 eps it is +-10 lr whatever g is, for a near-zero
     # gradient it moves by (lr eps / (0.1 |g| + eps)^2) per unit of gradient error.  Tolerance = 3e-6 (the CPU test's) +
@@ -182,16 +130,16 @@ def test_maddpg_one_optimizer_step_and_target_update_match_the_reference(gold, t
     from safe_marl_amd.learner import MADDPG
     from safe_marl_amd.trainer import PGTrainer
     _loaded_lib()
-    trainer = PGTrainer(_args(), MADDPG, StubEnv(), None)
+    trainer = PGTrainer(golden_args(cuda=True), MADDPG, StubEnv(), None)
     assert trainer.device.type == "cuda"
-    trainer.behaviour_net.load_state_dict(_load_sd("learner_state_dict.npz"))
-    b = _batch(tile)
+    trainer.behaviour_net.load_state_dict(golden_tensors("learner_state_dict.npz"))
+    b = golden_batch("learner", "cuda", tile)
     stat = {}
     trainer.value_transition_process(stat, b)
     trainer.policy_transition_process(stat, b)
     _check_after_step(gold, trainer, stat, 32 * tile, f"eager x{tile}")
     trainer.behaviour_net.update_target()
-    tgt = _load_sd("learner_target_after_update.npz")
+    tgt = golden_tensors("learner_target_after_update.npz")
     mine_t = trainer.behaviour_net.target_net.state_dict()
     for k, ref in tgt.items():
         if ref.is_floating_point() and "batchnorm" not in k:
@@ -208,12 +156,12 @@ def test_maddpg_graphed_sub_updates_match_the_reference(gold):
     _loaded_lib()
     tile = 64
     bs = 32 * tile
-    args = _args()
+    args = golden_args(cuda=True)
     trainer = PGTrainer(args, MADDPG, StubEnv(), None, batch_scale=tile, replay_capacity=4 * bs, graph_updates=True)
-    trainer.behaviour_net.load_state_dict(_load_sd("learner_state_dict.npz"))
+    trainer.behaviour_net.load_state_dict(golden_tensors("learner_state_dict.npz"))
     buf = trainer.replay_buffer
     n, o, a, h = 5, 144, 4, 64
-    b = _batch(tile)
+    b = golden_batch("learner", "cuda", tile)
     buf.alloc_slabs(bs, n, o, a, h)
     buf.begin_stream(b.state)
     buf.hid_ring[0].copy_(b.last_hid.reshape(bs, -1))
@@ -261,8 +209,8 @@ def test_matd3_matches_the_reference_on_the_gpu(gold, tile, monkeypatch):
     _loaded_lib()
     tdn, real, fake = _cpu_noise_for(tile)
     monkeypatch.setattr(tdn, "_standard_normal", fake)
-    model = _model(MATD3, "matd3_state_dict.npz")
-    b = _batch(tile)
+    model = golden_model(MATD3, golden_args(cuda=True), "matd3_state_dict.npz", "cuda")
+    b = golden_batch("learner", "cuda", tile)
     v = model.value(b.state, b.action)
     ref = gold["matd3_value"]                               # cat([Q1, Q2]) over 32 samples
     got = _np(v)
@@ -293,8 +241,8 @@ def test_iddpg_matches_the_reference_on_the_gpu(gold, tile):
     """iddpg.py:32-83 + learning_algorithms/ddpg.py:14-37 on the GPU."""
     from safe_marl_amd.learner import IDDPG
     _loaded_lib()
-    model = _model(IDDPG, "iddpg_state_dict.npz")
-    b = _batch(tile)
+    model = golden_model(IDDPG, golden_args(cuda=True), "iddpg_state_dict.npz", "cuda")
+    b = golden_batch("learner", "cuda", tile)
     v = model.value(b.state, b.action)
     assert np.allclose(_np(v)[:32], gold["iddpg_value"], atol=2e-5)
     pl, vl, _ = model.get_loss(b)
@@ -316,7 +264,7 @@ def test_iddpg_matches_the_reference_on_the_gpu(gold, tile):
 # fixtures: tests/golden/learner3_* = make_learner_golden.py --agents 3 (the reference's own modules, imported)
 @pytest.fixture(scope="module")
 def gold3():
-    return dict(np.load(os.path.join(G, "learner3_golden.npz")))
+    return golden_vectors("learner3")
 
 
 @pytest.mark.parametrize("tile", TILES)
@@ -329,12 +277,12 @@ def test_maddpg_3_agents_losses_grads_step_and_target_match_the_reference(gold3,
     _loaded_lib()
     util.FALLBACKS.clear()                                  # (other tests of the session decline shapes on purpose)
     gold, P = gold3, "learner3"
-    b = _batch(tile, P)
+    b = golden_batch(P, "cuda", tile)
     assert b.state.shape[1:] == (3, 144) and b.action.shape[1:] == (3, 4)
-    model = _model(MADDPG, P + "_state_dict.npz", P)
+    model = golden_model(MADDPG, golden_args(P, cuda=True), P + "_state_dict.npz", "cuda")
     assert model.value_dicts[0].fc1.weight.shape == (64, (144 + 4) * 3 + 3)
     assert np.allclose(_np(model.unpack_data(b)[5])[:32], gold["unpack_reward_bn"], atol=2e-5)
-    model = _model(MADDPG, P + "_state_dict.npz", P)
+    model = golden_model(MADDPG, golden_args(P, cuda=True), P + "_state_dict.npz", "cuda")
     with th.no_grad():
         means, _, hid = model.policy(b.state, last_hid=b.last_hid)
         v = model.value(b.state, b.action)
@@ -354,14 +302,14 @@ def test_maddpg_3_agents_losses_grads_step_and_target_match_the_reference(gold3,
         ref = gold["pgrad." + k]
         assert np.allclose(g, ref, atol=2e-7 + 1e-4 * np.abs(ref).max()), (tile, k, np.abs(g - ref).max())
     # one optimiser step of each kind through the trainer, then the target update
-    trainer = PGTrainer(_args(P), MADDPG, StubEnv(3), None)
-    trainer.behaviour_net.load_state_dict(_load_sd(P + "_state_dict.npz"))
+    trainer = PGTrainer(golden_args(P, cuda=True), MADDPG, StubEnv(3), None)
+    trainer.behaviour_net.load_state_dict(golden_tensors(P + "_state_dict.npz"))
     stat = {}
     trainer.value_transition_process(stat, b)
     trainer.policy_transition_process(stat, b)
     _check_after_step(gold, trainer, stat, 32 * tile, f"3 agents x{tile}", P)
     trainer.behaviour_net.update_target()
-    tgt = _load_sd(P + "_target_after_update.npz")
+    tgt = golden_tensors(P + "_target_after_update.npz")
     mine_t = trainer.behaviour_net.target_net.state_dict()
     for k, ref in tgt.items():
         if ref.is_floating_point() and "batchnorm" not in k:
@@ -389,11 +337,11 @@ def test_config3_maddpg_3_agents_4096_envs_trains_on_graphs():
     net3 = create_network(env_args)
     series = make_synthetic_series(net3, n_days=60)
     env = VecFlexProvisionEnv(env_args, n_envs, net=net3, series=series, seed=1234, warm_start=True)
-    d = json.load(open(os.path.join(G, "learner3_args.json")))
-    d.update(cuda=True, agent_num=env.n_agents, obs_size=env.obs_size, state_size=env.state_size, v_min=0.9, v_max=1.1)
+    args = golden_args("learner3", cuda=True, agent_num=env.n_agents, obs_size=env.obs_size, state_size=env.state_size,
+                       v_min=0.9, v_max=1.1)
     th.manual_seed(0)
     np.random.seed(0)
-    trainer = PGTrainer(util.convert(d), MADDPG, env, None, batch_scale=n_envs // 4, replay_capacity=n_envs * 96 * 2)
+    trainer = PGTrainer(args, MADDPG, env, None, batch_scale=n_envs // 4, replay_capacity=n_envs * 96 * 2)
     model = trainer.behaviour_net
     assert model.n_ == 3 and tuple(model.value_dicts[0].fc1.weight.shape) == (64, (144 + 4) * 3 + 3)
     before = {k: v.detach().clone() for k, v in model.state_dict().items()}

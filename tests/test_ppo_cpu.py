@@ -3,69 +3,25 @@ importing the reference's own modules (tests/golden/make_ppo_golden.py); the nee
 evaluation of the reference's literal loop; the on-policy cadence (buffer clear, pooled step-aligned windows, capacity);
 the old values filed at the start of an update event against the per-step route; ppo_consistent_ratio; the C ABI; one update event on two gloo ranks."""
 import ctypes as C
-import json
 import os
 
 import numpy as np
 import pytest
 import torch as th
 
-G = os.path.join(os.path.dirname(__file__), "golden")
+import safe_marl_amd.learner as L
+
+from .golden_io import StubEnv, _free_port, golden_args, golden_batch, golden_model, golden_tensors, golden_vectors
+
+FIELDS = ("action", "done", "last_step")          # what the reference's PPO runs stored in the batch
 CASES = [("ippo", "IPPO"), ("mappo", "MAPPO"), ("ippo3", "IPPO"), ("mappo3", "MAPPO")]
 
 
-def _args(prefix, **over):
-    from safe_marl_amd.util import convert
-    d = json.load(open(os.path.join(G, prefix + "_args.json")))
-    d.update(over)
-    return convert(d)
-
-
-def _cls(name):
-    import safe_marl_amd.learner as L
-    return getattr(L, name)
-
-
-def _load(name):
-    z = np.load(os.path.join(G, name))
-    return {k: th.from_numpy(z[k]) for k in z.files}
-
-
-def _gold(prefix):
-    return dict(np.load(os.path.join(G, prefix + "_golden.npz")))
-
-
-def _batch(prefix, gold):
-    from safe_marl_amd.replay_buffer import Transition
-    z = dict(np.load(os.path.join(G, "learner3_batch.npz" if prefix.endswith("3") else "learner_batch.npz")))
-    z["action"], z["done"], z["last_step"] = gold["batch.action"], gold["batch.done"], gold["batch.last_step"]
-    return Transition(**{k: th.from_numpy(z[k]).float() for k in Transition._fields})
-
-
-def _model(prefix, name, **over):
-    cls = _cls(name)
-    args = _args(prefix, **over)
-    model = cls(args, cls(args))
-    res = model.load_state_dict(_load(f"{prefix}_state_dict.npz"), strict=True)        # the reference's keys and shapes
-    assert not res.missing_keys and not res.unexpected_keys
-    return model, args
-
-
-class StubEnv:
-    n_envs = 1
-
-    def __init__(self, n):
-        self.n = n
-
-    def get_num_of_agents(self):
-        return self.n
-
-
 def test_batch_takes_every_branch_of_the_gae_mask():
-    gold = _gold("ippo")
+    gold = golden_vectors("ippo")
     done, last = gold["batch.done"], gold["batch.last_step"]
     assert ((last == 1) & (done == 0)).any() and ((last == 1) & (done == 1)).any() and ((last == 0) & (done == 0)).any()
-    b = _batch("ippo", gold)
+    b = golden_batch("ippo", gold=gold, fields=FIELDS)
     assert b.value.abs().max() > 0 and b.next_value.abs().max() > 0
     assert all(th.equal(b.action[:, i], b.action[:, 0]) for i in range(5))
 
@@ -73,10 +29,11 @@ def test_batch_takes_every_branch_of_the_gae_mask():
 @pytest.mark.parametrize("prefix,name", CASES)
 def test_golden_parity(prefix, name):
     from safe_marl_amd.trainer import PGTrainer
-    gold = _gold(prefix)
-    model, args = _model(prefix, name)
+    gold = golden_vectors(prefix)
+    args = golden_args(prefix)
+    model = golden_model(name, args, f"{prefix}_state_dict.npz")
     assert "batchnorm.running_mean" in model.state_dict() and not any(k.startswith("rl.") for k in model.state_dict())
-    batch = _batch(prefix, gold)
+    batch = golden_batch(prefix, gold=gold, fields=FIELDS)
     pl, vl, (means, log_stds) = model.get_loss(batch)
     # the tolerances of test_learner_cpu.py / test_sqddpg_cpu.py for the same kinds of quantity
     assert abs(pl.item() - float(gold["policy_loss"])) < 2e-6
@@ -102,9 +59,9 @@ def test_golden_parity(prefix, name):
 
     # one value step, then one policy step through PGTrainer; update_target
     th.manual_seed(2468)
-    trainer = PGTrainer(args, _cls(name), StubEnv(args.agent_num), None)
+    trainer = PGTrainer(args, getattr(L, name), StubEnv(args.agent_num), None)
     net = trainer.behaviour_net
-    sd0 = _load(f"{prefix}_state_dict.npz")
+    sd0 = golden_tensors(f"{prefix}_state_dict.npz")
     net.load_state_dict(sd0)
     net.target_net.load_state_dict({k[len("target_net."):]: v for k, v in sd0.items() if k.startswith("target_net.")})
     stat = {}
@@ -115,7 +72,7 @@ def test_golden_parity(prefix, name):
                                  "mean_train_policy_grad_norm", "mean_train_entropy"}
     for k in keys:
         assert abs(float(stat[k]) - gold["stat." + k]) < 1e-4 * max(1.0, abs(gold["stat." + k])), k
-    after = _load(f"{prefix}_state_dict_after_step.npz")
+    after = golden_tensors(f"{prefix}_state_dict_after_step.npz")
     mine = net.state_dict()
     assert sorted(mine) == sorted(after)
     for k, ref in after.items():
@@ -123,7 +80,7 @@ def test_golden_parity(prefix, name):
     for name_, bn in (("reward_bn", net.batchnorm), ("adv_bn", net.rl.batchnorm)):
         assert th.allclose(bn.running_var, th.from_numpy(gold[f"after_step.{name_}.running_var"]), atol=1e-6, rtol=1e-5)
     net.update_target()
-    tgt = _load(f"{prefix}_target_after_update.npz")
+    tgt = golden_tensors(f"{prefix}_target_after_update.npz")
     mine_t = net.target_net.state_dict()
     for k, ref in tgt.items():
         assert th.allclose(mine_t[k].float(), ref.float(), atol=3e-6, rtol=1e-5), k
@@ -136,11 +93,11 @@ def test_class_wiring_and_value_shapes():
     assert IPPO.on_policy and MAPPO.on_policy and not MADDPG.on_policy and not IDDPG.on_policy
     assert IPPO.get_actions is IDDPG.get_actions and IPPO.graph_safe_updates is False
     for prefix, name in CASES[:2]:
-        args = _args(prefix)
-        m = _cls(name)(args)
+        args = golden_args(prefix)
+        m = getattr(L, name)(args)
         n, o = args.agent_num, args.obs_size
         assert m.value_dicts[0].fc1.in_features == (o + n if name == "IPPO" else o * n + n)
-        noid = _cls(name)(_args(prefix, agent_id=False))
+        noid = getattr(L, name)(golden_args(prefix, agent_id=False))
         assert noid.value_dicts[0].fc1.in_features == (o if name == "IPPO" else o * n)
         obs = th.randn(7, n, o)
         v = m.value(obs, None)
@@ -149,12 +106,13 @@ def test_class_wiring_and_value_shapes():
         out = m.get_actions(obs, status="train", exploration=True, actions_avail=th.ones(7, n, 4), last_hid=th.zeros(7, n, 64))
         assert out[2] is not None and out[2].shape == (7, 1, 4) and out[1].shape == (7, n, 4)
     with pytest.raises(NotImplementedError):
-        IPPO(_args("ippo", continuous=False))
+        IPPO(golden_args("ippo", continuous=False))
 
 
 def test_mappo_value_is_the_reference_composition():
     """The first layer formed once per sample plus the id column equals the reference's materialised rows."""
-    m, args = _model("mappo", "MAPPO")
+    args = golden_args("mappo")
+    m = golden_model("MAPPO", args, "mappo_state_dict.npz")
     n, o = args.agent_num, args.obs_size
     obs = th.randn(9, n, o)
     inp = th.cat((obs.reshape(9, 1, n * o).expand(9, n, n * o), th.eye(n).expand(9, n, n)), dim=-1)
@@ -164,12 +122,12 @@ def test_mappo_value_is_the_reference_composition():
 
 @pytest.mark.parametrize("prefix,name", CASES[:2])
 def test_need_split(prefix, name):
-    gold = _gold(prefix)
-    batch = _batch(prefix, gold)
-    both, _ = _model(prefix, name)
+    gold = golden_vectors(prefix)
+    batch = golden_batch(prefix, gold=gold, fields=FIELDS)
+    both = golden_model(name, golden_args(prefix), f"{prefix}_state_dict.npz")
     pl, vl, _ = both.get_loss(batch)
     for need in ("value", "policy"):
-        m, _ = _model(prefix, name)
+        m = golden_model(name, golden_args(prefix), f"{prefix}_state_dict.npz")
         p, v, out = m.get_loss(batch, need=need)
         if need == "value":
             assert p is None and out is None and v.item() == vl.item()
@@ -287,9 +245,9 @@ class FakeVecEnv:
 def _vec_trainer(name, n_envs, **over):
     from safe_marl_amd.trainer import PGTrainer
     prefix = name.lower() + "3"
-    args = _args(prefix, **over)
+    args = golden_args(prefix, **over)
     env = FakeVecEnv(n_envs, args.agent_num, args.obs_size)
-    return PGTrainer(args, _cls(name), env, None, graph_rollout=False), args
+    return PGTrainer(args, getattr(L, name), env, None, graph_rollout=False), args
 
 
 @pytest.mark.parametrize("name", ["IPPO", "MAPPO"])
@@ -328,8 +286,8 @@ def test_reference_cadence_ten_and_ten_windows_at_240_steps(monkeypatch):
 def test_maddpg_keeps_its_buffer():
     from safe_marl_amd.learner import MADDPG
     from safe_marl_amd.trainer import PGTrainer
-    args = _args("ippo3", alg="maddpg", behaviour_update_freq=20, max_steps=30, value_update_epochs=1, policy_update_epochs=1,
-                 normalize_advantages=False)
+    args = golden_args("ippo3", alg="maddpg", behaviour_update_freq=20, max_steps=30, value_update_epochs=1,
+                       policy_update_epochs=1, normalize_advantages=False)
     env = FakeVecEnv(4, args.agent_num, args.obs_size)
     trainer = PGTrainer(args, MADDPG, env, None, graph_rollout=False, graph_updates=False)
     assert trainer.batch_scale == 1 and not trainer.on_policy
@@ -340,13 +298,13 @@ def test_maddpg_keeps_its_buffer():
 def test_default_capacity_and_misaligned_batches():
     from safe_marl_amd.replay_buffer import TransReplayBuffer
     from safe_marl_amd.trainer import PGTrainer
-    args = _args("ippo3")
+    args = golden_args("ippo3")
     env = FakeVecEnv(64, args.agent_num, args.obs_size)
-    trainer = PGTrainer(args, _cls("IPPO"), env, None)
+    trainer = PGTrainer(args, getattr(L, "IPPO"), env, None)
     assert trainer.replay_buffer.size >= (240 + 2) * 64
-    assert PGTrainer(args, _cls("IPPO"), FakeVecEnv(4096, 3, 144), None).replay_buffer.size >= 242 * 4096
+    assert PGTrainer(args, getattr(L, "IPPO"), FakeVecEnv(4096, 3, 144), None).replay_buffer.size >= 242 * 4096
     with pytest.raises(ValueError):
-        PGTrainer(args, _cls("IPPO"), env, None, batch_scale=33)              # 32 * 33 is not a multiple of 64
+        PGTrainer(args, getattr(L, "IPPO"), env, None, batch_scale=33)              # 32 * 33 is not a multiple of 64
     buf = TransReplayBuffer(1000, device="cpu")
     buf.add_batch(state=th.zeros(12, 3, 2), reward=th.zeros(12, 3))
     with pytest.raises(ValueError):
@@ -395,7 +353,8 @@ OLD_VALUES_MEASURED = 1.8e-7
 def test_event_start_pass_files_what_the_per_step_route_stores(name):
     from safe_marl_amd.replay_buffer import TransReplayBuffer
     prefix = name.lower() + "3"
-    model, args = _model(prefix, name)
+    args = golden_args(prefix)
+    model = golden_model(name, args, f"{prefix}_state_dict.npz")
     n, o = args.agent_num, args.obs_size
     th.manual_seed(3)
     steps = 24
@@ -508,13 +467,6 @@ def test_kernels_use_no_scratch():
 
 
 # ---- two ranks on gloo -----------------------------------------------------------------------------------------------
-def _free_port():
-    import socket
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 def _flat(tensors):
     return th.cat([t.detach().reshape(-1).double() for t in tensors]).numpy()
 
@@ -526,12 +478,12 @@ def _gloo_worker(rank, world, port, name, out):
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
     n_envs = 4
-    args = _args(name.lower() + "3", behaviour_update_freq=20, max_steps=21, batch_size=8, target_update_freq=20,
-                 value_update_epochs=3, policy_update_epochs=3)
+    args = golden_args(name.lower() + "3", behaviour_update_freq=20, max_steps=21, batch_size=8, target_update_freq=20,
+                       value_update_epochs=3, policy_update_epochs=3)
     th.manual_seed(300 + rank)                    # different initial weights, noise and data per rank: rank 0's weights win
     np.random.seed(40 + rank)                     # ... and different windows of each rank's own replay
     env = FakeVecEnv(n_envs, args.agent_num, args.obs_size, seed=7 + rank)
-    trainer = PGTrainer(args, _cls(name), env, None, graph_rollout=False, sync_reward_bn=True)
+    trainer = PGTrainer(args, getattr(L, name), env, None, graph_rollout=False, sync_reward_bn=True)
     net = trainer.behaviour_net
     assert trainer.world == 2 and trainer.sync_reward_bn
     assert net.batchnorm.flex_sync_ranks and net.rl.batchnorm.flex_sync_ranks

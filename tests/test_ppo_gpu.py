@@ -16,9 +16,10 @@ import pytest
 import torch as th
 import torch.nn as nn
 
+from .golden_io import StubEnv, golden_args, golden_batch, golden_model, golden_tensors, golden_vectors
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-G = os.path.join(ROOT, "tests", "golden")
 GAMMA, LAM, EPS, COEF = 0.99, 0.95, 0.6, 2.0
 SIZES = [(32, 3, 1), (32, 5, 8), (4096 * 8, 5, 4096), (4096 * 8, 3, 1), (4096 * 32, 5, 4096), (4096 * 32, 5, 1),
          (4096 * 32, 3, 4096),
@@ -307,17 +308,9 @@ class _nullcontext:
 # ---- golden on the device --------------------------------------------------------------------------------------------
 def _golden_setup(prefix, name):
     import safe_marl_amd.learner as L
-    from safe_marl_amd.replay_buffer import Transition
-    from safe_marl_amd.util import convert
-    d = json.load(open(os.path.join(G, prefix + "_args.json")))
-    d["cuda"] = True
-    args = convert(d)
-    gold = dict(np.load(os.path.join(G, prefix + "_golden.npz")))
-    z = dict(np.load(os.path.join(G, "learner3_batch.npz" if prefix.endswith("3") else "learner_batch.npz")))
-    z["action"], z["done"], z["last_step"] = gold["batch.action"], gold["batch.done"], gold["batch.last_step"]
-    batch = Transition(**{k: th.from_numpy(z[k]).float().cuda() for k in Transition._fields})
-    sd = {k: th.from_numpy(v) for k, v in np.load(os.path.join(G, prefix + "_state_dict.npz")).items()}
-    return getattr(L, name), args, gold, batch, sd
+    gold = golden_vectors(prefix)
+    batch = golden_batch(prefix, "cuda", gold=gold, fields=("action", "done", "last_step"))
+    return getattr(L, name), golden_args(prefix, cuda=True), gold, batch, golden_tensors(prefix + "_state_dict.npz")
 
 
 @pytest.mark.parametrize("prefix,name", [("ippo", "IPPO"), ("mappo", "MAPPO"), ("ippo3", "IPPO"), ("mappo3", "MAPPO")])
@@ -325,8 +318,7 @@ def test_golden_losses_and_steps_on_the_device(prefix, name):
     from safe_marl_amd.trainer import PGTrainer
     from safe_marl_amd.util import FALLBACKS
     cls, args, gold, batch, sd = _golden_setup(prefix, name)
-    model = cls(args, cls(args).cuda()).cuda()
-    model.load_state_dict(sd, strict=True)
+    model = golden_model(cls, args, sd, "cuda")
     # every action is available: flagged as the replay's constant mask is, the policy loss takes the kernel (a mask tensor
     # without the flag takes the composition — the steps through PGTrainer below run that way, as stored)
     before = {k: v for k, v in FALLBACKS.items() if k.startswith("ppo_")}
@@ -347,16 +339,13 @@ def test_golden_losses_and_steps_on_the_device(prefix, name):
         assert th.allclose(bn.running_var.cpu(), th.from_numpy(gold[key + ".running_var"]), atol=1e-6, rtol=1e-5)
         assert int(bn.num_batches_tracked) == 1
 
-    class StubEnv:
-        n_envs = 1
-
-    after = {k: th.from_numpy(v) for k, v in np.load(os.path.join(G, prefix + "_state_dict_after_step.npz")).items()}
-    tgt = {k: th.from_numpy(v) for k, v in np.load(os.path.join(G, prefix + "_target_after_update.npz")).items()}
+    after = golden_tensors(prefix + "_state_dict_after_step.npz")
+    tgt = golden_tensors(prefix + "_target_after_update.npz")
     # the steps through PGTrainer twice: with the mask flagged (ppo_policy_kernel's d_means goes through the optimiser step)
     # and as stored (a mask tensor without the flag: the policy loss takes the composition, a recorded fallback)
     for label, b in (("kernel", batch._replace(action_avail=avail)), ("as stored", batch)):
         th.manual_seed(2468)
-        trainer = PGTrainer(args, cls, StubEnv(), None)
+        trainer = PGTrainer(args, cls, StubEnv(args.agent_num), None)
         net = trainer.behaviour_net
         net.load_state_dict(sd)
         net.target_net.load_state_dict({k[len("target_net."):]: v for k, v in sd.items() if k.startswith("target_net.")})

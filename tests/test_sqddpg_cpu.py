@@ -2,45 +2,16 @@
 (tests/golden/make_sqddpg_golden.py), with the reference's coalition draws replayed by role; the coalition mapping on
 hand-picked permutations; the C ABI's argument checks of flexnet_sqddpg_*; the kernels' resources; two ranks on gloo."""
 import ctypes as C
-import json
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch as th
 
-G = os.path.join(os.path.dirname(__file__), "golden")
+from .golden_io import StubEnv, _free_port, golden_args, golden_batch, golden_model, golden_tensors, golden_vectors
+
 PREFIXES = ["sqddpg", "sqddpg3"]
 ROLES = ("policy", "value", "target")
-
-
-def _args(prefix="sqddpg"):
-    from safe_marl_amd.util import convert
-    return convert(json.load(open(os.path.join(G, prefix + "_args.json"))))
-
-
-def _load(name):
-    z = np.load(os.path.join(G, name))
-    return {k: th.from_numpy(z[k]) for k in z.files}
-
-
-def _gold(prefix):
-    return dict(np.load(os.path.join(G, prefix + "_golden.npz")))
-
-
-def _batch(prefix):
-    from safe_marl_amd.replay_buffer import Transition
-    z = np.load(os.path.join(G, "learner_batch.npz" if prefix == "sqddpg" else "learner3_batch.npz"))
-    return Transition(**{k: th.from_numpy(z[k]).float() for k in Transition._fields})
-
-
-def _model(args, prefix):
-    from safe_marl_amd.learner import SQDDPG
-    model = SQDDPG(args, SQDDPG(args))
-    res = model.load_state_dict(_load(f"{prefix}_state_dict.npz"), strict=True)     # the reference's keys and shapes
-    assert not res.missing_keys and not res.unexpected_keys
-    return model
 
 
 def _replay(model, gold, label, roles=ROLES):
@@ -48,28 +19,18 @@ def _replay(model, gold, label, roles=ROLES):
     model.coalition_source = lambda role, groups: src[role]
 
 
-class StubEnv:
-    n_envs = 1
-
-    def __init__(self, n):
-        self.n = n
-
-    def get_num_of_agents(self):
-        return self.n
-
-
 def test_state_dict_keys_and_class_wiring():
     from safe_marl_amd.learner import IDDPG, MADDPG, SQDDPG
     for prefix in PREFIXES:
-        args = _args(prefix)
-        ref = _load(f"{prefix}_state_dict.npz")
+        args = golden_args(prefix)
+        ref = golden_tensors(f"{prefix}_state_dict.npz")
         sd = SQDDPG(args, SQDDPG(args)).state_dict()
         assert sorted(sd) == sorted(ref)
         assert all(tuple(sd[k].shape) == tuple(v.shape) for k, v in ref.items())
         assert sorted(SQDDPG(args).state_dict()) == sorted(MADDPG(args).state_dict())
     assert SQDDPG.get_actions is IDDPG.get_actions
     assert SQDDPG.bootstrap_cacheable is False and SQDDPG.graph_safe_updates is False
-    m = SQDDPG(_args())
+    m = SQDDPG(golden_args("sqddpg"))
     assert m.reads_state_in_place(32768) is False and m.reads_next_state_in_place(32768) is False
     import safe_marl_amd
     assert safe_marl_amd.SQDDPG is SQDDPG
@@ -79,7 +40,7 @@ def test_coalition_mapping_on_hand_picked_permutations():
     """pos[g, i] is agent i's position; the agent at position p is gc[g, p]; row i holds the actions of positions
     0..pos[g, i] in coalition order, agent i's own in block pos[g, i]."""
     from safe_marl_amd.learner import SQDDPG
-    args = _args("sqddpg3")._replace(sample_size=2)
+    args = golden_args("sqddpg3")._replace(sample_size=2)
     m = SQDDPG(args)
     pos = th.tensor([[2, 0, 1], [0, 1, 2]])                                   # one sample, two coalitions
     sub, grand, ind = m.coalition_maps(pos, 1)
@@ -116,10 +77,10 @@ def test_coalition_mapping_on_hand_picked_permutations():
 
 @pytest.mark.parametrize("prefix", PREFIXES)
 def test_value_phi_losses_and_grads_match_the_reference(prefix):
-    args = _args(prefix)
-    gold = _gold(prefix)
-    model = _model(args, prefix)
-    batch = _batch(prefix)
+    args = golden_args(prefix)
+    gold = golden_vectors(prefix)
+    model = golden_model("SQDDPG", args, f"{prefix}_state_dict.npz")
+    batch = golden_batch(prefix)
     n = args.agent_num
     _replay(model, gold, "call", ("value", "target"))
     with th.no_grad():
@@ -152,14 +113,14 @@ def test_value_phi_losses_and_grads_match_the_reference(prefix):
 def test_trainer_steps_and_target_update_match_the_reference(prefix):
     from safe_marl_amd.learner import SQDDPG
     from safe_marl_amd.trainer import PGTrainer
-    args = _args(prefix)
-    gold = _gold(prefix)
+    args = golden_args(prefix)
+    gold = golden_vectors(prefix)
     trainer = PGTrainer(args, SQDDPG, StubEnv(args.agent_num), None)
-    sd = _load(f"{prefix}_state_dict.npz")
+    sd = golden_tensors(f"{prefix}_state_dict.npz")
     trainer.behaviour_net.load_state_dict(sd)
     trainer.behaviour_net.target_net.load_state_dict({k[len("target_net."):]: v for k, v in sd.items()
                                                        if k.startswith("target_net.")})
-    batch = _batch(prefix)
+    batch = golden_batch(prefix)
     stat = {}
     _replay(trainer.behaviour_net, gold, "vstep")
     trainer.value_transition_process(stat, batch)
@@ -170,11 +131,11 @@ def test_trainer_steps_and_target_update_match_the_reference(prefix):
         ref = gold["stat." + k]
         assert abs(float(stat[k]) - ref) < 1e-4 * max(1.0, abs(ref)), k
     cur = trainer.behaviour_net.state_dict()
-    for k, v in _load(f"{prefix}_state_dict_after_step.npz").items():
+    for k, v in golden_tensors(f"{prefix}_state_dict_after_step.npz").items():
         assert np.allclose(cur[k].numpy(), v.numpy(), atol=2e-5), k
     trainer.behaviour_net.update_target()
     tsd = trainer.behaviour_net.target_net.state_dict()
-    for k, v in _load(f"{prefix}_target_after_update.npz").items():
+    for k, v in golden_tensors(f"{prefix}_target_after_update.npz").items():
         assert np.allclose(tsd[k].numpy(), v.numpy(), atol=2e-5), k
 
 
@@ -227,12 +188,6 @@ def test_sqddpg_kernels_have_no_scratch():
         assert v.get("scratch_bytes_per_lane", 0) == 0 and v.get("vgpr_spills", 0) == 0
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 def _worker(rank, world, port, out):
     import torch.distributed as dist
     import safe_marl_amd  # noqa: F401
@@ -241,11 +196,11 @@ def _worker(rank, world, port, out):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    args = _args()
+    args = golden_args("sqddpg")
     th.manual_seed(200 + rank)                    # different initial weights and coalitions per rank: rank 0's weights win
     trainer = PGTrainer(args, SQDDPG, StubEnv(5), None)
     w0 = th.cat([p.detach().reshape(-1) for p in trainer.behaviour_net.parameters()])
-    full = _batch("sqddpg")
+    full = golden_batch("sqddpg")
     lo, hi = (0, 16) if rank == 0 else (16, 32)
     batch = type(full)(*[f[lo:hi] for f in full])
     stat = {}

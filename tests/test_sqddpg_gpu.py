@@ -1,44 +1,17 @@
 """SQDDPG on the GPU: csrc/sqddpg.hip (coalition draw, forward, backward) against the reference's own modules
 (tests/golden/sqddpg*_*, make_sqddpg_golden.py) and against autograd of the PyTorch composition, its determinism, the
 uniformity of the device draw, its memory at the update batch, the fallback, and a short training run."""
-import json
-import os
 import warnings
 
 import numpy as np
 import pytest
 import torch as th
 
+from .golden_io import StubEnv, _np, golden_args, golden_batch, golden_model, golden_tensors, golden_vectors
+
 pytestmark = pytest.mark.gpu
-G = os.path.join(os.path.dirname(__file__), "golden")
+
 ROLES = ("policy", "value", "target")
-
-
-def _args(prefix="sqddpg", **over):
-    from safe_marl_amd.util import convert
-    d = json.load(open(os.path.join(G, prefix + "_args.json")))
-    d.update(cuda=True)
-    d.update(over)
-    return convert(d)
-
-
-def _load(name):
-    z = np.load(os.path.join(G, name))
-    return {k: th.from_numpy(z[k]).cuda() for k in z.files}
-
-
-def _gold(prefix):
-    return dict(np.load(os.path.join(G, prefix + "_golden.npz")))
-
-
-def _batch(prefix, tile=1):
-    from safe_marl_amd.replay_buffer import Transition
-    z = np.load(os.path.join(G, "learner_batch.npz" if prefix == "sqddpg" else "learner3_batch.npz"))
-    out = {}
-    for k in Transition._fields:
-        t = th.from_numpy(z[k]).float().cuda()
-        out[k] = t.repeat((tile,) + (1,) * (t.dim() - 1)).contiguous()
-    return Transition(**out)
 
 
 def _tiled_pos(gold, key, args, tile):
@@ -47,36 +20,14 @@ def _tiled_pos(gold, key, args, tile):
     return p.view(-1, ns, n).repeat(tile, 1, 1).view(-1, n)
 
 
-def _model(prefix, args):
-    from safe_marl_amd.learner import SQDDPG
-    m = SQDDPG(args, SQDDPG(args).cuda()).cuda()
-    res = m.load_state_dict(_load(prefix + "_state_dict.npz"), strict=True)
-    assert not res.missing_keys and not res.unexpected_keys
-    return m
-
-
-class StubEnv:
-    n_envs = 1
-
-    def __init__(self, n):
-        self.n = n
-
-    def get_num_of_agents(self):
-        return self.n
-
-
-def _np(t):
-    return t.detach().float().cpu().numpy()
-
-
 @pytest.mark.parametrize("prefix,tile", [("sqddpg", 1), ("sqddpg", 64), ("sqddpg3", 1), ("sqddpg3", 64)])
 def test_fused_path_matches_the_reference(prefix, tile):
     from safe_marl_amd import util
     util.FALLBACKS.pop("sqddpg", None)
-    args = _args(prefix)
-    gold = _gold(prefix)
-    m = _model(prefix, args)
-    b = _batch(prefix, tile)
+    args = golden_args(prefix, cuda=True)
+    gold = golden_vectors(prefix)
+    m = golden_model("SQDDPG", args, prefix + "_state_dict.npz", "cuda")
+    b = golden_batch(prefix, "cuda", tile)
     assert m._fused(b.action)                                           # the HIP path is the one under test
     src = {}
     m.coalition_source = lambda role, groups: src[role]
@@ -109,13 +60,13 @@ def test_fused_path_matches_the_reference(prefix, tile):
 def test_trainer_steps_and_target_update_match_the_reference(prefix):
     from safe_marl_amd.learner import SQDDPG
     from safe_marl_amd.trainer import PGTrainer
-    args = _args(prefix)
-    gold = _gold(prefix)
+    args = golden_args(prefix, cuda=True)
+    gold = golden_vectors(prefix)
     tr = PGTrainer(args, SQDDPG, StubEnv(args.agent_num), None)
-    sd = _load(prefix + "_state_dict.npz")
+    sd = golden_tensors(prefix + "_state_dict.npz", "cuda")
     tr.behaviour_net.load_state_dict(sd)
     tr.behaviour_net.target_net.load_state_dict({k[len("target_net."):]: v for k, v in sd.items() if k.startswith("target_net.")})
-    b = _batch(prefix)
+    b = golden_batch(prefix, "cuda")
     src = {}
     tr.behaviour_net.coalition_source = lambda role, groups: src[role]
     stat = {}
@@ -126,19 +77,19 @@ def test_trainer_steps_and_target_update_match_the_reference(prefix):
     for k in ("mean_train_value_loss", "mean_train_policy_loss", "mean_train_value_grad_norm", "mean_train_policy_grad_norm"):
         ref = gold["stat." + k]
         assert abs(float(stat[k]) - ref) < 2e-4 * max(1.0, abs(ref)), k
-    after = _load(prefix + "_state_dict_after_step.npz")
+    after = golden_tensors(prefix + "_state_dict_after_step.npz", "cuda")
     cur = tr.behaviour_net.state_dict()
     for k, v in after.items():
         assert np.allclose(_np(cur[k]), _np(v), atol=5e-5), (k, np.abs(_np(cur[k]) - _np(v)).max())
     tr.behaviour_net.update_target()
     cur = tr.behaviour_net.target_net.state_dict()
-    for k, v in _load(prefix + "_target_after_update.npz").items():
+    for k, v in golden_tensors(prefix + "_target_after_update.npz", "cuda").items():
         assert np.allclose(_np(cur[k]), _np(v), atol=5e-5), k
 
 
 def _random_model(n, layernorm, seed=0):
     from safe_marl_amd.learner import SQDDPG
-    args = _args("sqddpg" if n == 5 else "sqddpg3", layernorm=layernorm)
+    args = golden_args("sqddpg" if n == 5 else "sqddpg3", cuda=True, layernorm=layernorm)
     th.manual_seed(seed)
     m = SQDDPG(args).cuda()
     with th.no_grad():
@@ -257,11 +208,11 @@ def test_device_draw_is_uniform_and_seeded():
 
 def test_value_sub_update_memory_at_the_update_batch():
     from safe_marl_amd.learner import SQDDPG
-    args = _args("sqddpg")
+    args = golden_args("sqddpg", cuda=True)
     th.manual_seed(0)
     m = SQDDPG(args, SQDDPG(args).cuda()).cuda()
     B = 32768
-    b = _batch("sqddpg", B // 32)
+    b = golden_batch("sqddpg", "cuda", B // 32)
     _, vl, _ = m.get_loss(b, need="value")                                      # warm-up (workspaces)
     th.autograd.grad(vl, list(m.value_dicts.parameters()))
     del vl
@@ -278,11 +229,11 @@ def test_value_sub_update_memory_at_the_update_batch():
 def test_unshared_critics_fall_back_to_the_composition():
     from safe_marl_amd import util
     from safe_marl_amd.learner import SQDDPG
-    args = _args("sqddpg", shared_params=False)
+    args = golden_args("sqddpg", cuda=True, shared_params=False)
     th.manual_seed(0)
     m = SQDDPG(args).cuda()
-    b = _batch("sqddpg")
-    pos = th.from_numpy(_gold("sqddpg")["pos.call.value"]).cuda()
+    b = golden_batch("sqddpg", "cuda")
+    pos = th.from_numpy(golden_vectors("sqddpg")["pos.call.value"]).cuda()
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")
         assert not m._fused(b.action)
@@ -304,8 +255,8 @@ def test_short_training_run_moves_critic_and_policy():
     env_args = {"buildings": blds, "pv_nodes": blds, "ess_nodes": blds}
     net = create_network(env_args)
     env = VecFlexProvisionEnv(env_args, 256, net=net, series=make_synthetic_series(net, n_days=60), seed=3, warm_start=True)
-    args = _args("sqddpg", agent_num=env.n_agents, obs_size=env.obs_size, state_size=env.state_size, v_min=0.9,
-                 v_max=1.1, target_update_freq=60, value_update_epochs=2)
+    args = golden_args("sqddpg", cuda=True, agent_num=env.n_agents, obs_size=env.obs_size, state_size=env.state_size,
+                       v_min=0.9, v_max=1.1, target_update_freq=60, value_update_epochs=2)
     th.manual_seed(0)
     np.random.seed(0)
     tr = PGTrainer(args, learner.SQDDPG, env, None, batch_scale=64, replay_capacity=256 * 96 * 2)
