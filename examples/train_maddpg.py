@@ -64,6 +64,8 @@ def main():
     ap.add_argument("--episodes", type=int, default=3)
     ap.add_argument("--agents", type=int, default=5, choices=[3, 5])
     ap.add_argument("--batch-scale", type=int, default=None)
+    ap.add_argument("--gaussian-policy", action="store_true",
+                    help="learned log-std heads (gaussian_policy: True, LOG_STD_MIN 0.0 / LOG_STD_MAX 0.5 of default.yaml)")
     a = ap.parse_args()
 
     import torch
@@ -101,6 +103,8 @@ def main():
         alg.update(PPO_ALG_ARGS)
     if a.alg == "coma":
         alg.update(COMA_ALG_ARGS)
+    if a.gaussian_policy:
+        alg.update(gaussian_policy=True)
     alg.update(alg=a.alg, agent_num=env.n_agents, obs_size=env.obs_size, state_size=env.state_size,
                action_dim=4, v_min=0.9, v_max=1.1)
     args = convert(alg)
@@ -127,7 +131,7 @@ def main():
     if rank == 0:
         out = {"metric": "training env-steps/s (rollout + replay + MADDPG updates)", "alg": a.alg,
                "value": a.envs * world * steps / dt, "unit": "env-steps/s", "n_gpus": world, "envs_per_gpu": a.envs,
-               "n_agents": env.n_agents, "vector_steps": steps, "ms_per_vector_step": dt / steps * 1e3,
+               "gaussian_policy": bool(a.gaussian_policy), "n_agents": env.n_agents, "vector_steps": steps, "ms_per_vector_step": dt / steps * 1e3,
                "batch": trainer.effective_batch_size(),
                "grad_steps": int(steps // args.behaviour_update_freq) * (args.value_update_epochs + args.policy_update_epochs
                                                                          + (args.mixer_update_epochs if args.mixer else 0)),

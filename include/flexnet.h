@@ -789,6 +789,76 @@ typedef struct {
 int flexnet_coma_baseline(const FlexComaBaselineArgs* args, void* stream);
 int flexnet_coma_policy_loss(const FlexComaPolicyArgs* args, void* stream);
 
+/* ---- Gaussian actors (madrl/agents/{rnn,mlp}_agent_gaussian.py, gaussian_policy: True; csrc/gauss.hip) -------------
+ * head forward:  u = h w^T + b;  t = tanh(u);  log_std = log_std_min + 0.5 (log_std_max - log_std_min) (t + 1) for
+ *         h [rows, 64], w [a, 64].  With means / noise / action (all three, [rows, a]) the exploration of maddpg.py:88
+ *         under util.py:56-64 runs in the same launch: action = tanh(means + exp(log_std) noise), and env_action (optional)
+ *         = translate_action of it (util.py:125-128).  No log-probability comes back.
+ * head backward: d_u = d_log_std 0.5 (log_std_max - log_std_min) (1 - t^2) [rows, a];  d_h = d_u w [rows, 64].  Either
+ *         output may be NULL.  dw / db: flexnet_wgrad(d_u, h) with its colsum.
+ *         hid == FLEXNET_HID, act_dim <= FLEXNET_MAX_ACT, rows <= 2^30, h / w / d_h 16-byte aligned; else
+ *         FLEXNET_EUNSUPPORTED.  Missing tensors: FLEXNET_EINVAL.  Both before any HIP call.
+ * sum explore:   the agent-summed selection of iddpg.py:64-70 / matd3.py:91-98 with per-sample standard deviations:
+ *         y[e, k] = tanh(((m[e,0,k] + m[e,1,k]) + ..) + exp((ls[e,0,k] + ls[e,1,k]) + ..) eps[e, k]), handed to every
+ *         agent, and env_action (optional) = translate_action of it.  n_agents <= FLEXNET_MAX_AGENTS, act_dim <=
+ *         FLEXNET_MAX_ACT, n_envs * act_dim < 2^31; else FLEXNET_EUNSUPPORTED.
+ * ppo rows:      flexnet_ppo_policy_loss with log_stds [rows, n, a], summed over agents per row like the means:
+ *         sigma[b, k] = exp(sum_i log_stds[b, i, k]);  besides d_means, d_log_stds[b, i, k] = sum_j dloss/dlogp[b, j]
+ *         ((actions[b, j, k] - mu[b, k])^2 / sigma[b, k]^2 - 1) for every agent i (optional).  Same workspace, fp64 block
+ *         sums and finish, same ties.  n_agents / act_dim beyond the maxima, rows >= 2^28: FLEXNET_EUNSUPPORTED. */
+typedef struct {
+    int64_t rows;
+    int32_t act_dim;           /* <= FLEXNET_MAX_ACT */
+    int32_t hid;               /* FLEXNET_HID */
+    float log_std_min, log_std_max;
+    float action_low, action_high;
+    const float* h;            /* [rows, 64] (forward) */
+    const float* w;            /* [a, 64] */
+    const float* b;            /* [a] or NULL (forward) */
+    float* log_std;            /* out [rows, a] (forward) */
+    float* t;                  /* forward: out [rows, a], optional; backward: in */
+    const float* means;        /* [rows, a]: with noise and action, the exploration epilogue */
+    const float* noise;        /* [rows, a] standard normal draws */
+    float* action;             /* out [rows, a] */
+    float* env_action;         /* out [rows, a] (optional) */
+    const float* d_log_std;    /* [rows, a] (backward) */
+    float* d_u;                /* out [rows, a] (backward, optional) */
+    float* d_h;                /* out [rows, 64] (backward, optional) */
+} FlexGaussHeadArgs;
+
+typedef struct {
+    int32_t n_envs, n_agents, act_dim, pad0;
+    float act_low, act_high;
+    const float* means;        /* [n_envs, n, a] */
+    const float* log_stds;     /* [n_envs, n, a] */
+    const float* eps;          /* [n_envs, a] standard normal draws */
+    float* action;             /* out [n_envs, n, a] */
+    float* env_action;         /* out [n_envs, n, a] (optional) */
+} FlexGaussSumArgs;
+
+typedef struct {
+    int64_t rows;
+    int32_t n_agents, act_dim; /* act_dim <= FLEXNET_MAX_ACT */
+    float eps_clip;
+    int32_t pad0;
+    const float* means;        /* [rows, n, a] */
+    const float* log_stds;     /* [rows, n, a] */
+    const float* actions;      /* [rows, n, a] */
+    const float* old_log_prob; /* [rows, n] or NULL */
+    const float* advantages;   /* [rows, n] */
+    float* loss;               /* out [1] */
+    float* d_means;            /* out [rows, n, a] */
+    float* d_log_stds;         /* out [rows, n, a] (optional) */
+    float* ratio;              /* out [rows, n] (optional) */
+    float* workspace;
+    int64_t workspace_floats;  /* >= FLEXNET_PPO_WS_FLOATS */
+} FlexPpoPolicyRowsArgs;
+
+int flexnet_gauss_head_forward(const FlexGaussHeadArgs* args, void* stream);
+int flexnet_gauss_head_backward(const FlexGaussHeadArgs* args, void* stream);
+int flexnet_gauss_sum_explore(const FlexGaussSumArgs* args, void* stream);
+int flexnet_ppo_policy_loss_rows(const FlexPpoPolicyRowsArgs* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,7 @@ SYMBOLS = (
     "flexnet_sqddpg_draw", "flexnet_sqddpg_forward", "flexnet_sqddpg_backward",
     "flexnet_ppo_gae", "flexnet_ppo_policy_loss", "flexnet_ppo_value_loss",
     "flexnet_coma_baseline", "flexnet_coma_policy_loss",
+    "flexnet_gauss_head_forward", "flexnet_gauss_head_backward", "flexnet_gauss_sum_explore", "flexnet_ppo_policy_loss_rows",
     "flexopf_qp_work_doubles", "flexopf_qp_solve",
 )
 
@@ -305,6 +306,30 @@ class FlexComaPolicyArgs(C.Structure):
                [("workspace_floats", C.c_int64)]
 
 
+class FlexGaussHeadArgs(C.Structure):
+    """include/flexnet.h"""
+    _fields_ = [("rows", C.c_int64), ("act_dim", C.c_int32), ("hid", C.c_int32), ("log_std_min", C.c_float),
+                ("log_std_max", C.c_float), ("action_low", C.c_float), ("action_high", C.c_float)] + \
+               [(k, C.c_void_p) for k in ("h", "w", "b", "log_std", "t", "means", "noise", "action", "env_action",
+                                          "d_log_std", "d_u", "d_h")]
+
+
+class FlexGaussSumArgs(C.Structure):
+    """include/flexnet.h"""
+    _fields_ = [("n_envs", C.c_int32), ("n_agents", C.c_int32), ("act_dim", C.c_int32), ("pad0", C.c_int32),
+                ("act_low", C.c_float), ("act_high", C.c_float)] + \
+               [(k, C.c_void_p) for k in ("means", "log_stds", "eps", "action", "env_action")]
+
+
+class FlexPpoPolicyRowsArgs(C.Structure):
+    """include/flexnet.h"""
+    _fields_ = [("rows", C.c_int64), ("n_agents", C.c_int32), ("act_dim", C.c_int32), ("eps_clip", C.c_float),
+                ("pad0", C.c_int32)] + \
+               [(k, C.c_void_p) for k in ("means", "log_stds", "actions", "old_log_prob", "advantages", "loss", "d_means",
+                                          "d_log_stds", "ratio", "workspace")] + \
+               [("workspace_floats", C.c_int64)]
+
+
 class FlexSumArgs(C.Structure):
     """include/flexnet.h"""
     _fields_ = [("n", C.c_int64), ("scale", C.c_float), ("pad0", C.c_int32), ("x", C.c_void_p), ("out", C.c_void_p),
@@ -349,6 +374,7 @@ class FlexWindowRefreshArgs(C.Structure):
 
 
 FLEXNET_EUNSUPPORTED = -3
+FLEXNET_HID, FLEXNET_MAX_AGENTS, FLEXNET_MAX_ACT = 64, 8, 8
 
 _lib = None
 
@@ -444,6 +470,10 @@ def load():
         fn.argtypes = [C.POINTER(FlexSqddpgArgs), vp]
         fn.restype = C.c_int
     for fn, st in ((lib.flexnet_coma_baseline, FlexComaBaselineArgs), (lib.flexnet_coma_policy_loss, FlexComaPolicyArgs)):
+        fn.argtypes = [C.POINTER(st), vp]
+        fn.restype = C.c_int
+    for fn, st in ((lib.flexnet_gauss_head_forward, FlexGaussHeadArgs), (lib.flexnet_gauss_head_backward, FlexGaussHeadArgs),
+                   (lib.flexnet_gauss_sum_explore, FlexGaussSumArgs), (lib.flexnet_ppo_policy_loss_rows, FlexPpoPolicyRowsArgs)):
         fn.argtypes = [C.POINTER(st), vp]
         fn.restype = C.c_int
     lib.flexnet_agent_sum_explore.argtypes = [C.POINTER(FlexAgentSumArgs), vp]

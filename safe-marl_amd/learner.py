@@ -22,7 +22,7 @@ import torch as th
 import torch.nn as nn
 
 from .nets import (WGRAD_MIN_ROWS, CriticTail, critic_first_layer, critic_td_loss, critic_td_loss_supported, critic_policy_loss,
-                   critic_policy_loss_supported, expand_agents, MLPAgent, MLPCritic, RNNAgent, critic_policy_supported, critic_replayed_supported,
+                   critic_policy_loss_supported, expand_agents, MLPAgent, MLPAgentGaussian, MLPCritic, RNNAgent, RNNAgentGaussian, critic_policy_supported, critic_replayed_supported,
                    critic_tail_supported, fused_actor_forward, tall_linear, td_loss, td_loss_supported, wide_batch_linear,
                    batchnorm_stats_supported, batchnorm_update_running_stats, sync_batchnorm, QMixer,
                    sqddpg_draw, sqddpg_fused_config, sqddpg_shapley_fused, ppo_gae, ppo_policy_loss, ppo_value_loss,
@@ -62,6 +62,10 @@ class RolloutGraph:
         self._rew_sum = th.zeros((), dtype=th.float64, device=dev)
         self._fail_sum = th.zeros((), dtype=th.float64, device=dev)
         self.std = float(model.args.fixed_policy_std)
+        # gaussian_policy: the standard deviation is an output of the policy, per row — the kernels that carry ONE constant std
+        # (the actor kernel's exploration epilogue and everything built on it: ring I/O, sink, burst) are not used; the
+        # general bodies draw from the log-stds Model.policy returns and neither ``std`` nor ``summed_std`` is consulted
+        self.gaussian = bool(model.args.gaussian_policy)
         self.graph = None
         self.bursts = {}                                       # k -> graph of k bodies (run())
         self._torch_noise = False
@@ -77,7 +81,8 @@ class RolloutGraph:
                        and bool(model.args.action_enforcebound) and bool(model.args.continuous) and a > 1
                        and env.obs.is_cuda and model.fused_inference and model.args.shared_params)
         if self.summed:
-            self.std_sum = model.summed_std(self.avail.device)
+            if not self.gaussian:
+                self.std_sum = model.summed_std(self.avail.device)
             self.act_pol_buf = th.zeros(N, n, a, device=dev)
             self.env_act_buf = th.zeros(N, n, a, device=dev)
         # plain MADDPG on the GPU: policy + exploration in one HIP launch, ring write + hand-over + statistics in another
@@ -86,7 +91,7 @@ class RolloutGraph:
         # the reference adds unbounded noise, util.py:66-74, and the general body below runs select_action itself)
         self._fast = (type(model).__name__ in ("MADDPG", "SAFEMADDPG") and model.fused_inference
                      and model.args.shared_params and env.obs.is_cuda and model.args.agent_type == "rnn" and h == 64
-                     and o <= 144 and bool(model.args.action_enforcebound))
+                     and o <= 144 and bool(model.args.action_enforcebound) and not self.gaussian)
         # ring write / hand-over / statistics in ONE launch of this project's kernel (fixed-order block sums): no ATen
         # reduction is ever captured into the rollout graph, whatever the algorithm
         self.packable = env.obs.is_cuda and h == 64 and o <= 144 and n <= 8 and a <= 8 and (n * o) % 4 == 0
@@ -115,7 +120,7 @@ class RolloutGraph:
         # step (files the transition): three launches, no pack kernel, the observation written once (round 3)
         self.summed_sink = bool(self.summed and self.cursor_stepped and self.rows_capable
                                 and hasattr(env, "set_replay_sink") and n * a <= 32 and n * h <= 384
-                                and two_per_wave and h == 64 and o <= 144
+                                and two_per_wave and h == 64 and o <= 144 and not self.gaussian
                                 and os.environ.get("FLEX_SUMMED_SINK", "1") != "0")
         if self.sink or self.summed_sink:
             self.act_buf = th.zeros(N * n, a, device=dev)
@@ -323,13 +328,17 @@ class RolloutGraph:
             return
         if self.summed:
             with th.no_grad():
-                means, _, hid = m.policy(self.obs, last_hid=self.hid)
-                summed_exploration(m, means.to(th.float32), env_action=self.env_act_buf, action_out=self.act_pol_buf)
+                means, log_stds, hid = m.policy(self.obs, last_hid=self.hid)
+                summed_exploration(m, means.to(th.float32), env_action=self.env_act_buf, action_out=self.act_pol_buf,
+                                   log_stds=log_stds if self.gaussian else None)
                 env.step(self.env_act_buf, fuse_obs=True, auto_reset=True)
                 self._pack(self.act_pol_buf, hid.reshape(N, m.n_, -1).to(th.float32).contiguous())
             return
         with th.no_grad():
-            if self.plain:
+            if self.plain and self.gaussian:
+                means, log_stds, hid = m.policy(self.obs, last_hid=self.hid)
+                action = action_pol = th.tanh(means + log_stds.exp() * th.randn_like(means))    # util.py:57-64, per-row std
+            elif self.plain:
                 means, _, hid = m.policy(self.obs, last_hid=self.hid)
                 action = action_pol = th.tanh(means + self.std * th.randn_like(means))          # util.py:57-64
             else:
@@ -503,9 +512,10 @@ class Model(nn.Module):
     def construct_policy_net(self):
         """model.py:145-169"""
         input_shape = self.obs_dim + self.n_ if self.args.agent_id else self.obs_dim
-        if self.args.gaussian_policy:
-            raise NotImplementedError("gaussian policies are outside the MADDPG hot path")
-        Agent = {"mlp": MLPAgent, "rnn": RNNAgent}[self.args.agent_type]
+        if self.args.gaussian_policy:                     # learned log-std heads (model.py:152-159)
+            Agent = {"mlp": MLPAgentGaussian, "rnn": RNNAgentGaussian}[self.args.agent_type]
+        else:
+            Agent = {"mlp": MLPAgent, "rnn": RNNAgent}[self.args.agent_type]
         count = 1 if self.args.shared_params else self.n_
         self.policy_dicts = nn.ModuleList([Agent(input_shape, self.args) for _ in range(count)])
 
@@ -539,12 +549,15 @@ class Model(nn.Module):
         """model.py:102-140. obs [b, n, o] -> means [b, n, a], log_stds, hiddens [b, n, hid]."""
         b = obs.size(0)
         fused = None
+        gauss = bool(self.args.gaussian_policy)      # log_stds [b, n, a] from the agents' log-std heads (model.py:119-120,135-136)
         if self.args.shared_params and obs.is_cuda and not th.is_grad_enabled() and self.fused_inference:
             # rollout steps and bootstrap targets: one HIP launch instead of the module's ten kernels
             fused = fused_actor_forward(self.policy_dicts[0], obs, last_hid, self.n_, self.args.agent_id)
         if fused is not None:
             means = fused[0].view(b, self.n_, -1)
             hiddens = fused[1].view(b, self.n_, -1)
+            if gauss:                                 # the mean head ran in the fc2 slot; the log-std head reads the new hidden state
+                return means, self.policy_dicts[0].log_std_of(fused[1]).view(b, self.n_, -1), hiddens
             return means, self._log_stds_like(means), hiddens
         if (self.args.shared_params and obs.is_cuda and th.is_grad_enabled() and self.fused_inference
                 and b * self.n_ >= WGRAD_MIN_ROWS and isinstance(self.policy_dicts[0], RNNAgent)):
@@ -552,16 +565,24 @@ class Model(nn.Module):
             out = self.policy_dicts[0].forward_update(obs.reshape(b * self.n_, -1), last_hid, self.n_, self.args.agent_id)
             if out is not None:
                 means, hiddens = out[0].view(b, self.n_, -1), out[2].view(b, self.n_, -1)
+                if gauss:
+                    return means, out[1].view(b, self.n_, -1), hiddens
                 return means, self._log_stds_like(means), hiddens
+        if gauss and obs.is_cuda and not (self.args.shared_params and isinstance(self.policy_dicts[0], RNNAgent)):
+            note_fallback("gaussian_policy", f"agent_type {self.args.agent_type}, shared_params {self.args.shared_params}")
         obs = self.with_ids(obs)
         if self.args.shared_params:
-            means, _, hiddens = self.policy_dicts[0](obs.reshape(b * self.n_, -1), last_hid)
+            means, log_stds, hiddens = self.policy_dicts[0](obs.reshape(b * self.n_, -1), last_hid)
             means = means.view(b, self.n_, -1)
             hiddens = hiddens.view(b, self.n_, -1)
+            if gauss:
+                return means, log_stds.view(b, self.n_, -1), hiddens
         else:
             outs = [pol(obs[:, i, :], last_hid[:, i, :]) for i, pol in enumerate(self.policy_dicts)]
             means = th.stack([o[0] for o in outs], dim=1)
             hiddens = th.stack([o[2] for o in outs], dim=1)
+            if gauss:
+                return means, th.stack([o[1] for o in outs], dim=1), hiddens
         # fixed_policy_std (model.py:121-123): log(1.0) = 0 at the default config
         return means, self._log_stds_like(means), hiddens
 
@@ -763,7 +784,10 @@ class Model(nn.Module):
                 # exploration of select_action (util.py:57-64): tanh(N(mean, std)); every action is available
                 # (env:721-730), so the restore mask is the identity and log_prob — unused by the DDPG losses — is
                 # not formed.  SAFEMADDPG routes through get_actions for its safety layer.
-                if type(self).get_actions is MADDPG.get_actions and self.args.action_enforcebound:
+                if type(self).get_actions is MADDPG.get_actions and self.args.action_enforcebound and self.args.gaussian_policy:
+                    means, log_stds, hid = self.policy(obs, last_hid=last_hid)
+                    action = action_pol = th.tanh(means + log_stds.exp() * th.randn_like(means))
+                elif type(self).get_actions is MADDPG.get_actions and self.args.action_enforcebound:
                     means, _, hid = self.policy(obs, last_hid=last_hid)
                     action = action_pol = th.tanh(means + std * th.randn_like(means))
                 else:
@@ -1219,10 +1243,33 @@ MADDPG.fused_eval = True                  # (tests switch it off to compare the 
 MADDPG.fused_td_backward = True          # (tests switch it off to compare with the forward / td_loss / backward sequence)
 
 
-def summed_exploration(model, means, env_action=None, action_out=None):
+def _summed_exploration_rows(model, means, log_stds, env_action, action_out):
+    """summed_exploration with per-sample log-stds (gaussian_policy): one launch of flexnet_gauss_sum_explore."""
+    import torch.distributions.normal as tdn
+    from . import _lib
+    b, n, a = means.shape
+    means = means.contiguous()
+    log_stds = log_stds.detach().to(th.float32).expand(b, n, a).contiguous()
+    eps = tdn._standard_normal((b, 1, a), means.dtype, means.device)
+    out = action_out if action_out is not None else th.empty(b, n, a, dtype=th.float32, device=means.device)
+    k = _lib.FlexGaussSumArgs()
+    k.n_envs, k.n_agents, k.act_dim = b, n, a
+    k.act_low, k.act_high = float(model.args.action_low), float(model.args.action_high)
+    k.means, k.log_stds, k.eps, k.action = means.data_ptr(), log_stds.data_ptr(), eps.data_ptr(), out.data_ptr()
+    if env_action is not None:
+        k.env_action = env_action.data_ptr()
+    _lib.launch("flexnet_gauss_sum_explore", k)
+    return out
+
+
+def summed_exploration(model, means, env_action=None, action_out=None, log_stds=None):
     """tanh(sum over agents of the means + exp(sum of log-stds) * eps), the ONE action of matd3.py:92-97 / iddpg.py:66-71
     under util.py:57-64, handed to every agent: [b, n, a] (and, with ``env_action``, translate_action of it) from one launch
-    of flexnet_agent_sum_explore.  eps is Normal.rsample's own draw; every fp32 rounding sits where the tensor ops have it."""
+    of flexnet_agent_sum_explore.  eps is Normal.rsample's own draw; every fp32 rounding sits where the tensor ops have it.
+    ``log_stds`` [b, n, a] without a ``_flex_entropy`` attribute (learned, per sample): flexnet_gauss_sum_explore instead of
+    the constant ``summed_std``."""
+    if log_stds is not None and getattr(log_stds, "_flex_entropy", None) is None:
+        return _summed_exploration_rows(model, means, log_stds, env_action, action_out)
     import torch.distributions.normal as tdn      # (looked up at call time: the very function Normal.rsample calls)
     from . import _lib
     b, n, a = means.shape
@@ -1302,7 +1349,7 @@ def _summed_get_actions(self, obs, status, exploration, actions_avail, target, l
     pol = self.target_net.policy if (target and self.args.target) else self.policy
     means, log_stds, hiddens = pol(obs, last_hid=last_hid)
     if _summed_exploration_applies(self, means, status, exploration, actions_avail, need_log_prob):
-        restore_actions = summed_exploration(self, means)
+        restore_actions = summed_exploration(self, means, log_stds=log_stds)
         return restore_actions[:, :1], restore_actions, None, (means, log_stds), hiddens
     if _summed_mean_applies(self, means, status, exploration, actions_avail):
         restore_actions = _SumBroadcastAgentsFn.apply(means, self)

@@ -53,8 +53,13 @@ class RNNAgent(nn.Module):
         if args.layernorm:
             self.layernorm = nn.LayerNorm(args.hid_size)
         self.rnn = nn.GRUCell(args.hid_size, args.hid_size)
-        self.fc2 = nn.Linear(args.hid_size, args.action_dim)
+        self._build_heads(args)
         self._act = _activation(args.hid_activation)
+
+    def _build_heads(self, args):
+        """What follows the GRU cell (RNNAgentGaussian: ``mean`` and ``log_std``; ``fc2`` is then a property over ``mean`` —
+        an ``self.fc2 = ...`` in __init__ would collide with it)."""
+        self.fc2 = nn.Linear(args.hid_size, args.action_dim)
 
     def init_hidden(self):
         return self.fc1.weight.new_zeros(1, self.args.agent_num, self.args.hid_size)
@@ -88,10 +93,10 @@ class RNNAgent(nn.Module):
             # one autograd node: fused matrix-core forward, hand-written backward (csrc/actor.hip, gru.hip, wgrad.hip, lnrelu.hip)
             ln = self.layernorm if self.args.layernorm else None
             r = self.rnn
-            means, h = _ActorTrainFn.apply(obs, hx0, n_agents, bool(agent_id), W, self.fc1.bias,
-                                           None if ln is None else ln.weight, None if ln is None else ln.bias,
-                                           1e-5 if ln is None else ln.eps, r.weight_ih, r.weight_hh, r.bias_ih, r.bias_hh,
-                                           self.fc2.weight, self.fc2.bias)
+            means, h = self._train_node().apply(obs, hx0, n_agents, bool(agent_id), W, self.fc1.bias,
+                                                None if ln is None else ln.weight, None if ln is None else ln.bias,
+                                                1e-5 if ln is None else ln.eps, r.weight_ih, r.weight_hh, r.bias_ih, r.bias_hh,
+                                                self.fc2.weight, self.fc2.bias)
             return means, None, h
         if not (obs.is_cuda and obs.dtype == th.float32 and lnrelu_supported(self, n_agents) and _FUSED_GRU is not None
                 and W.shape[1] == o + (n_agents if agent_id else 0) and obs.shape[0] % n_agents == 0):
@@ -106,6 +111,10 @@ class RNNAgent(nn.Module):
         r, hx = self.rnn, hidden_state.reshape(-1, self.args.hid_size)
         h = _gru_cell(x, hx, r)
         return tall_linear(h, self.fc2.weight, self.fc2.bias), None, h
+
+    def _train_node(self):
+        """The autograd node of the fused update pass (the Gaussian agent's also takes a gradient at the hidden state)."""
+        return _ActorTrainFn
 
 
 class MLPAgent(nn.Module):
@@ -130,6 +139,176 @@ class MLPAgent(nn.Module):
             x = self.layernorm(x)
         h = self._act(self.fc2(self._act(x)))
         return self.fc3(h), None, h
+
+
+def gauss_log_std_torch(h, weight, bias, lo, hi):
+    """rnn_agent_gaussian.py:37-39: lo + 0.5 (hi - lo) (tanh(h W^T + b) + 1), the tensor composition."""
+    return lo + 0.5 * (hi - lo) * (th.tanh(F.linear(h, weight, bias)) + 1)
+
+
+def _gauss_head_args(h, weight, lo, hi):
+    a = _lib.FlexGaussHeadArgs()
+    a.rows, a.act_dim, a.hid = h.shape[0], weight.shape[0], weight.shape[1]
+    a.log_std_min, a.log_std_max = float(lo), float(hi)
+    a.w = weight.data_ptr()
+    return a
+
+
+def gauss_head_supported(h, weight, bias=None):
+    """What csrc/gauss.hip covers: fp32 GPU rows of 64 hidden units, at most FLEXNET_MAX_ACT outputs."""
+    return (h.is_cuda and h.dim() == 2 and all(t is None or (t.is_cuda and t.dtype == th.float32) for t in (h, weight, bias))
+            and h.shape[1] == weight.shape[1] and h.is_contiguous() and h.data_ptr() % 16 == 0)
+
+
+def gauss_head_forward(h, weight, bias, lo, hi, means=None, noise=None, low=0.0, high=1.0, want_t=True):
+    """One launch of flexnet_gauss_head_forward, no graph: (log_std [rows, a], t = tanh(u) or None) and, with ``means`` and
+    ``noise`` [rows, a], also (action = tanh(means + exp(log_std) noise), env_action) — the per-agent exploration of
+    maddpg.py:88 under util.py:56-64 with translate_action (util.py:125-128).  None where the library declines.
+    (The epilogue is an entry of the library for callers that hold the noise; the learner's own paths draw in tensor
+    operations next to torch's generator, so today only the tests call it.)"""
+    if (means is None) != (noise is None):
+        raise ValueError("gauss_head_forward: the exploration epilogue needs both `means` and `noise`")
+    h, weight = h.detach().contiguous(), weight.detach().contiguous()
+    rows, na = h.shape[0], weight.shape[0]
+    log_std = th.empty(rows, na, dtype=th.float32, device=h.device)
+    t = th.empty_like(log_std) if want_t else None
+    a = _gauss_head_args(h, weight, lo, hi)
+    a.h, a.log_std = h.data_ptr(), log_std.data_ptr()
+    keep = [h, weight]
+    if bias is not None:
+        keep.append(bias.detach().contiguous())
+        a.b = keep[-1].data_ptr()
+    if t is not None:
+        a.t = t.data_ptr()
+    action = env_action = None
+    if noise is not None:
+        keep += [means.detach().reshape(rows, na).to(th.float32).contiguous(), noise.reshape(rows, na).to(th.float32).contiguous()]
+        action, env_action = th.empty_like(log_std), th.empty_like(log_std)
+        a.means, a.noise, a.action, a.env_action = keep[-2].data_ptr(), keep[-1].data_ptr(), action.data_ptr(), env_action.data_ptr()
+        a.action_low, a.action_high = float(low), float(high)
+    if not _lib.try_launch("flexnet_gauss_head_forward", a):
+        return None
+    return (log_std, t, action, env_action) if noise is not None else (log_std, t)
+
+
+def gauss_head_backward(d_log_std, t, weight, lo, hi, want_d_h=True):
+    """One launch of flexnet_gauss_head_backward: (d_u [rows, a], d_h [rows, 64] or None)."""
+    d_log_std, weight = d_log_std.contiguous(), weight.detach().contiguous()
+    rows = t.shape[0]
+    d_u = th.empty_like(t)
+    d_h = th.empty(rows, weight.shape[1], dtype=th.float32, device=t.device) if want_d_h else None
+    a = _gauss_head_args(t, weight, lo, hi)
+    a.hid = weight.shape[1]
+    a.d_log_std, a.t, a.d_u = d_log_std.data_ptr(), t.data_ptr(), d_u.data_ptr()
+    if d_h is not None:
+        a.d_h = d_h.data_ptr()
+    _lib.launch("flexnet_gauss_head_backward", a)
+    return d_u, d_h
+
+
+class _GaussHeadFn(th.autograd.Function):
+    """The log-std head of the Gaussian agents as one node: csrc/gauss.hip both ways, the weight and bias gradients from one
+    pass of csrc/wgrad.hip over d_u."""
+
+    @staticmethod
+    def forward(ctx, h, weight, bias, lo, hi):
+        out = gauss_head_forward(h, weight, bias, lo, hi, want_t=any(ctx.needs_input_grad[:3]))
+        if out is None:
+            raise _lib.FlexLibraryError("flexnet_gauss_head_forward declined a configuration gauss_log_std admitted")
+        log_std, t = out
+        if t is not None:
+            ctx.save_for_backward(h, weight, t)
+        ctx.lo, ctx.hi, ctx.has_bias = float(lo), float(hi), bias is not None
+        return log_std
+
+    @staticmethod
+    def backward(ctx, d_log_std):
+        h, weight, t = ctx.saved_tensors
+        d_u, d_h = gauss_head_backward(d_log_std, t, weight, ctx.lo, ctx.hi, want_d_h=ctx.needs_input_grad[0])
+        dw = db = None
+        want_db = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1]:
+            hd = h.detach()
+            if tall_wgrad_supported(d_u, hd):
+                if want_db:
+                    db = th.empty(d_u.shape[1], dtype=th.float32, device=d_u.device)
+                dw = tall_wgrad(d_u, hd, colsum=db)
+            else:
+                dw = d_u.t() @ hd
+        if want_db and db is None:
+            db = d_u.sum(0)
+        return d_h, dw, db, None, None
+
+
+def gauss_log_std(h, weight, bias, lo, hi):
+    """log_std [rows, a] of the Gaussian agents' head on ``h`` [rows, hid]: csrc/gauss.hip on the GPU (hid 64, a <= 8, fp32),
+    the tensor composition elsewhere."""
+    if gauss_head_supported(h, weight, bias):
+        if weight.shape[1] == _lib.FLEXNET_HID and weight.shape[0] <= _lib.FLEXNET_MAX_ACT and h.shape[0] >= 1:
+            return _GaussHeadFn.apply(h, weight, bias, lo, hi)
+        note_fallback("gauss_head", f"hid {weight.shape[1]}, act_dim {weight.shape[0]}")
+    elif h.is_cuda:
+        note_fallback("gauss_head", f"dtype {h.dtype}, shape {tuple(h.shape)}")
+    return gauss_log_std_torch(h, weight, bias, lo, hi)
+
+
+class RNNAgentGaussian(RNNAgent):
+    """madrl/agents/rnn_agent_gaussian.py:7-40: the RNN agent with the heads ``mean`` and ``log_std`` in place of ``fc2``;
+    forward returns (mean, log_std, new hidden) with log_std = MIN + 0.5 (MAX - MIN) (tanh(log_std(h)) + 1).  The ``mean``
+    head sits where the fixed-std agent has ``fc2``, so the fused actor kernels serve it unchanged; the log-std head is
+    csrc/gauss.hip on the hidden state they return."""
+
+    def _build_heads(self, args):
+        self.mean = nn.Linear(args.hid_size, args.action_dim)
+        self.log_std = nn.Linear(args.hid_size, args.action_dim)
+
+    @property
+    def fc2(self):
+        # a CLASS property: found before nn.Module.__getattr__ looks among the registered submodules, so the kernels' wrappers
+        # read agent.fc2.weight / .bias as the mean head's, and no "fc2.*" key enters the state_dict
+        return self.mean
+
+    def log_std_of(self, h):
+        return gauss_log_std(h, self.log_std.weight, self.log_std.bias, self.args.LOG_STD_MIN, self.args.LOG_STD_MAX)
+
+    def forward(self, inputs, hidden_state):
+        mean, _, h = super().forward(inputs, hidden_state)
+        return mean, self.log_std_of(h), h
+
+    def forward_update(self, obs, hidden_state, n_agents, agent_id):
+        out = super().forward_update(obs, hidden_state, n_agents, agent_id)
+        if out is None:
+            return None
+        return out[0], self.log_std_of(out[2]), out[2]
+
+    def _train_node(self):
+        return _ActorTrainHidFn
+
+
+class MLPAgentGaussian(nn.Module):
+    """madrl/agents/mlp_agent_gaussian.py:7-41 (agent_type: mlp): runs as the tensor composition."""
+
+    def __init__(self, input_shape, args):
+        super().__init__()
+        self.args = args
+        self.fc1 = nn.Linear(input_shape, args.hid_size)
+        if args.layernorm:
+            self.layernorm = nn.LayerNorm(args.hid_size)
+        self.fc2 = nn.Linear(args.hid_size, args.hid_size)
+        self.mean = nn.Linear(args.hid_size, args.action_dim)
+        self.log_std = nn.Linear(args.hid_size, args.action_dim)
+        self._act = _activation(args.hid_activation)
+
+    def init_hidden(self):
+        return self.fc1.weight.new_zeros(1, self.args.hid_size)
+
+    def forward(self, inputs, hidden_state):
+        x = self.fc1(inputs)
+        if self.args.layernorm:
+            x = self.layernorm(x)
+        h = self._act(self.fc2(self._act(x)))
+        log_std = gauss_log_std_torch(h, self.log_std.weight, self.log_std.bias, self.args.LOG_STD_MIN, self.args.LOG_STD_MAX)
+        return self.mean(h), log_std, h
 
 
 class MLPCritic(nn.Module):
@@ -715,7 +894,8 @@ class _ActorTrainFn(th.autograd.Function):
         _lib.launch("flexnet_actor_forward", a)
         ctx.n_agents, ctx.agent_id, ctx.ln_eps = n_agents, bool(agent_id), float(ln_eps)
         ctx.save_for_backward(obs, hidden, hid_out, saved, fc1_w, fc1_b, ln_w, ln_b, w_ih, fc2_w)
-        ctx.mark_non_differentiable(hid_out)          # the new hidden state is returned for the caller's bookkeeping only
+        if not getattr(ctx, "hid_grad", False):
+            ctx.mark_non_differentiable(hid_out)      # the new hidden state is returned for the caller's bookkeeping only
         ctx.set_materialize_grads(False)              # ... and must not cost a [rows, 64] zero fill per backward
         return means, hid_out
 
@@ -724,6 +904,8 @@ class _ActorTrainFn(th.autograd.Function):
         obs, hidden, hid_out, saved, fc1_w, fc1_b, ln_w, ln_b, w_ih, fc2_w = ctx.saved_tensors
         rows, o = obs.shape
         n, dev = ctx.n_agents, obs.device
+        if d_means is None:                           # (_ActorTrainHidFn: the gradient arrived at the hidden state alone)
+            d_means = th.zeros(rows, fc2_w.shape[0], dtype=th.float32, device=dev)
         d_means = d_means.contiguous()
         d_gi = th.empty(rows, 192, dtype=th.float32, device=dev)
         d_gh = th.empty(rows, 192, dtype=th.float32, device=dev)
@@ -732,6 +914,9 @@ class _ActorTrainFn(th.autograd.Function):
         g.d_means, g.fc2_w = d_means.data_ptr(), fc2_w.data_ptr()
         g.r, g.z, g.n, g.hn = saved[2].data_ptr(), saved[3].data_ptr(), saved[4].data_ptr(), saved[5].data_ptr()
         g.h_prev, g.d_gi, g.d_gh = hidden.data_ptr(), d_gi.data_ptr(), d_gh.data_ptr()
+        if _d_hid is not None:                        # (_ActorTrainHidFn: the log-std head's gradient at the new hidden state)
+            _d_hid = _d_hid.contiguous()
+            g.d_hidden = _d_hid.data_ptr()
         fused = GRU_BWD_FUSED
         if fused:
             # ... and the first layer's backward in the same launch (round 3): dx = d_gi @ W_ih on the matrix cores, never
@@ -796,6 +981,16 @@ class _ActorTrainFn(th.autograd.Function):
         has_ln = ln_w is not None
         return (None, None, None, None, d_fc1_w, small[2], small[0] if has_ln else None, small[1] if has_ln else None, None,
                 d_w_ih, d_w_hh, d_b_ih, d_b_hh, d_fc2_w, d_fc2_b)
+
+
+class _ActorTrainHidFn(_ActorTrainFn):
+    """_ActorTrainFn whose new hidden state takes a gradient too (FlexGruBwdArgs.d_hidden): the Gaussian agent's log-std
+    head reads it, and autograd sums that head's d_h with nothing else — the mean head's share is formed inside the kernel."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        ctx.hid_grad = True
+        return _ActorTrainFn.forward(ctx, *args)
 
 
 def actor_train_supported(agent, obs, n_agents, agent_id):
@@ -1864,6 +2059,52 @@ def ppo_value_loss_torch(values, old_values, next_values, reward_norm, done, gam
     return value_loss_coef * th.max(surr1, surr2).mean(), returns
 
 
+class _PpoRowsLossFn(th.autograd.Function):
+    """The policy loss of flexnet_ppo_policy_loss_rows: its gradients w.r.t. the means and the log-stds came out of the
+    forward launch."""
+
+    @staticmethod
+    def forward(ctx, means, log_stds, loss, d_means, d_log_stds):
+        ctx.save_for_backward(d_means, d_log_stds)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        d_means, d_log_stds = ctx.saved_tensors
+        from .util import is_unit_seed
+        unit = is_unit_seed(g)
+        dl = None
+        if ctx.needs_input_grad[1]:
+            dl = d_log_stds if unit else d_log_stds * g
+        return (d_means if unit else d_means * g), dl, None, None, None
+
+
+def _ppo_policy_loss_rows(means, log_stds, actions, old_log_prob, advantages, eps_clip):
+    """(loss, ratios) through flexnet_ppo_policy_loss_rows, or None where the library declines."""
+    rows, n, na = means.shape
+    with th.no_grad():
+        m, act, adv = means.detach().contiguous(), actions.contiguous(), advantages.reshape(rows, n).contiguous()
+        ls = log_stds.detach().expand_as(m).contiguous()
+        old = old_log_prob.sum(dim=-1).expand(rows, n).contiguous() if old_log_prob is not None else None
+        loss = th.empty((), dtype=th.float32, device=m.device)
+        d_means, ratio = th.empty_like(m), th.empty(rows, n, dtype=th.float32, device=m.device)
+        want_dl = log_stds.requires_grad
+        d_log_stds = th.empty_like(m) if want_dl else m.new_empty(0)
+        ws = _ppo_workspace(m.device)
+        a = _lib.FlexPpoPolicyRowsArgs()
+        a.rows, a.n_agents, a.act_dim, a.eps_clip = rows, n, na, float(eps_clip)
+        a.means, a.log_stds, a.actions, a.advantages = m.data_ptr(), ls.data_ptr(), act.data_ptr(), adv.data_ptr()
+        if old is not None:
+            a.old_log_prob = old.data_ptr()
+        a.loss, a.d_means, a.ratio = loss.data_ptr(), d_means.data_ptr(), ratio.data_ptr()
+        if want_dl:
+            a.d_log_stds = d_log_stds.data_ptr()
+        a.workspace, a.workspace_floats = ws.data_ptr(), 2 * ws.numel()
+        if not _lib.try_launch("flexnet_ppo_policy_loss_rows", a):
+            return None
+    return _PpoRowsLossFn.apply(means, log_stds, loss, d_means, d_log_stds), ratio
+
+
 class _PpoLossFn(th.autograd.Function):
     """A loss of csrc/ppo.hip whose gradient w.r.t. its one differentiable input came out of the forward launch."""
 
@@ -1904,6 +2145,12 @@ def ppo_policy_loss(means, log_stds, actions, old_log_prob, advantages, eps_clip
             ran = _lib.try_launch("flexnet_ppo_policy_loss", a)
         if ran:
             return _PpoLossFn.apply(means, loss, d_means), ratio
+    if (fused and every and n <= 8 and na <= 8 and na > 1 and means.is_cuda and actions.shape == means.shape
+            and ppo_fused_supported((), means, actions, advantages, old_log_prob, log_stds)
+            and getattr(log_stds, "_flex_entropy", None) is None and log_stds.shape == means.shape):
+        out = _ppo_policy_loss_rows(means, log_stds, actions, old_log_prob, advantages, eps_clip)      # learned log-stds
+        if out is not None:
+            return out
     if fused and means.is_cuda:
         note_fallback("ppo_policy_loss", f"agents {n}, act_dim {na}, dtype {means.dtype}, every action available: {every}")
     loss, ratios = ppo_policy_loss_torch(means, log_stds, actions, actions if old_log_prob is None else old_log_prob,
