@@ -66,6 +66,8 @@ def main():
     ap.add_argument("--batch-scale", type=int, default=None)
     ap.add_argument("--gaussian-policy", action="store_true",
                     help="learned log-std heads (gaussian_policy: True, LOG_STD_MIN 0.0 / LOG_STD_MAX 0.5 of default.yaml)")
+    ap.add_argument("--agent-type", choices=["rnn", "mlp"], default="rnn",
+                    help="agent_type of default.yaml: the recurrent agent, or the MLP agent on the stacked history (csrc/mlp_agent.hip)")
     a = ap.parse_args()
 
     import torch
@@ -105,6 +107,8 @@ def main():
         alg.update(COMA_ALG_ARGS)
     if a.gaussian_policy:
         alg.update(gaussian_policy=True)
+    if a.agent_type != "rnn":
+        alg.update(agent_type=a.agent_type)
     alg.update(alg=a.alg, agent_num=env.n_agents, obs_size=env.obs_size, state_size=env.state_size,
                action_dim=4, v_min=0.9, v_max=1.1)
     args = convert(alg)
@@ -138,6 +142,8 @@ def main():
                "stat": {k: (float(v) if not isinstance(v, float) else v) for k, v in stat.items()},
                # fused paths that declined a call and ran their PyTorch composition instead (util.note_fallback): none expected
                "fallbacks": dict(FALLBACKS)}
+        if a.agent_type != "rnn":
+            out["agent_type"] = a.agent_type
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

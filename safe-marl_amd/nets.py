@@ -118,7 +118,8 @@ class RNNAgent(nn.Module):
 
 
 class MLPAgent(nn.Module):
-    """madrl/agents/mlp_agent.py:5-32 (agent_type: mlp)."""
+    """madrl/agents/mlp_agent.py:5-32 (agent_type: mlp): fc1 -> LayerNorm -> act -> fc2 -> act -> fc3; forward returns
+    (action mean, None, h).  Runs as the tensor composition."""
 
     def __init__(self, input_shape, args):
         super().__init__()
@@ -127,8 +128,12 @@ class MLPAgent(nn.Module):
         if args.layernorm:
             self.layernorm = nn.LayerNorm(args.hid_size)
         self.fc2 = nn.Linear(args.hid_size, args.hid_size)
-        self.fc3 = nn.Linear(args.hid_size, args.action_dim)
+        self._build_heads(args)
         self._act = _activation(args.hid_activation)
+
+    def _build_heads(self, args):
+        """What follows fc2 (MLPAgentGaussian: ``mean`` and ``log_std``; ``fc3`` is then a property over ``mean``)."""
+        self.fc3 = nn.Linear(args.hid_size, args.action_dim)
 
     def init_hidden(self):
         return self.fc1.weight.new_zeros(1, self.args.hid_size)
@@ -285,30 +290,24 @@ class RNNAgentGaussian(RNNAgent):
         return _ActorTrainHidFn
 
 
-class MLPAgentGaussian(nn.Module):
-    """madrl/agents/mlp_agent_gaussian.py:7-41 (agent_type: mlp): runs as the tensor composition."""
+class MLPAgentGaussian(MLPAgent):
+    """madrl/agents/mlp_agent_gaussian.py:7-41 (agent_type: mlp): the MLP agent with the heads ``mean`` and ``log_std`` in
+    place of ``fc3``; forward returns (mean, log_std, h).  Runs as the tensor composition."""
 
-    def __init__(self, input_shape, args):
-        super().__init__()
-        self.args = args
-        self.fc1 = nn.Linear(input_shape, args.hid_size)
-        if args.layernorm:
-            self.layernorm = nn.LayerNorm(args.hid_size)
-        self.fc2 = nn.Linear(args.hid_size, args.hid_size)
+    def _build_heads(self, args):
         self.mean = nn.Linear(args.hid_size, args.action_dim)
         self.log_std = nn.Linear(args.hid_size, args.action_dim)
-        self._act = _activation(args.hid_activation)
 
-    def init_hidden(self):
-        return self.fc1.weight.new_zeros(1, self.args.hid_size)
+    @property
+    def fc3(self):
+        # a CLASS property (as RNNAgentGaussian.fc2): the base class reads self.fc3 as the mean head, and no "fc3.*" key
+        # enters the state_dict
+        return self.mean
 
     def forward(self, inputs, hidden_state):
-        x = self.fc1(inputs)
-        if self.args.layernorm:
-            x = self.layernorm(x)
-        h = self._act(self.fc2(self._act(x)))
+        mean, _, h = super().forward(inputs, hidden_state)
         log_std = gauss_log_std_torch(h, self.log_std.weight, self.log_std.bias, self.args.LOG_STD_MIN, self.args.LOG_STD_MAX)
-        return self.mean(h), log_std, h
+        return mean, log_std, h
 
 
 class MLPCritic(nn.Module):
