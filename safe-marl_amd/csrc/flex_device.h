@@ -71,6 +71,43 @@ struct LaneNet {
     int mk[6];                   // high words (1.0 or 0.0) of the segmented-scan step masks
 };
 
+// The DevNet header scalars a solve reads, behind one interface.  NetHdrMem reads each from the table at its point of use
+// (every kernel that solves once per launch: the compiler's choice of load stays what it was).  NetHdrRegs holds them in
+// three scalar registers, read ONCE per launch by flex_step_many_kernel: inside its loop the kernel has stored to global
+// memory, the table can no longer be proven unwritten, and every read of it is a VECTOR load with a wait on the
+// vector-memory counter behind it — which on gfx9 retires in order, so it also drains every prefetch and store still in flight.
+struct NetHdrMem {
+    const DevNet* __restrict__ net;
+    __device__ __forceinline__ int n_levels() const { return net->n_levels; }
+    __device__ __forceinline__ int max_children() const { return net->max_children; }
+    __device__ __forceinline__ int n_jump_rounds() const { return net->n_jump_rounds; }
+    __device__ __forceinline__ int n_seg_rounds() const { return net->n_seg_rounds; }
+    __device__ __forceinline__ int acc_lane() const { return net->acc_lane; }
+    __device__ __forceinline__ float acc_kappa() const { return net->acc_kappa; }
+    __device__ __forceinline__ float sweep_tol_frac() const { return net->sweep_tol_frac; }
+};
+struct NetHdrRegs {
+    // n_levels (<= FLEX_MAX_BUS) | max_children << 8 (<= 8) | n_jump_rounds << 12 (<= 6) | n_seg_rounds << 16 | acc_lane << 24
+    uint32_t w;
+    float kappa, tol_frac;
+    __device__ __forceinline__ int n_levels() const { return (int)(w & 0xFFu); }
+    __device__ __forceinline__ int max_children() const { return (int)((w >> 8) & 0xFu); }
+    __device__ __forceinline__ int n_jump_rounds() const { return (int)((w >> 12) & 0xFu); }
+    __device__ __forceinline__ int n_seg_rounds() const { return (int)((w >> 16) & 0xFFu); }
+    __device__ __forceinline__ int acc_lane() const { return (int)(w >> 24); }
+    __device__ __forceinline__ float acc_kappa() const { return kappa; }
+    __device__ __forceinline__ float sweep_tol_frac() const { return tol_frac; }
+};
+__device__ __forceinline__ NetHdrRegs load_net_hdr(const DevNet* __restrict__ net) {
+    NetHdrRegs h;
+    const uint32_t w = (uint32_t)net->n_levels | (uint32_t)net->max_children << 8 | (uint32_t)net->n_jump_rounds << 12 |
+                       (uint32_t)net->n_seg_rounds << 16 | (uint32_t)net->acc_lane << 24;
+    h.w = (uint32_t)__builtin_amdgcn_readfirstlane((int)w);
+    h.kappa = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(net->acc_kappa)));
+    h.tol_frac = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(net->sweep_tol_frac)));
+    return h;
+}
+
 template <int EPW>
 __device__ __forceinline__ void load_lane_net(const DevNet* __restrict__ net, int lane, LaneNet& ln) {
     constexpr int LW = FLEX_WAVE / EPW;
@@ -339,11 +376,11 @@ __device__ __forceinline__ NewtonLocal newton_local(const LaneNet& ln, int maxc,
 // reduction).  A group that has converged keeps stepping harmlessly while its neighbour finishes.
 //
 // Returns (per group) true when converged; `iters` = Newton steps taken until then.
-template <int EPW>
-__device__ __forceinline__ bool pf_newton_tree(const DevNet* __restrict__ net, const LaneNet& ln,
+template <int EPW, typename H>
+__device__ __forceinline__ bool pf_newton_tree(const H& h, const DevNet* __restrict__ net, const LaneNet& ln,
                                                double pnet, double qnet, double& e, double& f,
                                                double tol, int max_iter, int& iters) {
-    const int n_levels = net->n_levels, maxc = net->max_children;
+    const int n_levels = h.n_levels(), maxc = h.max_children();
     const double ps = -pnet, qs = -qnet;
     const int lane = ln.lane;
     bool ok = false;
@@ -410,6 +447,12 @@ __device__ __forceinline__ bool pf_newton_tree(const DevNet* __restrict__ net, c
         if (ln.pq) { e += dx0; f += dx1; }
     }
     return ok;
+}
+template <int EPW>
+__device__ __forceinline__ bool pf_newton_tree(const DevNet* __restrict__ net, const LaneNet& ln,
+                                               double pnet, double qnet, double& e, double& f,
+                                               double tol, int max_iter, int& iters) {
+    return pf_newton_tree<EPW>(NetHdrMem{net}, net, ln, pnet, qnet, e, f, tol, max_iter, iters);
 }
 
 // ---- backward/forward sweep (Z-bus Gauss) on the radial feeder ------------------------------------
@@ -510,10 +553,10 @@ __device__ __forceinline__ void zbus_apply_f32(const LaneNet& ln, const float (&
     xr = ar; xi = ai;
 }
 
-template <int EPW>
-__device__ __forceinline__ int pf_sweep(const DevNet* __restrict__ net, const LaneNet& ln, double pnet,
+template <int EPW, typename H>
+__device__ __forceinline__ int pf_sweep(const H& h, const DevNet* __restrict__ net, const LaneNet& ln, double pnet,
                                         double qnet, double& e, double& f, double tol, int max_sweeps) {
-    const int seg_rounds = net->n_seg_rounds, jump_rounds = net->n_jump_rounds;
+    const int seg_rounds = h.n_seg_rounds(), jump_rounds = h.n_jump_rounds();
     const bool use_seg = seg_rounds <= 2;       // deeper segment nesting: pointer jumping, fp64 sweeps only
     const double ps = ln.pq ? -pnet : 0.0, qs = ln.pq ? -qnet : 0.0;
     const float psf = (float)ps, qsf = (float)qs, rf = (float)ln.r, xf = (float)ln.x;
@@ -537,8 +580,8 @@ __device__ __forceinline__ int pf_sweep(const DevNet* __restrict__ net, const La
 #define FLEX_SWEEP_NOTE_PASS(miss, itv) do { } while (0)
 #endif
     bool fine = false;                          // re-anchored below the coarse threshold already
-    const float kappa = use_seg ? net->acc_kappa : 0.0f;
-    const int acc_lane = net->acc_lane;
+    const float kappa = use_seg ? h.acc_kappa() : 0.0f;
+    const int acc_lane = h.acc_lane();
     float relax = 1.0f;                         // 1 + omega of the two-sweep extrapolation, set after the first anchor
     while (it < max_sweeps) {
         // ---- anchor: one fp64 sweep from (e, f)
@@ -688,8 +731,8 @@ __device__ __forceinline__ bool pf_newton_dense(const DevNet* __restrict__ net, 
 
 #define FLEX_MAX_SWEEPS 40
 // One power-flow solve per group with the configured solver.  Returns converged?; iters = Newton steps, sweeps = sweeps.
-template <int EPW>
-__device__ __forceinline__ bool pf_solve(const DevNet* __restrict__ net, const LaneNet& ln, int solver, double pnet,
+template <int EPW, typename H>
+__device__ __forceinline__ bool pf_solve(const H& h, const DevNet* __restrict__ net, const LaneNet& ln, int solver, double pnet,
                                          double qnet, double& e, double& f, double tol, int max_iter, int& iters,
                                          int& sweeps) {
     sweeps = 0;
@@ -703,12 +746,18 @@ __device__ __forceinline__ bool pf_solve(const DevNet* __restrict__ net, const L
         //  the verification and paid a Newton step, 18.5 us per launch instead of 11.  Such tolerances sweep to the 1e-10
         //  level, which always re-anchors first; looser ones are met on the first anchor for real, tighter ones never were.
         //  Decided here, once per solve: a test inside the increment loop cost the default tolerance 3 %.)
-        double sweep_tol = (double)net->sweep_tol_frac * tol;
+        double sweep_tol = (double)h.sweep_tol_frac() * tol;
         if (sweep_tol < 2e-8 && sweep_tol > 2.5e-11) sweep_tol = 2.5e-11;
-        sweeps = pf_sweep<EPW>(net, ln, pnet, qnet, e, f, sweep_tol, FLEX_MAX_SWEEPS);
+        sweeps = pf_sweep<EPW>(h, net, ln, pnet, qnet, e, f, sweep_tol, FLEX_MAX_SWEEPS);
         if (sweeps >= FLEX_MAX_SWEEPS) { e = 1.0; f = 0.0; }   // sweeps stalled: Newton from a flat start
     }
-    return pf_newton_tree<EPW>(net, ln, pnet, qnet, e, f, tol, max_iter, iters);
+    return pf_newton_tree<EPW>(h, net, ln, pnet, qnet, e, f, tol, max_iter, iters);
+}
+template <int EPW>
+__device__ __forceinline__ bool pf_solve(const DevNet* __restrict__ net, const LaneNet& ln, int solver, double pnet,
+                                         double qnet, double& e, double& f, double tol, int max_iter, int& iters,
+                                         int& sweeps) {
+    return pf_solve<EPW>(NetHdrMem{net}, net, ln, solver, pnet, qnet, e, f, tol, max_iter, iters, sweeps);
 }
 
 // ---- per-building action handling (env:262-293, 621-677) -----------------------------------------

@@ -561,11 +561,20 @@ void flex_reset_kernel(KArgs a, const uint8_t* __restrict__ mask, DevResetSpec i
 #ifndef FLEX_MANY_EARLY_HEAD
 #define FLEX_MANY_EARLY_HEAD 1
 #endif
+// FLEX_MANY_HDR_REGS: the DevNet header scalars the solve reads (NetHdrRegs) are loaded once per launch into scalar registers,
+//   not at the head of the sweeps and of the verification in every step — inside the loop the kernel has stored to global
+//   memory, so those reads are VECTOR loads, each with a wait on the vector-memory counter behind it; that counter counts loads
+//   and stores alike and retires them in order, so the wait also drains the prefetches meant to land under the solve and the
+//   previous step's stores.
+#ifndef FLEX_MANY_HDR_REGS
+#define FLEX_MANY_HDR_REGS 1
+#endif
 struct StepCarry {
     flex_v4i iv;                 // steps, start, row, pushes: the 16 bytes the step wrote to ienv
     bool have;                   // wavefront-uniform: everything below is current
     bool have_iv;                // wavefront-uniform: `iv` is current although the rest is not (the launch's first step)
     LaneNet ln;
+    NetHdrRegs hdr;              // FLEX_MANY_HDR_REGS: the table's header scalars, in scalar registers for the whole launch
     // FLEX_MANY_PREFETCH_ACT: this step's actions, requested by the step before (by the kernel for the first step); the
     // actions are never written by the launch, so they hold whatever `have` says
     float4 af;
@@ -742,7 +751,11 @@ __device__ __forceinline__ void flex_step_body(const KArgs& a, const int wave, c
 #ifdef FLEX_MANY_STAMPS
     if constexpr (MANY) { asm volatile("" :: "v"(pnet), "v"(qnet), "v"(e), "v"(f)); FLEX_MANY_STAMP(mc, 0); }
 #endif
-    bool ok = pf_solve<EPW>(a.net, ln, c.solver, pnet, qnet, e, f, c.pf_tol, c.pf_max_iter, iters, sweeps);
+    bool ok;
+    if constexpr (MANY && FLEX_MANY_HDR_REGS)
+        ok = pf_solve<EPW>(mc->hdr, a.net, ln, c.solver, pnet, qnet, e, f, c.pf_tol, c.pf_max_iter, iters, sweeps);
+    else
+        ok = pf_solve<EPW>(a.net, ln, c.solver, pnet, qnet, e, f, c.pf_tol, c.pf_max_iter, iters, sweeps);
 #ifdef FLEX_STAMPS
     asm volatile("" :: "v"(e), "v"(f));
 #endif
@@ -979,6 +992,9 @@ void flex_step_many_kernel(ManyArgs m) {
         if constexpr (sizeof(ActT) == 4) mc.af = ld_at<float4>(b_act, o_act);
         else { mc.ad0 = ld_at<double2>(b_act, o_act); mc.ad1 = ld_at<double2>(b_act, o_act + 16); }
     }
+#endif
+#if FLEX_MANY_HDR_REGS
+    mc.hdr = load_net_hdr(m.k.net);
 #endif
 #ifdef FLEX_MANY_STAMPS
     mc.st_acc[0] = mc.st_acc[1] = mc.st_acc[2] = mc.st_acc[3] = 0;
