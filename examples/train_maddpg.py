@@ -68,7 +68,11 @@ def main():
                     help="learned log-std heads (gaussian_policy: True, LOG_STD_MIN 0.0 / LOG_STD_MAX 0.5 of default.yaml)")
     ap.add_argument("--agent-type", choices=["rnn", "mlp"], default="rnn",
                     help="agent_type of default.yaml: the recurrent agent, or the MLP agent on the stacked history (csrc/mlp_agent.hip)")
+    ap.add_argument("--unshared", action="store_true",
+                    help="shared_params: False of default.yaml — one actor and one critic per agent (csrc/actor_unshared.hip)")
     a = ap.parse_args()
+    if a.unshared and a.alg == "matd3":
+        ap.error("--unshared: MATD3 is built for shared_params (default.yaml:26)")
 
     import torch
     import safe_marl_amd  # noqa: F401
@@ -109,6 +113,8 @@ def main():
         alg.update(gaussian_policy=True)
     if a.agent_type != "rnn":
         alg.update(agent_type=a.agent_type)
+    if a.unshared:
+        alg.update(shared_params=False)
     alg.update(alg=a.alg, agent_num=env.n_agents, obs_size=env.obs_size, state_size=env.state_size,
                action_dim=4, v_min=0.9, v_max=1.1)
     args = convert(alg)
@@ -144,6 +150,8 @@ def main():
                "fallbacks": dict(FALLBACKS)}
         if a.agent_type != "rnn":
             out["agent_type"] = a.agent_type
+        if a.unshared:
+            out["shared_params"] = False
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

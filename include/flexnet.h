@@ -859,6 +859,88 @@ int flexnet_gauss_head_backward(const FlexGaussHeadArgs* args, void* stream);
 int flexnet_gauss_sum_explore(const FlexGaussSumArgs* args, void* stream);
 int flexnet_ppo_policy_loss_rows(const FlexPpoPolicyRowsArgs* args, void* stream);
 
+/* ---- shared_params: False (madrl/models/model.py:124-138: one RNNAgent per agent; csrc/actor_unshared.hip) ------------
+ * flexnet_actor_forward's computation (rnn_agent.py:25-33, the arithmetic of its variant 0) with PER-AGENT weights: row r of
+ * the [rows, .] tensors is agent r % n_agents of sample r / n_agents, and agent i's rows use fc1_w[i], fc1_b[i], ... — the
+ * modules' own parameter tensors through pointer tables, no stacked copy.  Under agent_id, fc1_w[i] is [64, obs_dim +
+ * n_agents] and only its OWN id column obs_dim + i enters (the other one-hot entries are zero).  One wavefront owns 32
+ * samples of one agent on v_mfma_f32_32x32x2_f32 (exact fp32).  No exploration epilogue, ring cursor or in-place
+ * observations.  The six save_* tensors are those of FlexActorArgs (all six or none).
+ * backward: flexnet_gru_backward's fused arithmetic on the same map, from d_means and the saves: d_gi, d_gh [rows, 192], dz
+ *         [rows, 64] (dx = d_gi @ w_ih[i] on the matrix cores, never stored), and d_ln_w, d_ln_b (layernorm), d_fc1_b as
+ *         [n_agents, 64], each summed over the agent's rows in a fixed order through `workspace`: no atomics,
+ *         bit-reproducible.  Agent i's id column of fc1's gradient equals d_fc1_b[i]; its other id columns are zero.  The
+ *         weight gradients are flexnet_wgrad products per agent through its row pitches (a = d_gi + 192 i, lda = 192 n, ...).
+ * hid 64, ReLU, obs_dim <= FLEXNET_MAX_OBS, n_agents <= FLEXNET_MAX_AGENTS, act_dim <= FLEXNET_MAX_ACT, fp32, contiguous,
+ * the [rows, 64] / [rows, 192] tensors and w_ih / w_hh / fc2_w 16-byte aligned; else FLEXNET_EUNSUPPORTED.  Missing
+ * tensors, rows % n_agents != 0, a short workspace: FLEXNET_EINVAL.  Both before any HIP call. */
+#define FLEXNET_ACTOR_UNSHARED_WS_FLOATS (FLEXNET_MAX_AGENTS * 128 * 192)
+typedef struct {
+    int32_t rows;              /* b * n_agents */
+    int32_t n_agents;
+    int32_t obs_dim;
+    int32_t act_dim;
+    int32_t agent_id;
+    int32_t layernorm;
+    float ln_eps;
+    int32_t pad0;
+    const float* obs;          /* [rows, obs_dim] */
+    const float* hidden_in;    /* [rows, 64] */
+    const float* fc1_w[FLEXNET_MAX_AGENTS];    /* per agent: [64, obs_dim (+ n_agents)] */
+    const float* fc1_b[FLEXNET_MAX_AGENTS];    /* [64] */
+    const float* ln_w[FLEXNET_MAX_AGENTS];     /* [64] (layernorm) */
+    const float* ln_b[FLEXNET_MAX_AGENTS];
+    const float* w_ih[FLEXNET_MAX_AGENTS];     /* [192, 64], gate order r, z, n */
+    const float* w_hh[FLEXNET_MAX_AGENTS];
+    const float* b_ih[FLEXNET_MAX_AGENTS];     /* [192] */
+    const float* b_hh[FLEXNET_MAX_AGENTS];
+    const float* fc2_w[FLEXNET_MAX_AGENTS];    /* [act_dim, 64] */
+    const float* fc2_b[FLEXNET_MAX_AGENTS];    /* [act_dim] */
+    float* means;              /* out [rows, act_dim] */
+    float* hidden_out;         /* out [rows, 64] */
+    float* save_z1;            /* out [rows, 64] each, all six or none (FlexActorArgs.save_*) */
+    float* save_x;
+    float* save_r;
+    float* save_z;
+    float* save_n;
+    float* save_hn;
+} FlexActorUnsharedArgs;
+
+typedef struct {
+    int32_t rows;
+    int32_t n_agents;
+    int32_t obs_dim;
+    int32_t act_dim;
+    int32_t agent_id;
+    int32_t layernorm;
+    float ln_eps;
+    int32_t pad0;
+    const float* d_means;      /* [rows, act_dim] */
+    const float* r;            /* the forward's saves, [rows, 64] each */
+    const float* z;
+    const float* n;
+    const float* hn;
+    const float* h_prev;       /* [rows, 64]: the forward's hidden_in */
+    const float* z1;
+    const float* x;
+    const float* fc1_w[FLEXNET_MAX_AGENTS];
+    const float* fc1_b[FLEXNET_MAX_AGENTS];
+    const float* ln_w[FLEXNET_MAX_AGENTS];     /* (layernorm) */
+    const float* w_ih[FLEXNET_MAX_AGENTS];
+    const float* fc2_w[FLEXNET_MAX_AGENTS];
+    float* d_gi;               /* out [rows, 192] */
+    float* d_gh;               /* out [rows, 192] */
+    float* dz;                 /* out [rows, 64] */
+    float* d_ln_w;             /* out [n_agents, 64] (layernorm) */
+    float* d_ln_b;
+    float* d_fc1_b;            /* out [n_agents, 64] */
+    float* workspace;
+    int64_t workspace_floats;  /* >= FLEXNET_ACTOR_UNSHARED_WS_FLOATS */
+} FlexActorUnsharedBwdArgs;
+
+int flexnet_actor_unshared_forward(const FlexActorUnsharedArgs* args, void* stream);
+int flexnet_actor_unshared_backward(const FlexActorUnsharedBwdArgs* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

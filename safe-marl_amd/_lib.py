@@ -82,6 +82,7 @@ SYMBOLS = (
     "flexnet_ppo_gae", "flexnet_ppo_policy_loss", "flexnet_ppo_value_loss",
     "flexnet_coma_baseline", "flexnet_coma_policy_loss",
     "flexnet_gauss_head_forward", "flexnet_gauss_head_backward", "flexnet_gauss_sum_explore", "flexnet_ppo_policy_loss_rows",
+    "flexnet_actor_unshared_forward", "flexnet_actor_unshared_backward",
     "flexopf_qp_work_doubles", "flexopf_qp_solve",
 )
 
@@ -144,6 +145,28 @@ class FlexGruBwdArgs(C.Structure):
                [("workspace_floats", C.c_int64), ("d_id_agent_stride", C.c_int64), ("d_id_unit_stride", C.c_int64),
                 ("fc1_ld", C.c_int32), ("obs_dim", C.c_int32), ("n_agents", C.c_int32), ("agent_id", C.c_int32),
                 ("layernorm", C.c_int32), ("ln_eps", C.c_float)]
+
+
+FLEXNET_MAX_AGENTS = 8
+FLEXNET_ACTOR_UNSHARED_WS_FLOATS = FLEXNET_MAX_AGENTS * 128 * 192
+_UNSHARED_HEAD = [(k, C.c_int32) for k in ("rows", "n_agents", "obs_dim", "act_dim", "agent_id", "layernorm")] + \
+                 [("ln_eps", C.c_float), ("pad0", C.c_int32)]
+_AgentPtrs = C.c_void_p * FLEXNET_MAX_AGENTS
+
+
+class FlexActorUnsharedArgs(C.Structure):
+    """include/flexnet.h: per-agent parameter tables (csrc/actor_unshared.hip)"""
+    _fields_ = _UNSHARED_HEAD + [("obs", C.c_void_p), ("hidden_in", C.c_void_p)] + \
+               [(k, _AgentPtrs) for k in ("fc1_w", "fc1_b", "ln_w", "ln_b", "w_ih", "w_hh", "b_ih", "b_hh", "fc2_w", "fc2_b")] + \
+               [(k, C.c_void_p) for k in ("means", "hidden_out", "save_z1", "save_x", "save_r", "save_z", "save_n", "save_hn")]
+
+
+class FlexActorUnsharedBwdArgs(C.Structure):
+    """include/flexnet.h"""
+    _fields_ = _UNSHARED_HEAD + [(k, C.c_void_p) for k in ("d_means", "r", "z", "n", "hn", "h_prev", "z1", "x")] + \
+               [(k, _AgentPtrs) for k in ("fc1_w", "fc1_b", "ln_w", "w_ih", "fc2_w")] + \
+               [(k, C.c_void_p) for k in ("d_gi", "d_gh", "dz", "d_ln_w", "d_ln_b", "d_fc1_b", "workspace")] + \
+               [("workspace_floats", C.c_int64)]
 
 
 class FlexCriticTailArgs(C.Structure):
@@ -433,6 +456,10 @@ def load():
     lib.flexnet_window_refresh.restype = C.c_int
     lib.flexnet_gru_backward.argtypes = [C.POINTER(FlexGruBwdArgs), vp]
     lib.flexnet_gru_backward.restype = C.c_int
+    lib.flexnet_actor_unshared_forward.argtypes = [C.POINTER(FlexActorUnsharedArgs), vp]
+    lib.flexnet_actor_unshared_forward.restype = C.c_int
+    lib.flexnet_actor_unshared_backward.argtypes = [C.POINTER(FlexActorUnsharedBwdArgs), vp]
+    lib.flexnet_actor_unshared_backward.restype = C.c_int
     lib.flexenv_set_step_counter.argtypes = [vp, vp, C.c_int64]
     lib.flexenv_set_step_counter.restype = C.c_int
     lib.flexenv_set_obs_ring.argtypes = [vp, vp, C.c_int64, i32]

@@ -23,7 +23,8 @@ import torch.nn as nn
 
 from .nets import (WGRAD_MIN_ROWS, CriticTail, critic_first_layer, critic_td_loss, critic_td_loss_supported, critic_policy_loss,
                    critic_policy_loss_supported, expand_agents, MLPAgent, MLPAgentGaussian, MLPCritic, RNNAgent, RNNAgentGaussian, critic_policy_supported, critic_replayed_supported,
-                   critic_tail_supported, fused_actor_forward, tall_linear, td_loss, td_loss_supported, wide_batch_linear,
+                   critic_tail_supported, fused_actor_forward, fused_actor_forward_unshared, actor_unshared_supported,
+                   actor_unshared_train, tall_linear, td_loss, td_loss_supported, wide_batch_linear,
                    batchnorm_stats_supported, batchnorm_update_running_stats, sync_batchnorm, QMixer,
                    sqddpg_draw, sqddpg_fused_config, sqddpg_shapley_fused, ppo_gae, ppo_policy_loss, ppo_value_loss,
                    coma_baseline, coma_baseline_torch, coma_fused_config, coma_policy_loss, coma_rows)
@@ -473,6 +474,18 @@ class RolloutGraph:
             self.acc.zero_()
 
 
+class _GraphSafe:
+    """``graph_safe_updates`` of an algorithm whose sub-updates may be captured into a HIP graph: the declared value on the class;
+    on a model, False under ``shared_params: False`` — the per-agent critics' gradient path holds ATen bias and LayerNorm
+    reductions (util.GRAPH_DENYLIST), so those sub-updates run eagerly."""
+
+    def __init__(self, value):
+        self.value = bool(value)
+
+    def __get__(self, obj, owner=None):
+        return self.value if obj is None else bool(self.value and obj.args.shared_params)
+
+
 class Model(nn.Module):
     """model.py:10-323, the parts the MADDPG path uses."""
 
@@ -568,6 +581,21 @@ class Model(nn.Module):
                 if gauss:
                     return means, out[1].view(b, self.n_, -1), hiddens
                 return means, self._log_stds_like(means), hiddens
+        if not self.args.shared_params and obs.is_cuda and self.fused_inference and not gauss:
+            # one actor per agent (model.py:124-138): one launch over all of them (csrc/actor_unshared.hip) instead of the loop
+            # below.  The Gaussian agents keep the loop.
+            out = None
+            if not th.is_grad_enabled():
+                out = fused_actor_forward_unshared(self.policy_dicts, obs, last_hid)
+            elif b * self.n_ >= WGRAD_MIN_ROWS and not last_hid.requires_grad:
+                if actor_unshared_supported(self.policy_dicts, obs, self.args.agent_id):
+                    out = actor_unshared_train(self.policy_dicts, obs, last_hid)
+                else:
+                    note_fallback("actor_unshared", f"update pass: agent_type {self.args.agent_type}, hid {self.args.hid_size}, "
+                                                    f"act {self.args.hid_activation}, obs {tuple(obs.shape)} {obs.dtype}")
+            if out is not None:
+                means = out[0].view(b, self.n_, -1)
+                return means, self._log_stds_like(means), out[1].view(b, self.n_, -1)
         if gauss and obs.is_cuda and not (self.args.shared_params and isinstance(self.policy_dicts[0], RNNAgent)):
             note_fallback("gaussian_policy", f"agent_type {self.args.agent_type}, shared_params {self.args.shared_params}")
         obs = self.with_ids(obs)
@@ -1026,7 +1054,7 @@ class MADDPG(Model):
     # replay fields each loss reads (get_loss below; MATD3 and SAFEMADDPG read the same ones): a graphed sub-update
     # refreshes only these columns of its static batch
     # (reward in both: unpack_data's batch-norm running statistics move on every get_loss call, model.py:308-323)
-    graph_safe_updates = True       # trainer._graphed_sub_update: the gradient path uses no multi-block PyTorch reduction
+    graph_safe_updates = _GraphSafe(True)       # trainer._graphed_sub_update: the gradient path uses no multi-block PyTorch reduction
     update_fields = {"policy": ("state", "reward", "last_hid"),
                      "value": ("state", "action", "reward", "next_state", "done", "hid"),
                      # trainer.replay_event with the bootstrap values filed per transition first (round 3)
@@ -1382,7 +1410,7 @@ class MATD3(MADDPG):
 
     # since round 2 the GPU path of both losses reduces only through this project's fixed-order kernels (twin critic
     # nodes, flexnet_td_loss, flexnet_scaled_sum, pointwise agent sums): sub-updates replay as HIP graphs like MADDPG's
-    graph_safe_updates = True
+    graph_safe_updates = _GraphSafe(True)
 
     def construct_value_net(self):
         """matd3.py:18-27: the MADDPG critic input plus the twin flag."""
@@ -1498,7 +1526,7 @@ class IDDPG(MADDPG):
     independent critics Q_i(o_i, a_i) on the agent's own observation and action (plus its one-hot id), the same
     DDPG losses as MADDPG, and the agent-summed action selection it shares with MATD3 (iddpg.py:66-71)."""
 
-    graph_safe_updates = True       # as MATD3: no PyTorch reduction is left on the GPU path of either loss
+    graph_safe_updates = _GraphSafe(True)       # as MATD3: no PyTorch reduction is left on the GPU path of either loss
 
     def construct_value_net(self):
         """iddpg.py:17-26"""

@@ -1003,6 +1003,193 @@ def actor_train_supported(agent, obs, n_agents, agent_id):
             and getattr(agent, "fused_training", True) and getattr(agent, "fused_epilogue", True))
 
 
+_UNSHARED_WS = {}
+_UNSHARED_TABLES = ("fc1_w", "fc1_b", "ln_w", "ln_b", "w_ih", "w_hh", "b_ih", "b_hh", "fc2_w", "fc2_b")
+ACTOR_UNSHARED_MAX_ROWS = 1 << 26        # csrc/wgrad.hip addresses a block's rows through 32-bit byte offsets
+
+
+def _unshared_params(agent):
+    """The ten parameters of one RNNAgent in ``_UNSHARED_TABLES`` order (the LayerNorm pair None without layernorm)."""
+    ln = agent.layernorm if agent.args.layernorm else None
+    r = agent.rnn
+    return (agent.fc1.weight, agent.fc1.bias, None if ln is None else ln.weight, None if ln is None else ln.bias,
+            r.weight_ih, r.weight_hh, r.bias_ih, r.bias_hh, agent.fc2.weight, agent.fc2.bias)
+
+
+def _unshared_declines(agents, obs, agent_id):
+    """Why csrc/actor_unshared.hip does not cover these per-agent actors on ``obs`` [b, n, obs_dim], or None."""
+    n, o = len(agents), obs.shape[-1]
+    a = agents[0].args
+    if not (obs.is_cuda and obs.dtype == th.float32 and obs.dim() == 3 and obs.shape[1] == n):
+        return f"obs {tuple(obs.shape)} {obs.dtype} for {n} agents"
+    if not (a.hid_size == 64 and a.hid_activation == "relu" and o <= 144 and 1 <= n <= 8 and a.action_dim <= 8):
+        return f"hid {a.hid_size}, act {a.hid_activation}, obs {o}, agents {n}, actions {a.action_dim}"
+    if obs.shape[0] * n >= ACTOR_UNSHARED_MAX_ROWS:
+        return f"{obs.shape[0] * n} rows"
+    for i, agent in enumerate(agents):
+        if type(agent) is not RNNAgent:              # (the Gaussian agent keeps the composition)
+            return f"agent {i} is a {type(agent).__name__}"
+        if agent.fc1.weight.shape[1] != o + (n if agent_id else 0):
+            return f"agent {i}: fc1 takes {agent.fc1.weight.shape[1]} columns, obs {o}, agent_id {bool(agent_id)}"
+        if not (getattr(agent, "fused_training", True) and getattr(agent, "fused_epilogue", True)):
+            return f"agent {i}: fused passes switched off"
+        for p in _unshared_params(agent):
+            if p is not None and not (p.is_cuda and p.dtype == th.float32 and p.is_contiguous()):
+                return f"agent {i}: a parameter is not a contiguous fp32 device tensor"
+    return None
+
+
+def actor_unshared_supported(agents, obs, agent_id, train=True):
+    """``actor_train_supported``'s conditions for EVERY agent of a ``shared_params: False`` model (obs [b, n, obs_dim]), and
+    ``type(agent) is RNNAgent``; ``train``: also the row threshold of the hand-written weight gradients."""
+    return (_unshared_declines(agents, obs, agent_id) is None and not obs.requires_grad
+            and (not train or obs.shape[0] * obs.shape[1] >= WGRAD_MIN_ROWS))
+
+
+def _unshared_args(cls, params, rows, n, o, act_dim, agent_id, ln_eps):
+    a = cls()
+    a.rows, a.n_agents, a.obs_dim, a.act_dim = rows, n, o, act_dim
+    a.agent_id, a.layernorm, a.ln_eps = int(bool(agent_id)), int(params[0][2] is not None), float(ln_eps)
+    names = {f[0] for f in cls._fields_}
+    for k, name in enumerate(_UNSHARED_TABLES):
+        if name in names:
+            table = getattr(a, name)
+            for i in range(n):
+                p = params[i][k]
+                table[i] = None if p is None else p.data_ptr()
+    return a
+
+
+def _unshared_launch_forward(params, obs, hidden, n, agent_id, ln_eps, saved=None):
+    """One flexnet_actor_unshared_forward launch on obs [rows, o], hidden [rows, 64] (both contiguous); (means, hidden) or None
+    when the library answers FLEXNET_EUNSUPPORTED."""
+    rows, o = obs.shape
+    act_dim = params[0][8].shape[0]
+    means = th.empty(rows, act_dim, dtype=th.float32, device=obs.device)
+    hid_out = th.empty(rows, 64, dtype=th.float32, device=obs.device)
+    a = _unshared_args(_lib.FlexActorUnsharedArgs, params, rows, n, o, act_dim, agent_id, ln_eps)
+    a.obs, a.hidden_in, a.means, a.hidden_out = obs.data_ptr(), hidden.data_ptr(), means.data_ptr(), hid_out.data_ptr()
+    if saved is not None:
+        for k, name in enumerate(("save_z1", "save_x", "save_r", "save_z", "save_n", "save_hn")):
+            setattr(a, name, saved[k].data_ptr())
+    if not _lib.try_launch("flexnet_actor_unshared_forward", a):
+        return None
+    return means, hid_out
+
+
+def _unshared_ln_eps(agents):
+    return float(agents[0].layernorm.eps) if agents[0].args.layernorm else 1e-5
+
+
+def fused_actor_forward_unshared(agents, obs, hidden):
+    """model.py:124-138 (one RNNAgent per agent) without an autograd graph, in ONE HIP launch (csrc/actor_unshared.hip) instead
+    of the loop's ten kernels per agent.  ``obs`` [b, n, obs_dim] WITHOUT the one-hot id columns (agent i's own id column of
+    its fc1 is added by the kernel), ``hidden`` [b, n, 64] or [b * n, 64].  Returns (means [b * n, act], hidden [b * n, 64]) in
+    the caller's row order, or None after ``note_fallback("actor_unshared", ...)`` when it declines on GPU tensors."""
+    agents = list(agents)
+    n, o = len(agents), obs.shape[-1]
+    agent_id = agents[0].fc1.weight.shape[1] != o
+    why = _unshared_declines(agents, obs, agent_id)
+    if why is None and hidden.dtype != th.float32:
+        why = f"hidden {hidden.dtype}"
+    if why is not None:
+        if obs.is_cuda:
+            note_fallback("actor_unshared", why)
+        return None
+    rows = obs.shape[0] * n
+    with th.no_grad():
+        out = _unshared_launch_forward([_unshared_params(g) for g in agents], obs.reshape(rows, o).contiguous(),
+                                       hidden.reshape(rows, 64).contiguous(), n, agent_id, _unshared_ln_eps(agents))
+    if out is None:
+        note_fallback("actor_unshared", "FLEXNET_EUNSUPPORTED from flexnet_actor_unshared_forward")
+    return out
+
+
+class _ActorUnsharedTrainFn(th.autograd.Function):
+    """The per-agent actors of ``shared_params: False`` for an update batch as ONE autograd node (csrc/actor_unshared.hip): the
+    fused forward with its saves, one backward launch for the gate gradients, dx and the first layer's epilogue of every agent,
+    then csrc/wgrad.hip per agent through row pitches (rows a, a + n, ... of the [rows, .] tensors are agent a's).  The id block
+    of agent a's fc1 gradient is zero except its own column a, which is its bias gradient (the one-hot input).  Observations
+    and the previous hidden state take no gradient; the new hidden state is non-differentiable.  Bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, obs, hidden, n_agents, agent_id, ln_eps, *flat):
+        rows, o = obs.shape
+        params = [flat[10 * i:10 * i + 10] for i in range(n_agents)]
+        obs, hidden = obs.contiguous(), hidden.contiguous()
+        saved = th.empty(6, rows, 64, dtype=th.float32, device=obs.device)          # z1 | x | r | z | n | hn
+        out = _unshared_launch_forward(params, obs, hidden, n_agents, agent_id, ln_eps, saved)
+        if out is None:
+            _lib.check(_lib.FLEXNET_EUNSUPPORTED, "flexnet_actor_unshared_forward")
+        means, hid_out = out
+        ctx.n_agents, ctx.agent_id, ctx.ln_eps = n_agents, bool(agent_id), float(ln_eps)
+        ctx.has_ln = params[0][2] is not None
+        ctx.save_for_backward(obs, hidden, hid_out, saved, *[p for p in flat if p is not None])
+        ctx.mark_non_differentiable(hid_out)
+        ctx.set_materialize_grads(False)
+        return means, hid_out
+
+    @staticmethod
+    def backward(ctx, d_means, _d_hid):
+        obs, hidden, hid_out, saved = ctx.saved_tensors[:4]
+        n, dev, has_ln = ctx.n_agents, obs.device, ctx.has_ln
+        per = 10 if has_ln else 8
+        params = []
+        for i in range(n):
+            p = list(ctx.saved_tensors[4 + per * i:4 + per * (i + 1)])
+            params.append(p if has_ln else p[:2] + [None, None] + p[2:])
+        rows, o = obs.shape
+        b, act_dim = rows // n, params[0][8].shape[0]
+        if d_means is None:
+            return (None,) * (5 + 10 * n)
+        d_means = d_means.contiguous()
+        d_gi = th.empty(rows, 192, dtype=th.float32, device=dev)
+        d_gh = th.empty(rows, 192, dtype=th.float32, device=dev)
+        dz = th.empty(rows, 64, dtype=th.float32, device=dev)
+        small = th.empty(3, n, 64, dtype=th.float32, device=dev)                   # d_ln_w | d_ln_b | d_fc1_b
+        if dev not in _UNSHARED_WS:
+            _UNSHARED_WS[dev] = th.empty(_lib.FLEXNET_ACTOR_UNSHARED_WS_FLOATS, dtype=th.float32, device=dev)
+        ws = _UNSHARED_WS[dev]
+        g = _unshared_args(_lib.FlexActorUnsharedBwdArgs, params, rows, n, o, act_dim, ctx.agent_id, ctx.ln_eps)
+        g.d_means, g.h_prev = d_means.data_ptr(), hidden.data_ptr()
+        g.z1, g.x, g.r, g.z, g.n, g.hn = (saved[k].data_ptr() for k in range(6))
+        g.d_gi, g.d_gh, g.dz = d_gi.data_ptr(), d_gh.data_ptr(), dz.data_ptr()
+        g.d_ln_w, g.d_ln_b, g.d_fc1_b = small[0].data_ptr(), small[1].data_ptr(), small[2].data_ptr()
+        g.workspace, g.workspace_floats = ws.data_ptr(), ws.numel()
+        _lib.launch("flexnet_actor_unshared_backward", g)
+        # the weight gradients: four csrc/wgrad.hip products per agent, each over the agent's rows through the row pitch; the
+        # GRU's and fc2's bias gradients are the column sums of the same passes
+        ld = params[0][0].shape[1]
+        d_fc1_w = th.zeros(n, 64, ld, dtype=th.float32, device=dev) if ctx.agent_id else th.empty(n, 64, ld, dtype=th.float32, device=dev)
+        d_w_ih, d_w_hh = th.empty(2, n, 192, 64, dtype=th.float32, device=dev).unbind(0)
+        d_b_ih, d_b_hh = th.empty(2, n, 192, dtype=th.float32, device=dev).unbind(0)
+        d_fc2_w = th.empty(n, act_dim, 64, dtype=th.float32, device=dev)
+        d_fc2_b = th.empty(n, act_dim, dtype=th.float32, device=dev)
+        obs3, hid3, hout3, x3 = obs.view(b, n, o), hidden.view(b, n, 64), hid_out.view(b, n, 64), saved[1].view(b, n, 64)
+        dm3, dgi3, dgh3, dz3 = d_means.view(b, n, act_dim), d_gi.view(b, n, 192), d_gh.view(b, n, 192), dz.view(b, n, 64)
+        for i in range(n):
+            tall_wgrad(dm3[:, i], hout3[:, i], out=d_fc2_w[i], colsum=d_fc2_b[i])
+            tall_wgrad(dgi3[:, i], x3[:, i], out=d_w_ih[i], colsum=d_b_ih[i])
+            tall_wgrad(dgh3[:, i], hid3[:, i], out=d_w_hh[i], colsum=d_b_hh[i])
+            tall_wgrad(dz3[:, i], obs3[:, i], out=d_fc1_w[i, :, :o])
+        if ctx.agent_id:
+            th.diagonal(d_fc1_w[:, :, o:], dim1=0, dim2=2).copy_(small[2].t())     # [64, n]: agent i's own id column
+        grads = []
+        for i in range(n):
+            grads += [d_fc1_w[i], small[2, i], small[0, i] if has_ln else None, small[1, i] if has_ln else None,
+                      d_w_ih[i], d_w_hh[i], d_b_ih[i], d_b_hh[i], d_fc2_w[i], d_fc2_b[i]]
+        return (None, None, None, None, None, *grads)
+
+
+def actor_unshared_train(agents, obs, hidden):
+    """The node on obs [b, n, obs_dim] / hidden [b, n, 64] (``actor_unshared_supported`` holds): (means, hidden) as [b * n, .]."""
+    agents = list(agents)
+    n, o = len(agents), obs.shape[-1]
+    agent_id = agents[0].fc1.weight.shape[1] != o
+    flat = [p for g in agents for p in _unshared_params(g)]
+    return _ActorUnsharedTrainFn.apply(obs.reshape(-1, o), hidden.reshape(-1, 64), n, agent_id, _unshared_ln_eps(agents), *flat)
+
+
 def lnrelu_supported(agent, n_agents):
     """Configurations csrc/lnrelu.hip covers: 64 hidden units, ReLU, at most FLEXNET_MAX_AGENTS id columns."""
     a = agent.args
