@@ -241,6 +241,21 @@ typedef struct {
 
 int flexnet_wgrad(const FlexWgradArgs* args, void* stream);
 
+/* `count` independent problems C_i = A_i^T B_i in one call — the per-agent weight gradients of `shared_params: False`
+ * (madrl/models/model.py:124-138: one RNNAgent and one MLPCritic per agent, each with its own fc1 / GRUCell / fc2 or fc1 / fc2
+ * of rnn_agent.py:13-33 and mlp_critic.py:5-34).  One first-stage and one second-stage launch per shape class present (the
+ * kernel instantiation flexnet_wgrad picks from m and n), the problem index a grid dimension, the per-problem parameters a
+ * table in the kernel arguments: no host-to-device copy.  Row pitches as in flexnet_wgrad — agent i's rows of an interleaved
+ * [b, n_agents, .] tensor (a = base + width * i, lda = width * n_agents) and a column block of a wider C are ordinary
+ * problems; `colsum` and `accumulate` are per problem.  Every problem brings its own workspace slice (any size from
+ * 520 * 192 + one register image per column chunk; a short one lowers that problem's parallelism): overlapping slices
+ * are FLEXNET_EINVAL.  Thread blocks per problem come from the launch's total, about two per CU over the whole class.  Sums
+ * in a fixed order: bit-reproducible, and count == 1 gives the bits of flexnet_wgrad on the same arguments.
+ * b2 / c2, b_row_cell and the critic-finish rider do not exist here: FLEXNET_EUNSUPPORTED.  count outside
+ * 1..FLEXNET_WGRAD_MAX_BATCH: FLEXNET_EINVAL.  Every check of every problem comes before the first launch. */
+#define FLEXNET_WGRAD_MAX_BATCH (4 * FLEXNET_MAX_AGENTS)
+int flexnet_wgrad_batched(const FlexWgradArgs* problems, int32_t count, void* stream);
+
 /* The actor's first-layer epilogue at update batches (rnn_agent.py:25-29 with the one-hot id columns of
  * model.py:105-108 folded in): out = relu(LayerNorm(z + bias + id_cols[r % n_agents])) for z = obs @ W_obs^T, and the
  * backward of that chain with its four parameter gradients (OVERWRITTEN, summed in a fixed order). */
@@ -940,6 +955,94 @@ typedef struct {
 
 int flexnet_actor_unshared_forward(const FlexActorUnsharedArgs* args, void* stream);
 int flexnet_actor_unshared_backward(const FlexActorUnsharedBwdArgs* args, void* stream);
+
+/* ---- shared_params: False, the critics (madrl/models/model.py:124-138: one MLPCritic per agent; csrc/critic_unshared.hip) ---
+ * Every agent's own MLPCritic (madrl/critics/mlp_critic.py:28-35: fc1 -> LayerNorm -> ReLU -> fc2 -> ReLU -> fc3) in one entry
+ * point per direction, with PER-AGENT weights through pointer tables (the modules' own tensors, no stacked copy).  Row
+ * s * n_agents + a of the [rows, .] tensors is agent a of sample s; q is [b, n_agents].  One wavefront owns 32 samples of one
+ * agent on v_mfma_f32_32x32x2_f32 (exact fp32).
+ * The first layer's input is described by blocks and never materialised.  Every agent's fc1.weight is [64, w1 + n_id + w2] with
+ * the column order [x1 | id columns | x2] (n_id = n_agents under agent_id, else 0); agent a's row of sample s reads
+ *     x1 + s * x1_pitch + a * x1_agent_off  (w1 floats)   and   x2 + s * x2_pitch + a * x2_agent_off  (w2 floats, w2 = 0: none)
+ * — an agent offset of 0 is a block shared by the sample's agents.  The id block is not read: agent a adds its own column
+ * w1 + a.  The four input rows of the reference:
+ *     maddpg.py:33-54   x1 = obs [b, n o] shared,     x2 = act [b, n a] shared  (the others' actions detached by the caller)
+ *     mappo.py:34-62    x1 = obs [b, n o] shared,     no x2
+ *     ippo.py:34-59     x1 = obs [b, n, o] per agent, no x2
+ *     iddpg.py:32-59    x1 = obs [b, n, o] per agent, x2 = act [b, n, a] per agent
+ * forward: q, and with both save_* set z1 (fc1's output with bias and id column) and x (after LayerNorm and ReLU).  The launch
+ *         with and without the saves gives the same bits.
+ * backward: from dq [b, n] and the two saves (fc2's output is recomputed): dz1 [rows, 64]; with param_grads also dz2
+ *         [rows, 64] and the per-agent sums d_ln_w, d_ln_b (layernorm), d_fc1_b, d_fc2_b, d_fc3_w as [n_agents, 64] and d_fc3_b
+ *         [n_agents], each summed over the agent's rows in a fixed order through `workspace` and a second launch: no atomics,
+ *         bit-reproducible.  The weight gradients are flexnet_wgrad_batched problems through row pitches: d_fc2_w[a] =
+ *         dz2[a]^T x[a], d_fc1_w[a] = dz1[a]^T [x1 | x2] into column blocks; agent a's id column of d_fc1_w equals d_fc1_b[a], its
+ *         other id columns are zero.  param_grads = 0 (the policy loss against frozen critics) writes dz1 and d_x2_own only.
+ *         d_x2_own (optional) [b, n_agents, own_w] = dz1[s, a, :] @ fc1_w[a][:, w1 + n_id + own_first + a * own_step .. + own_w):
+ *         the gradient of agent a's OWN action block (maddpg: own_first 0, own_step act_dim; iddpg: 0, 0).  Observations take
+ *         no gradient.
+ * hid 64, ReLU, fp32, n_agents <= FLEXNET_MAX_AGENTS, w1 <= FLEXNET_MAX_AGENTS * FLEXNET_MAX_OBS, w2 <= FLEXNET_MAX_AGENTS *
+ * FLEXNET_MAX_ACT, own_w <= FLEXNET_MAX_ACT, the [rows, 64] tensors and fc2_w 16-byte aligned; else FLEXNET_EUNSUPPORTED.
+ * Missing tensors, rows % n_agents != 0, one save without the other, an own block outside x2, a short workspace:
+ * FLEXNET_EINVAL.  Both before any HIP call. */
+#define FLEXNET_CRITIC_UNSHARED_WS_FLOATS (FLEXNET_MAX_AGENTS * 128 * 384)
+typedef struct {
+    int32_t rows;              /* b * n_agents */
+    int32_t n_agents;
+    int32_t w1, w2;
+    int32_t agent_id;
+    int32_t layernorm;
+    float ln_eps;
+    int32_t pad0;
+    const float* x1;
+    const float* x2;           /* NULL with w2 = 0 */
+    int64_t x1_pitch, x2_pitch;            /* floats between samples */
+    int64_t x1_agent_off, x2_agent_off;    /* floats between a sample's agents; 0: shared */
+    const float* fc1_w[FLEXNET_MAX_AGENTS];    /* per agent: [64, w1 + n_id + w2] */
+    const float* fc1_b[FLEXNET_MAX_AGENTS];    /* [64] */
+    const float* ln_w[FLEXNET_MAX_AGENTS];     /* [64] (layernorm) */
+    const float* ln_b[FLEXNET_MAX_AGENTS];
+    const float* fc2_w[FLEXNET_MAX_AGENTS];    /* [64, 64] */
+    const float* fc2_b[FLEXNET_MAX_AGENTS];    /* [64] */
+    const float* fc3_w[FLEXNET_MAX_AGENTS];    /* [1, 64] */
+    const float* fc3_b[FLEXNET_MAX_AGENTS];    /* [1] */
+    float* q;                  /* out [b, n_agents] */
+    float* save_z1;            /* out [rows, 64] each, both or none */
+    float* save_x;
+} FlexCriticUnsharedArgs;
+
+typedef struct {
+    int32_t rows;
+    int32_t n_agents;
+    int32_t w1, w2;
+    int32_t agent_id;
+    int32_t layernorm;
+    float ln_eps;
+    int32_t param_grads;       /* 0: dz1 and d_x2_own only, no gradient buffer is touched */
+    const float* dq;           /* [b, n_agents] */
+    const float* z1;           /* the forward's saves */
+    const float* x;
+    const float* fc1_w[FLEXNET_MAX_AGENTS];
+    const float* ln_w[FLEXNET_MAX_AGENTS];     /* (layernorm) */
+    const float* fc2_w[FLEXNET_MAX_AGENTS];
+    const float* fc2_b[FLEXNET_MAX_AGENTS];
+    const float* fc3_w[FLEXNET_MAX_AGENTS];
+    float* dz1;                /* out [rows, 64] */
+    float* dz2;                /* out [rows, 64] (param_grads) */
+    float* d_ln_w;             /* out [n_agents, 64] (param_grads and layernorm) */
+    float* d_ln_b;
+    float* d_fc1_b;            /* out [n_agents, 64] (param_grads) */
+    float* d_fc2_b;
+    float* d_fc3_w;
+    float* d_fc3_b;            /* out [n_agents] */
+    float* d_x2_own;           /* out [b, n_agents, own_w], or NULL */
+    int32_t own_first, own_step, own_w, pad1;
+    float* workspace;          /* (param_grads) */
+    int64_t workspace_floats;  /* >= FLEXNET_CRITIC_UNSHARED_WS_FLOATS */
+} FlexCriticUnsharedBwdArgs;
+
+int flexnet_critic_unshared_forward(const FlexCriticUnsharedArgs* args, void* stream);
+int flexnet_critic_unshared_backward(const FlexCriticUnsharedBwdArgs* args, void* stream);
 
 #ifdef __cplusplus
 }

@@ -83,6 +83,7 @@ SYMBOLS = (
     "flexnet_coma_baseline", "flexnet_coma_policy_loss",
     "flexnet_gauss_head_forward", "flexnet_gauss_head_backward", "flexnet_gauss_sum_explore", "flexnet_ppo_policy_loss_rows",
     "flexnet_actor_unshared_forward", "flexnet_actor_unshared_backward",
+    "flexnet_critic_unshared_forward", "flexnet_critic_unshared_backward", "flexnet_wgrad_batched",
     "flexopf_qp_work_doubles", "flexopf_qp_solve",
 )
 
@@ -169,6 +170,30 @@ class FlexActorUnsharedBwdArgs(C.Structure):
                [("workspace_floats", C.c_int64)]
 
 
+FLEXNET_MAX_OBS = 144
+FLEXNET_MAX_ACT = 8
+FLEXNET_CRITIC_UNSHARED_WS_FLOATS = FLEXNET_MAX_AGENTS * 128 * 384
+_CRITIC_UNSHARED_HEAD = [(k, C.c_int32) for k in ("rows", "n_agents", "w1", "w2", "agent_id", "layernorm")] + [("ln_eps", C.c_float)]
+
+
+class FlexCriticUnsharedArgs(C.Structure):
+    """include/flexnet.h: the per-agent critics' forward, the first layer's input as blocks (csrc/critic_unshared.hip)"""
+    _fields_ = _CRITIC_UNSHARED_HEAD + [("pad0", C.c_int32), ("x1", C.c_void_p), ("x2", C.c_void_p)] + \
+               [(k, C.c_int64) for k in ("x1_pitch", "x2_pitch", "x1_agent_off", "x2_agent_off")] + \
+               [(k, _AgentPtrs) for k in ("fc1_w", "fc1_b", "ln_w", "ln_b", "fc2_w", "fc2_b", "fc3_w", "fc3_b")] + \
+               [(k, C.c_void_p) for k in ("q", "save_z1", "save_x")]
+
+
+class FlexCriticUnsharedBwdArgs(C.Structure):
+    """include/flexnet.h"""
+    _fields_ = _CRITIC_UNSHARED_HEAD + [("param_grads", C.c_int32)] + [(k, C.c_void_p) for k in ("dq", "z1", "x")] + \
+               [(k, _AgentPtrs) for k in ("fc1_w", "ln_w", "fc2_w", "fc2_b", "fc3_w")] + \
+               [(k, C.c_void_p) for k in ("dz1", "dz2", "d_ln_w", "d_ln_b", "d_fc1_b", "d_fc2_b", "d_fc3_w", "d_fc3_b",
+                                          "d_x2_own")] + \
+               [(k, C.c_int32) for k in ("own_first", "own_step", "own_w", "pad1")] + \
+               [("workspace", C.c_void_p), ("workspace_floats", C.c_int64)]
+
+
 class FlexCriticTailArgs(C.Structure):
     """include/flexnet.h"""
     _fields_ = [("rows", C.c_int32), ("layernorm", C.c_int32), ("ln_eps", C.c_float), ("variant", C.c_int32)] + \
@@ -194,6 +219,8 @@ class FlexWgradArgs(C.Structure):
 
 
 FLEXNET_WGRAD_WS_FLOATS = 520 * 12288 + 520 * 192
+FLEXNET_WGRAD_MAX_BATCH = 4 * FLEXNET_MAX_AGENTS         # problems per flexnet_wgrad_batched call
+FLEXNET_WGRAD_CS_FLOATS = 520 * 192                      # head of every workspace (slice): the column-sum partials
 
 
 class FlexLnReluArgs(C.Structure):
@@ -476,6 +503,12 @@ def load():
     lib.flexnet_wgrad_critic_finish.restype = C.c_int
     lib.flexnet_wgrad.argtypes = [C.POINTER(FlexWgradArgs), vp]
     lib.flexnet_wgrad.restype = C.c_int
+    lib.flexnet_wgrad_batched.argtypes = [C.POINTER(FlexWgradArgs), i32, vp]
+    lib.flexnet_wgrad_batched.restype = C.c_int
+    lib.flexnet_critic_unshared_forward.argtypes = [C.POINTER(FlexCriticUnsharedArgs), vp]
+    lib.flexnet_critic_unshared_forward.restype = C.c_int
+    lib.flexnet_critic_unshared_backward.argtypes = [C.POINTER(FlexCriticUnsharedBwdArgs), vp]
+    lib.flexnet_critic_unshared_backward.restype = C.c_int
     lib.flexnet_clip_rmsprop.argtypes = [C.POINTER(FlexClipRmspropArgs), vp]
     lib.flexnet_clip_rmsprop.restype = C.c_int
     lib.flexnet_clip_rmsprop_refresh.argtypes = [C.POINTER(FlexClipRmspropArgs), C.POINTER(FlexWindowRefreshArgs), C.POINTER(FlexTdLossArgs), vp]

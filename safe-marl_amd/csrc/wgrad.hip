@@ -1,5 +1,5 @@
 // wgrad.hip — weight gradients of the learner's linear layers: C[m, n] = sum_k A[k, m] * B[k, n] with k = the batch
-// (gfx950).  Boundary: include/flexnet.h (flexnet_wgrad).
+// (gfx950).  Boundary: include/flexnet.h (flexnet_wgrad, flexnet_wgrad_batched).
 //
 // The reference's update (madrl/utils/trainer.py:62-111 -> loss.backward()) spends its GEMM time on exactly this
 // shape: dW = dY^T X for fc1 / GRUCell / fc2 of rnn_agent.py:13-33 and fc1 of mlp_critic.py:5-34, where the summed
@@ -77,178 +77,42 @@ __device__ __forceinline__ void wg_load(__amdgpu_buffer_rsrc_t r, int off, float
 
 template <int MT, int NT, bool CS, bool TWO = false>
 __global__ __launch_bounds__(64 * WG_WAVES, 2) void wgrad_kernel(WgradK p) {
-    __shared__ float fold[WG_IMG(MT, NT)];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t k0 = (int64_t)blockIdx.x * p.rows_per_block;
-    const int64_t left = p.k - k0;
-    const int rows = left < p.rows_per_block ? (int)left : p.rows_per_block;
-    const int n0 = blockIdx.y * (32 * NT);
-    // buffer views of this block's rows: anything past them (other blocks' rows, the end of the allocation) reads 0
-    int64_t fa = (int64_t)rows * p.lda, fb = (int64_t)rows * p.ldb - n0;
-    const int64_t ea = p.a_floats - k0 * p.lda, eb = p.b_floats - k0 * p.ldb - n0;
-    if (ea < fa) fa = ea;
-    if (eb < fb) fb = eb;
-    const __amdgpu_buffer_rsrc_t ra = wg_rsrc(p.a + k0 * p.lda, fa);
-    const float* const pb = p.b + (p.b_cell ? *p.b_cell * p.ldb : 0);
-    const __amdgpu_buffer_rsrc_t rb = wg_rsrc(pb + k0 * p.ldb + n0, fb);
-    // TWO: a lane's NT columns lie in b (virtual column < n) or in b2 (n is a multiple of NT: never astride); it loads
-    // from both views every step with the offset of the other one out of range (-> zeros) and keeps its own
-    int64_t fb2 = 0;
-    if (TWO) {
-        fb2 = (int64_t)rows * p.ldb2;
-        const int64_t eb2 = p.b2_floats - k0 * p.ldb2;
-        if (eb2 < fb2) fb2 = eb2;
-    }
-    const __amdgpu_buffer_rsrc_t rb2 = wg_rsrc(TWO ? p.b2 + k0 * p.ldb2 : p.b, TWO ? fb2 : 0);
+#include "wgrad_block.h"
+}
 
-    v16f acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+// ---- flexnet_wgrad_batched: up to FLEXNET_WGRAD_MAX_BATCH problems of one shape class (MT, NT) per launch; the problem is
+// grid dimension z and its parameters are entry z of a table in the kernel arguments (no host-to-device copy) ---------------
+struct WgradB {
+    const float* a;
+    const float* b;
+    float* c;
+    float* ws;
+    float* cs;
+    float* colsum;
+    int64_t k, lda, ldb, a_floats, b_floats;
+    int32_t m, n, rows_per_block, slabs, accumulate, ldc;
+};
+struct WgradBatchK {
+    WgradB p[FLEXNET_WGRAD_MAX_BATCH];
+};
+static_assert(sizeof(WgradBatchK) <= 4096, "the table travels in the kernel arguments");
 
-    // step s of the block: rows 2 s, 2 s + 1; wavefront w takes steps w, w + 4, ...
-    const int col = lane & 31, half = lane >> 5;
-    const int steps = (rows + 1) >> 1;
-    const int lda4 = (int)p.lda * 4, ldb4 = (int)p.ldb * 4;
-    int offa = (2 * wave + half) * lda4 + col * (MT * 4);
-    int offb = (2 * wave + half) * ldb4 + col * (NT * 4);
-    const int stepa = 2 * WG_WAVES * lda4, stepb = 2 * WG_WAVES * ldb4;
-    // (offsets are advanced as unsigned numbers: an out-of-range lane starts at 2^31 and stays past every view, whose
-    // size is below 2^31 bytes by the dispatcher's check on rows_per_block)
-    unsigned offb2 = 0x80000000u, stepb2 = 0;
-    bool in_b2 = false;
-    if (TWO) {
-        const int vcol = n0 + NT * col - p.n;            // this lane's first column, counted from the start of b2
-        in_b2 = vcol >= 0;
-        stepb2 = 2 * WG_WAVES * (unsigned)p.ldb2 * 4u;
-        if (in_b2) {
-            offb2 = (unsigned)((2 * wave + half) * (int)p.ldb2 * 4 + vcol * 4);
-            offb = (int)0x80000000u;
-        }
-    }
-    const int mine = steps > wave ? (steps - wave + WG_WAVES - 1) / WG_WAVES : 0;
+__device__ __forceinline__ WgradK wg_problem(const WgradB& e) {
+    WgradK p;
+    p.a = e.a; p.b = e.b; p.c = e.c; p.ws = e.ws; p.cs = e.cs; p.colsum = e.colsum;
+    p.k = e.k; p.lda = e.lda; p.ldb = e.ldb; p.a_floats = e.a_floats; p.b_floats = e.b_floats;
+    p.m = e.m; p.n = e.n; p.rows_per_block = e.rows_per_block; p.slabs = e.slabs; p.accumulate = e.accumulate; p.ldc = e.ldc;
+    p.b2 = nullptr; p.c2 = nullptr; p.ldb2 = 0; p.b2_floats = 0; p.n2 = 0; p.ldc2 = 0; p.b_cell = nullptr;
+    return p;
+}
 
-    constexpr int U = WG_UNROLL(MT, NT);
-    constexpr int D = WG_DEPTH(MT, NT);
-    float av[D][U][MT], bv[D][U][NT];
-    float bw[TWO ? D : 1][TWO ? U : 1][NT];
-    float csum[MT];                  // this lane's share of sum_k A[k, MT * col + i] (the bias gradient)
-#pragma unroll
-    for (int i = 0; i < MT; ++i) csum[i] = 0.0f;
-    const bool want_cs = CS && blockIdx.y == 0;
-    if (TWO) {
-#pragma unroll
-        for (int d = 0; d < D; ++d)
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int j = 0; j < NT; ++j) { bv[d][u][j] = 0.0f; bw[d][u][j] = 0.0f; }
-    }
-    auto issue = [&](int buf) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            wg_load<MT>(ra, offa, av[buf][u]);
-            offa += stepa;
-            if constexpr (TWO) {
-                // both views, unconditionally: the view a column chunk does not touch is out of range for every lane and its
-                // loads return zeros without memory traffic.  (Skipping them with `if (has1)` / `if (has2)` put uniform
-                // branches — and the waits behind them — into the prefetch: 51.2 -> 47.2 us at [32 768, 64] x [720 | 20].)
-                wg_load<NT>(rb, offb, bv[buf][u]);
-                wg_load<NT>(rb2, (int)offb2, bw[buf][u]);
-                offb = (int)((unsigned)offb + (unsigned)stepb);
-                offb2 += stepb2;
-            } else {
-                wg_load<NT>(rb, offb, bv[buf][u]);
-                offb += stepb;
-            }
-        }
-    };
-    auto multiply = [&](int buf) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            float bsel[NT];
-#pragma unroll
-            for (int j = 0; j < NT; ++j) bsel[j] = (TWO && in_b2) ? bw[TWO ? buf : 0][TWO ? u : 0][j] : bv[buf][u][j];
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[buf][u][i], bsel[j], acc[i][j], 0, 0, 0);
-                }
-        }
-        if (CS) {                    // (every column chunk adds; only chunk 0 stores)
-#pragma unroll
-            for (int u = 0; u < U; ++u)
-#pragma unroll
-                for (int i = 0; i < MT; ++i) csum[i] += av[buf][u][i];
-        }
-    };
-    // D register buffers in rotation, D - 1 groups of loads in flight behind the one being multiplied.  Rows past the
-    // block's end lie outside the buffer views and load 0 (0 * 0 adds nothing), so the trip count is rounded up to a
-    // whole rotation and the loads issued past the last group are harmless.
-    const int groups = (mine + U - 1) / U;
-    if (groups > 0) {
-#pragma unroll
-        for (int d = 0; d < D - 1; ++d) issue(d);
-        for (int g = 0; g < groups; g += D) {
-#pragma unroll
-            for (int d = 0; d < D; ++d) {
-                // the loads of the group D - 1 ahead go out BEFORE this group's products and stay there: left alone, the
-                // instruction scheduler sinks them to a few MFMAs before their use (to shorten register lifetimes), which
-                // turns the prefetch distance from a whole group (~1500 cycles of MFMA) into ~500 and the loop latency-bound
-                issue((d + D - 1) % D);
-                __builtin_amdgcn_sched_barrier(0);
-                multiply(d);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
-
-    if (want_cs) {                   // lanes l and l + 32 hold the same columns; then the four wavefronts in order
-        __shared__ float cfold[WG_WAVES][32 * MT];
-#pragma unroll
-        for (int i = 0; i < MT; ++i) {
-            const float s = csum[i] + __shfl_xor(csum[i], 32);
-            if (half == 0) cfold[wave][col * MT + i] = s;
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < 32 * MT; e += 64 * WG_WAVES) {
-            float s = cfold[0][e];
-#pragma unroll
-            for (int w = 1; w < WG_WAVES; ++w) s += cfold[w][e];
-            p.cs[(int64_t)blockIdx.x * (32 * MT) + e] = s;
-        }
-    }
-
-    // fold the four wavefronts' register images in LDS, wavefront 0 first
-#pragma unroll
-    for (int w = 0; w < WG_WAVES; ++w) {
-        if (wave == w) {
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int e = ((i * NT + j) * 16 + r) * 64 + lane;
-                        if (w == 0) fold[e] = acc[i][j][r];
-                        else if (w < WG_WAVES - 1) fold[e] += acc[i][j][r];
-                        else acc[i][j][r] += fold[e];
-                    }
-        }
-        __syncthreads();
-    }
-    if (wave != WG_WAVES - 1) return;
-    float* out = p.ws + ((int64_t)blockIdx.y * p.slabs + blockIdx.x) * WG_IMG(MT, NT);
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) out[((i * NT + j) * 16 + r) * 64 + lane] = acc[i][j][r];
+// the grid spans the class's largest problem: the blocks past this problem's own slabs / column chunks leave at once
+template <int MT, int NT>
+__global__ __launch_bounds__(64 * WG_WAVES, 2) void wgrad_batched_kernel(WgradBatchK t) {
+    const WgradK p = wg_problem(t.p[blockIdx.z]);
+    if ((int)blockIdx.x >= p.slabs || (int)blockIdx.y * (32 * NT) >= p.n) return;
+    constexpr bool CS = true, TWO = false;           // (column-sum partials are written for every problem; the second stage asks)
+#include "wgrad_block.h"
 }
 
 // element e of the slabs' register images, summed in a fixed order, stored at its place in C; the thread blocks past
@@ -289,6 +153,40 @@ __global__ __launch_bounds__(64 * WG_RED) void wgrad_reduce_kernel(WgradK p, Cri
     *dst = p.accumulate ? *dst + sum : sum;
 }
 
+// wgrad_reduce_kernel's sums in its order, per problem
+template <int MT, int NT>
+__global__ __launch_bounds__(64 * WG_RED) void wgrad_batched_reduce_kernel(WgradBatchK t) {
+    constexpr int IMG_BLOCKS = WG_IMG(MT, NT) / 64;
+    const WgradB& p = t.p[blockIdx.z];
+    if ((int)blockIdx.y * (32 * NT) >= p.n) return;
+    float sum;
+    if (blockIdx.x >= IMG_BLOCKS) {
+        if (blockIdx.y != 0 || !p.colsum) return;
+        const int m = (blockIdx.x - IMG_BLOCKS) * 64 + (threadIdx.x & 63);
+        if (!flex_reduce_rows(p.cs + m, 32 * MT, p.slabs, m < 32 * MT, sum) || m >= p.m) return;
+        p.colsum[m] = p.accumulate ? p.colsum[m] + sum : sum;
+        return;
+    }
+    const int e = blockIdx.x * 64 + (threadIdx.x & 63);
+    if (!flex_reduce_rows(p.ws + (int64_t)blockIdx.y * p.slabs * WG_IMG(MT, NT) + e, WG_IMG(MT, NT), p.slabs, true, sum)) return;
+    const int l = e & 63, r = (e >> 6) & 15, tt = e >> 10;
+    const int ti = tt / NT, tj = tt - ti * NT;
+    const int i = (r & 3) + 8 * (r >> 2) + 4 * (l >> 5), j = l & 31;
+    const int m = MT * i + ti, n = blockIdx.y * (32 * NT) + NT * j + tj;
+    if (m >= p.m || n >= p.n) return;
+    float* dst = p.c + (int64_t)m * p.ldc + n;
+    *dst = p.accumulate ? *dst + sum : sum;
+}
+
+template <int MT, int NT>
+static int wgrad_batched_launch(const WgradBatchK& t, int count, int slabs, int chunks, bool any_cs, hipStream_t s) {
+    hipLaunchKernelGGL((wgrad_batched_kernel<MT, NT>), dim3(slabs, chunks, count), dim3(64 * WG_WAVES), 0, s, t);
+    const int cs_blocks = any_cs ? (32 * MT + 63) / 64 : 0;
+    hipLaunchKernelGGL((wgrad_batched_reduce_kernel<MT, NT>), dim3(WG_IMG(MT, NT) / 64 + cs_blocks, chunks, count), dim3(64 * WG_RED),
+                       0, s, t);
+    return flex_launch_status();
+}
+
 template <int MT, int NT>
 static int wgrad_launch(WgradK p, int chunks, hipStream_t s, const CriticFinishK* rider) {
     if (p.b2) {
@@ -313,7 +211,8 @@ static int wgrad_launch(WgradK p, int chunks, hipStream_t s, const CriticFinishK
     return flex_launch_status();
 }
 
-static int wgrad_run(const FlexWgradArgs* a, void* stream, const CriticFinishK* rider) {
+// argument checks and the shape class of one problem
+static int wgrad_class(const FlexWgradArgs* a, int* mt_out, int* nt_out, int* chunks_out) {
     if (!a || !a->a || !a->b || !a->c || !a->workspace || a->k < 0 || a->m < 1 || a->n < 1) return FLEXNET_EINVAL;
     if (a->lda < a->m || a->ldb < a->n || (a->ldc != 0 && a->ldc < a->n)) return FLEXNET_EINVAL;
     if (a->m > 192 || a->lda >= (1 << 24) || a->ldb >= (1 << 24)) return FLEXNET_EUNSUPPORTED;
@@ -323,7 +222,13 @@ static int wgrad_run(const FlexWgradArgs* a, void* stream, const CriticFinishK* 
     const int nt = a->n <= 32 ? 1 : a->n <= 64 ? 2 : (mt == 6 ? 2 : 5);
     if (two && (mt != 2 || nt != 5 || a->n % nt != 0 || a->ldb2 >= (1 << 24))) return FLEXNET_EUNSUPPORTED;
     const int n_all = a->n + (two ? a->n2 : 0);
-    const int chunks = (n_all + 32 * nt - 1) / (32 * nt);
+    *mt_out = mt; *nt_out = nt; *chunks_out = (n_all + 32 * nt - 1) / (32 * nt);
+    return FLEXNET_OK;
+}
+
+// the kernels' view of one problem; `launch_chunks`: the column chunks of everything that shares the launch
+static int wgrad_prepare(const FlexWgradArgs* a, int mt, int nt, int chunks, int launch_chunks, WgradK* out) {
+    const bool two = a->b2 != nullptr || a->n2 != 0;
     const int64_t img = (int64_t)mt * nt * 1024;
     // thread blocks: about two per CU over all column chunks, at least 64 rows each, within the workspace
     const int64_t ws_floats = a->workspace_floats - WG_CS_FLOATS;
@@ -331,7 +236,7 @@ static int wgrad_run(const FlexWgradArgs* a, void* stream, const CriticFinishK* 
     int64_t slabs = (a->k + 63) / 64;
     // never more than two blocks per CU in total: with 515 blocks the last three ran as a second round (62 -> 3x us at
     // [32 768, 64] x [32 768, 720])
-    const int64_t want = 512 / chunks > 0 ? 512 / chunks : 1;
+    const int64_t want = 512 / launch_chunks > 0 ? 512 / launch_chunks : 1;
     if (slabs > want) slabs = want;
     if (slabs * chunks * img > ws_floats) slabs = ws_floats / (chunks * img);
     if (slabs > 520) slabs = 520;
@@ -355,6 +260,17 @@ static int wgrad_run(const FlexWgradArgs* a, void* stream, const CriticFinishK* 
     p.b2_floats = two && a->k > 0 ? (a->k - 1) * a->ldb2 + a->n2 : 0;
     p.n2 = two ? a->n2 : 0; p.ldc2 = two ? (a->ldc2 > 0 ? a->ldc2 : a->n2) : 0;
     p.b_cell = a->b_row_cell;
+    *out = p;
+    return FLEXNET_OK;
+}
+
+static int wgrad_run(const FlexWgradArgs* a, void* stream, const CriticFinishK* rider) {
+    int mt, nt, chunks;
+    int rc = wgrad_class(a, &mt, &nt, &chunks);
+    if (rc != FLEXNET_OK) return rc;
+    WgradK p;
+    rc = wgrad_prepare(a, mt, nt, chunks, chunks, &p);
+    if (rc != FLEXNET_OK) return rc;
     hipStream_t s = (hipStream_t)stream;
     switch (mt * 10 + nt) {
         case 11: return wgrad_launch<1, 1>(p, chunks, s, rider);
@@ -367,6 +283,69 @@ static int wgrad_run(const FlexWgradArgs* a, void* stream, const CriticFinishK* 
         case 62: return wgrad_launch<6, 2>(p, chunks, s, rider);
     }
     return FLEXNET_EUNSUPPORTED;
+}
+
+// `count` independent problems (include/flexnet.h): every check of every problem first, then one first-stage and one
+// second-stage launch per shape class present, classes in the order of wgrad_run's switch, problems in the caller's order.
+extern "C" int flexnet_wgrad_batched(const FlexWgradArgs* problems, int32_t count, void* stream) {
+    if (!problems || count < 1 || count > FLEXNET_WGRAD_MAX_BATCH) return FLEXNET_EINVAL;
+    int cls[FLEXNET_WGRAD_MAX_BATCH], chunks[FLEXNET_WGRAD_MAX_BATCH];
+    for (int i = 0; i < count; ++i) {
+        const FlexWgradArgs* a = problems + i;
+        int mt, nt;
+        const int rc = wgrad_class(a, &mt, &nt, &chunks[i]);
+        if (rc != FLEXNET_OK) return rc;
+        if (a->b2 || a->n2 != 0 || a->b_row_cell) return FLEXNET_EUNSUPPORTED;
+        if (a->workspace_floats < 0) return FLEXNET_EINVAL;
+        cls[i] = mt * 10 + nt;
+    }
+    for (int i = 0; i < count; ++i)                               // every problem its own workspace slice
+        for (int j = 0; j < i; ++j) {
+            const float *bi = problems[i].workspace, *ei = bi + problems[i].workspace_floats;
+            const float *bj = problems[j].workspace, *ej = bj + problems[j].workspace_floats;
+            if (bi < ej && bj < ei) return FLEXNET_EINVAL;
+        }
+    static const int classes[8] = {11, 12, 15, 21, 22, 25, 61, 62};
+    WgradBatchK tables[8];
+    int members[8], grid_x[8], grid_y[8];
+    bool any_cs[8];
+    for (int c = 0; c < 8; ++c) {
+        int total = 0;
+        members[c] = 0; grid_x[c] = 0; grid_y[c] = 0; any_cs[c] = false;
+        for (int i = 0; i < count; ++i) if (cls[i] == classes[c]) total += chunks[i];
+        for (int i = 0; i < count; ++i) {
+            if (cls[i] != classes[c]) continue;
+            WgradK p;
+            const int rc = wgrad_prepare(problems + i, classes[c] / 10, classes[c] % 10, chunks[i], total, &p);
+            if (rc != FLEXNET_OK) return rc;
+            WgradB& e = tables[c].p[members[c]++];
+            e.a = p.a; e.b = p.b; e.c = p.c; e.ws = p.ws; e.colsum = p.colsum;
+            e.cs = problems[i].workspace;                     // (the partials are written either way: one instantiation per class)
+            e.k = p.k; e.lda = p.lda; e.ldb = p.ldb; e.a_floats = p.a_floats; e.b_floats = p.b_floats;
+            e.m = p.m; e.n = p.n; e.rows_per_block = p.rows_per_block; e.slabs = p.slabs; e.accumulate = p.accumulate; e.ldc = p.ldc;
+            if (p.slabs > grid_x[c]) grid_x[c] = p.slabs;
+            if (chunks[i] > grid_y[c]) grid_y[c] = chunks[i];
+            any_cs[c] = any_cs[c] || p.cs != nullptr;
+        }
+        for (int i = members[c]; i < FLEXNET_WGRAD_MAX_BATCH; ++i) tables[c].p[i] = WgradB{};
+    }
+    hipStream_t s = (hipStream_t)stream;
+    for (int c = 0; c < 8; ++c) {
+        if (!members[c]) continue;
+        int rc = FLEXNET_EUNSUPPORTED;
+        switch (classes[c]) {
+            case 11: rc = wgrad_batched_launch<1, 1>(tables[c], members[c], grid_x[c], grid_y[c], any_cs[c], s); break;
+            case 12: rc = wgrad_batched_launch<1, 2>(tables[c], members[c], grid_x[c], grid_y[c], any_cs[c], s); break;
+            case 15: rc = wgrad_batched_launch<1, 5>(tables[c], members[c], grid_x[c], grid_y[c], any_cs[c], s); break;
+            case 21: rc = wgrad_batched_launch<2, 1>(tables[c], members[c], grid_x[c], grid_y[c], any_cs[c], s); break;
+            case 22: rc = wgrad_batched_launch<2, 2>(tables[c], members[c], grid_x[c], grid_y[c], any_cs[c], s); break;
+            case 25: rc = wgrad_batched_launch<2, 5>(tables[c], members[c], grid_x[c], grid_y[c], any_cs[c], s); break;
+            case 61: rc = wgrad_batched_launch<6, 1>(tables[c], members[c], grid_x[c], grid_y[c], any_cs[c], s); break;
+            case 62: rc = wgrad_batched_launch<6, 2>(tables[c], members[c], grid_x[c], grid_y[c], any_cs[c], s); break;
+        }
+        if (rc != FLEXNET_OK) return rc;
+    }
+    return FLEXNET_OK;
 }
 
 extern "C" int flexnet_wgrad(const FlexWgradArgs* a, void* stream) { return wgrad_run(a, stream, nullptr); }

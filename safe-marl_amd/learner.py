@@ -24,7 +24,8 @@ import torch.nn as nn
 from .nets import (WGRAD_MIN_ROWS, CriticTail, critic_first_layer, critic_td_loss, critic_td_loss_supported, critic_policy_loss,
                    critic_policy_loss_supported, expand_agents, MLPAgent, MLPAgentGaussian, MLPCritic, RNNAgent, RNNAgentGaussian, critic_policy_supported, critic_replayed_supported,
                    critic_tail_supported, fused_actor_forward, fused_actor_forward_unshared, actor_unshared_supported,
-                   actor_unshared_train, tall_linear, td_loss, td_loss_supported, wide_batch_linear,
+                   actor_unshared_train, critic_unshared_supported, critic_unshared_train, fused_critic_forward_unshared,
+                   tall_linear, td_loss, td_loss_supported, wide_batch_linear,
                    batchnorm_stats_supported, batchnorm_update_running_stats, sync_batchnorm, QMixer,
                    sqddpg_draw, sqddpg_fused_config, sqddpg_shapley_fused, ppo_gae, ppo_policy_loss, ppo_value_loss,
                    coma_baseline, coma_baseline_torch, coma_fused_config, coma_policy_loss, coma_rows)
@@ -647,6 +648,32 @@ class Model(nn.Module):
             rows = th.cat((rows, ids), dim=-1)
         return rows
 
+    # algorithms whose per-agent critics (shared_params False) csrc/critic_unshared.hip covers: their `value` is one MLPCritic
+    # per agent on rows made of an observation block, the id columns and an optional action block
+    unshared_critic_kernel = False
+
+    def unshared_values(self, obs, act, shared, critic_frozen=False):
+        """The per-agent critics of ``shared_params: False`` on the blocks obs [b, n, o] / act [b, n, a] or None in one launch
+        per direction (nets.fused_critic_forward_unshared without a graph at any size, the node nets._CriticUnsharedFn with
+        one from WGRAD_MIN_ROWS rows): [b, n, 1], or None where the per-agent loop runs — the CPU, ``fused_inference`` off,
+        small batches with a graph (silently) and configurations the kernel declines (after a ``critic_unshared`` note)."""
+        if not (self.unshared_critic_kernel and not self.args.shared_params and obs.is_cuda and self.fused_inference):
+            return None
+        b, n = obs.size(0), self.n_
+        critics = list(self.value_dicts)
+        with_grad = th.is_grad_enabled() and ((act is not None and act.requires_grad) or obs.requires_grad
+                                              or any(p.requires_grad for c in critics for p in c.parameters()))
+        if not with_grad:
+            q = fused_critic_forward_unshared(critics, obs, None if act is None else act.detach(), shared)
+        elif b * n < WGRAD_MIN_ROWS:
+            return None
+        elif critic_unshared_supported(critics, obs, act, shared, train=True):
+            q = critic_unshared_train(critics, obs, act, shared, param_grads=not critic_frozen)
+        else:
+            self.note_unfused("critic_unshared")
+            return None
+        return None if q is None else q.view(b, n, 1)
+
     def row_values(self, rows, tall):
         """The critic on materialised rows [b, n, w] -> [b, n, 1]: the shared one on all of them, else agent i's on row i.
         ``tall``: update batches on the GPU take the shared critic's first layer with the batch-reduced weight gradient of
@@ -1055,6 +1082,7 @@ class MADDPG(Model):
     # refreshes only these columns of its static batch
     # (reward in both: unpack_data's batch-norm running statistics move on every get_loss call, model.py:308-323)
     graph_safe_updates = _GraphSafe(True)       # trainer._graphed_sub_update: the gradient path uses no multi-block PyTorch reduction
+    unshared_critic_kernel = True
     update_fields = {"policy": ("state", "reward", "last_hid"),
                      "value": ("state", "action", "reward", "next_state", "done", "hid"),
                      # trainer.replay_event with the bootstrap values filed per transition first (round 3)
@@ -1072,6 +1100,9 @@ class MADDPG(Model):
         if (critic_frozen and self.args.shared_params and self.args.agent_id and act.requires_grad and th.is_grad_enabled()
                 and critic_policy_supported(self.value_dicts[0], obs.reshape(b, n * o), act, n)):
             return CriticTail.apply_policy(obs.reshape(b, n * o), act, self.value_dicts[0]).view(b, n, 1)
+        v = self.unshared_values(obs, act, True, critic_frozen)            # non-shared critics: csrc/critic_unshared.hip
+        if v is not None:
+            return v
         act_det = act.detach()
         own = act - act_det if act.requires_grad else None                # zeros that carry d/d act_i
         values = []
@@ -1407,6 +1438,7 @@ class MATD3(MADDPG):
     value loss averaged over the twins (matd3.py:148).  Bug-compatible with the reference's action selection, which
     sums the policy means over the AGENT axis before sampling (matd3.py:92-97)."""
     bootstrap_cacheable = False      # own get_loss (min of twins, target-smoothing noise drawn inside): values are per sub-update
+    unshared_critic_kernel = False
 
     # since round 2 the GPU path of both losses reduces only through this project's fixed-order kernels (twin critic
     # nodes, flexnet_td_loss, flexnet_scaled_sum, pointwise agent sums): sub-updates replay as HIP graphs like MADDPG's
@@ -1534,6 +1566,9 @@ class IDDPG(MADDPG):
 
     def value(self, obs, act, critic_frozen=False):
         """iddpg.py:32-59: rows [o_i | onehot(i) | a_i] -> [b, n, 1]."""
+        v = self.unshared_values(obs, act, False, critic_frozen)
+        if v is not None:
+            return v
         return self.row_values(th.cat((self.with_ids(obs), act), dim=-1), True)
 
     def get_actions(self, state, status, exploration, actions_avail, target=False, last_hid=None, need_log_prob=True):
@@ -1608,6 +1643,7 @@ class FACMADDPG(IDDPG):
     (trainer.mixer_replay_process, args.mixer)."""
 
     graph_safe_updates = False       # sub-updates run eagerly (the mixer's losses are not audited for graph capture)
+    unshared_critic_kernel = False   # (unshared critics keep the per-agent loop)
     bootstrap_cacheable = False      # own get_loss: the bootstrap target is Q_tot', not per-agent values
 
     def construct_value_net(self):
@@ -1657,6 +1693,7 @@ class SQDDPG(MADDPG):
     (``marginal_contribution_torch``)."""
 
     graph_safe_updates = False       # sub-updates run eagerly (fresh coalitions per call; not audited for graph capture)
+    unshared_critic_kernel = False   # (unshared critics keep the per-agent loop)
     bootstrap_cacheable = False      # own get_loss: the target term draws its own coalitions in every value sub-update
     get_actions = IDDPG.get_actions  # the same function object (RolloutGraph.summed checks identity)
     coalition_source = None          # tests: callable(role, groups) -> pos [groups, n], role "policy" / "value" / "target"
@@ -1782,6 +1819,7 @@ class IPPO(Model):
 
     on_policy = True
     graph_safe_updates = False       # sub-updates run eagerly
+    unshared_critic_kernel = True
     gae_chain_stride = 1
     fused_ppo = True                 # (tests switch it off to compare with the tensor composition)
     get_actions = IDDPG.get_actions  # ippo.py:61-79 (continuous branch): the same function object
@@ -1802,6 +1840,9 @@ class IPPO(Model):
 
     def value(self, obs, act=None):
         """ippo.py:34-59: rows [o_i | onehot(i)] -> [b, n, 1]; ``act`` is ignored."""
+        v = self.unshared_values(obs, None, False)
+        if v is not None:
+            return v
         return self.row_values(self.with_ids(obs), self.fused_inference)
 
     def _unfiled_columns(self, n_envs):
@@ -1910,6 +1951,9 @@ class MAPPO(IPPO):
                     h = h + W[:, n * o:n * o + n].t().unsqueeze(0)
                 v, _ = net.forward_from_hidden(h.reshape(b * n, -1), need_hidden=False)
                 return v.view(b, n, 1)
+        v = self.unshared_values(obs, None, True)       # per-agent critics: the shared observation block, not n copies of it
+        if v is not None:
+            return v
         return self.row_values(self.with_ids(obs_cols.unsqueeze(1).expand(b, n, n * o)), False)
 
 

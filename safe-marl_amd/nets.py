@@ -511,6 +511,63 @@ def tall_wgrad(dy, x, out=None, accumulate=False, colsum=None, x2=None, out2=Non
     return out
 
 
+_WGRAD_BATCH_WS = {}
+
+
+def _wgrad_class(m, n):
+    """csrc/wgrad.hip's shape class of an [m, n] result: (MT, NT, column chunks, floats per register image)."""
+    mt = 1 if m <= 32 else 2 if m <= 64 else 6
+    nt = 1 if n <= 32 else 2 if n <= 64 else (2 if mt == 6 else 5)
+    return mt, nt, (n + 32 * nt - 1) // (32 * nt), mt * nt * 1024
+
+
+def tall_wgrad_batched(problems):
+    """Independent weight gradients out_i = dy_i^T x_i in ONE flexnet_wgrad_batched call (csrc/wgrad.hip: one first-stage and
+    one second-stage launch per shape class instead of two launches per problem).  ``problems``: (dy, x, out, colsum or None)
+    with ``tall_wgrad_supported(dy, x)`` and ``out`` an fp32 [m, n] tensor or a column block of a wider one — agent i's rows
+    ``t.view(b, n, w)[:, i]`` of an interleaved tensor are an ordinary problem.  Every problem gets its own slice of a per-device
+    workspace, sized for the thread blocks the library will choose for it (a shorter slice would only lower that number).  More
+    problems than FLEXNET_WGRAD_MAX_BATCH go in several calls.  Bit-reproducible."""
+    for c0 in range(0, len(problems), _lib.FLEXNET_WGRAD_MAX_BATCH):
+        _wgrad_batched_call(problems[c0:c0 + _lib.FLEXNET_WGRAD_MAX_BATCH])
+
+
+def _wgrad_batched_call(problems):
+    dev = problems[0][0].device
+    classes = [_wgrad_class(dy.shape[1], x.shape[1]) for dy, x, _, _ in problems]
+    launch_chunks = {}
+    for mt, nt, chunks, _ in classes:
+        launch_chunks[(mt, nt)] = launch_chunks.get((mt, nt), 0) + chunks
+    need = []
+    for (dy, _, _, _), (mt, nt, chunks, img) in zip(problems, classes):
+        slabs = max(1, min((dy.shape[0] + 63) // 64, max(1, 512 // launch_chunks[(mt, nt)]), 520))
+        need.append(_lib.FLEXNET_WGRAD_CS_FLOATS + slabs * chunks * img)
+    total = sum(need)
+    ws = _WGRAD_BATCH_WS.get(dev)
+    if ws is None or ws.numel() < total:
+        ws = _WGRAD_BATCH_WS[dev] = th.empty(total, dtype=th.float32, device=dev)
+    table = (_lib.FlexWgradArgs * len(problems))()
+    at, keep = 0, []
+    for a, (dy, x, out, colsum), floats in zip(table, problems, need):
+        k, m = dy.shape
+        n = x.shape[1]
+        if k <= 1:                        # (a single row's pitch is arbitrary: dense copies, as tall_wgrad)
+            dy, x = dy.contiguous(), x.contiguous()
+            keep += [dy, x]
+        if (not tall_wgrad_supported(dy, x) or out.shape != (m, n) or out.dtype != th.float32
+                or (m > 1 and (out.stride(1) != 1 or out.stride(0) < n))):
+            raise ValueError("tall_wgrad_batched: fp32 [k, m <= 192] x [k, n] problems into [m, n] blocks")
+        a.k, a.m, a.n = k, m, n
+        a.lda, a.ldb = (dy.stride(0), x.stride(0)) if k > 1 else (m, n)
+        a.a, a.b, a.c = dy.data_ptr(), x.data_ptr(), out.data_ptr()
+        a.ldc = out.stride(0) if m > 1 else n
+        if colsum is not None:
+            a.colsum = colsum.data_ptr()
+        a.workspace, a.workspace_floats = ws.data_ptr() + 4 * at, floats
+        at += floats
+    _lib.launch("flexnet_wgrad_batched", table, len(problems))
+
+
 class _TallLinear(th.autograd.Function):
     """y = x @ W.T (+ b) for a tall x: the library GEMM forward and for dx, csrc/wgrad.hip for dW."""
 
@@ -1108,7 +1165,8 @@ def fused_actor_forward_unshared(agents, obs, hidden):
 class _ActorUnsharedTrainFn(th.autograd.Function):
     """The per-agent actors of ``shared_params: False`` for an update batch as ONE autograd node (csrc/actor_unshared.hip): the
     fused forward with its saves, one backward launch for the gate gradients, dx and the first layer's epilogue of every agent,
-    then csrc/wgrad.hip per agent through row pitches (rows a, a + n, ... of the [rows, .] tensors are agent a's).  The id block
+    then csrc/wgrad.hip per agent through row pitches (rows a, a + n, ... of the [rows, .] tensors are agent a's), the 4 n
+    products as one flexnet_wgrad_batched call.  The id block
     of agent a's fc1 gradient is zero except its own column a, which is its bias gradient (the one-hot input).  Observations
     and the previous hidden state take no gradient; the new hidden state is non-differentiable.  Bit-reproducible."""
 
@@ -1157,8 +1215,8 @@ class _ActorUnsharedTrainFn(th.autograd.Function):
         g.d_ln_w, g.d_ln_b, g.d_fc1_b = small[0].data_ptr(), small[1].data_ptr(), small[2].data_ptr()
         g.workspace, g.workspace_floats = ws.data_ptr(), ws.numel()
         _lib.launch("flexnet_actor_unshared_backward", g)
-        # the weight gradients: four csrc/wgrad.hip products per agent, each over the agent's rows through the row pitch; the
-        # GRU's and fc2's bias gradients are the column sums of the same passes
+        # the weight gradients: four csrc/wgrad.hip products per agent, each over the agent's rows through the row pitch, all in
+        # ONE flexnet_wgrad_batched call; the GRU's and fc2's bias gradients are the column sums of the same passes
         ld = params[0][0].shape[1]
         d_fc1_w = th.zeros(n, 64, ld, dtype=th.float32, device=dev) if ctx.agent_id else th.empty(n, 64, ld, dtype=th.float32, device=dev)
         d_w_ih, d_w_hh = th.empty(2, n, 192, 64, dtype=th.float32, device=dev).unbind(0)
@@ -1167,11 +1225,11 @@ class _ActorUnsharedTrainFn(th.autograd.Function):
         d_fc2_b = th.empty(n, act_dim, dtype=th.float32, device=dev)
         obs3, hid3, hout3, x3 = obs.view(b, n, o), hidden.view(b, n, 64), hid_out.view(b, n, 64), saved[1].view(b, n, 64)
         dm3, dgi3, dgh3, dz3 = d_means.view(b, n, act_dim), d_gi.view(b, n, 192), d_gh.view(b, n, 192), dz.view(b, n, 64)
+        problems = []
         for i in range(n):
-            tall_wgrad(dm3[:, i], hout3[:, i], out=d_fc2_w[i], colsum=d_fc2_b[i])
-            tall_wgrad(dgi3[:, i], x3[:, i], out=d_w_ih[i], colsum=d_b_ih[i])
-            tall_wgrad(dgh3[:, i], hid3[:, i], out=d_w_hh[i], colsum=d_b_hh[i])
-            tall_wgrad(dz3[:, i], obs3[:, i], out=d_fc1_w[i, :, :o])
+            problems += [(dm3[:, i], hout3[:, i], d_fc2_w[i], d_fc2_b[i]), (dgi3[:, i], x3[:, i], d_w_ih[i], d_b_ih[i]),
+                         (dgh3[:, i], hid3[:, i], d_w_hh[i], d_b_hh[i]), (dz3[:, i], obs3[:, i], d_fc1_w[i, :, :o], None)]
+        tall_wgrad_batched(problems)
         if ctx.agent_id:
             th.diagonal(d_fc1_w[:, :, o:], dim1=0, dim2=2).copy_(small[2].t())     # [64, n]: agent i's own id column
         grads = []
@@ -1188,6 +1246,222 @@ def actor_unshared_train(agents, obs, hidden):
     agent_id = agents[0].fc1.weight.shape[1] != o
     flat = [p for g in agents for p in _unshared_params(g)]
     return _ActorUnsharedTrainFn.apply(obs.reshape(-1, o), hidden.reshape(-1, 64), n, agent_id, _unshared_ln_eps(agents), *flat)
+
+
+# ---- the per-agent critics of shared_params: False (csrc/critic_unshared.hip) ------------------------------------------------
+_CRITIC_UNSHARED_WS = {}
+_CRITIC_UNSHARED_TABLES = ("fc1_w", "fc1_b", "ln_w", "ln_b", "fc2_w", "fc2_b", "fc3_w", "fc3_b")
+
+
+def _critic_unshared_params(critic):
+    """The eight parameters of one MLPCritic in ``_CRITIC_UNSHARED_TABLES`` order (the LayerNorm pair None without layernorm)."""
+    ln = critic.layernorm if critic.args.layernorm else None
+    return (critic.fc1.weight, critic.fc1.bias, None if ln is None else ln.weight, None if ln is None else ln.bias,
+            critic.fc2.weight, critic.fc2.bias, critic.fc3.weight, critic.fc3.bias)
+
+
+def _critic_unshared_widths(x1, x2, shared):
+    """(w1, w2) of the first layer's blocks: x1 [b, n, o] / x2 [b, n, a] (or None) as ONE block per sample (``shared``: every
+    agent's critic reads [b, n o] — maddpg.py:33-54, mappo.py:34-62) or as agent i's own row (ippo.py:34-59, iddpg.py:32-59)."""
+    n = x1.shape[1]
+    w1 = x1.shape[2] * (n if shared else 1)
+    w2 = 0 if x2 is None else x2.shape[2] * (n if shared else 1)
+    return w1, w2
+
+
+def _critic_unshared_declines(critics, x1, x2, shared):
+    """Why csrc/critic_unshared.hip does not cover these per-agent critics on the blocks x1 [b, n, o], x2 [b, n, a] / None."""
+    n = len(critics)
+    for name, t in (("x1", x1), ("x2", x2)):
+        if t is not None and not (t.is_cuda and t.dtype == th.float32 and t.dim() == 3 and t.shape[1] == n
+                                  and t.shape[0] == x1.shape[0]):
+            return f"{name} {tuple(t.shape)} {t.dtype} for {n} agents"
+    w1, w2 = _critic_unshared_widths(x1, x2, shared)
+    if not (1 <= n <= _lib.FLEXNET_MAX_AGENTS and 1 <= w1 <= _lib.FLEXNET_MAX_AGENTS * _lib.FLEXNET_MAX_OBS
+            and w2 <= _lib.FLEXNET_MAX_AGENTS * _lib.FLEXNET_MAX_ACT and (x2 is None or 1 <= x2.shape[2] <= _lib.FLEXNET_MAX_ACT)):
+        return f"agents {n}, first block {w1}, second block {w2}"
+    if x1.shape[0] * n >= ACTOR_UNSHARED_MAX_ROWS:
+        return f"{x1.shape[0] * n} rows"
+    for i, c in enumerate(critics):
+        if type(c) is not MLPCritic:
+            return f"critic {i} is a {type(c).__name__}"
+        a = c.args
+        if not (a.hid_size == 64 and a.hid_activation == "relu" and c.fc3.out_features == 1):
+            return f"critic {i}: hid {a.hid_size}, act {a.hid_activation}, out {c.fc3.out_features}"
+        if c.fc1.weight.shape[1] not in (w1 + w2, w1 + n + w2):
+            return f"critic {i}: fc1 takes {c.fc1.weight.shape[1]} columns, blocks {w1} + {w2}, {n} agents"
+        if c.fc1.weight.shape[1] != critics[0].fc1.weight.shape[1] or bool(a.layernorm) != bool(critics[0].args.layernorm):
+            return f"critic {i} differs from critic 0 in its input width or LayerNorm"
+        if not getattr(c, "fused_tail", True):
+            return f"critic {i}: fused passes switched off"
+        for p in _critic_unshared_params(c):
+            if p is not None and not (p.is_cuda and p.dtype == th.float32 and p.is_contiguous()):
+                return f"critic {i}: a parameter is not a contiguous fp32 device tensor"
+    return None
+
+
+def critic_unshared_supported(critics, x1, x2=None, shared=False, train=False):
+    """What csrc/critic_unshared.hip covers: every module ``type(...) is MLPCritic`` with 64 hidden units, ReLU and one output,
+    fp32 contiguous device tensors, at most FLEXNET_MAX_AGENTS agents, blocks of at most FLEXNET_MAX_AGENTS * FLEXNET_MAX_OBS
+    and FLEXNET_MAX_AGENTS * FLEXNET_MAX_ACT columns; ``train``: also the row threshold of the hand-written weight gradients."""
+    critics = list(critics)
+    return (_critic_unshared_declines(critics, x1, x2, shared) is None and not x1.requires_grad
+            and (not train or x1.shape[0] * x1.shape[1] >= WGRAD_MIN_ROWS))
+
+
+def _critic_unshared_args(cls, params, x1, x2, shared, ln_eps):
+    b, n, _ = x1.shape
+    w1, w2 = _critic_unshared_widths(x1, x2, shared)
+    a = cls()
+    a.rows, a.n_agents, a.w1, a.w2 = b * n, n, w1, w2
+    a.agent_id, a.layernorm, a.ln_eps = int(params[0][0].shape[1] != w1 + w2), int(params[0][2] is not None), float(ln_eps)
+    names = {f[0] for f in cls._fields_}
+    for k, name in enumerate(_CRITIC_UNSHARED_TABLES):
+        if name in names:
+            table = getattr(a, name)
+            for i in range(n):
+                p = params[i][k]
+                table[i] = None if p is None else p.data_ptr()
+    return a
+
+
+def _critic_unshared_launch_forward(params, x1, x2, shared, ln_eps, saved=None):
+    """One flexnet_critic_unshared_forward launch on contiguous x1 [b, n, o] / x2 [b, n, a] or None; q [b, n], or None when the
+    library answers FLEXNET_EUNSUPPORTED."""
+    b, n, o = x1.shape
+    q = th.empty(b, n, dtype=th.float32, device=x1.device)
+    a = _critic_unshared_args(_lib.FlexCriticUnsharedArgs, params, x1, x2, shared, ln_eps)
+    a.x1, a.x1_pitch, a.x1_agent_off = x1.data_ptr(), n * o, 0 if shared else o
+    if x2 is not None:
+        a.x2, a.x2_pitch, a.x2_agent_off = x2.data_ptr(), n * x2.shape[2], 0 if shared else x2.shape[2]
+    a.q = q.data_ptr()
+    if saved is not None:
+        a.save_z1, a.save_x = saved[0].data_ptr(), saved[1].data_ptr()
+    if not _lib.try_launch("flexnet_critic_unshared_forward", a):
+        return None
+    return q
+
+
+def _critic_unshared_ln_eps(critics):
+    return float(critics[0].layernorm.eps) if critics[0].args.layernorm else 1e-5
+
+
+def fused_critic_forward_unshared(critics, x1, x2=None, shared=False):
+    """model.py:124-138 (one MLPCritic per agent) without an autograd graph, in ONE HIP launch (csrc/critic_unshared.hip) at
+    any batch size, instead of the loop's clone / eye / cat and ten kernels per agent.  ``x1`` [b, n, o] (observations) and
+    ``x2`` [b, n, a] (actions) or None are the blocks of the first layer's input, never concatenated: ``shared`` — every agent's
+    critic reads all of them ([o_1 .. o_n | onehot(i) | a_1 .. a_n]), else agent i's reads its own ([o_i | onehot(i) | a_i]).
+    Returns q [b, n], or None after ``note_fallback("critic_unshared", ...)`` when it declines on GPU tensors."""
+    critics = list(critics)
+    why = _critic_unshared_declines(critics, x1, x2, shared)
+    if why is not None:
+        if x1.is_cuda:
+            note_fallback("critic_unshared", why)
+        return None
+    with th.no_grad():
+        q = _critic_unshared_launch_forward([_critic_unshared_params(c) for c in critics], x1.contiguous(),
+                                            None if x2 is None else x2.contiguous(), shared, _critic_unshared_ln_eps(critics))
+    if q is None:
+        note_fallback("critic_unshared", "FLEXNET_EUNSUPPORTED from flexnet_critic_unshared_forward")
+    return q
+
+
+class _CriticUnsharedFn(th.autograd.Function):
+    """The per-agent critics of ``shared_params: False`` for an update batch as ONE autograd node (csrc/critic_unshared.hip): the
+    fused forward with its two saves (fc1's output and the first activation; fc2's output is recomputed), one backward launch
+    for dz1, dz2, the per-agent vector sums and the own-action gradient, then ONE flexnet_wgrad_batched call for every agent's
+    d_fc1_w (its x1 block and its x2 block as two problems into column slices) and d_fc2_w.  The id block of agent a's fc1
+    gradient is zero except its own column a, which is its bias gradient (the one-hot input).  ``x1`` takes no gradient; ``x2``
+    takes the gradient of agent i's own action block only — maddpg.py:47-54 detaches the others, iddpg.py has no others.
+    ``param_grads`` False: the critics are frozen (the policy sub-update), no parameter gradient is formed.  Bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, shared, ln_eps, param_grads, *flat):
+        b, n, _ = x1.shape
+        params = [flat[8 * i:8 * i + 8] for i in range(n)]
+        x1 = x1.contiguous()
+        x2 = None if x2 is None else x2.contiguous()
+        saved = th.empty(2, b * n, 64, dtype=th.float32, device=x1.device)           # z1 | x
+        q = _critic_unshared_launch_forward(params, x1, x2, shared, ln_eps, saved)
+        if q is None:
+            _lib.check(_lib.FLEXNET_EUNSUPPORTED, "flexnet_critic_unshared_forward")
+        ctx.shared, ctx.ln_eps, ctx.param_grads = bool(shared), float(ln_eps), bool(param_grads)
+        ctx.has_ln, ctx.has_x2 = params[0][2] is not None, x2 is not None
+        ctx.save_for_backward(x1, saved, *([x2] if x2 is not None else []), *[p for p in flat if p is not None])
+        ctx.set_materialize_grads(False)
+        return q
+
+    @staticmethod
+    def backward(ctx, dq):
+        x1, saved = ctx.saved_tensors[:2]
+        rest = ctx.saved_tensors[2:]
+        x2 = None
+        if ctx.has_x2:
+            x2, rest = rest[0], rest[1:]
+        b, n, _ = x1.shape
+        dev, has_ln, shared = x1.device, ctx.has_ln, ctx.shared
+        per = 8 if has_ln else 6
+        params = []
+        for i in range(n):
+            p = list(rest[per * i:per * (i + 1)])
+            params.append(p if has_ln else p[:2] + [None, None] + p[2:])
+        if dq is None:
+            return (None,) * (5 + 8 * n)
+        rows = b * n
+        pg = ctx.param_grads and any(ctx.needs_input_grad[5:])
+        want_x2 = x2 is not None and ctx.needs_input_grad[1]
+        dq = dq.contiguous()
+        dz1 = th.empty(rows, 64, dtype=th.float32, device=dev)
+        g = _critic_unshared_args(_lib.FlexCriticUnsharedBwdArgs, params, x1, x2, shared, ctx.ln_eps)
+        g.param_grads = int(pg)
+        g.dq, g.z1, g.x, g.dz1 = dq.data_ptr(), saved[0].data_ptr(), saved[1].data_ptr(), dz1.data_ptr()
+        d_x2 = None
+        if want_x2:
+            act_dim = x2.shape[2]
+            d_x2 = th.empty(b, n, act_dim, dtype=th.float32, device=dev)
+            g.d_x2_own, g.own_first, g.own_step, g.own_w = d_x2.data_ptr(), 0, act_dim if shared else 0, act_dim
+        if pg:
+            dz2 = th.empty(rows, 64, dtype=th.float32, device=dev)
+            small = th.empty(5, n, 64, dtype=th.float32, device=dev)          # d_ln_w | d_ln_b | d_fc1_b | d_fc2_b | d_fc3_w
+            d_fc3_b = th.empty(n, 1, dtype=th.float32, device=dev)
+            if dev not in _CRITIC_UNSHARED_WS:
+                _CRITIC_UNSHARED_WS[dev] = th.empty(_lib.FLEXNET_CRITIC_UNSHARED_WS_FLOATS, dtype=th.float32, device=dev)
+            ws = _CRITIC_UNSHARED_WS[dev]
+            g.dz2, g.d_fc3_b = dz2.data_ptr(), d_fc3_b.data_ptr()
+            g.d_ln_w, g.d_ln_b, g.d_fc1_b, g.d_fc2_b, g.d_fc3_w = (small[k].data_ptr() for k in range(5))
+            g.workspace, g.workspace_floats = ws.data_ptr(), ws.numel()
+        _lib.launch("flexnet_critic_unshared_backward", g)
+        if not pg:
+            return (None, d_x2, None, None, None) + (None,) * (8 * n)
+        # the weight gradients: per agent d_fc1_w's x1 block, its x2 block and d_fc2_w, each over the agent's rows through the
+        # row pitch — one flexnet_wgrad_batched call
+        w1, w2 = g.w1, g.w2
+        ld = params[0][0].shape[1]
+        n_id = ld - w1 - w2
+        d_fc1_w = (th.zeros if n_id else th.empty)(n, 64, ld, dtype=th.float32, device=dev)
+        d_fc2_w = th.empty(n, 64, 64, dtype=th.float32, device=dev)
+        dz1_3, dz2_3, x_3 = dz1.view(b, n, 64), dz2.view(b, n, 64), saved[1].view(b, n, 64)
+        problems = []
+        for i in range(n):
+            problems.append((dz1_3[:, i], x1.view(b, w1) if shared else x1[:, i], d_fc1_w[i, :, :w1], None))
+            if x2 is not None:
+                problems.append((dz1_3[:, i], x2.view(b, w2) if shared else x2[:, i], d_fc1_w[i, :, w1 + n_id:], None))
+            problems.append((dz2_3[:, i], x_3[:, i], d_fc2_w[i], None))
+        tall_wgrad_batched(problems)
+        if n_id:
+            th.diagonal(d_fc1_w[:, :, w1:w1 + n], dim1=0, dim2=2).copy_(small[2].t())     # [64, n]: agent i's own id column
+        grads = []
+        for i in range(n):
+            grads += [d_fc1_w[i], small[2, i], small[0, i] if has_ln else None, small[1, i] if has_ln else None,
+                      d_fc2_w[i], small[3, i], small[4, i].view(1, 64), d_fc3_b[i]]
+        return (None, d_x2, None, None, None, *grads)
+
+
+def critic_unshared_train(critics, x1, x2=None, shared=False, param_grads=True):
+    """The node on the blocks x1 [b, n, o] / x2 [b, n, a] or None (``critic_unshared_supported(..., train=True)`` holds): q [b, n]."""
+    critics = list(critics)
+    flat = [p for c in critics for p in _critic_unshared_params(c)]
+    return _CriticUnsharedFn.apply(x1, x2, shared, _critic_unshared_ln_eps(critics), param_grads, *flat)
 
 
 def lnrelu_supported(agent, n_agents):
