@@ -67,7 +67,7 @@ def main():
     ap.add_argument("--gaussian-policy", action="store_true",
                     help="learned log-std heads (gaussian_policy: True, LOG_STD_MIN 0.0 / LOG_STD_MAX 0.5 of default.yaml)")
     ap.add_argument("--agent-type", choices=["rnn", "mlp"], default="rnn",
-                    help="agent_type of default.yaml: the recurrent agent, or the MLP agent on the stacked history (csrc/mlp_agent.hip)")
+                    help="agent_type of default.yaml: the recurrent agent, or the MLP agent on the stacked history (csrc/actor_mlp.hip)")
     ap.add_argument("--unshared", action="store_true",
                     help="shared_params: False of default.yaml — one actor and one critic per agent (csrc/actor_unshared.hip)")
     a = ap.parse_args()

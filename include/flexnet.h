@@ -1044,6 +1044,85 @@ typedef struct {
 int flexnet_critic_unshared_forward(const FlexCriticUnsharedArgs* args, void* stream);
 int flexnet_critic_unshared_backward(const FlexCriticUnsharedBwdArgs* args, void* stream);
 
+/* ---- agent_type: mlp under shared_params: True (madrl/agents/mlp_agent.py:20-32, mlp_agent_gaussian.py; csrc/actor_mlp.hip) ----
+ * The MLP actor (fc1 -> LayerNorm -> ReLU -> fc2 -> ReLU = h -> fc3: the MLPCritic's layers with act_dim outputs) in one entry
+ * point per direction, with ONE set of weights.  Row s * n_agents + a of the [rows, .] tensors is agent a of sample s.  One
+ * wavefront owns 32 samples of one agent on v_mfma_f32_32x32x2_f32 (exact fp32): the agent only selects the id column of fc1
+ * and the row of the per-agent sums.  The Gaussian agent's `mean` head goes in the fc3 slot.
+ * FOR EAGER CALLS ONLY: no caller in this project launches either entry point on a stream that is being captured into a HIP
+ * graph ("the capture rule").
+ * forward: obs is [b, n_agents, obs_dim] WITHOUT id columns, read in place with scalar loads (no alignment or width asked of a
+ *         row); under agent_id, fc1_w is [64, obs_dim + n_agents] and agent a adds its column obs_dim + a.  Out: means
+ *         [rows, act_dim] and h [rows, 64] (always: the module's second result), and with both save_* set z1 (fc1's output
+ *         with bias and id column) and x (after LayerNorm and ReLU).  The launch with and without the saves gives the same bits.
+ * backward: from d_means [rows, act_dim], the optional d_h [rows, 64] (the gradient the Gaussian agent's log-std head sends to
+ *         h) and the saves z1, x, h:  dh = d_means @ fc3_w (+ d_h);  dz2 = dh [h > 0];  dx = dz2 @ fc2_w (matrix cores, never
+ *         stored);  LayerNorm / ReLU backward with csrc/lnrelu.hip's arithmetic -> dz1.  Out: dz1, dz2 [rows, 64]; d_ln_w, d_ln_b
+ *         (layernorm), d_fc1_b, d_fc2_b [64], d_fc3_b [act_dim]; d_dz1_agent [n_agents, 64], the sum of dz1 over each agent's
+ *         rows — the id columns of fc1's gradient, transposed.  Every sum in a fixed order through `workspace` and a second
+ *         launch: no atomics, bit-reproducible.  The weight gradients are three flexnet_wgrad_batched problems: d_fc1_w[:, :obs_dim]
+ *         = dz1^T obs, d_fc2_w = dz2^T x, d_fc3_w = d_means^T h.  Observations take no gradient.
+ * hid == FLEXNET_HID, ReLU, fp32, n_agents <= FLEXNET_MAX_AGENTS, obs_dim <= FLEXNET_MAX_OBS, act_dim <= FLEXNET_MAX_ACT, the
+ * [rows, 64] tensors, fc2_w and fc3_w 16-byte aligned; else FLEXNET_EUNSUPPORTED.  Missing tensors, rows % n_agents != 0, one
+ * save without the other, LayerNorm without its pair, a short workspace: FLEXNET_EINVAL.  Both before any HIP call; after the
+ * checks an entry point computes its grid and launches on `stream`, nothing else. */
+#define FLEXNET_ACTOR_MLP_WS_FLOATS (FLEXNET_MAX_AGENTS * 128 * 320)
+typedef struct {
+    int32_t rows;              /* b * n_agents */
+    int32_t n_agents;
+    int32_t obs_dim;
+    int32_t act_dim;
+    int32_t agent_id;
+    int32_t layernorm;
+    float ln_eps;
+    int32_t hid;               /* FLEXNET_HID */
+    const float* obs;          /* [rows, obs_dim] */
+    const float* fc1_w;        /* [64, obs_dim (+ n_agents)] */
+    const float* fc1_b;        /* [64] */
+    const float* ln_w;         /* [64] (layernorm) */
+    const float* ln_b;
+    const float* fc2_w;        /* [64, 64] */
+    const float* fc2_b;        /* [64] */
+    const float* fc3_w;        /* [act_dim, 64] */
+    const float* fc3_b;        /* [act_dim] */
+    float* means;              /* out [rows, act_dim] */
+    float* h;                  /* out [rows, 64] */
+    float* save_z1;            /* out [rows, 64] each, both or none */
+    float* save_x;
+} FlexActorMlpArgs;
+
+typedef struct {
+    int32_t rows;
+    int32_t n_agents;
+    int32_t obs_dim;
+    int32_t act_dim;
+    int32_t agent_id;
+    int32_t layernorm;
+    float ln_eps;
+    int32_t hid;
+    const float* d_means;      /* [rows, act_dim] */
+    const float* d_h;          /* [rows, 64] or NULL */
+    const float* z1;           /* the forward's saves */
+    const float* x;
+    const float* h;            /* the forward's h */
+    const float* ln_w;         /* (layernorm) */
+    const float* fc2_w;
+    const float* fc3_w;
+    float* dz1;                /* out [rows, 64] */
+    float* dz2;                /* out [rows, 64] */
+    float* d_ln_w;             /* out [64] (layernorm) */
+    float* d_ln_b;
+    float* d_fc1_b;            /* out [64] */
+    float* d_fc2_b;            /* out [64] */
+    float* d_fc3_b;            /* out [act_dim] */
+    float* d_dz1_agent;        /* out [n_agents, 64] */
+    float* workspace;
+    int64_t workspace_floats;  /* >= FLEXNET_ACTOR_MLP_WS_FLOATS */
+} FlexActorMlpBwdArgs;
+
+int flexnet_actor_mlp_forward(const FlexActorMlpArgs* args, void* stream);
+int flexnet_actor_mlp_backward(const FlexActorMlpBwdArgs* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

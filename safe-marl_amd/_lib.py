@@ -84,6 +84,7 @@ SYMBOLS = (
     "flexnet_gauss_head_forward", "flexnet_gauss_head_backward", "flexnet_gauss_sum_explore", "flexnet_ppo_policy_loss_rows",
     "flexnet_actor_unshared_forward", "flexnet_actor_unshared_backward",
     "flexnet_critic_unshared_forward", "flexnet_critic_unshared_backward", "flexnet_wgrad_batched",
+    "flexnet_actor_mlp_forward", "flexnet_actor_mlp_backward",
     "flexopf_qp_work_doubles", "flexopf_qp_solve",
 )
 
@@ -192,6 +193,25 @@ class FlexCriticUnsharedBwdArgs(C.Structure):
                                           "d_x2_own")] + \
                [(k, C.c_int32) for k in ("own_first", "own_step", "own_w", "pad1")] + \
                [("workspace", C.c_void_p), ("workspace_floats", C.c_int64)]
+
+
+FLEXNET_ACTOR_MLP_WS_FLOATS = FLEXNET_MAX_AGENTS * 128 * 320
+_ACTOR_MLP_HEAD = [(k, C.c_int32) for k in ("rows", "n_agents", "obs_dim", "act_dim", "agent_id", "layernorm")] + \
+                  [("ln_eps", C.c_float), ("hid", C.c_int32)]
+
+
+class FlexActorMlpArgs(C.Structure):
+    """include/flexnet.h: the MLP actor's forward, one set of weights (csrc/actor_mlp.hip)"""
+    _fields_ = _ACTOR_MLP_HEAD + [(k, C.c_void_p) for k in ("obs", "fc1_w", "fc1_b", "ln_w", "ln_b", "fc2_w", "fc2_b", "fc3_w",
+                                                            "fc3_b", "means", "h", "save_z1", "save_x")]
+
+
+class FlexActorMlpBwdArgs(C.Structure):
+    """include/flexnet.h"""
+    _fields_ = _ACTOR_MLP_HEAD + [(k, C.c_void_p) for k in ("d_means", "d_h", "z1", "x", "h", "ln_w", "fc2_w", "fc3_w", "dz1",
+                                                            "dz2", "d_ln_w", "d_ln_b", "d_fc1_b", "d_fc2_b", "d_fc3_b",
+                                                            "d_dz1_agent", "workspace")] + \
+               [("workspace_floats", C.c_int64)]
 
 
 class FlexCriticTailArgs(C.Structure):
@@ -509,6 +529,9 @@ def load():
     lib.flexnet_critic_unshared_forward.restype = C.c_int
     lib.flexnet_critic_unshared_backward.argtypes = [C.POINTER(FlexCriticUnsharedBwdArgs), vp]
     lib.flexnet_critic_unshared_backward.restype = C.c_int
+    for fn, st in ((lib.flexnet_actor_mlp_forward, FlexActorMlpArgs), (lib.flexnet_actor_mlp_backward, FlexActorMlpBwdArgs)):
+        fn.argtypes = [C.POINTER(st), vp]
+        fn.restype = C.c_int
     lib.flexnet_clip_rmsprop.argtypes = [C.POINTER(FlexClipRmspropArgs), vp]
     lib.flexnet_clip_rmsprop.restype = C.c_int
     lib.flexnet_clip_rmsprop_refresh.argtypes = [C.POINTER(FlexClipRmspropArgs), C.POINTER(FlexWindowRefreshArgs), C.POINTER(FlexTdLossArgs), vp]

@@ -24,6 +24,7 @@ import torch.nn as nn
 from .nets import (WGRAD_MIN_ROWS, CriticTail, critic_first_layer, critic_td_loss, critic_td_loss_supported, critic_policy_loss,
                    critic_policy_loss_supported, expand_agents, MLPAgent, MLPAgentGaussian, MLPCritic, RNNAgent, RNNAgentGaussian, critic_policy_supported, critic_replayed_supported,
                    critic_tail_supported, fused_actor_forward, fused_actor_forward_unshared, actor_unshared_supported,
+                   actor_mlp_declines, actor_mlp_train, fused_actor_forward_mlp, mlp_actor_allowed,
                    actor_unshared_train, critic_unshared_supported, critic_unshared_train, fused_critic_forward_unshared,
                    tall_linear, td_loss, td_loss_supported, wide_batch_linear,
                    batchnorm_stats_supported, batchnorm_update_running_stats, sync_batchnorm, QMixer,
@@ -564,7 +565,29 @@ class Model(nn.Module):
         b = obs.size(0)
         fused = None
         gauss = bool(self.args.gaussian_policy)      # log_stds [b, n, a] from the agents' log-std heads (model.py:119-120,135-136)
-        if self.args.shared_params and obs.is_cuda and not th.is_grad_enabled() and self.fused_inference:
+        mlp = self.args.shared_params and isinstance(self.policy_dicts[0], MLPAgent)
+        standing_aside = False
+        if mlp and obs.is_cuda and self.fused_inference:
+            # agent_type mlp: csrc/actor_mlp.hip, one launch without a graph and one autograd node with one — for eager calls.
+            # While a HIP graph is captured (or audited for a capture) the composition below runs, and nothing is noted.
+            agent, out = self.policy_dicts[0], None
+            standing_aside = not mlp_actor_allowed()
+            if not standing_aside and not th.is_grad_enabled():
+                if getattr(agent, "fused_inference", True):
+                    out = fused_actor_forward_mlp(agent, obs, self.n_, self.args.agent_id)
+            elif (not standing_aside and b * self.n_ >= WGRAD_MIN_ROWS and getattr(agent, "fused_training", True)
+                  and not obs.requires_grad):
+                why = actor_mlp_declines(agent, obs, self.n_, self.args.agent_id)
+                if why is None:
+                    out = actor_mlp_train(agent, obs, self.n_, self.args.agent_id)
+                else:
+                    note_fallback("actor_forward", "update pass: " + why)
+            if out is not None:
+                means, hiddens = out[0].view(b, self.n_, -1), out[1].view(b, self.n_, -1)
+                if gauss:                             # the mean head ran in the fc3 slot; csrc/gauss.hip reads h
+                    return means, agent.log_std_of(out[1]).view(b, self.n_, -1), hiddens
+                return means, self._log_stds_like(means), hiddens
+        if self.args.shared_params and obs.is_cuda and not th.is_grad_enabled() and self.fused_inference and not mlp:
             # rollout steps and bootstrap targets: one HIP launch instead of the module's ten kernels
             fused = fused_actor_forward(self.policy_dicts[0], obs, last_hid, self.n_, self.args.agent_id)
         if fused is not None:
@@ -597,7 +620,8 @@ class Model(nn.Module):
             if out is not None:
                 means = out[0].view(b, self.n_, -1)
                 return means, self._log_stds_like(means), out[1].view(b, self.n_, -1)
-        if gauss and obs.is_cuda and not (self.args.shared_params and isinstance(self.policy_dicts[0], RNNAgent)):
+        if (gauss and obs.is_cuda and not standing_aside
+                and not (self.args.shared_params and isinstance(self.policy_dicts[0], RNNAgent))):
             note_fallback("gaussian_policy", f"agent_type {self.args.agent_type}, shared_params {self.args.shared_params}")
         obs = self.with_ids(obs)
         if self.args.shared_params:

@@ -11,7 +11,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .util import note_fallback
+from .util import in_graph_audit, note_fallback
 
 
 def _find_fused_gru():
@@ -119,7 +119,9 @@ class RNNAgent(nn.Module):
 
 class MLPAgent(nn.Module):
     """madrl/agents/mlp_agent.py:5-32 (agent_type: mlp): fc1 -> LayerNorm -> act -> fc2 -> act -> fc3; forward returns
-    (action mean, None, h).  Runs as the tensor composition."""
+    (action mean, None, h).  This ``forward`` is the tensor composition; on the GPU under ``shared_params`` ``Model.policy``
+    takes csrc/actor_mlp.hip instead (``fused_actor_forward_mlp`` / ``actor_mlp_train``) wherever no HIP graph is being
+    captured.  ``fused_inference`` / ``fused_training`` (read with getattr, default True): the two switches of those paths."""
 
     def __init__(self, input_shape, args):
         super().__init__()
@@ -292,7 +294,8 @@ class RNNAgentGaussian(RNNAgent):
 
 class MLPAgentGaussian(MLPAgent):
     """madrl/agents/mlp_agent_gaussian.py:7-41 (agent_type: mlp): the MLP agent with the heads ``mean`` and ``log_std`` in
-    place of ``fc3``; forward returns (mean, log_std, h).  Runs as the tensor composition."""
+    place of ``fc3``; forward returns (mean, log_std, h).  The ``mean`` head sits where the fixed-std agent has ``fc3``, so
+    csrc/actor_mlp.hip serves it unchanged; on that path the log-std head is csrc/gauss.hip on the ``h`` it returns."""
 
     def _build_heads(self, args):
         self.mean = nn.Linear(args.hid_size, args.action_dim)
@@ -303,6 +306,9 @@ class MLPAgentGaussian(MLPAgent):
         # a CLASS property (as RNNAgentGaussian.fc2): the base class reads self.fc3 as the mean head, and no "fc3.*" key
         # enters the state_dict
         return self.mean
+
+    def log_std_of(self, h):
+        return gauss_log_std(h, self.log_std.weight, self.log_std.bias, self.args.LOG_STD_MIN, self.args.LOG_STD_MAX)
 
     def forward(self, inputs, hidden_state):
         mean, _, h = super().forward(inputs, hidden_state)
@@ -1462,6 +1468,168 @@ def critic_unshared_train(critics, x1, x2=None, shared=False, param_grads=True):
     critics = list(critics)
     flat = [p for c in critics for p in _critic_unshared_params(c)]
     return _CriticUnsharedFn.apply(x1, x2, shared, _critic_unshared_ln_eps(critics), param_grads, *flat)
+
+
+# ---- the MLP actor of agent_type mlp under shared_params (csrc/actor_mlp.hip): eager calls only --------------------------------
+_ACTOR_MLP_WS = {}
+
+
+def mlp_actor_allowed():
+    """The capture rule of csrc/actor_mlp.hip: its entry points are launched eagerly only.  False while the
+    current stream is capturing a HIP graph and while ``util.audit_graph_body`` runs a body on behalf of a capture site (the
+    audit must see what the capture will see); the MLP agent then runs the tensor composition, silently — nothing is
+    misconfigured.  Both the inference launch and the training node consult this one function."""
+    return not (in_graph_audit() or th.cuda.is_current_stream_capturing())
+
+
+def _actor_mlp_params(agent):
+    """The eight parameters of an MLPAgent in FlexActorMlpArgs order (the LayerNorm pair None without layernorm; the Gaussian
+    agent's ``mean`` head in the fc3 slot, through its class property)."""
+    ln = agent.layernorm if agent.args.layernorm else None
+    return (agent.fc1.weight, agent.fc1.bias, None if ln is None else ln.weight, None if ln is None else ln.bias,
+            agent.fc2.weight, agent.fc2.bias, agent.fc3.weight, agent.fc3.bias)
+
+
+def actor_mlp_declines(agent, obs, n_agents, agent_id):
+    """Why csrc/actor_mlp.hip does not cover ``agent`` on ``obs`` [b, n, obs_dim] / [b * n, obs_dim] (no id columns), or None."""
+    if type(agent) not in (MLPAgent, MLPAgentGaussian):
+        return f"a {type(agent).__name__}"
+    a, o = agent.args, obs.shape[-1]
+    if not (obs.is_cuda and obs.dtype == th.float32 and obs.dim() in (2, 3)):
+        return f"obs {tuple(obs.shape)} {obs.dtype} on {obs.device.type}"
+    if not (a.hid_size == _lib.FLEXNET_HID and a.hid_activation == "relu"):
+        return f"hid {a.hid_size}, act {a.hid_activation}"
+    if not (1 <= o <= _lib.FLEXNET_MAX_OBS and 1 <= n_agents <= _lib.FLEXNET_MAX_AGENTS and 1 <= a.action_dim <= _lib.FLEXNET_MAX_ACT):
+        return f"obs {o}, agents {n_agents}, actions {a.action_dim}"
+    rows = obs.numel() // o
+    if rows % n_agents != 0 or rows >= ACTOR_UNSHARED_MAX_ROWS or (obs.dim() == 3 and obs.shape[1] != n_agents):
+        return f"obs {tuple(obs.shape)} for {n_agents} agents"
+    if agent.fc1.weight.shape[1] != o + (n_agents if agent_id else 0):
+        return f"fc1 takes {agent.fc1.weight.shape[1]} columns, obs {o}, agent_id {bool(agent_id)}"
+    for p in _actor_mlp_params(agent):
+        if p is not None and not (p.is_cuda and p.dtype == th.float32 and p.is_contiguous()):
+            return "a parameter is not a contiguous fp32 device tensor"
+    return None
+
+
+def actor_mlp_supported(agent, obs, n_agents, agent_id):
+    """What csrc/actor_mlp.hip covers: ``type(agent)`` MLPAgent or MLPAgentGaussian with 64 hidden units and ReLU, fp32
+    contiguous device tensors, obs_dim <= 144, at most 8 agents and 8 actions, fc1 of obs_dim (+ n) columns."""
+    return actor_mlp_declines(agent, obs, n_agents, agent_id) is None
+
+
+def _actor_mlp_head(cls, rows, n, o, act_dim, agent_id, ln_w, ln_eps):
+    if not mlp_actor_allowed():
+        raise RuntimeError("csrc/actor_mlp.hip is launched eagerly only (nets.mlp_actor_allowed): never under a capture")
+    a = cls()
+    a.rows, a.n_agents, a.obs_dim, a.act_dim, a.hid = rows, n, o, act_dim, _lib.FLEXNET_HID
+    a.agent_id, a.layernorm, a.ln_eps = int(bool(agent_id)), int(ln_w is not None), float(ln_eps)
+    return a
+
+
+def _actor_mlp_launch_forward(params, obs, n, agent_id, ln_eps, saved=None):
+    """One flexnet_actor_mlp_forward launch on contiguous obs [rows, o]: (means [rows, a], h [rows, 64]), or None when the
+    library answers FLEXNET_EUNSUPPORTED."""
+    rows, o = obs.shape
+    act_dim = params[6].shape[0]
+    means = th.empty(rows, act_dim, dtype=th.float32, device=obs.device)
+    h = th.empty(rows, 64, dtype=th.float32, device=obs.device)
+    a = _actor_mlp_head(_lib.FlexActorMlpArgs, rows, n, o, act_dim, agent_id, params[2], ln_eps)
+    for name, p in zip(("fc1_w", "fc1_b", "ln_w", "ln_b", "fc2_w", "fc2_b", "fc3_w", "fc3_b"), params):
+        setattr(a, name, None if p is None else p.data_ptr())
+    a.obs, a.means, a.h = obs.data_ptr(), means.data_ptr(), h.data_ptr()
+    if saved is not None:
+        a.save_z1, a.save_x = saved[0].data_ptr(), saved[1].data_ptr()
+    if not _lib.try_launch("flexnet_actor_mlp_forward", a):
+        return None
+    return means, h
+
+
+def _actor_mlp_ln_eps(agent):
+    return float(agent.layernorm.eps) if agent.args.layernorm else 1e-5
+
+
+def fused_actor_forward_mlp(agent, obs, n_agents, agent_id):
+    """mlp_agent.py:20-32 + model.py:102-116 without an autograd graph, in ONE HIP launch (csrc/actor_mlp.hip) at any batch
+    size, instead of the module's ten kernels.  ``obs`` [b, n, obs_dim] WITHOUT the one-hot id columns (the kernel adds fc1's id
+    column of row r % n itself).  Returns (means [b * n, act], h [b * n, 64]), or None after ``note_fallback("actor_forward",
+    ...)`` when it declines on GPU tensors.  Never called under a capture (``mlp_actor_allowed``)."""
+    why = actor_mlp_declines(agent, obs, n_agents, agent_id)
+    if why is not None:
+        if obs.is_cuda:
+            note_fallback("actor_forward", why)
+        return None
+    with th.no_grad():
+        out = _actor_mlp_launch_forward(_actor_mlp_params(agent), obs.reshape(-1, obs.shape[-1]).contiguous(), n_agents, agent_id,
+                                        _actor_mlp_ln_eps(agent))
+    if out is None:
+        note_fallback("actor_forward", "FLEXNET_EUNSUPPORTED from flexnet_actor_mlp_forward")
+    return out
+
+
+class _ActorMlpTrainFn(th.autograd.Function):
+    """The MLP actor of ``agent_type: mlp`` for an update batch as ONE autograd node (csrc/actor_mlp.hip): the fused forward with
+    its saves (z1, x; h is its second result), one backward launch for dz1, dz2 and every vector sum, then ONE
+    flexnet_wgrad_batched call for d_fc1_w's observation block, d_fc2_w and d_fc3_w.  The id block of fc1's gradient is the
+    per-agent sums of dz1.  ``hid_grad``: h takes a gradient too (the Gaussian agent's log-std head reads it; the mean head's
+    share is formed inside the kernel), else it is non-differentiable.  Observations take no gradient.  Bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, obs, n_agents, agent_id, ln_eps, hid_grad, fc1_w, fc1_b, ln_w, ln_b, fc2_w, fc2_b, fc3_w, fc3_b):
+        obs = obs.contiguous()
+        saved = th.empty(2, obs.shape[0], 64, dtype=th.float32, device=obs.device)           # z1 | x
+        out = _actor_mlp_launch_forward((fc1_w, fc1_b, ln_w, ln_b, fc2_w, fc2_b, fc3_w, fc3_b), obs, n_agents, agent_id, ln_eps, saved)
+        if out is None:
+            _lib.check(_lib.FLEXNET_EUNSUPPORTED, "flexnet_actor_mlp_forward")
+        means, h = out
+        ctx.n_agents, ctx.agent_id, ctx.ln_eps = n_agents, bool(agent_id), float(ln_eps)
+        ctx.save_for_backward(obs, h, saved, fc1_w, ln_w, fc2_w, fc3_w)
+        if not hid_grad:
+            ctx.mark_non_differentiable(h)
+        ctx.set_materialize_grads(False)
+        return means, h
+
+    @staticmethod
+    def backward(ctx, d_means, d_h):
+        obs, h, saved, fc1_w, ln_w, fc2_w, fc3_w = ctx.saved_tensors
+        if d_means is None and d_h is None:
+            return (None,) * 13
+        rows, o = obs.shape
+        n, dev, act_dim, has_ln = ctx.n_agents, obs.device, fc3_w.shape[0], ln_w is not None
+        d_means = th.zeros(rows, act_dim, dtype=th.float32, device=dev) if d_means is None else d_means.contiguous()
+        dz = th.empty(2, rows, 64, dtype=th.float32, device=dev)                           # dz1 | dz2
+        small = th.empty(4, 64, dtype=th.float32, device=dev)                              # d_ln_w | d_ln_b | d_fc1_b | d_fc2_b
+        d_fc3_b = th.empty(act_dim, dtype=th.float32, device=dev)
+        d_id = th.empty(n, 64, dtype=th.float32, device=dev)
+        if dev not in _ACTOR_MLP_WS:
+            _ACTOR_MLP_WS[dev] = th.empty(_lib.FLEXNET_ACTOR_MLP_WS_FLOATS, dtype=th.float32, device=dev)
+        ws = _ACTOR_MLP_WS[dev]
+        g = _actor_mlp_head(_lib.FlexActorMlpBwdArgs, rows, n, o, act_dim, ctx.agent_id, ln_w, ctx.ln_eps)
+        g.d_means, g.z1, g.x, g.h = d_means.data_ptr(), saved[0].data_ptr(), saved[1].data_ptr(), h.data_ptr()
+        if d_h is not None:
+            d_h = d_h.contiguous()
+            g.d_h = d_h.data_ptr()
+        g.fc2_w, g.fc3_w, g.dz1, g.dz2 = fc2_w.data_ptr(), fc3_w.data_ptr(), dz[0].data_ptr(), dz[1].data_ptr()
+        if has_ln:
+            g.ln_w, g.d_ln_w, g.d_ln_b = ln_w.data_ptr(), small[0].data_ptr(), small[1].data_ptr()
+        g.d_fc1_b, g.d_fc2_b, g.d_fc3_b, g.d_dz1_agent = small[2].data_ptr(), small[3].data_ptr(), d_fc3_b.data_ptr(), d_id.data_ptr()
+        g.workspace, g.workspace_floats = ws.data_ptr(), ws.numel()
+        _lib.launch("flexnet_actor_mlp_backward", g)
+        d_fc1_w = th.empty_like(fc1_w)
+        d_fc2_w = th.empty_like(fc2_w)
+        d_fc3_w = th.empty_like(fc3_w)
+        tall_wgrad_batched([(dz[0], obs, d_fc1_w[:, :o], None), (dz[1], saved[1], d_fc2_w, None), (d_means, h, d_fc3_w, None)])
+        if ctx.agent_id:
+            d_fc1_w[:, o:] = d_id.t()
+        return (None, None, None, None, None, d_fc1_w, small[2], small[0] if has_ln else None, small[1] if has_ln else None,
+                d_fc2_w, small[3], d_fc3_w, d_fc3_b)
+
+
+def actor_mlp_train(agent, obs, n_agents, agent_id):
+    """The node on obs [b, n, obs_dim] / [b * n, obs_dim] (``actor_mlp_supported`` holds, ``mlp_actor_allowed()``, obs takes no
+    gradient): (means [b * n, act], h [b * n, 64]); for the Gaussian agent h carries the log-std head's gradient back."""
+    return _ActorMlpTrainFn.apply(obs.reshape(-1, obs.shape[-1]), n_agents, bool(agent_id), _actor_mlp_ln_eps(agent),
+                                  type(agent) is MLPAgentGaussian, *_actor_mlp_params(agent))
 
 
 def lnrelu_supported(agent, n_agents):

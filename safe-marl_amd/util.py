@@ -73,13 +73,33 @@ GRAPH_DENYLIST = ("at::native::reduce_kernel", "batch_norm_collect_statistics", 
                   "at::native::(anonymous namespace)::LpNormFunctor")
 
 
+_GRAPH_AUDITS = 0       # audit_graph_body calls in progress
+
+
+class _graph_audit:
+    """While ``audit_graph_body`` runs a body: ``in_graph_audit()`` holds, so that paths which stand aside during a capture
+    (nets.mlp_actor_allowed) stand aside here too and the audit sees the kernels the capture will see."""
+
+    def __enter__(self):
+        global _GRAPH_AUDITS
+        _GRAPH_AUDITS += 1
+
+    def __exit__(self, *exc):
+        global _GRAPH_AUDITS
+        _GRAPH_AUDITS -= 1
+
+
+def in_graph_audit():
+    return _GRAPH_AUDITS > 0
+
+
 def audit_graph_body(fn, allow=()):
     """Run ``fn`` (the body about to be captured) eagerly under torch.profiler and return the device kernel names it
     launched; raises if one of them is on ``GRAPH_DENYLIST``.  Used by the tests and, with FLEX_GRAPH_AUDIT=1, by the
     capture sites themselves (trainer._capture_sub_update, learner.RolloutGraph.capture)."""
     from torch.profiler import ProfilerActivity, profile
     th.cuda.synchronize()
-    with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU]) as prof:
+    with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU]) as prof, _graph_audit():
         fn()
         th.cuda.synchronize()
     names = sorted({ev.key for ev in prof.key_averages() if "cuda" in str(getattr(ev, "device_type", "")).lower()})
