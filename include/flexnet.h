@@ -1123,6 +1123,117 @@ typedef struct {
 int flexnet_actor_mlp_forward(const FlexActorMlpArgs* args, void* stream);
 int flexnet_actor_mlp_backward(const FlexActorMlpBwdArgs* args, void* stream);
 
+/* ---- agent_type: mlp under shared_params: False (madrl/models/model.py:124-138: one MLPAgent / MLPAgentGaussian per agent;
+ * csrc/actor_mlp_unshared.hip) ----
+ * flexnet_actor_mlp_*'s computation and work map with PER-AGENT weights: row s * n_agents + a of the [rows, .] tensors is agent a
+ * of sample s and uses fc1_w[a], fc1_b[a], ... — the modules' own parameter tensors through pointer tables, no stacked copy.  A
+ * wavefront owns 32 samples of one agent; a work-group's agent, blockIdx.x % n_agents, selects the weights.  Under agent_id,
+ * fc1_w[a] is [64, obs_dim + n_agents] and only its OWN id column obs_dim + a enters (the other one-hot entries are zero).  The
+ * Gaussian agent's `mean` head goes in the fc3 slot.
+ * FOR EAGER CALLS ONLY, like flexnet_actor_mlp_*: no caller in this project launches either entry point on a stream that is
+ * being captured into a HIP graph.
+ * forward: means [rows, act_dim] and h [rows, 64] always; with both save_* set also z1 and x.  Same bits with and without.
+ * backward: from d_means, the optional d_h [rows, 64] and the saves z1, x, h: dz1, dz2 [rows, 64]; per agent d_ln_w, d_ln_b
+ *         (layernorm), d_fc1_b, d_fc2_b as [n_agents, 64] and d_fc3_b as [n_agents, act_dim], each summed over the agent's rows
+ *         in a fixed order through `workspace` and a second launch: no atomics, bit-reproducible.  Agent a's id column of
+ *         d_fc1_w[a] equals d_fc1_b[a]; its other id columns are zero.  The weight gradients are three flexnet_wgrad_batched
+ *         problems per agent through its row pitch (a = dz1 + 64 a, lda = 64 n_agents, ...), all in one call.
+ * Limits and return codes are flexnet_actor_mlp_*'s: hid == FLEXNET_HID, ReLU, fp32, n_agents <= FLEXNET_MAX_AGENTS, obs_dim <=
+ * FLEXNET_MAX_OBS, act_dim <= FLEXNET_MAX_ACT, the [rows, 64] tensors and every fc2_w / fc3_w 16-byte aligned; else
+ * FLEXNET_EUNSUPPORTED.  Missing tensors or table entries, rows % n_agents != 0, one save without the other, LayerNorm without
+ * its pair, a short workspace: FLEXNET_EINVAL.  Both before any HIP call; then the grid and the launches on `stream`. */
+#define FLEXNET_ACTOR_MLP_UNSHARED_WS_FLOATS (FLEXNET_MAX_AGENTS * 128 * 320)
+typedef struct {
+    int32_t rows;              /* b * n_agents */
+    int32_t n_agents;
+    int32_t obs_dim;
+    int32_t act_dim;
+    int32_t agent_id;
+    int32_t layernorm;
+    float ln_eps;
+    int32_t hid;               /* FLEXNET_HID */
+    const float* obs;          /* [rows, obs_dim] */
+    const float* fc1_w[FLEXNET_MAX_AGENTS];    /* per agent: [64, obs_dim (+ n_agents)] */
+    const float* fc1_b[FLEXNET_MAX_AGENTS];    /* [64] */
+    const float* ln_w[FLEXNET_MAX_AGENTS];     /* [64] (layernorm) */
+    const float* ln_b[FLEXNET_MAX_AGENTS];
+    const float* fc2_w[FLEXNET_MAX_AGENTS];    /* [64, 64] */
+    const float* fc2_b[FLEXNET_MAX_AGENTS];    /* [64] */
+    const float* fc3_w[FLEXNET_MAX_AGENTS];    /* [act_dim, 64] */
+    const float* fc3_b[FLEXNET_MAX_AGENTS];    /* [act_dim] */
+    float* means;              /* out [rows, act_dim] */
+    float* h;                  /* out [rows, 64] */
+    float* save_z1;            /* out [rows, 64] each, both or none */
+    float* save_x;
+} FlexActorMlpUnsharedArgs;
+
+typedef struct {
+    int32_t rows;
+    int32_t n_agents;
+    int32_t obs_dim;
+    int32_t act_dim;
+    int32_t agent_id;
+    int32_t layernorm;
+    float ln_eps;
+    int32_t hid;
+    const float* d_means;      /* [rows, act_dim] */
+    const float* d_h;          /* [rows, 64] or NULL */
+    const float* z1;           /* the forward's saves */
+    const float* x;
+    const float* h;            /* the forward's h */
+    const float* ln_w[FLEXNET_MAX_AGENTS];     /* (layernorm) */
+    const float* fc2_w[FLEXNET_MAX_AGENTS];
+    const float* fc3_w[FLEXNET_MAX_AGENTS];
+    float* dz1;                /* out [rows, 64] */
+    float* dz2;                /* out [rows, 64] */
+    float* d_ln_w;             /* out [n_agents, 64] (layernorm) */
+    float* d_ln_b;
+    float* d_fc1_b;            /* out [n_agents, 64] */
+    float* d_fc2_b;            /* out [n_agents, 64] */
+    float* d_fc3_b;            /* out [n_agents, act_dim] */
+    float* workspace;
+    int64_t workspace_floats;  /* >= FLEXNET_ACTOR_MLP_UNSHARED_WS_FLOATS */
+} FlexActorMlpUnsharedBwdArgs;
+
+int flexnet_actor_mlp_unshared_forward(const FlexActorMlpUnsharedArgs* args, void* stream);
+int flexnet_actor_mlp_unshared_backward(const FlexActorMlpUnsharedBwdArgs* args, void* stream);
+
+/* ---- gaussian_policy: True under shared_params: False: every agent's own log-std head (csrc/gauss.hip) ----
+ * flexnet_gauss_head_*'s arithmetic with PER-AGENT weights: row r of the [rows, .] tensors uses w[r % n_agents] and
+ * b[r % n_agents] (pointer tables of the modules' own tensors; b all set or all NULL).  A wavefront owns 32 rows of one agent,
+ * so the weights are one uniform pointer per wavefront.  There is no exploration epilogue in this form.
+ * forward: log_std [rows, act_dim], and t = tanh(u) (optional).
+ * backward: from d_log_std and t: d_u [rows, act_dim] and d_h [rows, 64], either optional.  dw_a / db_a are
+ *         flexnet_wgrad_batched problems with the column sum, operands d_u and h at agent a's row pitch.
+ * hid == FLEXNET_HID, act_dim <= FLEXNET_MAX_ACT, n_agents <= FLEXNET_MAX_AGENTS, rows <= 2^30, h / d_h / every w 16-byte
+ * aligned; else FLEXNET_EUNSUPPORTED.  Missing tensors or table entries, rows % n_agents != 0: FLEXNET_EINVAL.  Both before any
+ * HIP call.  Launched eagerly only, like the actors they follow. */
+typedef struct {
+    int64_t rows;              /* b * n_agents */
+    int32_t n_agents;
+    int32_t act_dim;           /* <= FLEXNET_MAX_ACT */
+    int32_t hid;               /* FLEXNET_HID */
+    int32_t pad0;
+    float log_std_min, log_std_max;
+    const float* h;            /* [rows, 64] (forward) */
+    const float* w[FLEXNET_MAX_AGENTS];        /* per agent: [a, 64] */
+    const float* b[FLEXNET_MAX_AGENTS];        /* [a], or all NULL (forward) */
+    float* log_std;            /* out [rows, a] (forward) */
+    float* t;                  /* forward: out [rows, a], optional; backward: in */
+    const float* d_log_std;    /* [rows, a] (backward) */
+    float* d_u;                /* out [rows, a] (backward, optional) */
+    float* d_h;                /* out [rows, 64] (backward, optional) */
+} FlexGaussHeadUnsharedArgs;
+
+int flexnet_gauss_head_unshared_forward(const FlexGaussHeadUnsharedArgs* args, void* stream);
+int flexnet_gauss_head_unshared_backward(const FlexGaussHeadUnsharedArgs* args, void* stream);
+
+/* flexnet_actor_unshared_backward with the gradient the per-agent log-std heads send to the NEW hidden state: d_hn [rows, 64]
+ * (16-byte aligned, not NULL) is added to dh' = d_means @ fc2_w[a] before the gate gradients — what the shared-weight node does
+ * with its hidden-state gradient.  A compile-time variant of the same kernel body: flexnet_actor_unshared_backward itself is
+ * untouched.  Same checks and return codes; d_hn NULL: FLEXNET_EINVAL.  Launched eagerly only. */
+int flexnet_actor_unshared_backward_hn(const FlexActorUnsharedBwdArgs* args, const float* d_hn, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

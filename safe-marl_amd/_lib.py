@@ -85,6 +85,8 @@ SYMBOLS = (
     "flexnet_actor_unshared_forward", "flexnet_actor_unshared_backward",
     "flexnet_critic_unshared_forward", "flexnet_critic_unshared_backward", "flexnet_wgrad_batched",
     "flexnet_actor_mlp_forward", "flexnet_actor_mlp_backward",
+    "flexnet_actor_mlp_unshared_forward", "flexnet_actor_mlp_unshared_backward",
+    "flexnet_gauss_head_unshared_forward", "flexnet_gauss_head_unshared_backward", "flexnet_actor_unshared_backward_hn",
     "flexopf_qp_work_doubles", "flexopf_qp_solve",
 )
 
@@ -212,6 +214,31 @@ class FlexActorMlpBwdArgs(C.Structure):
                                                             "dz2", "d_ln_w", "d_ln_b", "d_fc1_b", "d_fc2_b", "d_fc3_b",
                                                             "d_dz1_agent", "workspace")] + \
                [("workspace_floats", C.c_int64)]
+
+
+FLEXNET_ACTOR_MLP_UNSHARED_WS_FLOATS = FLEXNET_MAX_AGENTS * 128 * 320
+
+
+class FlexActorMlpUnsharedArgs(C.Structure):
+    """include/flexnet.h: the per-agent MLP actors' forward, parameter tables (csrc/actor_mlp_unshared.hip)"""
+    _fields_ = _ACTOR_MLP_HEAD + [("obs", C.c_void_p)] + \
+               [(k, _AgentPtrs) for k in ("fc1_w", "fc1_b", "ln_w", "ln_b", "fc2_w", "fc2_b", "fc3_w", "fc3_b")] + \
+               [(k, C.c_void_p) for k in ("means", "h", "save_z1", "save_x")]
+
+
+class FlexActorMlpUnsharedBwdArgs(C.Structure):
+    """include/flexnet.h"""
+    _fields_ = _ACTOR_MLP_HEAD + [(k, C.c_void_p) for k in ("d_means", "d_h", "z1", "x", "h")] + \
+               [(k, _AgentPtrs) for k in ("ln_w", "fc2_w", "fc3_w")] + \
+               [(k, C.c_void_p) for k in ("dz1", "dz2", "d_ln_w", "d_ln_b", "d_fc1_b", "d_fc2_b", "d_fc3_b", "workspace")] + \
+               [("workspace_floats", C.c_int64)]
+
+
+class FlexGaussHeadUnsharedArgs(C.Structure):
+    """include/flexnet.h: every agent's own log-std head (csrc/gauss.hip)"""
+    _fields_ = [("rows", C.c_int64), ("n_agents", C.c_int32), ("act_dim", C.c_int32), ("hid", C.c_int32), ("pad0", C.c_int32),
+                ("log_std_min", C.c_float), ("log_std_max", C.c_float), ("h", C.c_void_p), ("w", _AgentPtrs), ("b", _AgentPtrs)] + \
+               [(k, C.c_void_p) for k in ("log_std", "t", "d_log_std", "d_u", "d_h")]
 
 
 class FlexCriticTailArgs(C.Structure):
@@ -532,6 +559,14 @@ def load():
     for fn, st in ((lib.flexnet_actor_mlp_forward, FlexActorMlpArgs), (lib.flexnet_actor_mlp_backward, FlexActorMlpBwdArgs)):
         fn.argtypes = [C.POINTER(st), vp]
         fn.restype = C.c_int
+    for fn, st in ((lib.flexnet_actor_mlp_unshared_forward, FlexActorMlpUnsharedArgs),
+                   (lib.flexnet_actor_mlp_unshared_backward, FlexActorMlpUnsharedBwdArgs),
+                   (lib.flexnet_gauss_head_unshared_forward, FlexGaussHeadUnsharedArgs),
+                   (lib.flexnet_gauss_head_unshared_backward, FlexGaussHeadUnsharedArgs)):
+        fn.argtypes = [C.POINTER(st), vp]
+        fn.restype = C.c_int
+    lib.flexnet_actor_unshared_backward_hn.argtypes = [C.POINTER(FlexActorUnsharedBwdArgs), vp, vp]
+    lib.flexnet_actor_unshared_backward_hn.restype = C.c_int
     lib.flexnet_clip_rmsprop.argtypes = [C.POINTER(FlexClipRmspropArgs), vp]
     lib.flexnet_clip_rmsprop.restype = C.c_int
     lib.flexnet_clip_rmsprop_refresh.argtypes = [C.POINTER(FlexClipRmspropArgs), C.POINTER(FlexWindowRefreshArgs), C.POINTER(FlexTdLossArgs), vp]

@@ -12,6 +12,8 @@
 // the six training saves of FlexActorArgs.  Backward: gru.hip's fused arithmetic (gate gradients, dx = d_gi @ W_ih on the
 // matrix cores and never stored, LayerNorm / ReLU / bias backward) on this map; the [n_agents, 64] parameter sums are per-lane
 // sums folded per work-group in a fixed order and summed over work-groups by a second launch: no atomics, bit-reproducible.
+// A second backward kernel from the same body (flexnet_actor_unshared_backward_hn) starts dh' from d_hn, the gradient the
+// per-agent log-std heads of RNNAgentGaussian modules send to the new hidden state; it is launched eagerly only.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "flexnet.h"
@@ -182,7 +184,10 @@ __global__ __launch_bounds__(64 * AU_W) void actor_unshared_forward_kernel(FlexA
 }
 
 // ---- backward ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64 * AU_W) void actor_unshared_backward_kernel(FlexActorUnsharedBwdArgs a, int blocks_per_agent) {
+// (the body of both backward kernels: WITH_HN = the variant that starts dh' from d_hn, the gradient the per-agent log-std heads
+// send to the new hidden state; without it the body is the kernel as it always was)
+template <bool WITH_HN>
+__device__ __forceinline__ void au_backward_body(const FlexActorUnsharedBwdArgs& a, const float* d_hn, int blocks_per_agent) {
     __shared__ __attribute__((aligned(16))) float s_add[SH], s_lnw[SH];
     __shared__ __attribute__((aligned(16))) float s_w2[FLEXNET_MAX_ACT * SH];
     // W_ih of the agent, read by the dx chains from ONE base register (with the weights in global memory the compiler kept a
@@ -224,6 +229,10 @@ __global__ __launch_bounds__(64 * AU_W) void actor_unshared_backward_kernel(Flex
 
         // dh' = d_means @ fc2_w: four steps per 32 units (the outputs past act_dim are zero rows)
         tv16 dh[2] = {au_zero_tile(), au_zero_tile()};
+        if (WITH_HN && ok) {                                      // (+ d_hn: the accumulators start from it)
+            dh[0] = load_tile(d_hn + row * SH + 4 * h);
+            dh[1] = load_tile(d_hn + row * SH + 32 + 4 * h);
+        }
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int k = 4 * h + j;
@@ -349,6 +358,15 @@ __global__ __launch_bounds__(64 * AU_W) void actor_unshared_backward_kernel(Flex
     }
 }
 
+__global__ __launch_bounds__(64 * AU_W) void actor_unshared_backward_kernel(FlexActorUnsharedBwdArgs a, int blocks_per_agent) {
+    au_backward_body<false>(a, nullptr, blocks_per_agent);
+}
+
+__global__ __launch_bounds__(64 * AU_W) void actor_hn_unshared_backward_kernel(FlexActorUnsharedBwdArgs a, const float* d_hn,
+                                                                             int blocks_per_agent) {
+    au_backward_body<true>(a, d_hn, blocks_per_agent);
+}
+
 // element e of every work-group's partial row of one agent, summed in a fixed order: block = 3 * agent + vector
 __global__ __launch_bounds__(64 * FLEX_RED_G) void actor_unshared_reduce_kernel(FlexActorUnsharedBwdArgs a, int blocks_per_agent) {
     const int ex = threadIdx.x & 63;
@@ -395,7 +413,8 @@ extern "C" int flexnet_actor_unshared_forward(const FlexActorUnsharedArgs* a, vo
     return flex_launch_status();
 }
 
-extern "C" int flexnet_actor_unshared_backward(const FlexActorUnsharedBwdArgs* a, void* stream) {
+// (d_hn NULL: flexnet_actor_unshared_backward; else its variant)
+static int au_backward(const FlexActorUnsharedBwdArgs* a, const float* d_hn, void* stream) {
     if (!a || a->rows < 0) return FLEXNET_EINVAL;
     if (!a->d_means || !a->r || !a->z || !a->n || !a->hn || !a->h_prev || !a->z1 || !a->x || !a->d_gi || !a->d_gh || !a->dz ||
         !a->d_fc1_b || !a->workspace || (a->layernorm && (!a->d_ln_w || !a->d_ln_b)))
@@ -408,14 +427,27 @@ extern "C" int flexnet_actor_unshared_backward(const FlexActorUnsharedBwdArgs* a
     for (int k = 0; k < a->n_agents; ++k) {
         if (!a->fc1_w[k] || !a->fc1_b[k] || !a->w_ih[k] || !a->fc2_w[k] || (a->layernorm && !a->ln_w[k])) return FLEXNET_EINVAL;
     }
-    if (!aligned) return FLEXNET_EUNSUPPORTED;
+    if (!aligned || !flex_aligned(d_hn, 16)) return FLEXNET_EUNSUPPORTED;
     if (a->rows == 0) return FLEXNET_OK;
     const int64_t batch = a->rows / a->n_agents;
     int64_t bpa = ((batch + 31) / 32 + AU_W - 1) / AU_W;
     if (bpa > AU_MAX_BLOCKS) bpa = AU_MAX_BLOCKS;
     if (bpa * a->n_agents * AU_PITCH > a->workspace_floats) return FLEXNET_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(actor_unshared_backward_kernel, dim3((unsigned)(bpa * a->n_agents)), dim3(64 * AU_W), 0, s, *a, (int)bpa);
+    if (d_hn)
+        hipLaunchKernelGGL(actor_hn_unshared_backward_kernel, dim3((unsigned)(bpa * a->n_agents)), dim3(64 * AU_W), 0, s, *a, d_hn,
+                           (int)bpa);
+    else
+        hipLaunchKernelGGL(actor_unshared_backward_kernel, dim3((unsigned)(bpa * a->n_agents)), dim3(64 * AU_W), 0, s, *a, (int)bpa);
     hipLaunchKernelGGL(actor_unshared_reduce_kernel, dim3(3 * a->n_agents), dim3(64 * FLEX_RED_G), 0, s, *a, (int)bpa);
     return flex_launch_status();
+}
+
+extern "C" int flexnet_actor_unshared_backward(const FlexActorUnsharedBwdArgs* a, void* stream) {
+    return au_backward(a, nullptr, stream);
+}
+
+extern "C" int flexnet_actor_unshared_backward_hn(const FlexActorUnsharedBwdArgs* a, const float* d_hn, void* stream) {
+    if (!d_hn) return FLEXNET_EINVAL;
+    return au_backward(a, d_hn, stream);
 }

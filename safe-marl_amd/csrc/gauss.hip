@@ -11,6 +11,9 @@
 //                   HBM-bound at update size: 42 MB of h at 163 840 rows.
 //   head backward:  d_u = d_log_std 0.5 (MAX - MIN) (1 - t^2);  d_h = d_u W in the same layout (16-byte stores).  dW / db
 //                   are flexnet_wgrad(d_u, h) with its column sums.
+//   per-agent heads: head forward / backward with the weights of agent r % n for row r (shared_params: False), on the actors'
+//                   work map — a wavefront owns 32 rows of one agent — so that the weights stay uniform per wavefront;
+//                   eager calls only, like the actors they follow.
 //   sum explore:    the agent-summed selection of iddpg.py:64-70 / matd3.py:91-98 with per-sample log-stds, one thread per
 //                   (environment, action component), every fp32 rounding where the tensor composition has it.
 //   ppo rows:       ppo.hip's policy loss with log_stds [rows, n, a] (summed over agents per row) and d_log_stds.
@@ -167,6 +170,152 @@ extern "C" int flexnet_gauss_head_backward(const FlexGaussHeadArgs* a, void* str
     if (a->rows == 0) return FLEXNET_OK;
     const unsigned blocks = (unsigned)((a->rows + GAUSS_ROWS - 1) / GAUSS_ROWS);
     hipLaunchKernelGGL(gauss_head_backward_kernel, dim3(blocks), dim3(GAUSS_THREADS), 0, (hipStream_t)stream, *a);
+    return flex_launch_status();
+}
+
+// ---- shared_params: False: every agent's own head (FlexGaussHeadUnsharedArgs) ------------------------------------------------
+// The two kernels above with the actors' work map instead of consecutive rows: a wavefront owns 32 samples of ONE agent (rows
+// s * n + a), a work-group is four wavefronts of agent blockIdx.x % n, so W and b are one uniform pointer per work-group out of
+// the tables.  Per row the arithmetic — and so the bits — are gauss_head_*_kernel's on that agent's weights.
+__global__ __launch_bounds__(GAUSS_THREADS) void gauss_head_unshared_forward_kernel(FlexGaussHeadUnsharedArgs a) {
+    const int lane = threadIdx.x & 63, i = lane & 31, hf = lane >> 5;
+    const int n = a.n_agents, ag = blockIdx.x % n;
+    const int64_t batch = a.rows / n;
+    const int64_t s = ((int64_t)(blockIdx.x / n) * (GAUSS_THREADS / 64) + (threadIdx.x >> 6)) * 32 + i;
+    const bool ok = s < batch;
+    const int64_t row = s * n + ag;
+    const int na = a.act_dim;
+    const float* W = a.w[ag];
+    const float* B = a.b[ag];
+    tv16 x0, x1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { x0[r] = 0.0f; x1[r] = 0.0f; }
+    if (ok) {
+        const float* hr = a.h + row * SH + 4 * hf;
+        x0 = load_tile(hr);
+        x1 = load_tile(hr + 32);
+    }
+    const float half_span = 0.5f * (a.log_std_max - a.log_std_min);
+    float ls[FLEXNET_MAX_ACT], t[FLEXNET_MAX_ACT];
+#pragma unroll
+    for (int k = 0; k < FLEXNET_MAX_ACT; ++k) {
+        ls[k] = 0.0f; t[k] = 0.0f;
+        if (k < na) {                                   // (the same for every lane: the exchange below is wavefront-wide)
+            const float* wr = W + k * SH + 4 * hf;
+            float p0 = 0.0f, p1 = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const tv4 w0 = ld4(wr + 8 * q), w1 = ld4(wr + 32 + 8 * q);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    p0 = fmaf(x0[4 * q + j], w0[j], p0);
+                    p1 = fmaf(x1[4 * q + j], w1[j], p1);
+                }
+            }
+            const float p = p0 + p1;
+            float u = p + other_half(p);
+            if (B) u += B[k];
+            t[k] = tanhf(u);
+            ls[k] = a.log_std_min + half_span * (t[k] + 1.0f);
+        }
+    }
+    if (!ok || hf != 0) return;
+    float* lo = a.log_std + row * na;
+#pragma unroll
+    for (int k = 0; k < FLEXNET_MAX_ACT; ++k)
+        if (k < na) lo[k] = ls[k];
+    if (a.t) {
+        float* to = a.t + row * na;
+#pragma unroll
+        for (int k = 0; k < FLEXNET_MAX_ACT; ++k)
+            if (k < na) to[k] = t[k];
+    }
+}
+
+__global__ __launch_bounds__(GAUSS_THREADS) void gauss_head_unshared_backward_kernel(FlexGaussHeadUnsharedArgs a) {
+    const int lane = threadIdx.x & 63, i = lane & 31, hf = lane >> 5;
+    const int n = a.n_agents, ag = blockIdx.x % n;
+    const int64_t batch = a.rows / n;
+    const int64_t s = ((int64_t)(blockIdx.x / n) * (GAUSS_THREADS / 64) + (threadIdx.x >> 6)) * 32 + i;
+    if (s >= batch) return;                             // (no exchange between lanes in this kernel)
+    const int64_t row = s * n + ag;
+    const int na = a.act_dim;
+    const float* W = a.w[ag];
+    const float half_span = 0.5f * (a.log_std_max - a.log_std_min);
+    float du[FLEXNET_MAX_ACT];
+#pragma unroll
+    for (int k = 0; k < FLEXNET_MAX_ACT; ++k) {
+        du[k] = 0.0f;
+        if (k < na) {
+            const float tt = a.t[row * na + k];
+            du[k] = a.d_log_std[row * na + k] * (half_span * (1.0f - tt * tt));
+        }
+    }
+    if (hf == 0 && a.d_u) {
+#pragma unroll
+        for (int k = 0; k < FLEXNET_MAX_ACT; ++k)
+            if (k < na) a.d_u[row * na + k] = du[k];
+    }
+    if (!a.d_h) return;
+    tv16 g0, g1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { g0[r] = 0.0f; g1[r] = 0.0f; }
+#pragma unroll
+    for (int k = 0; k < FLEXNET_MAX_ACT; ++k)
+        if (k < na) {
+            const float* wr = W + k * SH + 4 * hf;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const tv4 w0 = ld4(wr + 8 * q), w1 = ld4(wr + 32 + 8 * q);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    g0[4 * q + j] = fmaf(du[k], w0[j], g0[4 * q + j]);
+                    g1[4 * q + j] = fmaf(du[k], w1[j], g1[4 * q + j]);
+                }
+            }
+        }
+    float* dr = a.d_h + row * SH + 4 * hf;
+    store_tile(dr, g0, true);
+    store_tile(dr + 32, g1, true);
+}
+
+static int gauss_head_unshared_check(const FlexGaussHeadUnsharedArgs* a) {
+    if (!a || a->rows < 0 || a->act_dim < 1 || a->n_agents < 1) return FLEXNET_EINVAL;
+    if (a->hid != FLEXNET_HID || a->act_dim > FLEXNET_MAX_ACT || a->n_agents > FLEXNET_MAX_AGENTS || a->rows > GAUSS_MAX_ROWS)
+        return FLEXNET_EUNSUPPORTED;
+    if (a->rows % a->n_agents != 0) return FLEXNET_EINVAL;
+    bool aligned = true;
+    for (int k = 0; k < a->n_agents; ++k) {
+        if (!a->w[k] || ((a->b[k] != nullptr) != (a->b[0] != nullptr))) return FLEXNET_EINVAL;
+        aligned = aligned && flex_aligned(a->w[k], 16);
+    }
+    return aligned ? FLEXNET_OK : FLEXNET_EUNSUPPORTED;
+}
+
+static unsigned gauss_head_unshared_grid(const FlexGaussHeadUnsharedArgs* a) {
+    const int64_t batch = a->rows / a->n_agents;
+    return (unsigned)(((batch + GAUSS_ROWS - 1) / GAUSS_ROWS) * a->n_agents);
+}
+
+extern "C" int flexnet_gauss_head_unshared_forward(const FlexGaussHeadUnsharedArgs* a, void* stream) {
+    const int rc = gauss_head_unshared_check(a);
+    if (rc != FLEXNET_OK) return rc;
+    if (!a->h || !a->log_std) return FLEXNET_EINVAL;
+    if (!flex_aligned(a->h, 16)) return FLEXNET_EUNSUPPORTED;
+    if (a->rows == 0) return FLEXNET_OK;
+    hipLaunchKernelGGL(gauss_head_unshared_forward_kernel, dim3(gauss_head_unshared_grid(a)), dim3(GAUSS_THREADS), 0,
+                       (hipStream_t)stream, *a);
+    return flex_launch_status();
+}
+
+extern "C" int flexnet_gauss_head_unshared_backward(const FlexGaussHeadUnsharedArgs* a, void* stream) {
+    const int rc = gauss_head_unshared_check(a);
+    if (rc != FLEXNET_OK) return rc;
+    if (!a->d_log_std || !a->t || !(a->d_u || a->d_h)) return FLEXNET_EINVAL;
+    if (a->d_h && !flex_aligned(a->d_h, 16)) return FLEXNET_EUNSUPPORTED;
+    if (a->rows == 0) return FLEXNET_OK;
+    hipLaunchKernelGGL(gauss_head_unshared_backward_kernel, dim3(gauss_head_unshared_grid(a)), dim3(GAUSS_THREADS), 0,
+                       (hipStream_t)stream, *a);
     return flex_launch_status();
 }
 

@@ -25,13 +25,15 @@ from .nets import (WGRAD_MIN_ROWS, CriticTail, critic_first_layer, critic_td_los
                    critic_policy_loss_supported, expand_agents, MLPAgent, MLPAgentGaussian, MLPCritic, RNNAgent, RNNAgentGaussian, critic_policy_supported, critic_replayed_supported,
                    critic_tail_supported, fused_actor_forward, fused_actor_forward_unshared, actor_unshared_supported,
                    actor_mlp_declines, actor_mlp_train, fused_actor_forward_mlp, mlp_actor_allowed,
+                   actor_mlp_unshared_declines, actor_mlp_unshared_train, fused_actor_forward_mlp_unshared,
+                   gauss_head_unshared_declines, gauss_log_std_unshared,
                    actor_unshared_train, critic_unshared_supported, critic_unshared_train, fused_critic_forward_unshared,
                    tall_linear, td_loss, td_loss_supported, wide_batch_linear,
                    batchnorm_stats_supported, batchnorm_update_running_stats, sync_batchnorm, QMixer,
                    sqddpg_draw, sqddpg_fused_config, sqddpg_shapley_fused, ppo_gae, ppo_policy_loss, ppo_value_loss,
                    coma_baseline, coma_baseline_torch, coma_fused_config, coma_policy_loss, coma_rows)
 from .replay_buffer import Transition
-from .util import graph_capture, prep_obs, scale_action, select_action, translate_action, mean_all, note_fallback
+from .util import _graph_audit, graph_capture, prep_obs, scale_action, select_action, translate_action, mean_all, note_fallback
 
 
 class RolloutGraph:
@@ -427,7 +429,10 @@ class RolloutGraph:
             self.audit = audit_graph_body(self.body)
         side = th.cuda.Stream()
         side.wait_stream(th.cuda.current_stream())
-        with th.cuda.stream(side):
+        # The warm-up runs the body the capture will run: paths that stand aside for a capture (nets.mlp_actor_allowed) stand
+        # aside here too.  Otherwise the module loop they fall back to would run for the first time INSIDE the capture, and a
+        # library GEMM's first call of a process sets its handle and workspace up with calls a capturing stream forbids.
+        with th.cuda.stream(side), _graph_audit():
             for _ in range(3):
                 self.body()                      # warm-up on a side stream, as graph capture requires
         th.cuda.current_stream().wait_stream(side)
@@ -605,9 +610,17 @@ class Model(nn.Module):
                 if gauss:
                     return means, out[1].view(b, self.n_, -1), hiddens
                 return means, self._log_stds_like(means), hiddens
-        if not self.args.shared_params and obs.is_cuda and self.fused_inference and not gauss:
-            # one actor per agent (model.py:124-138): one launch over all of them (csrc/actor_unshared.hip) instead of the loop
-            # below.  The Gaussian agents keep the loop.
+        per_agent_eager = not self.args.shared_params and (gauss or isinstance(self.policy_dicts[0], MLPAgent))
+        if per_agent_eager and obs.is_cuda and self.fused_inference:
+            # one MLP or Gaussian actor per agent: csrc/actor_mlp_unshared.hip, or csrc/actor_unshared.hip with the gradient at the
+            # new hidden state, and csrc/gauss.hip's per-agent heads — for eager calls.  While a HIP graph is captured (or audited
+            # for a capture) the loop below runs, and nothing is noted.
+            out = self._policy_per_agent_eager(obs, last_hid, gauss)
+            if out is not None:
+                return out
+        if not self.args.shared_params and obs.is_cuda and self.fused_inference and not per_agent_eager:
+            # one RNN actor per agent with the fixed std (model.py:124-138): one launch over all of them (csrc/actor_unshared.hip)
+            # instead of the loop below, captures included.
             out = None
             if not th.is_grad_enabled():
                 out = fused_actor_forward_unshared(self.policy_dicts, obs, last_hid)
@@ -620,8 +633,8 @@ class Model(nn.Module):
             if out is not None:
                 means = out[0].view(b, self.n_, -1)
                 return means, self._log_stds_like(means), out[1].view(b, self.n_, -1)
-        if (gauss and obs.is_cuda and not standing_aside
-                and not (self.args.shared_params and isinstance(self.policy_dicts[0], RNNAgent))):
+        if (gauss and obs.is_cuda and not standing_aside and self.args.shared_params
+                and not isinstance(self.policy_dicts[0], RNNAgent)):
             note_fallback("gaussian_policy", f"agent_type {self.args.agent_type}, shared_params {self.args.shared_params}")
         obs = self.with_ids(obs)
         if self.args.shared_params:
@@ -638,6 +651,45 @@ class Model(nn.Module):
                 return means, th.stack([o[1] for o in outs], dim=1), hiddens
         # fixed_policy_std (model.py:121-123): log(1.0) = 0 at the default config
         return means, self._log_stds_like(means), hiddens
+
+    def _policy_per_agent_eager(self, obs, last_hid, gauss):
+        """``policy`` under ``shared_params: False`` for MLP agents and for Gaussian agents of either type, on GPU tensors: the
+        launch under no_grad, the autograd node with gradients from WGRAD_MIN_ROWS actor rows, and for Gaussian agents the
+        per-agent head node on the ``h`` / new hidden state either returns.  None where the per-agent loop runs: silently while
+        a HIP graph is captured or audited (``mlp_actor_allowed``), below the threshold and with a switch off
+        (``fused_inference`` / ``fused_training`` on any agent); after a note where the configuration declines."""
+        agents = list(self.policy_dicts)
+        b, n = obs.size(0), self.n_
+        if not mlp_actor_allowed():
+            return None
+        mlp = isinstance(agents[0], MLPAgent)
+        out = None
+        if not th.is_grad_enabled():
+            if all(getattr(g, "fused_inference", True) for g in agents):
+                out = fused_actor_forward_mlp_unshared(agents, obs) if mlp else fused_actor_forward_unshared(agents, obs, last_hid)
+        elif (b * n >= WGRAD_MIN_ROWS and not obs.requires_grad and all(getattr(g, "fused_training", True) for g in agents)
+              and (mlp or not last_hid.requires_grad)):
+            if mlp:
+                why = actor_mlp_unshared_declines(agents, obs, self.args.agent_id)
+                if why is None:
+                    out = actor_mlp_unshared_train(agents, obs)
+                else:
+                    note_fallback("actor_mlp_unshared", "update pass: " + why)
+            elif actor_unshared_supported(agents, obs, self.args.agent_id, kind=type(agents[0])):
+                out = actor_unshared_train(agents, obs, last_hid)
+            else:
+                note_fallback("actor_unshared", f"update pass: agent_type {self.args.agent_type}, hid {self.args.hid_size}, "
+                                                f"act {self.args.hid_activation}, obs {tuple(obs.shape)} {obs.dtype}")
+        if out is None:
+            return None
+        means, hiddens = out[0].view(b, n, -1), out[1].view(b, n, -1)
+        if not gauss:
+            return means, self._log_stds_like(means), hiddens
+        why = gauss_head_unshared_declines(agents, out[1])
+        if why is None:
+            return means, gauss_log_std_unshared(agents, out[1]).view(b, n, -1), hiddens
+        note_fallback("gauss_head", "per-agent heads: " + why)
+        return means, th.stack([g.log_std_of(hiddens[:, i]) for i, g in enumerate(agents)], dim=1), hiddens
 
     def _log_stds_like(self, means):
         """fixed_policy_std (model.py:121-123) as a broadcast view of ONE cached element per device — a fill kernel per

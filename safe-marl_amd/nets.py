@@ -4,6 +4,7 @@ Training (autograd) runs through PyTorch-ROCm; the actor's INFERENCE pass — ev
 bootstrap target — is one fused HIP launch (csrc/actor.hip, include/flexnet.h) through ``fused_actor_forward``."""
 from __future__ import annotations
 
+import ctypes as C
 import math
 import os
 import torch as th
@@ -121,7 +122,8 @@ class MLPAgent(nn.Module):
     """madrl/agents/mlp_agent.py:5-32 (agent_type: mlp): fc1 -> LayerNorm -> act -> fc2 -> act -> fc3; forward returns
     (action mean, None, h).  This ``forward`` is the tensor composition; on the GPU under ``shared_params`` ``Model.policy``
     takes csrc/actor_mlp.hip instead (``fused_actor_forward_mlp`` / ``actor_mlp_train``) wherever no HIP graph is being
-    captured.  ``fused_inference`` / ``fused_training`` (read with getattr, default True): the two switches of those paths."""
+    captured, and under ``shared_params: False`` csrc/actor_mlp_unshared.hip over all the agents' modules
+    (``fused_actor_forward_mlp_unshared`` / ``actor_mlp_unshared_train``).  ``fused_inference`` / ``fused_training`` (read with getattr, default True): the two switches of those paths."""
 
     def __init__(self, input_shape, args):
         super().__init__()
@@ -1079,8 +1081,10 @@ def _unshared_params(agent):
             r.weight_ih, r.weight_hh, r.bias_ih, r.bias_hh, agent.fc2.weight, agent.fc2.bias)
 
 
-def _unshared_declines(agents, obs, agent_id):
-    """Why csrc/actor_unshared.hip does not cover these per-agent actors on ``obs`` [b, n, obs_dim], or None."""
+def _unshared_declines(agents, obs, agent_id, kind=None):
+    """Why csrc/actor_unshared.hip does not cover these per-agent actors on ``obs`` [b, n, obs_dim], or None.  ``kind``: the one
+    class every agent must be — RNNAgent (default), or RNNAgentGaussian, whose ``mean`` head sits in the fc2 slot."""
+    kind = RNNAgent if kind is None else kind
     n, o = len(agents), obs.shape[-1]
     a = agents[0].args
     if not (obs.is_cuda and obs.dtype == th.float32 and obs.dim() == 3 and obs.shape[1] == n):
@@ -1090,7 +1094,7 @@ def _unshared_declines(agents, obs, agent_id):
     if obs.shape[0] * n >= ACTOR_UNSHARED_MAX_ROWS:
         return f"{obs.shape[0] * n} rows"
     for i, agent in enumerate(agents):
-        if type(agent) is not RNNAgent:              # (the Gaussian agent keeps the composition)
+        if type(agent) is not kind:
             return f"agent {i} is a {type(agent).__name__}"
         if agent.fc1.weight.shape[1] != o + (n if agent_id else 0):
             return f"agent {i}: fc1 takes {agent.fc1.weight.shape[1]} columns, obs {o}, agent_id {bool(agent_id)}"
@@ -1102,10 +1106,10 @@ def _unshared_declines(agents, obs, agent_id):
     return None
 
 
-def actor_unshared_supported(agents, obs, agent_id, train=True):
+def actor_unshared_supported(agents, obs, agent_id, train=True, kind=None):
     """``actor_train_supported``'s conditions for EVERY agent of a ``shared_params: False`` model (obs [b, n, obs_dim]), and
-    ``type(agent) is RNNAgent``; ``train``: also the row threshold of the hand-written weight gradients."""
-    return (_unshared_declines(agents, obs, agent_id) is None and not obs.requires_grad
+    ``type(agent) is kind`` (RNNAgent); ``train``: also the row threshold of the hand-written weight gradients."""
+    return (_unshared_declines(agents, obs, agent_id, kind) is None and not obs.requires_grad
             and (not train or obs.shape[0] * obs.shape[1] >= WGRAD_MIN_ROWS))
 
 
@@ -1152,7 +1156,7 @@ def fused_actor_forward_unshared(agents, obs, hidden):
     agents = list(agents)
     n, o = len(agents), obs.shape[-1]
     agent_id = agents[0].fc1.weight.shape[1] != o
-    why = _unshared_declines(agents, obs, agent_id)
+    why = _unshared_declines(agents, obs, agent_id, RNNAgentGaussian if type(agents[0]) is RNNAgentGaussian else None)
     if why is None and hidden.dtype != th.float32:
         why = f"hidden {hidden.dtype}"
     if why is not None:
@@ -1189,12 +1193,13 @@ class _ActorUnsharedTrainFn(th.autograd.Function):
         ctx.n_agents, ctx.agent_id, ctx.ln_eps = n_agents, bool(agent_id), float(ln_eps)
         ctx.has_ln = params[0][2] is not None
         ctx.save_for_backward(obs, hidden, hid_out, saved, *[p for p in flat if p is not None])
-        ctx.mark_non_differentiable(hid_out)
+        if not getattr(ctx, "hid_grad", False):
+            ctx.mark_non_differentiable(hid_out)
         ctx.set_materialize_grads(False)
         return means, hid_out
 
     @staticmethod
-    def backward(ctx, d_means, _d_hid):
+    def backward(ctx, d_means, d_hid):
         obs, hidden, hid_out, saved = ctx.saved_tensors[:4]
         n, dev, has_ln = ctx.n_agents, obs.device, ctx.has_ln
         per = 10 if has_ln else 8
@@ -1204,9 +1209,9 @@ class _ActorUnsharedTrainFn(th.autograd.Function):
             params.append(p if has_ln else p[:2] + [None, None] + p[2:])
         rows, o = obs.shape
         b, act_dim = rows // n, params[0][8].shape[0]
-        if d_means is None:
+        if d_means is None and d_hid is None:
             return (None,) * (5 + 10 * n)
-        d_means = d_means.contiguous()
+        d_means = th.zeros(rows, act_dim, dtype=th.float32, device=dev) if d_means is None else d_means.contiguous()
         d_gi = th.empty(rows, 192, dtype=th.float32, device=dev)
         d_gh = th.empty(rows, 192, dtype=th.float32, device=dev)
         dz = th.empty(rows, 64, dtype=th.float32, device=dev)
@@ -1220,7 +1225,13 @@ class _ActorUnsharedTrainFn(th.autograd.Function):
         g.d_gi, g.d_gh, g.dz = d_gi.data_ptr(), d_gh.data_ptr(), dz.data_ptr()
         g.d_ln_w, g.d_ln_b, g.d_fc1_b = small[0].data_ptr(), small[1].data_ptr(), small[2].data_ptr()
         g.workspace, g.workspace_floats = ws.data_ptr(), ws.numel()
-        _lib.launch("flexnet_actor_unshared_backward", g)
+        if d_hid is None:
+            _lib.launch("flexnet_actor_unshared_backward", g)
+        else:                                        # (_ActorUnsharedTrainHidFn: the log-std heads' gradient at the new hidden state)
+            if not mlp_actor_allowed():
+                raise RuntimeError("flexnet_actor_unshared_backward_hn is launched eagerly only (nets.mlp_actor_allowed)")
+            d_hid = d_hid.contiguous()
+            _lib.launch("flexnet_actor_unshared_backward_hn", g, C.c_void_p(d_hid.data_ptr()))
         # the weight gradients: four csrc/wgrad.hip products per agent, each over the agent's rows through the row pitch, all in
         # ONE flexnet_wgrad_batched call; the GRU's and fc2's bias gradients are the column sums of the same passes
         ld = params[0][0].shape[1]
@@ -1245,13 +1256,26 @@ class _ActorUnsharedTrainFn(th.autograd.Function):
         return (None, None, None, None, None, *grads)
 
 
+class _ActorUnsharedTrainHidFn(_ActorUnsharedTrainFn):
+    """_ActorUnsharedTrainFn whose new hidden state takes a gradient too (flexnet_actor_unshared_backward_hn): the Gaussian
+    agents' per-agent log-std heads read it (``_GaussHeadUnsharedFn``); the mean heads' share is formed inside the kernel.  For
+    eager calls only (``mlp_actor_allowed``)."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        ctx.hid_grad = True
+        return _ActorUnsharedTrainFn.forward(ctx, *args)
+
+
 def actor_unshared_train(agents, obs, hidden):
-    """The node on obs [b, n, obs_dim] / hidden [b, n, 64] (``actor_unshared_supported`` holds): (means, hidden) as [b * n, .]."""
+    """The node on obs [b, n, obs_dim] / hidden [b, n, 64] (``actor_unshared_supported`` holds): (means, hidden) as [b * n, .].
+    For RNNAgentGaussian modules the new hidden state carries the log-std heads' gradient back."""
     agents = list(agents)
     n, o = len(agents), obs.shape[-1]
     agent_id = agents[0].fc1.weight.shape[1] != o
     flat = [p for g in agents for p in _unshared_params(g)]
-    return _ActorUnsharedTrainFn.apply(obs.reshape(-1, o), hidden.reshape(-1, 64), n, agent_id, _unshared_ln_eps(agents), *flat)
+    node = _ActorUnsharedTrainHidFn if type(agents[0]) is RNNAgentGaussian else _ActorUnsharedTrainFn
+    return node.apply(obs.reshape(-1, o), hidden.reshape(-1, 64), n, agent_id, _unshared_ln_eps(agents), *flat)
 
 
 # ---- the per-agent critics of shared_params: False (csrc/critic_unshared.hip) ------------------------------------------------
@@ -1630,6 +1654,288 @@ def actor_mlp_train(agent, obs, n_agents, agent_id):
     gradient): (means [b * n, act], h [b * n, 64]); for the Gaussian agent h carries the log-std head's gradient back."""
     return _ActorMlpTrainFn.apply(obs.reshape(-1, obs.shape[-1]), n_agents, bool(agent_id), _actor_mlp_ln_eps(agent),
                                   type(agent) is MLPAgentGaussian, *_actor_mlp_params(agent))
+
+
+# ---- the MLP actors of agent_type mlp under shared_params False (csrc/actor_mlp_unshared.hip): eager calls only ----------------
+_ACTOR_MLP_UNSHARED_WS = {}
+_ACTOR_MLP_TABLES = ("fc1_w", "fc1_b", "ln_w", "ln_b", "fc2_w", "fc2_b", "fc3_w", "fc3_b")
+
+
+def _one_configuration(agents):
+    """None when every agent is of agent 0's class and configuration (the kernels take ONE set of sizes and switches), else why
+    not."""
+    first = agents[0]
+    a0 = first.args
+
+    def key(g):
+        a = g.args
+        eps = float(g.layernorm.eps) if a.layernorm else None
+        return (a.hid_size, a.hid_activation, bool(a.layernorm), eps, a.action_dim, tuple(g.fc1.weight.shape),
+                getattr(a, "LOG_STD_MIN", None), getattr(a, "LOG_STD_MAX", None))
+    for i, g in enumerate(agents):
+        if type(g) is not type(first):
+            return f"agent {i} is a {type(g).__name__}, agent 0 a {type(first).__name__}"
+        if g.args is not a0 and key(g) != key(first):
+            return f"agent {i} is configured unlike agent 0"
+    return None
+
+
+def actor_mlp_unshared_declines(agents, obs, agent_id):
+    """Why csrc/actor_mlp_unshared.hip does not cover these per-agent MLP actors on ``obs`` [b, n, obs_dim] (no id columns), or
+    None: ``actor_mlp_declines``'s predicates for every agent, and all agents of one class and one configuration."""
+    agents = list(agents)
+    n = len(agents)
+    if not (obs.dim() == 3 and obs.shape[1] == n):
+        return f"obs {tuple(obs.shape)} for {n} agents"
+    why = _one_configuration(agents)
+    if why is not None:
+        return why
+    for i, g in enumerate(agents):
+        why = actor_mlp_declines(g, obs, n, agent_id)
+        if why is not None:
+            return f"agent {i}: {why}"
+    return None
+
+
+def actor_mlp_unshared_supported(agents, obs, agent_id):
+    """What csrc/actor_mlp_unshared.hip covers: ``actor_mlp_supported`` for every agent, all of one class and configuration."""
+    return actor_mlp_unshared_declines(agents, obs, agent_id) is None
+
+
+def _fill_tables(a, names, params, n):
+    for k, name in enumerate(names):
+        table = getattr(a, name, None)
+        if table is not None:
+            for i in range(n):
+                p = params[i][k]
+                table[i] = None if p is None else p.data_ptr()
+
+
+def _actor_mlp_unshared_launch_forward(params, obs, n, agent_id, ln_eps, saved=None):
+    """One flexnet_actor_mlp_unshared_forward launch on contiguous obs [rows, o]: (means [rows, a], h [rows, 64]), or None when
+    the library answers FLEXNET_EUNSUPPORTED.  ``params``: per agent, the eight tensors in ``_ACTOR_MLP_TABLES`` order."""
+    rows, o = obs.shape
+    act_dim = params[0][6].shape[0]
+    means = th.empty(rows, act_dim, dtype=th.float32, device=obs.device)
+    h = th.empty(rows, 64, dtype=th.float32, device=obs.device)
+    a = _actor_mlp_head(_lib.FlexActorMlpUnsharedArgs, rows, n, o, act_dim, agent_id, params[0][2], ln_eps)
+    _fill_tables(a, _ACTOR_MLP_TABLES, params, n)
+    a.obs, a.means, a.h = obs.data_ptr(), means.data_ptr(), h.data_ptr()
+    if saved is not None:
+        a.save_z1, a.save_x = saved[0].data_ptr(), saved[1].data_ptr()
+    if not _lib.try_launch("flexnet_actor_mlp_unshared_forward", a):
+        return None
+    return means, h
+
+
+def fused_actor_forward_mlp_unshared(agents, obs):
+    """model.py:124-138 with one MLPAgent (or MLPAgentGaussian) per agent, without an autograd graph, in ONE HIP launch
+    (csrc/actor_mlp_unshared.hip) instead of the loop's ten kernels per agent.  ``obs`` [b, n, obs_dim] WITHOUT the one-hot id
+    columns (agent i's own id column of its fc1 is added by the kernel).  Returns (means [b * n, act], h [b * n, 64]), or None
+    after ``note_fallback("actor_mlp_unshared", ...)`` when it declines on GPU tensors.  Never called under a capture
+    (``mlp_actor_allowed``)."""
+    agents = list(agents)
+    n, o = len(agents), obs.shape[-1]
+    agent_id = agents[0].fc1.weight.shape[1] != o
+    why = actor_mlp_unshared_declines(agents, obs, agent_id)
+    if why is not None:
+        if obs.is_cuda:
+            note_fallback("actor_mlp_unshared", why)
+        return None
+    with th.no_grad():
+        out = _actor_mlp_unshared_launch_forward([_actor_mlp_params(g) for g in agents], obs.reshape(-1, o).contiguous(), n,
+                                                 agent_id, _actor_mlp_ln_eps(agents[0]))
+    if out is None:
+        note_fallback("actor_mlp_unshared", "FLEXNET_EUNSUPPORTED from flexnet_actor_mlp_unshared_forward")
+    return out
+
+
+class _ActorMlpUnsharedTrainFn(th.autograd.Function):
+    """The per-agent MLP actors of ``shared_params: False`` for an update batch as ONE autograd node over all agents' parameters
+    (csrc/actor_mlp_unshared.hip): the fused forward with its saves (z1, x; h is its second result), one backward launch for
+    dz1, dz2 and every agent's vector sums, then the 3 n weight gradients — per agent d_fc1_w's observation block, d_fc2_w and
+    d_fc3_w over the agent's rows through the row pitch — as ONE flexnet_wgrad_batched call.  The id block of agent a's fc1
+    gradient is zero except its own column a, which is its bias gradient (the one-hot input).  ``hid_grad``: h takes a gradient
+    too (the Gaussian agents' log-std heads read it), else it is non-differentiable.  Observations take no gradient.
+    Bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, obs, n_agents, agent_id, ln_eps, hid_grad, *flat):
+        obs = obs.contiguous()
+        params = [flat[8 * i:8 * i + 8] for i in range(n_agents)]
+        saved = th.empty(2, obs.shape[0], 64, dtype=th.float32, device=obs.device)           # z1 | x
+        out = _actor_mlp_unshared_launch_forward(params, obs, n_agents, agent_id, ln_eps, saved)
+        if out is None:
+            _lib.check(_lib.FLEXNET_EUNSUPPORTED, "flexnet_actor_mlp_unshared_forward")
+        means, h = out
+        ctx.n_agents, ctx.agent_id, ctx.ln_eps = n_agents, bool(agent_id), float(ln_eps)
+        ctx.has_ln = params[0][2] is not None
+        keep = [p for q in params for p in (q[0], q[2], q[4], q[6]) if p is not None]        # fc1_w, ln_w, fc2_w, fc3_w
+        ctx.save_for_backward(obs, h, saved, *keep)
+        if not hid_grad:
+            ctx.mark_non_differentiable(h)
+        ctx.set_materialize_grads(False)
+        return means, h
+
+    @staticmethod
+    def backward(ctx, d_means, d_h):
+        obs, h, saved = ctx.saved_tensors[:3]
+        n, dev, has_ln = ctx.n_agents, obs.device, ctx.has_ln
+        if d_means is None and d_h is None:
+            return (None,) * (5 + 8 * n)
+        per = 4 if has_ln else 3
+        kept = [list(ctx.saved_tensors[3 + per * i:3 + per * (i + 1)]) for i in range(n)]
+        if not has_ln:
+            kept = [[q[0], None, q[1], q[2]] for q in kept]
+        rows, o = obs.shape
+        b, act_dim, ld = rows // n, kept[0][3].shape[0], kept[0][0].shape[1]
+        d_means = th.zeros(rows, act_dim, dtype=th.float32, device=dev) if d_means is None else d_means.contiguous()
+        dz = th.empty(2, rows, 64, dtype=th.float32, device=dev)                           # dz1 | dz2
+        small = th.empty(4, n, 64, dtype=th.float32, device=dev)                           # d_ln_w | d_ln_b | d_fc1_b | d_fc2_b
+        d_fc3_b = th.empty(n, act_dim, dtype=th.float32, device=dev)
+        if dev not in _ACTOR_MLP_UNSHARED_WS:
+            _ACTOR_MLP_UNSHARED_WS[dev] = th.empty(_lib.FLEXNET_ACTOR_MLP_UNSHARED_WS_FLOATS, dtype=th.float32, device=dev)
+        ws = _ACTOR_MLP_UNSHARED_WS[dev]
+        g = _actor_mlp_head(_lib.FlexActorMlpUnsharedBwdArgs, rows, n, o, act_dim, ctx.agent_id, kept[0][1], ctx.ln_eps)
+        g.d_means, g.z1, g.x, g.h = d_means.data_ptr(), saved[0].data_ptr(), saved[1].data_ptr(), h.data_ptr()
+        if d_h is not None:
+            d_h = d_h.contiguous()
+            g.d_h = d_h.data_ptr()
+        for i in range(n):
+            g.fc2_w[i], g.fc3_w[i] = kept[i][2].data_ptr(), kept[i][3].data_ptr()
+            if has_ln:
+                g.ln_w[i] = kept[i][1].data_ptr()
+        g.dz1, g.dz2 = dz[0].data_ptr(), dz[1].data_ptr()
+        if has_ln:
+            g.d_ln_w, g.d_ln_b = small[0].data_ptr(), small[1].data_ptr()
+        g.d_fc1_b, g.d_fc2_b, g.d_fc3_b = small[2].data_ptr(), small[3].data_ptr(), d_fc3_b.data_ptr()
+        g.workspace, g.workspace_floats = ws.data_ptr(), ws.numel()
+        _lib.launch("flexnet_actor_mlp_unshared_backward", g)
+        d_fc1_w = (th.zeros if ctx.agent_id else th.empty)(n, 64, ld, dtype=th.float32, device=dev)
+        d_fc2_w = th.empty(n, 64, 64, dtype=th.float32, device=dev)
+        d_fc3_w = th.empty(n, act_dim, 64, dtype=th.float32, device=dev)
+        obs3, h3, x3 = obs.view(b, n, o), h.view(b, n, 64), saved[1].view(b, n, 64)
+        dm3, dz1_3, dz2_3 = d_means.view(b, n, act_dim), dz[0].view(b, n, 64), dz[1].view(b, n, 64)
+        problems = []
+        for i in range(n):
+            problems += [(dz1_3[:, i], obs3[:, i], d_fc1_w[i, :, :o], None), (dz2_3[:, i], x3[:, i], d_fc2_w[i], None),
+                         (dm3[:, i], h3[:, i], d_fc3_w[i], None)]
+        tall_wgrad_batched(problems)                                                       # 3 n <= 24 problems: one call
+        if ctx.agent_id:
+            th.diagonal(d_fc1_w[:, :, o:], dim1=0, dim2=2).copy_(small[2].t())             # [64, n]: agent i's own id column
+        grads = []
+        for i in range(n):
+            grads += [d_fc1_w[i], small[2, i], small[0, i] if has_ln else None, small[1, i] if has_ln else None,
+                      d_fc2_w[i], small[3, i], d_fc3_w[i], d_fc3_b[i]]
+        return (None, None, None, None, None, *grads)
+
+
+def actor_mlp_unshared_train(agents, obs):
+    """The node on obs [b, n, obs_dim] (``actor_mlp_unshared_supported`` holds, ``mlp_actor_allowed()``, obs takes no gradient):
+    (means [b * n, act], h [b * n, 64]); for the Gaussian agents h carries the log-std heads' gradient back."""
+    agents = list(agents)
+    n, o = len(agents), obs.shape[-1]
+    agent_id = agents[0].fc1.weight.shape[1] != o
+    flat = [p for g in agents for p in _actor_mlp_params(g)]
+    return _ActorMlpUnsharedTrainFn.apply(obs.reshape(-1, o), n, agent_id, _actor_mlp_ln_eps(agents[0]),
+                                          type(agents[0]) is MLPAgentGaussian, *flat)
+
+
+# ---- every agent's own log-std head under shared_params False (csrc/gauss.hip): eager calls only -------------------------------
+def gauss_head_unshared_declines(agents, h):
+    """Why flexnet_gauss_head_unshared_* does not cover the ``log_std`` heads of these per-agent Gaussian agents on ``h``
+    [b * n, 64], or None: ``gauss_log_std``'s predicates for every head, and all agents of one class and configuration."""
+    agents = list(agents)
+    n = len(agents)
+    if not all(type(g) in (RNNAgentGaussian, MLPAgentGaussian) for g in agents):
+        return "an agent without a log_std head"
+    why = _one_configuration(agents)
+    if why is not None:
+        return why
+    if not (h.is_cuda and h.dtype == th.float32 and h.dim() == 2 and h.shape[1] == _lib.FLEXNET_HID and h.shape[0] % n == 0
+            and 1 <= n <= _lib.FLEXNET_MAX_AGENTS and h.shape[0] <= (1 << 30)):
+        return f"h {tuple(h.shape)} {h.dtype} on {h.device.type} for {n} agents"
+    for i, g in enumerate(agents):
+        w, b = g.log_std.weight, g.log_std.bias
+        if not (w.shape[1] == _lib.FLEXNET_HID and 1 <= w.shape[0] <= _lib.FLEXNET_MAX_ACT):
+            return f"agent {i}: hid {w.shape[1]}, act_dim {w.shape[0]}"
+        if not all(p.is_cuda and p.dtype == th.float32 and p.is_contiguous() for p in (w, b)):
+            return f"agent {i}: a parameter is not a contiguous fp32 device tensor"
+    return None
+
+
+def gauss_head_unshared_supported(agents, h):
+    return gauss_head_unshared_declines(agents, h) is None
+
+
+def _gauss_head_unshared_args(rows, n, ws, lo, hi):
+    if not mlp_actor_allowed():
+        raise RuntimeError("flexnet_gauss_head_unshared_* are launched eagerly only (nets.mlp_actor_allowed): never under a capture")
+    a = _lib.FlexGaussHeadUnsharedArgs()
+    a.rows, a.n_agents, a.act_dim, a.hid = rows, n, ws[0].shape[0], ws[0].shape[1]
+    a.log_std_min, a.log_std_max = float(lo), float(hi)
+    for i in range(n):
+        a.w[i] = ws[i].data_ptr()
+    return a
+
+
+class _GaussHeadUnsharedFn(th.autograd.Function):
+    """The log-std heads of per-agent Gaussian agents (RNN or MLP) on the actors' ``h`` [b * n, 64] as ONE node: row r uses agent
+    r % n's head; csrc/gauss.hip's per-agent kernels both ways, and every head's weight and bias gradient — d_u^T h and d_u's
+    column sums over the agent's rows through the row pitch — as the n problems of one flexnet_wgrad_batched call.
+    Bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, h, n_agents, lo, hi, *flat):
+        h = h.contiguous()
+        ws, bs = flat[0::2], flat[1::2]
+        rows, na = h.shape[0], ws[0].shape[0]
+        log_std = th.empty(rows, na, dtype=th.float32, device=h.device)
+        want_t = any(ctx.needs_input_grad)
+        t = th.empty_like(log_std) if want_t else None
+        a = _gauss_head_unshared_args(rows, n_agents, ws, lo, hi)
+        for i in range(n_agents):
+            a.b[i] = bs[i].data_ptr()
+        a.h, a.log_std = h.data_ptr(), log_std.data_ptr()
+        if t is not None:
+            a.t = t.data_ptr()
+        _lib.launch("flexnet_gauss_head_unshared_forward", a)
+        if t is not None:
+            ctx.save_for_backward(h, t, *ws)
+        ctx.n_agents, ctx.lo, ctx.hi = n_agents, float(lo), float(hi)
+        return log_std
+
+    @staticmethod
+    def backward(ctx, d_log_std):
+        h, t = ctx.saved_tensors[:2]
+        ws = ctx.saved_tensors[2:]
+        n, rows, na, dev = ctx.n_agents, t.shape[0], t.shape[1], t.device
+        d_log_std = d_log_std.contiguous()
+        d_u = th.empty_like(t)
+        d_h = th.empty(rows, 64, dtype=th.float32, device=dev) if ctx.needs_input_grad[0] else None
+        a = _gauss_head_unshared_args(rows, n, ws, ctx.lo, ctx.hi)
+        a.d_log_std, a.t, a.d_u = d_log_std.data_ptr(), t.data_ptr(), d_u.data_ptr()
+        if d_h is not None:
+            a.d_h = d_h.data_ptr()
+        _lib.launch("flexnet_gauss_head_unshared_backward", a)
+        dw = th.empty(n, na, 64, dtype=th.float32, device=dev)
+        db = th.empty(n, na, dtype=th.float32, device=dev)
+        b = rows // n
+        du3, h3 = d_u.view(b, n, na), h.detach().view(b, n, 64)
+        tall_wgrad_batched([(du3[:, i], h3[:, i], dw[i], db[i]) for i in range(n)])
+        grads = []
+        for i in range(n):
+            grads += [dw[i], db[i]]
+        return (d_h, None, None, None, *grads)
+
+
+def gauss_log_std_unshared(agents, h):
+    """log_std [b * n, a] of per-agent Gaussian agents on the actors' ``h`` [b * n, 64] (``gauss_head_unshared_supported``
+    holds, ``mlp_actor_allowed()``)."""
+    agents = list(agents)
+    a0 = agents[0].args
+    flat = [p for g in agents for p in (g.log_std.weight, g.log_std.bias)]
+    return _GaussHeadUnsharedFn.apply(h, len(agents), a0.LOG_STD_MIN, a0.LOG_STD_MAX, *flat)
 
 
 def lnrelu_supported(agent, n_agents):

@@ -24,7 +24,7 @@ from torch.optim import RMSprop
 from . import dist as fdist
 from .optim import clip_and_step
 from .replay_buffer import TransReplayBuffer
-from .util import graph_capture, normal_entropy
+from .util import _graph_audit, graph_capture, normal_entropy
 
 train_logger = logging.getLogger("TrainLogger")
 
@@ -615,7 +615,7 @@ class PGTrainer(object):
 
         side = th.cuda.Stream()
         side.wait_stream(th.cuda.current_stream())
-        with th.cuda.stream(side):
+        with th.cuda.stream(side), _graph_audit():   # (the warm-up runs what the capture will run: RolloutGraph.capture)
             for _ in range(2):
                 body()
         th.cuda.current_stream().wait_stream(side)
