@@ -150,7 +150,7 @@ __global__ __launch_bounds__(64 * AW, 1) void actor_forward_kernel(FlexActorArgs
                 const float var = wave_sum(d * d) * (1.0f / HID);               // biased, like nn.LayerNorm
                 z1 = d * rsqrtf(var + a.ln_eps) * s.lnw[lane] + s.lnb[lane];
             }
-            x[r] = fmaxf(z1, 0.0f);
+            x[r] = relu_nan(z1);
             h[r] = a.hidden_in[(int64_t)row[r] * HID + lane];
         }
         // ---- GRUCell (rnn_agent.py:30-31; torch gate order r, z, n) ------------------------------------------
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(64 * AW, 1) void actor_forward_kernel(FlexActorArgs
                 if (a.noise) {                                                    // util.py:57-64, 125-128
                     const float act = tanhf(o + a.std * a.noise[at]);
                     a.action[at] = act;
-                    a.env_action[at] = 0.5f * (fminf(fmaxf(act, a.action_low), a.action_high) + 1.0f) * (a.action_high - a.action_low) + a.action_low;
+                    a.env_action[at] = 0.5f * (clamp_nan(act, a.action_low, a.action_high) + 1.0f) * (a.action_high - a.action_low) + a.action_low;
                 }
             }
         }
@@ -447,7 +447,7 @@ __global__ __launch_bounds__(64 * MW, 2) void actor_forward_mfma_kernel(FlexActo
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
-            for (int i = 0; i < 16; ++i) z1[u][i] = fmaxf(z1[u][i], 0.0f);     // x = ReLU(LayerNorm(z1))
+            for (int i = 0; i < 16; ++i) z1[u][i] = relu_nan(z1[u][i]);     // x = ReLU(LayerNorm(z1))
         if (save) {
 #pragma unroll
             for (int u = 0; u < 2; ++u)
@@ -541,7 +541,7 @@ __global__ __launch_bounds__(64 * MW, 2) void actor_forward_mfma_kernel(FlexActo
                     if (a.action) {                                           // util.py:57-64, 125-128
                         const float act = tanhf(o + a.std * (a.noise ? a.noise[at] : zr[r]));
                         a.action[at] = act;
-                        a.env_action[at] = 0.5f * (fminf(fmaxf(act, a.action_low), a.action_high) + 1.0f) * (a.action_high - a.action_low) + a.action_low;
+                        a.env_action[at] = 0.5f * (clamp_nan(act, a.action_low, a.action_high) + 1.0f) * (a.action_high - a.action_low) + a.action_low;
                     }
                 }
             }

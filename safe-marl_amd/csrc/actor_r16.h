@@ -15,10 +15,17 @@
 #define ASTAMP_C(k) do { } while (0)
 #endif
 
+// ReLU and clamp that hand a NaN on, as torch.relu / torch.clamp do (fmaxf / fminf return the other operand: a NaN observation
+// would come out as a finite action): IEEE 754-2019 maximum / minimum, one v_maximum3_f32 / v_minimum3_f32 each on gfx950.
+// Finite values: the same bits as fmaxf(v, 0) / fminf(fmaxf(v, lo), hi).
+__device__ __forceinline__ float relu_nan(float v) { return __builtin_elementwise_maximum(v, 0.0f); }
+__device__ __forceinline__ float clamp_nan(float v, float lo, float hi) {
+    return __builtin_elementwise_minimum(__builtin_elementwise_maximum(v, lo), hi);
+}
 // v_exp_f32 / v_rcp_f32 forms (about 1 ulp each): sigmoid(x) = 1 / (1 + 2^(-x log2 e)), tanh(x) = 1 - 2 / (2^(2x log2 e) + 1)
 __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * x)); }
 __device__ __forceinline__ float fast_tanh(float x) {
-    const float xc = fminf(fmaxf(x, -15.0f), 15.0f);
+    const float xc = clamp_nan(x, -15.0f, 15.0f);
     return 1.0f - 2.0f * __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(2.88539008f * xc) + 1.0f);
 }
 // Exploration noise drawn in the kernel (FlexActorArgs::rng_state): four standard normal numbers for actions
@@ -107,7 +114,7 @@ __device__ __forceinline__ void r16_ln_relu(f32x4* z, bool layernorm, float eps,
 #pragma unroll
     for (int S = 0; S < 4; ++S)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) z[S][r] = fmaxf(z[S][r], 0.0f);
+        for (int r = 0; r < 4; ++r) z[S][r] = relu_nan(z[S][r]);
 }
 
 // the three gates of output-unit tile T from x and h (16 k-steps, six products), and the new hidden state of those units
@@ -458,7 +465,7 @@ __device__ __forceinline__ void actor_r16_body(FlexActorArgs a, ActorLds16& s) {
                     if (a.action) {                                           // util.py:57-64, 125-128
                         const float act = fast_tanh(o + a.std * (a.noise ? a.noise[at] : zr[r]));     // (~1 ulp, as the gates)
                         a.action[at] = act;
-                        a.env_action[at] = 0.5f * (fminf(fmaxf(act, a.action_low), a.action_high) + 1.0f) * (a.action_high - a.action_low) + a.action_low;
+                        a.env_action[at] = 0.5f * (clamp_nan(act, a.action_low, a.action_high) + 1.0f) * (a.action_high - a.action_low) + a.action_low;
                     }
                 }
             }
@@ -629,7 +636,7 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
                         a.means[at] = o;
                         const float act = fast_tanh(o + a.std * zr[r]);                       // util.py:57-64, 125-128
                         a.action[at] = act;
-                        a.env_action[at] = 0.5f * (fminf(fmaxf(act, a.action_low), a.action_high) + 1.0f) * (a.action_high - a.action_low) + a.action_low;
+                        a.env_action[at] = 0.5f * (clamp_nan(act, a.action_low, a.action_high) + 1.0f) * (a.action_high - a.action_low) + a.action_low;
                     }
                 }
             }

@@ -297,11 +297,16 @@ __device__ __forceinline__ void critic_load_z1(const FlexCriticTailArgs& a, cons
 // LayerNorm of the row (statistics over this lane's 32 units and the other half's 32): v <- xhat, returns rstd
 __device__ __forceinline__ float critic_ln_inplace(cf32x16* v, bool layernorm, float eps) {
     if (!layernorm) return 1.0f;
-    float sum = 0.0f;
+    // pairwise, like the VALU kernels' wave sums: as many additions as a running sum, an error of log2(64) roundings instead of
+    // 63 — and exact on a row whose units are all equal, where rstd = eps^-1/2 multiplies whatever the mean is off by
+    float ps[16];
 #pragma unroll
-    for (int u = 0; u < 2; ++u)
+    for (int i = 0; i < 16; ++i) ps[i] = v[0][i] + v[1][i];
 #pragma unroll
-        for (int i = 0; i < 16; ++i) sum += v[u][i];
+    for (int w = 8; w >= 1; w >>= 1)
+#pragma unroll
+        for (int i = 0; i < w; ++i) ps[i] += ps[i + w];
+    float sum = ps[0];
     sum += __shfl_xor(sum, 32, 64);
     const float mean = sum * (1.0f / HID);
     float var = 0.0f;
@@ -992,11 +997,10 @@ __global__ __launch_bounds__(64 * C16W) void critic_tail_pgrad16_kernel(FlexCrit
         }
         float rstd = 1.0f;
         if (ln) {
-            float sum = 0.0f;
+            float ps[4];                                                       // pairwise: see critic_ln_inplace
 #pragma unroll
-            for (int S = 0; S < 4; ++S)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) sum += xh[S][r];
+            for (int S = 0; S < 4; ++S) ps[S] = (xh[S][0] + xh[S][1]) + (xh[S][2] + xh[S][3]);
+            const float sum = (ps[0] + ps[1]) + (ps[2] + ps[3]);
             const float mean = critic16_group_sum(sum) * (1.0f / HID);
             float var = 0.0f;
 #pragma unroll
