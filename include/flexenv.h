@@ -284,6 +284,42 @@ typedef struct {
 int flexenv_rollout_burst(FlexEnv* env, const FlexActorArgs* actor, double* reward, uint8_t* done,
                           double* info, uint8_t* failed, float* obs_ring, int32_t steps,
                           const FlexBurstSafety* safety /* NULL: plain MADDPG */, void* stream);
+/* One TEST-mode episode per environment (madrl/models/model.py:269-306 for every environment at once) in ONE persistent
+ * launch, with a per-episode record.  Block b owns environments 16 b .. 16 b + 15 as in flexenv_rollout_burst; the launch
+ * starts from the state flexenv_reset leaves and every one of its `steps` steps is
+ *   1. the policy in test mode: tanh(mean) (utils/util.py:79-82), translate_action (util.py:125-128); the observation is read
+ *      in place from the environment's own history, the recurrent state alternates between the two slabs `actor->hidden_in`
+ *      and `actor->hidden_out` ([rows, 64] each, both written; the launch zeroes hidden_in first);
+ *   2. `safety` non-NULL: the safety projection of flexenv_rollout_burst (same arguments, same arithmetic);
+ *      `summed` = 1: the agent-summed selection of matd3.py:92-97 / iddpg.py:66-71 in test mode — the agents' means of an
+ *      environment summed in fp32, left to right, the same tanh and translate_action, the one action handed to every agent;
+ *   3. env.step with the row push (FLEX_STEP_OBS_ROWS), and nothing else.
+ * No noise is drawn: actor->rng_state, noise, cursor, cursor_out and ring_slabs are ignored, the row ring, the replay sink and
+ * the step counter registered with the handle are neither read nor written.  An environment's episode ends with its first
+ * `done` (episode_limit or solver failure) or after `steps` steps; behind its end nothing is accumulated or traced for it (it is
+ * restarted as FLEX_STEP_AUTORESET restarts it and stepped on, for the sake of the environment it shares a wavefront with).
+ * Afterwards the environments hold valid state that the caller resets before using them again.
+ * FLEX_EINVAL (before any HIP call): env, actor, out, out->sums or out->length missing; steps < 1; summed outside {0, 1};
+ * n_agents > 5; summed together with safety; safety with act_dim != 4; actor shapes that are not this environment's, act_dim
+ * != 4, missing policy tensors.  FLEXNET_EUNSUPPORTED (also before any HIP call): shapes the burst's tiles do not hold —
+ * obs_dim > FLEXNET_MAX_OBS or not a multiple of 4, a feeder of more than 32 PQ buses (the kernels are built for a 64-unit
+ * recurrent layer: a caller with another width keeps its loop). */
+typedef struct {
+    double*  sums;     /* [N,10]: info[0..6], reward, steps with voltage_penalty > 0, solver_failed — each summed
+                          over the episode's own steps IN STEP ORDER (fp64, one accumulator per env: no atomics) */
+    int32_t* length;   /* [N]: steps the episode ran (ends on done — episode_limit or solver failure — or at `steps`) */
+    /* optional per-step trace, every pointer may be NULL; row t of an env is written only while its episode is alive */
+    float*   actions;  /* [steps,N,n_agents,4]  what the env step read */
+    double*  v;        /* [steps,N,n_bus] */
+    double*  agent;    /* [steps,N,n_agents,5]  E, PRED, CH, DIS, QPV after the step (the FLEX_PEEK_* fields) */
+    int32_t* row;      /* [steps,N]  data row after the step (FLEX_PEEK ROW) */
+    double*  reward;   /* [steps,N] */
+    double*  info;     /* [steps,N,7] */
+    uint8_t* flags;    /* [steps,N]  bit0 done, bit1 solver_failed, bit2 alive (row valid); the one array written for
+                          EVERY step: 0 behind the episode's end */
+} FlexTestOut;
+int flexenv_test_episodes(FlexEnv* env, const FlexActorArgs* actor, int32_t steps, int32_t summed,
+                          const FlexBurstSafety* safety /* or NULL */, const FlexTestOut* out, void* stream);
 int32_t flexenv_obs_size(const FlexEnv* env);    /* 6*history, env:71 */
 int32_t flexenv_state_size(const FlexEnv* env);  /* env:72 */
 

@@ -538,7 +538,10 @@ __device__ __forceinline__ void r16_stage_simple(const FlexActorArgs& a, ActorLd
     if (tid < ad) s.b2[tid] = a.fc2_b[tid];
 }
 
-template <typename EnvStep, typename Mark>
+// TEST (flexenv_test_episodes): the policy in test mode — tanh(mean) (utils/util.py:79-82), translate_action (util.py:125-128):
+// no noise is drawn and rng_state is not read, no slab ring and no cursor cell: the hidden state alternates between
+// a.hidden_in and a.hidden_out (step 0 reads hidden_in), and env_step is handed the step's index instead of a slab.
+template <bool TEST = false, typename EnvStep, typename Mark>
 __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds16B& s, const int n_steps, EnvStep&& env_step,
                                                 Mark&& mark) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -546,7 +549,7 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
     const int grp = wave >> 2, w = wave & 3;
     const int od = a.obs_dim, na = a.n_agents, ad = a.act_dim;
     const int nq = (od + 15) >> 4;
-    const uint64_t rng_seed = a.rng_state[0], rng_step = a.rng_state[1];
+    const uint64_t rng_seed = TEST ? 0ull : a.rng_state[0], rng_step = TEST ? 0ull : a.rng_state[1];
     // this group's rows, this wavefront's tile
     const int grow0 = (16 * (int)blockIdx.x + 8 * grp) * na;
     const int grows = min(8 * na, a.rows - grow0);                         // (<= 0: a tail block's empty group)
@@ -570,7 +573,7 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
         }
     };
     r16_stage_simple(a, s, tid);
-    if (w == 3) draw(rng_step);
+    if (!TEST && w == 3) draw(rng_step);
     if (tid < 2) s.gsync[tid] = 0;
     __syncthreads();
 
@@ -582,7 +585,7 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
     const float* lnw_l = s.lnw + 4 * g;
     const float* lnb_l = s.lnb + 4 * g;
     const float* w1id_l = s.w1id + (row % na) * HID + 4 * g;
-    int64_t slab = *a.cursor;
+    int64_t slab = TEST ? 0 : *a.cursor;
     int meets = 0;
     // (Both groups start together and drift apart on their own — their steps take different times.  Holding group 1 back
     //  by half a period at the start was measured: the same 31.6 us per step in a long burst, 0.6 us per step more in a
@@ -590,7 +593,9 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
     for (int step = 0; step < n_steps; ++step) {
         mark(12, step);
         if (has_tile) {
-            const float* hid_p = a.hidden_in + slab * a.hid_slab_stride + (int64_t)row * HID + 4 * g;
+            const float* hid_p = (TEST ? ((step & 1) ? a.hidden_out : a.hidden_in) : a.hidden_in + slab * a.hid_slab_stride) +
+                                 (int64_t)row * HID + 4 * g;
+            float* const hid_o = TEST && (step & 1) ? const_cast<float*>(a.hidden_in) : a.hidden_out;
             f32x4 xq[FLEXNET_MAX_OBS / 16], hv[4], x[4], hnew[4];
             {
                 // (the loads of actor_r16_body: whole-slab descriptor, a 16-column group behind obs_dim reads what follows the
@@ -617,7 +622,7 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
             for (int T = 0; T < 4; ++T) {
                 hnew[T] = r16_gru_tile(wg_l, gb_l, T, x, hv);
                 if (live)
-                    *reinterpret_cast<float4*>(a.hidden_out + (int64_t)row * HID + 16 * T + 4 * g) =
+                    *reinterpret_cast<float4*>(hid_o + (int64_t)row * HID + 16 * T + 4 * g) =
                         make_float4(hnew[T][0], hnew[T][1], hnew[T][2], hnew[T][3]);
             }
             f32x4 mo = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
@@ -625,8 +630,11 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
             for (int st = 0; st < 16; ++st)
                 mo = MFMA16(w2_l[(16 * (st >> 2) + (st & 3)) * R16_P2], hnew[st >> 2][st & 3], mo);
             if (live && 4 * g < ad) {
-                const float4 zv = *reinterpret_cast<const float4*>(&s.noise[(rng_step + step) & 1][grp][w][j][4 * g]);
-                const float zr[4] = {zv.x, zv.y, zv.z, zv.w};
+                float zr[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                if constexpr (!TEST) {
+                    const float4 zv = *reinterpret_cast<const float4*>(&s.noise[(rng_step + step) & 1][grp][w][j][4 * g]);
+                    zr[0] = zv.x; zr[1] = zv.y; zr[2] = zv.z; zr[3] = zv.w;
+                }
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int k = 4 * g + r;
@@ -634,13 +642,13 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
                         const float o = mo[r] + s.b2[k];
                         const int64_t at = (int64_t)row * ad + k;
                         a.means[at] = o;
-                        const float act = fast_tanh(o + a.std * zr[r]);                       // util.py:57-64, 125-128
+                        const float act = fast_tanh(TEST ? o : o + a.std * zr[r]);            // util.py:57-64 (TEST: 79-82), 125-128
                         a.action[at] = act;
                         a.env_action[at] = 0.5f * (clamp_nan(act, a.action_low, a.action_high) + 1.0f) * (a.action_high - a.action_low) + a.action_low;
                     }
                 }
             }
-        } else if (w == 3 && step + 1 < n_steps) {
+        } else if (!TEST && w == 3 && step + 1 < n_steps) {
             draw(rng_step + step + 1);                                     // (the other parity: read in the next policy phase)
         }
         // policy outputs (global memory: env action, action, new hidden state) and the noise (LDS) -> the group's other
@@ -649,7 +657,7 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
         ++meets;
         r16_rendezvous(&s.gsync[grp], 4 * meets, lane);
         mark(9, step);
-        env_step(slab);
+        env_step(TEST ? (int64_t)step : slab);
         mark(10, step);
         // ... and the step's outputs (observation, masked hidden state: slab + 1) -> the next policy phase
         ++meets;

@@ -61,6 +61,7 @@ struct FlexEnv {
     int32_t obs_slabs;
     FlexReplaySink sink;         // FLEX_STEP_REPLAY_SINK (flexenv_set_replay_sink)
     int32_t has_sink;
+    double* test_scratch;        // flexenv_test_episodes: [N, 8] doubles (info, reward) + [2, N] bytes (done, failed); first call
 };
 
 // Diagnostic build only (-DFLEX_STAMPS): per-phase s_memtime stamps, lane 0 of each wave, written to a
@@ -1404,6 +1405,141 @@ __global__ void flex_burst_finish_kernel(int64_t* cell0, int64_t* cell1, uint64_
 }
 
 // -------------------------------------------------------------------------------------------------
+// flexenv_test_episodes: one test-mode episode per environment in ONE persistent launch (model.py:269-306 for every
+// environment at once) — the burst above without exploration, replay and cursor cells, with a record of what it did.  Block,
+// groups and hand-overs are the burst's (actor_r16_burst<true>); the environment phase of a step is, per wavefront and for
+// its own two environments:
+//   1. MODE 1: the safety projection (as in the burst).  MODE 2: the agent-summed selection (matd3.py:92-97 / iddpg.py:66-71
+//      in test mode) — the agents' means summed in fp32, left to right, tanh, translate_action, the one action to every agent;
+//   2. flex_step_body with the row push, without restart, its outputs into one row of scratch per environment;
+//   3. the record: lanes 0..9 of an environment's group add the step's ten figures to sums[env] (one lane per cell, plain
+//      load-add-store: step order), lane 0 keeps `length`, the group copies the optional trace rows out of the state the step
+//      left — all of it only while the episode is alive (`alive`, a per-lane flag carried through the launch);
+//   4. an environment whose episode ended (in this step or, already restarted, again) restarts as FLEX_STEP_AUTORESET restarts
+//      it, unless this was the launch's last step: its wavefront goes on for the sake of the other environment.
+// KArgs first: the step body re-reads it through relaunder_kernarg.
+// -------------------------------------------------------------------------------------------------
+struct TestArgs {
+    KArgs k;
+    FlexActorArgs act;
+    int n_steps;
+    int pad0;
+    // one row per environment, rewritten by every step: what flex_step_body stores
+    double* s_reward;           // [N]
+    double* s_info;             // [N, FLEX_INFO_W]
+    uint8_t* s_done;            // [N]
+    uint8_t* s_failed;          // [N]
+    // MODE 1 (FlexBurstSafety, as in BurstArgs)
+    const double* s_p;
+    const double* s_q;
+    const double* beta;
+    double v_min, v_max, rho;
+    double* adjusted;
+    float* safe_env_action;
+    float act_low, act_span;
+    FlexTestOut out;
+};
+
+template <int MODE>
+__device__ __forceinline__ void flex_test_env_step(int step_v, unsigned kbase_lo, unsigned kbase_hi, int& alive) {
+    const unsigned long long kbase = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)kbase_lo) |
+                                     ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)kbase_hi) << 32);
+    const TestArgs& b = *relaunder_kernarg<TestArgs>(kbase);
+    const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * R16_W + (threadIdx.x >> 6));
+    const int t = __builtin_amdgcn_readfirstlane(step_v);
+    const int n_envs = b.k.n_envs;
+    if (2 * wave >= n_envs) return;                                    // (as flex_step_body: a tail block's spare wavefronts)
+    __builtin_amdgcn_s_setprio(3);
+    const int lane = threadIdx.x & 63;
+    const float* actions = b.act.env_action;
+    if constexpr (MODE == 1) {
+        const int na = b.k.cfg.n_agents;
+        const int env = 2 * wave + lane / na;
+        if (lane < 2 * na && env < n_envs)
+            flex_safety_one(b.k, env, lane % na, b.act.action, FLEX_F32, b.s_p, b.s_q, b.beta, b.v_min, b.v_max, b.rho, b.adjusted,
+                            nullptr, b.safe_env_action, b.act_low, b.act_span);
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        actions = b.safe_env_action;
+    }
+    if constexpr (MODE == 2) {
+        // learner._sum_agents: ((m_0 + m_1) + m_2) + ..., fp32; then the policy epilogue's own tanh and translate_action
+        const int na = b.k.cfg.n_agents, ad = b.act.act_dim;            // (ad == 4: checked on the host)
+        const int env = 2 * wave + lane / ad, k = lane % ad;
+        if (lane < 2 * ad && env < n_envs) {
+            const float* m = b.act.means + (int64_t)env * na * ad + k;
+            float sum = m[0];
+            for (int j = 1; j < na; ++j) sum = __fadd_rn(sum, m[(int64_t)j * ad]);
+            const float act = fast_tanh(sum);
+            const float ea = 0.5f * (clamp_nan(act, b.act.action_low, b.act.action_high) + 1.0f) * (b.act.action_high - b.act.action_low) + b.act.action_low;
+            for (int j = 0; j < na; ++j) {
+                b.act.action[((int64_t)env * na + j) * ad + k] = act;
+                b.act.env_action[((int64_t)env * na + j) * ad + k] = ea;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+    flex_step_body<2, float, float, FLEX_OBS_AGENTS_SMALL, false, true>(b.k, wave, actions, b.s_reward, b.s_done, b.s_info, b.s_failed,
+                                                                        nullptr, 1, 0, -1, false, kbase);
+    // (this wavefront's own stores, read back by itself)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    const TestArgs& z = *relaunder_kernarg<TestArgs>(kbase);
+    const int g = lane >> 5, l = lane & 31;
+    const bool valid = 2 * wave + g < n_envs;
+    const int env = valid ? 2 * wave + g : 2 * wave;
+    const int na = z.k.cfg.n_agents, nb = z.k.n_bus;
+    const FlexTestOut& o = z.out;
+    const int done = z.s_done[env], failed = z.s_failed[env];
+    const double vpen = z.s_info[(int64_t)env * FLEX_INFO_W + 5];
+    const double inf_l = z.s_info[(int64_t)env * FLEX_INFO_W + (l < FLEX_INFO_W ? l : 0)];
+    const double rwd = z.s_reward[env];
+    const double val = l < FLEX_INFO_W ? inf_l : l == 7 ? rwd : l == 8 ? (vpen > 0.0 ? 1.0 : 0.0) : (failed ? 1.0 : 0.0);
+    const bool rec = valid && alive != 0;
+    const int64_t te = (int64_t)t * n_envs + env;
+    if (rec) {
+        if (l < 10) { double* const sp = o.sums + (int64_t)env * 10 + l; *sp = *sp + val; }
+        if (l == 0) o.length[env] = t + 1;
+        if (o.actions) for (int i = l; i < 4 * na; i += 32) o.actions[te * 4 * na + i] = actions[(int64_t)env * 4 * na + i];
+        if (o.v) for (int i = l; i < nb; i += 32) o.v[te * nb + i] = z.k.st.vm[(int64_t)env * nb + i];
+        if (o.agent) {
+            const double* const agst = z.k.st.agent + (int64_t)env * agent_rec_doubles(na);
+            for (int i = l; i < 5 * na; i += 32) {
+                const int ag = i / 5, f = i - 5 * ag;                   // E, PRED, CH, DIS, QPV = AF_E .. AF_Q
+                o.agent[te * 5 * na + i] = agst[f * na + ag];
+            }
+        }
+        if (o.info && l < FLEX_INFO_W) o.info[te * FLEX_INFO_W + l] = inf_l;
+        if (l == 0) {
+            if (o.row) o.row[te] = z.k.st.ienv[(int64_t)env * IF_COUNT + IF_ROW];
+            if (o.reward) o.reward[te] = rwd;
+        }
+    }
+    if (valid && l == 0 && o.flags) o.flags[te] = rec ? (uint8_t)(4 | (done ? 1 : 0) | (failed ? 2 : 0)) : (uint8_t)0;
+    if (done) alive = 0;
+    const bool restart = valid && done != 0;
+    if (t + 1 < z.n_steps && __ballot(restart) != 0ull) {               // wavefront-uniform, once per episode
+        LaneNet ln0;
+        load_lane_net<2>(z.k.net, lane, ln0);
+        const DevResetSpec none = {nullptr, nullptr, nullptr, nullptr, nullptr};
+        const TestArgs& ar = *relaunder_kernarg<TestArgs>(kbase);
+        flex_reset_body<2, float>(ar.k, env, restart, ln0, none, nullptr, 1, nullptr, nullptr, true);
+    }
+    __builtin_amdgcn_s_setprio(0);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(64 * R16_W)
+void flex_test_episodes_kernel(TestArgs b) {
+    __shared__ ActorLds16B s;
+    const unsigned long long kb = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
+    int alive = 1;
+    auto env_step = [&](int64_t step) { flex_test_env_step<MODE>((int)step, (unsigned)kb, (unsigned)(kb >> 32), alive); };
+    actor_r16_burst<true>(b.act, s, b.n_steps, env_step, [](int, int) {});
+}
+
+// -------------------------------------------------------------------------------------------------
 // host side
 // -------------------------------------------------------------------------------------------------
 static int build_devnet(const NetFix* nf, int n_agents, DevNet* dn) {
@@ -1677,7 +1813,7 @@ int flexenv_create(const FlexCfg* cfg, const NetFix* net, const SeriesTab* serie
 void flexenv_destroy(FlexEnv* e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
-    void* ptrs[] = {e->net, e->st.vm, e->st.vw, e->st.agent, e->st.cumrew, e->st.ienv, e->st.ring};
+    void* ptrs[] = {e->net, e->st.vm, e->st.vw, e->st.agent, e->st.cumrew, e->st.ienv, e->st.ring, e->test_scratch};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     delete e;
 }
@@ -1877,6 +2013,59 @@ int flexenv_rollout_burst(FlexEnv* e, const FlexActorArgs* actor, double* reward
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(flex_burst_finish_kernel, dim3(1), dim3(64), 0, s, const_cast<int64_t*>(p.cursor), p.cursor_out,
                        e->sink.aux_counter ? const_cast<uint64_t*>(p.rng_state) : nullptr, (int)steps, (int)e->obs_slabs);
+    HIP_TRY(hipGetLastError());
+    return FLEX_OK;
+}
+
+int flexenv_test_episodes(FlexEnv* e, const FlexActorArgs* actor, int32_t steps, int32_t summed, const FlexBurstSafety* safety,
+                          const FlexTestOut* out, void* stream) {
+    // every argument check comes before the first HIP call
+    if (!actor || !out || !out->sums || !out->length || steps < 1 || (summed != 0 && summed != 1)) return FLEX_EINVAL;
+    const FlexActorArgs& p = *actor;
+    if (p.n_agents > 5 || (summed && safety) || (safety && p.act_dim != 4) || !e) return FLEX_EINVAL;
+    const int na = e->cfg.n_agents;
+    if (na > 5) return FLEX_EINVAL;
+    if (safety && (!safety->s_p || !safety->s_q || !safety->beta || !safety->adjusted || !safety->env_action ||
+                   !(safety->act_high >= safety->act_low))) return FLEX_EINVAL;
+    // shapes the burst's policy tiles do not hold (the caller keeps its loop)
+    if (p.obs_dim > FLEXNET_MAX_OBS || (p.obs_dim & 3) || e->hnet.epw != 2) return FLEXNET_EUNSUPPORTED;
+    // the environment step reads four controls per building (env:260)
+    if (p.rows != (int64_t)e->n_envs * na || p.n_agents != na || p.obs_dim != 6 * e->cfg.history || p.act_dim != 4) return FLEX_EINVAL;
+    if (!p.hidden_in || !p.hidden_out || p.hidden_in == p.hidden_out || !p.means || !p.action || !p.env_action ||
+        !p.fc1_w || !p.fc1_b || !p.w_ih || !p.w_hh || !p.b_ih || !p.b_hh || !p.fc2_w || !p.fc2_b ||
+        (p.layernorm && (!p.ln_w || !p.ln_b)) || p.save_z1 || !(p.action_high >= p.action_low)) return FLEX_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t N = e->n_envs;
+    if (!e->test_scratch) {
+        HIP_TRY(hipSetDevice(e->device));
+        HIP_TRY(hipMalloc(&e->test_scratch, N * 8 * sizeof(double) + 2 * N));
+    }
+    TestArgs b;
+    memset(&b, 0, sizeof(b));
+    b.k = make_args(e);                          // no row ring, no sink, no step counter: nothing of the rollout's is touched
+    b.act = p;
+    b.act.rng_state = nullptr; b.act.noise = nullptr; b.act.cursor = nullptr; b.act.cursor_out = nullptr; b.act.ring_slabs = 0;
+    // the policy reads the stacked observation IN PLACE from this environment's history (what flexenv_obs_source hands out)
+    b.act.obs = e->st.ring; b.act.obs_pushed = e->st.ienv + IF_OBSCNT;
+    b.act.obs_row_stride = e->cfg.history * 12; b.act.obs_pushed_stride = IF_COUNT; b.act.obs_slots = e->cfg.history; b.act.obs_slot_w = 6;
+    b.n_steps = (int)steps;
+    b.s_info = e->test_scratch; b.s_reward = e->test_scratch + N * FLEX_INFO_W;
+    b.s_done = reinterpret_cast<uint8_t*>(e->test_scratch + N * 8); b.s_failed = b.s_done + N;
+    b.out = *out;
+    if (safety) {
+        b.s_p = safety->s_p; b.s_q = safety->s_q; b.beta = safety->beta;
+        b.v_min = safety->v_min; b.v_max = safety->v_max; b.rho = safety->penalty;
+        b.adjusted = safety->adjusted; b.safe_env_action = safety->env_action;
+        b.act_low = safety->act_low; b.act_span = safety->act_high - safety->act_low;
+    }
+    // the recurrent state starts at zero (model.py:271), every episode's record at nothing
+    HIP_TRY(hipMemsetAsync(const_cast<float*>(p.hidden_in), 0, (size_t)p.rows * HID * sizeof(float), s));
+    HIP_TRY(hipMemsetAsync(out->sums, 0, (size_t)N * 10 * sizeof(double), s));
+    HIP_TRY(hipMemsetAsync(out->length, 0, (size_t)N * sizeof(int32_t), s));
+    const dim3 grid((e->n_envs + 15) / 16), block(64 * R16_W);
+    if (safety) hipLaunchKernelGGL((flex_test_episodes_kernel<1>), grid, block, 0, s, b);
+    else if (summed) hipLaunchKernelGGL((flex_test_episodes_kernel<2>), grid, block, 0, s, b);
+    else hipLaunchKernelGGL((flex_test_episodes_kernel<0>), grid, block, 0, s, b);
     HIP_TRY(hipGetLastError());
     return FLEX_OK;
 }

@@ -278,23 +278,69 @@ class VecFlexProvisionEnv:
         [N, 4 n] float64 and env_action [N, 4 n] float32 device tensors; act_low, act_high) — safety_project(...,
         env_action_range=...) between policy and step, inside the launch."""
         self.calls += int(steps)
-        sf = None
-        if safety is not None:
-            sf = _lib.FlexBurstSafety()
-            for k in ("s_p", "s_q", "beta", "adjusted", "env_action"):
-                t = safety[k]
-                want = torch.float32 if k == "env_action" else torch.float64
-                if not (t.is_cuda and t.is_contiguous() and t.dtype == want):
-                    raise ValueError(f"rollout_burst safety: {k} must be a contiguous {want} device tensor")
-                setattr(sf, k, t.data_ptr())
-            if safety["adjusted"].numel() != self.n_envs * 4 * self.n_agents or safety["env_action"].numel() != self.n_envs * 4 * self.n_agents:
-                raise ValueError("rollout_burst safety: adjusted / env_action must hold n_envs x 4 n_agents elements")
-            sf.v_min, sf.v_max, sf.penalty = float(safety["v_min"]), float(safety["v_max"]), float(safety.get("penalty", 1000.0))
-            sf.act_low, sf.act_high = float(safety["act_low"]), float(safety["act_high"])
+        sf = self._burst_safety(safety, "rollout_burst") if safety is not None else None
         _lib.check(self.lib.flexenv_rollout_burst(self.handle, C.byref(actor_args), _ptr(self.reward), _ptr(self.done),
                                                   _ptr(self.info), _ptr(self.failed), _ptr(obs_ring), int(steps),
                                                   C.byref(sf) if sf is not None else None, _stream()),
                    "flexenv_rollout_burst")
+
+    TEST_TRACE = (("actions", torch.float32), ("v", torch.float64), ("agent", torch.float64), ("row", torch.int32),
+                  ("reward", torch.float64), ("info", torch.float64), ("flags", torch.uint8))
+
+    def test_out(self, steps, trace=False):
+        """The record ``test_episodes`` fills: ``sums`` [N, 10] fp64 and ``length`` [N] int32, with ``trace`` also the per-step
+        arrays of include/flexenv.h FlexTestOut (zero-filled: rows behind an episode's end are never written)."""
+        N, na, dev = self.n_envs, self.n_agents, self.device
+        out = dict(sums=torch.zeros(N, 10, dtype=torch.float64, device=dev), length=torch.zeros(N, dtype=torch.int32, device=dev))
+        if trace:
+            shapes = dict(actions=(steps, N, na, 4), v=(steps, N, self.n_bus), agent=(steps, N, na, 5), row=(steps, N),
+                          reward=(steps, N), info=(steps, N, _lib.FLEX_INFO_W), flags=(steps, N))
+            for k, dt in self.TEST_TRACE:
+                out[k] = torch.zeros(shapes[k], dtype=dt, device=dev)
+        return out
+
+    def test_episodes(self, actor_args, steps, summed=False, safety=None, out=None):
+        """One TEST-mode episode per environment — policy (tanh(mean), no noise), optional safety projection or agent-summed
+        selection, environment step — for ``steps`` steps in ONE launch (include/flexenv.h: flexenv_test_episodes), from the
+        state ``reset`` left.  ``actor_args``: the FlexActorArgs of the policy (nets.fused_actor_forward builds it; hidden_in
+        and hidden_out are the two slabs the recurrent state alternates between).  ``safety``: as in ``rollout_burst``.
+        ``out``: ``test_out(steps, trace)`` (default: no trace).  Returns ``out``, or None where the library declines the shape
+        (FLEXNET_EUNSUPPORTED).  The environments are left to be reset by the caller."""
+        steps = int(steps)
+        if out is None:
+            out = self.test_out(steps)
+        rec = _lib.FlexTestOut()
+        want = dict(self.TEST_TRACE, sums=torch.float64, length=torch.int32)
+        per_step = dict(actions=4 * self.n_agents, v=self.n_bus, agent=5 * self.n_agents, row=1, reward=1, info=_lib.FLEX_INFO_W, flags=1)
+        for k, t in out.items():
+            if k not in want:
+                raise ValueError(f"test_episodes: unknown record field {k!r}")
+            n = self.n_envs * (10 if k == "sums" else 1 if k == "length" else steps * per_step[k])
+            if not (t.device == self.device and t.is_contiguous() and t.dtype == want[k] and t.numel() == n):
+                raise ValueError(f"test_episodes: {k} must be a contiguous {want[k]} device tensor of {n} elements")
+            setattr(rec, k, t.data_ptr())
+        sf = self._burst_safety(safety, "test_episodes") if safety is not None else None
+        rc = self.lib.flexenv_test_episodes(self.handle, C.byref(actor_args), steps, int(bool(summed)),
+                                            C.byref(sf) if sf is not None else None, C.byref(rec), _stream())
+        if rc == _lib.FLEXNET_EUNSUPPORTED:
+            return None
+        _lib.check(rc, "flexenv_test_episodes")
+        self.calls += steps
+        return out
+
+    def _burst_safety(self, safety, what):
+        sf = _lib.FlexBurstSafety()
+        for k in ("s_p", "s_q", "beta", "adjusted", "env_action"):
+            t = safety[k]
+            want = torch.float32 if k == "env_action" else torch.float64
+            if not (t.is_cuda and t.is_contiguous() and t.dtype == want):
+                raise ValueError(f"{what} safety: {k} must be a contiguous {want} device tensor")
+            setattr(sf, k, t.data_ptr())
+        if safety["adjusted"].numel() != self.n_envs * 4 * self.n_agents or safety["env_action"].numel() != self.n_envs * 4 * self.n_agents:
+            raise ValueError(f"{what} safety: adjusted / env_action must hold n_envs x 4 n_agents elements")
+        sf.v_min, sf.v_max, sf.penalty = float(safety["v_min"]), float(safety["v_max"]), float(safety.get("penalty", 1000.0))
+        sf.act_low, sf.act_high = float(safety["act_low"]), float(safety["act_high"])
+        return sf
 
     def set_step_counter(self, counter, modulo=0):
         """Every later step() adds 1 to ``counter[0]`` (int64 device tensor, or None to switch it off) from inside the

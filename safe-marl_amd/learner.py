@@ -493,6 +493,70 @@ class _GraphSafe:
         return self.value if obj is None else bool(self.value and obj.args.shared_params)
 
 
+def episode_stats(sums, length):
+    """The reference's ``mean_test_*`` keys from per-episode sums, as model.py:285-306 forms them: every figure summed over an
+    episode's steps, divided by THAT episode's length ``t + 1``, then averaged over the episodes (accumulated in episode order,
+    as the reference's loop does).  ``sums`` [N, 10]: info[0..6] (``_lib.INFO_KEYS``), reward, steps with voltage_penalty > 0,
+    solver_failed; ``length`` [N].  ``mean_test_reward`` is the reference's: its running sum takes info["reward"] AND the
+    step's reward (model.py:286-290: the info key collides with the reward's own), so it is their sum — ``evaluate_on``
+    reports the step reward alone.  Besides the reference's keys: ``mean_test_violation_rate`` (share of an episode's steps with
+    any bus voltage outside its band) and ``mean_test_solver_failed``."""
+    from ._lib import INFO_KEYS
+    sums = np.asarray(sums, dtype=np.float64).reshape(-1, 10)
+    length = np.asarray(length).reshape(-1)
+    if sums.shape[0] != length.shape[0] or sums.shape[0] < 1 or (length < 1).any():
+        raise ValueError("episode_stats: sums [N, 10] and length [N] >= 1 of the same N >= 1 episodes")
+    per = sums / length.astype(np.float64)[:, None]                  # model.py:297-298
+    per[:, 7] = (sums[:, 0] + sums[:, 7]) / length                   # model.py:286-290
+    mean = np.cumsum(per, axis=0)[-1] / float(sums.shape[0])         # model.py:299-305, in episode order
+    stat = {"mean_test_" + k: float(mean[i]) for i, k in enumerate(INFO_KEYS) if k != "reward"}
+    stat["mean_test_reward"] = float(mean[7])
+    stat["mean_test_violation_rate"] = float(mean[8])
+    stat["mean_test_solver_failed"] = float(mean[9])
+    return stat
+
+
+def one_launch_declines(model):
+    """None where ``Model.test_episodes`` may take the single launch (flexenv_test_episodes), else the reason — decided from the
+    model's class and arguments alone, whatever the device."""
+    args = model.args
+    if not args.shared_params:
+        return "shared_params is False: the launch stages one shared actor"
+    if args.agent_type != "rnn" or not isinstance(model.policy_dicts[0], RNNAgent):
+        return f"agent_type {args.agent_type}: the launch holds the RNN actor's tiles"
+    if args.hid_size != 64 or args.hid_activation != "relu":
+        return f"hid_size {args.hid_size} / hid_activation {args.hid_activation}: the tiles are built for 64 relu units"
+    if model.obs_dim > 144 or model.obs_dim % 4:
+        return f"obs_size {model.obs_dim}: the tiles hold up to 144 columns, a multiple of 4"
+    if model.n_ > 5:
+        return f"{model.n_} agents: a block's policy tiles hold sixteen environments of at most 5"
+    if model.act_dim != 4:
+        return f"action_dim {model.act_dim}: the environment step reads four controls per building"
+    if not args.action_enforcebound:
+        return "action_enforcebound is False: the launch's test mode is tanh(mean)"
+    own = type(model).get_actions
+    if own is SAFEMADDPG.get_actions:
+        return "SAFEMADDPG with intended_actions: that routing is not in the launch" if model.intended_actions else None
+    if own is MADDPG.get_actions or own is MATD3.get_actions or own is IDDPG.get_actions:
+        return None
+    return f"{type(model).__name__}.get_actions is none of MADDPG's, SAFEMADDPG's, MATD3's or IDDPG's"
+
+
+class TestEpisodes:
+    """What ``Model.test_episodes`` returns: ``sums`` [N, 10] and ``length`` [N] (NumPy), ``trace`` (dict of NumPy arrays, or
+    None), ``launch`` (True: the single launch ran; False: the loop) and ``stat()``."""
+    __test__ = False               # (not a pytest class)
+
+    def __init__(self, out, first, launch):
+        host = {k: v.cpu().numpy() for k, v in {**out, **first}.items()}
+        self.sums, self.length = host.pop("sums"), host.pop("length")
+        self.trace = host or None
+        self.launch = bool(launch)
+
+    def stat(self):
+        return episode_stats(self.sums, self.length)
+
+
 class Model(nn.Module):
     """model.py:10-323, the parts the MADDPG path uses."""
 
@@ -1077,8 +1141,15 @@ class Model(nn.Module):
         for k, v in stat_test.items():
             stat[k] = v / float(self.args.num_eval_episodes)
 
+    # a caller's switch: the periodic evaluation of a vectorised trainer as per-episode statistics (test_episodes below, the
+    # reference's own arithmetic: model.py:285-306) instead of evaluate_on's means over env-steps
+    one_launch_eval = False
+
     def _evaluation_vec(self, stat, trainer):
-        stat.update(self.evaluate_on(trainer.env))
+        if self.one_launch_eval:
+            stat.update(self.test_episodes(trainer.env).stat())
+        else:
+            stat.update(self.evaluate_on(trainer.env))
 
     def evaluate_on(self, env, spec=None):
         """model.py:269-306 on every environment of ``env`` (a VecFlexProvisionEnv, not necessarily the trainer's): one
@@ -1140,6 +1211,125 @@ class Model(nn.Module):
         stat["mean_test_violation_rate"] = float(vals[-2])
         stat["mean_test_solver_failed"] = float(vals[-1])
         return stat
+
+    def test_episodes(self, env, spec=None, trace=False, one_launch=None, steps=None):
+        """One test-mode episode per environment of ``env`` (model.py:269-306: tanh(mean), no exploration) with a record PER
+        EPISODE: ``.sums`` [N, 10] (info[0..6], reward, steps with voltage_penalty > 0, solver_failed, each summed over the
+        episode's own steps in step order), ``.length`` [N] (an episode ends with its first ``done`` or after ``steps`` steps,
+        default min(max_steps, episode_limit - 1)), ``.stat()`` (``episode_stats``) and, with ``trace``, ``.trace``: the per-step
+        arrays of include/flexenv.h FlexTestOut plus ``v0`` / ``agent0`` / ``row0``, the state the reset left.  Nothing is
+        accumulated or traced for an environment behind its episode's end; ``env`` is left to be reset by the caller.
+        ``one_launch``: None takes the single launch (flexenv_test_episodes) where ``one_launch_declines`` has no objection and
+        the tensors are on the GPU, else the loop; False the loop; True raises ValueError with the reason where it declines.
+        ``spec``: injected episode draws, as in ``evaluate_on``."""
+        vec = env.vec if hasattr(env, "vec") else env
+        why = one_launch_declines(self)
+        if why is None and not vec.obs.is_cuda:
+            why = "the environment is not on a GPU"
+        if one_launch and why is not None:
+            raise ValueError("test_episodes(one_launch=True): " + why)
+        steps = min(self.args.max_steps, vec.episode_limit - 1) if steps is None else int(steps)
+        if steps < 1:
+            raise ValueError("steps must be >= 1")
+        bound = self.__dict__.get("env", None)
+        rebind = bound is not None and (bound.vec if hasattr(bound, "vec") else bound) is not vec
+        if rebind:                    # SAFEMADDPG projects against the env it is bound to (safemaddpg.py:143-172)
+            self.__dict__["env"] = vec
+        try:
+            with th.no_grad():
+                res = None
+                if why is None and one_launch is not False:
+                    res = self._test_episodes_launch(vec, spec, trace, steps)
+                    if res is None and one_launch:
+                        raise ValueError("test_episodes(one_launch=True): the library declined the shape")
+                if res is None:
+                    res = self._test_episodes_loop(vec, spec, trace, steps)
+                return res
+        finally:
+            if rebind:
+                self.__dict__["env"] = bound
+
+    def _test_snapshot(self, vec, trace):
+        if not trace:
+            return {}
+        return dict(v0=vec.peek("V"), row0=vec.peek("ROW"),
+                    agent0=th.stack([vec.peek(f) for f in ("E", "PRED", "CH", "DIS", "QPV")], dim=-1))
+
+    def _fused_test_policy(self):
+        """Where test mode is the actor kernel's epilogue with a zero standard deviation (what _evaluate_on takes for MADDPG);
+        SAFEMADDPG's reference routing puts the safety launch behind the same call."""
+        own = type(self).get_actions
+        safe = own is SAFEMADDPG.get_actions and not self.intended_actions and self.act_dim == 4
+        return ((own is MADDPG.get_actions or safe) and self.fused_eval and self.fused_inference and self.args.shared_params
+                and self.args.agent_type == "rnn" and self.hid_dim == 64 and self.obs_dim <= 144
+                and bool(self.args.action_enforcebound)), safe
+
+    def _test_episodes_loop(self, vec, spec, trace, steps):
+        """The loop form of test_episodes: every algorithm, agent type and shared_params value; the launch's record, step by step."""
+        N, n, a = vec.n_envs, self.n_, self.act_dim
+        obs = vec.reset(spec=spec)
+        out = vec.test_out(steps, trace)
+        first = self._test_snapshot(vec, trace)
+        fused, safe = self._fused_test_policy()
+        fused = fused and obs.is_cuda
+        last_hid = th.zeros(N, n, self.hid_dim, device=self.device)
+        avail = th.ones(N, n, a, device=self.device)
+        zero_noise = th.zeros(N, n, a, device=self.device) if fused else None
+        alive = th.ones(N, dtype=th.bool, device=self.device)
+        for t in range(steps):
+            res = fused_actor_forward(self.policy_dicts[0], obs, last_hid, n, self.args.agent_id, noise=zero_noise, std=0.0,
+                                      low=self.args.action_low, high=self.args.action_high) if fused else None
+            if res is not None and safe:
+                hid = res[1].view(N, n, -1)
+                actual = vec.safety_project(res[2].view(N, n, a), *self.predictor, self.V_min, self.V_max,
+                                            env_action_range=(self.args.action_low, self.args.action_high),
+                                            want_hit=False)[2].view(N, n, a)
+            elif res is not None:
+                hid, actual = res[1].view(N, n, -1), res[3].view(N, n, a)
+            else:
+                action, _, _, _, hid = self.get_actions(obs, status="test", exploration=False, actions_avail=avail,
+                                                        target=False, last_hid=last_hid)
+                actual = self.env_action(action).to(th.float32).contiguous()
+            reward, done, info = vec.step(actual, fuse_obs=True)
+            failed = vec.failed
+            col = alive.view(N, 1)
+            fig = th.cat([info, reward.view(N, 1), (info[:, 5:6] > 0).double(), failed.view(N, 1).double()], dim=1)
+            out["sums"] += th.where(col, fig, th.zeros_like(fig))
+            out["length"] += alive.to(th.int32)
+            if trace:
+                flags = 4 + (done != 0).to(th.uint8) + 2 * (failed != 0).to(th.uint8)
+                agent = th.stack([vec.peek(f) for f in ("E", "PRED", "CH", "DIS", "QPV")], dim=-1)
+                for k, val in (("actions", actual.reshape(N, n, 4)), ("v", vec.peek("V")), ("agent", agent), ("row", vec.peek("ROW")),
+                               ("reward", reward), ("info", info), ("flags", flags)):
+                    dst = out[k][t]
+                    dst.copy_(th.where(alive.view([N] + [1] * (dst.dim() - 1)), val, th.zeros_like(dst)))
+            alive = alive & (done == 0)
+            obs, last_hid = vec.obs, hid
+        return TestEpisodes(out, first, launch=False)
+
+    def _test_episodes_launch(self, vec, spec, trace, steps):
+        """flexenv_test_episodes on the model's shared RNN actor; None where the library declines the shape."""
+        N, n, a = vec.n_envs, self.n_, self.act_dim
+        obs = vec.reset(spec=spec)                 # (pushes every first observation: the launch reads the history in place)
+        out = vec.test_out(steps, trace)
+        first = self._test_snapshot(vec, trace)
+        own = type(self).get_actions
+        safety = None
+        if own is SAFEMADDPG.get_actions:
+            s_p, s_q, beta = (th.as_tensor(x, dtype=th.float64, device=vec.device).contiguous() for x in self.predictor)
+            safety = dict(s_p=s_p, s_q=s_q, beta=beta, v_min=self.V_min, v_max=self.V_max,
+                          adjusted=th.empty(N, 4 * n, dtype=th.float64, device=vec.device),
+                          env_action=th.empty(N, 4 * n, dtype=th.float32, device=vec.device),
+                          act_low=self.args.action_low, act_high=self.args.action_high)
+        summed = own is MATD3.get_actions or own is IDDPG.get_actions
+        done = []
+        res = fused_actor_forward(self.policy_dicts[0], obs.view(N, n, -1), th.zeros(N * n, 64, device=vec.device), n,
+                                  self.args.agent_id, noise=th.zeros(N, n, a, device=vec.device), std=0.0,
+                                  low=self.args.action_low, high=self.args.action_high,
+                                  launch=lambda args: done.append(vec.test_episodes(args, steps, summed=summed, safety=safety, out=out)))
+        if res is None or not done or done[0] is None:
+            return None
+        return TestEpisodes(out, first, launch=True)
 
 
 class MADDPG(Model):

@@ -16,6 +16,27 @@ RECORD_KEYS = ("pv_active", "pv_reactive", "bus_active", "bus_reactive", "bus_vo
                "power_reduction", "ess_charging", "ess_discharging", "price")
 
 
+def record_from_trace(trace, series_rows):
+    """The record of ``PGTester.run`` on a vectorised env from the trace of ``Model.test_episodes(trace=True)``: ``RECORD_KEYS``
+    plus ``actions``, the reset entry plus one entry per step (``actions``: one per step), every entry with the leading
+    environment axis ``_run_vec`` gives it.  ``series_rows`` [steps + 1, N, cols]: the series table's rows at ``row0`` and at
+    every traced ``row`` ([Pd(n_bus) | Qd(n_bus) | Ppv(n_agents) | price]).  Entries behind an environment's episode end hold
+    what the trace holds there: zeros."""
+    v = np.concatenate([trace["v0"][None], trace["v"]], axis=0)                    # [steps + 1, N, n_bus]
+    agent = np.concatenate([trace["agent0"][None], trace["agent"]], axis=0)        # [steps + 1, N, n_agents, 5]: E, PRED, CH, DIS, QPV
+    series_rows = np.asarray(series_rows)
+    nb, na = v.shape[2], agent.shape[2]
+    if series_rows.shape != (v.shape[0], v.shape[1], 2 * nb + na + 1):
+        raise ValueError(f"series_rows must be [steps + 1, N, {2 * nb + na + 1}], got {series_rows.shape}")
+    whole = {"bus_active": series_rows[:, :, :nb], "bus_reactive": series_rows[:, :, nb:2 * nb],
+             "pv_active": series_rows[:, :, 2 * nb:2 * nb + na], "price": series_rows[:, :, 2 * nb + na:],
+             "bus_voltage": v, "ess_energy": agent[..., 0], "power_reduction": agent[..., 1], "ess_charging": agent[..., 2],
+             "ess_discharging": agent[..., 3], "pv_reactive": agent[..., 4]}
+    record = {k: [np.ascontiguousarray(x) for x in whole[k]] for k in RECORD_KEYS}
+    record["actions"] = [np.ascontiguousarray(x) for x in trace["actions"]]
+    return record
+
+
 class PGTester(object):
     def __init__(self, args, behaviour_net, env):
         self.args, self.env = args, env
@@ -89,7 +110,25 @@ class PGTester(object):
             obs, last_hid = v.obs.clone(), hid
         return record
 
-    def run(self, day, hour, quarter, **spec):
+    def _run_vec_traced(self, day, hour, quarter, e0=None, a0=None):
+        """``_run_vec`` from the trace of ``Model.test_episodes``: one launch where the model is eligible, no host copy per
+        step either way, and ONE gather of the series table by the traced rows at the end."""
+        v = self.env
+        N = v.n_envs
+        spec = dict(day=np.broadcast_to(np.asarray(day, np.int32), (N,)).copy(),
+                    hour=np.broadcast_to(np.asarray(hour, np.int32), (N,)).copy(),
+                    interval=np.broadcast_to(np.asarray(quarter, np.int32), (N,)).copy(), e0=e0, a0=a0)
+        res = self.behaviour_net.test_episodes(v, spec=spec, trace=True)
+        tr = res.trace
+        rows = np.concatenate([tr["row0"][None], tr["row"]], axis=0)              # [steps + 1, N]
+        idx = th.as_tensor(rows.reshape(-1), device=v.series_dev.device).long()
+        series_rows = v.series_dev.index_select(0, idx).cpu().numpy().reshape(rows.shape + (-1,))
+        return record_from_trace(tr, series_rows)
+
+    def run(self, day, hour, quarter, one_launch=False, **spec):
+        """``one_launch`` (vectorised env only): the record from ``Model.test_episodes``' trace instead of the stepping loop."""
         if hasattr(self.env, "handle"):
+            if one_launch:
+                return self._run_vec_traced(day, hour, quarter, **spec)
             return self._run_vec(day, hour, quarter, **spec)
         return self._run_single(day, hour, quarter)

@@ -51,6 +51,9 @@ def parse():
     ap.add_argument("--opf-days", type=int, default=32, help="evaluation episodes handed to the OPF comparator")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--lr", type=float, default=None, help="override policy_lrate / value_lrate (default.yaml: 1e-4)")
+    ap.add_argument("--one-launch", action="store_true",
+                    help="evaluate with Model.test_episodes (one launch per evaluation where the model is eligible; per-episode "
+                         "means, model.py:285-306) instead of evaluate_on's loop")
     ap.add_argument("--out", default=None)
     return ap.parse_args()
 
@@ -109,8 +112,17 @@ def main():
     out = {"what": "evaluation curves on fixed episodes: mean per env-step over %d episodes x 95 steps, test mode "
                    "(tanh(mean), util.py:79-82)" % a.eval_envs,
            "data": "synthetic (stand-in IEEE-33 Baran-Wu network, generated series; SURVEY.md App. C, §8d)",
-           "load_scale": a.load_scale, "episodes": a.episodes, "eval_freq": a.eval_freq, "eval_envs": a.eval_envs, "seed": a.seed,
+           "one_launch": bool(a.one_launch), "load_scale": a.load_scale, "episodes": a.episodes, "eval_freq": a.eval_freq, "eval_envs": a.eval_envs, "seed": a.seed,
            "lr": a.lr if a.lr is not None else DEFAULT_ALG_ARGS["policy_lrate"], "runs": []}
+
+    def evaluate(model, ev):
+        if not a.one_launch:
+            return strip(model.evaluate_on(ev, spec))
+        res = model.test_episodes(ev, spec)
+        stat = res.stat()
+        # (the curve's "reward" stays the step reward alone, as evaluate_on reports it: episode_stats' key is the reference's sum)
+        stat["mean_test_reward"] = float(np.mean(res.sums[:, 7] / res.length))
+        return strip(stat)
 
     def gradient_steps(args, steps):
         events = sum(1 for st in range(steps) if st > 0 and st % args.behaviour_update_freq == 0)
@@ -140,7 +152,7 @@ def main():
         train_s = 0.0
         for ep in range(a.episodes + 1):
             if ep % a.eval_freq == 0 or ep == a.episodes:
-                e = strip(tr.behaviour_net.evaluate_on(ev, spec))
+                e = evaluate(tr.behaviour_net, ev)
                 e.update(episode=ep, vector_steps=tr.steps, gradient_steps=gradient_steps(args, tr.steps))
                 run["curve"].append(e)
                 print(f"[{alg_label} x{envs} bs={bs}] ep {ep:4d} test reward {e['reward']:+.5f} rev {e['revenue']:.5f} der {e['der_cost']:+.5f} "
@@ -188,7 +200,7 @@ def main():
         import io
         for ep in range(episodes + 1):
             if ep % a.eval_freq == 0 or ep == episodes:
-                e = strip(tr.behaviour_net.evaluate_on(ev, spec))
+                e = evaluate(tr.behaviour_net, ev)
                 e.update(episode=ep, vector_steps=tr.steps, gradient_steps=gradient_steps(args, tr.steps))
                 run["curve"].append(e)
                 print(f"[maddpg N=1] ep {ep:4d} test reward {e['reward']:+.5f} rev {e['revenue']:.5f} der {e['der_cost']:+.5f} "
