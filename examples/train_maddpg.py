@@ -55,10 +55,15 @@ PPO_ALG_ARGS = dict(policy_lrate=1.0e-4, value_lrate=1.0e-4, value_update_epochs
 COMA_ALG_ARGS = dict(policy_lrate=1.0e-4, value_lrate=1.0e-4, sample_size=10, gaussian_policy=False,
                      action_enforcebound=True)
 
+# alg_args/maac.yaml over the defaults above: soft actor-critic with ONE attention critic for all agents (csrc/attn_critic.hip);
+# off-policy with transition replay, an update event every 60 vector steps like MADDPG
+MAAC_ALG_ARGS = dict(policy_lrate=1.0e-4, value_lrate=1.0e-4, attend_heads=1, norm_in=False, soft=True, reward_scale=100,
+                     gaussian_policy=True, action_enforcebound=True)
+
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--alg", choices=["maddpg", "safemaddpg", "matd3", "iddpg", "facmaddpg", "sqddpg", "ippo", "mappo", "coma"],
+    ap.add_argument("--alg", choices=["maddpg", "safemaddpg", "matd3", "iddpg", "facmaddpg", "sqddpg", "ippo", "mappo", "coma", "maac"],
                     default="maddpg")
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--episodes", type=int, default=3)
@@ -77,7 +82,7 @@ def main():
     import torch
     import safe_marl_amd  # noqa: F401
     from safe_marl_amd.flex_env import VecFlexProvisionEnv
-    from safe_marl_amd.learner import COMA, FACMADDPG, IDDPG, IPPO, MADDPG, MAPPO, MATD3, SAFEMADDPG, SQDDPG
+    from safe_marl_amd.learner import COMA, FACMADDPG, IDDPG, IPPO, MAAC, MADDPG, MAPPO, MATD3, SAFEMADDPG, SQDDPG
     from safe_marl_amd.network import create_network
     from safe_marl_amd.series import make_synthetic_series
     from safe_marl_amd.trainer import PGTrainer
@@ -109,6 +114,8 @@ def main():
         alg.update(PPO_ALG_ARGS)
     if a.alg == "coma":
         alg.update(COMA_ALG_ARGS)
+    if a.alg == "maac":
+        alg.update(MAAC_ALG_ARGS)
     if a.gaussian_policy:
         alg.update(gaussian_policy=True)
     if a.agent_type != "rnn":
@@ -121,7 +128,7 @@ def main():
     torch.manual_seed(0)
     trainer = PGTrainer(args, {"maddpg": MADDPG, "safemaddpg": SAFEMADDPG, "matd3": MATD3, "iddpg": IDDPG,
                                  "facmaddpg": FACMADDPG, "sqddpg": SQDDPG, "ippo": IPPO, "mappo": MAPPO,
-                                 "coma": COMA}[a.alg], env, None,
+                                 "coma": COMA, "maac": MAAC}[a.alg], env, None,
                         batch_scale=a.batch_scale,
                         # (on-policy: the trainer's default holds what is collected between two update events)
                         replay_capacity=None if a.alg in ("ippo", "mappo", "coma") else a.envs * 96 * 2)
@@ -141,7 +148,7 @@ def main():
     if rank == 0:
         out = {"metric": "training env-steps/s (rollout + replay + MADDPG updates)", "alg": a.alg,
                "value": a.envs * world * steps / dt, "unit": "env-steps/s", "n_gpus": world, "envs_per_gpu": a.envs,
-               "gaussian_policy": bool(a.gaussian_policy), "n_agents": env.n_agents, "vector_steps": steps, "ms_per_vector_step": dt / steps * 1e3,
+               "gaussian_policy": bool(args.gaussian_policy), "n_agents": env.n_agents, "vector_steps": steps, "ms_per_vector_step": dt / steps * 1e3,
                "batch": trainer.effective_batch_size(),
                "grad_steps": int(steps // args.behaviour_update_freq) * (args.value_update_epochs + args.policy_update_epochs
                                                                          + (args.mixer_update_epochs if args.mixer else 0)),

@@ -1234,6 +1234,111 @@ int flexnet_gauss_head_unshared_backward(const FlexGaussHeadUnsharedArgs* args, 
  * untouched.  Same checks and return codes; d_hn NULL: FLEXNET_EINVAL.  Launched eagerly only. */
 int flexnet_actor_unshared_backward_hn(const FlexActorUnsharedBwdArgs* args, const float* d_hn, void* stream);
 
+/* ---- MAAC: the attention critic (madrl/critics/maac_critic.py:86-159, continuous branch; csrc/attn_critic.hip) ----------------
+ * ONE critic for all agents: per agent j an encoder of [o_j | a_j] (enc: [64, obs_dim + act_dim]), a state encoder of o_j
+ * (senc: [64, obs_dim]), a critic head on [sa_j | other_j] (c1: [64, 128], c2: [1, 64]) and a bias head on s_j (b1: [64, 64],
+ * b2: [1, 64]), all with LeakyReLU(0.01), through per-agent pointer tables; the key, selector and value extractors of the one
+ * attention head ([64, 64]; the value extractor with a bias) are shared.  obs is [b, n, obs_dim], act [b, n, act_dim], both
+ * contiguous and never concatenated; row s * n_agents + j of the [b n, 64] tensors is agent j of sample s.  One wavefront owns
+ * 32 samples with all their agents on v_mfma_f32_32x32x2_f32 (exact fp32).
+ * forward: q [b, n] = critic_i - bias_i, and reg [n] = 1e-3 * mean over (samples, other agents) of the UNSCALED logits squared,
+ *         through one partial per wavefront and agent in `workspace` (>= ceil(b / 32) * n floats) and a second launch that sums
+ *         them in index order: no atomics, bit-reproducible.  sa, key, val are staging tensors the launch always writes (and
+ *         the backward reads); the six save_* are all set or all NULL, and q / reg are the same bits either way.
+ * backward: from dq [b, n] and what the forward left.  param_grads = 1: the gradients at the seven pre-activations, [b n, 64]
+ *         each — dz_sa (encoder), dz_s (state encoder), d_key, d_sel, dz_v (extractors), dz_c (critic fc1), dz_b (bias fc1) —
+ *         for flexnet_wgrad_batched, whose column sums are the [64] bias gradients, and d_c2_b / d_b2_b [n] = +- the sum of dq
+ *         over the samples (one fp64 partial per wavefront in `workspace`, summed in a fixed order by a second launch); actions take
+ *         no gradient.  param_grads = 0:
+ *         d_act [b, n, act_dim] alone (the critic frozen).  g_direct, g_other [b n, 64] and g_dl [b, n, n] are scratch.  The
+ *         regulariser takes no backward.
+ * n_agents 2..FLEXNET_MAX_AGENTS, obs_dim <= FLEXNET_MAX_OBS and a multiple of 4, act_dim <= FLEXNET_MAX_ACT, b <=
+ * FLEXNET_ATTN_CRITIC_MAX_BATCH, hid 64, fp32, the [b n, 64] tensors and every [64, 64] / [64, 128] weight 16-byte aligned; else
+ * FLEXNET_EUNSUPPORTED.  Missing tensors, some saves without the others, a short workspace: FLEXNET_EINVAL.  Both before any
+ * HIP call.  Launched eagerly only (never on a capturing stream). */
+#define FLEXNET_ATTN_CRITIC_MAX_BATCH (1 << 24)
+typedef struct {
+    int64_t batch;             /* b */
+    int32_t n_agents;
+    int32_t obs_dim;
+    int32_t act_dim;
+    int32_t pad0;
+    const float* obs;          /* [b, n, obs_dim] */
+    const float* act;          /* [b, n, act_dim] */
+    const float* enc_w[FLEXNET_MAX_AGENTS];    /* per agent: [64, obs_dim + act_dim] */
+    const float* enc_b[FLEXNET_MAX_AGENTS];    /* [64] */
+    const float* senc_w[FLEXNET_MAX_AGENTS];   /* [64, obs_dim] */
+    const float* senc_b[FLEXNET_MAX_AGENTS];
+    const float* c1_w[FLEXNET_MAX_AGENTS];     /* [64, 128] */
+    const float* c1_b[FLEXNET_MAX_AGENTS];
+    const float* c2_w[FLEXNET_MAX_AGENTS];     /* [1, 64] */
+    const float* c2_b[FLEXNET_MAX_AGENTS];     /* [1] */
+    const float* b1_w[FLEXNET_MAX_AGENTS];     /* [64, 64] */
+    const float* b1_b[FLEXNET_MAX_AGENTS];
+    const float* b2_w[FLEXNET_MAX_AGENTS];     /* [1, 64] */
+    const float* b2_b[FLEXNET_MAX_AGENTS];     /* [1] */
+    const float* key_w;        /* [64, 64] */
+    const float* sel_w;
+    const float* val_w;
+    const float* val_b;        /* [64] */
+    float* sa;                 /* out [b n, 64]: staging, always written */
+    float* key;
+    float* val;
+    float* q;                  /* out [b, n] */
+    float* reg;                /* out [n] */
+    float* save_s;             /* out [b n, 64] each, and save_w [b, n, n]: all six or none */
+    float* save_sel;
+    float* save_other;
+    float* save_hc;
+    float* save_hb;
+    float* save_w;
+    float* workspace;
+    int64_t workspace_floats;  /* >= ceil(b / 32) * n_agents */
+} FlexAttnCriticArgs;
+
+typedef struct {
+    int64_t batch;
+    int32_t n_agents;
+    int32_t obs_dim;
+    int32_t act_dim;
+    int32_t param_grads;       /* 1: the seven pre-activation gradients; 0: d_act alone */
+    const float* dq;           /* [b, n] */
+    const float* sa;           /* the forward's staging tensors and saves */
+    const float* key;
+    const float* val;
+    const float* s;            /* (param_grads) */
+    const float* sel;
+    const float* hc;
+    const float* hb;           /* (param_grads) */
+    const float* w;            /* [b, n, n] */
+    const float* enc_w[FLEXNET_MAX_AGENTS];
+    const float* c1_w[FLEXNET_MAX_AGENTS];
+    const float* c2_w[FLEXNET_MAX_AGENTS];
+    const float* b1_w[FLEXNET_MAX_AGENTS];     /* (param_grads) */
+    const float* b2_w[FLEXNET_MAX_AGENTS];     /* (param_grads) */
+    const float* key_w;
+    const float* sel_w;        /* (param_grads) */
+    const float* val_w;
+    float* g_direct;           /* scratch [b n, 64] */
+    float* g_other;            /* scratch [b n, 64] */
+    float* g_dl;               /* scratch [b, n, n] */
+    float* dz_c;               /* out [b n, 64] each (param_grads) */
+    float* dz_b;
+    float* dz_s;
+    float* d_sel;
+    float* d_key;
+    float* dz_v;
+    float* dz_sa;
+    float* d_act;              /* out [b, n, act_dim] (param_grads == 0) */
+    float* d_c2_b;             /* out [n] each (param_grads): the bias gradients of critic_fc2 and bias_fc2, +- sum_b dq */
+    float* d_b2_b;
+    float* workspace;          /* (param_grads) 8-byte aligned: it holds doubles */
+    int64_t workspace_floats;  /* >= 2 * ceil(b / 32) * n_agents */
+} FlexAttnCriticBwdArgs;
+
+int flexnet_attn_critic_forward(const FlexAttnCriticArgs* args, void* stream);
+int flexnet_attn_critic_backward(const FlexAttnCriticBwdArgs* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

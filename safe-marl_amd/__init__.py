@@ -1,7 +1,7 @@
 """MI355X-native flexibility-provision environment + safe-MADDPG hot path.
 
 Drop-in surface (same names as the reference):
-    FlexibilityProvisionEnv, TransReplayBuffer, PGTrainer, MADDPG, SAFEMADDPG (and MATD3, IDDPG, FACMADDPG, SQDDPG, IPPO, MAPPO, COMA)
+    FlexibilityProvisionEnv, TransReplayBuffer, PGTrainer, MADDPG, SAFEMADDPG (and MATD3, IDDPG, FACMADDPG, SQDDPG, IPPO, MAPPO, COMA, MAAC)
 plus the batched device objects they are built on (VecFlexProvisionEnv, ...).
 """
 from .network import create_network, build_tables, NetTables          # noqa: F401
@@ -16,7 +16,7 @@ def __getattr__(name):
     if name in ("TransReplayBuffer", "DeviceReplayBuffer"):
         from . import replay_buffer
         return getattr(replay_buffer, name)
-    if name in ("MADDPG", "SAFEMADDPG", "MATD3", "IDDPG", "FACMADDPG", "SQDDPG", "IPPO", "MAPPO", "COMA", "Model"):
+    if name in ("MADDPG", "SAFEMADDPG", "MATD3", "IDDPG", "FACMADDPG", "SQDDPG", "IPPO", "MAPPO", "COMA", "MAAC", "Model"):
         from . import learner
         return getattr(learner, name)
     if name == "PGTrainer":

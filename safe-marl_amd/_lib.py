@@ -87,6 +87,7 @@ SYMBOLS = (
     "flexnet_actor_mlp_forward", "flexnet_actor_mlp_backward",
     "flexnet_actor_mlp_unshared_forward", "flexnet_actor_mlp_unshared_backward",
     "flexnet_gauss_head_unshared_forward", "flexnet_gauss_head_unshared_backward", "flexnet_actor_unshared_backward_hn",
+    "flexnet_attn_critic_forward", "flexnet_attn_critic_backward",
     "flexopf_qp_work_doubles", "flexopf_qp_solve",
 )
 
@@ -475,6 +476,30 @@ class FlexWindowRefreshArgs(C.Structure):
                 ("reward_job", C.c_int32), ("pad0", C.c_int32)]
 
 
+FLEXNET_ATTN_CRITIC_MAX_BATCH = 1 << 24
+
+
+class FlexAttnCriticArgs(C.Structure):
+    """include/flexnet.h: MAAC's attention critic, forward (csrc/attn_critic.hip)"""
+    _fields_ = [("batch", C.c_int64)] + [(k, C.c_int32) for k in ("n_agents", "obs_dim", "act_dim", "pad0")] + \
+               [("obs", C.c_void_p), ("act", C.c_void_p)] + \
+               [(k, _AgentPtrs) for k in ("enc_w", "enc_b", "senc_w", "senc_b", "c1_w", "c1_b", "c2_w", "c2_b", "b1_w", "b1_b",
+                                          "b2_w", "b2_b")] + \
+               [(k, C.c_void_p) for k in ("key_w", "sel_w", "val_w", "val_b", "sa", "key", "val", "q", "reg", "save_s", "save_sel",
+                                          "save_other", "save_hc", "save_hb", "save_w", "workspace")] + \
+               [("workspace_floats", C.c_int64)]
+
+
+class FlexAttnCriticBwdArgs(C.Structure):
+    """include/flexnet.h"""
+    _fields_ = [("batch", C.c_int64)] + [(k, C.c_int32) for k in ("n_agents", "obs_dim", "act_dim", "param_grads")] + \
+               [(k, C.c_void_p) for k in ("dq", "sa", "key", "val", "s", "sel", "hc", "hb", "w")] + \
+               [(k, _AgentPtrs) for k in ("enc_w", "c1_w", "c2_w", "b1_w", "b2_w")] + \
+               [(k, C.c_void_p) for k in ("key_w", "sel_w", "val_w", "g_direct", "g_other", "g_dl", "dz_c", "dz_b", "dz_s", "d_sel",
+                                          "d_key", "dz_v", "dz_sa", "d_act", "d_c2_b", "d_b2_b", "workspace")] + \
+               [("workspace_floats", C.c_int64)]
+
+
 FLEXNET_EUNSUPPORTED = -3
 FLEXNET_HID, FLEXNET_MAX_AGENTS, FLEXNET_MAX_ACT = 64, 8, 8
 
@@ -574,6 +599,10 @@ def load():
         fn.restype = C.c_int
     lib.flexnet_actor_unshared_backward_hn.argtypes = [C.POINTER(FlexActorUnsharedBwdArgs), vp, vp]
     lib.flexnet_actor_unshared_backward_hn.restype = C.c_int
+    lib.flexnet_attn_critic_forward.argtypes = [C.POINTER(FlexAttnCriticArgs), vp]
+    lib.flexnet_attn_critic_forward.restype = C.c_int
+    lib.flexnet_attn_critic_backward.argtypes = [C.POINTER(FlexAttnCriticBwdArgs), vp]
+    lib.flexnet_attn_critic_backward.restype = C.c_int
     lib.flexnet_clip_rmsprop.argtypes = [C.POINTER(FlexClipRmspropArgs), vp]
     lib.flexnet_clip_rmsprop.restype = C.c_int
     lib.flexnet_clip_rmsprop_refresh.argtypes = [C.POINTER(FlexClipRmspropArgs), C.POINTER(FlexWindowRefreshArgs), C.POINTER(FlexTdLossArgs), vp]

@@ -21,7 +21,7 @@ import numpy as np
 import torch as th
 import torch.nn as nn
 
-from .nets import (WGRAD_MIN_ROWS, CriticTail, critic_first_layer, critic_td_loss, critic_td_loss_supported, critic_policy_loss,
+from .nets import (WGRAD_MIN_ROWS, AttentionCritic, attn_critic, CriticTail, critic_first_layer, critic_td_loss, critic_td_loss_supported, critic_policy_loss,
                    critic_policy_loss_supported, expand_agents, MLPAgent, MLPAgentGaussian, MLPCritic, RNNAgent, RNNAgentGaussian, critic_policy_supported, critic_replayed_supported,
                    critic_tail_supported, fused_actor_forward, fused_actor_forward_unshared, actor_unshared_supported,
                    actor_mlp_declines, actor_mlp_train, fused_actor_forward_mlp, mlp_actor_allowed,
@@ -2357,3 +2357,154 @@ class COMA(Model):
             terms.update(values=values.detach(), next_values=next_values, returns=returns)
         self.last_terms = terms          # (tests and tools read the intermediates of the last call)
         return policy_loss, value_loss, action_out
+
+
+def _sum_last(x):
+    """x.sum(dim=-1) over the (small) action axis as pointwise adds, like ``_sum_agents``: the same numbers up to fp32 summation
+    order, and no ATen reduce_kernel in a captured rollout graph."""
+    parts = x.unbind(-1)
+    out = parts[0]
+    for p in parts[1:]:
+        out = out + p
+    return out
+
+
+class MAAC(Model):
+    """madrl/models/maac.py:9-119 (continuous branch): soft actor-critic with ONE attention critic for all agents
+    (nets.AttentionCritic, whatever ``shared_params`` says) and the Gaussian agents of ``agent_type``; ``gaussian_policy`` is
+    forced, as alg_args/maac.yaml does.  Off-policy with transition replay, like MADDPG.
+
+    The reference's quirks are kept: both action selections of ``get_loss`` explore, the next actions come from the TARGET
+    policy, the agent-summed means and log-stds give ONE action and one log-density per sample that every agent shares
+    (maac.py:70-80 — unlike IDDPG's the means are not masked), the TD target carries the ``soft`` / ``reward_scale`` entropy
+    term, and the attention regulariser is added to the POLICY loss only — whose optimiser holds no critic parameter, so the
+    regulariser never moves anything and is formed without a graph outside ``need="both"``.
+
+    On the GPU the critic is csrc/attn_critic.hip through ``nets.attn_critic`` (eager calls only); elsewhere, and for
+    ``need="both"`` — the reference's single call — the tensor composition."""
+
+    graph_safe_updates = False       # sub-updates run eagerly
+    noise_source = None              # tests: callable(role, shape) -> the standard-normal draw of "behaviour" / "target"
+
+    def __init__(self, args, target_net=None):
+        if not args.gaussian_policy:
+            args = args._replace(gaussian_policy=True)
+        super().__init__(args)
+        if not args.continuous:
+            raise NotImplementedError("discrete control is outside the flexibility-provision hot path")
+        self.build_nets(target_net)
+        self.batchnorm = nn.BatchNorm1d(self.args.agent_num).to(self.device)      # maac.py:16
+        self.last_terms = {}
+
+    def construct_value_net(self):
+        """maac.py:38-39"""
+        self.value_dicts = nn.ModuleList([AttentionCritic(self.args)])
+
+    def update_target(self):
+        """model.py:28-38; with norm_in the critic holds BatchNorm counters, which are copied."""
+        if not self.args.norm_in:
+            return super().update_target()
+        with th.no_grad():
+            for k in ("policy_dicts", "value_dicts"):
+                src = getattr(self, k).state_dict()
+                for name, t in getattr(self.target_net, k).state_dict().items():
+                    if t.is_floating_point():
+                        t.mul_(1 - self.args.target_lr).add_(src[name], alpha=self.args.target_lr)
+                    else:
+                        t.copy_(src[name])
+
+    # -- critic ---------------------------------------------------------------------------------------------------------
+    def critic(self, obs, act, critic_frozen=False, composed=False):
+        """(q - b [b, n], regulariser [n]) of the attention critic.  ``critic_frozen``: the caller differentiates w.r.t. the
+        actions only and the regulariser comes back detached; ``composed``: the tensor composition whatever the device."""
+        net = self.value_dicts[0]
+        if composed or not self.fused_inference:
+            return net(obs, act)
+        return attn_critic(net, obs, act, critic_frozen=critic_frozen)
+
+    def value(self, obs, act, critic_frozen=False):
+        """maac.py:45-64: [b + 1, n] — the values, and the regulariser as the last row."""
+        q, reg = self.critic(obs, act, critic_frozen)
+        return th.cat((q, reg.view(1, -1)), dim=0)
+
+    # -- actions --------------------------------------------------------------------------------------------------------
+    def _explore(self, means, log_stds, role):
+        """util.py:56-64 on a recorded draw: Normal.rsample is loc + eps * scale."""
+        from torch.distributions.normal import Normal
+        std = log_stds.exp()
+        eps = self.noise_source(role, tuple(means.shape)).to(means.device, means.dtype)
+        x_t = means + eps * std
+        y_t = th.tanh(x_t)
+        return y_t, Normal(means, std, validate_args=False).log_prob(x_t) - th.log(1 - y_t.pow(2) + 1e-6)
+
+    def get_actions(self, state, status, exploration, actions_avail, target=False, last_hid=None):
+        """maac.py:66-90 (continuous branch): actions [b, 1, a], restored actions [b, n, a], log_prob_a [b, n]."""
+        pol = self.target_net.policy if (target and self.args.target) else self.policy
+        means, log_stds, hiddens = pol(state, last_hid=last_hid)
+        if means.size(-1) > 1:
+            means_, log_stds_ = _sum_agents(means), _sum_agents(log_stds)
+        else:
+            means_, log_stds_ = means, log_stds
+        if (self.noise_source is not None and status == "train" and exploration and self.args.action_enforcebound):
+            actions, log_prob_a = self._explore(means_, log_stds_, "target" if target else "behaviour")
+        else:
+            actions, log_prob_a = select_action(self.args, means_, status=status, exploration=exploration,
+                                                info={"log_std": log_stds_})
+        if getattr(actions_avail, "_flex_const", None) == 1.0 and actions.size(1) == 1:
+            # every action available (env:721-730): the mask is 1
+            restore_actions = expand_agents(actions, self.n_)
+            if log_prob_a is not None:
+                log_prob_a = _sum_last(log_prob_a).expand(-1, self.n_)
+        else:
+            restore_mask = 1.0 - (actions_avail.to(means.device) == 0).float()
+            if log_prob_a is not None:
+                log_prob_a = _sum_last(restore_mask * log_prob_a)
+            restore_actions = restore_mask * actions
+        return actions, restore_actions, log_prob_a, (means, log_stds), hiddens
+
+    # -- loss -----------------------------------------------------------------------------------------------------------
+    def get_loss(self, batch, need="both"):
+        """maac.py:92-119 -> (policy_loss, value_loss, (means, log_stds)).  ``need`` = "value": the value loss alone — the
+        behaviour policy's draw still enters the TD target through its log-density, without a graph: only the value
+        optimiser's parameters take this loss's gradient; "policy": the policy loss with the critic frozen and the regulariser
+        from a pass without a graph; "both": the reference's call, one graph through everything, on the composition."""
+        args, n = self.args, self.n_
+        batch = self._tensor_batch(batch)
+        state, actions, _, _, _, rewards, next_state, done, _, actions_avail, last_hids, hids = self.unpack_data(batch)
+        both = need == "both"
+        tgt = self.target_net if args.target else self
+        terms = {}
+        policy_loss = value_loss = action_out = None
+        with th.set_grad_enabled(th.is_grad_enabled() and need != "value"):
+            _, actions_pol, log_prob_a, action_out, _ = self.get_actions(
+                state, status="train", exploration=True, actions_avail=actions_avail, target=False, last_hid=last_hids)
+        terms["log_prob_a"] = log_prob_a.detach()
+        if need in ("both", "value"):
+            with th.no_grad():
+                _, next_actions, _, _, _ = self.get_actions(next_state, status="train", exploration=True,
+                                                            actions_avail=actions_avail, target=True, last_hid=hids)
+                next_values = tgt.critic(next_state, next_actions, composed=both)[0]
+        if both:
+            values, attn_reg = self.critic(state, actions.detach(), composed=True)
+        elif need == "value":
+            values, attn_reg = self.critic(state, actions.detach())
+        else:
+            with th.no_grad():
+                attn_reg = self.critic(state, actions.detach())[1]
+        terms["attn_reg"] = attn_reg.detach()
+        if need in ("both", "policy"):
+            advantages = self.critic(state, actions_pol, critic_frozen=not both, composed=both)[0]
+            if args.normalize_advantages:
+                advantages = self.batchnorm(advantages)
+            if args.soft:
+                policy_loss = log_prob_a / args.reward_scale - advantages
+            else:
+                policy_loss = -advantages.detach() * log_prob_a
+            policy_loss = mean_all(policy_loss + attn_reg)
+        if need in ("both", "value"):
+            assert values.size() == next_values.size() == log_prob_a.size()
+            returns = rewards + args.gamma * (1 - done) * next_values.detach() - args.soft * log_prob_a / args.reward_scale
+            value_loss = mean_all((returns - values).pow(2))
+            terms.update(values=values.detach(), next_values=next_values, returns=returns.detach())
+        self.last_terms = terms          # (tests and tools read the intermediates of the last call)
+        return policy_loss, value_loss, (action_out if need != "value" else None)

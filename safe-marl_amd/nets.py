@@ -3295,3 +3295,311 @@ def coma_policy_loss(means, log_stds, actions, actions_avail, values=None, basel
     adv = advantages if advantages is not None else values - baseline
     loss, logp = coma_policy_loss_torch(means, log_stds, actions, actions_avail, adv.reshape(rows, n))
     return loss, logp.detach()
+
+
+# ---- MAAC: the attention critic (madrl/critics/maac_critic.py; csrc/attn_critic.hip) ----------------------------------------
+class AttentionCritic(nn.Module):
+    """madrl/critics/maac_critic.py:6-159 (continuous branch): ONE critic for all agents.  Per agent an encoder of
+    [o_j | a_j], an encoder of o_i, a critic head on [sa_i | other_i] and a bias head on s_i; shared key, selector and value
+    extractors per attention head.  Agent i attends over the other n - 1 agents: logits sel_i . key_j, scaled by
+    1 / sqrt(attend_dim), softmax, other_i = sum_j w_ij val_j.  The state_dict keys are the reference's.
+
+    ``forward(obs [b, n, o], act [b, n, a])`` -> (q - b [b, n], regulariser [n]): the regulariser is 1e-3 times the sum over
+    heads of the mean of the UNSCALED logits squared (maac_critic.py:125-134, 154).  ``pre``: a list that receives every
+    LeakyReLU pre-activation, [b, n, .] each (tests clear the samples where one of them ties at zero)."""
+
+    def __init__(self, args):
+        super().__init__()
+        self.args = args
+        self.hidden_dim, self.attend_heads, self.nagents = args.hid_size, args.attend_heads, args.agent_num
+        assert self.hidden_dim % self.attend_heads == 0
+        if not args.continuous:
+            raise NotImplementedError("discrete control is outside the flexibility-provision hot path")
+        sdim, adim, hid = args.obs_size, args.action_dim, self.hidden_dim
+        self.norm_in = bool(args.norm_in)
+        self.critic_encoders, self.critics = nn.ModuleList(), nn.ModuleList()
+        self.biases, self.state_encoders = nn.ModuleList(), nn.ModuleList()
+        for _ in range(self.nagents):
+            enc = nn.Sequential()
+            if self.norm_in:
+                enc.add_module("enc_bn", nn.BatchNorm1d(sdim + adim, affine=False))
+            enc.add_module("enc_fc1", nn.Linear(sdim + adim, hid))
+            enc.add_module("enc_nl", nn.LeakyReLU())
+            self.critic_encoders.append(enc)
+            critic = nn.Sequential()
+            critic.add_module("critic_fc1", nn.Linear(2 * hid, hid))
+            critic.add_module("critic_nl", nn.LeakyReLU())
+            critic.add_module("critic_fc2", nn.Linear(hid, 1))
+            self.critics.append(critic)
+            bias = nn.Sequential()
+            bias.add_module("bias_fc1", nn.Linear(hid, hid))
+            bias.add_module("bias_nl", nn.LeakyReLU())
+            bias.add_module("bias_fc2", nn.Linear(hid, 1))
+            self.biases.append(bias)
+            senc = nn.Sequential()
+            if self.norm_in:
+                senc.add_module("s_enc_bn", nn.BatchNorm1d(sdim, affine=False))
+            senc.add_module("s_enc_fc1", nn.Linear(sdim, hid))
+            senc.add_module("s_enc_nl", nn.LeakyReLU())
+            self.state_encoders.append(senc)
+        attend_dim = hid // self.attend_heads
+        self.key_extractors, self.selector_extractors, self.value_extractors = nn.ModuleList(), nn.ModuleList(), nn.ModuleList()
+        for _ in range(self.attend_heads):
+            self.key_extractors.append(nn.Linear(hid, attend_dim, bias=False))
+            self.selector_extractors.append(nn.Linear(hid, attend_dim, bias=False))
+            self.value_extractors.append(nn.Sequential(nn.Linear(hid, attend_dim), nn.LeakyReLU()))
+
+    def forward(self, obs, act, pre=None):
+        n = self.nagents
+        sa_in = th.cat((obs, act), dim=-1)
+        lrelu = F.leaky_relu
+
+        def first(seq, x, bn, fc):
+            if self.norm_in:
+                x = getattr(seq, bn)(x)
+            return getattr(seq, fc)(x)
+
+        z_sa = th.stack([first(e, sa_in[:, j], "enc_bn", "enc_fc1") for j, e in enumerate(self.critic_encoders)], dim=1)
+        z_s = th.stack([first(e, obs[:, i], "s_enc_bn", "s_enc_fc1") for i, e in enumerate(self.state_encoders)], dim=1)
+        sa, s = lrelu(z_sa), lrelu(z_s)                                              # [b, n, hid]
+        diag = th.eye(n, dtype=th.bool, device=obs.device)
+        others, reg, z_vals = [], 0.0, []
+        for k_ext, s_ext, v_ext in zip(self.key_extractors, self.selector_extractors, self.value_extractors):
+            keys, sels, z_v = k_ext(sa), s_ext(s), v_ext[0](sa)                      # [b, n, d]
+            z_vals.append(z_v)
+            logits = th.matmul(sels, keys.transpose(1, 2))                           # [b, i, j]
+            reg = reg + logits.masked_fill(diag, 0.0).pow(2).sum(dim=(0, 2)) / (logits.shape[0] * (n - 1))
+            w = (logits / math.sqrt(keys.shape[-1])).masked_fill(diag, float("-inf")).softmax(dim=-1)
+            others.append(th.matmul(w, lrelu(z_v)))
+        critic_in = th.cat([sa] + others, dim=-1)
+        z_c = th.stack([c.critic_fc1(critic_in[:, i]) for i, c in enumerate(self.critics)], dim=1)
+        z_b = th.stack([m.bias_fc1(s[:, i]) for i, m in enumerate(self.biases)], dim=1)
+        q = th.cat([c.critic_fc2(lrelu(z_c[:, i])) for i, c in enumerate(self.critics)], dim=1)
+        bb = th.cat([m.bias_fc2(lrelu(z_b[:, i])) for i, m in enumerate(self.biases)], dim=1)
+        if pre is not None:
+            pre += [z_sa, z_s, z_c, z_b] + z_vals
+        return q - bb, 1e-3 * reg
+
+
+_ATTN_CRITIC_TABLES = ("enc_w", "enc_b", "senc_w", "senc_b", "c1_w", "c1_b", "c2_w", "c2_b", "b1_w", "b1_b", "b2_w", "b2_b")
+_ATTN_CRITIC_SHARED = ("key_w", "sel_w", "val_w", "val_b")
+# call classes that take csrc/attn_critic.hip by default (DESIGN.md §4.6j: each is gated by its own measurement);
+# FLEX_ATTN_CRITIC_FUSED=0: none does — the A/B switch of tools/maac_bench.py and profiles/maac_bench.txt
+ATTN_CRITIC_FUSED = {k: os.environ.get("FLEX_ATTN_CRITIC_FUSED", "1") != "0" for k in ("no_grad", "value", "policy")}
+
+
+def _attn_critic_params(critic):
+    """The parameters of an AttentionCritic in FlexAttnCriticArgs order: twelve per agent, then the four shared ones."""
+    flat = []
+    for e, se, c, bm in zip(critic.critic_encoders, critic.state_encoders, critic.critics, critic.biases):
+        flat += [e.enc_fc1.weight, e.enc_fc1.bias, se.s_enc_fc1.weight, se.s_enc_fc1.bias, c.critic_fc1.weight, c.critic_fc1.bias,
+                 c.critic_fc2.weight, c.critic_fc2.bias, bm.bias_fc1.weight, bm.bias_fc1.bias, bm.bias_fc2.weight, bm.bias_fc2.bias]
+    v = critic.value_extractors[0][0]
+    return flat + [critic.key_extractors[0].weight, critic.selector_extractors[0].weight, v.weight, v.bias]
+
+
+def attn_critic_declines(critic, obs, act):
+    """Why csrc/attn_critic.hip does not cover ``critic`` on obs [b, n, o] / act [b, n, a], or None."""
+    if type(critic) is not AttentionCritic:
+        return f"a {type(critic).__name__}"
+    n = critic.nagents
+    if critic.attend_heads != 1 or critic.norm_in or critic.hidden_dim != _lib.FLEXNET_HID:
+        return f"attend_heads {critic.attend_heads}, norm_in {critic.norm_in}, hid {critic.hidden_dim}"
+    for name, t in (("obs", obs), ("act", act)):
+        if not (t.is_cuda and t.dtype == th.float32 and t.dim() == 3 and t.shape[1] == n and t.shape[0] == obs.shape[0]):
+            return f"{name} {tuple(t.shape)} {t.dtype} on {t.device.type} for {n} agents"
+    b, _, o = obs.shape
+    a = act.shape[2]
+    if not (2 <= n <= _lib.FLEXNET_MAX_AGENTS and 1 <= o <= _lib.FLEXNET_MAX_OBS and o % 4 == 0 and 1 <= a <= _lib.FLEXNET_MAX_ACT
+            and o == critic.args.obs_size and a == critic.args.action_dim):
+        return f"agents {n}, obs {o}, actions {a}"
+    if not 1 <= b <= _lib.FLEXNET_ATTN_CRITIC_MAX_BATCH:
+        return f"{b} samples"
+    if not getattr(critic, "fused", True):
+        return "fused passes switched off"
+    for p in _attn_critic_params(critic):
+        if not (p.is_cuda and p.dtype == th.float32 and p.is_contiguous()):
+            return "a parameter is not a contiguous fp32 device tensor"
+    return None
+
+
+def _attn_critic_tables(k, flat, n):
+    names = {f[0] for f in k._fields_}
+    for c, name in enumerate(_ATTN_CRITIC_TABLES):
+        if name in names:
+            table = getattr(k, name)
+            for i in range(n):
+                table[i] = flat[12 * i + c].data_ptr()
+    for c, name in enumerate(_ATTN_CRITIC_SHARED):
+        if name in names:
+            setattr(k, name, flat[12 * n + c].data_ptr())
+
+
+def _attn_critic_eager_only():
+    if not mlp_actor_allowed():
+        raise RuntimeError("csrc/attn_critic.hip is launched eagerly only (nets.mlp_actor_allowed): never under a capture")
+
+
+def _attn_critic_launch_forward(flat, obs, act, saves=None):
+    """One flexnet_attn_critic_forward call on contiguous obs [b, n, o] / act [b, n, a]: (q [b, n], reg [n], stage [3, b n, 64]
+    = sa | key | val), or None when the library answers FLEXNET_EUNSUPPORTED.  ``saves`` = (five [5, b n, 64], w [b, n, n])."""
+    _attn_critic_eager_only()
+    b, n, o = obs.shape
+    dev = obs.device
+    stage = th.empty(3, b * n, 64, dtype=th.float32, device=dev)
+    q = th.empty(b, n, dtype=th.float32, device=dev)
+    reg = th.empty(n, dtype=th.float32, device=dev)
+    ws = th.empty(((b + 31) // 32) * n, dtype=th.float32, device=dev)
+    k = _lib.FlexAttnCriticArgs()
+    k.batch, k.n_agents, k.obs_dim, k.act_dim = b, n, o, act.shape[2]
+    k.obs, k.act = obs.data_ptr(), act.data_ptr()
+    _attn_critic_tables(k, flat, n)
+    k.sa, k.key, k.val = (stage[c].data_ptr() for c in range(3))
+    k.q, k.reg, k.workspace, k.workspace_floats = q.data_ptr(), reg.data_ptr(), ws.data_ptr(), ws.numel()
+    if saves is not None:
+        five, w = saves
+        k.save_s, k.save_sel, k.save_other, k.save_hc, k.save_hb = (five[c].data_ptr() for c in range(5))
+        k.save_w = w.data_ptr()
+    if not _lib.try_launch("flexnet_attn_critic_forward", k):
+        return None
+    return q, reg, stage
+
+
+def fused_attn_critic_forward(critic, obs, act):
+    """maac_critic.py:86-159 without an autograd graph in ONE launch (and the regulariser's small second one) at any batch
+    size: (q - b [b, n], regulariser [n]), or None after ``note_fallback("maac", ...)`` when it declines on GPU tensors.
+    Never called under a capture (``mlp_actor_allowed``)."""
+    why = attn_critic_declines(critic, obs, act)
+    if why is not None:
+        if obs.is_cuda:
+            note_fallback("maac", why)
+        return None
+    with th.no_grad():
+        out = _attn_critic_launch_forward(_attn_critic_params(critic), obs.contiguous(), act.contiguous())
+    if out is None:
+        note_fallback("maac", "FLEXNET_EUNSUPPORTED from flexnet_attn_critic_forward")
+        return None
+    return out[0], out[1]
+
+
+class _AttnCriticFn(th.autograd.Function):
+    """The attention critic for an update batch as ONE autograd node (csrc/attn_critic.hip): the fused forward with its saves
+    and one backward launch.  ``param_grads`` (the value sub-update; the actions carry no gradient): the gradients at the seven
+    pre-activations, then flexnet_wgrad_batched for every weight — per agent the encoder's observation and action blocks, the
+    state encoder, the critic head's two blocks and the bias head's first layer over the agent's rows through the row pitch,
+    the two [1, 64] output layers against dq's column, and K, Q, V over all b n rows — with the [64] bias gradients as the
+    column sums of the same passes; the output layers' bias gradients, +- the sum of dq, come from the backward launch.  Without (the policy sub-update, critic frozen): d_act alone.  The regulariser is returned
+    detached: no optimiser ever steps a parameter on it.  Bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, obs, act, param_grads, *flat):
+        b, n, _ = obs.shape
+        obs, act = obs.contiguous(), act.contiguous()
+        five = th.empty(5, b * n, 64, dtype=th.float32, device=obs.device)             # s | sel | other | hc | hb
+        w = th.empty(b, n, n, dtype=th.float32, device=obs.device)
+        out = _attn_critic_launch_forward(flat, obs, act, (five, w))
+        if out is None:
+            _lib.check(_lib.FLEXNET_EUNSUPPORTED, "flexnet_attn_critic_forward")
+        q, reg, stage = out
+        ctx.param_grads = bool(param_grads)
+        ctx.save_for_backward(obs, act, stage, five, w, *flat)
+        ctx.mark_non_differentiable(reg)
+        ctx.set_materialize_grads(False)
+        return q, reg
+
+    @staticmethod
+    def backward(ctx, dq, _dreg):
+        obs, act, stage, five, w = ctx.saved_tensors[:5]
+        flat = ctx.saved_tensors[5:]
+        b, n, o = obs.shape
+        a = act.shape[2]
+        none = (None,) * (3 + len(flat))
+        if dq is None:
+            return none
+        _attn_critic_eager_only()
+        dev, rows = obs.device, b * n
+        pg = ctx.param_grads and any(ctx.needs_input_grad[3:])
+        want_act = ctx.needs_input_grad[1]
+        dq = dq.contiguous()
+        scratch = th.empty(2, rows, 64, dtype=th.float32, device=dev)
+        g_dl = th.empty(b, n, n, dtype=th.float32, device=dev)
+
+        def args(param_grads):
+            k = _lib.FlexAttnCriticBwdArgs()
+            k.batch, k.n_agents, k.obs_dim, k.act_dim, k.param_grads = b, n, o, a, int(param_grads)
+            k.dq, k.w = dq.data_ptr(), w.data_ptr()
+            k.sa, k.key, k.val = (stage[c].data_ptr() for c in range(3))
+            k.s, k.sel, _, k.hc, k.hb = (five[c].data_ptr() for c in range(5))
+            _attn_critic_tables(k, flat, n)
+            k.g_direct, k.g_other, k.g_dl = scratch[0].data_ptr(), scratch[1].data_ptr(), g_dl.data_ptr()
+            return k
+
+        d_act = None
+        if want_act:
+            d_act = th.empty(b, n, a, dtype=th.float32, device=dev)
+            k = args(False)
+            k.d_act = d_act.data_ptr()
+            _lib.launch("flexnet_attn_critic_backward", k)
+        if not pg:
+            return (None, d_act) + none[2:]
+        g = th.empty(7, rows, 64, dtype=th.float32, device=dev)       # dz_c | dz_b | dz_s | d_sel | d_key | dz_v | dz_sa
+        k = args(True)
+        k.dz_c, k.dz_b, k.dz_s, k.d_sel, k.d_key, k.dz_v, k.dz_sa = (g[c].data_ptr() for c in range(7))
+        d_out_b = th.empty(2, n, 1, dtype=th.float32, device=dev)     # critic_fc2.bias | bias_fc2.bias: +- sum_b dq
+        ws = th.empty(2 * ((b + 31) // 32) * n, dtype=th.float32, device=dev)          # (fp64 partials)
+        k.d_c2_b, k.d_b2_b, k.workspace, k.workspace_floats = d_out_b[0].data_ptr(), d_out_b[1].data_ptr(), ws.data_ptr(), ws.numel()
+        _lib.launch("flexnet_attn_critic_backward", k)
+        dz_c, dz_b, dz_s, d_sel, d_key, dz_v, dz_sa = (g[c].view(b, n, 64) for c in range(7))
+        sa, s3, other, hc, hb = stage[0].view(b, n, 64), five[0].view(b, n, 64), five[2].view(b, n, 64), \
+            five[3].view(b, n, 64), five[4].view(b, n, 64)
+        new = lambda *shape: th.empty(*shape, dtype=th.float32, device=dev)      # noqa: E731
+        d_enc_w, d_senc_w, d_c1_w, d_b1_w = new(n, 64, o + a), new(n, 64, o), new(n, 64, 128), new(n, 64, 64)
+        d_vec = new(4, n, 64)                                                     # d_enc_b | d_senc_b | d_c1_b | d_b1_b
+        d_out_w = new(2, n, 1, 64)                                                # critic_fc2 | bias_fc2 (sign below)
+        d_kqv, d_val_b = new(3, 64, 64), new(64)
+        problems = []
+        for i in range(n):
+            problems += [(dz_sa[:, i], obs[:, i], d_enc_w[i, :, :o], d_vec[0, i]), (dz_sa[:, i], act[:, i], d_enc_w[i, :, o:], None),
+                         (dz_s[:, i], obs[:, i], d_senc_w[i], d_vec[1, i]),
+                         (dz_c[:, i], sa[:, i], d_c1_w[i, :, :64], d_vec[2, i]), (dz_c[:, i], other[:, i], d_c1_w[i, :, 64:], None),
+                         (dz_b[:, i], s3[:, i], d_b1_w[i], d_vec[3, i]),
+                         (dq[:, i:i + 1], hc[:, i], d_out_w[0, i], None), (dq[:, i:i + 1], hb[:, i], d_out_w[1, i], None)]
+        problems += [(g[4], stage[0], d_kqv[0], None), (g[3], five[0], d_kqv[1], None), (g[5], stage[0], d_kqv[2], d_val_b)]
+        tall_wgrad_batched(problems)
+        d_out_w[1].neg_()                                             # out = q - b: the bias head's output layer sees -dq
+        grads = []
+        for i in range(n):
+            grads += [d_enc_w[i], d_vec[0, i], d_senc_w[i], d_vec[1, i], d_c1_w[i], d_vec[2, i], d_out_w[0, i], d_out_b[0, i],
+                      d_b1_w[i], d_vec[3, i], d_out_w[1, i], d_out_b[1, i]]
+        grads += [d_kqv[0], d_kqv[1], d_kqv[2], d_val_b]
+        return (None, d_act, None, *grads)
+
+
+def attn_critic_train(critic, obs, act, param_grads=True):
+    """The node on obs [b, n, o] / act [b, n, a] (``attn_critic_declines`` is None): (q - b [b, n], regulariser [n] detached)."""
+    return _AttnCriticFn.apply(obs, act, param_grads, *_attn_critic_params(critic))
+
+
+def attn_critic(critic, obs, act, critic_frozen=False):
+    """(q - b [b, n], regulariser [n]) of an AttentionCritic on obs [b, n, o] / act [b, n, a].  On GPU tensors, for EAGER calls
+    (``mlp_actor_allowed``: while a HIP graph is captured or audited the composition runs, silently): csrc/attn_critic.hip —
+    the forward launch under no_grad at any batch size, the node ``_AttnCriticFn`` with gradients from WGRAD_MIN_ROWS rows
+    (``critic_frozen``: d_act only, else parameter gradients only) — or, after ``note_fallback("maac", ...)``, the module's own
+    composition where the kernel declines.  On the CPU the composition, silently.  With the node the regulariser comes back
+    detached."""
+    if not obs.is_cuda or not mlp_actor_allowed():
+        return critic(obs, act)
+    with_grad = th.is_grad_enabled() and (act.requires_grad or obs.requires_grad or any(p.requires_grad for p in critic.parameters()))
+    kind = "no_grad" if not with_grad else "policy" if critic_frozen else "value"
+    if not ATTN_CRITIC_FUSED[kind] or (with_grad and obs.shape[0] * obs.shape[1] < WGRAD_MIN_ROWS):
+        return critic(obs, act)
+    if not with_grad:
+        out = fused_attn_critic_forward(critic, obs, act)
+        return out if out is not None else critic(obs, act)
+    why = attn_critic_declines(critic, obs, act)
+    if why is None and (obs.requires_grad or (act.requires_grad and not critic_frozen)):
+        why = "gradients for the observations, or for actions and parameters at once"
+    if why is not None:
+        note_fallback("maac", "update pass: " + why)
+        return critic(obs, act)
+    return attn_critic_train(critic, obs, act, param_grads=not critic_frozen)
