@@ -78,11 +78,19 @@ __device__ __forceinline__ tv16 load_tile(const float* row) {
     return t;
 }
 
-// LayerNorm statistics of the lane's row over its 64 units (both halves end with the same pair)
+// LayerNorm statistics of the lane's row over its 64 units (both halves end with the same pair).  The mean is summed pairwise,
+// as critic.hip's critic_ln_inplace does: as many additions as a running sum, log2(64) roundings instead of 63 — and exact on a
+// row whose units are all equal, where rstd = eps^-1/2 multiplies whatever the mean is off by
 __device__ __forceinline__ void row_stats(const tv16& z0, const tv16& z1, float eps, float& mean, float& rstd) {
-    float p = 0.0f;
+    float ps[16];
 #pragma unroll
-    for (int r2 = 0; r2 < 16; ++r2) p += z0[r2] + z1[r2];
+    for (int r2 = 0; r2 < 16; ++r2) ps[r2] = z0[r2] + z1[r2];
+#pragma unroll
+    for (int w = 8; w >= 1; w >>= 1) {
+#pragma unroll
+        for (int r2 = 0; r2 < w; ++r2) ps[r2] += ps[r2 + w];
+    }
+    const float p = ps[0];
     mean = (p + other_half(p)) * (1.0f / SH);
     float v = 0.0f;
 #pragma unroll

@@ -100,19 +100,7 @@ __device__ __forceinline__ void sq_forward_row(const FlexSqddpgArgs& a, const Sq
         }
     }
     float mean = 0.0f, rstd = 1.0f;
-    if (a.layernorm) {
-        float p = 0.0f;
-#pragma unroll
-        for (int r2 = 0; r2 < 16; ++r2) p += f.z[0][r2] + f.z[1][r2];
-        mean = (p + other_half(p)) * (1.0f / SH);
-        float v = 0.0f;
-#pragma unroll
-        for (int r2 = 0; r2 < 16; ++r2) {
-            const float d0 = f.z[0][r2] - mean, d1 = f.z[1][r2] - mean;
-            v += d0 * d0 + d1 * d1;
-        }
-        rstd = rsqrtf((v + other_half(v)) * (1.0f / SH) + a.ln_eps);
-    }
+    if (a.layernorm) row_stats(f.z[0], f.z[1], a.ln_eps, mean, rstd);
     f.rstd = rstd;
 #pragma unroll
     for (int t = 0; t < 2; ++t) {

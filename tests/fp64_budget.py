@@ -7,10 +7,11 @@ yardstick is measured in the test that uses it, never taken from a kernel.  ``fa
 LayerNorm, gate and ReLU code can go wrong without zero-mean, unit-scale inputs noticing; ``clear_ties`` removes from a
 gradient comparison the rows whose ReLU side is arbitrary in any fp32 form.
 
-The compositions below (``actor_plain``, ``lnrelu_plain``, ``critic_tail_plain``, ``critic_first_layer_plain``) are the layers of
-nets.RNNAgent / nets.MLPCritic written with torch.nn.functional alone, in whatever dtype the module has: the modules' own
-forward takes the project's HIP weight-gradient kernels at update sizes, which neither the yardstick nor the fp64 reference
-may.  tests/test_fp64_budget_cpu.py pins them to the modules' forward (1e-12 in fp64)."""
+The compositions below (``actor_plain``, ``mlp_actor_plain``, ``lnrelu_plain``, ``critic_tail_plain``, ``critic_plain``,
+``critic_first_layer_plain``, ``coma_baseline_plain``, ``sqddpg_plain``) are the layers of nets.RNNAgent / nets.MLPAgent /
+nets.MLPCritic written with torch.nn.functional alone, in whatever dtype the module has: the modules' own forward takes the
+project's HIP weight-gradient kernels at update sizes, which neither the yardstick nor the fp64 reference may.
+tests/test_fp64_budget_cpu.py pins them to the modules' forward (1e-12 in fp64)."""
 import copy
 from typing import NamedTuple
 
@@ -73,11 +74,24 @@ def make_critic(layernorm=True, device="cpu", seed=0, in_features=745):
     import types
     from safe_marl_amd.nets import MLPCritic
     th.manual_seed(seed)
-    c = MLPCritic(in_features, 1, types.SimpleNamespace(hid_size=64, layernorm=layernorm, hid_activation="relu"))
+    c = MLPCritic(in_features, 1, types.SimpleNamespace(hid_size=64, layernorm=layernorm, hid_activation="relu", agent_id=True))
     with th.no_grad():
         for p in c.parameters():
             p.copy_(th.randn_like(p) * 0.2)
     return c.to(device)
+
+
+def make_mlp_agent(obs_dim, n_agents, act_dim, layernorm=True, device="cpu", seed=0):
+    """An MLPAgent (agent_type mlp) with ``make_agent``'s parameters: every one 0.3 randn."""
+    import types
+    from safe_marl_amd.nets import MLPAgent
+    th.manual_seed(seed)
+    args = types.SimpleNamespace(hid_size=64, layernorm=layernorm, action_dim=act_dim, agent_num=n_agents, hid_activation="relu")
+    agent = MLPAgent(obs_dim + n_agents, args)
+    with th.no_grad():
+        for p in agent.parameters():
+            p.copy_(th.randn_like(p) * 0.3)
+    return agent.to(device)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -87,6 +101,60 @@ def with_ids(obs, n_agents):
     """[rows, obs_dim] -> [rows, obs_dim + n]: the one-hot id block of model.py:105-108, row r being agent r % n."""
     eye = th.eye(n_agents, dtype=obs.dtype, device=obs.device)
     return th.cat((obs, eye[th.arange(obs.shape[0], device=obs.device) % n_agents]), -1)
+
+
+def layer_norm_running_sum(z, weight, bias, eps):
+    """LayerNorm over 64 units with the statistics accumulated in the dtype of ``z`` one addend after the other in the order of
+    the tile scheme's lanes before their repair (csrc/flex_mfma_tile.h ``row_stats``): lane half h holds units 8 q + 4 h + j of
+    both 32-unit tiles and adds z0[r] + z1[r] for r = 0 .. 15 onto a running sum; the two halves meet at the end.  The mean of
+    64 equal values then is off by an ulp or two and rstd = eps^-1/2 multiplies that: the third wrong evaluation
+    tests/test_fp64_budget_cpu.py has the budget reject."""
+    r = th.arange(16, device=z.device)
+    halves = []
+    for h in range(2):
+        u = 8 * (r // 4) + 4 * h + (r % 4)
+        halves.append((z[:, u], z[:, 32 + u]))
+    part = []
+    for z0, z1 in halves:
+        p = th.zeros_like(z[:, 0])
+        for k in range(16):
+            p = p + (z0[:, k] + z1[:, k])
+        part.append(p)
+    mean = ((part[0] + part[1]) * (1.0 / 64)).unsqueeze(1)
+    part = []
+    for z0, z1 in halves:
+        v = th.zeros_like(z[:, 0])
+        for k in range(16):
+            d0, d1 = z0[:, k] - mean[:, 0], z1[:, k] - mean[:, 0]
+            v = v + (d0 * d0 + d1 * d1)
+        part.append(v)
+    rstd = th.rsqrt((part[0] + part[1]) * (1.0 / 64) + eps).unsqueeze(1)
+    return ((z - mean) * rstd) * weight + bias
+
+
+def _first_layer(module, obs, n_agents, agent_id, agent_index):
+    """fc1 of rows [rows, obs_dim] without the id columns: the id column of agent r % n (or ``agent_index``) added."""
+    W = module.fc1.weight
+    o = obs.shape[1]
+    z = F.linear(obs, W[:, :o], module.fc1.bias)
+    if agent_id:
+        ids = W[:, o:].t()
+        z = z + (ids[th.arange(obs.shape[0], device=obs.device) % n_agents] if agent_index is None else ids[agent_index])
+    return z
+
+
+def mlp_actor_plain(agent, obs, n_agents, agent_id=True, agent_index=None, running_sum=False):
+    """mlp_agent.py:20-32 on rows [rows, obs_dim] without the id columns: (means, h, first ReLU's pre-activation, second
+    ReLU's).  Row r is agent r % n_agents, or every row agent ``agent_index``.  ``running_sum``: ``layer_norm_running_sum``
+    in LayerNorm's place."""
+    pre1 = _first_layer(agent, obs, n_agents, agent_id, agent_index)
+    if agent.args.layernorm:
+        ln = agent.layernorm
+        pre1 = (layer_norm_running_sum if running_sum else lambda z, w, b, e: F.layer_norm(z, (64,), w, b, e))(
+            pre1, ln.weight, ln.bias, ln.eps)
+    pre2 = F.linear(th.relu(pre1), agent.fc2.weight, agent.fc2.bias)
+    h = th.relu(pre2)
+    return F.linear(h, agent.fc3.weight, agent.fc3.bias), h, pre1, pre2
 
 
 def actor_plain(agent, obs, hidden, n_agents, agent_id=True, ln_units=64, drop_id_of=None, agent_index=None):
@@ -135,8 +203,72 @@ def critic_tail_plain(critic, z):
     if critic.args.layernorm:
         ln = critic.layernorm
         pre1 = F.layer_norm(z, (64,), ln.weight, ln.bias, ln.eps)
-    pre2 = critic.fc2(th.relu(pre1))
-    return critic.fc3(th.relu(pre2)), pre1, pre2
+    pre2 = F.linear(th.relu(pre1), critic.fc2.weight, critic.fc2.bias)
+    return F.linear(th.relu(pre2), critic.fc3.weight, critic.fc3.bias), pre1, pre2
+
+
+def critic_plain(critic, rows):
+    """mlp_critic.py:27-35 on materialised input rows [rows, in_features]: (q [rows, 1], first ReLU's pre-activation, second
+    ReLU's)."""
+    return critic_tail_plain(critic, F.linear(rows, critic.fc1.weight, critic.fc1.bias))
+
+
+CRITIC_FORMS = {"maddpg": (True, True), "mappo": (True, False), "ippo": (False, False), "iddpg": (False, True)}   # (shared, x2)
+
+
+def critic_rows(obs, act, i, form, agent_id=True):
+    """Agent i's critic input rows [b, width] of tests/test_critic_unshared_gpu.py's four forms from obs [b, n, o] and act
+    [b, n, a]: [o_1 .. o_n | onehot(i) | a_1 .. a_n] (maddpg.py:33-54, the other agents' actions detached; mappo without the
+    actions) or [o_i | onehot(i) | a_i] (iddpg.py:32-59; ippo without the action)."""
+    shared, has_act = CRITIC_FORMS[form]
+    b, n, _ = obs.shape
+    parts = [obs.reshape(b, -1) if shared else obs[:, i]]
+    if agent_id:
+        parts.append(F.one_hot(th.full((b,), i, device=obs.device), n).to(obs.dtype))
+    if has_act:
+        if shared:
+            own = th.zeros(1, n, 1, dtype=act.dtype, device=act.device)
+            own[0, i, 0] = 1.0
+            parts.append((act.detach() * (1.0 - own) + act * own).reshape(b, -1))
+        else:
+            parts.append(act[:, i])
+    return th.cat(parts, 1)
+
+
+def coma_baseline_plain(critic, z1, act, sampled):
+    """coma.py:139-149 from fc1's pre-activation ``z1`` [b n, 64] of the rows on the actions taken (COMA's row layout: the
+    action columns are fc1.weight's last n a): z(s, b, i) = z1[b, i] + W_act[:, i a:(i + 1) a] (sampled[s, b, i] - act[b, i]),
+    then the tail.  Returns (baseline [b, n], q_sampled [s, b, n], values [b, n], the pre-activations of the sampled rows and
+    of the rows themselves: four tensors [.., 64])."""
+    s, b, n, a = sampled.shape
+    w_act = critic.fc1.weight[:, critic.fc1.in_features - n * a:].reshape(-1, n, a)                 # [64, n, a]
+    delta = sampled - act.unsqueeze(0)
+    z = z1.view(1, b, n, -1) + (delta.unsqueeze(-2) * w_act.permute(1, 0, 2)).sum(-1)               # [s, b, n, 64]
+    qs, pre1, pre2 = critic_tail_plain(critic, z.reshape(s * b * n, -1))
+    q, vpre1, vpre2 = critic_tail_plain(critic, z1)
+    qs = qs.reshape(s, b, n)
+    return qs.mean(0), qs, q.reshape(b, n), (pre1, pre2, vpre1, vpre2)
+
+
+def sqddpg_plain(critic, obs, act, pos, ns):
+    """sqddpg.py:63-104 on the coalitions ``pos`` [b ns, n] (pos[g, i]: the position of agent i in group g = b ns + s): the
+    critic on the materialised rows [obs_1 .. obs_n | block p = the action of the agent at position p if p <= pos[g, i],
+    else 0 | onehot(i)], only agent i's own action keeping its gradient.  obs [b, n, o], act [b, n, a].  Returns (phi [b, n],
+    q [b, ns, n], first ReLU's pre-activation, second ReLU's — [b ns n, 64] each)."""
+    b, n, a = act.shape
+    dev = act.device
+    pos = pos.long().view(b, ns, n)
+    who = th.empty_like(pos).scatter_(2, pos, th.arange(n, device=dev).expand(b, ns, n))           # the agent at position p
+    ordered = act.unsqueeze(1).expand(b, ns, n, a).gather(2, who.unsqueeze(-1).expand(b, ns, n, a)).unsqueeze(2)
+    p = th.arange(n, device=dev).view(1, 1, 1, n)
+    own = (p == pos.unsqueeze(-1)).to(act.dtype).unsqueeze(-1)                                      # [b, ns, i, p, 1]
+    before = (p < pos.unsqueeze(-1)).to(act.dtype).unsqueeze(-1)
+    acts = ordered.detach() * before + ordered * own                                                # [b, ns, i, p, a]
+    rows = th.cat((obs.reshape(b, 1, 1, -1).expand(b, ns, n, -1), acts.reshape(b, ns, n, n * a),
+                   th.eye(n, dtype=act.dtype, device=dev).expand(b, ns, n, n)), -1)
+    q, pre1, pre2 = critic_plain(critic, rows.reshape(b * ns * n, -1))
+    q = q.view(b, ns, n)
+    return q.mean(1), q, pre1, pre2
 
 
 def critic_first_layer_plain(critic, obs_cols, act_cols, n_agents):
@@ -195,6 +327,49 @@ def gate_rounding(agent, obs, hidden, n_agents, noise, std, agent_index=None):
     return {"hidden": 3.0 * var_h.sqrt(), "means": d_m, "action": d_a, "env_action": 0.5 * d_a}
 
 
+def row_sum_rounding(addends):
+    """What fp32 rounding of the partial sums alone does to a gradient that is a sum over rows, element by element: ``addends``
+    [rows, ...] are the fp64 terms whose sum over dim 0 is the gradient (a bias gradient's are the rows of dL/d pre-activation).
+
+    The N rows' terms of an element have mean m and variance v, so the partial sum after k terms, in whatever order the rows
+    are taken, has mean square k^2 m^2 + k (1 - k / N) v (the drift to the sum N m that is known, and a random walk tied to it at
+    both ends); its rounding is uniform within 2^-24 of it (gate_rounding's model; half an ulp is between 2^-25 and 2^-24 of
+    the value, so measured running sums have 0.74 of this sigma), variance (2^-24)^2 (k^2 m^2 + k (1 - k / N) v) / 3.  Summed
+    over k up to N: sigma = 2^-24 sqrt((m^2 N^3 / 3 + v N^2 / 6) / 3), which for terms of zero mean and mean square t^2 (m^2 of
+    the order t^2 / N) is 2^-24 N t / sqrt(6) — a running sum, the least accurate order a correct fp32 kernel
+    may use (the tile kernels keep a running sum per lane or per work-group over its tiles and fold those in a tree, which lies
+    between this and a balanced tree).  The figure is 3 sigma.  It matters where the terms cancel: the gradient, and with it
+    the 8-ulp floor, is then far smaller than the partial sums, and the fp32 composition — a tree sum — can come out with an
+    error of a fraction of an ulp by luck (d_fc3.bias, one number, over 257 rows: 2e-10 on a gradient of 7e-3, a running
+    sum's sigma 8e-9).  Where nothing cancels (v = 0) it is sqrt(N) / 3 ulps of the gradient N m: 10 ulps at 1 000 rows.
+    tests/test_fp64_budget_cpu.py holds the derivation against running fp32 sums with and without drift, and that a budget
+    with this floor still rejects a gradient off by 1e-5 of itself."""
+    import math
+    a = addends.detach().double()
+    n = float(a.shape[0])
+    return 3.0 * ULP * ((a.mean(0).square() * n ** 3 / 3.0 + a.var(0, unbiased=False) * n ** 2 / 6.0) / 3.0).sqrt()
+
+
+def tail_sum_floors(g_q, g_pre1, g_pre2, pre1, pre2, ln):
+    """``row_sum_rounding`` of the vector-sum gradients of an MLPCritic's tail from the fp64 reference's row gradients: ``g_q``
+    [rows, 1], ``g_pre1`` / ``g_pre2`` [rows, 64] = dL / d(q, first ReLU's pre-activation, second ReLU's) with the
+    pre-activations themselves; ``ln`` the fp64 LayerNorm or None.  {parameter name: floor, shaped as the parameter}."""
+    out = {"fc3.bias": row_sum_rounding(g_q).reshape(1), "fc3.weight": row_sum_rounding(g_q * th.relu(pre2)).reshape(1, 64),
+           "fc2.bias": row_sum_rounding(g_pre2)}
+    if ln is not None:
+        out["layernorm.bias"] = row_sum_rounding(g_pre1)
+        out["layernorm.weight"] = row_sum_rounding(g_pre1 * (pre1 - ln.bias) / ln.weight)       # dL/dy xhat
+    return out
+
+
+def floor_ulps(extra, ref):
+    """FLOOR_ULPS plus the largest figure of an element-wise floor ``extra`` (or None) in ulps of the scale of ``ref``: what
+    ``within_budget`` takes as ``floor_ulps``."""
+    if extra is None:
+        return FLOOR_ULPS
+    return FLOOR_ULPS + float(extra.max()) / (ULP * max(float(ref.detach().abs().max()), TINY))
+
+
 def run_with_grads(forward, params, upstream):
     """One training pass: ``forward()`` returns a tuple of tensors, ``upstream`` the same number of gradients fed into them
     (None: none into that output); returns (outputs detached, {name: gradient}) for the named parameters ``params`` (a
@@ -248,12 +423,15 @@ def clear_ties(ref_module, inputs, upstream, eps=1e-5):
 
 class Family(NamedTuple):
     name: str
-    inputs: tuple         # (obs [rows, obs_dim], hidden [rows, 64]) for the actor, (z [rows, 64],) for the direct entry points
+    inputs: tuple         # (obs [rows, obs_dim], hidden [rows, 64]) for the RNN actor, (obs [rows, obs_dim],) for a module with
+    #                       its own first layer and no state ("mlp"), (z [rows, 64],) for the direct entry points
     params: dict          # parameter changes the family needs: {"fc1.bias": ("add", 30.0)} / {"ln_b": ("fill", -10.0)}
     groups: object = None  # mixed: int64 [rows], the index into MIXED_OF[kind] of each row's family
 
 
-MIXED_OF = {"actor": ("plain", "reset", "saturated"), "z": ("plain", "reset", "offset", "constant")}
+MIXED_OF = {"actor": ("plain", "reset", "saturated"), "mlp": ("plain", "reset"), "z": ("plain", "reset", "offset", "constant")}
+CONSTANT_BIAS = 2.7   # not a dyadic fraction: 2.7 k is inexact in fp32 for most k, so a running sum of equal addends rounds
+CONSTANT_PARAMS = {"fc1.weight": ("fill", 0.0), "fc1.bias": ("fill", CONSTANT_BIAS)}
 
 
 def _actor_inputs(name, rows, obs_dim, g, dev):
@@ -263,6 +441,12 @@ def _actor_inputs(name, rows, obs_dim, g, dev):
         hid = 40.0 * th.sign(th.randn(rows, 64, device=dev, generator=g))
         return 8.0 * th.randn(rows, obs_dim, device=dev, generator=g), hid
     return 0.5 * th.randn(rows, obs_dim, device=dev, generator=g), 0.5 * th.randn(rows, 64, device=dev, generator=g)
+
+
+def _mlp_inputs(name, rows, obs_dim, g, dev):
+    if name == "reset":
+        return (th.zeros(rows, obs_dim, device=dev),)
+    return (0.5 * th.randn(rows, obs_dim, device=dev, generator=g),)
 
 
 def _z_inputs(name, rows, g, dev):
@@ -276,31 +460,38 @@ def _z_inputs(name, rows, g, dev):
     return z
 
 
-def families(rows, n_agents, obs_dim, generator):
-    """The named input families for ``rows`` = samples x ``n_agents`` rows, drawn from ``generator`` on its device.  With an
-    ``obs_dim`` the actor's: inputs (obs, hidden); with ``obs_dim`` None the direct entry points' (csrc/lnrelu.hip without bias
-    or ids, the critic tail): inputs (z,).
+def families(rows, n_agents, obs_dim, generator, kind=None):
+    """The named input families for ``rows`` = samples x ``n_agents`` rows, drawn from ``generator`` on its device.  ``kind``
+    "actor" (the default with an ``obs_dim``): the RNN actor's, inputs (obs, hidden); "mlp": a module with its own first layer
+    and no state (nets.MLPAgent; nets.MLPCritic on materialised rows, ``obs_dim`` then the width the test draws), inputs
+    (obs,); "z" (the default with ``obs_dim`` None): the direct entry points' (csrc/lnrelu.hip without bias or ids, the critic
+    tail, csrc/coma.hip), inputs (z,).
 
     plain      0.5 randn.
     reset      inputs exactly zero: the workload's own first step.
-    offset     the row mean about 70 times the row spread: fc1.bias += 30 on the agent, a +30 common term on z.
-    constant   (z only) the 64 LayerNorm inputs of a row all equal: variance exactly zero, rstd = eps^-1/2.
-    saturated  (actor only) hidden = 40 sign(randn), obs = 8 randn: gate pre-activations of several tens.
+    offset     the row mean about 70 times the row spread: fc1.bias += 30 on the module, a +30 common term on z.
+    constant   the 64 LayerNorm inputs of a row all equal, bit for bit: variance exactly zero, rstd = eps^-1/2.  On z: one
+               draw per row repeated.  On a module: fc1.weight (its id columns and, for the SQDDPG and COMA critics, its
+               action block are part of it) filled with 0, fc1.bias with CONSTANT_BIAS, inputs plain.
+    saturated  (RNN actor only) hidden = 40 sign(randn), obs = 8 randn: gate pre-activations of several tens.
     dead       ln_b = -10: every ReLU unit of every row is off.
     mixed      the families that are inputs alone (MIXED_OF) interleaved row by row, so that one 16-row or 32-row tile
-               holds rows of each kind; ``groups`` says which.  (offset on the agent and dead are parameter changes: they
-               hold for a whole batch and cannot be interleaved.)"""
+               holds rows of each kind; ``groups`` says which.  (offset, constant on a module and dead are parameter
+               changes: they hold for a whole batch and cannot be interleaved.)"""
     dev = generator.device
-    kind = "z" if obs_dim is None else "actor"
-    draw = (lambda nm: (_z_inputs(nm, rows, generator, dev),)) if kind == "z" else \
-        (lambda nm: _actor_inputs(nm, rows, obs_dim, generator, dev))
+    if kind is None:
+        kind = "z" if obs_dim is None else "actor"
+    draw = {"z": lambda nm: (_z_inputs(nm, rows, generator, dev),),
+            "mlp": lambda nm: _mlp_inputs(nm, rows, obs_dim, generator, dev),
+            "actor": lambda nm: _actor_inputs(nm, rows, obs_dim, generator, dev)}[kind]
     out = {"plain": Family("plain", draw("plain"), {}), "reset": Family("reset", draw("reset"), {})}
     if kind == "z":
         out["offset"] = Family("offset", draw("offset"), {})
         out["constant"] = Family("constant", draw("constant"), {})
     else:
         out["offset"] = Family("offset", draw("plain"), {"fc1.bias": ("add", 30.0)})
-        out["saturated"] = Family("saturated", draw("saturated"), {})
+        if kind == "actor":
+            out["saturated"] = Family("saturated", draw("saturated"), {})
     out["dead"] = Family("dead", draw("plain"), {"ln_b": ("fill", -10.0)})
     names = MIXED_OF[kind]
     groups = th.arange(rows, device=dev) % len(names)
@@ -312,11 +503,19 @@ def families(rows, n_agents, obs_dim, generator):
             t[groups == j] = parts[j][k][groups == j]
         mixed.append(t)
     out["mixed"] = Family("mixed", tuple(mixed), {}, groups)
+    if kind != "z":
+        # (plain's own inputs, no further draw: whatever a test draws after this call is what it was before this family existed)
+        out["constant"] = Family("constant", out["plain"].inputs, dict(CONSTANT_PARAMS))
     return out
 
 
 def apply_params(module, family):
-    """Make the family's parameter changes on ``module`` (an RNNAgent or an MLPCritic; ``ln_b`` is its LayerNorm's bias)."""
+    """Make the family's parameter changes on ``module`` (an RNNAgent, an MLPAgent or an MLPCritic, or a list of them: every
+    one; ``ln_b`` is its LayerNorm's bias)."""
+    if isinstance(module, (list, tuple)):
+        for m in module:
+            apply_params(m, family)
+        return module
     with th.no_grad():
         for key, (op, value) in family.params.items():
             p = module.layernorm.bias if key == "ln_b" else dict(module.named_parameters())[key]

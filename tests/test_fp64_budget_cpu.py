@@ -1,14 +1,15 @@
-"""tests/fp64_budget.py itself, on the CPU: its plain compositions are the modules' forward; every input family keeps the share
-of rows with an arbitrary ReLU side within the cap; the fp32 modules pass their own budget; and the budget rejects four wrong
-fp32 results — two of them (a gradient off by 1e-5 of itself, an output off by 1e-5 of its scale) errors that the fixed
-tolerances of the fp32-against-fp32 tests accept."""
+"""tests/fp64_budget.py itself, on the CPU: its plain compositions are the modules' forward; every input family — and every
+case of the GPU tests that draw theirs from the CPU generator — keeps the share of rows with an arbitrary ReLU side within the
+cap; the fp32 modules pass their own budget; and the budget rejects five wrong fp32 results — two of them (a gradient off by
+1e-5 of itself, an output off by 1e-5 of its scale) errors that the fixed tolerances of the fp32-against-fp32 tests accept,
+one (LayerNorm statistics from a running fp32 sum) wrong only on rows whose 64 inputs are all equal."""
 import pytest
 import torch as th
 
 from . import fp64_budget as fb
 
 ROWS, N, OBS, ACT = 2565, 5, 144, 4
-ACTOR_FAMILIES = ("plain", "reset", "offset", "saturated", "dead", "mixed")
+ACTOR_FAMILIES = ("plain", "reset", "offset", "constant", "saturated", "dead", "mixed")
 Z_FAMILIES = ("plain", "reset", "offset", "constant", "dead", "mixed")
 
 
@@ -156,3 +157,202 @@ def test_the_floor_of_saturated_rows_still_rejects_the_wrong_evaluations(b, n, o
         if nm != "action":
             with pytest.raises(AssertionError):
                 fb.within_budget(mutant[k], good[k], ref[k], floor_ulps=floor, name=f"mutant {list(wrong)[0]} saturated {b}x{n} {nm}")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the tile-scheme kernels' compositions, families and cases (tests/test_coma_fp64_gpu.py, test_sqddpg_fp64_gpu.py,
+# test_critic_unshared_fp64_gpu.py, test_actor_mlp_fp64_gpu.py, test_unshared_fp64_gpu.py)
+
+def test_tile_scheme_compositions_are_the_modules_forward():
+    from safe_marl_amd.learner import SQDDPG
+    from safe_marl_amd.nets import coma_baseline
+    from .golden_io import golden_args
+    g = th.Generator().manual_seed(0)
+    n, o, a, b = 3, 30, 2, 7
+    with th.no_grad():
+        agent = fb.make_mlp_agent(o, n, a).double()
+        obs = th.randn(b * n, o, generator=g).double()
+        m, _, h = agent(fb.with_ids(obs, n), None)
+        pm, ph, pre1, pre2 = fb.mlp_actor_plain(agent, obs, n)
+        assert (m - pm).abs().max() < 1e-12 and (h - ph).abs().max() < 1e-12 and th.equal(th.relu(pre2), ph)
+        one = fb.mlp_actor_plain(agent, obs[1::n], n, agent_index=1)            # every row agent 1: the per-agent modules' form
+        assert (one[0] - pm[1::n]).abs().max() < 1e-12
+        obs3, act3 = obs.view(b, n, o), th.randn(b, n, a, generator=g).double()
+        for form, (shared, has_act) in fb.CRITIC_FORMS.items():
+            width = o * (n if shared else 1) + n + (a * (n if shared else 1) if has_act else 0)
+            critic = fb.make_critic(in_features=width).double()
+            for i in range(n):
+                rows = fb.critic_rows(obs3, act3 if has_act else None, i, form)
+                assert rows.shape == (b, width)
+                assert (critic(rows, None)[0] - fb.critic_plain(critic, rows)[0]).abs().max() < 1e-12
+        # COMA: the action columns are the last n a of fc1.weight
+        critic = fb.make_critic(in_features=(n + 1) * o + n + n * a).double()
+        z1 = th.randn(b * n, 64, generator=g).double()
+        sampled = act3.unsqueeze(0) + th.randn(4, b, n, a, generator=g).double()
+        base, qs, q = coma_baseline(critic, z1, act3, sampled, want_q=True, want_values=True, fused=False)
+        pb, pqs, pq, pres = fb.coma_baseline_plain(critic, z1, act3, sampled)
+        assert (base - pb).abs().max() < 1e-12 and (qs - pqs).abs().max() < 1e-12 and (q - pq).abs().max() < 1e-12
+        assert [tuple(p.shape) for p in pres] == [(4 * b * n, 64)] * 2 + [(b * n, 64)] * 2
+    # SQDDPG: values and the own-action gradient of the learner's materialising form
+    m = SQDDPG(golden_args("sqddpg3")._replace(sample_size=4)).double()
+    with th.no_grad():
+        for p in m.value_dicts.parameters():
+            p.copy_(0.2 * th.randn_like(p))
+    obs = th.randn(b, 3, m.obs_dim, generator=g).double()
+    act = th.rand(b, 3, m.act_dim, generator=g).double()
+    pos = th.argsort(th.rand(b * 4, 3, generator=g), dim=1).argsort(dim=1)
+    up = th.randn(b, 4, 3, generator=g).double()
+    a1, a2 = act.clone().requires_grad_(True), act.clone().requires_grad_(True)
+    v = m.marginal_contribution_torch(obs, a1, pos).view(b, 4, 3)
+    phi, q, pre1, pre2 = fb.sqddpg_plain(m.value_dicts[0], obs, a2, pos, 4)
+    assert (v - q).abs().max() < 1e-12 and (phi - v.mean(1)).abs().max() < 1e-12 and pre1.shape == (b * 4 * 3, 64)
+    (g1,), (g2,) = th.autograd.grad((v * up).sum(), [a1]), th.autograd.grad((q * up).sum(), [a2])
+    assert (g1 - g2).abs().max() < 1e-12 and g1.abs().max() > 0
+
+
+def test_constant_family_makes_every_rows_layernorm_inputs_equal():
+    g = th.Generator().manual_seed(5)
+    fam = fb.families(35, 5, 30, g, kind="mlp")["constant"]
+    agent = fb.apply_params(fb.make_mlp_agent(30, 5, 4), fam)
+    z = agent.fc1(fb.with_ids(fam.inputs[0], 5))
+    assert th.equal(z, th.full_like(z, fb.CONSTANT_BIAS))
+    # ... and the running sum of 64 such values in fp32 is not 64 times the value: what the family is for
+    run = th.zeros(())
+    for _ in range(64):
+        run = run + th.tensor(fb.CONSTANT_BIAS)
+    assert float(run) != float(th.tensor(fb.CONSTANT_BIAS) * 64)
+    fam = fb.families(35, 5, 30, g)["constant"]                                # the RNN actor's
+    agent = fb.apply_params(fb.make_agent(30, 5, 4), fam)
+    z = agent.fc1(fb.with_ids(fam.inputs[0], 5))
+    assert th.equal(z, th.full_like(z, fb.CONSTANT_BIAS))
+
+
+@pytest.mark.parametrize("name,rejected", [("plain", False), ("offset", False), ("constant", True)])
+def test_budget_rejects_a_running_sum_layernorm_on_constant_rows(name, rejected):
+    """The third wrong evaluation: LayerNorm's statistics accumulated one unit after the other in fp32 in the order of the
+    tile scheme's lanes (fb.layer_norm_running_sum).  On plain and offset rows it is one more correct fp32 evaluation; on rows
+    of 64 equal inputs its mean is off by an ulp or two, rstd = eps^-1/2 multiplies that, and the budget must say so."""
+    n, o, a, rows = 5, 144, 4, 320
+    g = th.Generator().manual_seed(3)
+    fam = fb.families(rows, n, o, g, kind="mlp")[name]
+    agent = fb.apply_params(fb.make_mlp_agent(o, n, a), fam)
+    a64 = fb.ref64(agent)
+    obs = fam.inputs[0]
+    with th.no_grad():
+        good = fb.mlp_actor_plain(agent, obs, n)[:2]
+        mutant = fb.mlp_actor_plain(agent, obs, n, running_sum=True)[:2]
+        ref = fb.mlp_actor_plain(a64, obs.double(), n)[:2]
+        # the helper is LayerNorm: in fp64 the two agree
+        assert (fb.mlp_actor_plain(a64, obs.double(), n, running_sum=True)[0] - ref[0]).abs().max() < 1e-9
+    for k, nm in enumerate(("means", "h")):
+        if rejected:
+            with pytest.raises(AssertionError):
+                fb.within_budget(mutant[k], good[k], ref[k], name=f"mutant running-sum {name} {nm}")
+        else:
+            fb.within_budget(mutant[k], good[k], ref[k], name=f"running-sum {name} {nm}")
+
+
+def _share_line(tag, share):
+    print(f"tie share {tag}: {share:.4%}")
+    assert share <= fb.TIE_CAP, tag
+
+
+def test_tie_shares_of_the_mlp_actor_cases():
+    from . import test_actor_mlp_fp64_gpu as T
+    for kind in T.KINDS:
+        for family in T.FAMILIES:
+            for shape in T.TRAINING:
+                agents, _, obs, up = T.case_inputs(kind, *shape, family, "cpu")
+                a64 = fb.ref64(agents)
+                _share_line(f"actor_mlp {kind} {family} {shape}", fb.clear_ties(lambda o: T.plain(a64, o, th.float64)[2:], (obs,), [up]))
+
+
+@pytest.mark.parametrize("form", ["maddpg", "ippo"])
+def test_tie_shares_of_the_unshared_critic_cases(form):
+    from . import test_critic_unshared_fp64_gpu as T
+    assert T.FORMS == ("maddpg", "ippo")
+    for family in T.FAMILIES:
+        for shape in T.SHAPES:
+            critics, _, obs, act, up = T.case_inputs(form, *shape, family, "cpu")
+            c64 = fb.ref64(critics)
+            _share_line(f"critic_unshared {form} {family} {shape}",
+                        fb.clear_ties(lambda o, a: T.plain(c64, o, a, form, th.float64)[1:], (obs, act), [up]))
+
+
+@pytest.mark.parametrize("ns", [1, 10])
+@pytest.mark.parametrize("family", ["plain", "reset", "offset", "constant", "constant-act", "dead"])
+def test_tie_shares_of_the_sqddpg_cases(family, ns):
+    from . import test_sqddpg_fp64_gpu as T
+    assert family in T.FAMILIES and set(T.FAMILIES) == {"plain", "reset", "offset", "constant", "constant-act", "dead"}
+    assert ns in T.SAMPLE_SIZES and len(T.SAMPLE_SIZES) == 2
+    for b, n in T.SHAPES:
+        m, obs, act, pos, w, attempt = T.case_inputs(b, n, ns, family, "cpu")
+        share, keep = T.clear_tied(fb.ref64(m.value_dicts[0]), obs, act, pos, ns, w)
+        _share_line(f"sqddpg {family} {b}x{n} ns={ns} (attempt {attempt})", share)
+        tied = T.tied(fb.ref64(m.value_dicts[0]), obs, act, pos, ns)
+        assert th.equal(w == 0, tied) and th.equal(keep == 0, tied.any(1))
+
+
+@pytest.mark.parametrize("b,n,obs_dim,act", [(13, 5, 144, 4), (417, 5, 144, 4), (1025, 2, 30, 2)])
+def test_tie_shares_of_the_unshared_rnn_actor_families(b, n, obs_dim, act):
+    """tests/test_unshared_fp64_gpu.py's per-agent modules (seeds 10 + i) at its shapes: in the constant and dead families every
+    row of an agent has the same LayerNorm output, so one ln_b entry within 1e-5 of zero would clear all of them — none is.
+    (The inputs are this generator's, as in the tests above: those of the GPU test come from the device's.)"""
+    from . import test_unshared_fp64_gpu as T
+    assert (b, n, obs_dim, act) in T.SHAPES and len(T.SHAPES) == 3
+    rows = b * n
+    for family in T.FAMILIES:
+        g = th.Generator().manual_seed(rows + act)
+        fam = fb.families(rows, n, obs_dim, g)[family]
+        agents = fb.apply_params([fb.make_agent(obs_dim, n, act, seed=10 + i) for i in range(n)], fam)
+        a64 = fb.ref64(agents)
+        obs, hid = fam.inputs[0].view(b, n, obs_dim), fam.inputs[1].view(b, n, 64)
+        up = [th.randn(rows, act, generator=g) / rows]
+        _share_line(f"actor_unshared {family} {b}x{n}x{obs_dim}x{act}",
+                    fb.clear_ties(lambda o_, h_: [T._per_agent(a64, o_, h_, th.float64)[2]], (obs, hid), up))
+
+
+def test_row_sum_rounding_is_what_a_running_fp32_sum_does_and_still_rejects_1e_5():
+    """fb.row_sum_rounding, the floor of the vector-sum gradients in tests/test_sqddpg_fp64_gpu.py and
+    tests/test_critic_unshared_fp64_gpu.py: 2 000 sums of 257 cancelling addends, accumulated in fp32 one after the other — the
+    order the figure is derived for — with zero-mean addends and with a drift of half their spread.  Their errors have 0.74 of its sigma (the figure takes a rounding to be within 2^-24 of
+    the value; half an ulp is between 2^-25 and 2^-24 of it, root mean square 0.74 * 2^-24 over a binade), 3 sigma holds for
+    all but a percent of them, a pairwise sum stays inside it, and the budget with the floor still rejects a gradient off by 1e-5 of itself and a
+    sum that leaves one row out."""
+    g = th.Generator().manual_seed(11)
+    n, m = 257, 2000
+    for drift in (0.0, 0.5):
+        addends = (th.randn(n, m, generator=g) + drift) / n
+        ref = addends.double().sum(0)
+        run = th.zeros(m)
+        for k in range(n):
+            run = run + addends[k]
+        floor = fb.row_sum_rounding(addends)
+        err = (run.double() - ref).abs()
+        sigma = floor / 3.0
+        ratio = float((err.square().mean() / sigma.square().mean()).sqrt())
+        print(f"running sum, drift {drift}: rms error / sigma = {ratio:.3f}, beyond 3 sigma {float((err > floor).double().mean()):.4%}")
+        assert 0.6 <= ratio <= 0.9 and float((err > floor).double().mean()) <= 0.01
+    addends = th.randn(n, m, generator=g) / n
+    ref = addends.double().sum(0)
+    run = th.zeros(m)
+    for k in range(n):
+        run = run + addends[k]
+    floor = fb.row_sum_rounding(addends)
+    pairwise = addends.clone()
+    pad = th.zeros(512 - n, m)
+    pairwise = th.cat((pairwise, pad), 0)
+    while pairwise.shape[0] > 1:
+        pairwise = pairwise[0::2] + pairwise[1::2]
+    assert bool(((pairwise[0].double() - ref).abs() <= floor).all())
+    # the budget with the floor: the running sum passes with a tree sum as the yardstick; the two wrong sums do not
+    tree = addends.sum(0)
+    ulps = fb.floor_ulps(floor, ref)
+    print(f"floor: {ulps:.1f} ulps of the gradients' scale")
+    assert ulps < 100.0
+    fb.within_budget(run, tree, ref, floor_ulps=ulps, name="running fp32 sum of 257 rows")
+    with pytest.raises(AssertionError):
+        fb.within_budget(run * (1.0 + 1e-5), tree, ref, floor_ulps=ulps, name="mutant running sum (1 + 1e-5)")
+    with pytest.raises(AssertionError):
+        fb.within_budget(run - addends[-1], tree, ref, floor_ulps=ulps, name="mutant running sum without its last row")
+    assert fb.floor_ulps(None, ref) == fb.FLOOR_ULPS

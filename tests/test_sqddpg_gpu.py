@@ -98,25 +98,17 @@ def _random_model(n, layernorm, seed=0):
     return m
 
 
-def _clear_ties(m, obs, act, pos, w, eps=1e-5):
-    """Zero the loss weight of samples with a ReLU pre-activation within eps of 0 in any of their rows (both fp32 forms
-    may take different sides of the kink there)."""
+def _clear_ties(m, obs, act, pos, w):
+    """Zero the loss weight of samples with a ReLU pre-activation within 1e-5 of 0 in any of their rows (both fp32 forms may
+    take different sides of the kink there): tests/fp64_budget.py's ``clear_ties`` on the fp64 pre-activations of a sample's
+    rows side by side."""
     import copy
-    md = copy.deepcopy(m).double()
-    net = md.value_dicts[0]
-    with th.no_grad():
-        b, n, ns = obs.size(0), m.n_, m.sample_size
-        sub, grand, ind = md.coalition_maps(pos, b)
-        acts = act.double().view(b, 1, 1, n, -1).expand(b, ns, n, n, m.act_dim).gather(
-            3, grand.unsqueeze(-1).expand(b, ns, n, n, m.act_dim)) * sub.double().unsqueeze(-1)
-        rows = th.cat((obs.double().reshape(b, 1, 1, -1).expand(b, ns, n, -1), acts.reshape(b, ns, n, -1),
-                       th.eye(n, device=obs.device, dtype=th.float64).expand(b, ns, n, n)), -1)
-        z = net.fc1(rows)
-        y = net.layernorm(z) if m.args.layernorm else z
-        z2 = net.fc2(th.relu(y))
-        tie = ((y.abs() < eps).any(-1) | (z2.abs() < eps).any(-1)).view(b, -1).any(1)
+    from . import fp64_budget as fb
+    net = copy.deepcopy(m.value_dicts[0]).double()
+    b = obs.size(0)
     w = w.clone()
-    w[tie] = 0.0
+    fb.clear_ties(lambda: [p.reshape(b, -1) for p in fb.sqddpg_plain(net, obs.double(), act.double(), pos, m.sample_size)[2:]],
+                  (), [w])
     return w
 
 

@@ -12,7 +12,7 @@ from . import fp64_budget as fb
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(13, 5, 144, 4), (417, 5, 144, 4), (1025, 2, 30, 2)]      # 65 rows; 2 085 and 2 050: what the training node accepts
-FAMILIES = ("plain", "reset", "saturated", "mixed")
+FAMILIES = ("plain", "reset", "saturated", "mixed", "offset", "constant", "dead")
 
 
 def _per_agent(agents, obs, hid, dtype):
@@ -39,7 +39,7 @@ def _case(b, n, obs_dim, act, family):
     rows = b * n
     g = th.Generator(device="cuda").manual_seed(rows + act)
     fam = fb.families(rows, n, obs_dim, g)[family]
-    agents = [fb.make_agent(obs_dim, n, act, device="cuda", seed=10 + i) for i in range(n)]
+    agents = fb.apply_params([fb.make_agent(obs_dim, n, act, device="cuda", seed=10 + i) for i in range(n)], fam)
     a64 = fb.ref64(agents)
     obs, hid = fam.inputs[0].view(b, n, obs_dim), fam.inputs[1].view(b, n, 64)
     up = [th.randn(rows, act, device="cuda", generator=g) / rows, None]
