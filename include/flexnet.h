@@ -1124,7 +1124,7 @@ int flexnet_actor_mlp_forward(const FlexActorMlpArgs* args, void* stream);
 int flexnet_actor_mlp_backward(const FlexActorMlpBwdArgs* args, void* stream);
 
 /* ---- agent_type: mlp under shared_params: False (madrl/models/model.py:124-138: one MLPAgent / MLPAgentGaussian per agent;
- * csrc/actor_mlp_unshared.hip) ----
+ * csrc/actor_mlp.hip's per-agent form) ----
  * flexnet_actor_mlp_*'s computation and work map with PER-AGENT weights: row s * n_agents + a of the [rows, .] tensors is agent a
  * of sample s and uses fc1_w[a], fc1_b[a], ... — the modules' own parameter tensors through pointer tables, no stacked copy.  A
  * wavefront owns 32 samples of one agent; a work-group's agent, blockIdx.x % n_agents, selects the weights.  Under agent_id,

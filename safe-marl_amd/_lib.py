@@ -226,7 +226,7 @@ FLEXNET_ACTOR_MLP_UNSHARED_WS_FLOATS = FLEXNET_MAX_AGENTS * 128 * 320
 
 
 class FlexActorMlpUnsharedArgs(C.Structure):
-    """include/flexnet.h: the per-agent MLP actors' forward, parameter tables (csrc/actor_mlp_unshared.hip)"""
+    """include/flexnet.h: the per-agent MLP actors' forward, parameter tables (csrc/actor_mlp.hip's per-agent form)"""
     _fields_ = _ACTOR_MLP_HEAD + [("obs", C.c_void_p)] + \
                [(k, _AgentPtrs) for k in ("fc1_w", "fc1_b", "ln_w", "ln_b", "fc2_w", "fc2_b", "fc3_w", "fc3_b")] + \
                [(k, C.c_void_p) for k in ("means", "h", "save_z1", "save_x")]

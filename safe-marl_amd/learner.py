@@ -676,7 +676,7 @@ class Model(nn.Module):
                 return means, self._log_stds_like(means), hiddens
         per_agent_eager = not self.args.shared_params and (gauss or isinstance(self.policy_dicts[0], MLPAgent))
         if per_agent_eager and obs.is_cuda and self.fused_inference:
-            # one MLP or Gaussian actor per agent: csrc/actor_mlp_unshared.hip, or csrc/actor_unshared.hip with the gradient at the
+            # one MLP or Gaussian actor per agent: csrc/actor_mlp.hip's per-agent form, or csrc/actor_unshared.hip with the gradient at the
             # new hidden state, and csrc/gauss.hip's per-agent heads — for eager calls.  While a HIP graph is captured (or audited
             # for a capture) the loop below runs, and nothing is noted.
             out = self._policy_per_agent_eager(obs, last_hid, gauss)

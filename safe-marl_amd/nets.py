@@ -96,7 +96,7 @@ class RNNAgent(nn.Module):
             r = self.rnn
             means, h = self._train_node().apply(obs, hx0, n_agents, bool(agent_id), W, self.fc1.bias,
                                                 None if ln is None else ln.weight, None if ln is None else ln.bias,
-                                                1e-5 if ln is None else ln.eps, r.weight_ih, r.weight_hh, r.bias_ih, r.bias_hh,
+                                                _ln_eps(self), r.weight_ih, r.weight_hh, r.bias_ih, r.bias_hh,
                                                 self.fc2.weight, self.fc2.bias)
             return means, None, h
         if not (obs.is_cuda and obs.dtype == th.float32 and lnrelu_supported(self, n_agents) and _FUSED_GRU is not None
@@ -108,7 +108,7 @@ class RNNAgent(nn.Module):
         z = wide_batch_linear(obs, W[:, :o]) if not obs.requires_grad else tall_linear(obs, W[:, :o])
         ln = self.layernorm if self.args.layernorm else None
         x = _LnReluFn.apply(z, self.fc1.bias, W[:, o:].t() if agent_id else None, None if ln is None else ln.weight,
-                            None if ln is None else ln.bias, 1e-5 if ln is None else ln.eps, n_agents)
+                            None if ln is None else ln.bias, _ln_eps(self), n_agents)
         r, hx = self.rnn, hidden_state.reshape(-1, self.args.hid_size)
         h = _gru_cell(x, hx, r)
         return tall_linear(h, self.fc2.weight, self.fc2.bias), None, h
@@ -122,7 +122,7 @@ class MLPAgent(nn.Module):
     """madrl/agents/mlp_agent.py:5-32 (agent_type: mlp): fc1 -> LayerNorm -> act -> fc2 -> act -> fc3; forward returns
     (action mean, None, h).  This ``forward`` is the tensor composition; on the GPU under ``shared_params`` ``Model.policy``
     takes csrc/actor_mlp.hip instead (``fused_actor_forward_mlp`` / ``actor_mlp_train``) wherever no HIP graph is being
-    captured, and under ``shared_params: False`` csrc/actor_mlp_unshared.hip over all the agents' modules
+    captured, and under ``shared_params: False`` csrc/actor_mlp.hip's per-agent form over all the agents' modules
     (``fused_actor_forward_mlp_unshared`` / ``actor_mlp_unshared_train``).  ``fused_inference`` / ``fused_training`` (read with getattr, default True): the two switches of those paths."""
 
     def __init__(self, input_shape, args):
@@ -409,7 +409,7 @@ def fused_actor_forward(agent, obs, hidden, n_agents, agent_id, noise=None, std=
         hid_out = th.empty(rows, 64, dtype=th.float32, device=obs.device)
     args = _lib.FlexActorArgs()
     args.rows, args.n_agents, args.obs_dim, args.act_dim = rows, n_agents, obs_dim, a.action_dim
-    args.agent_id, args.layernorm, args.ln_eps = int(bool(agent_id)), int(bool(a.layernorm)), 1e-5
+    args.agent_id, args.layernorm, args.ln_eps = int(bool(agent_id)), int(bool(a.layernorm)), _ln_eps(agent)
     args.variant = int(ACTOR_VARIANT if variant is None else variant)
     action = env_action = None
     explore = noise is not None or rng_state is not None
@@ -431,8 +431,6 @@ def fused_actor_forward(agent, obs, hidden, n_agents, agent_id, noise=None, std=
             action = th.empty_like(means)
         args.std, args.action_low, args.action_high = float(std), float(low), float(high)
     ln = agent.layernorm if a.layernorm else None
-    if ln is not None:
-        args.ln_eps = float(ln.eps)
     for name, t in (("obs", obs), ("hidden_in", hidden), ("fc1_w", agent.fc1.weight), ("fc1_b", agent.fc1.bias),
                     ("ln_w", ln.weight if ln is not None else None), ("ln_b", ln.bias if ln is not None else None),
                     ("w_ih", agent.rnn.weight_ih), ("w_hh", agent.rnn.weight_hh), ("b_ih", agent.rnn.bias_ih),
@@ -457,8 +455,78 @@ def fused_actor_forward(agent, obs, hidden, n_agents, agent_id, noise=None, std=
     return (means, hid_out, action, env_action) if explore else (means, hid_out)
 
 
-_WGRAD_WS = {}
-WGRAD_MIN_ROWS = 2048          # below this the library GEMM is launch-bound either way
+# ---- plumbing that every fused family below shares ------------------------------------------------------------------------------
+_SCRATCH = {}
+
+
+def _scratch(name, device, numel, dtype=th.float32):
+    """The per-device scratch of one kernel family: ``numel`` elements of ``dtype``, allocated once per (name, device) and kept
+    (it never shrinks).  Calls of one family are expected on one stream at a time (the update's); a family whose calls may
+    run on several streams puts the stream into its ``name``."""
+    key = (name, device)
+    if key not in _SCRATCH:
+        _SCRATCH[key] = th.empty(numel, dtype=dtype, device=device)
+    return _SCRATCH[key]
+
+
+def _ln_eps(module):
+    """LayerNorm's eps of an agent or critic module (without LayerNorm the library's default: no kernel reads it then)."""
+    return float(module.layernorm.eps) if module.args.layernorm else 1e-5
+
+
+NOT_FP32_DEVICE = "a parameter is not a contiguous fp32 device tensor"
+
+
+def _params_decline(params):
+    """``NOT_FP32_DEVICE`` unless every parameter the kernels read through a raw pointer is a contiguous fp32 device tensor
+    (None, an absent LayerNorm pair, passes), else None."""
+    for p in params:
+        if p is not None and not (p.is_cuda and p.dtype == th.float32 and p.is_contiguous()):
+            return NOT_FP32_DEVICE
+    return None
+
+
+def _fill_tables(a, names, params, n):
+    """Writes ``params[i][k]`` of agent i < n into entry i of the pointer table ``names[k]`` of the ctypes struct ``a`` (None:
+    a null pointer); a table the struct does not have is skipped, so one list of names serves a family's forward and backward
+    structs."""
+    for k, name in enumerate(names):
+        table = getattr(a, name, None)
+        if table is not None:
+            for i in range(n):
+                p = params[i][k]
+                table[i] = None if p is None else p.data_ptr()
+
+
+def _regroup_params(saved, n, width, has_ln, ln_slots=(2, 3)):
+    """Per-agent parameter lists of ``width`` entries from ``saved``, the flat run of n agents' parameters that a node gave
+    ``save_for_backward`` without its None entries: without LayerNorm the ``ln_slots`` of every agent come back as None."""
+    absent = () if has_ln else ln_slots
+    per = width - len(absent)
+    out = []
+    for i in range(n):
+        it = iter(saved[per * i:per * (i + 1)])
+        out.append([None if k in absent else next(it) for k in range(width)])
+    return out
+
+
+def _fused_inference(key, why, on_gpu, entry, launch):
+    """The protocol of every ``fused_*_forward*`` below.  ``why``: the reason its kernel does not cover the call, or None;
+    a decline is noted under ``key`` on GPU tensors only (on the CPU the caller's composition is simply what runs).  Else
+    ``launch()`` under no_grad, whose None — the library answered FLEXNET_EUNSUPPORTED from ``entry`` — is noted too.  Returns
+    the launch's result, or None for "run the composition"."""
+    if why is not None:
+        if on_gpu:
+            note_fallback(key, why)
+        return None
+    with th.no_grad():
+        out = launch()
+    if out is None:
+        note_fallback(key, f"FLEXNET_EUNSUPPORTED from {entry}")
+    return out
+
+
+WGRAD_MIN_ROWS = 2048         # below this the library GEMM is launch-bound either way
 
 
 # the finish of the fused value loss rides in the first-layer weight gradient's second-stage launch (FLEX_WGRAD_FINISH_RIDER=0:
@@ -493,9 +561,7 @@ def tall_wgrad(dy, x, out=None, accumulate=False, colsum=None, x2=None, out2=Non
         out = th.empty(m, n, dtype=th.float32, device=dy.device)
     elif out.shape != (m, n) or out.dtype != th.float32 or (m > 1 and (out.stride(1) != 1 or out.stride(0) < n)):
         raise ValueError("tall_wgrad: `out` must be an fp32 [m, n] tensor or a column block of a wider one")
-    if dy.device not in _WGRAD_WS:
-        _WGRAD_WS[dy.device] = th.empty(_lib.FLEXNET_WGRAD_WS_FLOATS, dtype=th.float32, device=dy.device)
-    ws = _WGRAD_WS[dy.device]
+    ws = _scratch("wgrad", dy.device, _lib.FLEXNET_WGRAD_WS_FLOATS)
     a = _lib.FlexWgradArgs()
     a.k, a.m, a.n = k, m, n
     a.lda, a.ldb = (dy.stride(0), x.stride(0)) if k > 1 else (m, n)
@@ -688,14 +754,9 @@ def critic_first_layer(bias, obs2d, act2d, W, c_act):
     return shared
 
 
-_TD_WS = {}
-
-
 def _td_workspace(device):
     """Per-device fp64 scratch of csrc/tdloss.hip (statistics partials)."""
-    if device not in _TD_WS:
-        _TD_WS[device] = th.empty(_lib.FLEXNET_TD_WS_FLOATS // 2, dtype=th.float64, device=device)
-    return _TD_WS[device]
+    return _scratch("td", device, _lib.FLEXNET_TD_WS_FLOATS // 2, th.float64)
 
 
 # Cross-rank reward statistics (SURVEY.md 8e: "or all-reduce 2 x 5 moments"; off unless the trainer switches it on):
@@ -869,7 +930,9 @@ def td_loss(q, next_q, reward, done, gamma, bn=None, update_stats=True):
     return _TdLossFn.apply(q, next_q, reward, done, gamma, bn, update_stats)
 
 
-_LNRELU_WS = {}
+def _lnrelu_workspace(device):
+    """Per-device scratch of csrc/lnrelu.hip's backward and of the first layer's backward inside csrc/gru.hip (same partials)."""
+    return _scratch("lnrelu", device, _lib.FLEXNET_LNRELU_WS_FLOATS)
 
 
 def _lnrelu_args(z, bias, id_cols, ln_w, ln_b, eps, n_agents):
@@ -913,9 +976,7 @@ class _LnReluFn(th.autograd.Function):
             a.d_bias = small[2].data_ptr()
         if id_cols is not None:
             a.d_id = small[3:].data_ptr()
-        if z.device not in _LNRELU_WS:
-            _LNRELU_WS[z.device] = th.empty(_lib.FLEXNET_LNRELU_WS_FLOATS, dtype=th.float32, device=z.device)
-        ws = _LNRELU_WS[z.device]
+        ws = _lnrelu_workspace(z.device)
         a.workspace, a.workspace_floats = ws.data_ptr(), ws.numel()
         _lib.launch("flexnet_lnrelu_backward", a)
         return (dz, None if bias is None else small[2], None if id_cols is None else small[3:],
@@ -988,9 +1049,7 @@ class _ActorTrainFn(th.autograd.Function):
             dz = th.empty(rows, 64, dtype=th.float32, device=dev)
             small = th.empty(3, 64, dtype=th.float32, device=dev)
             d_fc1_w = th.empty_like(fc1_w)
-            if dev not in _LNRELU_WS:
-                _LNRELU_WS[dev] = th.empty(_lib.FLEXNET_LNRELU_WS_FLOATS, dtype=th.float32, device=dev)
-            ws = _LNRELU_WS[dev]
+            ws = _lnrelu_workspace(dev)
             g.w_ih, g.z1, g.fc1_w, g.dz = w_ih.data_ptr(), saved[0].data_ptr(), fc1_w.data_ptr(), dz.data_ptr()
             g.x = saved[1].data_ptr()                  # ReLU's mask: the forward's own output
             g.fc1_b = fc1_b.data_ptr() if fc1_b is not None else None
@@ -1031,9 +1090,7 @@ class _ActorTrainFn(th.autograd.Function):
         la.d_bias = small[2].data_ptr()
         if id_cols is not None:
             la.d_id = small[3:].data_ptr()
-        if dev not in _LNRELU_WS:
-            _LNRELU_WS[dev] = th.empty(_lib.FLEXNET_LNRELU_WS_FLOATS, dtype=th.float32, device=dev)
-        ws = _LNRELU_WS[dev]
+        ws = _lnrelu_workspace(dev)
         la.workspace, la.workspace_floats = ws.data_ptr(), ws.numel()
         _lib.launch("flexnet_lnrelu_backward", la)
         if _DEBUG_KEEP is not None:
@@ -1068,7 +1125,6 @@ def actor_train_supported(agent, obs, n_agents, agent_id):
             and getattr(agent, "fused_training", True) and getattr(agent, "fused_epilogue", True))
 
 
-_UNSHARED_WS = {}
 _UNSHARED_TABLES = ("fc1_w", "fc1_b", "ln_w", "ln_b", "w_ih", "w_hh", "b_ih", "b_hh", "fc2_w", "fc2_b")
 ACTOR_UNSHARED_MAX_ROWS = 1 << 26        # csrc/wgrad.hip addresses a block's rows through 32-bit byte offsets
 
@@ -1100,9 +1156,9 @@ def _unshared_declines(agents, obs, agent_id, kind=None):
             return f"agent {i}: fc1 takes {agent.fc1.weight.shape[1]} columns, obs {o}, agent_id {bool(agent_id)}"
         if not (getattr(agent, "fused_training", True) and getattr(agent, "fused_epilogue", True)):
             return f"agent {i}: fused passes switched off"
-        for p in _unshared_params(agent):
-            if p is not None and not (p.is_cuda and p.dtype == th.float32 and p.is_contiguous()):
-                return f"agent {i}: a parameter is not a contiguous fp32 device tensor"
+        why = _params_decline(_unshared_params(agent))
+        if why is not None:
+            return f"agent {i}: {why}"
     return None
 
 
@@ -1117,13 +1173,7 @@ def _unshared_args(cls, params, rows, n, o, act_dim, agent_id, ln_eps):
     a = cls()
     a.rows, a.n_agents, a.obs_dim, a.act_dim = rows, n, o, act_dim
     a.agent_id, a.layernorm, a.ln_eps = int(bool(agent_id)), int(params[0][2] is not None), float(ln_eps)
-    names = {f[0] for f in cls._fields_}
-    for k, name in enumerate(_UNSHARED_TABLES):
-        if name in names:
-            table = getattr(a, name)
-            for i in range(n):
-                p = params[i][k]
-                table[i] = None if p is None else p.data_ptr()
+    _fill_tables(a, _UNSHARED_TABLES, params, n)
     return a
 
 
@@ -1144,10 +1194,6 @@ def _unshared_launch_forward(params, obs, hidden, n, agent_id, ln_eps, saved=Non
     return means, hid_out
 
 
-def _unshared_ln_eps(agents):
-    return float(agents[0].layernorm.eps) if agents[0].args.layernorm else 1e-5
-
-
 def fused_actor_forward_unshared(agents, obs, hidden):
     """model.py:124-138 (one RNNAgent per agent) without an autograd graph, in ONE HIP launch (csrc/actor_unshared.hip) instead
     of the loop's ten kernels per agent.  ``obs`` [b, n, obs_dim] WITHOUT the one-hot id columns (agent i's own id column of
@@ -1159,17 +1205,12 @@ def fused_actor_forward_unshared(agents, obs, hidden):
     why = _unshared_declines(agents, obs, agent_id, RNNAgentGaussian if type(agents[0]) is RNNAgentGaussian else None)
     if why is None and hidden.dtype != th.float32:
         why = f"hidden {hidden.dtype}"
-    if why is not None:
-        if obs.is_cuda:
-            note_fallback("actor_unshared", why)
-        return None
-    rows = obs.shape[0] * n
-    with th.no_grad():
-        out = _unshared_launch_forward([_unshared_params(g) for g in agents], obs.reshape(rows, o).contiguous(),
-                                       hidden.reshape(rows, 64).contiguous(), n, agent_id, _unshared_ln_eps(agents))
-    if out is None:
-        note_fallback("actor_unshared", "FLEXNET_EUNSUPPORTED from flexnet_actor_unshared_forward")
-    return out
+
+    def launch():
+        rows = obs.shape[0] * n
+        return _unshared_launch_forward([_unshared_params(g) for g in agents], obs.reshape(rows, o).contiguous(),
+                                        hidden.reshape(rows, 64).contiguous(), n, agent_id, _ln_eps(agents[0]))
+    return _fused_inference("actor_unshared", why, obs.is_cuda, "flexnet_actor_unshared_forward", launch)
 
 
 class _ActorUnsharedTrainFn(th.autograd.Function):
@@ -1202,11 +1243,7 @@ class _ActorUnsharedTrainFn(th.autograd.Function):
     def backward(ctx, d_means, d_hid):
         obs, hidden, hid_out, saved = ctx.saved_tensors[:4]
         n, dev, has_ln = ctx.n_agents, obs.device, ctx.has_ln
-        per = 10 if has_ln else 8
-        params = []
-        for i in range(n):
-            p = list(ctx.saved_tensors[4 + per * i:4 + per * (i + 1)])
-            params.append(p if has_ln else p[:2] + [None, None] + p[2:])
+        params = _regroup_params(ctx.saved_tensors[4:], n, 10, has_ln)
         rows, o = obs.shape
         b, act_dim = rows // n, params[0][8].shape[0]
         if d_means is None and d_hid is None:
@@ -1216,9 +1253,7 @@ class _ActorUnsharedTrainFn(th.autograd.Function):
         d_gh = th.empty(rows, 192, dtype=th.float32, device=dev)
         dz = th.empty(rows, 64, dtype=th.float32, device=dev)
         small = th.empty(3, n, 64, dtype=th.float32, device=dev)                   # d_ln_w | d_ln_b | d_fc1_b
-        if dev not in _UNSHARED_WS:
-            _UNSHARED_WS[dev] = th.empty(_lib.FLEXNET_ACTOR_UNSHARED_WS_FLOATS, dtype=th.float32, device=dev)
-        ws = _UNSHARED_WS[dev]
+        ws = _scratch("actor_unshared", dev, _lib.FLEXNET_ACTOR_UNSHARED_WS_FLOATS)
         g = _unshared_args(_lib.FlexActorUnsharedBwdArgs, params, rows, n, o, act_dim, ctx.agent_id, ctx.ln_eps)
         g.d_means, g.h_prev = d_means.data_ptr(), hidden.data_ptr()
         g.z1, g.x, g.r, g.z, g.n, g.hn = (saved[k].data_ptr() for k in range(6))
@@ -1275,11 +1310,10 @@ def actor_unshared_train(agents, obs, hidden):
     agent_id = agents[0].fc1.weight.shape[1] != o
     flat = [p for g in agents for p in _unshared_params(g)]
     node = _ActorUnsharedTrainHidFn if type(agents[0]) is RNNAgentGaussian else _ActorUnsharedTrainFn
-    return node.apply(obs.reshape(-1, o), hidden.reshape(-1, 64), n, agent_id, _unshared_ln_eps(agents), *flat)
+    return node.apply(obs.reshape(-1, o), hidden.reshape(-1, 64), n, agent_id, _ln_eps(agents[0]), *flat)
 
 
 # ---- the per-agent critics of shared_params: False (csrc/critic_unshared.hip) ------------------------------------------------
-_CRITIC_UNSHARED_WS = {}
 _CRITIC_UNSHARED_TABLES = ("fc1_w", "fc1_b", "ln_w", "ln_b", "fc2_w", "fc2_b", "fc3_w", "fc3_b")
 
 
@@ -1324,9 +1358,9 @@ def _critic_unshared_declines(critics, x1, x2, shared):
             return f"critic {i} differs from critic 0 in its input width or LayerNorm"
         if not getattr(c, "fused_tail", True):
             return f"critic {i}: fused passes switched off"
-        for p in _critic_unshared_params(c):
-            if p is not None and not (p.is_cuda and p.dtype == th.float32 and p.is_contiguous()):
-                return f"critic {i}: a parameter is not a contiguous fp32 device tensor"
+        why = _params_decline(_critic_unshared_params(c))
+        if why is not None:
+            return f"critic {i}: {why}"
     return None
 
 
@@ -1345,13 +1379,7 @@ def _critic_unshared_args(cls, params, x1, x2, shared, ln_eps):
     a = cls()
     a.rows, a.n_agents, a.w1, a.w2 = b * n, n, w1, w2
     a.agent_id, a.layernorm, a.ln_eps = int(params[0][0].shape[1] != w1 + w2), int(params[0][2] is not None), float(ln_eps)
-    names = {f[0] for f in cls._fields_}
-    for k, name in enumerate(_CRITIC_UNSHARED_TABLES):
-        if name in names:
-            table = getattr(a, name)
-            for i in range(n):
-                p = params[i][k]
-                table[i] = None if p is None else p.data_ptr()
+    _fill_tables(a, _CRITIC_UNSHARED_TABLES, params, n)
     return a
 
 
@@ -1372,10 +1400,6 @@ def _critic_unshared_launch_forward(params, x1, x2, shared, ln_eps, saved=None):
     return q
 
 
-def _critic_unshared_ln_eps(critics):
-    return float(critics[0].layernorm.eps) if critics[0].args.layernorm else 1e-5
-
-
 def fused_critic_forward_unshared(critics, x1, x2=None, shared=False):
     """model.py:124-138 (one MLPCritic per agent) without an autograd graph, in ONE HIP launch (csrc/critic_unshared.hip) at
     any batch size, instead of the loop's clone / eye / cat and ten kernels per agent.  ``x1`` [b, n, o] (observations) and
@@ -1384,16 +1408,11 @@ def fused_critic_forward_unshared(critics, x1, x2=None, shared=False):
     Returns q [b, n], or None after ``note_fallback("critic_unshared", ...)`` when it declines on GPU tensors."""
     critics = list(critics)
     why = _critic_unshared_declines(critics, x1, x2, shared)
-    if why is not None:
-        if x1.is_cuda:
-            note_fallback("critic_unshared", why)
-        return None
-    with th.no_grad():
-        q = _critic_unshared_launch_forward([_critic_unshared_params(c) for c in critics], x1.contiguous(),
-                                            None if x2 is None else x2.contiguous(), shared, _critic_unshared_ln_eps(critics))
-    if q is None:
-        note_fallback("critic_unshared", "FLEXNET_EUNSUPPORTED from flexnet_critic_unshared_forward")
-    return q
+
+    def launch():
+        return _critic_unshared_launch_forward([_critic_unshared_params(c) for c in critics], x1.contiguous(),
+                                               None if x2 is None else x2.contiguous(), shared, _ln_eps(critics[0]))
+    return _fused_inference("critic_unshared", why, x1.is_cuda, "flexnet_critic_unshared_forward", launch)
 
 
 class _CriticUnsharedFn(th.autograd.Function):
@@ -1430,11 +1449,7 @@ class _CriticUnsharedFn(th.autograd.Function):
             x2, rest = rest[0], rest[1:]
         b, n, _ = x1.shape
         dev, has_ln, shared = x1.device, ctx.has_ln, ctx.shared
-        per = 8 if has_ln else 6
-        params = []
-        for i in range(n):
-            p = list(rest[per * i:per * (i + 1)])
-            params.append(p if has_ln else p[:2] + [None, None] + p[2:])
+        params = _regroup_params(rest, n, 8, has_ln)
         if dq is None:
             return (None,) * (5 + 8 * n)
         rows = b * n
@@ -1454,9 +1469,7 @@ class _CriticUnsharedFn(th.autograd.Function):
             dz2 = th.empty(rows, 64, dtype=th.float32, device=dev)
             small = th.empty(5, n, 64, dtype=th.float32, device=dev)          # d_ln_w | d_ln_b | d_fc1_b | d_fc2_b | d_fc3_w
             d_fc3_b = th.empty(n, 1, dtype=th.float32, device=dev)
-            if dev not in _CRITIC_UNSHARED_WS:
-                _CRITIC_UNSHARED_WS[dev] = th.empty(_lib.FLEXNET_CRITIC_UNSHARED_WS_FLOATS, dtype=th.float32, device=dev)
-            ws = _CRITIC_UNSHARED_WS[dev]
+            ws = _scratch("critic_unshared", dev, _lib.FLEXNET_CRITIC_UNSHARED_WS_FLOATS)
             g.dz2, g.d_fc3_b = dz2.data_ptr(), d_fc3_b.data_ptr()
             g.d_ln_w, g.d_ln_b, g.d_fc1_b, g.d_fc2_b, g.d_fc3_w = (small[k].data_ptr() for k in range(5))
             g.workspace, g.workspace_floats = ws.data_ptr(), ws.numel()
@@ -1491,13 +1504,10 @@ def critic_unshared_train(critics, x1, x2=None, shared=False, param_grads=True):
     """The node on the blocks x1 [b, n, o] / x2 [b, n, a] or None (``critic_unshared_supported(..., train=True)`` holds): q [b, n]."""
     critics = list(critics)
     flat = [p for c in critics for p in _critic_unshared_params(c)]
-    return _CriticUnsharedFn.apply(x1, x2, shared, _critic_unshared_ln_eps(critics), param_grads, *flat)
+    return _CriticUnsharedFn.apply(x1, x2, shared, _ln_eps(critics[0]), param_grads, *flat)
 
 
 # ---- the MLP actor of agent_type mlp under shared_params (csrc/actor_mlp.hip): eager calls only --------------------------------
-_ACTOR_MLP_WS = {}
-
-
 def mlp_actor_allowed():
     """The capture rule of csrc/actor_mlp.hip: its entry points are launched eagerly only.  False while the
     current stream is capturing a HIP graph and while ``util.audit_graph_body`` runs a body on behalf of a capture site (the
@@ -1530,10 +1540,7 @@ def actor_mlp_declines(agent, obs, n_agents, agent_id):
         return f"obs {tuple(obs.shape)} for {n_agents} agents"
     if agent.fc1.weight.shape[1] != o + (n_agents if agent_id else 0):
         return f"fc1 takes {agent.fc1.weight.shape[1]} columns, obs {o}, agent_id {bool(agent_id)}"
-    for p in _actor_mlp_params(agent):
-        if p is not None and not (p.is_cuda and p.dtype == th.float32 and p.is_contiguous()):
-            return "a parameter is not a contiguous fp32 device tensor"
-    return None
+    return _params_decline(_actor_mlp_params(agent))
 
 
 def actor_mlp_supported(agent, obs, n_agents, agent_id):
@@ -1569,26 +1576,55 @@ def _actor_mlp_launch_forward(params, obs, n, agent_id, ln_eps, saved=None):
     return means, h
 
 
-def _actor_mlp_ln_eps(agent):
-    return float(agent.layernorm.eps) if agent.args.layernorm else 1e-5
-
-
 def fused_actor_forward_mlp(agent, obs, n_agents, agent_id):
     """mlp_agent.py:20-32 + model.py:102-116 without an autograd graph, in ONE HIP launch (csrc/actor_mlp.hip) at any batch
     size, instead of the module's ten kernels.  ``obs`` [b, n, obs_dim] WITHOUT the one-hot id columns (the kernel adds fc1's id
     column of row r % n itself).  Returns (means [b * n, act], h [b * n, 64]), or None after ``note_fallback("actor_forward",
     ...)`` when it declines on GPU tensors.  Never called under a capture (``mlp_actor_allowed``)."""
     why = actor_mlp_declines(agent, obs, n_agents, agent_id)
-    if why is not None:
-        if obs.is_cuda:
-            note_fallback("actor_forward", why)
-        return None
-    with th.no_grad():
-        out = _actor_mlp_launch_forward(_actor_mlp_params(agent), obs.reshape(-1, obs.shape[-1]).contiguous(), n_agents, agent_id,
-                                        _actor_mlp_ln_eps(agent))
+
+    def launch():
+        return _actor_mlp_launch_forward(_actor_mlp_params(agent), obs.reshape(-1, obs.shape[-1]).contiguous(), n_agents, agent_id,
+                                         _ln_eps(agent))
+    return _fused_inference("actor_forward", why, obs.is_cuda, "flexnet_actor_mlp_forward", launch)
+
+
+def _actor_mlp_node_forward(ctx, launch_forward, entry, params, keep, obs, n_agents, agent_id, ln_eps, hid_grad):
+    """What the ``forward`` of the two MLP-actor nodes share: ``launch_forward`` (``_actor_mlp_launch_forward`` or its per-agent
+    form, whose entry point is ``entry``) on ``params`` with the saves z1 | x, then the bookkeeping — obs, h, the saves and
+    ``keep`` (the weights the backward reads) saved, h non-differentiable unless ``hid_grad``, no zero-filled gradients."""
+    obs = obs.contiguous()
+    saved = th.empty(2, obs.shape[0], 64, dtype=th.float32, device=obs.device)               # z1 | x
+    out = launch_forward(params, obs, n_agents, agent_id, ln_eps, saved)
     if out is None:
-        note_fallback("actor_forward", "FLEXNET_EUNSUPPORTED from flexnet_actor_mlp_forward")
-    return out
+        _lib.check(_lib.FLEXNET_EUNSUPPORTED, entry)
+    means, h = out
+    ctx.n_agents, ctx.agent_id, ctx.ln_eps = n_agents, bool(agent_id), float(ln_eps)
+    ctx.save_for_backward(obs, h, saved, *keep)
+    if not hid_grad:
+        ctx.mark_non_differentiable(h)
+    ctx.set_materialize_grads(False)
+    return means, h
+
+
+def _actor_mlp_node_backward_args(cls, ctx, ws, act_dim, ln_w, d_means, d_h):
+    """What the ``backward`` of the two MLP-actor nodes share: d_means made dense (zeros where only h took a gradient), dz1 | dz2
+    allocated, and ``cls`` (FlexActorMlpBwdArgs or its per-agent form) filled up to the weight pointers and the vector sums'
+    outputs, which differ: the sizes and switches, d_means, the optional d_h, the three saves, dz1, dz2 and the workspace
+    ``ws``.  Returns (args, d_means, dz, d_h); the caller holds d_h until the launch."""
+    obs, h, saved = ctx.saved_tensors[:3]
+    rows, o = obs.shape
+    dev = obs.device
+    d_means = th.zeros(rows, act_dim, dtype=th.float32, device=dev) if d_means is None else d_means.contiguous()
+    dz = th.empty(2, rows, 64, dtype=th.float32, device=dev)                               # dz1 | dz2
+    g = _actor_mlp_head(cls, rows, ctx.n_agents, o, act_dim, ctx.agent_id, ln_w, ctx.ln_eps)
+    g.d_means, g.z1, g.x, g.h = d_means.data_ptr(), saved[0].data_ptr(), saved[1].data_ptr(), h.data_ptr()
+    if d_h is not None:
+        d_h = d_h.contiguous()
+        g.d_h = d_h.data_ptr()
+    g.dz1, g.dz2 = dz[0].data_ptr(), dz[1].data_ptr()
+    g.workspace, g.workspace_floats = ws.data_ptr(), ws.numel()
+    return g, d_means, dz, d_h
 
 
 class _ActorMlpTrainFn(th.autograd.Function):
@@ -1600,44 +1636,26 @@ class _ActorMlpTrainFn(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, obs, n_agents, agent_id, ln_eps, hid_grad, fc1_w, fc1_b, ln_w, ln_b, fc2_w, fc2_b, fc3_w, fc3_b):
-        obs = obs.contiguous()
-        saved = th.empty(2, obs.shape[0], 64, dtype=th.float32, device=obs.device)           # z1 | x
-        out = _actor_mlp_launch_forward((fc1_w, fc1_b, ln_w, ln_b, fc2_w, fc2_b, fc3_w, fc3_b), obs, n_agents, agent_id, ln_eps, saved)
-        if out is None:
-            _lib.check(_lib.FLEXNET_EUNSUPPORTED, "flexnet_actor_mlp_forward")
-        means, h = out
-        ctx.n_agents, ctx.agent_id, ctx.ln_eps = n_agents, bool(agent_id), float(ln_eps)
-        ctx.save_for_backward(obs, h, saved, fc1_w, ln_w, fc2_w, fc3_w)
-        if not hid_grad:
-            ctx.mark_non_differentiable(h)
-        ctx.set_materialize_grads(False)
-        return means, h
+        return _actor_mlp_node_forward(ctx, _actor_mlp_launch_forward, "flexnet_actor_mlp_forward",
+                                       (fc1_w, fc1_b, ln_w, ln_b, fc2_w, fc2_b, fc3_w, fc3_b), (fc1_w, ln_w, fc2_w, fc3_w),
+                                       obs, n_agents, agent_id, ln_eps, hid_grad)
 
     @staticmethod
     def backward(ctx, d_means, d_h):
         obs, h, saved, fc1_w, ln_w, fc2_w, fc3_w = ctx.saved_tensors
         if d_means is None and d_h is None:
             return (None,) * 13
-        rows, o = obs.shape
+        o = obs.shape[1]
         n, dev, act_dim, has_ln = ctx.n_agents, obs.device, fc3_w.shape[0], ln_w is not None
-        d_means = th.zeros(rows, act_dim, dtype=th.float32, device=dev) if d_means is None else d_means.contiguous()
-        dz = th.empty(2, rows, 64, dtype=th.float32, device=dev)                           # dz1 | dz2
         small = th.empty(4, 64, dtype=th.float32, device=dev)                              # d_ln_w | d_ln_b | d_fc1_b | d_fc2_b
         d_fc3_b = th.empty(act_dim, dtype=th.float32, device=dev)
         d_id = th.empty(n, 64, dtype=th.float32, device=dev)
-        if dev not in _ACTOR_MLP_WS:
-            _ACTOR_MLP_WS[dev] = th.empty(_lib.FLEXNET_ACTOR_MLP_WS_FLOATS, dtype=th.float32, device=dev)
-        ws = _ACTOR_MLP_WS[dev]
-        g = _actor_mlp_head(_lib.FlexActorMlpBwdArgs, rows, n, o, act_dim, ctx.agent_id, ln_w, ctx.ln_eps)
-        g.d_means, g.z1, g.x, g.h = d_means.data_ptr(), saved[0].data_ptr(), saved[1].data_ptr(), h.data_ptr()
-        if d_h is not None:
-            d_h = d_h.contiguous()
-            g.d_h = d_h.data_ptr()
-        g.fc2_w, g.fc3_w, g.dz1, g.dz2 = fc2_w.data_ptr(), fc3_w.data_ptr(), dz[0].data_ptr(), dz[1].data_ptr()
+        ws = _scratch("actor_mlp", dev, _lib.FLEXNET_ACTOR_MLP_WS_FLOATS)
+        g, d_means, dz, d_h = _actor_mlp_node_backward_args(_lib.FlexActorMlpBwdArgs, ctx, ws, act_dim, ln_w, d_means, d_h)
+        g.fc2_w, g.fc3_w = fc2_w.data_ptr(), fc3_w.data_ptr()
         if has_ln:
             g.ln_w, g.d_ln_w, g.d_ln_b = ln_w.data_ptr(), small[0].data_ptr(), small[1].data_ptr()
         g.d_fc1_b, g.d_fc2_b, g.d_fc3_b, g.d_dz1_agent = small[2].data_ptr(), small[3].data_ptr(), d_fc3_b.data_ptr(), d_id.data_ptr()
-        g.workspace, g.workspace_floats = ws.data_ptr(), ws.numel()
         _lib.launch("flexnet_actor_mlp_backward", g)
         d_fc1_w = th.empty_like(fc1_w)
         d_fc2_w = th.empty_like(fc2_w)
@@ -1652,12 +1670,11 @@ class _ActorMlpTrainFn(th.autograd.Function):
 def actor_mlp_train(agent, obs, n_agents, agent_id):
     """The node on obs [b, n, obs_dim] / [b * n, obs_dim] (``actor_mlp_supported`` holds, ``mlp_actor_allowed()``, obs takes no
     gradient): (means [b * n, act], h [b * n, 64]); for the Gaussian agent h carries the log-std head's gradient back."""
-    return _ActorMlpTrainFn.apply(obs.reshape(-1, obs.shape[-1]), n_agents, bool(agent_id), _actor_mlp_ln_eps(agent),
+    return _ActorMlpTrainFn.apply(obs.reshape(-1, obs.shape[-1]), n_agents, bool(agent_id), _ln_eps(agent),
                                   type(agent) is MLPAgentGaussian, *_actor_mlp_params(agent))
 
 
-# ---- the MLP actors of agent_type mlp under shared_params False (csrc/actor_mlp_unshared.hip): eager calls only ----------------
-_ACTOR_MLP_UNSHARED_WS = {}
+# ---- the MLP actors of agent_type mlp under shared_params False (csrc/actor_mlp.hip's per-agent form): eager calls only -------
 _ACTOR_MLP_TABLES = ("fc1_w", "fc1_b", "ln_w", "ln_b", "fc2_w", "fc2_b", "fc3_w", "fc3_b")
 
 
@@ -1681,7 +1698,7 @@ def _one_configuration(agents):
 
 
 def actor_mlp_unshared_declines(agents, obs, agent_id):
-    """Why csrc/actor_mlp_unshared.hip does not cover these per-agent MLP actors on ``obs`` [b, n, obs_dim] (no id columns), or
+    """Why csrc/actor_mlp.hip's per-agent form does not cover these per-agent MLP actors on ``obs`` [b, n, obs_dim] (no id columns), or
     None: ``actor_mlp_declines``'s predicates for every agent, and all agents of one class and one configuration."""
     agents = list(agents)
     n = len(agents)
@@ -1698,17 +1715,8 @@ def actor_mlp_unshared_declines(agents, obs, agent_id):
 
 
 def actor_mlp_unshared_supported(agents, obs, agent_id):
-    """What csrc/actor_mlp_unshared.hip covers: ``actor_mlp_supported`` for every agent, all of one class and configuration."""
+    """What csrc/actor_mlp.hip's per-agent form covers: ``actor_mlp_supported`` for every agent, all of one class and configuration."""
     return actor_mlp_unshared_declines(agents, obs, agent_id) is None
-
-
-def _fill_tables(a, names, params, n):
-    for k, name in enumerate(names):
-        table = getattr(a, name, None)
-        if table is not None:
-            for i in range(n):
-                p = params[i][k]
-                table[i] = None if p is None else p.data_ptr()
 
 
 def _actor_mlp_unshared_launch_forward(params, obs, n, agent_id, ln_eps, saved=None):
@@ -1730,7 +1738,7 @@ def _actor_mlp_unshared_launch_forward(params, obs, n, agent_id, ln_eps, saved=N
 
 def fused_actor_forward_mlp_unshared(agents, obs):
     """model.py:124-138 with one MLPAgent (or MLPAgentGaussian) per agent, without an autograd graph, in ONE HIP launch
-    (csrc/actor_mlp_unshared.hip) instead of the loop's ten kernels per agent.  ``obs`` [b, n, obs_dim] WITHOUT the one-hot id
+    (csrc/actor_mlp.hip's per-agent form) instead of the loop's ten kernels per agent.  ``obs`` [b, n, obs_dim] WITHOUT the one-hot id
     columns (agent i's own id column of its fc1 is added by the kernel).  Returns (means [b * n, act], h [b * n, 64]), or None
     after ``note_fallback("actor_mlp_unshared", ...)`` when it declines on GPU tensors.  Never called under a capture
     (``mlp_actor_allowed``)."""
@@ -1738,21 +1746,16 @@ def fused_actor_forward_mlp_unshared(agents, obs):
     n, o = len(agents), obs.shape[-1]
     agent_id = agents[0].fc1.weight.shape[1] != o
     why = actor_mlp_unshared_declines(agents, obs, agent_id)
-    if why is not None:
-        if obs.is_cuda:
-            note_fallback("actor_mlp_unshared", why)
-        return None
-    with th.no_grad():
-        out = _actor_mlp_unshared_launch_forward([_actor_mlp_params(g) for g in agents], obs.reshape(-1, o).contiguous(), n,
-                                                 agent_id, _actor_mlp_ln_eps(agents[0]))
-    if out is None:
-        note_fallback("actor_mlp_unshared", "FLEXNET_EUNSUPPORTED from flexnet_actor_mlp_unshared_forward")
-    return out
+
+    def launch():
+        return _actor_mlp_unshared_launch_forward([_actor_mlp_params(g) for g in agents], obs.reshape(-1, o).contiguous(), n,
+                                                  agent_id, _ln_eps(agents[0]))
+    return _fused_inference("actor_mlp_unshared", why, obs.is_cuda, "flexnet_actor_mlp_unshared_forward", launch)
 
 
 class _ActorMlpUnsharedTrainFn(th.autograd.Function):
     """The per-agent MLP actors of ``shared_params: False`` for an update batch as ONE autograd node over all agents' parameters
-    (csrc/actor_mlp_unshared.hip): the fused forward with its saves (z1, x; h is its second result), one backward launch for
+    (csrc/actor_mlp.hip's per-agent form): the fused forward with its saves (z1, x; h is its second result), one backward launch for
     dz1, dz2 and every agent's vector sums, then the 3 n weight gradients — per agent d_fc1_w's observation block, d_fc2_w and
     d_fc3_w over the agent's rows through the row pitch — as ONE flexnet_wgrad_batched call.  The id block of agent a's fc1
     gradient is zero except its own column a, which is its bias gradient (the one-hot input).  ``hid_grad``: h takes a gradient
@@ -1761,21 +1764,11 @@ class _ActorMlpUnsharedTrainFn(th.autograd.Function):
 
     @staticmethod
     def forward(ctx, obs, n_agents, agent_id, ln_eps, hid_grad, *flat):
-        obs = obs.contiguous()
         params = [flat[8 * i:8 * i + 8] for i in range(n_agents)]
-        saved = th.empty(2, obs.shape[0], 64, dtype=th.float32, device=obs.device)           # z1 | x
-        out = _actor_mlp_unshared_launch_forward(params, obs, n_agents, agent_id, ln_eps, saved)
-        if out is None:
-            _lib.check(_lib.FLEXNET_EUNSUPPORTED, "flexnet_actor_mlp_unshared_forward")
-        means, h = out
-        ctx.n_agents, ctx.agent_id, ctx.ln_eps = n_agents, bool(agent_id), float(ln_eps)
         ctx.has_ln = params[0][2] is not None
         keep = [p for q in params for p in (q[0], q[2], q[4], q[6]) if p is not None]        # fc1_w, ln_w, fc2_w, fc3_w
-        ctx.save_for_backward(obs, h, saved, *keep)
-        if not hid_grad:
-            ctx.mark_non_differentiable(h)
-        ctx.set_materialize_grads(False)
-        return means, h
+        return _actor_mlp_node_forward(ctx, _actor_mlp_unshared_launch_forward, "flexnet_actor_mlp_unshared_forward",
+                                       params, keep, obs, n_agents, agent_id, ln_eps, hid_grad)
 
     @staticmethod
     def backward(ctx, d_means, d_h):
@@ -1783,33 +1776,18 @@ class _ActorMlpUnsharedTrainFn(th.autograd.Function):
         n, dev, has_ln = ctx.n_agents, obs.device, ctx.has_ln
         if d_means is None and d_h is None:
             return (None,) * (5 + 8 * n)
-        per = 4 if has_ln else 3
-        kept = [list(ctx.saved_tensors[3 + per * i:3 + per * (i + 1)]) for i in range(n)]
-        if not has_ln:
-            kept = [[q[0], None, q[1], q[2]] for q in kept]
+        kept = _regroup_params(ctx.saved_tensors[3:], n, 4, has_ln, ln_slots=(1,))           # fc1_w, ln_w, fc2_w, fc3_w
         rows, o = obs.shape
         b, act_dim, ld = rows // n, kept[0][3].shape[0], kept[0][0].shape[1]
-        d_means = th.zeros(rows, act_dim, dtype=th.float32, device=dev) if d_means is None else d_means.contiguous()
-        dz = th.empty(2, rows, 64, dtype=th.float32, device=dev)                           # dz1 | dz2
         small = th.empty(4, n, 64, dtype=th.float32, device=dev)                           # d_ln_w | d_ln_b | d_fc1_b | d_fc2_b
         d_fc3_b = th.empty(n, act_dim, dtype=th.float32, device=dev)
-        if dev not in _ACTOR_MLP_UNSHARED_WS:
-            _ACTOR_MLP_UNSHARED_WS[dev] = th.empty(_lib.FLEXNET_ACTOR_MLP_UNSHARED_WS_FLOATS, dtype=th.float32, device=dev)
-        ws = _ACTOR_MLP_UNSHARED_WS[dev]
-        g = _actor_mlp_head(_lib.FlexActorMlpUnsharedBwdArgs, rows, n, o, act_dim, ctx.agent_id, kept[0][1], ctx.ln_eps)
-        g.d_means, g.z1, g.x, g.h = d_means.data_ptr(), saved[0].data_ptr(), saved[1].data_ptr(), h.data_ptr()
-        if d_h is not None:
-            d_h = d_h.contiguous()
-            g.d_h = d_h.data_ptr()
-        for i in range(n):
-            g.fc2_w[i], g.fc3_w[i] = kept[i][2].data_ptr(), kept[i][3].data_ptr()
-            if has_ln:
-                g.ln_w[i] = kept[i][1].data_ptr()
-        g.dz1, g.dz2 = dz[0].data_ptr(), dz[1].data_ptr()
+        ws = _scratch("actor_mlp_unshared", dev, _lib.FLEXNET_ACTOR_MLP_UNSHARED_WS_FLOATS)
+        g, d_means, dz, d_h = _actor_mlp_node_backward_args(_lib.FlexActorMlpUnsharedBwdArgs, ctx, ws, act_dim, kept[0][1],
+                                                            d_means, d_h)
+        _fill_tables(g, ("fc1_w", "ln_w", "fc2_w", "fc3_w"), kept, n)                      # (the backward has no fc1_w table)
         if has_ln:
             g.d_ln_w, g.d_ln_b = small[0].data_ptr(), small[1].data_ptr()
         g.d_fc1_b, g.d_fc2_b, g.d_fc3_b = small[2].data_ptr(), small[3].data_ptr(), d_fc3_b.data_ptr()
-        g.workspace, g.workspace_floats = ws.data_ptr(), ws.numel()
         _lib.launch("flexnet_actor_mlp_unshared_backward", g)
         d_fc1_w = (th.zeros if ctx.agent_id else th.empty)(n, 64, ld, dtype=th.float32, device=dev)
         d_fc2_w = th.empty(n, 64, 64, dtype=th.float32, device=dev)
@@ -1837,7 +1815,7 @@ def actor_mlp_unshared_train(agents, obs):
     n, o = len(agents), obs.shape[-1]
     agent_id = agents[0].fc1.weight.shape[1] != o
     flat = [p for g in agents for p in _actor_mlp_params(g)]
-    return _ActorMlpUnsharedTrainFn.apply(obs.reshape(-1, o), n, agent_id, _actor_mlp_ln_eps(agents[0]),
+    return _ActorMlpUnsharedTrainFn.apply(obs.reshape(-1, o), n, agent_id, _ln_eps(agents[0]),
                                           type(agents[0]) is MLPAgentGaussian, *flat)
 
 
@@ -1859,8 +1837,9 @@ def gauss_head_unshared_declines(agents, h):
         w, b = g.log_std.weight, g.log_std.bias
         if not (w.shape[1] == _lib.FLEXNET_HID and 1 <= w.shape[0] <= _lib.FLEXNET_MAX_ACT):
             return f"agent {i}: hid {w.shape[1]}, act_dim {w.shape[0]}"
-        if not all(p.is_cuda and p.dtype == th.float32 and p.is_contiguous() for p in (w, b)):
-            return f"agent {i}: a parameter is not a contiguous fp32 device tensor"
+        why = _params_decline((w, b))
+        if why is not None:
+            return f"agent {i}: {why}"
     return None
 
 
@@ -2005,7 +1984,7 @@ def _tail_params(critic):
     """(ln_w, ln_b, w2, b2, w3, b3, eps) of an MLPCritic: the tail's arguments, in the order every critic node takes them."""
     ln = critic.layernorm if critic.args.layernorm else None
     return (None if ln is None else ln.weight, None if ln is None else ln.bias, critic.fc2.weight, critic.fc2.bias,
-            critic.fc3.weight, critic.fc3.bias, 1e-5 if ln is None else ln.eps)
+            critic.fc3.weight, critic.fc3.bias, _ln_eps(critic))
 
 
 def _critic_args(z1, ln_w, ln_b, w2, b2, w3, b3, eps):
@@ -2033,14 +2012,9 @@ def _composed_args(shared, n, W, no, tail, dense_ids=None):
     return args
 
 
-_CRITIC_WS = {}
-
-
 def _critic_workspace(device):
     """Per-device scratch for the backward kernel's per-block partial sums (18 MB, allocated once)."""
-    if device not in _CRITIC_WS:
-        _CRITIC_WS[device] = th.empty(_lib.FLEXNET_CRITIC_WS_FLOATS, dtype=th.float32, device=device)
-    return _CRITIC_WS[device]
+    return _scratch("critic", device, _lib.FLEXNET_CRITIC_WS_FLOATS)
 
 
 def _bind_workspace(args, device, overwrite=False):
@@ -2323,7 +2297,7 @@ class _CriticTdLossFn(th.autograd.Function):
         dev = obs2d.device
         nq, r, d = next_q.reshape(-1, n).contiguous(), reward.contiguous(), done.reshape(-1).contiguous()
         t = _td_args(r, d, nq, gamma, bn, update_stats=True)
-        _td_sync_stats(t, _TD_WS[r.device], bn)
+        _td_sync_stats(t, _td_workspace(r.device), bn)
         offer = TD_OFFERS.get(r.data_ptr())
         if offer is not None and offer["ref"]() is None:
             del TD_OFFERS[r.data_ptr()]
@@ -2752,9 +2726,6 @@ class _QmixFn(th.autograd.Function):
 
 
 # ---- SQDDPG's Shapley-value critic (madrl/models/sqddpg.py:35-104) -------------------------------------------------------
-_SQDDPG_WS = {}
-
-
 def sqddpg_fused_config(critic, n_agents, act_dim, sample_size):
     """The configuration csrc/sqddpg.hip implements (include/flexnet.h: flexnet_sqddpg_forward): a shared MLPCritic with hid
     64, ReLU and one output, the agent id columns, n <= 8 agents, act_dim <= 8 with n * act_dim <= 32."""
@@ -2836,14 +2807,12 @@ class _SqddpgFn(th.autograd.Function):
             k.d_act_own = da.data_ptr()
         grads = [None] * 8
         if want_w:
-            if dev not in _SQDDPG_WS:
-                _SQDDPG_WS[dev] = th.empty(_lib.FLEXNET_SQDDPG_BWD_GRID * _lib.FLEXNET_SQDDPG_WS_ROW, dtype=th.float32,
-                                           device=dev)
+            ws = _scratch("sqddpg", dev, _lib.FLEXNET_SQDDPG_BWD_GRID * _lib.FLEXNET_SQDDPG_WS_ROW)
             grads = [th.empty(n, 64, device=dev), th.empty(64, n * ad, device=dev), th.zeros(64, device=dev),
                      th.zeros(64, device=dev), th.empty(64, 64, device=dev), th.empty(64, device=dev),
                      th.empty(1, 64, device=dev), th.empty(1, device=dev)]
             k.want_param_grads = 1
-            k.workspace = _SQDDPG_WS[dev].data_ptr()
+            k.workspace = ws.data_ptr()
             for name, t in zip(("d_z_id", "d_w_act", "d_ln_w", "d_ln_b", "d_fc2_w", "d_fc2_b", "d_fc3_w", "d_fc3_b"), grads):
                 setattr(k, name, t.data_ptr())
         _lib.launch("flexnet_sqddpg_backward", k)
@@ -2874,16 +2843,10 @@ def sqddpg_shapley_fused(critic, obs2d, act, pos, ns, want_q=False, frozen=False
 # Three pieces, each as a fused launch sequence of csrc/ppo.hip on the GPU and as the tensor composition of the same
 # formulas everywhere else (CPU, fp64, more than 8 agents, a masked action_avail, cross-rank BatchNorm statistics): the
 # composition is also what the GPU tests compare the kernels with.
-_PPO_WS = {}
-
-
 def _ppo_workspace(device):
     """The statistics and loss partials of one call, read by that call's own finish launch: one workspace per (device,
     stream), so calls on different streams never share one (calls on one stream run in order)."""
-    key = (device, th.cuda.current_stream(device).cuda_stream)
-    if key not in _PPO_WS:
-        _PPO_WS[key] = th.empty(_lib.FLEXNET_PPO_WS_FLOATS // 2, dtype=th.float64, device=device)
-    return _PPO_WS[key]
+    return _scratch(("ppo", th.cuda.current_stream(device).cuda_stream), device, _lib.FLEXNET_PPO_WS_FLOATS // 2, th.float64)
 
 
 def ppo_gae_torch(reward_norm, old_values, old_next_values, done, last_step, gamma, lambda_, chain_stride=1):
@@ -3120,9 +3083,6 @@ def ppo_value_loss(values, old_values, next_values, reward_norm, done, gamma, ep
 # The baseline as the launch of csrc/coma.hip on the GPU (from the first-layer pre-activation of the rows on the actions
 # taken: no [s b n, width] input exists) and as the reference's materialising composition everywhere else (CPU, fp64,
 # configurations the kernel does not cover); the composition is also what the GPU tests compare the kernel with.
-_COMA_WS = {}
-
-
 def coma_rows(obs, act, agent_id=True, per_row=False):
     """coma.py:41-78 (continuous branch): the critic's input rows [.., n, (n + 1) o + n + n a] =
     [o_1 .. o_n | o_i | onehot(i) | actions].  ``obs`` [b, n, o]; ``act`` [b, n, a] (every row of a sample sees the same n
@@ -3266,10 +3226,8 @@ def coma_policy_loss(means, log_stds, actions, actions_avail, values=None, basel
             want_dl = log_stds.requires_grad and not uniform
             d_log_stds = th.empty_like(m) if want_dl else m.new_empty(0)
             logp = th.empty(rows, n, dtype=th.float32, device=m.device)
-            key = (m.device, th.cuda.current_stream(m.device).cuda_stream)
-            if key not in _COMA_WS:
-                _COMA_WS[key] = th.empty(_lib.FLEXNET_COMA_WS_FLOATS // 2, dtype=th.float64, device=m.device)
-            ws = _COMA_WS[key]
+            ws = _scratch(("coma", th.cuda.current_stream(m.device).cuda_stream), m.device, _lib.FLEXNET_COMA_WS_FLOATS // 2,
+                          th.float64)
             k = _lib.FlexComaPolicyArgs()
             k.rows, k.n_agents, k.act_dim, k.log_std_uniform = rows, n, na, int(uniform)
             k.means, k.log_stds, k.actions = m.data_ptr(), ls.data_ptr(), act.data_ptr()
@@ -3417,19 +3375,13 @@ def attn_critic_declines(critic, obs, act):
         return f"{b} samples"
     if not getattr(critic, "fused", True):
         return "fused passes switched off"
-    for p in _attn_critic_params(critic):
-        if not (p.is_cuda and p.dtype == th.float32 and p.is_contiguous()):
-            return "a parameter is not a contiguous fp32 device tensor"
-    return None
+    return _params_decline(_attn_critic_params(critic))
 
 
 def _attn_critic_tables(k, flat, n):
+    """The pointers of ``flat`` (``_attn_critic_params``' order) into the forward's or the backward's struct ``k``."""
+    _fill_tables(k, _ATTN_CRITIC_TABLES, [flat[12 * i:12 * i + 12] for i in range(n)], n)
     names = {f[0] for f in k._fields_}
-    for c, name in enumerate(_ATTN_CRITIC_TABLES):
-        if name in names:
-            table = getattr(k, name)
-            for i in range(n):
-                table[i] = flat[12 * i + c].data_ptr()
     for c, name in enumerate(_ATTN_CRITIC_SHARED):
         if name in names:
             setattr(k, name, flat[12 * n + c].data_ptr())
@@ -3470,16 +3422,11 @@ def fused_attn_critic_forward(critic, obs, act):
     size: (q - b [b, n], regulariser [n]), or None after ``note_fallback("maac", ...)`` when it declines on GPU tensors.
     Never called under a capture (``mlp_actor_allowed``)."""
     why = attn_critic_declines(critic, obs, act)
-    if why is not None:
-        if obs.is_cuda:
-            note_fallback("maac", why)
-        return None
-    with th.no_grad():
-        out = _attn_critic_launch_forward(_attn_critic_params(critic), obs.contiguous(), act.contiguous())
-    if out is None:
-        note_fallback("maac", "FLEXNET_EUNSUPPORTED from flexnet_attn_critic_forward")
-        return None
-    return out[0], out[1]
+
+    def launch():
+        return _attn_critic_launch_forward(_attn_critic_params(critic), obs.contiguous(), act.contiguous())
+    out = _fused_inference("maac", why, obs.is_cuda, "flexnet_attn_critic_forward", launch)
+    return None if out is None else (out[0], out[1])
 
 
 class _AttnCriticFn(th.autograd.Function):

@@ -1,5 +1,5 @@
 """The MLP actors (csrc/actor_mlp.hip: nets.fused_actor_forward_mlp and the training node nets.actor_mlp_train;
-csrc/actor_mlp_unshared.hip: nets.fused_actor_forward_mlp_unshared and nets.actor_mlp_unshared_train) against the fp64 copies
+csrc/actor_mlp.hip's per-agent form: nets.fused_actor_forward_mlp_unshared and nets.actor_mlp_unshared_train) against the fp64 copies
 of the modules, on tests/fp64_budget.py's error budget and its families for a module with its own first layer: ``constant``
 is fc1.weight = 0 with one inexact bias value, so that every row's 64 LayerNorm inputs are equal bit for bit.  The figures of a
 run are filed in profiles/fp64_error_budget.txt."""

@@ -1,4 +1,4 @@
-"""The per-agent MLP actors (csrc/actor_mlp_unshared.hip), the per-agent log-std heads (csrc/gauss.hip) and the per-agent RNN
+"""The per-agent MLP actors (csrc/actor_mlp.hip's per-agent form), the per-agent log-std heads (csrc/gauss.hip) and the per-agent RNN
 backward's d_hn variant (csrc/actor_unshared.hip) on the host side, no GPU: the binding against include/flexnet.h, the argument
 checks that run before any device work, the kernels' resources as compiled, and the CPU dispatch."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""GPU: the per-agent MLP actors of ``shared_params: False`` in one launch per direction (csrc/actor_mlp_unshared.hip;
+"""GPU: the per-agent MLP actors of ``shared_params: False`` in one launch per direction (csrc/actor_mlp.hip's per-agent form;
 nets.fused_actor_forward_mlp_unshared, nets._ActorMlpUnsharedTrainFn) against the per-agent module loop (mlp_agent.py:20-32 on
 agent i's rows [obs | onehot(i)]) in fp64, and ``Model.policy``'s dispatch with its capture rule.  Nothing here captures a HIP
 graph: the rule is tested by patching what it asks.
@@ -290,16 +290,71 @@ def test_permuting_the_modules_permutes_the_outputs():
 
 @pytest.mark.parametrize("n,b", [(5, 64), (3, 257)])
 def test_identical_copies_agree_with_the_shared_kernel(n, b):
-    from safe_marl_amd.nets import fused_actor_forward_mlp, fused_actor_forward_mlp_unshared
-    agent = _agent(n, 144, 4, True, True, seed=3)
+    """The two forms are two instantiations of ONE kernel body per direction (csrc/actor_mlp.hip): on n copies of one agent
+    they give the same bits — means and h forward; dz1, dz2 backward (on the forward's own saves, a gradient at h present), and
+    the per-agent form's d_fc1_b[a] is the shared form's row a of d_dz1_agent: the same rows, folded and reduced in the same
+    order."""
+    from safe_marl_amd import _lib
+    from safe_marl_amd.nets import _actor_mlp_params, fused_actor_forward_mlp, fused_actor_forward_mlp_unshared
+    obs_dim, act_dim, rows = 144, 4, b * n
+    agent = _agent(n, obs_dim, act_dim, True, True, seed=3)
     copies = [copy.deepcopy(agent) for _ in range(n)]
-    obs = 0.5 * th.randn(b, n, 144, device="cuda")
+    obs = 0.5 * th.randn(b, n, obs_dim, device="cuda")
     ms, hs = fused_actor_forward_mlp(agent, obs, n, True)
     mu, hu = fused_actor_forward_mlp_unshared(copies, obs)
     for what, got, ref in (("means", mu, ms), ("h", hu, hs)):
-        err, bound = (got - ref).abs().max().item(), 2e-5 * max(1.0, ref.abs().max().item())
-        print(f"n {n} b {b} {what}: against the shared-weight kernel {err:.3e}, value bound {bound:.3e}")
-        assert err <= bound
+        print(f"n {n} b {b} {what}: against the shared-weight kernel {(got - ref).abs().max().item():.3e}")
+        assert th.equal(got, ref), what
+
+    # the backward entry points, each on its own form's forward with the saves (arguments as in
+    # test_entry_points_and_node_against_the_loop)
+    new = lambda *shape: th.full(shape, SENTINEL, dtype=th.float32, device="cuda")      # noqa: E731
+    d_means, d_h = th.randn(rows, act_dim, device="cuda") / rows, th.randn(rows, 64, device="cuda") / rows
+    bufs_u = {k: (None, new(rows, w)) for k, w in (("means", act_dim), ("h", 64), ("save_z1", 64), ("save_x", 64))}
+    _lib.launch("flexnet_actor_mlp_unshared_forward", _forward_args(copies, obs, True, bufs_u))
+    bufs_s = {k: new(rows, w) for k, w in (("means", act_dim), ("h", 64), ("save_z1", 64), ("save_x", 64))}
+    a = _lib.FlexActorMlpArgs()
+    a.rows, a.n_agents, a.obs_dim, a.act_dim, a.hid = rows, n, obs_dim, act_dim, 64
+    a.agent_id, a.layernorm, a.ln_eps = 1, 1, float(agent.layernorm.eps)
+    for name, p in zip(TABLES, _actor_mlp_params(agent)):
+        setattr(a, name, p.data_ptr())
+    a.obs = obs.data_ptr()
+    for k, t in bufs_s.items():
+        setattr(a, k, t.data_ptr())
+    _lib.launch("flexnet_actor_mlp_forward", a)
+    for k, t in bufs_s.items():
+        assert th.equal(bufs_u[k][1], t), k
+    assert th.equal(bufs_s["means"], ms) and th.equal(bufs_s["h"], hs)
+
+    out_u = {"dz1": new(rows, 64), "dz2": new(rows, 64), "d_ln_w": new(n, 64), "d_ln_b": new(n, 64), "d_fc1_b": new(n, 64),
+             "d_fc2_b": new(n, 64), "d_fc3_b": new(n, act_dim)}
+    out_s = {"dz1": new(rows, 64), "dz2": new(rows, 64), "d_ln_w": new(64), "d_ln_b": new(64), "d_fc1_b": new(64),
+             "d_fc2_b": new(64), "d_fc3_b": new(act_dim), "d_dz1_agent": new(n, 64)}
+    for cls, entry, outs, saves, floats in (
+            (_lib.FlexActorMlpUnsharedBwdArgs, "flexnet_actor_mlp_unshared_backward", out_u, {k: v[1] for k, v in bufs_u.items()},
+             _lib.FLEXNET_ACTOR_MLP_UNSHARED_WS_FLOATS),
+            (_lib.FlexActorMlpBwdArgs, "flexnet_actor_mlp_backward", out_s, bufs_s, _lib.FLEXNET_ACTOR_MLP_WS_FLOATS)):
+        ws = new(floats)
+        g = cls()
+        g.rows, g.n_agents, g.obs_dim, g.act_dim, g.hid = rows, n, obs_dim, act_dim, 64
+        g.agent_id, g.layernorm, g.ln_eps = 1, 1, float(agent.layernorm.eps)
+        g.d_means, g.d_h = d_means.data_ptr(), d_h.data_ptr()
+        g.z1, g.x, g.h = saves["save_z1"].data_ptr(), saves["save_x"].data_ptr(), saves["h"].data_ptr()
+        if outs is out_u:
+            _fill(g, copies, ("ln_w", "fc2_w", "fc3_w"))
+        else:
+            g.ln_w, g.fc2_w, g.fc3_w = agent.layernorm.weight.data_ptr(), agent.fc2.weight.data_ptr(), agent.fc3.weight.data_ptr()
+        for k, t in outs.items():
+            setattr(g, k, t.data_ptr())
+        g.workspace, g.workspace_floats = ws.data_ptr(), ws.numel()
+        _lib.launch(entry, g)
+    th.cuda.synchronize()
+    for k in ("dz1", "dz2"):
+        print(f"n {n} b {b} {k}: against the shared-weight kernel {(out_u[k] - out_s[k]).abs().max().item():.3e}")
+        assert th.equal(out_u[k], out_s[k]), k
+    assert bool((out_u["dz1"] != SENTINEL).all()) and bool((out_s["d_dz1_agent"] != SENTINEL).all())
+    for i in range(n):
+        assert th.equal(out_u["d_fc1_b"][i], out_s["d_dz1_agent"][i]), i
 
 
 def _model(n=5, cls="MADDPG", **over):

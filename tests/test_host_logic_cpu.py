@@ -198,3 +198,29 @@ def test_stacked_ring_bookkeeping_expands_every_slab_once_and_mirrors_the_head()
     assert buf.stack_gen == 2 and buf.stack_tail == 6 * N and buf.stacked_next is None
     buf.expand_stacked()
     check()
+
+
+def test_saved_parameters_regroup_per_agent_and_the_parameter_predicate():
+    """nets._regroup_params gives back, per agent, the parameter lists a node flattened into save_for_backward without their
+    None entries (the LayerNorm pair of a model without LayerNorm), and nets._params_decline names a parameter the kernels
+    cannot read through a raw pointer with the message every ``*_declines`` reports."""
+    from safe_marl_amd import nets
+    for has_ln in (True, False):
+        for n in (1, 3):
+            for width, ln_slots in ((10, (2, 3)), (8, (2, 3)), (4, (1,))):
+                params = [[None if (k in ln_slots and not has_ln) else torch.zeros(1) for k in range(width)] for _ in range(n)]
+                head = (torch.zeros(2), torch.zeros(3))                 # what a node saves before its parameters
+                saved = head + tuple(p for q in params for p in q if p is not None)
+                assert len(saved) == len(head) + n * (width if has_ln else width - len(ln_slots))
+                back = nets._regroup_params(saved[len(head):], n, width, has_ln, ln_slots=ln_slots)
+                assert len(back) == n and all(len(q) == width for q in back)
+                for q, want in zip(back, params):
+                    assert all(got is p for got, p in zip(q, want)), (has_ln, n, width)
+    assert nets._regroup_params(saved[2:], 3, 4, False, ln_slots=(1,))[2][1] is None
+    # the predicate: CPU, fp64 and non-contiguous tensors are named with the one message, None entries pass
+    msg = "a parameter is not a contiguous fp32 device tensor"
+    assert nets.NOT_FP32_DEVICE == msg
+    assert nets._params_decline([None, None]) is None and nets._params_decline([]) is None
+    assert nets._params_decline([None, torch.zeros(4)]) == msg           # not on the device
+    assert nets._params_decline([torch.zeros(4, dtype=torch.float64)]) == msg
+    assert nets._params_decline([torch.zeros(4, 4).t()[1:]]) == msg

@@ -1,4 +1,4 @@
-"""The per-agent MLP and Gaussian actors of ``shared_params: False`` (csrc/actor_mlp_unshared.hip, csrc/gauss.hip's per-agent heads,
+"""The per-agent MLP and Gaussian actors of ``shared_params: False`` (csrc/actor_mlp.hip's per-agent form, csrc/gauss.hip's per-agent heads,
 csrc/actor_unshared.hip's d_hn variant) against the per-agent module loop they replace — ``Model.policy`` with
 ``model.fused_inference = False`` — in ONE process on one GPU, on the same tensors, alternating: 5 agents, obs_dim 144, act_dim 4
 at 20 480 and 163 840 actor rows, for the MLP, the MLP-Gaussian and the RNN-Gaussian agents: ``policy()`` under no_grad, and
