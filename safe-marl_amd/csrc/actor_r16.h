@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "flexnet.h"
+#include "flex_nan.h"           // relu_nan, clamp_nan
 
 #ifndef HID
 #define HID FLEXNET_HID
@@ -15,13 +16,6 @@
 #define ASTAMP_C(k) do { } while (0)
 #endif
 
-// ReLU and clamp that hand a NaN on, as torch.relu / torch.clamp do (fmaxf / fminf return the other operand: a NaN observation
-// would come out as a finite action): IEEE 754-2019 maximum / minimum, one v_maximum3_f32 / v_minimum3_f32 each on gfx950.
-// Finite values: the same bits as fmaxf(v, 0) / fminf(fmaxf(v, lo), hi).
-__device__ __forceinline__ float relu_nan(float v) { return __builtin_elementwise_maximum(v, 0.0f); }
-__device__ __forceinline__ float clamp_nan(float v, float lo, float hi) {
-    return __builtin_elementwise_minimum(__builtin_elementwise_maximum(v, lo), hi);
-}
 // v_exp_f32 / v_rcp_f32 forms (about 1 ulp each): sigmoid(x) = 1 / (1 + 2^(-x log2 e)), tanh(x) = 1 - 2 / (2^(2x log2 e) + 1)
 __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * x)); }
 __device__ __forceinline__ float fast_tanh(float x) {

@@ -26,6 +26,7 @@
 #include "flexnet.h"
 #include "flex_launch.h"
 #include "flex_mfma_tile.h"
+#include "flex_nan.h"
 
 #define QM_WAVES 4                                   // wavefronts per block: 128 samples
 #define QM_E FLEXNET_QMIX_EMBED                      // 64
@@ -77,7 +78,7 @@ __global__ __launch_bounds__(64 * QM_WAVES, 1) void qmix_forward_kernel(FlexQmix
     for (int t = 0; t < 8; ++t) {
         if ((t >> 1) != 2) {                                    // hyper_b_1 is a single linear layer
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[t][r] = fmaxf(acc[t][r], 0.0f);
+            for (int r = 0; r < 16; ++r) acc[t][r] = relu_nan(acc[t][r]);     // a NaN weight must reach q_tot, as torch.relu's does
         }
     }
     if (a.h1) {
@@ -197,7 +198,8 @@ __global__ __launch_bounds__(64 * QM_WAVES, 1) void qmix_backward_kernel(FlexQmi
         if (h == 0 && ok) a.d_agent_qs[smp * n + ag] = tot;
     }
     if (!pg) return;
-    // ReLU masks; hyper_w_final's input gradient; V: d h1[192 + u] = g V2[u]
+    // ReLU masks, torch's threshold_backward: zero where h1 <= 0, so a NaN unit hands its gradient on; hyper_w_final's input
+    // gradient; V: d h1[192 + u] = g V2[u]
     tv16 d2 = tv16{}, d3 = tv16{};
 #pragma unroll
     for (int eh = 0; eh < 2; ++eh) {
@@ -206,10 +208,10 @@ __global__ __launch_bounds__(64 * QM_WAVES, 1) void qmix_backward_kernel(FlexQmi
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        dx0[r] = h0[r] > 0.0f ? dx0[r] : 0.0f;
-        dx1[r] = h1t[r] > 0.0f ? dx1[r] : 0.0f;
-        d2[r] = h2[r] > 0.0f ? d2[r] : 0.0f;
-        d3[r] = h3[r] > 0.0f ? d3[r] : 0.0f;
+        dx0[r] = h0[r] <= 0.0f ? 0.0f : dx0[r];
+        dx1[r] = h1t[r] <= 0.0f ? 0.0f : dx1[r];
+        d2[r] = h2[r] <= 0.0f ? 0.0f : d2[r];
+        d3[r] = h3[r] <= 0.0f ? 0.0f : d3[r];
     }
     store_tile(pr, dx0, ok);
     store_tile(pr + 32, dx1, ok);
@@ -220,7 +222,7 @@ __global__ __launch_bounds__(64 * QM_WAVES, 1) void qmix_backward_kernel(FlexQmi
         const tv16 hv = load_tile(hr + 192 + 32 * t);
         tv16 dv;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) dv[r] = hv[r] > 0.0f ? g * a.v_2_w[32 * t + TILE_U(r, h)] : 0.0f;
+        for (int r = 0; r < 16; ++r) dv[r] = hv[r] <= 0.0f ? 0.0f : g * a.v_2_w[32 * t + TILE_U(r, h)];
         store_tile(pr + 192 + 32 * t, dv, ok);
     }
 }

@@ -2670,6 +2670,8 @@ class _QmixFn(th.autograd.Function):
         q = q.contiguous()
         if x.stride(-1) != 1 or (x.shape[0] > 1 and x.stride(0) % 4 != 0) or x.data_ptr() % 16 != 0:
             x = x.contiguous()
+            if x.data_ptr() % 16 != 0:          # already contiguous on a base that is not: contiguous() hands the view back
+                x = x.clone()
         ws = [w.contiguous() for w in ws]
         B = q.shape[0]
         out = th.empty(B, dtype=th.float32, device=q.device)

@@ -8,9 +8,9 @@ LayerNorm, gate and ReLU code can go wrong without zero-mean, unit-scale inputs 
 gradient comparison the rows whose ReLU side is arbitrary in any fp32 form.
 
 The compositions below (``actor_plain``, ``mlp_actor_plain``, ``lnrelu_plain``, ``critic_tail_plain``, ``critic_plain``,
-``critic_first_layer_plain``, ``coma_baseline_plain``, ``sqddpg_plain``) are the layers of nets.RNNAgent / nets.MLPAgent /
-nets.MLPCritic written with torch.nn.functional alone, in whatever dtype the module has: the modules' own forward takes the
-project's HIP weight-gradient kernels at update sizes, which neither the yardstick nor the fp64 reference may.
+``critic_first_layer_plain``, ``coma_baseline_plain``, ``sqddpg_plain``, ``qmix_plain``) are the layers of nets.RNNAgent /
+nets.MLPAgent / nets.MLPCritic / nets.QMixer written with torch.nn.functional alone, in whatever dtype the module has: the modules' own forward takes the
+project's HIP weight-gradient kernels at update sizes (the mixer's: csrc/qmix.hip on any GPU tensors), which neither the yardstick nor the fp64 reference may.
 tests/test_fp64_budget_cpu.py pins them to the modules' forward (1e-12 in fp64)."""
 import copy
 from typing import NamedTuple
@@ -92,6 +92,26 @@ def make_mlp_agent(obs_dim, n_agents, act_dim, layernorm=True, device="cpu", see
         for p in agent.parameters():
             p.copy_(th.randn_like(p) * 0.3)
     return agent.to(device)
+
+
+def make_mixer(n_agents, obs_size, device="cpu", seed=0, zero_rows=False):
+    """A nets.QMixer in the shipped configuration (two-layer hypernetworks, embed 64, not gated, no skip) with
+    tests/test_qmix_gpu.py's parameters: every one 0.1 randn, drawn on the CPU.  ``zero_rows`` as there: exact zeros in rows of
+    hyper_w_1.2 and hyper_w_final.2, whose outputs then are exactly zero on every sample — abs' sign(0) = 0 must come through."""
+    from safe_marl_amd.nets import QMixer
+    from safe_marl_amd.util import convert
+    th.manual_seed(seed)
+    m = QMixer(convert(dict(agent_num=n_agents, obs_size=obs_size, mixing_embed_dim=64, hypernet_layers=2, hypernet_embed=64,
+                            hyper_initialization_nonzeros=0, gated=False, skip_connections=False)))
+    with th.no_grad():
+        for p in m.parameters():
+            p.copy_(th.randn_like(p) * 0.1)
+        if zero_rows:
+            m.hyper_w_1[2].weight[::7].zero_()
+            m.hyper_w_1[2].bias[::7].zero_()
+            m.hyper_w_final[2].weight[::5].zero_()
+            m.hyper_w_final[2].bias[::5].zero_()
+    return m.to(device)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -269,6 +289,72 @@ def sqddpg_plain(critic, obs, act, pos, ns):
     q, pre1, pre2 = critic_plain(critic, rows.reshape(b * ns * n, -1))
     q = q.view(b, ns, n)
     return q.mean(1), q, pre1, pre2
+
+
+QMIX_RELU_HEADS = ("hyper_w_1", "hyper_w_final", "V")
+QMIX_WRONG = ("abs_grad_one_at_zero", "drop_last_agent", "elu_slope_one")
+
+
+def qmix_plain(mixer, agent_qs, states, wrong=None, taps=None):
+    """qmix.py:53-81 (nets.QMixer.forward_torch) in the shipped configuration on agent_qs [B, n] and states [B, S], in the
+    module's dtype: (q_tot [B], the pre-activations whose side of a kink is arbitrary in fp32 — the first-layer outputs of the
+    three ReLU heads hyper_w_1, hyper_w_final, V, [B, 64] each, then the outputs of hyper_w_1 [B, 64 n] and hyper_w_final
+    [B, 64] before ``abs``).  ELU is C1 at 0: no tie.  ``taps``: a dict that receives the two linear taps, ``b1`` [B, 64] and
+    ``v`` [B, 1] (with the pre-activations, every bias gradient's per-sample addends are a gradient into one of these).
+    ``wrong``: one of QMIX_WRONG, the wrong evaluations tests/test_fp64_budget_cpu.py has the budget reject — abs' gradient
+    taken as +1 where its argument is exactly zero, the last agent's term left out of the mixing sum, ELU's slope taken as 1 on
+    its negative branch (values unchanged: only the backward is wrong)."""
+    assert wrong is None or wrong in QMIX_WRONG, wrong
+    n, B = mixer.n_agents, agent_qs.shape[0]
+    x, q = states.reshape(B, -1), agent_qs.reshape(B, n)
+
+    def first(head):
+        return F.linear(x, head[0].weight, head[0].bias)
+
+    def absolute(t):
+        if wrong == "abs_grad_one_at_zero":
+            return t.abs() + (t == 0).to(t.dtype) * (t - t.detach())
+        return t.abs()
+
+    pre_w1, pre_wf, pre_v = (first(getattr(mixer, name)) for name in QMIX_RELU_HEADS)
+    out_w1 = F.linear(F.relu(pre_w1), mixer.hyper_w_1[2].weight, mixer.hyper_w_1[2].bias)
+    out_wf = F.linear(F.relu(pre_wf), mixer.hyper_w_final[2].weight, mixer.hyper_w_final[2].bias)
+    v = F.linear(F.relu(pre_v), mixer.V[2].weight, mixer.V[2].bias)
+    b1 = F.linear(x, mixer.hyper_b_1.weight, mixer.hyper_b_1.bias)
+    w1 = absolute(out_w1).view(B, n, 64)
+    if wrong == "drop_last_agent":
+        mix = th.bmm(q[:, None, :n - 1], w1[:, :n - 1])
+    else:
+        mix = th.bmm(q[:, None, :], w1)
+    z = mix + b1.view(B, 1, 64)
+    hidden = F.elu(z)
+    if wrong == "elu_slope_one":
+        hidden = hidden.detach() + (z - z.detach())
+    q_tot = th.bmm(hidden, absolute(out_wf).view(B, 64, 1)) + v.view(B, 1, 1)
+    if taps is not None:
+        taps.update(b1=b1, v=v)
+    return q_tot.view(B), [pre_w1, pre_wf, pre_v, out_w1, out_wf]
+
+
+# the bias gradients of the mixer as sums over the samples: index into qmix_plain's pre-activations, or the name of a tap
+QMIX_BIAS_ADDENDS = {"hyper_w_1.0.bias": 0, "hyper_w_final.0.bias": 1, "V.0.bias": 2, "hyper_w_1.2.bias": 3,
+                     "hyper_w_final.2.bias": 4, "hyper_b_1.bias": "b1", "V.2.bias": "v"}
+
+
+def qmix_run(mixer, agent_qs, states, w, dtype, wrong=None):
+    """One training pass of ``qmix_plain`` with the loss (q_tot w).sum(), everything cast to ``dtype`` (``mixer`` already is):
+    (q_tot, d agent_qs, {parameter name: gradient}, {bias name: fb.row_sum_rounding of its per-sample addends}, the
+    pre-activations detached)."""
+    q = agent_qs.detach().to(dtype).requires_grad_(True)
+    taps = {}
+    q_tot, pre = qmix_plain(mixer, q, states.detach().to(dtype), wrong=wrong, taps=taps)
+    loss = (q_tot * w.detach().to(dtype)).sum()
+    params = dict(mixer.named_parameters())
+    where = {name: (pre[k] if isinstance(k, int) else taps[k]) for name, k in QMIX_BIAS_ADDENDS.items()}
+    addends = th.autograd.grad(loss, list(where.values()), retain_graph=True)
+    floors = {name: row_sum_rounding(a).reshape(params[name].shape) for name, a in zip(where, addends)}
+    grads = th.autograd.grad(loss, [q] + list(params.values()))
+    return q_tot.detach(), grads[0], dict(zip(params, grads[1:])), floors, [p.detach() for p in pre]
 
 
 def critic_first_layer_plain(critic, obs_cols, act_cols, n_agents):
@@ -509,15 +595,63 @@ def families(rows, n_agents, obs_dim, generator, kind=None):
     return out
 
 
+QMIX_FAMILIES = ("plain", "reset", "dead", "zeros", "elu_neg", "elu_deep", "big_q", "mixed")
+QMIX_MIXED_OF = ("plain", "reset", "elu_neg", "big_q")
+
+
+def qmix_families(B, n, S, generator):
+    """The mixer's named input families for ``B`` samples of ``n`` agents and a state of ``S``: inputs (agent_qs [B, n],
+    states [B, S], loss weights w [B]) from ONE set of base draws q = randn, x = 0.3 randn, w = randn / B (the scales of
+    tests/test_qmix_gpu.py), on the generator's device.
+
+    plain     the base draws.
+    reset     state exactly zero: the first-layer outputs are the biases, the first-layer weight gradients exactly zero.
+    dead      the three ReLU heads' first-layer biases filled with -10: every hidden unit off, w1 = |hyper_w_1.2.bias|,
+              gradients into the .0 layers of those heads exactly zero.
+    zeros     a mixer made with ``zero_rows=True`` (``params`` says so: {"zero_rows": ...}, for ``make_mixer``); the inputs
+              are plain's.
+    elu_neg   q = -4 |randn|: every mixing unit on ELU's exponential branch, a few units deep.
+    elu_deep  q = -300 - |randn|: hidden = -1 to the last bit, the slope exp(x) underflows.
+    big_q     q = 100 randn: hundreds per unit on the linear branch, deep saturation on the other.
+    mixed     plain, reset, elu_neg, big_q interleaved sample by sample (``groups``: which), so that one 32-sample tile holds
+              each kind.  (dead and zeros are parameter changes; elu_deep has no gradient to compare.)"""
+    dev = generator.device
+    q = th.randn(B, n, device=dev, generator=generator)
+    x = 0.3 * th.randn(B, S, device=dev, generator=generator)
+    w = th.randn(B, device=dev, generator=generator) / B
+    qs = {"plain": q, "reset": q, "elu_neg": -4.0 * q.abs(), "elu_deep": -300.0 - q.abs(), "big_q": 100.0 * q}
+    xs = {"reset": th.zeros_like(x)}
+    dead = {f"{head}.0.bias": ("fill", -10.0) for head in QMIX_RELU_HEADS}
+    out = {name: Family(name, (qs[name], xs.get(name, x), w.clone()), {}) for name in qs}
+    out["dead"] = Family("dead", (q, x, w.clone()), dead)
+    out["zeros"] = Family("zeros", (q, x, w.clone()), {"zero_rows": ("make", True)})
+    groups = th.arange(B, device=dev) % len(QMIX_MIXED_OF)
+    mq, mx = q.clone(), x.clone()
+    for j, name in enumerate(QMIX_MIXED_OF):
+        mq[groups == j] = qs[name][groups == j]
+        mx[groups == j] = xs.get(name, x)[groups == j]
+    out["mixed"] = Family("mixed", (mq, mx, w.clone()), {}, groups)
+    return out
+
+
+def qmix_clear_ties(mixer64, states, w, eps=1e-5):
+    """``clear_ties`` per SAMPLE for the mixer: w[b] = 0 IN PLACE where sample b has one of ``qmix_plain``'s pre-activations
+    within ``eps`` of zero in fp64 (exact zeros excepted); the agent q-values play no part in them.  Returns the share."""
+    zeros = th.zeros(states.shape[0], mixer64.n_agents, dtype=th.float64, device=states.device)
+    return clear_ties(lambda x: qmix_plain(mixer64, zeros, x)[1], (states.double(),), [w], eps)
+
+
 def apply_params(module, family):
-    """Make the family's parameter changes on ``module`` (an RNNAgent, an MLPAgent or an MLPCritic, or a list of them: every
-    one; ``ln_b`` is its LayerNorm's bias)."""
+    """Make the family's parameter changes on ``module`` (an RNNAgent, an MLPAgent, an MLPCritic or a QMixer, or a list of
+    them: every one; ``ln_b`` is its LayerNorm's bias; a "make" entry is for the module's constructor, not for here)."""
     if isinstance(module, (list, tuple)):
         for m in module:
             apply_params(m, family)
         return module
     with th.no_grad():
         for key, (op, value) in family.params.items():
+            if op == "make":
+                continue
             p = module.layernorm.bias if key == "ln_b" else dict(module.named_parameters())[key]
             if op == "add":
                 p.add_(value)

@@ -2,7 +2,9 @@
 case of the GPU tests that draw theirs from the CPU generator — keeps the share of rows with an arbitrary ReLU side within the
 cap; the fp32 modules pass their own budget; and the budget rejects five wrong fp32 results — two of them (a gradient off by
 1e-5 of itself, an output off by 1e-5 of its scale) errors that the fixed tolerances of the fp32-against-fp32 tests accept,
-one (LayerNorm statistics from a running fp32 sum) wrong only on rows whose 64 inputs are all equal."""
+one (LayerNorm statistics from a running fp32 sum) wrong only on rows whose 64 inputs are all equal.  The QMIX mixer's part is
+at the end: ``qmix_plain`` is ``QMixer.forward_torch``, every case of tests/test_qmix_fp64_gpu.py keeps its tie share within the
+cap, and the budget rejects three wrong evaluations of the mixer."""
 import pytest
 import torch as th
 
@@ -356,3 +358,101 @@ def test_row_sum_rounding_is_what_a_running_fp32_sum_does_and_still_rejects_1e_5
     with pytest.raises(AssertionError):
         fb.within_budget(run - addends[-1], tree, ref, floor_ulps=ulps, name="mutant running sum without its last row")
     assert fb.floor_ulps(None, ref) == fb.FLOOR_ULPS
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the QMIX mixer's composition, families and cases (tests/test_qmix_fp64_gpu.py)
+
+@pytest.mark.parametrize("n", [1, 3, 8])
+def test_qmix_plain_is_the_mixers_forward(n):
+    g = th.Generator().manual_seed(n)
+    m = fb.make_mixer(n, 16, seed=n, zero_rows=(n == 3)).double()
+    q, x = th.randn(35, n, generator=g).double(), 0.3 * th.randn(35, n * 16, generator=g).double()
+    with th.no_grad():
+        y, pre = fb.qmix_plain(m, q, x)
+        assert y.shape == (35,) and (y - m.forward_torch(q, x).view(-1)).abs().max() < 1e-12
+        assert [tuple(p.shape) for p in pre] == [(35, 64)] * 3 + [(35, 64 * n), (35, 64)]
+        assert th.equal(pre[0], m.hyper_w_1[0](x)) and th.equal(pre[3], m.hyper_w_1(x)) and th.equal(pre[4], m.hyper_w_final(x))
+        # the wrong evaluations are wrong in the backward alone, but for the dropped agent
+        for wrong in ("abs_grad_one_at_zero", "elu_slope_one"):
+            assert th.equal(fb.qmix_plain(m, q, x, wrong=wrong)[0], y)
+
+
+def test_qmix_families_are_what_they_say():
+    B, n, S = 64, 3, 48
+    fams = fb.qmix_families(B, n, S, th.Generator().manual_seed(0))
+    assert tuple(sorted(fams)) == tuple(sorted(fb.QMIX_FAMILIES))
+    q, x, w = fams["plain"].inputs
+    assert not fams["reset"].inputs[1].any() and th.equal(fams["reset"].inputs[0], q)
+    assert (fams["elu_neg"].inputs[0] <= 0).all() and (fams["elu_deep"].inputs[0] <= -300).all()
+    assert th.equal(fams["big_q"].inputs[0], 100.0 * q)
+    mq, mx, _ = fams["mixed"].inputs
+    for j, name in enumerate(fb.QMIX_MIXED_OF):
+        rows = fams["mixed"].groups == j
+        assert rows[:32].any() and th.equal(mq[rows], fams[name].inputs[0][rows]) and th.equal(mx[rows], fams[name].inputs[1][rows])
+    m64 = fb.ref64(fb.apply_params(fb.make_mixer(n, 16), fams["dead"]))
+    with th.no_grad():
+        y, pre = fb.qmix_plain(m64, q.double(), x.double())
+        assert all((p < 0).all() for p in pre[:3])                                     # every hidden unit off
+        assert th.equal(pre[3], m64.hyper_w_1[2].bias.expand(B, -1))                   # w1 = |hyper_w_1.2.bias|
+        taps = {}
+        fb.qmix_plain(fb.ref64(fb.make_mixer(n, 16)), fams["elu_deep"].inputs[0].double(), x.double(), taps=taps)
+        assert taps["b1"].shape == (B, 64) and taps["v"].shape == (B, 1)
+    mz = fb.make_mixer(n, 16, zero_rows=True)
+    with th.no_grad():
+        pre = fb.qmix_plain(mz, q, x)[1]
+        assert not pre[3][:, ::7].any() and not pre[4][:, ::5].any() and pre[3][:, 1].all()
+
+
+@pytest.mark.parametrize("family", fb.QMIX_FAMILIES)
+def test_tie_shares_of_the_qmix_cases_and_the_yardsticks_own_budget(family):
+    from . import test_qmix_fp64_gpu as T
+    assert family in T.FAMILIES and len(T.FAMILIES) == 8 and len(T.SHAPES) == 6
+    for B, n, obs in T.SHAPES:
+        m, q, x, w, share, attempt = T.case_inputs(B, n, obs, family, "cpu")
+        m64 = fb.ref64(m)
+        _share_line(f"qmix {family} {B}x{n}x{obs} (attempt {attempt})", share)
+        with th.no_grad():
+            tied = fb.tie_rows(fb.qmix_plain(m64, q.double(), x.double())[1])
+        assert th.equal(w == 0, tied) and float(tied.double().mean()) == share
+        t32, r64 = fb.qmix_run(m, q, x, w, th.float32), fb.qmix_run(m64, q, x, w, th.float64)
+        fb.within_budget(t32[0], t32[0], r64[0], name=f"cpu-yardstick qmix {family} {B}x{n}x{obs} q_tot")
+        fb.within_budget(t32[1], t32[1], r64[1], name=f"cpu-yardstick qmix {family} {B}x{n}x{obs} d_agent_qs")
+        assert set(r64[3]) == set(fb.QMIX_BIAS_ADDENDS) and all(r64[3][k].shape == r64[2][k].shape for k in r64[3])
+    for B, n, obs in T.STRUCTURE:
+        assert (B, n, obs) in T.SHAPES
+
+
+# the tensors a wrong evaluation must be rejected on, and the least number of parameter gradients among the rejected
+QMIX_REJECTED_ON = {"abs_grad_one_at_zero": (("hyper_w_1.2.weight", "hyper_w_1.2.bias"), 2),
+                    "drop_last_agent": (("q_tot", "agent_qs"), 7), "elu_slope_one": (("agent_qs",), 4)}
+
+
+@pytest.mark.parametrize("B,n,obs", [(33, 8, 16), (129, 5, 144), (31, 3, 16)])
+@pytest.mark.parametrize("family", ["plain", "reset", "elu_neg"])
+@pytest.mark.parametrize("wrong", fb.QMIX_WRONG)
+def test_budget_rejects_three_wrong_evaluations_of_the_mixer(wrong, family, B, n, obs):
+    """At three of tests/test_qmix_fp64_gpu.py's shapes, with zero_rows on (what the first wrong evaluation needs; the other
+    two do not mind): the right fp32 evaluation is accepted on every tensor, each wrong one is rejected on the tensors named in
+    QMIX_REJECTED_ON and on at least the number of parameter gradients given there."""
+    g = th.Generator().manual_seed(1000 * B + 10 * obs + n)
+    q, x, w = fb.qmix_families(B, n, n * obs, g)[family].inputs
+    m = fb.make_mixer(n, obs, seed=1, zero_rows=True)
+    m64 = fb.ref64(m)
+    fb.qmix_clear_ties(m64, x, w)
+    good, ref = fb.qmix_run(m, q, x, w, th.float32), fb.qmix_run(m64, q, x, w, th.float64)
+    bad = fb.qmix_run(m, q, x, w, th.float32, wrong=wrong)
+
+    def tensors(run):
+        return dict(q_tot=run[0], agent_qs=run[1], **run[2])
+
+    rejected = []
+    for name, r in tensors(ref).items():
+        fb.within_budget(tensors(good)[name], tensors(good)[name], r, name=f"right evaluation {family} {B}x{n}x{obs} {name}")
+        try:
+            fb.within_budget(tensors(bad)[name], tensors(good)[name], r, name=f"mutant {wrong} {family} {B}x{n}x{obs} {name}")
+        except AssertionError:
+            rejected.append(name)
+    print(f"{wrong} {family} {B}x{n}x{obs}: rejected on {rejected}")
+    named, least = QMIX_REJECTED_ON[wrong]
+    assert set(named) <= set(rejected) and len(set(rejected) - {"q_tot", "agent_qs"}) >= least, rejected

@@ -1,5 +1,6 @@
 """csrc/qmix.hip (flexnet_qmix_forward / flexnet_qmix_backward + the flexnet_wgrad reductions) against fp32 PyTorch autograd
-of the same QMixer (its reference composition, ``forward_torch``)."""
+of the same QMixer (its reference composition, ``forward_torch``).  The fp64 error budget on edge-case inputs and shapes, the
+bit-for-bit structure and the NaN rule are tests/test_qmix_fp64_gpu.py's."""
 import warnings
 
 import pytest
