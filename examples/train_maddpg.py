@@ -75,6 +75,10 @@ def main():
                     help="agent_type of default.yaml: the recurrent agent, or the MLP agent on the stacked history (csrc/actor_mlp.hip)")
     ap.add_argument("--unshared", action="store_true",
                     help="shared_params: False of default.yaml — one actor and one critic per agent (csrc/actor_unshared.hip)")
+    ap.add_argument("--episodic", action="store_true",
+                    help="episodic: True of default.yaml — one update event per block of 95 vector steps, on batches of whole "
+                         "episodes gathered by csrc/episodes.hip (ippo / mappo / coma: the on-policy triple batch_size = "
+                         "replay_buffer_size = behaviour_update_freq, in blocks)")
     a = ap.parse_args()
     if a.unshared and a.alg == "matd3":
         ap.error("--unshared: MATD3 is built for shared_params (default.yaml:26)")
@@ -122,6 +126,12 @@ def main():
         alg.update(agent_type=a.agent_type)
     if a.unshared:
         alg.update(shared_params=False)
+    if a.episodic:
+        # capacity and cadence count BLOCKS of 95 vector steps of every environment (replay_buffer.EpisodeReplayBuffer)
+        if a.alg in ("ippo", "mappo", "coma"):
+            alg.update(episodic=True, batch_size=2, replay_buffer_size=2, behaviour_update_freq=2)      # default.yaml:1
+        else:
+            alg.update(episodic=True, replay_buffer_size=2, behaviour_update_freq=1)
     alg.update(alg=a.alg, agent_num=env.n_agents, obs_size=env.obs_size, state_size=env.state_size,
                action_dim=4, v_min=0.9, v_max=1.1)
     args = convert(alg)
@@ -150,7 +160,7 @@ def main():
                "value": a.envs * world * steps / dt, "unit": "env-steps/s", "n_gpus": world, "envs_per_gpu": a.envs,
                "gaussian_policy": bool(args.gaussian_policy), "n_agents": env.n_agents, "vector_steps": steps, "ms_per_vector_step": dt / steps * 1e3,
                "batch": trainer.effective_batch_size(),
-               "grad_steps": int(steps // args.behaviour_update_freq) * (args.value_update_epochs + args.policy_update_epochs
+               "grad_steps": int((a.episodes if a.episodic else steps) // args.behaviour_update_freq) * (args.value_update_epochs + args.policy_update_epochs
                                                                          + (args.mixer_update_epochs if args.mixer else 0)),
                "stat": {k: (float(v) if not isinstance(v, float) else v) for k, v in stat.items()},
                # fused paths that declined a call and ran their PyTorch composition instead (util.note_fallback): none expected
@@ -159,6 +169,8 @@ def main():
             out["agent_type"] = a.agent_type
         if a.unshared:
             out["shared_params"] = False
+        if a.episodic:
+            out["episodic"] = True
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

@@ -484,6 +484,50 @@ typedef struct {
 } FlexWindowArgs;
 int flexnet_gather_window(const FlexWindowArgs* args, void* stream);
 
+/* A batch of whole EPISODES out of the slab rings (episodic replay, utils/replay_buffer.py:44-50: the chosen episodes'
+ * transitions concatenated in the drawn order) in ONE launch.  Episode i of the table is (first slab counter c0,
+ * environment e, length L, first output row off): for j < L, output row off + j of every field is what the window of one
+ * transition at global slot (c0 + j) * n_envs + e holds —
+ *     state / next_state  the stacked observations of slabs c0 + j and c0 + j + 1: from row_ring by flexnet_gather_window's
+ *                         rule (history >= 1, obs_dim = 6 * history), or copied from obs_ring (history = 0);
+ *     last_hid / hid      hid_ring at those two slabs;   action | reward | done | last_step   the small record of slab c0 + j;
+ *     value / next_value / log_prob_a   v_ring / nv_ring / lp_ring at slab c0 + j, each where ring AND output are given
+ * (slab indices modulo `slabs`).  Plain copies.  The table is handed over twice: `episodes` on the device for the kernel,
+ * `episodes_host` — the host's mirror of the same [n_episodes][4] int64 — for the checks, so that nothing is read back.
+ * The offsets must tile the batch: off[0] = 0, off[i + 1] = off[i] + L[i], the last one ending at `rows`.
+ * FLEXNET_EINVAL before any HIP call: a missing ring, table or output (or both / neither of row_ring and obs_ring, a filed
+ * ring without its output or the reverse), n_episodes / rows / a dimension < 1, small_w < n_agents * act_dim + n_agents + 2,
+ * history not matching the ring (row_ring: obs_dim != 6 * history or history < 1; obs_ring: history != 0), and per episode
+ * c0 < 0, e outside [0, n_envs), L < 1, L + history exceeding what `slabs` holds, an offset that is not the running sum, a total
+ * other than `rows`.  FLEXNET_EUNSUPPORTED: rows >= 2^31 / FLEXNET_EPISODE_ROWS blocks, with row_ring history > 32 or n_agents >
+ * FLEXNET_MAX_AGENTS or a row_ring that is not 16-byte aligned, state / next_state not 8-byte aligned. */
+#define FLEXNET_EPISODE_ROWS 4                 /* output rows per thread block */
+typedef struct {
+    const float* row_ring;                     /* [slabs][n_envs][n_agents * 8], or NULL */
+    const float* obs_ring;                     /* [slabs][n_envs][n_agents * obs_dim], or NULL */
+    const float* hid_ring;                     /* [slabs][n_envs][n_agents * hid_dim] */
+    const float* small_ring;                   /* [slabs][n_envs][small_w] */
+    const float* v_ring;                       /* [slabs][n_envs][n_agents], optional */
+    const float* nv_ring;                      /* [slabs][n_envs][n_agents], optional */
+    const float* lp_ring;                      /* [slabs][n_envs][n_agents * act_dim], optional */
+    const int64_t* episodes;                   /* device [n_episodes][4]: c0, e, L, off */
+    const int64_t* episodes_host;              /* host mirror of the same table */
+    float* state;                              /* out [rows, n_agents * obs_dim] */
+    float* next_state;
+    float* last_hid;                           /* out [rows, n_agents * hid_dim] */
+    float* hid;
+    float* action;                             /* out [rows, n_agents * act_dim] */
+    float* reward;                             /* out [rows, n_agents] */
+    float* done;                               /* out [rows] */
+    float* last_step;                          /* out [rows] */
+    float* value;                              /* out [rows, n_agents], with v_ring */
+    float* next_value;                         /* out [rows, n_agents], with nv_ring */
+    float* log_prob_a;                         /* out [rows, n_agents * act_dim], with lp_ring */
+    int64_t rows;
+    int32_t n_episodes, n_envs, n_agents, history, obs_dim, hid_dim, act_dim, small_w, slabs, pad0;
+} FlexEpisodeGatherArgs;
+int flexnet_gather_episodes(const FlexEpisodeGatherArgs* args, void* stream);
+
 /* Replay-window refresh: up to FLEXNET_GATHER_MAX_JOBS strided row copies in one launch.  A sampled window of the slab
  * ring (utils/replay_buffer.py:17-21: consecutive transitions) becomes the contiguous static batch a captured sub-update
  * reads; each field is one job (two where the window crosses the ring's seam). */

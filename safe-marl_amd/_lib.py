@@ -76,7 +76,7 @@ SYMBOLS = (
     "flexenv_peek", "flexenv_poke", "flexenv_num_envs", "flexenv_set_step_counter", "flexenv_set_obs_ring", "flexenv_set_replay_sink", "flexenv_rollout_burst", "flexenv_test_episodes", "flexenv_obs_size", "flexenv_state_size",
     "pf_solve_batch", "flexenv_safety_project", "flexenv_safety_project_env", "flexenv_version", "flexenv_abi_version",
     "flexnet_actor_forward", "flexnet_critic_tail_forward", "flexnet_critic_tail_backward", "flexnet_rollout_pack", "flexnet_wgrad", "flexnet_lnrelu_forward", "flexnet_lnrelu_backward", "flexnet_clip_rmsprop", "flexnet_clip_rmsprop_refresh", "flexnet_td_loss", "flexnet_td_stats", "flexnet_critic_td_backward", "flexnet_critic_td_backward_phases", "flexnet_wgrad_critic_finish",
-    "flexnet_scaled_sum", "flexnet_agent_sum_explore", "flexnet_gather_rows", "flexnet_gather_rows_td", "flexnet_window_refresh", "flexnet_gather_window", "flexnet_linear2", "flexnet_gru_backward",
+    "flexnet_scaled_sum", "flexnet_agent_sum_explore", "flexnet_gather_rows", "flexnet_gather_rows_td", "flexnet_window_refresh", "flexnet_gather_window", "flexnet_gather_episodes", "flexnet_linear2", "flexnet_gru_backward",
     "flexnet_qmix_forward", "flexnet_qmix_backward",
     "flexnet_sqddpg_draw", "flexnet_sqddpg_forward", "flexnet_sqddpg_backward",
     "flexnet_ppo_gae", "flexnet_ppo_policy_loss", "flexnet_ppo_value_loss",
@@ -115,6 +115,19 @@ class FlexWindowArgs(C.Structure):
     """include/flexnet.h"""
     _fields_ = [("row_ring", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int64), ("first_slot", C.c_int64),
                 ("n_envs", C.c_int32), ("n_agents", C.c_int32), ("history", C.c_int32), ("slabs", C.c_int32)]
+
+
+class FlexEpisodeGatherArgs(C.Structure):
+    """include/flexnet.h"""
+    _fields_ = [(k, C.c_void_p) for k in ("row_ring", "obs_ring", "hid_ring", "small_ring", "v_ring", "nv_ring", "lp_ring",
+                                          "episodes", "episodes_host", "state", "next_state", "last_hid", "hid", "action",
+                                          "reward", "done", "last_step", "value", "next_value", "log_prob_a")] + \
+               [("rows", C.c_int64)] + \
+               [(k, C.c_int32) for k in ("n_episodes", "n_envs", "n_agents", "history", "obs_dim", "hid_dim", "act_dim",
+                                         "small_w", "slabs", "pad0")]
+
+
+FLEXNET_EPISODE_ROWS = 4
 
 
 class FlexQpArgs(C.Structure):
@@ -656,6 +669,8 @@ def load():
     lib.flexenv_obs_source.restype = C.c_int
     lib.flexnet_gather_window.argtypes = [C.POINTER(FlexWindowArgs), vp]
     lib.flexnet_gather_window.restype = C.c_int
+    lib.flexnet_gather_episodes.argtypes = [C.POINTER(FlexEpisodeGatherArgs), vp]
+    lib.flexnet_gather_episodes.restype = C.c_int
     lib.flexnet_linear2.argtypes = [C.POINTER(FlexLinear2Args), vp]
     lib.flexnet_linear2.restype = C.c_int
     lib.flexopf_qp_work_doubles.argtypes = [i32, i32, i32]

@@ -878,6 +878,37 @@ class Model(nn.Module):
         if self.args.target and trainer.steps % self.args.target_update_freq == 0:
             self.update_target()
 
+    def episode_update(self, trainer, stat, episode=None):
+        """model.py:73-86, the replay branch of ``episodic: True``: the episode joins the replay (``episode``: the list of its
+        Transitions, one environment; the vectorised rollouts have filed theirs through ``end_block``), and an update event
+        — value sub-updates, policy sub-updates, the mixer's, each on a fresh batch of whole episodes — fires when
+        ``trainer.episodes`` is past ``replay_warmup``, a multiple of ``behaviour_update_freq``, and the replay holds a batch
+        of episodes.  With a vectorised env ``trainer.episodes`` counts blocks (replay_buffer.EpisodeReplayBuffer).
+        Quirks kept from the reference: ``update_target`` is called from transition_update only (model.py:68-71), so in
+        episodic mode the target network stays at its initial copy; the on-policy classes' replay is NOT cleared here —
+        their episodic mode is batch_size = replay_buffer_size = behaviour_update_freq (default.yaml:1); and without a
+        replay the reference reads a buffer that does not exist (model.py:87-97), which raises here.
+        On-policy classes: ``begin_update_event`` files value / next_value (/ log_prob_a) of the replay's transitions
+        before the first batch is gathered — for every transition in the ring, so outside the on-policy triple, blocks
+        older than the last update are re-valued by the current critic."""
+        if not self.args.replay:
+            raise NotImplementedError("episodic updates without a replay read a buffer the reference never builds (model.py:87-97)")
+        if episode is not None:
+            trainer.replay_buffer.add_experience(episode)
+        replay_cond = trainer.episodes > self.args.replay_warmup \
+            and len(trainer.replay_buffer.buffer) >= trainer.effective_batch_size() \
+            and trainer.episodes % self.args.behaviour_update_freq == 0
+        if replay_cond:
+            if self.on_policy:
+                self.begin_update_event(trainer)
+            for _ in range(self.args.value_update_epochs):
+                trainer.value_replay_process(stat)
+            for _ in range(self.args.policy_update_epochs):
+                trainer.policy_replay_process(stat)
+            if getattr(self.args, "mixer", False):
+                for _ in range(self.args.mixer_update_epochs):
+                    trainer.mixer_replay_process(stat)
+
     # -- batches -----------------------------------------------------------------------------------------
     def _tensor_batch(self, batch):
         """A Transition of per-sample tuples (trainer.py:68) as a Transition of device tensors; tensors pass through."""
@@ -923,6 +954,7 @@ class Model(nn.Module):
         last_hid = self.policy_dicts[0].init_hidden()
         avail = th.tensor(env.get_avail_actions())
         t = 0
+        episodic, episode = bool(getattr(self.args, "episodic", False)), []
         for t in range(self.args.max_steps):
             state_ = prep_obs(state).to(self.device).contiguous().view(1, self.n_, self.obs_dim)
             action, action_pol, log_prob_a, _, hid = self.get_actions(state_, status="train", exploration=True,
@@ -940,7 +972,10 @@ class Model(nn.Module):
                                value.detach().cpu().numpy(), next_value.detach().cpu().numpy(),
                                np.array([reward] * env.get_num_of_agents()), next_state, done, done_,
                                env.get_avail_actions(), last_hid.detach().cpu().numpy(), hid.detach().cpu().numpy())
-            self.transition_update(trainer, trans, stat)
+            if episodic:                                  # model.py:243-246: collected, no update inside the episode
+                episode.append(trans)
+            else:
+                self.transition_update(trainer, trans, stat)
             for k, v in info.items():
                 stat_train["mean_train_" + k] = stat_train.get("mean_train_" + k, 0) + v
             stat_train["mean_train_reward"] += reward
@@ -953,6 +988,8 @@ class Model(nn.Module):
             if k.split("_")[0] == "mean":
                 stat_train[k] = v / float(t + 1)
         stat.update(stat_train)
+        if episodic:                                      # model.py:265-266
+            self.episode_update(trainer, stat, episode)
 
     def _train_process_vec(self, stat, trainer):
         """The same rollout over N environments at once.  One "episode" is ``episode_limit - 1`` vector
@@ -999,7 +1036,8 @@ class Model(nn.Module):
             buf.add_batch(state=obs, action=action_pol, **self._unfiled_columns(N),
                           reward=reward.float().unsqueeze(1).expand(N, self.n_), next_state=next_obs, done=donef,
                           last_step=last_step, action_avail=1.0, last_hid=last_hid, hid=hid)
-            self.transition_update(trainer, None, stat)
+            if not getattr(args, "episodic", False):
+                self.transition_update(trainer, None, stat)
             info_sum += info.sum(0)
             rew_sum += reward.sum()
             fail_sum += env.failed.sum()
@@ -1015,6 +1053,9 @@ class Model(nn.Module):
             stat["mean_train_" + k] = float(vals[i])
         stat["mean_train_reward"] = float(vals[-2])
         stat["mean_train_solver_failed"] = float(vals[-1])
+        if getattr(args, "episodic", False):              # the block's episodes into the table, then model.py:265-266
+            buf.end_block(horizon)
+            self.episode_update(trainer, stat)
 
     def _use_rollout_graph(self, trainer):
         """HIP-graph rollout: CUDA device, not switched off by the trainer.  MADDPG and SAFEMADDPG take the fused two-kernel
@@ -1029,7 +1070,7 @@ class Model(nn.Module):
         """Every run length the loop of _train_process_graph will ask the rollout for, from step counter ``steps`` on: the
         schedule repeats once the counter's phase against the update frequencies repeats at an episode start."""
         freqs = [int(self.args.behaviour_update_freq)] + ([int(self.args.target_update_freq)] if self.args.target else [])
-        freqs = [f for f in freqs if f > 0]
+        freqs = [f for f in freqs if f > 0 and not getattr(self.args, "episodic", False)]      # (episodic: nothing interrupts a block)
         period = int(np.lcm.reduce(freqs)) if freqs else 1
         seen, lengths, s = set(), set(), int(steps)
         while s % period not in seen and len(seen) < 4096:
@@ -1078,6 +1119,9 @@ class Model(nn.Module):
         # counter reaches a multiple of behaviour_update_freq / target_update_freq (model.py:43-50).  The steps up to the
         # next such multiple (or the end of the episode) need nothing from the host and go out as bursts.
         freqs = [int(self.args.behaviour_update_freq)] + ([int(self.args.target_update_freq)] if self.args.target else [])
+        episodic = bool(getattr(self.args, "episodic", False))
+        if episodic:                                      # no update event interrupts a block: it is a single run
+            freqs = []
         t = 0
         while t < horizon:
             s0 = trainer.steps
@@ -1087,7 +1131,8 @@ class Model(nn.Module):
             if t == horizon:                                                  # model.py:229: last_step on the final step
                 small[slabs[-1], :, last_col] = 1.0
             trainer.steps = s0 + m - 1
-            self.transition_update(trainer, None, stat)
+            if not episodic:
+                self.transition_update(trainer, None, stat)
             trainer.steps += 1
         trainer.episodes += 1
         vals = th.cat([rg.info_sum, rg.rew_sum.view(1), rg.fail_sum.view(1), env.done.double().sum().view(1)]).cpu().numpy()
@@ -1099,6 +1144,9 @@ class Model(nn.Module):
             stat["mean_train_" + k] = float(vals[i])
         stat["mean_train_reward"] = float(vals[-2])
         stat["mean_train_solver_failed"] = float(vals[-1])
+        if episodic:                                      # the block's episodes into the table, then model.py:265-266
+            buf.end_block(horizon)
+            self.episode_update(trainer, stat)
 
     def env_action(self, action):
         """translate_action (util.py:121-130) kept on the device: [N, n, a] in the env's range.  MATD3 samples ONE

@@ -12,6 +12,8 @@ Added for the vectorised path: ``add_batch`` appends one transition per environm
 indexed copy, and ``get_batch_tensors`` returns the window as device tensors (no host round trip,
 no per-sample Python objects).  With N envs the ring is time-major — consecutive slots are the N envs
 of one vector step — so a window is a contiguous, coalesced slab.
+``EpisodeReplayBuffer`` (below) is the memory of ``episodic: True`` (utils/replay_buffer.py:33-56): whole episodes, drawn
+without replacement and concatenated.
 """
 from __future__ import annotations
 
@@ -24,6 +26,24 @@ Transition = namedtuple("Transition", ("state", "action", "log_prob_a", "value",
                                        "next_state", "done", "last_step", "action_avail", "last_hid", "hid"))
 
 FIELDS = Transition._fields
+
+
+def _transition_row(trans):
+    """The Transition of model.py:230-242 (numpy fields) as one row [1, ...] per field."""
+    return {
+        "state": np.asarray(trans.state, np.float32)[None],
+        "action": np.asarray(trans.action, np.float32).reshape(1, *np.shape(trans.action)[-2:]),
+        "log_prob_a": np.asarray(trans.log_prob_a, np.float32).reshape(1, *np.shape(trans.log_prob_a)[-2:]),
+        "value": np.asarray(trans.value, np.float32).reshape(1, *np.shape(trans.value)[-2:]),
+        "next_value": np.asarray(trans.next_value, np.float32).reshape(1, *np.shape(trans.next_value)[-2:]),
+        "reward": np.asarray(trans.reward, np.float32)[None],
+        "next_state": np.asarray(trans.next_state, np.float32)[None],
+        "done": np.asarray([float(trans.done)], np.float32),
+        "last_step": np.asarray([float(trans.last_step)], np.float32),
+        "action_avail": np.asarray(trans.action_avail, np.float32).reshape(1, *np.shape(trans.action_avail)[-2:]),
+        "last_hid": np.asarray(trans.last_hid, np.float32).reshape(1, *np.shape(trans.last_hid)[-2:]),
+        "hid": np.asarray(trans.hid, np.float32).reshape(1, *np.shape(trans.hid)[-2:]),
+    }
 
 
 class _LenView:
@@ -342,6 +362,10 @@ class DeviceReplayBuffer:
         """Row mode: the stacked observations [rows, n_agents * obs_dim] of the global slot range [slot, slot + rows), formed
         from the row ring by ONE launch of flexnet_gather_window (include/flexnet.h); the ring's seam is the kernel's business."""
         from . import _lib
+        if self.device.type != "cuda":                    # (no kernel off the GPU: the same rows as a tensor composition)
+            g = th.arange(int(slot), int(slot) + rows, dtype=th.int64)
+            res = self.stacked_rows(g // self.n_envs, g % self.n_envs).reshape(rows, -1)
+            return res if out is None else out.copy_(res)
         if out is None:
             out = th.empty(rows, self.n_agents * self.obs_dim, dtype=th.float32, device=self.device)
         a = _lib.FlexWindowArgs()
@@ -349,6 +373,21 @@ class DeviceReplayBuffer:
         a.n_envs, a.n_agents, a.history, a.slabs = self.n_envs, self.n_agents, self.history, self.slabs
         _lib.launch("flexnet_gather_window", a)
         return out
+
+    def stacked_rows(self, counters, envs):
+        """Row mode: the stacked observations [R, n_agents, obs_dim] of the (slab counter, environment) pairs given as two
+        int64 tensors — flexnet_gather_window's rule (include/flexnet.h) as index tensors, an im2col and a select; plain
+        copies, so bit-equal to the kernel's rows."""
+        H, n, N = self.history, self.n_agents, self.n_envs
+        dev = self.device
+        c, e = counters.to(dev), envs.to(dev)
+        rec = self.row_ring.view(self.slabs, N, n, self.ROW_W)
+        back = th.arange(H - 1, -1, -1, device=dev)                                   # slot h reaches H - 1 - h slabs back
+        rows = rec[(c[:, None] - back[None, :]) % self.slabs, e[:, None]]            # [R, H, n, 8]
+        older = rec[c % self.slabs, e][:, :, 6]                                       # [R, n]
+        live = back.to(th.float32)[None, :, None] <= older[:, None, :]               # [R, H, n]
+        out = th.where(live[..., None], rows[..., :6], th.zeros((), device=dev))
+        return out.permute(0, 2, 1, 3).reshape(c.shape[0], n, 6 * H)
 
     # -- stacked-observation ring (row mode, round 5): every slab's stacked observations formed ONCE ------------------------
     def enable_stacked_ring(self, max_window_rows):
@@ -584,20 +623,7 @@ class DeviceReplayBuffer:
 
     def add_experience(self, trans):
         """replay_buffer.py:23-27 with the Transition of model.py:230-242 (numpy fields)."""
-        row = {
-            "state": np.asarray(trans.state, np.float32)[None],
-            "action": np.asarray(trans.action, np.float32).reshape(1, *np.shape(trans.action)[-2:]),
-            "log_prob_a": np.asarray(trans.log_prob_a, np.float32).reshape(1, *np.shape(trans.log_prob_a)[-2:]),
-            "value": np.asarray(trans.value, np.float32).reshape(1, *np.shape(trans.value)[-2:]),
-            "next_value": np.asarray(trans.next_value, np.float32).reshape(1, *np.shape(trans.next_value)[-2:]),
-            "reward": np.asarray(trans.reward, np.float32)[None],
-            "next_state": np.asarray(trans.next_state, np.float32)[None],
-            "done": np.asarray([float(trans.done)], np.float32),
-            "last_step": np.asarray([float(trans.last_step)], np.float32),
-            "action_avail": np.asarray(trans.action_avail, np.float32).reshape(1, *np.shape(trans.action_avail)[-2:]),
-            "last_hid": np.asarray(trans.last_hid, np.float32).reshape(1, *np.shape(trans.last_hid)[-2:]),
-            "hid": np.asarray(trans.hid, np.float32).reshape(1, *np.shape(trans.hid)[-2:]),
-        }
+        row = _transition_row(trans)
         self.add_batch(**{k: th.from_numpy(v).to(self.device) for k, v in row.items()})
 
     def clear(self):
@@ -661,3 +687,306 @@ class TransReplayBuffer(DeviceReplayBuffer):
         if device is None:
             device = "cuda" if th.cuda.is_available() else "cpu"
         super().__init__(size, device)
+
+
+class _EpisodeCount:
+    """``.buffer`` of the episodic memory: len() is the number of EPISODES (model.py:77)."""
+
+    def __init__(self, owner):
+        self._owner = owner
+
+    def __len__(self):
+        return len(self._owner.episodes)
+
+
+class EpisodeReplayBuffer(DeviceReplayBuffer):
+    """utils/replay_buffer.py:33-56 (``episodic: True``, default.yaml:9), device-resident: ``add_experience(episode)``,
+    ``get_batch``, ``get_single`` and ``.buffer`` whose len() counts episodes.  Kept from the reference:
+      * the capacity ``size`` counts EPISODES and the oldest episode is dropped first (replay_buffer.py:52-56);
+      * a batch is the transitions of ``np.random.choice(len, batch_size, replace=False)`` episodes — that very call on the
+        global NumPy stream, so ``np.random.seed`` reproduces the reference's draws — CONCATENATED in the drawn order
+        (replay_buffer.py:44-50);
+      * there is no ``clear`` in the reference; the on-policy classes' data is NOT dropped after an update — their episodic
+        mode is ``batch_size = replay_buffer_size = behaviour_update_freq`` (default.yaml:1).
+
+    Three stores, one surface (``get_batch_tensors`` is what the trainer uses: a Transition of device tensors, rows
+    episode-major in the drawn order; ``last_draw`` keeps the drawn ids):
+      * one environment (``add_experience``): a list of episodes, each a tensor per field — the reference's semantics
+        exactly;
+      * N environments in lockstep (``configure_blocks`` by the trainer, then the rollouts' own ``add_batch`` / slab ring and
+        ``end_block``): the transitions live in the parent's time-major ring, field by field (eager rollout) or in slabs
+        (graph rollout), and this class keeps an episode TABLE of (step counter of the first step, environment, length).
+
+    The N > 1 mapping.  One ``train_process`` call is a *block*: N environments for ``horizon`` vector
+    steps.  Each environment's rows of a block split at ``last_step`` into complete episodes (an early termination restarts
+    in place; the block's last step carries last_step = 1), so a block adds at least N episodes.  Capacity: ``size`` counts
+    BLOCKS — the table holds the episodes of the last ``size`` blocks, and the ring is sized to keep their slabs:
+    ``size * (horizon + 1)`` vector steps (one slab per block may be a gap, left behind by a hard reset) + the two in flight
+    + the slabs an observation reaches back into; should the ring retire the slab of an episode's first step all the same,
+    that episode leaves too.  "Oldest first" is therefore by block: the episodes of the oldest block leave together, whichever
+    environment they belong to; within the table the order is (first step, environment).  Cadence:
+    ``trainer.episodes`` counts blocks, as a vector step is one "step" of the transition modes.  An episode of environment e
+    is the strided rows (c0 + j) * N + e of the ring; a batch is gathered by ONE launch of flexnet_gather_episodes
+    (include/flexnet.h) from the slab rings, by index tensors from the field-by-field store."""
+
+    def __init__(self, size, device=None):
+        if device is None:
+            device = "cuda" if th.cuda.is_available() else "cpu"
+        super().__init__(size, device)
+        self.capacity = int(size)         # episodes (blocks, once configure_blocks was called)
+        self.episodes = []                # list store: {field: tensor [L, ...]}; ring stores: (first step, env, length)
+        self.buffer = _EpisodeCount(self)
+        self.block_steps = None           # ring stores: vector steps per block
+        self.block_envs = 1
+        self.block_starts = []            # ring stores: step counter of the first step of every block in the table
+        self.k_field = 0                  # field-by-field ring: vector steps added so far (the slab ring's ``k``)
+        self.last_draw = None             # ids of the last batch's episodes, in the drawn order
+        self.use_kernel = True            # (tests and tools compare with the tensor composition)
+
+    # -- configuration of the vectorised form ----------------------------------------------------------------------------
+    def configure_blocks(self, n_envs, horizon):
+        """N environments for ``horizon`` vector steps per block: the parent's ring is sized for ``capacity`` blocks, a gap slab
+        per block, plus the two vector steps the slab ring keeps back for the step in flight."""
+        if self.episodes or self.store is not None or self.slab_mode:
+            raise RuntimeError("configure_blocks comes before the first transition")
+        self.block_envs, self.block_steps = int(n_envs), int(horizon)
+        self.size = (self.capacity * (self.block_steps + 1) + 2) * self.block_envs
+
+    @property
+    def ring_store(self):
+        return self.block_steps is not None
+
+    def _step_counter(self):
+        return self.k if self.slab_mode else self.k_field
+
+    def add_batch(self, **fields):
+        super().add_batch(**fields)
+        if self.ring_store:
+            b = next(v for v in fields.values() if isinstance(v, th.Tensor)).shape[0]
+            if b != self.block_envs:
+                raise ValueError("the episodic ring takes one vector step of all its environments per add_batch")
+            self.k_field += 1
+
+    def release_slabs(self):
+        super().release_slabs()
+        self.episodes, self.block_starts, self.k_field = [], [], 0
+
+    def clear(self):
+        """Not part of the reference's EpisodeReplayBuffer; drops every episode (and, with them, the ring's transitions)."""
+        super().clear()
+        self.episodes, self.block_starts = [], []
+        if self.ring_store and not self.slab_mode:
+            self.store, self.k_field = None, 0
+
+    # -- filling ----------------------------------------------------------------------------------------------------------
+    def add_experience(self, episode):
+        """replay_buffer.py:52-56: ``episode`` is the list of an episode's Transitions (model.py:230-242, numpy fields)."""
+        if self.ring_store:
+            raise RuntimeError("this episodic memory was configured for a vectorised rollout (end_block files its episodes)")
+        if len(episode) < 1:
+            raise ValueError("an episode holds at least one transition")
+        rows = [_transition_row(t) for t in episode]
+        if 1 + len(self.episodes) > self.capacity:
+            self.episodes.pop(0)
+        self.episodes.append({k: th.from_numpy(np.concatenate([r[k] for r in rows])).to(self.device) for k in FIELDS})
+
+    def end_block(self, steps):
+        """The last ``steps`` vector steps of the ring are a block: every environment's rows split at ``last_step`` into
+        episodes, which join the table; rows behind an environment's last mark belong to no episode.  One device read."""
+        if not self.ring_store:
+            raise RuntimeError("end_block belongs to the vectorised form (configure_blocks)")
+        N, k = self.block_envs, self._step_counter()
+        steps = int(steps)
+        if steps < 1 or steps > k:
+            raise ValueError("a block is at least one and at most every vector step filed so far")
+        cs = th.arange(k - steps, k, device=self.device)
+        if self.slab_mode:
+            col = self.n_agents * self.act_dim + self.n_agents + 1
+            last = self.small_ring[cs % self.slabs, :, col]
+        else:
+            rows = (cs[:, None] * N + th.arange(N, device=self.device)[None, :]) % self.size
+            last = self.store["last_step"].reshape(self.size)[rows]
+        last = last.cpu().numpy() != 0
+        new = []
+        for e in range(N):
+            start = 0
+            for t in np.flatnonzero(last[:, e]):
+                new.append((k - steps + start, e, int(t) - start + 1))
+                start = int(t) + 1
+        self.episodes.extend(sorted(new))
+        self.block_starts.append(k - steps)
+        del self.block_starts[:-self.capacity]
+        self._retire_episodes()
+
+    def _retire_episodes(self):
+        if not self.ring_store or not self.episodes:
+            return
+        k = self._step_counter()
+        lo = max(self.block_starts[0], self.first if self.slab_mode else k - self.size // self.block_envs)
+        if self.episodes[0][0] < lo:
+            self.episodes = [ep for ep in self.episodes if ep[0] >= lo]
+
+    # -- batches ----------------------------------------------------------------------------------------------------------
+    def draw(self, batch_size):
+        """replay_buffer.py:45-46, verbatim."""
+        self._retire_episodes()
+        length = len(self.episodes)
+        indices = np.random.choice(length, batch_size, replace=False)
+        self.last_draw = [int(i) for i in indices]
+        return self.last_draw
+
+    def get_batch_tensors(self, batch_size):
+        return self.episodes_batch(self.draw(batch_size))
+
+    def episode_table(self, ids):
+        """[len(ids), 4] int64 (first step, environment, length, first output row) of the episodes ``ids``, in that order."""
+        table = np.zeros((len(ids), 4), dtype=np.int64)
+        at = 0
+        for i, j in enumerate(ids):
+            c0, e, length = self.episodes[j]
+            table[i] = (c0, e, length, at)
+            at += length
+        return table
+
+    def episodes_batch(self, ids):
+        """The transitions of the episodes ``ids`` one behind the other, as a Transition of device tensors."""
+        if not self.ring_store:
+            eps = [self.episodes[i] for i in ids]
+            return Transition(**{k: th.cat([ep[k] for ep in eps]) for k in FIELDS})
+        table = self.episode_table(ids)
+        if not self.slab_mode:
+            return self._compose_fields(table)
+        if self.use_kernel and self.device.type == "cuda":
+            out = self._gather_slabs(table)
+            if out is not None:
+                return out
+            from .util import note_fallback
+            note_fallback("gather_episodes", f"rows {int(table[:, 2].sum())}, agents {self.n_agents}, obs_dim {self.obs_dim}")
+        return self._compose_slabs(table)
+
+    def _table_rows(self, table):
+        """(step counter, environment) of every output row, as int64 device tensors."""
+        c = np.concatenate([np.arange(c0, c0 + length) for c0, _, length, _ in table])
+        e = np.concatenate([np.full(length, env) for _, env, length, _ in table])
+        return th.from_numpy(c).to(self.device), th.from_numpy(e).to(self.device)
+
+    def _const_fields(self, rows):
+        out = {}
+        for k, c in self.consts.items():
+            shape = self.const_shapes.get(k, ())
+            out[k] = th.full((1,) + tuple(1 for _ in shape), float(c), device=self.device).expand((rows,) + tuple(shape))
+            out[k]._flex_const = float(c)
+        return out
+
+    def _compose_fields(self, table):
+        c, e = self._table_rows(table)
+        idx = (c * self.block_envs + e) % self.size
+        out = self._const_fields(idx.shape[0])
+        out.update({k: v.index_select(0, idx) for k, v in self.store.items()})
+        return Transition(**out)
+
+    def _compose_slabs(self, table):
+        """What flexnet_gather_episodes writes, as index tensors, ``index_select`` on the rings and the stacked-observation
+        im2col: row i equals ``slab_window`` of one transition at that row's slot."""
+        N, n = self.n_envs, self.n_agents
+        c, e = self._table_rows(table)
+        rows = c.shape[0]
+        p0, p1 = (c % self.slabs) * N + e, ((c + 1) % self.slabs) * N + e
+
+        def take(ring, p):
+            return ring.view(self.slabs * N, -1).index_select(0, p)
+
+        if self.row_mode:
+            state, next_state = self.stacked_rows(c, e), self.stacked_rows(c + 1, e)
+        else:
+            state, next_state = take(self.obs_ring, p0), take(self.obs_ring, p1)
+        na = n * self.act_dim
+        small = take(self.small_ring, p0)
+        out = self._const_fields(rows)
+        out.update({"state": state.reshape(rows, n, self.obs_dim), "next_state": next_state.reshape(rows, n, self.obs_dim),
+                    "last_hid": take(self.hid_ring, p0).view(rows, n, self.hid_dim),
+                    "hid": take(self.hid_ring, p1).view(rows, n, self.hid_dim),
+                    "action": small[:, :na].reshape(rows, n, self.act_dim), "reward": small[:, na:na + n].contiguous(),
+                    "done": small[:, na + n].contiguous(), "last_step": small[:, na + n + 1].contiguous()})
+        for k, ring in self._filed_rings().items():
+            out[k] = take(ring, p0).view((rows,) + tuple(self.const_shapes[k]))
+        return Transition(**out)
+
+    def _gather_slabs(self, table, out=None, dev_table=None):
+        """ONE launch of flexnet_gather_episodes; None where the library answers FLEXNET_EUNSUPPORTED.  ``out``: tensors to
+        write into (tools and tests), field -> contiguous fp32 tensor; ``dev_table``: the table already on the device."""
+        from . import _lib
+        n, rows = self.n_agents, int(table[:, 2].sum())
+        dev = self.device
+        table = np.ascontiguousarray(table, dtype=np.int64)
+        shapes = {"state": (n, self.obs_dim), "next_state": (n, self.obs_dim), "last_hid": (n, self.hid_dim),
+                  "hid": (n, self.hid_dim), "action": (n, self.act_dim), "reward": (n,), "done": (), "last_step": ()}
+        filed = self._filed_rings()
+        for k in filed:
+            shapes[k] = tuple(self.const_shapes[k])
+        if out is None:
+            out = {k: th.empty((rows,) + s, dtype=th.float32, device=dev) for k, s in shapes.items()}
+        if dev_table is None:
+            dev_table = th.from_numpy(table).to(dev)
+        a = _lib.FlexEpisodeGatherArgs()
+        a.row_ring = self.row_ring.data_ptr() if self.row_mode else None
+        a.obs_ring = None if self.row_mode else self.obs_ring.data_ptr()
+        a.hid_ring, a.small_ring = self.hid_ring.data_ptr(), self.small_ring.data_ptr()
+        a.v_ring = self.v_ring.data_ptr() if "value" in filed else None
+        a.nv_ring = self.nv_ring.data_ptr() if "next_value" in filed else None
+        a.lp_ring = self.lp_ring.data_ptr() if "log_prob_a" in filed else None
+        a.episodes, a.episodes_host = dev_table.data_ptr(), table.ctypes.data
+        for k in shapes:
+            setattr(a, k, out[k].data_ptr())
+        a.rows, a.n_episodes, a.n_envs, a.n_agents = rows, table.shape[0], self.n_envs, n
+        a.history, a.obs_dim, a.hid_dim, a.act_dim = self.history or 0, self.obs_dim, self.hid_dim, self.act_dim
+        a.small_w, a.slabs = self.small_w, self.slabs
+        if not _lib.try_launch("flexnet_gather_episodes", a):
+            return None
+        res = self._const_fields(rows)
+        res.update(out)
+        return Transition(**res)
+
+    def get_single(self, index):
+        """replay_buffer.py:38-39: episode ``index`` (0 = the oldest) as its list of per-transition tuples."""
+        w = self.episodes_batch([index])
+        return [Transition(*[f[i] for f in w]) for i in range(w.reward.shape[0])]
+
+    def get_batch(self, batch_size):
+        """replay_buffer.py:44-50: the drawn episodes' per-transition tuples, one list (device tensors inside)."""
+        w = self.get_batch_tensors(batch_size)
+        return [Transition(*[f[i] for f in w]) for i in range(w.reward.shape[0])]
+
+    # -- the list store as logical transitions (columns an on-policy learner files after the fact) ---------------------------
+    def contiguous_runs(self):
+        if self.ring_store:
+            return super().contiguous_runs()
+        out, at = [], 0
+        for ep in self.episodes:
+            out.append((at, ep["reward"].shape[0]))
+            at += ep["reward"].shape[0]
+        return out
+
+    def _locate(self, start, rows):
+        for (at, count), ep in zip(self.contiguous_runs(), self.episodes):
+            if at <= start and start + rows <= at + count:
+                return ep, start - at
+        raise ValueError("window spans two episodes")
+
+    def window(self, start, batch_size):
+        if self.ring_store:
+            return super().window(start, batch_size)
+        ep, off = self._locate(start, batch_size)
+        return Transition(**{k: ep[k][off:off + batch_size] for k in FIELDS})
+
+    def file_columns(self, start, rows, **cols):
+        if self.ring_store:
+            return super().file_columns(start, rows, **cols)
+        ep, off = self._locate(start, rows)
+        for k, v in cols.items():
+            ep[k][off:off + rows].copy_(v.reshape((rows,) + ep[k].shape[1:]))
+
+    def field_rows(self, name):
+        if self.ring_store:
+            return super().field_rows(name)
+        return self.episodes[0][name].shape[1]

@@ -34,10 +34,15 @@ _RMSPROP = dict(alpha=0.99, eps=1e-5)       # trainer.py:34-35
 class PGTrainer(object):
     def __init__(self, args, model, env, logger, batch_scale=None, replay_capacity=None, graph_rollout=True,
                  graph_updates=True, sync_reward_bn=None):
-        if args.episodic:
-            raise NotImplementedError("episodic replay is outside the MADDPG hot path (default.yaml:9)")
         self.args, self.env, self.logger = args, env, logger
-        self.episodic = False
+        # default.yaml:9 — updates once per episode from a replay of whole episodes (trainer.py:29-33, model.py:73-86).  Its
+        # batches' row counts depend on the data, so episodic sub-updates always run eagerly: never as captured graphs, never
+        # through replay_event's pipeline
+        self.episodic = bool(getattr(args, "episodic", False))
+        if self.episodic and not args.replay:
+            raise NotImplementedError("episodic updates without a replay read a buffer the reference never builds (model.py:87-97)")
+        if self.episodic and fdist.world_size() > 1:
+            raise NotImplementedError("episodic replay on more than one rank is out of scope")
         self.device = th.device("cuda" if th.cuda.is_available() and args.cuda else "cpu")
         self.steps = self.episodes = 0
         self.graph_rollout = graph_rollout      # vectorised envs: replay each rollout step as one HIP graph
@@ -111,7 +116,20 @@ class PGTrainer(object):
         self.on_policy = bool(getattr(net, "on_policy", False))
         if batch_scale is None:
             batch_scale = 1 if n_envs == 1 else (n_envs if self.on_policy else max(1, n_envs // 4))
+            if self.episodic and n_envs > 1:
+                # a batch is batch_size * batch_scale EPISODES of up to `horizon` rows: as many whole blocks' worth of rows as fit
+                # into the transition mode's default batch at the same n_envs (never less than one: DESIGN.md §4.7)
+                batch_scale = max(1, batch_scale // self._block_steps())
         self.batch_scale = batch_scale
+        if self.episodic:
+            # PPO's GAE chains are rows i -> i + 1 of a batch of concatenated episodes (gae_chain_stride = 1, the reference's own
+            # layout); every episode ends with last_step = 1, which is where a chain stops
+            if args.replay:
+                from .replay_buffer import EpisodeReplayBuffer
+                self.replay_buffer = EpisodeReplayBuffer(int(args.replay_buffer_size), device=self.device)
+                if n_envs > 1 or hasattr(env, "handle"):
+                    self.replay_buffer.configure_blocks(n_envs, self._block_steps())
+            return
         if self.on_policy and n_envs > 1:
             if self.effective_batch_size() % n_envs != 0:
                 raise ValueError(f"an on-policy batch of {self.effective_batch_size()} transitions is not a whole number of "
@@ -126,6 +144,10 @@ class PGTrainer(object):
                     replay_capacity = max(replay_capacity, (int(args.behaviour_update_freq) + 4) * n_envs)
             self.replay_buffer = TransReplayBuffer(replay_capacity, device=self.device)
 
+    def _block_steps(self):
+        """Vector steps of one train_process call on a vectorised env (learner._train_process_vec's horizon)."""
+        return int(min(self.args.max_steps, getattr(self.env, "episode_limit", self.args.max_steps + 1) - 1))
+
     # ---- sampling ----------------------------------------------------------------------------
     def effective_batch_size(self):
         return self.args.batch_size * self.batch_scale
@@ -135,16 +157,18 @@ class PGTrainer(object):
 
     def _sample_batch(self):
         """The eager sub-updates' batch: utils/replay_buffer.py:17-21, step-aligned for the pooled on-policy windows."""
+        if self.episodic:                           # replay_buffer.py:44-50: whole episodes, effective_batch_size() of them
+            return self.replay_buffer.get_batch_tensors(self.effective_batch_size())
         if self.on_policy and self.n_envs > 1:
             return self.replay_buffer.get_window_aligned(self.effective_batch_size(), self.n_envs)
         return self.replay_buffer.get_batch_tensors(self.effective_batch_size())
 
     def policy_replay_process(self, stat):      # model.py:50
-        if not self._graphed_sub_update("policy", stat):
+        if self.episodic or not self._graphed_sub_update("policy", stat):
             self._sub_update("policy", stat, self._sample_batch())
 
     def value_replay_process(self, stat):       # model.py:48
-        if not self._graphed_sub_update("value", stat):
+        if self.episodic or not self._graphed_sub_update("value", stat):
             self._sub_update("value", stat, self._sample_batch())
 
     def mixer_replay_process(self, stat):       # model.py:51-53 (eager: FACMADDPG's sub-updates are not graphed)
