@@ -861,7 +861,8 @@ int flexnet_coma_policy_loss(const FlexComaPolicyArgs* args, void* stream);
  *         y[e, k] = tanh(((m[e,0,k] + m[e,1,k]) + ..) + exp((ls[e,0,k] + ls[e,1,k]) + ..) eps[e, k]), handed to every
  *         agent, and env_action (optional) = translate_action of it.  n_agents <= FLEXNET_MAX_AGENTS, act_dim <=
  *         FLEXNET_MAX_ACT, n_envs * act_dim < 2^31; else FLEXNET_EUNSUPPORTED.
- * ppo rows:      flexnet_ppo_policy_loss with log_stds [rows, n, a], summed over agents per row like the means:
+ * ppo rows:      (csrc/ppo.hip: the other instantiation of flexnet_ppo_policy_loss's one kernel body, with that file's
+ *         helpers and finish.)  flexnet_ppo_policy_loss with log_stds [rows, n, a], summed over agents per row like the means:
  *         sigma[b, k] = exp(sum_i log_stds[b, i, k]);  besides d_means, d_log_stds[b, i, k] = sum_j dloss/dlogp[b, j]
  *         ((actions[b, j, k] - mu[b, k])^2 / sigma[b, k]^2 - 1) for every agent i (optional).  Same workspace, fp64 block
  *         sums and finish, same ties.  n_agents / act_dim beyond the maxima, rows >= 2^28: FLEXNET_EUNSUPPORTED. */

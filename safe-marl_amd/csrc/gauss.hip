@@ -1,5 +1,5 @@
 // gauss.hip — the learned log-std head of the Gaussian actors and what consumes per-row standard deviations (gfx950).
-// Boundary: include/flexnet.h (flexnet_gauss_*, flexnet_ppo_policy_loss_rows).
+// Boundary: include/flexnet.h (flexnet_gauss_*).
 //
 // madrl/agents/{rnn,mlp}_agent_gaussian.py: log_std = MIN + 0.5 (MAX - MIN) (tanh(W h + b) + 1) on the actor's hidden state
 // h [rows, 64], W [a, 64] with a <= 8.
@@ -13,16 +13,17 @@
 //                   are flexnet_wgrad(d_u, h) with its column sums.
 //   per-agent heads: head forward / backward with the weights of agent r % n for row r (shared_params: False), on the actors'
 //                   work map — a wavefront owns 32 rows of one agent — so that the weights stay uniform per wavefront;
-//                   eager calls only, like the actors they follow.
+//                   eager calls only, like the actors they follow.  The SAME two bodies as the shared
+//                   head's (templates over the argument struct), without the exploration epilogue.
 //   sum explore:    the agent-summed selection of iddpg.py:64-70 / matd3.py:91-98 with per-sample log-stds, one thread per
 //                   (environment, action component), every fp32 rounding where the tensor composition has it.
-//   ppo rows:       ppo.hip's policy loss with log_stds [rows, n, a] (summed over agents per row) and d_log_stds.
-// No LDS beyond the loss sum, no scratch, no atomics: the same inputs give the same bits.
+// (PPO's policy loss on per-row log-stds, flexnet_ppo_policy_loss_rows, is an instantiation of ppo.hip's one body and lives there.)
+// No LDS, no scratch, no atomics: the same inputs give the same bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "flexnet.h"
 #include "flex_launch.h"
-#include "flex_reduce.h"
 #include "flex_mfma_tile.h"
 
 #define GAUSS_THREADS 256
@@ -35,11 +36,35 @@ __device__ __forceinline__ float gauss_env_action(float y, float lo, float hi) {
     return __fadd_rn(__fmul_rn(__fmul_rn(0.5f, __fadd_rn(c, 1.0f)), hi - lo), lo);
 }
 
-__global__ __launch_bounds__(GAUSS_THREADS) void gauss_head_forward_kernel(FlexGaussHeadArgs a) {
-    const int lane = threadIdx.x & 63, i = lane & 31, hf = lane >> 5;
+// ---- the head, both ways: ONE body each, a template over the argument struct (A = FlexGaussHeadArgs or, shared_params: False,
+// FlexGaussHeadUnsharedArgs).  The forms differ in the row map, in where W and b come from and in the exploration epilogue,
+// which only the shared form has; per row the arithmetic — and so the bits — are the same code.
+struct GaussRow { int64_t row; bool ok; int ag; };
+
+// shared weights: consecutive rows, 32 per wavefront
+__device__ __forceinline__ GaussRow gauss_row(const FlexGaussHeadArgs& a, int i) {
     const int64_t row = (int64_t)blockIdx.x * GAUSS_ROWS + (threadIdx.x >> 6) * 32 + i;
-    const bool ok = row < a.rows;
+    return {row, row < a.rows, 0};
+}
+// per-agent weights, the actors' work map: a wavefront owns 32 samples of ONE agent (rows s * n + ag), a work-group is four
+// wavefronts of agent blockIdx.x % n, so W and b are one uniform pointer per work-group out of the tables
+__device__ __forceinline__ GaussRow gauss_row(const FlexGaussHeadUnsharedArgs& a, int i) {
+    const int n = a.n_agents, ag = blockIdx.x % n;
+    const int64_t s = ((int64_t)(blockIdx.x / n) * (GAUSS_THREADS / 64) + (threadIdx.x >> 6)) * 32 + i;
+    return {s * n + ag, s < a.rows / n, ag};
+}
+__device__ __forceinline__ const float* gauss_pick(const float* p, int) { return p; }
+__device__ __forceinline__ const float* gauss_pick(const float* const (&p)[FLEXNET_MAX_AGENTS], int ag) { return p[ag]; }
+
+template <class A>
+__device__ __forceinline__ void gauss_head_forward(const A& a) {
+    const int lane = threadIdx.x & 63, i = lane & 31, hf = lane >> 5;
+    const GaussRow m = gauss_row(a, i);
+    const int64_t row = m.row;
+    const bool ok = m.ok;
     const int na = a.act_dim;
+    const float* W = gauss_pick(a.w, m.ag);
+    const float* B = gauss_pick(a.b, m.ag);
     tv16 x0, x1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { x0[r] = 0.0f; x1[r] = 0.0f; }
@@ -54,7 +79,7 @@ __global__ __launch_bounds__(GAUSS_THREADS) void gauss_head_forward_kernel(FlexG
     for (int k = 0; k < FLEXNET_MAX_ACT; ++k) {
         ls[k] = 0.0f; t[k] = 0.0f;
         if (k < na) {                                   // (the same for every lane: the exchange below is wavefront-wide)
-            const float* wr = a.w + k * SH + 4 * hf;
+            const float* wr = W + k * SH + 4 * hf;
             float p0 = 0.0f, p1 = 0.0f;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -67,7 +92,7 @@ __global__ __launch_bounds__(GAUSS_THREADS) void gauss_head_forward_kernel(FlexG
             }
             const float p = p0 + p1;
             float u = p + other_half(p);                // (an fp32 add commutes: both halves hold the same bits)
-            if (a.b) u += a.b[k];
+            if (B) u += B[k];
             t[k] = tanhf(u);
             ls[k] = a.log_std_min + half_span * (t[k] + 1.0f);
         }
@@ -84,7 +109,8 @@ __global__ __launch_bounds__(GAUSS_THREADS) void gauss_head_forward_kernel(FlexG
             for (int k = 0; k < FLEXNET_MAX_ACT; ++k)
                 if (k < na) to[k] = t[k];
         }
-    } else if (a.action) {
+    } else if constexpr (std::is_same_v<A, FlexGaussHeadArgs>) {      // the exploration epilogue: the shared form's alone
+        if (!a.action) return;
         const float* mp = a.means + row * na;
         const float* np_ = a.noise + row * na;
         float* ao = a.action + row * na;
@@ -98,11 +124,14 @@ __global__ __launch_bounds__(GAUSS_THREADS) void gauss_head_forward_kernel(FlexG
     }
 }
 
-__global__ __launch_bounds__(GAUSS_THREADS) void gauss_head_backward_kernel(FlexGaussHeadArgs a) {
+template <class A>
+__device__ __forceinline__ void gauss_head_backward(const A& a) {
     const int lane = threadIdx.x & 63, i = lane & 31, hf = lane >> 5;
-    const int64_t row = (int64_t)blockIdx.x * GAUSS_ROWS + (threadIdx.x >> 6) * 32 + i;
-    if (row >= a.rows) return;                          // (no exchange between lanes in this kernel)
+    const GaussRow m = gauss_row(a, i);
+    if (!m.ok) return;                                  // (no exchange between lanes in this kernel)
+    const int64_t row = m.row;
     const int na = a.act_dim;
+    const float* W = gauss_pick(a.w, m.ag);
     const float half_span = 0.5f * (a.log_std_max - a.log_std_min);
     float du[FLEXNET_MAX_ACT];
 #pragma unroll
@@ -119,26 +148,36 @@ __global__ __launch_bounds__(GAUSS_THREADS) void gauss_head_backward_kernel(Flex
             if (k < na) a.d_u[row * na + k] = du[k];
     }
     if (!a.d_h) return;
-    tv16 g0, g1;
+    // The lane's two tiles one after the other (per element the same chain of FMAs over k, so the same bits): with both sets of
+    // accumulators live the body, inlined into its kernels, takes 82 VGPRs and 5 waves per SIMD where the kernels had 7.
+    float* dr = a.d_h + row * SH + 4 * hf;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) { g0[r] = 0.0f; g1[r] = 0.0f; }
+    for (int t = 0; t < 2; ++t) {
+        tv16 g;
 #pragma unroll
-    for (int k = 0; k < FLEXNET_MAX_ACT; ++k)
-        if (k < na) {
-            const float* wr = a.w + k * SH + 4 * hf;
+        for (int r = 0; r < 16; ++r) g[r] = 0.0f;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const tv4 w0 = ld4(wr + 8 * q), w1 = ld4(wr + 32 + 8 * q);
+        for (int k = 0; k < FLEXNET_MAX_ACT; ++k)
+            if (k < na) {
+                const float* wr = W + k * SH + 4 * hf + 32 * t;
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    g0[4 * q + j] = fmaf(du[k], w0[j], g0[4 * q + j]);
-                    g1[4 * q + j] = fmaf(du[k], w1[j], g1[4 * q + j]);
+                for (int q = 0; q < 4; ++q) {
+                    const tv4 w = ld4(wr + 8 * q);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) g[4 * q + j] = fmaf(du[k], w[j], g[4 * q + j]);
                 }
             }
-        }
-    float* dr = a.d_h + row * SH + 4 * hf;
-    store_tile(dr, g0, true);
-    store_tile(dr + 32, g1, true);
+        store_tile(dr + 32 * t, g, true);
+    }
+}
+
+__global__ __launch_bounds__(GAUSS_THREADS) void gauss_head_forward_kernel(FlexGaussHeadArgs a) { gauss_head_forward(a); }
+__global__ __launch_bounds__(GAUSS_THREADS) void gauss_head_backward_kernel(FlexGaussHeadArgs a) { gauss_head_backward(a); }
+__global__ __launch_bounds__(GAUSS_THREADS) void gauss_head_unshared_forward_kernel(FlexGaussHeadUnsharedArgs a) {
+    gauss_head_forward(a);
+}
+__global__ __launch_bounds__(GAUSS_THREADS) void gauss_head_unshared_backward_kernel(FlexGaussHeadUnsharedArgs a) {
+    gauss_head_backward(a);
 }
 
 static int gauss_head_check(const FlexGaussHeadArgs* a) {
@@ -174,111 +213,6 @@ extern "C" int flexnet_gauss_head_backward(const FlexGaussHeadArgs* a, void* str
 }
 
 // ---- shared_params: False: every agent's own head (FlexGaussHeadUnsharedArgs) ------------------------------------------------
-// The two kernels above with the actors' work map instead of consecutive rows: a wavefront owns 32 samples of ONE agent (rows
-// s * n + a), a work-group is four wavefronts of agent blockIdx.x % n, so W and b are one uniform pointer per work-group out of
-// the tables.  Per row the arithmetic — and so the bits — are gauss_head_*_kernel's on that agent's weights.
-__global__ __launch_bounds__(GAUSS_THREADS) void gauss_head_unshared_forward_kernel(FlexGaussHeadUnsharedArgs a) {
-    const int lane = threadIdx.x & 63, i = lane & 31, hf = lane >> 5;
-    const int n = a.n_agents, ag = blockIdx.x % n;
-    const int64_t batch = a.rows / n;
-    const int64_t s = ((int64_t)(blockIdx.x / n) * (GAUSS_THREADS / 64) + (threadIdx.x >> 6)) * 32 + i;
-    const bool ok = s < batch;
-    const int64_t row = s * n + ag;
-    const int na = a.act_dim;
-    const float* W = a.w[ag];
-    const float* B = a.b[ag];
-    tv16 x0, x1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { x0[r] = 0.0f; x1[r] = 0.0f; }
-    if (ok) {
-        const float* hr = a.h + row * SH + 4 * hf;
-        x0 = load_tile(hr);
-        x1 = load_tile(hr + 32);
-    }
-    const float half_span = 0.5f * (a.log_std_max - a.log_std_min);
-    float ls[FLEXNET_MAX_ACT], t[FLEXNET_MAX_ACT];
-#pragma unroll
-    for (int k = 0; k < FLEXNET_MAX_ACT; ++k) {
-        ls[k] = 0.0f; t[k] = 0.0f;
-        if (k < na) {                                   // (the same for every lane: the exchange below is wavefront-wide)
-            const float* wr = W + k * SH + 4 * hf;
-            float p0 = 0.0f, p1 = 0.0f;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const tv4 w0 = ld4(wr + 8 * q), w1 = ld4(wr + 32 + 8 * q);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    p0 = fmaf(x0[4 * q + j], w0[j], p0);
-                    p1 = fmaf(x1[4 * q + j], w1[j], p1);
-                }
-            }
-            const float p = p0 + p1;
-            float u = p + other_half(p);
-            if (B) u += B[k];
-            t[k] = tanhf(u);
-            ls[k] = a.log_std_min + half_span * (t[k] + 1.0f);
-        }
-    }
-    if (!ok || hf != 0) return;
-    float* lo = a.log_std + row * na;
-#pragma unroll
-    for (int k = 0; k < FLEXNET_MAX_ACT; ++k)
-        if (k < na) lo[k] = ls[k];
-    if (a.t) {
-        float* to = a.t + row * na;
-#pragma unroll
-        for (int k = 0; k < FLEXNET_MAX_ACT; ++k)
-            if (k < na) to[k] = t[k];
-    }
-}
-
-__global__ __launch_bounds__(GAUSS_THREADS) void gauss_head_unshared_backward_kernel(FlexGaussHeadUnsharedArgs a) {
-    const int lane = threadIdx.x & 63, i = lane & 31, hf = lane >> 5;
-    const int n = a.n_agents, ag = blockIdx.x % n;
-    const int64_t batch = a.rows / n;
-    const int64_t s = ((int64_t)(blockIdx.x / n) * (GAUSS_THREADS / 64) + (threadIdx.x >> 6)) * 32 + i;
-    if (s >= batch) return;                             // (no exchange between lanes in this kernel)
-    const int64_t row = s * n + ag;
-    const int na = a.act_dim;
-    const float* W = a.w[ag];
-    const float half_span = 0.5f * (a.log_std_max - a.log_std_min);
-    float du[FLEXNET_MAX_ACT];
-#pragma unroll
-    for (int k = 0; k < FLEXNET_MAX_ACT; ++k) {
-        du[k] = 0.0f;
-        if (k < na) {
-            const float tt = a.t[row * na + k];
-            du[k] = a.d_log_std[row * na + k] * (half_span * (1.0f - tt * tt));
-        }
-    }
-    if (hf == 0 && a.d_u) {
-#pragma unroll
-        for (int k = 0; k < FLEXNET_MAX_ACT; ++k)
-            if (k < na) a.d_u[row * na + k] = du[k];
-    }
-    if (!a.d_h) return;
-    tv16 g0, g1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { g0[r] = 0.0f; g1[r] = 0.0f; }
-#pragma unroll
-    for (int k = 0; k < FLEXNET_MAX_ACT; ++k)
-        if (k < na) {
-            const float* wr = W + k * SH + 4 * hf;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const tv4 w0 = ld4(wr + 8 * q), w1 = ld4(wr + 32 + 8 * q);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    g0[4 * q + j] = fmaf(du[k], w0[j], g0[4 * q + j]);
-                    g1[4 * q + j] = fmaf(du[k], w1[j], g1[4 * q + j]);
-                }
-            }
-        }
-    float* dr = a.d_h + row * SH + 4 * hf;
-    store_tile(dr, g0, true);
-    store_tile(dr + 32, g1, true);
-}
-
 static int gauss_head_unshared_check(const FlexGaussHeadUnsharedArgs* a) {
     if (!a || a->rows < 0 || a->act_dim < 1 || a->n_agents < 1) return FLEXNET_EINVAL;
     if (a->hid != FLEXNET_HID || a->act_dim > FLEXNET_MAX_ACT || a->n_agents > FLEXNET_MAX_AGENTS || a->rows > GAUSS_MAX_ROWS)
@@ -353,101 +287,5 @@ extern "C" int flexnet_gauss_sum_explore(const FlexGaussSumArgs* a, void* stream
     const int64_t tot = (int64_t)a->n_envs * a->act_dim;
     if (tot > 0x7fffffff) return FLEXNET_EUNSUPPORTED;
     hipLaunchKernelGGL(gauss_sum_explore_kernel, dim3((int)((tot + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *a);
-    return flex_launch_status();
-}
-
-// ---- PPO's policy loss on per-row log-stds (ppo.hip's ppo_policy_kernel with exp / log per row) --------------------------
-#define GPPO_THREADS 256
-#define GPPO_BLOCKS FLEXNET_PPO_BLOCKS
-#define GPPO_WS_LOSS FLEXNET_TD_WS_FLOATS           // (doubles) the loss partials' place in the PPO workspace, as ppo.hip's
-
-// th.min / th.clamp hand a NaN on (fminf would drop it and report a finite loss for a diverged run)
-__device__ __forceinline__ float gppo_minf(float a, float b) { return (a < b || a != a) ? a : b; }
-__device__ __forceinline__ float gppo_clampf(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
-// (ppo.hip's ppo_loss_finish_kernel again: that kernel is local to its file, which this one leaves as it is)
-__global__ __launch_bounds__(64) void gauss_loss_finish_kernel(const double* partial, double scale, float* loss) {
-    flex_loss_finish(partial, GPPO_BLOCKS, scale, loss);
-}
-
-__global__ __launch_bounds__(GPPO_THREADS) void ppo_policy_rows_kernel(FlexPpoPolicyRowsArgs a) {
-    const int n = a.n_agents, na = a.act_dim;
-    const float lo = 1.0f - a.eps_clip, hi = 1.0f + a.eps_clip;
-    const float inv = 1.0f / (float)(a.rows * n);
-    double acc = 0.0;
-    for (int64_t b = (int64_t)blockIdx.x * GPPO_THREADS + threadIdx.x; b < a.rows; b += (int64_t)GPPO_BLOCKS * GPPO_THREADS) {
-        const float* mp = a.means + b * n * na;
-        const float* lp = a.log_stds + b * n * na;
-        const float* ap = a.actions + b * n * na;
-        float mu[FLEXNET_MAX_ACT], g[FLEXNET_MAX_ACT], gl[FLEXNET_MAX_ACT];
-        float inv2var[FLEXNET_MAX_ACT], invvar[FLEXNET_MAX_ACT], logc[FLEXNET_MAX_ACT];
-#pragma unroll
-        for (int k = 0; k < FLEXNET_MAX_ACT; ++k) {
-            float s = 0.0f, l = 0.0f;
-            if (k < na) {
-                s = mp[k]; l = lp[k];
-                for (int i = 1; i < n; ++i) { s += mp[i * na + k]; l += lp[i * na + k]; }     // agent order
-            }
-            // Normal(mu, exp(log_std)).log_prob: -(x - mu)^2 / (2 var) - log(std) - log(sqrt(2 pi))
-            const float sd = expf(l);
-            const float var = sd * sd;
-            mu[k] = s; g[k] = 0.0f; gl[k] = 0.0f;
-            inv2var[k] = 1.0f / (2.0f * var); invvar[k] = 1.0f / var;
-            logc[k] = logf(sd) + 0.918938533204672742f;
-        }
-        for (int i = 0; i < n; ++i) {
-            float logp = 0.0f, old = 0.0f;
-#pragma unroll
-            for (int k = 0; k < FLEXNET_MAX_ACT; ++k)
-                if (k < na) {
-                    const float x = ap[i * na + k], d = x - mu[k];
-                    logp += -(d * d) * inv2var[k] - logc[k];
-                    old += x;                                          // model.py:313: old_log_prob_a IS the action
-                }
-            if (a.old_log_prob) old = a.old_log_prob[b * n + i];
-            const float ratio = expf(logp - old);
-            const float adv = a.advantages[b * n + i];
-            const bool inside = ratio >= lo && ratio <= hi;
-            const float clipped = gppo_clampf(ratio, lo, hi);
-            const float s1 = ratio * adv, s2 = clipped * adv;
-            acc += (double)gppo_minf(s1, s2);
-            // th.min: half the gradient to each argument at a tie; th.clamp: gradient inside [lo, hi], ends included
-            const float w1 = s1 < s2 ? 1.0f : (s1 == s2 ? 0.5f : 0.0f);
-            const float w2 = (1.0f - w1) * (inside ? 1.0f : 0.0f);
-            const float dlogp = -inv * (w1 + w2) * adv * ratio;        // d loss / d log p[b, i]
-            if (a.ratio) a.ratio[b * n + i] = ratio;
-#pragma unroll
-            for (int k = 0; k < FLEXNET_MAX_ACT; ++k)
-                if (k < na) {
-                    const float d = ap[i * na + k] - mu[k];
-                    g[k] += dlogp * d * invvar[k];
-                    gl[k] += dlogp * (d * d * invvar[k] - 1.0f);       // d log p / d log_std = (x - mu)^2 / var - 1
-                }
-        }
-        float* dp = a.d_means + b * n * na;
-        float* dl = a.d_log_stds ? a.d_log_stds + b * n * na : nullptr;
-        for (int i = 0; i < n; ++i)
-#pragma unroll
-            for (int k = 0; k < FLEXNET_MAX_ACT; ++k)
-                if (k < na) {                                          // the sums over agents hand them to every agent
-                    dp[i * na + k] = g[k];
-                    if (dl) dl[i * na + k] = gl[k];
-                }
-    }
-    flex_block_sum_f64<GPPO_THREADS>(acc, reinterpret_cast<double*>(a.workspace) + GPPO_WS_LOSS);
-}
-
-extern "C" int flexnet_ppo_policy_loss_rows(const FlexPpoPolicyRowsArgs* a, void* stream) {
-    if (!a || a->rows < 1 || a->n_agents < 1 || a->act_dim < 1 || !a->means || !a->log_stds || !a->actions || !a->advantages ||
-        !a->loss || !a->d_means || !a->workspace || a->workspace_floats < FLEXNET_PPO_WS_FLOATS ||
-        !flex_aligned(a->workspace, 8))
-        return FLEXNET_EINVAL;
-    if (a->n_agents > FLEXNET_MAX_AGENTS || a->act_dim > FLEXNET_MAX_ACT || a->rows >= ((int64_t)1 << 28))
-        return FLEXNET_EUNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(ppo_policy_rows_kernel, dim3(GPPO_BLOCKS), dim3(GPPO_THREADS), 0, s, *a);
-    hipLaunchKernelGGL(gauss_loss_finish_kernel, dim3(1), dim3(64), 0, s,
-                       reinterpret_cast<const double*>(a->workspace) + GPPO_WS_LOSS,
-                       -1.0 / ((double)a->rows * a->n_agents), a->loss);
     return flex_launch_status();
 }

@@ -9,6 +9,9 @@
 //            moves them.  The recurrence is a composition of affine maps x -> b_i + a_i x: a chain is a reverse scan.
 //   policy:  mu = sum over agents of the means;  log p = sum_k log N(act_k; mu_k, sigma_k);  ratio = exp(log p - old);
 //            loss = -mean(min(ratio A^, clamp(ratio, 1 -+ eps) A^));  d loss / d means (the same for every agent).
+//            ONE body, two instantiations: sigma from a fixed log_std [a] (flexnet_ppo_policy_loss), or from the Gaussian
+//            actors' log_stds [rows, n, a], summed over agents per row like the means, with d loss / d log_stds besides
+//            (flexnet_ppo_policy_loss_rows, declared in flexnet.h's Gaussian section).
 //   value:   ret = r^ + gamma (1 - done) V(s');  vc = old + clamp(V - old, -+eps);
 //            loss = coef mean(max((V - ret)^2, (vc - ret)^2));  d loss / d V.
 // Pointwise values are formed in fp32 in the order the tensor composition forms them (so branch decisions agree with it);
@@ -20,6 +23,7 @@
 // value exactly eps away from the old one still passes the clipped branch's gradient.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "flexnet.h"
 #include "flex_launch.h"
 #include "flex_reduce.h"
@@ -175,32 +179,47 @@ __global__ __launch_bounds__(64) void ppo_loss_finish_kernel(const double* parti
     flex_loss_finish(partial, PPO_BLOCKS, scale, loss);
 }
 
-__global__ __launch_bounds__(PPO_THREADS) void ppo_policy_kernel(FlexPpoPolicyArgs a) {
+// Normal(mu, sd).log_prob(x) = -(x - mu)^2 inv2var - logc, and its d / d mu = (x - mu) invvar
+__device__ __forceinline__ void ppo_normal(float sd, float& inv2var, float& invvar, float& logc) {
+    const float var = sd * sd;
+    inv2var = 1.0f / (2.0f * var); invvar = 1.0f / var;
+    logc = logf(sd) + 0.918938533204672742f;           // log(std) + log(sqrt(2 pi))
+}
+
+// The policy loss, ONE body: A = FlexPpoPolicyArgs (the fixed-std policy: log_std [a], already summed over the agents, so the
+// Normal's constants are formed once in front of the row loop) or FlexPpoPolicyRowsArgs (learned log-stds [rows, n, a], summed
+// over the agents per row like the means: the constants are formed per row, and d_log_stds comes out besides d_means).
+template <class A>
+__device__ __forceinline__ void ppo_policy(const A& a) {
+    constexpr bool ROWS = std::is_same_v<A, FlexPpoPolicyRowsArgs>;
     const int n = a.n_agents, na = a.act_dim;
     const float lo = 1.0f - a.eps_clip, hi = 1.0f + a.eps_clip;
     const float inv = 1.0f / (float)(a.rows * n);
     float inv2var[FLEXNET_MAX_ACT], invvar[FLEXNET_MAX_ACT], logc[FLEXNET_MAX_ACT];
+    if constexpr (!ROWS) {
 #pragma unroll
-    for (int k = 0; k < FLEXNET_MAX_ACT; ++k) {
-        // Normal(mu, exp(log_std)).log_prob: -(x - mu)^2 / (2 var) - log(std) - log(sqrt(2 pi))
-        const float sd = k < na ? expf(a.log_std[k]) : 1.0f;
-        const float var = sd * sd;
-        inv2var[k] = 1.0f / (2.0f * var); invvar[k] = 1.0f / var;
-        logc[k] = logf(sd) + 0.918938533204672742f;
+        for (int k = 0; k < FLEXNET_MAX_ACT; ++k) ppo_normal(k < na ? expf(a.log_std[k]) : 1.0f, inv2var[k], invvar[k], logc[k]);
     }
     double acc = 0.0;
     for (int64_t b = (int64_t)blockIdx.x * PPO_THREADS + threadIdx.x; b < a.rows; b += (int64_t)PPO_BLOCKS * PPO_THREADS) {
         const float* mp = a.means + b * n * na;
         const float* ap = a.actions + b * n * na;
-        float mu[FLEXNET_MAX_ACT], g[FLEXNET_MAX_ACT];
+        const float* lp = nullptr;
+        if constexpr (ROWS) lp = a.log_stds + b * n * na;
+        float mu[FLEXNET_MAX_ACT], g[FLEXNET_MAX_ACT], gl[FLEXNET_MAX_ACT];
 #pragma unroll
         for (int k = 0; k < FLEXNET_MAX_ACT; ++k) {
-            float s = 0.0f;
+            float s = 0.0f, l = 0.0f;
             if (k < na) {
                 s = mp[k];
-                for (int i = 1; i < n; ++i) s += mp[i * na + k];      // agent order, as the pointwise adds of the composition
+                if constexpr (ROWS) l = lp[k];
+                for (int i = 1; i < n; ++i) {           // agent order, as the pointwise adds of the composition
+                    s += mp[i * na + k];
+                    if constexpr (ROWS) l += lp[i * na + k];
+                }
             }
-            mu[k] = s; g[k] = 0.0f;
+            mu[k] = s; g[k] = 0.0f; gl[k] = 0.0f;
+            if constexpr (ROWS) ppo_normal(expf(l), inv2var[k], invvar[k], logc[k]);
         }
         for (int i = 0; i < n; ++i) {
             float logp = 0.0f, old = 0.0f;
@@ -225,15 +244,37 @@ __global__ __launch_bounds__(PPO_THREADS) void ppo_policy_kernel(FlexPpoPolicyAr
             if (a.ratio) a.ratio[b * n + i] = ratio;
 #pragma unroll
             for (int k = 0; k < FLEXNET_MAX_ACT; ++k)
-                if (k < na) g[k] += dlogp * (ap[i * na + k] - mu[k]) * invvar[k];
+                if (k < na) {
+                    const float d = ap[i * na + k] - mu[k];
+                    g[k] += dlogp * d * invvar[k];
+                    if constexpr (ROWS) gl[k] += dlogp * (d * d * invvar[k] - 1.0f);   // d log p / d log_std = (x - mu)^2 / var - 1
+                }
         }
         float* dp = a.d_means + b * n * na;
+        float* dl = nullptr;
+        if constexpr (ROWS) dl = a.d_log_stds ? a.d_log_stds + b * n * na : nullptr;
         for (int i = 0; i < n; ++i)
 #pragma unroll
             for (int k = 0; k < FLEXNET_MAX_ACT; ++k)
-                if (k < na) dp[i * na + k] = g[k];                     // the sum over agents hands it to every agent
+                if (k < na) {                                          // the sums over agents hand them to every agent
+                    dp[i * na + k] = g[k];
+                    if (dl) dl[i * na + k] = gl[k];
+                }
     }
     flex_block_sum_f64<PPO_THREADS>(acc, reinterpret_cast<double*>(a.workspace) + PPO_WS_LOSS);
+}
+
+__global__ __launch_bounds__(PPO_THREADS) void ppo_policy_kernel(FlexPpoPolicyArgs a) { ppo_policy(a); }
+__global__ __launch_bounds__(PPO_THREADS) void ppo_policy_rows_kernel(FlexPpoPolicyRowsArgs a) { ppo_policy(a); }
+
+// the policy loss of both forms: the kernel, then the finish
+template <class A, class K>
+static int ppo_policy_launch(const A* a, K kernel, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(kernel, dim3(PPO_BLOCKS), dim3(PPO_THREADS), 0, s, *a);
+    hipLaunchKernelGGL(ppo_loss_finish_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<const double*>(a->workspace) + PPO_WS_LOSS,
+                       -1.0 / ((double)a->rows * a->n_agents), a->loss);
+    return flex_launch_status();
 }
 
 extern "C" int flexnet_ppo_policy_loss(const FlexPpoPolicyArgs* a, void* stream) {
@@ -242,11 +283,17 @@ extern "C" int flexnet_ppo_policy_loss(const FlexPpoPolicyArgs* a, void* stream)
         !flex_aligned(a->workspace, 8))
         return FLEXNET_EINVAL;
     if (a->n_agents > FLEXNET_MAX_AGENTS || a->act_dim > FLEXNET_MAX_ACT) return FLEXNET_EUNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(ppo_policy_kernel, dim3(PPO_BLOCKS), dim3(PPO_THREADS), 0, s, *a);
-    hipLaunchKernelGGL(ppo_loss_finish_kernel, dim3(1), dim3(64), 0, s, reinterpret_cast<const double*>(a->workspace) + PPO_WS_LOSS,
-                       -1.0 / ((double)a->rows * a->n_agents), a->loss);
-    return flex_launch_status();
+    return ppo_policy_launch(a, ppo_policy_kernel, stream);
+}
+
+extern "C" int flexnet_ppo_policy_loss_rows(const FlexPpoPolicyRowsArgs* a, void* stream) {
+    if (!a || a->rows < 1 || a->n_agents < 1 || a->act_dim < 1 || !a->means || !a->log_stds || !a->actions || !a->advantages ||
+        !a->loss || !a->d_means || !a->workspace || a->workspace_floats < FLEXNET_PPO_WS_FLOATS ||
+        !flex_aligned(a->workspace, 8))
+        return FLEXNET_EINVAL;
+    if (a->n_agents > FLEXNET_MAX_AGENTS || a->act_dim > FLEXNET_MAX_ACT || a->rows >= ((int64_t)1 << 28))
+        return FLEXNET_EUNSUPPORTED;
+    return ppo_policy_launch(a, ppo_policy_rows_kernel, stream);
 }
 
 __global__ __launch_bounds__(PPO_THREADS) void ppo_value_kernel(FlexPpoValueArgs a) {

@@ -155,12 +155,29 @@ def gauss_log_std_torch(h, weight, bias, lo, hi):
     return lo + 0.5 * (hi - lo) * (th.tanh(F.linear(h, weight, bias)) + 1)
 
 
-def _gauss_head_args(h, weight, lo, hi):
-    a = _lib.FlexGaussHeadArgs()
-    a.rows, a.act_dim, a.hid = h.shape[0], weight.shape[0], weight.shape[1]
+def _gauss_head_fill(a, rows, weight, lo, hi):
+    """The fields FlexGaussHeadArgs and FlexGaussHeadUnsharedArgs share (``weight``: the head's, or any agent's)."""
+    a.rows, a.act_dim, a.hid = rows, weight.shape[0], weight.shape[1]
     a.log_std_min, a.log_std_max = float(lo), float(hi)
+    return a
+
+
+def _gauss_head_args(h, weight, lo, hi):
+    a = _gauss_head_fill(_lib.FlexGaussHeadArgs(), h.shape[0], weight, lo, hi)
     a.w = weight.data_ptr()
     return a
+
+
+def _gauss_head_backward_launch(entry, a, d_log_std, t, want_d_h):
+    """(d_u [rows, a], d_h [rows, 64] or None) from either form's backward entry point on its filled struct ``a``."""
+    d_log_std = d_log_std.contiguous()
+    d_u = th.empty_like(t)
+    d_h = th.empty(t.shape[0], a.hid, dtype=th.float32, device=t.device) if want_d_h else None
+    a.d_log_std, a.t, a.d_u = d_log_std.data_ptr(), t.data_ptr(), d_u.data_ptr()
+    if d_h is not None:
+        a.d_h = d_h.data_ptr()
+    _lib.launch(entry, a)
+    return d_u, d_h
 
 
 def gauss_head_supported(h, weight, bias=None):
@@ -202,17 +219,8 @@ def gauss_head_forward(h, weight, bias, lo, hi, means=None, noise=None, low=0.0,
 
 def gauss_head_backward(d_log_std, t, weight, lo, hi, want_d_h=True):
     """One launch of flexnet_gauss_head_backward: (d_u [rows, a], d_h [rows, 64] or None)."""
-    d_log_std, weight = d_log_std.contiguous(), weight.detach().contiguous()
-    rows = t.shape[0]
-    d_u = th.empty_like(t)
-    d_h = th.empty(rows, weight.shape[1], dtype=th.float32, device=t.device) if want_d_h else None
-    a = _gauss_head_args(t, weight, lo, hi)
-    a.hid = weight.shape[1]
-    a.d_log_std, a.t, a.d_u = d_log_std.data_ptr(), t.data_ptr(), d_u.data_ptr()
-    if d_h is not None:
-        a.d_h = d_h.data_ptr()
-    _lib.launch("flexnet_gauss_head_backward", a)
-    return d_u, d_h
+    weight = weight.detach().contiguous()
+    return _gauss_head_backward_launch("flexnet_gauss_head_backward", _gauss_head_args(t, weight, lo, hi), d_log_std, t, want_d_h)
 
 
 class _GaussHeadFn(th.autograd.Function):
@@ -1850,9 +1858,8 @@ def gauss_head_unshared_supported(agents, h):
 def _gauss_head_unshared_args(rows, n, ws, lo, hi):
     if not mlp_actor_allowed():
         raise RuntimeError("flexnet_gauss_head_unshared_* are launched eagerly only (nets.mlp_actor_allowed): never under a capture")
-    a = _lib.FlexGaussHeadUnsharedArgs()
-    a.rows, a.n_agents, a.act_dim, a.hid = rows, n, ws[0].shape[0], ws[0].shape[1]
-    a.log_std_min, a.log_std_max = float(lo), float(hi)
+    a = _gauss_head_fill(_lib.FlexGaussHeadUnsharedArgs(), rows, ws[0], lo, hi)
+    a.n_agents = n
     for i in range(n):
         a.w[i] = ws[i].data_ptr()
     return a
@@ -1889,14 +1896,9 @@ class _GaussHeadUnsharedFn(th.autograd.Function):
         h, t = ctx.saved_tensors[:2]
         ws = ctx.saved_tensors[2:]
         n, rows, na, dev = ctx.n_agents, t.shape[0], t.shape[1], t.device
-        d_log_std = d_log_std.contiguous()
-        d_u = th.empty_like(t)
-        d_h = th.empty(rows, 64, dtype=th.float32, device=dev) if ctx.needs_input_grad[0] else None
-        a = _gauss_head_unshared_args(rows, n, ws, ctx.lo, ctx.hi)
-        a.d_log_std, a.t, a.d_u = d_log_std.data_ptr(), t.data_ptr(), d_u.data_ptr()
-        if d_h is not None:
-            a.d_h = d_h.data_ptr()
-        _lib.launch("flexnet_gauss_head_unshared_backward", a)
+        d_u, d_h = _gauss_head_backward_launch("flexnet_gauss_head_unshared_backward",
+                                               _gauss_head_unshared_args(rows, n, ws, ctx.lo, ctx.hi), d_log_std, t,
+                                               ctx.needs_input_grad[0])
         dw = th.empty(n, na, 64, dtype=th.float32, device=dev)
         db = th.empty(n, na, dtype=th.float32, device=dev)
         b = rows // n
@@ -2845,10 +2847,29 @@ def sqddpg_shapley_fused(critic, obs2d, act, pos, ns, want_q=False, frozen=False
 # Three pieces, each as a fused launch sequence of csrc/ppo.hip on the GPU and as the tensor composition of the same
 # formulas everywhere else (CPU, fp64, more than 8 agents, a masked action_avail, cross-rank BatchNorm statistics): the
 # composition is also what the GPU tests compare the kernels with.
-def _ppo_workspace(device):
-    """The statistics and loss partials of one call, read by that call's own finish launch: one workspace per (device,
-    stream), so calls on different streams never share one (calls on one stream run in order)."""
-    return _scratch(("ppo", th.cuda.current_stream(device).cuda_stream), device, _lib.FLEXNET_PPO_WS_FLOATS // 2, th.float64)
+def _loss_workspace(family, device, floats):
+    """The fp64 statistics and loss partials of one call of ``family`` ("ppo", "coma"), read by that call's own finish launch: one
+    workspace per (family, device, stream), so calls on different streams never share one (calls on one stream run in order)."""
+    return _scratch((family, th.cuda.current_stream(device).cuda_stream), device, floats // 2, th.float64)
+
+
+class _FusedLossFn(th.autograd.Function):
+    """A loss whose gradients came out of the forward launch: ``apply(loss, x_1, dx_1, x_2, dx_2, ...)`` is ``loss`` with
+    d loss / d x_k = dx_k (csrc/ppo.hip's losses, csrc/coma.hip's policy loss)."""
+
+    @staticmethod
+    def forward(ctx, loss, *pairs):
+        ctx.save_for_backward(*pairs[1::2])
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        from .util import is_unit_seed
+        unit = is_unit_seed(g)                          # the trainer's root gradient: the stored ones are the answer
+        out = [None]
+        for k, dx in enumerate(ctx.saved_tensors):
+            out += [(dx if unit else dx * g) if ctx.needs_input_grad[1 + 2 * k] else None, None]
+        return tuple(out)
 
 
 def ppo_gae_torch(reward_norm, old_values, old_next_values, done, last_step, gamma, lambda_, chain_stride=1):
@@ -2910,7 +2931,7 @@ def ppo_gae(reward, old_values, old_next_values, done, last_step, gamma, lambda_
             r, v, nv, d, ls = (x.contiguous() for x in (reward, old_values, old_next_values, done, last_step))
             rn, adv = th.empty_like(r), th.empty_like(r)
             advn = th.empty_like(r) if adv_bn is not None else adv
-            ws = _ppo_workspace(r.device)
+            ws = _loss_workspace("ppo", r.device, _lib.FLEXNET_PPO_WS_FLOATS)
             a = _lib.FlexPpoGaeArgs()
             a.rows, a.chain_stride, a.n_agents, a.gamma, a.lambda_ = rows, stride, n, float(gamma), float(lambda_)
             a.reward, a.old_values, a.old_next_values, a.done, a.last_step = (x.data_ptr() for x in (r, v, nv, d, ls))
@@ -2958,65 +2979,43 @@ def ppo_value_loss_torch(values, old_values, next_values, reward_norm, done, gam
     return value_loss_coef * th.max(surr1, surr2).mean(), returns
 
 
-class _PpoRowsLossFn(th.autograd.Function):
-    """The policy loss of flexnet_ppo_policy_loss_rows: its gradients w.r.t. the means and the log-stds came out of the
-    forward launch."""
-
-    @staticmethod
-    def forward(ctx, means, log_stds, loss, d_means, d_log_stds):
-        ctx.save_for_backward(d_means, d_log_stds)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        d_means, d_log_stds = ctx.saved_tensors
-        from .util import is_unit_seed
-        unit = is_unit_seed(g)
-        dl = None
-        if ctx.needs_input_grad[1]:
-            dl = d_log_stds if unit else d_log_stds * g
-        return (d_means if unit else d_means * g), dl, None, None, None
-
-
-def _ppo_policy_loss_rows(means, log_stds, actions, old_log_prob, advantages, eps_clip):
-    """(loss, ratios) through flexnet_ppo_policy_loss_rows, or None where the library declines."""
+def _ppo_policy_loss_fused(means, log_stds, actions, old_log_prob, advantages, eps_clip, every=True, per_row=None):
+    """(loss, ratios) through csrc/ppo.hip's policy loss, or None where the configuration is not the kernel's or the library
+    declines: flexnet_ppo_policy_loss for a fixed-std policy's log_stds (marked ``_flex_entropy``; the kernel takes the
+    agent-summed log-std of one row), flexnet_ppo_policy_loss_rows for learned ones [rows, n, a], whose gradient comes out too.
+    ``per_row`` given: that form whatever the configuration, so that the library itself answers."""
     rows, n, na = means.shape
+    if per_row is None:
+        per_row = getattr(log_stds, "_flex_entropy", None) is None
+        if not (every and n <= 8 and na <= 8 and na > 1 and means.is_cuda and actions.shape == means.shape
+                and ppo_fused_supported((), means, actions, advantages, old_log_prob, log_stds if per_row else None)
+                and (not per_row or log_stds.shape == means.shape)):
+            return None
     with th.no_grad():
         m, act, adv = means.detach().contiguous(), actions.contiguous(), advantages.reshape(rows, n).contiguous()
-        ls = log_stds.detach().expand_as(m).contiguous()
+        if per_row:
+            ls = log_stds.detach().expand_as(m).contiguous()
+        else:
+            ls = log_stds.detach()[:1].sum(dim=1).reshape(na).contiguous()        # the agent-summed log-std of one row
         old = old_log_prob.sum(dim=-1).expand(rows, n).contiguous() if old_log_prob is not None else None
         loss = th.empty((), dtype=th.float32, device=m.device)
         d_means, ratio = th.empty_like(m), th.empty(rows, n, dtype=th.float32, device=m.device)
-        want_dl = log_stds.requires_grad
-        d_log_stds = th.empty_like(m) if want_dl else m.new_empty(0)
-        ws = _ppo_workspace(m.device)
-        a = _lib.FlexPpoPolicyRowsArgs()
+        grads = (means, d_means)
+        ws = _loss_workspace("ppo", m.device, _lib.FLEXNET_PPO_WS_FLOATS)
+        a = _lib.FlexPpoPolicyRowsArgs() if per_row else _lib.FlexPpoPolicyArgs()
         a.rows, a.n_agents, a.act_dim, a.eps_clip = rows, n, na, float(eps_clip)
-        a.means, a.log_stds, a.actions, a.advantages = m.data_ptr(), ls.data_ptr(), act.data_ptr(), adv.data_ptr()
+        a.means, a.actions, a.advantages = m.data_ptr(), act.data_ptr(), adv.data_ptr()
+        setattr(a, "log_stds" if per_row else "log_std", ls.data_ptr())
         if old is not None:
             a.old_log_prob = old.data_ptr()
         a.loss, a.d_means, a.ratio = loss.data_ptr(), d_means.data_ptr(), ratio.data_ptr()
-        if want_dl:
-            a.d_log_stds = d_log_stds.data_ptr()
+        if per_row and log_stds.requires_grad:
+            grads += (log_stds, th.empty_like(m))
+            a.d_log_stds = grads[-1].data_ptr()
         a.workspace, a.workspace_floats = ws.data_ptr(), 2 * ws.numel()
-        if not _lib.try_launch("flexnet_ppo_policy_loss_rows", a):
+        if not _lib.try_launch("flexnet_ppo_policy_loss_rows" if per_row else "flexnet_ppo_policy_loss", a):
             return None
-    return _PpoRowsLossFn.apply(means, log_stds, loss, d_means, d_log_stds), ratio
-
-
-class _PpoLossFn(th.autograd.Function):
-    """A loss of csrc/ppo.hip whose gradient w.r.t. its one differentiable input came out of the forward launch."""
-
-    @staticmethod
-    def forward(ctx, x, loss, dx):
-        ctx.save_for_backward(dx)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        (dx,) = ctx.saved_tensors
-        from .util import is_unit_seed
-        return (dx if is_unit_seed(g) else dx * g), None, None
+    return _FusedLossFn.apply(loss, *grads), ratio
 
 
 def ppo_policy_loss(means, log_stds, actions, old_log_prob, advantages, eps_clip, actions_avail=None, fused=True):
@@ -3024,34 +3023,12 @@ def ppo_policy_loss(means, log_stds, actions, old_log_prob, advantages, eps_clip
     None for the reference's own choice, the action (model.py:313)."""
     rows, n, na = means.shape
     every = actions_avail is None or getattr(actions_avail, "_flex_const", None) == 1.0
-    if (fused and every and n <= 8 and na <= 8 and na > 1 and means.is_cuda and actions.shape == means.shape
-            and ppo_fused_supported((), means, actions, advantages, old_log_prob)
-            and getattr(log_stds, "_flex_entropy", None) is not None):
-        with th.no_grad():
-            m, act, adv = means.detach().contiguous(), actions.contiguous(), advantages.reshape(rows, n).contiguous()
-            ls = log_stds.detach()[:1].sum(dim=1).reshape(na).contiguous()        # the agent-summed log-std of one row
-            old = old_log_prob.sum(dim=-1).expand(rows, n).contiguous() if old_log_prob is not None else None
-            loss = th.empty((), dtype=th.float32, device=m.device)
-            d_means, ratio = th.empty_like(m), th.empty(rows, n, dtype=th.float32, device=m.device)
-            ws = _ppo_workspace(m.device)
-            a = _lib.FlexPpoPolicyArgs()
-            a.rows, a.n_agents, a.act_dim, a.eps_clip = rows, n, na, float(eps_clip)
-            a.means, a.log_std, a.actions, a.advantages = m.data_ptr(), ls.data_ptr(), act.data_ptr(), adv.data_ptr()
-            if old is not None:
-                a.old_log_prob = old.data_ptr()
-            a.loss, a.d_means, a.ratio = loss.data_ptr(), d_means.data_ptr(), ratio.data_ptr()
-            a.workspace, a.workspace_floats = ws.data_ptr(), 2 * ws.numel()
-            ran = _lib.try_launch("flexnet_ppo_policy_loss", a)
-        if ran:
-            return _PpoLossFn.apply(means, loss, d_means), ratio
-    if (fused and every and n <= 8 and na <= 8 and na > 1 and means.is_cuda and actions.shape == means.shape
-            and ppo_fused_supported((), means, actions, advantages, old_log_prob, log_stds)
-            and getattr(log_stds, "_flex_entropy", None) is None and log_stds.shape == means.shape):
-        out = _ppo_policy_loss_rows(means, log_stds, actions, old_log_prob, advantages, eps_clip)      # learned log-stds
+    if fused:
+        out = _ppo_policy_loss_fused(means, log_stds, actions, old_log_prob, advantages, eps_clip, every)
         if out is not None:
             return out
-    if fused and means.is_cuda:
-        note_fallback("ppo_policy_loss", f"agents {n}, act_dim {na}, dtype {means.dtype}, every action available: {every}")
+        if means.is_cuda:
+            note_fallback("ppo_policy_loss", f"agents {n}, act_dim {na}, dtype {means.dtype}, every action available: {every}")
     loss, ratios = ppo_policy_loss_torch(means, log_stds, actions, actions if old_log_prob is None else old_log_prob,
                                          advantages, eps_clip, actions_avail)
     return loss, ratios.detach()
@@ -3066,7 +3043,7 @@ def ppo_value_loss(values, old_values, next_values, reward_norm, done, gamma, ep
             v, ov, nv, rn, d = (x.detach().contiguous() for x in (values2, old_values, next_values, reward_norm, done.reshape(rows)))
             loss = th.empty((), dtype=th.float32, device=v.device)
             d_values, returns = th.empty_like(v), th.empty_like(v)
-            ws = _ppo_workspace(v.device)
+            ws = _loss_workspace("ppo", v.device, _lib.FLEXNET_PPO_WS_FLOATS)
             a = _lib.FlexPpoValueArgs()
             a.rows, a.n_agents, a.gamma, a.eps_clip, a.value_loss_coef = rows, n, float(gamma), float(eps_clip), float(value_loss_coef)
             a.values, a.old_values, a.next_values, a.reward_norm, a.done = (x.data_ptr() for x in (v, ov, nv, rn, d))
@@ -3074,7 +3051,7 @@ def ppo_value_loss(values, old_values, next_values, reward_norm, done, gamma, ep
             a.workspace, a.workspace_floats = ws.data_ptr(), 2 * ws.numel()
             ran = _lib.try_launch("flexnet_ppo_value_loss", a)
         if ran:
-            return _PpoLossFn.apply(values, loss, d_values.view(values.shape)), returns
+            return _FusedLossFn.apply(loss, values, d_values.view(values.shape)), returns
     if fused and values.is_cuda:
         note_fallback("ppo_value_loss", f"agents {n}, dtype {values.dtype}")
     loss, returns = ppo_value_loss_torch(values2, old_values, next_values, reward_norm, done, gamma, eps_clip, value_loss_coef)
@@ -3191,25 +3168,6 @@ def coma_policy_loss_torch(means, log_stds, actions, actions_avail, advantages):
     return (-advantages.detach() * log_prob_a).mean(), log_prob_a
 
 
-class _ComaLossFn(th.autograd.Function):
-    """The policy loss of csrc/coma.hip: its gradients w.r.t. the means and the log-stds came out of the forward launch."""
-
-    @staticmethod
-    def forward(ctx, means, log_stds, loss, d_means, d_log_stds):
-        ctx.save_for_backward(d_means, d_log_stds)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        d_means, d_log_stds = ctx.saved_tensors
-        from .util import is_unit_seed
-        unit = is_unit_seed(g)
-        dl = None
-        if ctx.needs_input_grad[1]:
-            dl = d_log_stds if unit else d_log_stds * g
-        return (d_means if unit else d_means * g), dl, None, None, None
-
-
 def coma_policy_loss(means, log_stds, actions, actions_avail, values=None, baseline=None, advantages=None, fused=True):
     """(loss, log_prob_a [b, n] detached) of coma.py:180-188: -mean(adv log p) with adv = ``advantages`` when given (the
     normalised ones), else ``values`` - ``baseline``; nothing but the means and the log-stds takes a gradient."""
@@ -3228,8 +3186,7 @@ def coma_policy_loss(means, log_stds, actions, actions_avail, values=None, basel
             want_dl = log_stds.requires_grad and not uniform
             d_log_stds = th.empty_like(m) if want_dl else m.new_empty(0)
             logp = th.empty(rows, n, dtype=th.float32, device=m.device)
-            ws = _scratch(("coma", th.cuda.current_stream(m.device).cuda_stream), m.device, _lib.FLEXNET_COMA_WS_FLOATS // 2,
-                          th.float64)
+            ws = _loss_workspace("coma", m.device, _lib.FLEXNET_COMA_WS_FLOATS)
             k = _lib.FlexComaPolicyArgs()
             k.rows, k.n_agents, k.act_dim, k.log_std_uniform = rows, n, na, int(uniform)
             k.means, k.log_stds, k.actions = m.data_ptr(), ls.data_ptr(), act.data_ptr()
@@ -3249,7 +3206,7 @@ def coma_policy_loss(means, log_stds, actions, actions_avail, values=None, basel
             k.workspace, k.workspace_floats = ws.data_ptr(), 2 * ws.numel()
             ran = _lib.try_launch("flexnet_coma_policy_loss", k)
         if ran:
-            return _ComaLossFn.apply(means, log_stds, loss, d_means, d_log_stds), logp
+            return _FusedLossFn.apply(loss, means, d_means, log_stds, d_log_stds), logp
     if fused and means.is_cuda:
         note_fallback("coma_policy_loss", f"agents {n}, act_dim {na}, dtype {means.dtype}")
     adv = advantages if advantages is not None else values - baseline

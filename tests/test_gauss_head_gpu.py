@@ -174,7 +174,7 @@ def test_ppo_policy_loss_rows_with_large_ratios():
 
 def test_limits_are_refused():
     from safe_marl_amd import _lib
-    from safe_marl_amd.nets import _ppo_policy_loss_rows, gauss_head_forward, gauss_log_std, gauss_log_std_torch
+    from safe_marl_amd.nets import _ppo_policy_loss_fused, gauss_head_forward, gauss_log_std, gauss_log_std_torch
     from safe_marl_amd.util import FALLBACKS
     _lib.load()
     h32, w32 = th.randn(8, 32, device="cuda"), th.randn(4, 32, device="cuda")
@@ -193,5 +193,5 @@ def test_limits_are_refused():
     s.n_agents, s.act_dim = 5, 9
     assert not _lib.try_launch("flexnet_gauss_sum_explore", s)
     means, log_stds, actions, _, adv = _ppo_inputs(4, 9, 4, 3, False)
-    assert _ppo_policy_loss_rows(means, log_stds.requires_grad_(), actions, None, adv, 0.2) is None
+    assert _ppo_policy_loss_fused(means, log_stds.requires_grad_(), actions, None, adv, 0.2, per_row=True) is None
     th.cuda.synchronize()

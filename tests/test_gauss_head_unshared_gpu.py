@@ -102,6 +102,35 @@ def test_entry_points_against_the_composition(b, n, act_dim, want_t, want_dh):
     assert all(th.equal(first[k], outs[k][0]) for k in outs)
 
 
+# a single row; a ragged last 32-sample tile; more than one work-group per agent; the agent maximum
+@pytest.mark.parametrize("b,n,act_dim", [(1, 1, 1), (33, 3, 4), (129, 5, 8), (31, 8, 4)])
+def test_copies_of_one_head_agree_with_the_shared_kernel_both_ways(b, n, act_dim):
+    """The per-agent entry points on n copies of ONE head are the shared entry points on the same rows, bit for bit: the two
+    forms are instantiations of one body (csrc/gauss.hip) and differ in the row map alone."""
+    from safe_marl_amd import _lib
+    g = th.Generator(device="cuda").manual_seed(1000 * b + 10 * n + act_dim)
+    rows = b * n
+    h = th.randn(rows, 64, device="cuda", generator=g)
+    w = 0.3 * th.randn(act_dim, 64, device="cuda", generator=g)
+    bias = 0.3 * th.randn(act_dim, device="cuda", generator=g)
+    d_ls = th.randn(rows, act_dim, device="cuda", generator=g)
+    shared = _lib.FlexGaussHeadArgs()
+    shared.rows, shared.act_dim, shared.hid, shared.log_std_min, shared.log_std_max = rows, act_dim, 64, LO, HI
+    shared.w, shared.b = w.data_ptr(), bias.data_ptr()
+    out = {}
+    for form, a in (("shared", shared), ("unshared", _head_args(h, [w] * n, [bias] * n, n, act_dim))):
+        o = out[form] = {k: th.full((rows, width), SENTINEL, device="cuda")
+                         for k, width in (("log_std", act_dim), ("t", act_dim), ("d_u", act_dim), ("d_h", 64))}
+        a.h, a.log_std, a.t = h.data_ptr(), o["log_std"].data_ptr(), o["t"].data_ptr()
+        _lib.launch(f"flexnet_gauss_head{'_unshared' if form == 'unshared' else ''}_forward", a)
+        a.d_log_std, a.d_u, a.d_h = d_ls.data_ptr(), o["d_u"].data_ptr(), o["d_h"].data_ptr()
+        _lib.launch(f"flexnet_gauss_head{'_unshared' if form == 'unshared' else ''}_backward", a)
+    th.cuda.synchronize()
+    for k, got in out["unshared"].items():
+        assert not bool((got == SENTINEL).any()), k
+        assert th.equal(got, out["shared"][k]), k
+
+
 def _rnn_agents(n, obs_dim, act_dim, seed):
     """n RNNAgentGaussian modules with distinct seeded weights, scaled up."""
     from safe_marl_amd.nets import RNNAgentGaussian

@@ -244,7 +244,7 @@ def test_new_kernels_use_no_scratch(lib):
     names = {}
     for prefix in ("gauss_", "ppo_policy_rows_kernel"):
         names.update({v["name"]: v for v in build.kernel_resources(prefix).values()})
-    assert {"gauss_head_forward_kernel", "gauss_head_backward_kernel", "gauss_sum_explore_kernel", "gauss_loss_finish_kernel",
+    assert {"gauss_head_forward_kernel", "gauss_head_backward_kernel", "gauss_sum_explore_kernel",
             "ppo_policy_rows_kernel"} <= set(names)
     for k, v in names.items():
         assert v["scratch_bytes_per_lane"] == 0 and v["vgpr_spills"] == 0 and v["sgpr_spills"] == 0, (k, v)

@@ -461,8 +461,8 @@ def test_kernels_use_no_scratch():
     build.build()
     res = build.kernel_resources("ppo_")
     names = {v["name"] for v in res.values()}
-    assert {"ppo_gae_lane_kernel", "ppo_gae_wave_kernel", "ppo_gae_finish_kernel", "ppo_policy_kernel", "ppo_value_kernel",
-            "ppo_loss_finish_kernel"} <= names
+    assert {"ppo_gae_lane_kernel", "ppo_gae_wave_kernel", "ppo_gae_finish_kernel", "ppo_policy_kernel", "ppo_policy_rows_kernel",
+            "ppo_value_kernel", "ppo_loss_finish_kernel"} <= names
     assert all(v["scratch_bytes_per_lane"] == 0 for v in res.values())
 
 
