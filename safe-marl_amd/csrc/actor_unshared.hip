@@ -2,11 +2,9 @@
 // whole batch in ONE launch, forward and backward (gfx950).  Boundary: include/flexnet.h (FlexActorUnsharedArgs /
 // FlexActorUnsharedBwdArgs).  Reference arithmetic: madrl/agents/rnn_agent.py:25-33 per agent.
 //
-// Work map: one wavefront owns 32 samples of ONE agent — rows r = s * n_agents + a of the caller's [b * n, .] tensors — so the
-// whole tile multiplies with that agent's weights: flex_mfma_tile.h's transposed fp32 scheme (v_mfma_f32_32x32x2_f32, A =
-// weights, B = the wavefront's rows; lane (row i, half h) holds 32 of its row's 64 units as two accumulator tiles).  A work-group
-// is four wavefronts of the same agent (their weight reads share the CU's cache); the weights are read where the modules keep
-// them, through per-agent pointer tables in the argument struct.
+// Work map and the stages shared with critic_unshared.hip and actor_mlp.hip: flex_agent_tile.h (one wavefront owns 32 samples
+// of ONE agent, a work-group is four wavefronts of the same agent: their weight reads share the CU's cache).  The weights are
+// read where the modules keep them, through per-agent pointer tables in the argument struct.
 //
 // Forward: fc1 over the observation columns, + bias + the agent's OWN id column, LayerNorm, ReLU, GRUCell (r, z, n), fc2; with
 // the six training saves of FlexActorArgs.  Backward: gru.hip's fused arithmetic (gate gradients, dx = d_gi @ W_ih on the
@@ -18,25 +16,14 @@
 #include <stdint.h>
 #include "flexnet.h"
 #include "flex_launch.h"
-#include "flex_mfma_tile.h"
-#include "flex_reduce.h"
+#include "flex_agent_tile.h"
 
-#define AU_W 4                                   // wavefronts per work-group (one per SIMD)
-#define AU_MAX_BLOCKS 128                        // backward work-groups per agent (FLEXNET_ACTOR_UNSHARED_WS_FLOATS)
-#define AU_PITCH (3 * SH)                        // a work-group's partial row: d_ln_w | d_ln_b | d_fc1_b
-#define AU_FOLD 33                               // pitch of a lane's 32 sums in the fold buffer
-#define AU_WP 72                                 // pitch of a W_ih row in LDS: the two lane halves (four rows apart) hit disjoint banks
+#define AU_VECS 3                                // d_ln_w | d_ln_b | d_fc1_b
+#define AU_PITCH (AU_VECS * SH)                  // a work-group's partial row
 
-static_assert(FLEXNET_ACTOR_UNSHARED_WS_FLOATS >= FLEXNET_MAX_AGENTS * AU_MAX_BLOCKS * AU_PITCH, "workspace macro");
+static_assert(FLEXNET_ACTOR_UNSHARED_WS_FLOATS >= FLEXNET_MAX_AGENTS * AT_MAX_BLOCKS * AU_PITCH, "workspace macro");
 
 __device__ __forceinline__ float au_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-__device__ __forceinline__ tv16 au_zero_tile() {
-    tv16 t;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) t[r] = 0.0f;
-    return t;
-}
 
 // the sum of two bias vectors over the lane's units
 __device__ __forceinline__ tv16 au_bias2_tile(const float* b0, const float* b1, int h) {
@@ -47,13 +34,13 @@ __device__ __forceinline__ tv16 au_bias2_tile(const float* b0, const float* b1, 
 }
 
 // (one kernel with or without the saves: the inference launch and the training forward give the same bits)
-__global__ __launch_bounds__(64 * AU_W) void actor_unshared_forward_kernel(FlexActorUnsharedArgs a) {
+__global__ __launch_bounds__(64 * AT_W) void actor_unshared_forward_kernel(FlexActorUnsharedArgs a) {
     const bool SAVE = a.save_z1 != nullptr;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, h = lane >> 5;
     const int n = a.n_agents, ad = a.act_dim, od = a.obs_dim;
     const int ag = blockIdx.x % n;
     const int64_t batch = a.rows / n;
-    const int64_t s0 = ((int64_t)(blockIdx.x / n) * AU_W + wave) * 32;
+    const int64_t s0 = ((int64_t)(blockIdx.x / n) * AT_W + wave) * 32;
     if (s0 >= batch) return;                                   // (the kernel has no barrier)
     const bool ok = s0 + i < batch;
     const int64_t s = ok ? s0 + i : batch - 1;                 // the last partial tile re-reads a valid sample
@@ -66,8 +53,10 @@ __global__ __launch_bounds__(64 * AU_W) void actor_unshared_forward_kernel(FlexA
     const float* bih = a.b_ih[ag];
     const float* bhh = a.b_hh[ag];
 
-    // fc1 over the observation columns: MFMA step j of a group of eight columns takes the pair (c0 + j, c0 + 4 + j)
-    tv16 x[2] = {au_zero_tile(), au_zero_tile()};
+    // fc1 over the observation columns -> z1 (saved BEFORE the bias: the backward adds it again), + bias + the agent's own id
+    // column, LayerNorm, ReLU -> x (saved).  The block product is at_fc1_block's text, kept in the kernel: through the function
+    // this launch measured 1.5 % slower at 163 840 rows (profiles/agent_tile_shared_bench.txt).
+    tv16 x[2] = {zero_tile(), zero_tile()};
     {
         const float* op = a.obs + row * od;
         const float* w0 = W1 + (int64_t)i * ld1;
@@ -93,36 +82,8 @@ __global__ __launch_bounds__(64 * AU_W) void actor_unshared_forward_kernel(FlexA
         store_tile(a.save_z1 + row * SH + 4 * h, x[0], ok);
         store_tile(a.save_z1 + row * SH + 32 + 4 * h, x[1], ok);
     }
-    // + bias + the agent's own id column, LayerNorm, ReLU
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int u = 32 * t + TILE_U(r, h);
-            float add = b1[u];
-            if (a.agent_id) add += W1[(int64_t)u * ld1 + od + ag];
-            x[t][r] += add;
-        }
-    }
-    if (a.layernorm) {
-        float mean, rstd;
-        row_stats(x[0], x[1], a.ln_eps, mean, rstd);
-        const float* lw = a.ln_w[ag];
-        const float* lb = a.ln_b[ag];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int u = 32 * t + TILE_U(r, h);
-                x[t][r] = ((x[t][r] - mean) * rstd) * lw[u] + lb[u];
-            }
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) x[t][r] = fmaxf(x[t][r], 0.0f);
-    }
+    at_add_bias_id(x, b1, a.agent_id ? W1 + od + ag : nullptr, ld1, h);
+    at_layernorm_relu(x, a.layernorm, a.ln_w[ag], a.ln_b[ag], a.ln_eps, h);
     if (SAVE) {
         store_tile(a.save_x + row * SH + 4 * h, x[0], ok);
         store_tile(a.save_x + row * SH + 32 + 4 * h, x[1], ok);
@@ -160,21 +121,10 @@ __global__ __launch_bounds__(64 * AU_W) void actor_unshared_forward_kernel(FlexA
         store_tile(a.hidden_out + row * SH + ub + 4 * h, hn[t], ok);
     }
 
-    // fc2: the A operand's rows past act_dim are zero; output k = 4 h + r sits in accumulator register r < 4
-    tv16 m = au_zero_tile();
-    {
-        const bool live = i < ad;
-        const float* w2 = a.fc2_w[ag] + (int64_t)(live ? i : 0) * SH + 4 * h;
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const tv4 w = ld4(w2 + 32 * kt + 8 * q);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) m = TILE_MFMA(live ? w[j] : 0.0f, hn[kt][4 * q + j], m);
-            }
-        }
-    }
+    // fc2
+    const bool live = i < ad;
+    tv16 m = zero_tile();
+    at_head(m, a.fc2_w[ag] + (int64_t)(live ? i : 0) * SH + 4 * h, live, hn);
     const float* b2 = a.fc2_b[ag];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -192,56 +142,40 @@ __device__ __forceinline__ void au_backward_body(const FlexActorUnsharedBwdArgs&
     __shared__ __attribute__((aligned(16))) float s_w2[FLEXNET_MAX_ACT * SH];
     // W_ih of the agent, read by the dx chains from ONE base register (with the weights in global memory the compiler kept a
     // 64-bit address per chain step live across the tile loop and spilled); after the loop the same memory is the fold buffer
-    __shared__ float s_wih[3 * SH * AU_WP];
-    static_assert(AU_W * 64 * AU_FOLD <= 3 * SH * AU_WP, "the fold buffer lives in the W_ih tile");
-    float (*fold)[64][AU_FOLD] = reinterpret_cast<float (*)[64][AU_FOLD]>(s_wih);
+    __shared__ float s_wih[3 * SH * AT_WP];
+    static_assert(AT_W * 64 * AT_FOLD <= 3 * SH * AT_WP, "the fold buffer lives in the W_ih tile");
+    float (*fold)[64][AT_FOLD] = reinterpret_cast<float (*)[64][AT_FOLD]>(s_wih);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 31, h = lane >> 5;
     const int n = a.n_agents, ad = a.act_dim, od = a.obs_dim;
     const int ag = blockIdx.x % n, kb = blockIdx.x / n;
     const int64_t batch = a.rows / n;
     const int64_t tiles = (batch + 31) / 32;
     const int ld1 = od + (a.agent_id ? n : 0);
-    {
-        const float* W2 = a.fc2_w[ag];
-        const float* Wih = a.w_ih[ag];
-        for (int idx = tid; idx < 3 * SH * SH; idx += 64 * AU_W) s_wih[(idx >> 6) * AU_WP + (idx & 63)] = Wih[idx];
-        for (int idx = tid; idx < FLEXNET_MAX_ACT * SH; idx += 64 * AU_W) s_w2[idx] = idx < ad * SH ? W2[idx] : 0.0f;
-    }
+    at_stage_weight(s_wih, a.w_ih[ag], 3 * SH, tid);
+    at_stage_head(s_w2, a.fc2_w[ag], ad, tid);
     if (tid < SH) {
-        float add = a.fc1_b[ag][tid];
-        if (a.agent_id) add += a.fc1_w[ag][(int64_t)tid * ld1 + od + ag];
-        s_add[tid] = add;
+        s_add[tid] = at_unit_add(a.fc1_b[ag], a.agent_id ? a.fc1_w[ag] + od + ag : nullptr, ld1, tid);
         s_lnw[tid] = a.layernorm ? a.ln_w[ag][tid] : 1.0f;
     }
     __syncthreads();
 
-    tv16 acc_g[2] = {au_zero_tile(), au_zero_tile()}, acc_b[2] = {au_zero_tile(), au_zero_tile()},
-         acc_d[2] = {au_zero_tile(), au_zero_tile()};
+    tv16 acc_g[2] = {zero_tile(), zero_tile()}, acc_b[2] = {zero_tile(), zero_tile()},
+         acc_d[2] = {zero_tile(), zero_tile()};
 #pragma unroll 1
-    for (int64_t tile = (int64_t)kb * AU_W + wave; tile < tiles; tile += (int64_t)blocks_per_agent * AU_W) {
-        // (a compiler fence: without it the loop-invariant LDS reads of W_ih — 192 values per lane — are hoisted out of the
-        // tile loop into registers the kernel does not have, and spill)
-        __asm__ volatile("" ::: "memory");
-        const int64_t s0 = tile * 32;
-        const bool ok = s0 + i < batch;
-        const int64_t s = ok ? s0 + i : batch - 1;
-        const int64_t row = s * n + ag;
+    for (int64_t tile = (int64_t)kb * AT_W + wave; tile < tiles; tile += (int64_t)blocks_per_agent * AT_W) {
+        bool ok;
+        const int64_t row = at_loop_sample(tile, i, batch, ok) * n + ag;
 
         // dh' = d_means @ fc2_w: four steps per 32 units (the outputs past act_dim are zero rows)
-        tv16 dh[2] = {au_zero_tile(), au_zero_tile()};
+        tv16 dh[2] = {zero_tile(), zero_tile()};
         if (WITH_HN && ok) {                                      // (+ d_hn: the accumulators start from it)
             dh[0] = load_tile(d_hn + row * SH + 4 * h);
             dh[1] = load_tile(d_hn + row * SH + 32 + 4 * h);
         }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int k = 4 * h + j;
-            const bool in = k < ad;
-            const float dv = a.d_means[row * ad + (in ? k : ad - 1)];
-            const float dm = (in && ok) ? dv : 0.0f;
-            dh[0] = TILE_MFMA(s_w2[k * SH + i], dm, dh[0]);
-            dh[1] = TILE_MFMA(s_w2[k * SH + 32 + i], dm, dh[1]);
-        }
+        float dm[4];
+        at_head_grad(dm, a.d_means + row * ad, ad, h, ok);
+        dh[0] = at_head_transposed(s_w2 + i, h, dh[0], dm);
+        dh[1] = at_head_transposed(s_w2 + 32 + i, h, dh[1], dm);
         // gate gradients (a dead row's dh' is zero: so is everything below)
         tv16 dgi[3][2];
 #pragma unroll
@@ -265,116 +199,40 @@ __device__ __forceinline__ void au_backward_body(const FlexActorUnsharedBwdArgs&
             store_tile(gh, dgi[0][t], ok); store_tile(gh + SH, dgi[1][t], ok); store_tile(gh + 2 * SH, dnr, ok);
         }
         // dx = d_gi @ W_ih: never stored
-        tv16 dx[2] = {au_zero_tile(), au_zero_tile()};
+        tv16 dx[2] = {zero_tile(), zero_tile()};
 #pragma unroll
         for (int G = 0; G < 3; ++G) {
 #pragma unroll
             for (int to = 0; to < 2; ++to) {
-                const float* wc = s_wih + (SH * G + 32 * to) * AU_WP + i;
-                dx[0] = transposed_tile(wc, AU_WP, h, dx[0], dgi[G][to]);
-                dx[1] = transposed_tile(wc + 32, AU_WP, h, dx[1], dgi[G][to]);
+                const float* wc = s_wih + (SH * G + 32 * to) * AT_WP + i;
+                dx[0] = transposed_tile(wc, AT_WP, h, dx[0], dgi[G][to]);
+                dx[1] = transposed_tile(wc + 32, AT_WP, h, dx[1], dgi[G][to]);
             }
         }
-        // LayerNorm / ReLU / bias backward (csrc/lnrelu.hip's arithmetic); ReLU's mask from the forward's own output
-        tv16 xh[2];
-        float rstd = 1.0f;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            xh[t] = load_tile(a.z1 + row * SH + 32 * t + 4 * h);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const tv4 ad4 = ld4(s_add + 32 * t + 8 * q + 4 * h);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) xh[t][4 * q + j] += ad4[j];
-            }
-        }
-        if (a.layernorm) {
-            float mean;
-            row_stats(xh[0], xh[1], a.ln_eps, mean, rstd);
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) xh[t][e] = (xh[t][e] - mean) * rstd;
-            }
-        }
+        // LayerNorm / ReLU / bias backward; ReLU's mask from the forward's own output
         tv16 dzv[2];
-        float s1 = 0.0f, s2 = 0.0f;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const tv16 XS = load_tile(a.x + row * SH + 32 * t + 4 * h);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const tv4 gw = ld4(s_lnw + 32 * t + 8 * q + 4 * h);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int e = 4 * q + j;
-                    const float dy = (XS[e] > 0.0f && ok) ? dx[t][e] : 0.0f;
-                    acc_g[t][e] = fmaf(dy, xh[t][e], acc_g[t][e]);
-                    acc_b[t][e] += dy;
-                    const float dxh = dy * gw[j];
-                    dzv[t][e] = dxh;
-                    s1 += dxh;
-                    s2 = fmaf(dxh, xh[t][e], s2);
-                }
-            }
-        }
-        if (a.layernorm) {
-            const float m1 = (s1 + other_half(s1)) * (1.0f / SH), m2 = (s2 + other_half(s2)) * (1.0f / SH);
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) dzv[t][e] = rstd * (dzv[t][e] - m1 - xh[t][e] * m2);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            store_tile(a.dz + row * SH + 32 * t + 4 * h, dzv[t], ok);
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc_d[t][e] += ok ? dzv[t][e] : 0.0f;
-        }
+        at_ln_relu_backward<true, true>(a.z1 + row * SH, s_add, nullptr, a.x + row * SH, dx, s_lnw, a.layernorm, a.ln_eps,
+                                        a.dz + row * SH, h, ok, acc_g, acc_b, acc_d, dzv);
     }
 
-    // work-group fold, fixed order: wavefronts in index order, rows in index order.  Register r of tile t in lane (i, h) is
-    // unit 32 t + TILE_U(r, h) of one row.
-    float* out = a.workspace + ((int64_t)ag * blocks_per_agent + kb) * AU_PITCH;
     __syncthreads();                                           // every wavefront is done with the W_ih tile
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        const tv16* src = q == 0 ? acc_g : q == 1 ? acc_b : acc_d;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) fold[wave][lane][16 * t + r] = src[t][r];
-        }
-        __syncthreads();
-        if (tid < SH) {
-            const int t = tid >> 5, w = tid & 31, uh = (w >> 2) & 1, r = 4 * (w >> 3) + (w & 3);
-            float sum = 0.0f;
-            for (int wv = 0; wv < AU_W; ++wv)
-                for (int ii = 0; ii < 32; ++ii) sum += fold[wv][32 * uh + ii][16 * t + r];
-            out[q * SH + tid] = sum;
-        }
-        __syncthreads();
-    }
+    at_fold(fold, a.workspace + ((int64_t)ag * blocks_per_agent + kb) * AU_PITCH, tid, acc_g, acc_b, acc_d);
 }
 
-__global__ __launch_bounds__(64 * AU_W) void actor_unshared_backward_kernel(FlexActorUnsharedBwdArgs a, int blocks_per_agent) {
+__global__ __launch_bounds__(64 * AT_W) void actor_unshared_backward_kernel(FlexActorUnsharedBwdArgs a, int blocks_per_agent) {
     au_backward_body<false>(a, nullptr, blocks_per_agent);
 }
 
-__global__ __launch_bounds__(64 * AU_W) void actor_hn_unshared_backward_kernel(FlexActorUnsharedBwdArgs a, const float* d_hn,
+__global__ __launch_bounds__(64 * AT_W) void actor_hn_unshared_backward_kernel(FlexActorUnsharedBwdArgs a, const float* d_hn,
                                                                              int blocks_per_agent) {
     au_backward_body<true>(a, d_hn, blocks_per_agent);
 }
 
-// element e of every work-group's partial row of one agent, summed in a fixed order: block = 3 * agent + vector
+// the second launch: block = AU_VECS * agent + vector
 __global__ __launch_bounds__(64 * FLEX_RED_G) void actor_unshared_reduce_kernel(FlexActorUnsharedBwdArgs a, int blocks_per_agent) {
-    const int ex = threadIdx.x & 63;
-    const int ag = blockIdx.x / 3, vec = blockIdx.x % 3;
+    int ag, vec, ex;
     float sum;
-    if (!flex_reduce_rows(a.workspace + (int64_t)ag * blocks_per_agent * AU_PITCH + vec * SH + ex, AU_PITCH, blocks_per_agent,
-                          true, sum))
-        return;
+    if (!at_reduce_agent(a.workspace, AU_VECS, blocks_per_agent, ag, vec, ex, sum)) return;
     if (vec == 0) { if (a.layernorm) a.d_ln_w[ag * SH + ex] = sum; }
     else if (vec == 1) { if (a.layernorm) a.d_ln_b[ag * SH + ex] = sum; }
     else a.d_fc1_b[ag * SH + ex] = sum;
@@ -406,9 +264,8 @@ extern "C" int flexnet_actor_unshared_forward(const FlexActorUnsharedArgs* a, vo
                          flex_aligned(a->save_z, 16) && flex_aligned(a->save_n, 16) && flex_aligned(a->save_hn, 16);
     if (!aligned) return FLEXNET_EUNSUPPORTED;
     if (a->rows == 0) return FLEXNET_OK;
-    const int64_t batch = a->rows / a->n_agents;
-    const int64_t groups = ((batch + 31) / 32 + AU_W - 1) / AU_W;
-    const dim3 grid((unsigned)(groups * a->n_agents)), block(64 * AU_W);
+    const int64_t groups = at_groups(a->rows / a->n_agents);
+    const dim3 grid((unsigned)(groups * a->n_agents)), block(64 * AT_W);
     hipLaunchKernelGGL(actor_unshared_forward_kernel, grid, block, 0, (hipStream_t)stream, *a);
     return flex_launch_status();
 }
@@ -429,17 +286,15 @@ static int au_backward(const FlexActorUnsharedBwdArgs* a, const float* d_hn, voi
     }
     if (!aligned || !flex_aligned(d_hn, 16)) return FLEXNET_EUNSUPPORTED;
     if (a->rows == 0) return FLEXNET_OK;
-    const int64_t batch = a->rows / a->n_agents;
-    int64_t bpa = ((batch + 31) / 32 + AU_W - 1) / AU_W;
-    if (bpa > AU_MAX_BLOCKS) bpa = AU_MAX_BLOCKS;
+    const int64_t bpa = at_blocks_per_agent(a->rows / a->n_agents);
     if (bpa * a->n_agents * AU_PITCH > a->workspace_floats) return FLEXNET_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     if (d_hn)
-        hipLaunchKernelGGL(actor_hn_unshared_backward_kernel, dim3((unsigned)(bpa * a->n_agents)), dim3(64 * AU_W), 0, s, *a, d_hn,
+        hipLaunchKernelGGL(actor_hn_unshared_backward_kernel, dim3((unsigned)(bpa * a->n_agents)), dim3(64 * AT_W), 0, s, *a, d_hn,
                            (int)bpa);
     else
-        hipLaunchKernelGGL(actor_unshared_backward_kernel, dim3((unsigned)(bpa * a->n_agents)), dim3(64 * AU_W), 0, s, *a, (int)bpa);
-    hipLaunchKernelGGL(actor_unshared_reduce_kernel, dim3(3 * a->n_agents), dim3(64 * FLEX_RED_G), 0, s, *a, (int)bpa);
+        hipLaunchKernelGGL(actor_unshared_backward_kernel, dim3((unsigned)(bpa * a->n_agents)), dim3(64 * AT_W), 0, s, *a, (int)bpa);
+    hipLaunchKernelGGL(actor_unshared_reduce_kernel, dim3(AU_VECS * a->n_agents), dim3(64 * FLEX_RED_G), 0, s, *a, (int)bpa);
     return flex_launch_status();
 }
 

@@ -35,13 +35,6 @@
 __device__ __forceinline__ float attn_critic_lrelu(float x) { return x > 0.0f ? x : x * AC_SLOPE; }
 __device__ __forceinline__ float attn_critic_slope(float y) { return y > 0.0f ? 1.0f : AC_SLOPE; }      // from the OUTPUT's sign
 
-__device__ __forceinline__ tv16 attn_critic_zero() {
-    tv16 t;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) t[r] = 0.0f;
-    return t;
-}
-
 // The FORWARD's dot products are no single fp32 chain.  The softmax carries a logit's rounding into the attention weights
 // (times 8 at unit-scale logits, times 64 and more between near-tied saturated ones), and the logit is the end of three chained
 // layers (encoder, extractor, sel . key), each of which would add a K-term chain's rounding.  So every group of four MFMA steps
@@ -80,7 +73,7 @@ __device__ __forceinline__ void attn_critic_block(dv16* x, const float* xp, cons
             const float ov = xp[cc], av = w0[cc], bv = w1[cc];
             o[j] = in ? ov : 0.0f; wa[j] = in ? av : 0.0f; wb[j] = in ? bv : 0.0f;
         }
-        tv16 p0 = attn_critic_zero(), p1 = attn_critic_zero();
+        tv16 p0 = zero_tile(), p1 = zero_tile();
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             p0 = TILE_MFMA(wa[j], o[j], p0);
@@ -99,7 +92,7 @@ __device__ __forceinline__ void attn_critic_tile(dv16& acc, const float* wrow, c
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const tv4 w = ld4(wrow + 32 * kt + 8 * q);
-            tv16 p = attn_critic_zero();
+            tv16 p = zero_tile();
 #pragma unroll
             for (int j = 0; j < 4; ++j) p = TILE_MFMA(w[j], kt ? in1[4 * q + j] : in0[4 * q + j], p);
             attn_critic_fold(acc, p);
@@ -285,7 +278,7 @@ __global__ __launch_bounds__(64 * AC_W) void attn_critic_forward_kernel(FlexAttn
             }
         }
         const float inv = 1.0f / den;
-        tv16 oth[2] = {attn_critic_zero(), attn_critic_zero()};
+        tv16 oth[2] = {zero_tile(), zero_tile()};
 #pragma unroll
         for (int j = 0; j < FLEXNET_MAX_AGENTS; ++j) {
             if (j < n && j != ai) {
@@ -380,7 +373,7 @@ __global__ __launch_bounds__(64 * AC_W) void attn_critic_backward_kernel(FlexAtt
             for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off, 64);
             if (lane == 0) reinterpret_cast<double*>(a.workspace)[tile * n + ai] = total;
         }
-        tv16 dsa[2] = {attn_critic_zero(), attn_critic_zero()}, dot[2] = {attn_critic_zero(), attn_critic_zero()};
+        tv16 dsa[2] = {zero_tile(), zero_tile()}, dot[2] = {zero_tile(), zero_tile()};
         attn_critic_layer_t(dsa, a.c1_w[ai], 2 * SH, 0, dzc, i, h);
         attn_critic_layer_t(dot, a.c1_w[ai], 2 * SH, SH, dzc, i, h);
         attn_critic_store(a.g_direct + row * SH, dsa, h, ok);
@@ -399,7 +392,7 @@ __global__ __launch_bounds__(64 * AC_W) void attn_critic_backward_kernel(FlexAtt
         }
         if (PG) {
             // the selector, the bias head and the state encoder
-            tv16 dsel[2] = {attn_critic_zero(), attn_critic_zero()};
+            tv16 dsel[2] = {zero_tile(), zero_tile()};
 #pragma unroll 1
             for (int j = 0; j < n; ++j) {
                 if (j == ai) continue;
@@ -427,7 +420,7 @@ __global__ __launch_bounds__(64 * AC_W) void attn_critic_backward_kernel(FlexAtt
                 }
             }
             attn_critic_store(a.dz_b + row * SH, dzb, h, ok);
-            tv16 ds[2] = {attn_critic_zero(), attn_critic_zero()};
+            tv16 ds[2] = {zero_tile(), zero_tile()};
             attn_critic_layer_t(ds, a.sel_w, SH, 0, dsel, i, h);
             attn_critic_layer_t(ds, a.b1_w[ai], SH, 0, dzb, i, h);
             tv16 sx[2];
@@ -453,7 +446,7 @@ __global__ __launch_bounds__(64 * AC_W) void attn_critic_backward_kernel(FlexAtt
     for (int j = 0; j < n; ++j) {
         __asm__ volatile("" ::: "memory");
         const int64_t row = s * n + j;
-        tv16 dval[2] = {attn_critic_zero(), attn_critic_zero()}, dkey[2] = {attn_critic_zero(), attn_critic_zero()};
+        tv16 dval[2] = {zero_tile(), zero_tile()}, dkey[2] = {zero_tile(), zero_tile()};
 #pragma unroll 1
         for (int ai = 0; ai < n; ++ai) {
             if (ai == j) continue;
@@ -501,7 +494,7 @@ __global__ __launch_bounds__(64 * AC_W) void attn_critic_backward_kernel(FlexAtt
         } else {
             // d_act_j = dz_sa_j @ the action columns of enc_j: the A operand's rows past act_dim are zero; output c = 4 h + r
             // sits in accumulator register r < 4
-            tv16 m = attn_critic_zero();
+            tv16 m = zero_tile();
             const bool live = i < ad;
             const float* wo = a.enc_w[j] + o + (live ? i : 0);
 #pragma unroll

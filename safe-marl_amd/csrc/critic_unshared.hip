@@ -3,9 +3,8 @@
 // FlexCriticUnsharedBwdArgs).  Reference arithmetic: madrl/critics/mlp_critic.py:28-35 per agent on the input rows of
 // maddpg.py:33-54, mappo.py:34-62, ippo.py:34-59 and iddpg.py:32-59.
 //
-// Work map (actor_unshared.hip's): one wavefront owns 32 samples of ONE agent — rows r = s * n_agents + a of the [b * n, .]
-// tensors — on flex_mfma_tile.h's transposed fp32 scheme; a work-group is four wavefronts of the same agent; the weights are
-// read where the modules keep them, through per-agent pointer tables.
+// Work map and the stages shared with actor_unshared.hip and actor_mlp.hip: flex_agent_tile.h.  The weights are read where the
+// modules keep them, through per-agent pointer tables.
 //
 // The first layer's input is never materialised: agent a's row of sample s is [x1 block | onehot(a) | x2 block], each block
 // `base + s * pitch + a * agent_off` (agent_off 0: the block is shared by the sample's agents).  The id block is not read —
@@ -14,7 +13,7 @@
 // Forward: fc1 over the blocks + bias + id column -> z1 (saved), LayerNorm, ReLU -> x (saved), fc2, ReLU, fc3 -> q [b, n].
 // Backward, from dq and the two saves: z2 = fc2(x) is RECOMPUTED (64 matrix-core steps per tile against a [rows, 64] tensor
 // written and read back), dz2 and dz1 come out for the weight gradients (flexnet_wgrad_batched), dx = dz2 @ fc2_w on the
-// matrix cores from an LDS copy of fc2_w, LayerNorm / ReLU backward as csrc/lnrelu.hip, and the optional own-block input
+// matrix cores from an LDS copy of fc2_w, LayerNorm / ReLU backward (at_ln_relu_backward), and the optional own-block input
 // gradient d_x2_own = dz1 @ fc1_w[a][:, own columns].  The per-agent [64] sums (d_ln_w, d_ln_b, d_fc1_b, d_fc2_b, d_fc3_w) and
 // d_fc3_b are per-lane sums folded per work-group in a fixed order and summed over work-groups by a second launch: no
 // atomics, bit-reproducible.
@@ -22,56 +21,23 @@
 #include <stdint.h>
 #include "flexnet.h"
 #include "flex_launch.h"
-#include "flex_mfma_tile.h"
-#include "flex_reduce.h"
+#include "flex_agent_tile.h"
 
-#define CU_W 4                                   // wavefronts per work-group (one per SIMD)
-#define CU_MAX_BLOCKS 128                        // backward work-groups per agent (FLEXNET_CRITIC_UNSHARED_WS_FLOATS)
 #define CU_VECS 6                                // d_ln_w | d_ln_b | d_fc1_b | d_fc2_b | d_fc3_w | d_fc3_b (element 0)
 #define CU_PITCH (CU_VECS * SH)                  // a work-group's partial row
-#define CU_FOLD 33                               // pitch of a lane's 32 sums in the fold buffer
-#define CU_WP 72                                 // pitch of an fc2_w row in LDS: the two lane halves hit disjoint banks
 #define CU_MAX_W1 (FLEXNET_MAX_AGENTS * FLEXNET_MAX_OBS)
 #define CU_MAX_W2 (FLEXNET_MAX_AGENTS * FLEXNET_MAX_ACT)
 
-static_assert(FLEXNET_CRITIC_UNSHARED_WS_FLOATS >= FLEXNET_MAX_AGENTS * CU_MAX_BLOCKS * CU_PITCH, "workspace macro");
-
-__device__ __forceinline__ tv16 cu_zero_tile() {
-    tv16 t;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) t[r] = 0.0f;
-    return t;
-}
-
-// x += W[:, c0 .. c0 + width) @ xp[0 .. width) for the lane's row: MFMA step j of a group of eight columns takes the pair
-// (c + j, c + 4 + j); `w0` / `w1` = the lane's two weight rows at the block's first column.  (Clamped: no load past a row.)
-__device__ __forceinline__ void cu_fc1_block(tv16* x, const float* xp, const float* w0, const float* w1, int width, int h) {
-    for (int c0 = 0; c0 < width; c0 += 8) {
-        float o[4], wa[4], wb[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int c = c0 + 4 * h + j;
-            const bool in = c < width;
-            const int cc = in ? c : width - 1;
-            const float ov = xp[cc], av = w0[cc], bv = w1[cc];
-            o[j] = in ? ov : 0.0f; wa[j] = in ? av : 0.0f; wb[j] = in ? bv : 0.0f;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            x[0] = TILE_MFMA(wa[j], o[j], x[0]);
-            x[1] = TILE_MFMA(wb[j], o[j], x[1]);
-        }
-    }
-}
+static_assert(FLEXNET_CRITIC_UNSHARED_WS_FLOATS >= FLEXNET_MAX_AGENTS * AT_MAX_BLOCKS * CU_PITCH, "workspace macro");
 
 // (one kernel with or without the saves: the no-grad launch and the training forward give the same bits)
-__global__ __launch_bounds__(64 * CU_W) void critic_unshared_forward_kernel(FlexCriticUnsharedArgs a) {
+__global__ __launch_bounds__(64 * AT_W) void critic_unshared_forward_kernel(FlexCriticUnsharedArgs a) {
     const bool SAVE = a.save_z1 != nullptr;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, h = lane >> 5;
     const int n = a.n_agents;
     const int ag = blockIdx.x % n;
     const int64_t batch = a.rows / n;
-    const int64_t s0 = ((int64_t)(blockIdx.x / n) * CU_W + wave) * 32;
+    const int64_t s0 = ((int64_t)(blockIdx.x / n) * AT_W + wave) * 32;
     if (s0 >= batch) return;                                   // (the kernel has no barrier)
     const bool ok = s0 + i < batch;
     const int64_t s = ok ? s0 + i : batch - 1;                 // the last partial tile re-reads a valid sample
@@ -81,46 +47,19 @@ __global__ __launch_bounds__(64 * CU_W) void critic_unshared_forward_kernel(Flex
     const float* W1 = a.fc1_w[ag];
     const float* b1 = a.fc1_b[ag];
 
-    tv16 x[2] = {cu_zero_tile(), cu_zero_tile()};
-    cu_fc1_block(x, a.x1 + s * a.x1_pitch + (int64_t)ag * a.x1_agent_off, W1 + (int64_t)i * ld1, W1 + (int64_t)(32 + i) * ld1,
+    tv16 x[2] = {zero_tile(), zero_tile()};
+    at_fc1_block(x, a.x1 + s * a.x1_pitch + (int64_t)ag * a.x1_agent_off, W1 + (int64_t)i * ld1, W1 + (int64_t)(32 + i) * ld1,
                  a.w1, h);
     if (a.w2 > 0)
-        cu_fc1_block(x, a.x2 + s * a.x2_pitch + (int64_t)ag * a.x2_agent_off, W1 + (int64_t)i * ld1 + a.w1 + n_id,
+        at_fc1_block(x, a.x2 + s * a.x2_pitch + (int64_t)ag * a.x2_agent_off, W1 + (int64_t)i * ld1 + a.w1 + n_id,
                      W1 + (int64_t)(32 + i) * ld1 + a.w1 + n_id, a.w2, h);
-    // + bias + the agent's own id column
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int u = 32 * t + TILE_U(r, h);
-            float add = b1[u];
-            if (a.agent_id) add += W1[(int64_t)u * ld1 + a.w1 + ag];
-            x[t][r] += add;
-        }
-    }
+    // + bias + the agent's own id column -> z1 (saved), LayerNorm, ReLU -> x (saved)
+    at_add_bias_id(x, b1, a.agent_id ? W1 + a.w1 + ag : nullptr, ld1, h);
     if (SAVE) {
         store_tile(a.save_z1 + row * SH + 4 * h, x[0], ok);
         store_tile(a.save_z1 + row * SH + 32 + 4 * h, x[1], ok);
     }
-    if (a.layernorm) {
-        float mean, rstd;
-        row_stats(x[0], x[1], a.ln_eps, mean, rstd);
-        const float* lw = a.ln_w[ag];
-        const float* lb = a.ln_b[ag];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int u = 32 * t + TILE_U(r, h);
-                x[t][r] = ((x[t][r] - mean) * rstd) * lw[u] + lb[u];
-            }
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) x[t][r] = fmaxf(x[t][r], 0.0f);
-    }
+    at_layernorm_relu(x, a.layernorm, a.ln_w[ag], a.ln_b[ag], a.ln_eps, h);
     if (SAVE) {
         store_tile(a.save_x + row * SH + 4 * h, x[0], ok);
         store_tile(a.save_x + row * SH + 32 + 4 * h, x[1], ok);
@@ -144,13 +83,13 @@ __global__ __launch_bounds__(64 * CU_W) void critic_unshared_forward_kernel(Flex
 // ---- backward ---------------------------------------------------------------------------------------------------------
 // PG: with the parameter sums and dz2 (the value loss); without, only dz1 and d_x2_own come out (`critic_frozen`)
 template <bool PG>
-__global__ __launch_bounds__(64 * CU_W) void critic_unshared_backward_kernel(FlexCriticUnsharedBwdArgs a, int blocks_per_agent) {
+__global__ __launch_bounds__(64 * AT_W) void critic_unshared_backward_kernel(FlexCriticUnsharedBwdArgs a, int blocks_per_agent) {
     __shared__ __attribute__((aligned(16))) float s_lnw[SH], s_b2[SH], s_w3[SH];
     __shared__ __attribute__((aligned(16))) float s_own[SH * FLEXNET_MAX_ACT];
     // fc2_w of the agent (rows for z2, columns for dx); after the tile loop the same memory is the fold buffer
-    __shared__ __attribute__((aligned(16))) float s_buf[CU_W * 64 * CU_FOLD];
-    static_assert(SH * CU_WP <= CU_W * 64 * CU_FOLD, "the fc2_w tile lives in the fold buffer");
-    float (*fold)[64][CU_FOLD] = reinterpret_cast<float (*)[64][CU_FOLD]>(s_buf);
+    __shared__ __attribute__((aligned(16))) float s_buf[AT_W * 64 * AT_FOLD];
+    static_assert(SH * AT_WP <= AT_W * 64 * AT_FOLD, "the fc2_w tile lives in the fold buffer");
+    float (*fold)[64][AT_FOLD] = reinterpret_cast<float (*)[64][AT_FOLD]>(s_buf);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = lane & 31, h = lane >> 5;
     const int n = a.n_agents;
     const int ag = blockIdx.x % n, kb = blockIdx.x / n;
@@ -160,11 +99,10 @@ __global__ __launch_bounds__(64 * CU_W) void critic_unshared_backward_kernel(Fle
     const int ld1 = a.w1 + n_id + a.w2;
     const int ow = a.d_x2_own ? a.own_w : 0;
     {
-        const float* W2 = a.fc2_w[ag];
-        for (int idx = tid; idx < SH * SH; idx += 64 * CU_W) s_buf[(idx >> 6) * CU_WP + (idx & 63)] = W2[idx];
+        at_stage_weight(s_buf, a.fc2_w[ag], SH, tid);
         // the own-block columns of fc1_w: s_own[u * 8 + c] (zero past own_w)
         const float* W1 = a.fc1_w[ag] + a.w1 + n_id + a.own_first + (int64_t)ag * a.own_step;
-        for (int idx = tid; idx < SH * FLEXNET_MAX_ACT; idx += 64 * CU_W) {
+        for (int idx = tid; idx < SH * FLEXNET_MAX_ACT; idx += 64 * AT_W) {
             const int u = idx >> 3, c = idx & 7;
             s_own[idx] = c < ow ? W1[(int64_t)u * ld1 + c] : 0.0f;
         }
@@ -181,19 +119,14 @@ __global__ __launch_bounds__(64 * CU_W) void critic_unshared_backward_kernel(Fle
     if (PG) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            acc_g[t] = cu_zero_tile(); acc_b[t] = cu_zero_tile(); acc_d[t] = cu_zero_tile();
-            acc_b2[t] = cu_zero_tile(); acc_w3[t] = cu_zero_tile();
+            acc_g[t] = zero_tile(); acc_b[t] = zero_tile(); acc_d[t] = zero_tile();
+            acc_b2[t] = zero_tile(); acc_w3[t] = zero_tile();
         }
     }
 #pragma unroll 1
-    for (int64_t tile = (int64_t)kb * CU_W + wave; tile < tiles; tile += (int64_t)blocks_per_agent * CU_W) {
-        // (a compiler fence, as in actor_unshared.hip: without it the loop-invariant LDS reads of fc2_w are hoisted out of the
-        // tile loop into registers the kernel does not have, and spill)
-        __asm__ volatile("" ::: "memory");
-        const int64_t s0 = tile * 32;
-        const bool ok = s0 + i < batch;
-        const int64_t s = ok ? s0 + i : batch - 1;
-        const int64_t row = s * n + ag;
+    for (int64_t tile = (int64_t)kb * AT_W + wave; tile < tiles; tile += (int64_t)blocks_per_agent * AT_W) {
+        bool ok;
+        const int64_t row = at_loop_sample(tile, i, batch, ok) * n + ag;
         const float dqv = ok ? a.dq[row] : 0.0f;               // a dead row's dq is zero: so is everything below
 
         // z2 = fc2(x) again, dz2 = dq w3 [z2 > 0]
@@ -202,7 +135,7 @@ __global__ __launch_bounds__(64 * CU_W) void critic_unshared_backward_kernel(Fle
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             tv16 z2 = bias_tile(s_b2 + 32 * t, h);
-            z2 = layer_tile(s_buf + (32 * t + i) * CU_WP + 4 * h, z2, XS[0], XS[1]);
+            z2 = layer_tile(s_buf + (32 * t + i) * AT_WP + 4 * h, z2, XS[0], XS[1]);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const tv4 w3 = ld4(s_w3 + 32 * t + 8 * q + 4 * h);
@@ -222,67 +155,21 @@ __global__ __launch_bounds__(64 * CU_W) void critic_unshared_backward_kernel(Fle
         }
         if (PG) acc_b3 += dqv;
         // dx = dz2 @ fc2_w: never stored
-        tv16 dx[2] = {cu_zero_tile(), cu_zero_tile()};
+        tv16 dx[2] = {zero_tile(), zero_tile()};
 #pragma unroll
         for (int to = 0; to < 2; ++to) {
-            const float* wc = s_buf + (32 * to) * CU_WP + i;
-            dx[0] = transposed_tile(wc, CU_WP, h, dx[0], dz2[to]);
-            dx[1] = transposed_tile(wc + 32, CU_WP, h, dx[1], dz2[to]);
+            const float* wc = s_buf + (32 * to) * AT_WP + i;
+            dx[0] = transposed_tile(wc, AT_WP, h, dx[0], dz2[to]);
+            dx[1] = transposed_tile(wc + 32, AT_WP, h, dx[1], dz2[to]);
         }
-        // LayerNorm / ReLU backward (csrc/lnrelu.hip's arithmetic); ReLU's mask from the forward's own output
-        tv16 xh[2] = {load_tile(a.z1 + row * SH + 4 * h), load_tile(a.z1 + row * SH + 32 + 4 * h)};
-        float rstd = 1.0f;
-        if (a.layernorm) {
-            float mean;
-            row_stats(xh[0], xh[1], a.ln_eps, mean, rstd);
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) xh[t][e] = (xh[t][e] - mean) * rstd;
-            }
-        }
+        // LayerNorm / ReLU backward; ReLU's mask from the forward's own output
         tv16 dzv[2];
-        float s1 = 0.0f, s2 = 0.0f;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const tv4 gw = ld4(s_lnw + 32 * t + 8 * q + 4 * h);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int e = 4 * q + j;
-                    const float dy = XS[t][e] > 0.0f ? dx[t][e] : 0.0f;
-                    if (PG) {
-                        acc_g[t][e] = fmaf(dy, xh[t][e], acc_g[t][e]);
-                        acc_b[t][e] += dy;
-                    }
-                    const float dxh = dy * gw[j];
-                    dzv[t][e] = dxh;
-                    s1 += dxh;
-                    s2 = fmaf(dxh, xh[t][e], s2);
-                }
-            }
-        }
-        if (a.layernorm) {
-            const float m1 = (s1 + other_half(s1)) * (1.0f / SH), m2 = (s2 + other_half(s2)) * (1.0f / SH);
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) dzv[t][e] = rstd * (dzv[t][e] - m1 - xh[t][e] * m2);
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            store_tile(a.dz1 + row * SH + 32 * t + 4 * h, dzv[t], ok);
-            if (PG) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) acc_d[t][e] += dzv[t][e];
-            }
-        }
+        at_ln_relu_backward<PG, false>(a.z1 + row * SH, nullptr, XS, nullptr, dx, s_lnw, a.layernorm, a.ln_eps, a.dz1 + row * SH,
+                                       h, ok, acc_g, acc_b, acc_d, dzv);
         // d_x2_own = dz1 @ the own-block columns: the A operand's rows past own_w are zero; output c = 4 h + r sits in
         // accumulator register r < 4
         if (ow > 0) {
-            tv16 m = cu_zero_tile();
+            tv16 m = zero_tile();
             const bool live = i < FLEXNET_MAX_ACT;
             const float* wo = s_own + (live ? i : 0);
 #pragma unroll
@@ -305,49 +192,27 @@ __global__ __launch_bounds__(64 * CU_W) void critic_unshared_backward_kernel(Fle
     }
     if (!PG) return;
 
-    // work-group fold, fixed order: wavefronts in index order, rows in index order.  Register r of tile t in lane (i, h) is
-    // unit 32 t + TILE_U(r, h) of one row.
     float* out = a.workspace + ((int64_t)ag * blocks_per_agent + kb) * CU_PITCH;
     __syncthreads();                                           // every wavefront is done with the fc2_w tile
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-        const tv16* src = q == 0 ? acc_g : q == 1 ? acc_b : q == 2 ? acc_d : q == 3 ? acc_b2 : acc_w3;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) fold[wave][lane][16 * t + r] = src[t][r];
-        }
-        __syncthreads();
-        if (tid < SH) {
-            const int t = tid >> 5, w = tid & 31, uh = (w >> 2) & 1, r = 4 * (w >> 3) + (w & 3);
-            float sum = 0.0f;
-            for (int wv = 0; wv < CU_W; ++wv)
-                for (int ii = 0; ii < 32; ++ii) sum += fold[wv][32 * uh + ii][16 * t + r];
-            out[q * SH + tid] = sum;
-        }
-        __syncthreads();
-    }
+    at_fold(fold, out, tid, acc_g, acc_b, acc_d, acc_b2, acc_w3);
     // d_fc3_b: both halves of a row hold its dq; half 0 counts
     fold[wave][lane][0] = acc_b3;
     __syncthreads();
     if (tid < SH) {
         float sum = 0.0f;
         if (tid == 0) {
-            for (int wv = 0; wv < CU_W; ++wv)
+            for (int wv = 0; wv < AT_W; ++wv)
                 for (int ii = 0; ii < 32; ++ii) sum += fold[wv][ii][0];
         }
         out[5 * SH + tid] = sum;
     }
 }
 
-// element e of every work-group's partial row of one agent, summed in a fixed order: block = CU_VECS * agent + vector
+// the second launch: block = CU_VECS * agent + vector
 __global__ __launch_bounds__(64 * FLEX_RED_G) void critic_unshared_reduce_kernel(FlexCriticUnsharedBwdArgs a, int blocks_per_agent) {
-    const int ex = threadIdx.x & 63;
-    const int ag = blockIdx.x / CU_VECS, vec = blockIdx.x % CU_VECS;
+    int ag, vec, ex;
     float sum;
-    if (!flex_reduce_rows(a.workspace + (int64_t)ag * blocks_per_agent * CU_PITCH + vec * SH + ex, CU_PITCH, blocks_per_agent,
-                          true, sum))
-        return;
+    if (!at_reduce_agent(a.workspace, CU_VECS, blocks_per_agent, ag, vec, ex, sum)) return;
     if (vec == 0) { if (a.layernorm) a.d_ln_w[ag * SH + ex] = sum; }
     else if (vec == 1) { if (a.layernorm) a.d_ln_b[ag * SH + ex] = sum; }
     else if (vec == 2) a.d_fc1_b[ag * SH + ex] = sum;
@@ -380,9 +245,8 @@ extern "C" int flexnet_critic_unshared_forward(const FlexCriticUnsharedArgs* a, 
     if (a->save_z1) aligned = aligned && flex_aligned(a->save_z1, 16) && flex_aligned(a->save_x, 16);
     if (!aligned) return FLEXNET_EUNSUPPORTED;
     if (a->rows == 0) return FLEXNET_OK;
-    const int64_t batch = a->rows / a->n_agents;
-    const int64_t groups = ((batch + 31) / 32 + CU_W - 1) / CU_W;
-    hipLaunchKernelGGL(critic_unshared_forward_kernel, dim3((unsigned)(groups * a->n_agents)), dim3(64 * CU_W), 0,
+    const int64_t groups = at_groups(a->rows / a->n_agents);
+    hipLaunchKernelGGL(critic_unshared_forward_kernel, dim3((unsigned)(groups * a->n_agents)), dim3(64 * AT_W), 0,
                        (hipStream_t)stream, *a);
     return flex_launch_status();
 }
@@ -408,12 +272,10 @@ extern "C" int flexnet_critic_unshared_backward(const FlexCriticUnsharedBwdArgs*
     }
     if (!aligned) return FLEXNET_EUNSUPPORTED;
     if (a->rows == 0) return FLEXNET_OK;
-    const int64_t batch = a->rows / a->n_agents;
-    int64_t bpa = ((batch + 31) / 32 + CU_W - 1) / CU_W;
-    if (bpa > CU_MAX_BLOCKS) bpa = CU_MAX_BLOCKS;
+    const int64_t bpa = at_blocks_per_agent(a->rows / a->n_agents);
     if (pg && bpa * a->n_agents * CU_PITCH > a->workspace_floats) return FLEXNET_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)(bpa * a->n_agents)), block(64 * CU_W);
+    const dim3 grid((unsigned)(bpa * a->n_agents)), block(64 * AT_W);
     if (pg) {
         hipLaunchKernelGGL(critic_unshared_backward_kernel<true>, grid, block, 0, s, *a, (int)bpa);
         hipLaunchKernelGGL(critic_unshared_reduce_kernel, dim3(CU_VECS * a->n_agents), dim3(64 * FLEX_RED_G), 0, s, *a, (int)bpa);

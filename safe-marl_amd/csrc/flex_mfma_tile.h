@@ -1,8 +1,9 @@
-// flex_mfma_tile.h — the transposed fp32 matrix-core tile scheme of qmix.hip, sqddpg.hip and coma.hip: A = weights (rows =
-// output units), B = the wavefront's 32 rows (v_mfma_f32_32x32x2_f32, exact fp32).  Lane (row i = lane & 31, half h =
-// lane >> 5) holds 32 of its row's 64 units as two accumulator tiles; register r of tile t is unit 32 t + TILE_U(r, h) —
-// exactly what the next layer's B operand wants when MFMA step (q, j) takes the k-pair (8 q + j, 8 q + 4 + j).
-// (critic.hip / actor.hip keep their own register map: actor_r16.h.)
+// flex_mfma_tile.h — the transposed fp32 matrix-core tile scheme of qmix.hip, sqddpg.hip, coma.hip, gauss.hip, attn_critic.hip,
+// actor_unshared.hip, critic_unshared.hip and actor_mlp.hip: A = weights (rows = output units), B = the wavefront's 32 rows
+// (v_mfma_f32_32x32x2_f32, exact fp32).  Lane (row i = lane & 31, half h = lane >> 5) holds 32 of its row's 64 units as two
+// accumulator tiles; register r of tile t is unit 32 t + TILE_U(r, h) — exactly what the next layer's B operand wants when MFMA
+// step (q, j) takes the k-pair (8 q + j, 8 q + 4 + j).  The per-agent work map of the last three and the stages they share on
+// it: flex_agent_tile.h.  (critic.hip / actor.hip keep their own register map: actor_r16.h.)
 #ifndef FLEX_MFMA_TILE_H
 #define FLEX_MFMA_TILE_H
 #include <hip/hip_runtime.h>
@@ -18,6 +19,13 @@ typedef float tv4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ tv4 ld4(const float* p) { return *reinterpret_cast<const tv4*>(p); }
 __device__ __forceinline__ void st4(float* p, tv4 v) { *reinterpret_cast<tv4*>(p) = v; }
 __device__ __forceinline__ float other_half(float v) { return __shfl_xor(v, 32, 64); }
+
+__device__ __forceinline__ tv16 zero_tile() {
+    tv16 t;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) t[r] = 0.0f;
+    return t;
+}
 
 // accumulators start from the bias of their units
 __device__ __forceinline__ tv16 bias_tile(const float* b, int h) {
