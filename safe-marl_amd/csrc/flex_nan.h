@@ -1,5 +1,6 @@
 // flex_nan.h — the NaN-propagating ReLU and clamp of the kernels that stand in for torch.relu / torch.clamp: csrc/actor.hip and
-// csrc/flexenv.hip through actor_r16.h, csrc/qmix.hip.
+// csrc/flexenv.hip through actor_r16.h, csrc/qmix.hip, and the environment-action clamps of csrc/gauss.hip (gauss_env_action) and
+// csrc/rollout.hip (agent_sum_explore_kernel).
 #ifndef FLEX_NAN_H
 #define FLEX_NAN_H
 #include <hip/hip_runtime.h>

@@ -25,14 +25,15 @@
 #include "flexnet.h"
 #include "flex_launch.h"
 #include "flex_mfma_tile.h"
+#include "flex_nan.h"
 
 #define GAUSS_THREADS 256
 #define GAUSS_ROWS (GAUSS_THREADS / 2)       // 32 rows per wavefront
 #define GAUSS_MAX_ROWS ((int64_t)1 << 30)
 
-// translate_action (util.py:125-128) with the roundings of scale_action's tensor ops
+// translate_action (util.py:125-128) with the roundings of scale_action's tensor ops; a NaN action stays NaN, as through th.clamp
 __device__ __forceinline__ float gauss_env_action(float y, float lo, float hi) {
-    const float c = fminf(fmaxf(y, lo), hi);
+    const float c = clamp_nan(y, lo, hi);
     return __fadd_rn(__fmul_rn(__fmul_rn(0.5f, __fadd_rn(c, 1.0f)), hi - lo), lo);
 }
 

@@ -10,6 +10,7 @@
 #include <stdint.h>
 #include "flexnet.h"
 #include "flex_launch.h"
+#include "flex_nan.h"
 #include "flex_td.h"
 #include "window_refresh.h"
 
@@ -166,7 +167,7 @@ __global__ __launch_bounds__(256) void agent_sum_explore_kernel(FlexAgentSumArgs
     // eps == NULL: no exploration — the agent-summed mean itself goes to every agent (util.py:75-77 behind matd3.py:94-96)
     const float y = a.eps ? tanhf(__fadd_rn(s, __fmul_rn(a.eps[tid], a.std[k]))) : s;  // tanh(loc + eps * scale)
     const float span = a.act_high - a.act_low;
-    const float c = fminf(fmaxf(y, a.act_low), a.act_high);
+    const float c = clamp_nan(y, a.act_low, a.act_high);                               // th.clamp: a NaN action stays NaN
     const float ev = __fadd_rn(__fmul_rn(__fmul_rn(0.5f, __fadd_rn(c, 1.0f)), span), a.act_low);
     float* ao = a.action + (int64_t)e * n * ad + k;
     for (int i = 0; i < n; ++i) ao[i * ad] = y;

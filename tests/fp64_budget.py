@@ -11,7 +11,13 @@ The compositions below (``actor_plain``, ``mlp_actor_plain``, ``lnrelu_plain``, 
 ``critic_first_layer_plain``, ``coma_baseline_plain``, ``sqddpg_plain``, ``qmix_plain``) are the layers of nets.RNNAgent /
 nets.MLPAgent / nets.MLPCritic / nets.QMixer written with torch.nn.functional alone, in whatever dtype the module has: the modules' own forward takes the
 project's HIP weight-gradient kernels at update sizes (the mixer's: csrc/qmix.hip on any GPU tensors), which neither the yardstick nor the fp64 reference may.
-tests/test_fp64_budget_cpu.py pins them to the modules' forward (1e-12 in fp64)."""
+tests/test_fp64_budget_cpu.py pins them to the modules' forward (1e-12 in fp64).
+
+The last part holds what has no module: csrc/ppo.hip (``gae_plain``, ``policy_loss_plain``, ``value_loss_plain``), csrc/gauss.hip's
+log-std head (``gauss_head_plain``) and the stand-alone csrc/tdloss.hip (``td_run``) against the ``nets`` compositions of the same
+formulas in fp64, with their input families (``gae_families``, ``policy_families``, ``value_families``, ``gauss_families``,
+``td_families``), the elements whose side of a clip end is arbitrary (``policy_clear_kinks``, ``value_keep``) and the one floor
+derived for them (``policy_loss_rounding``)."""
 import copy
 from typing import NamedTuple
 
@@ -658,3 +664,510 @@ def apply_params(module, family):
             else:
                 p.fill_(value)
     return module
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# csrc/ppo.hip, csrc/gauss.hip and the stand-alone csrc/tdloss.hip (tests/test_ppo_fp64_gpu.py, test_gauss_fp64_gpu.py,
+# test_tdloss_fp64_gpu.py): the plain compositions with their wrong evaluations, and the input families.  Every family is drawn
+# from a CPU generator, so that tests/test_fp64_budget_cpu.py holds conditions on the very cases the GPU tests run.
+
+GAMMA, LAM = 0.99, 0.95
+POLICY_EPS = 0.2
+KINK = 1e-5
+GAE_WRONG = ("mask_everywhere", "drop_carry_64", "biased_running_var")
+GAE_FAMILIES = ("plain", "all_terminal", "open_sum", "tile_edges", "gamma0", "failure", "mixed")
+GAE_MIXED_OF = ("plain", "all_terminal", "open_sum", "tile_edges")        # the FLAGS of these, chain by chain
+FAILURE_REWARD, FAILURE_SPREAD = -200.0, 0.05
+POLICY_FAMILIES = ("plain", "on_mean", "zero_adv", "clipped_out", "ends_min", "ends_max", "wide", "mixed")
+POLICY_MIXED_OF = ("plain", "on_mean", "zero_adv", "clipped_out")         # (ends and wide are held in the rms form: not mixed in)
+POLICY_RMS = ("ends_min", "ends_max", "wide")
+VALUE_FAMILIES = ("plain", "eps0", "all_done")
+GAUSS_FAMILIES = ("plain", "reset", "saturated", "flat", "wide_noise", "mixed")
+GAUSS_MIXED_OF = ("plain", "reset", "saturated")
+GAUSS_SATURATED = 25.0     # |u| of every saturated element in fp64: tanh is 1 to the last bit of fp64 beyond 19.1
+LOG_STD_RANGES = ((0.0, 0.5), (-5.0, 2.0))
+TD_FAMILIES = ("plain", "failure")
+
+
+def bn_module(n, dtype=th.float32, device="cpu", seed=0):
+    """tests/test_ppo_gpu.py's BatchNorm1d: affine parameters and running statistics that are not the initial ones."""
+    g = th.Generator().manual_seed(seed)
+    bn = th.nn.BatchNorm1d(n)
+    with th.no_grad():
+        bn.weight.copy_(1 + 0.1 * th.randn(n, generator=g))
+        bn.bias.copy_(0.1 * th.randn(n, generator=g))
+        bn.running_mean.copy_(th.randn(n, generator=g))
+        bn.running_var.copy_(1 + th.rand(n, generator=g))
+    return bn.to(dtype).to(device)
+
+
+def fixed_log_stds(means, log_std):
+    """The fixed-std policy's log_stds as the learner hands them over (tests/test_ppo_gpu.py's ``_log_stds``): ONE number
+    expanded to the shape of ``means``, marked ``_flex_entropy``.  ``log_std``: a tensor whose first element is taken (in its
+    own precision: the fp32 number is the input of every form)."""
+    c = log_std.reshape(-1)[:1].detach().to(dtype=means.dtype, device=means.device)
+    ls = c.expand_as(means)
+    ls._flex_entropy = th.zeros((), device=means.device)
+    return ls
+
+
+def gae_chain_loop(reward_norm, old_values, old_next_values, done, last_step, gamma, lam, stride, wrong=None):
+    """ppo.py:44-52 chain by chain, literally, in the dtype of its inputs: chain e is rows e, e + stride, ... and need not be as
+    long as the others (``rows % stride != 0``: include/flexnet.h allows it, nets.ppo_gae_torch does not).  The loop runs over
+    the steps from the last one back, each chain meeting ppo_gae_torch's operations in ppo_gae_torch's order.  ``wrong``:
+    "mask_everywhere", m = 1 - done on every row instead of on last steps alone; "drop_carry_64", the advantage of the next
+    step is not handed over at every 64th step counted from the chain's end (a wavefront scan that loses its carry between
+    tiles)."""
+    rows, n = reward_norm.shape
+    per = min(int(stride), rows)
+    done, last_step = done.reshape(rows, 1), last_step.reshape(rows, 1)
+    mask = 1.0 - done if wrong == "mask_everywhere" else th.where(last_step != 0, 1.0 - done, th.ones_like(done))
+    steps_of = (rows - th.arange(per) + stride - 1) // stride                          # chain e has this many steps
+    out = th.empty_like(reward_norm)
+    nxt = th.zeros(per, n, dtype=reward_norm.dtype)
+    for t in reversed(range(int(steps_of.max()))):
+        lo, hi = t * stride, min((t + 1) * stride, rows)
+        k = hi - lo
+        carry = nxt[:k]
+        if wrong == "drop_carry_64":
+            carry = th.where(((steps_of[:k] - 1 - t) % 64 == 0).view(k, 1), th.zeros_like(carry), carry)
+        deltas = reward_norm[lo:hi] + gamma * old_next_values[lo:hi] * mask[lo:hi] - old_values[lo:hi]
+        cur = deltas + gamma * lam * carry * mask[lo:hi]
+        out[lo:hi] = cur
+        nxt = th.zeros_like(nxt)
+        nxt[:k] = cur
+    return out
+
+
+def gae_plain(reward, old_values, old_next_values, done, last_step, gamma, lam, stride, reward_bn=None, adv_bn=None, wrong=None):
+    """nets.ppo_gae(..., fused=False) — the reward through its BatchNorm, GAE along the chains, the advantages through theirs —
+    with both modules' running statistics beside the three tensors: {"reward_norm", "advantages", "advantages_norm",
+    "reward_bn.running_mean", "reward_bn.running_var", "adv_bn.running_mean", ..., "reward_bn.num_batches_tracked", ...}.  The
+    modules are moved as their training-mode forward moves them.  Ragged chains and the wrong evaluations (GAE_WRONG;
+    "biased_running_var": the running variance moved by the biased batch variance) take ``gae_chain_loop`` between the modules."""
+    from safe_marl_amd.nets import ppo_gae
+    assert wrong is None or wrong in GAE_WRONG, wrong
+    rows = reward.shape[0]
+    before = {key: bn.running_var.clone() for key, bn in (("reward_bn", reward_bn), ("adv_bn", adv_bn)) if bn is not None}
+    with th.no_grad():
+        if wrong in (None, "biased_running_var") and rows % stride == 0:
+            rn, adv, advn = ppo_gae(reward, old_values, old_next_values, done, last_step, gamma, lam, stride, reward_bn, adv_bn,
+                                    fused=False)
+        else:
+            rn = reward_bn(reward) if reward_bn is not None else reward
+            adv = gae_chain_loop(rn, old_values, old_next_values, done, last_step, gamma, lam, stride, wrong)
+            advn = adv_bn(adv) if adv_bn is not None else adv
+        out = {"reward_norm": rn, "advantages": adv, "advantages_norm": advn}
+        for key, bn, x in (("reward_bn", reward_bn, reward), ("adv_bn", adv_bn, adv)):
+            if bn is None:
+                continue
+            if wrong == "biased_running_var":
+                bn.running_var.copy_((1 - bn.momentum) * before[key] + bn.momentum * x.var(0, unbiased=False))
+            out[key + ".running_mean"], out[key + ".running_var"] = bn.running_mean.clone(), bn.running_var.clone()
+            out[key + ".num_batches_tracked"] = bn.num_batches_tracked.clone()
+    return out
+
+
+def steps_from_end(rows, stride):
+    """int64 [rows]: how many steps of its chain follow row r (0: the chain's last step), and the chain's length."""
+    r = th.arange(rows)
+    e = r % stride
+    steps_of = (rows - e + stride - 1) // stride
+    return steps_of - 1 - r // stride, steps_of
+
+
+def gae_families(rows, n, stride, generator):
+    """The named input families of GAE on ``rows`` rows of ``n`` agents in chains ``stride`` apart: inputs (reward, old_values,
+    old_next_values, done, last_step), ``params`` {"gamma", "lam"}, from ONE set of base draws (tests/test_ppo_gpu.py's scales:
+    reward 0.05 randn - 0.03, values randn, a last step on 8 % of the rows).
+
+    plain         done on half of ALL rows, drawn independently of last_step: all four (done, last) combinations occur, and
+                  done = 1 on a row that is not a last step must change nothing.
+    all_terminal  last = done = 1 on every row: A = delta.
+    open_sum      no last step (done as plain's: it must not matter), gamma = lambda = 1: suffix sums over the whole chain.
+    tile_edges    last = done = 1 exactly at the steps that fall on lanes 0 and 63 of every 64-step tile counted from the
+                  chain's end, and at the chain's first and last step; 0 elsewhere.
+    gamma0        plain's inputs with gamma = 0.
+    failure       plain's with reward column 0 exactly FAILURE_REWARD on every row (variance exactly zero) and column 1
+                  FAILURE_REWARD + FAILURE_SPREAD randn (|mean| / std = 4 000: the workload's own extreme, a column of
+                  failure rewards).
+    mixed         the flags of GAE_MIXED_OF interleaved chain by chain (``groups`` [rows]: which), plain's gamma and lambda."""
+    g = generator
+    r = 0.05 * th.randn(rows, n, generator=g) - 0.03
+    v, nv = th.randn(rows, n, generator=g), th.randn(rows, n, generator=g)
+    last = (th.rand(rows, generator=g) < 0.08).float()
+    done = (th.rand(rows, generator=g) < 0.5).float()
+    spread = th.randn(rows, generator=g)
+    after, steps_of = steps_from_end(rows, stride)
+    edge = ((after % 64 == 0) | (after % 64 == 63) | (after == steps_of - 1)).float()
+    ones, zeros = th.ones(rows), th.zeros(rows)
+    flags = {"plain": (done, last), "all_terminal": (ones, ones), "open_sum": (done, zeros), "tile_edges": (edge, edge)}
+    std = {"gamma": GAMMA, "lam": LAM}
+    out = {name: Family(name, (r, v, nv, d.clone(), l.clone()), dict(std)) for name, (d, l) in flags.items()}
+    out["open_sum"] = out["open_sum"]._replace(params={"gamma": 1.0, "lam": 1.0})
+    out["gamma0"] = Family("gamma0", (r, v, nv, done.clone(), last.clone()), {"gamma": 0.0, "lam": LAM})
+    rf = r.clone()
+    rf[:, 0] = FAILURE_REWARD
+    if n > 1:
+        rf[:, 1] = FAILURE_REWARD + FAILURE_SPREAD * spread
+    out["failure"] = Family("failure", (rf, v, nv, done.clone(), last.clone()), dict(std))
+    groups = (th.arange(rows) % stride) % len(GAE_MIXED_OF)
+    md, ml = done.clone(), last.clone()
+    for j, name in enumerate(GAE_MIXED_OF):
+        md[groups == j], ml[groups == j] = flags[name][0][groups == j], flags[name][1][groups == j]
+    out["mixed"] = Family("mixed", (r, v, nv, md, ml), dict(std), groups)
+    return out
+
+
+def _log_density64(means, log_stds, actions):
+    """log p [rows, n] in fp64 of ``actions`` [rows, n, a] under the agent-summed Gaussian of ``means`` / ``log_stds``."""
+    import math
+    mu, ls = means.double().sum(1, keepdim=True), log_stds.double().sum(1, keepdim=True)
+    return (-(actions.double() - mu).square() / (2.0 * th.exp(2.0 * ls)) - ls - 0.5 * math.log(2.0 * math.pi)).sum(-1)
+
+
+def _stored_log_prob(logp, a):
+    """A stored log-density [rows, n, a] in fp32 whose sum over the action dimension is ``logp`` [rows, n] (fp64)."""
+    return (logp / a).unsqueeze(-1).expand(*logp.shape, a).float().contiguous()
+
+
+def policy_families(rows, n, a, generator, per_row=True, log_std_range=LOG_STD_RANGES[0]):
+    """The named input families of the PPO policy loss on ``rows`` rows of ``n`` agents and ``a`` action components: inputs
+    (means, log_stds, actions, old_log_prob — each [rows, n, a] —, advantages [rows, n]), ``params`` {"eps_clip"}.  ``per_row``
+    False: every log-std is one number (the fixed-std policy; the test hands ``fixed_log_stds`` of it over).  One action for
+    every agent of a row (ippo.py:72-73).  old_log_prob is the fp64 log-density plus 0.1 randn unless said otherwise.
+
+    plain        tests/test_gauss_head_gpu.py's centred regime: ratios of order one on both sides of the clip range; every
+                 seventh row's advantages exactly zero.
+    on_mean      means on a grid of 2^-10 (their sum is exact in any order and any precision) and the action bit-equal to the
+                 agent-summed mean: d = 0, d_means exactly zero, d_log_stds = -sum of dlogp.
+    zero_adv     every advantage 0: the loss and both gradients exactly zero.
+    clipped_out  old = log p - sign(adv): every ratio e or 1 / e on the side where the clipped branch is the smaller and has no
+                 gradient; no advantage is zero.  Gradients exactly zero, the loss the clipped surrogate.
+    ends_min / ends_max  every agent's log-std at the lower / upper end of ``log_std_range``.  Means and actions are plain's
+                 times the summed standard deviation exp(n end), so that the standardised residual stays of order one while
+                 log p is of order n a |end|.
+    wide         the large-ratio regime of test_ppo_policy_loss_rows_with_large_ratios: uncentred means, old = the action.
+    mixed        POLICY_MIXED_OF interleaved row by row (``groups``: which)."""
+    import math
+    g = generator
+    rnd = lambda *s: th.randn(*s, generator=g)
+    m0, l0, z, e, adv = rnd(rows, n, a), rnd(rows, n, a), rnd(rows, 1, a), rnd(rows, n), rnd(rows, n)
+    mw, lw = rnd(rows, n, a), rnd(rows, n, a)
+    adv0 = adv.clone()
+    adv0[::7] = 0.0
+
+    def log_stds_of(t):
+        return t if per_row else t[:1, :1, :1].expand(rows, n, a).contiguous()
+
+    def finish(name, means, log_stds, one, advantages, old=None, shift=None):
+        actions = one.expand(rows, n, a).contiguous()
+        if old is None:
+            logp = _log_density64(means, log_stds, actions)
+            old = _stored_log_prob(logp + (0.1 * e.double() if shift is None else shift), a)
+        return Family(name, (means, log_stds, actions, old, advantages.clone()), {"eps_clip": POLICY_EPS})
+
+    means = -0.9 / n + 0.1 / n ** 0.5 * m0
+    ls = log_stds_of(0.15 / n ** 0.5 * l0 - 0.05 / n)
+    one = means.sum(1, keepdim=True) + 0.25 * z
+    out = {"plain": finish("plain", means, ls, one, adv0)}
+    grid = (means * 1024.0).round() / 1024.0
+    out["on_mean"] = finish("on_mean", grid, ls, grid.sum(1, keepdim=True), adv0)
+    out["zero_adv"] = finish("zero_adv", means, ls, one, th.zeros_like(adv))
+    nz = th.where(adv == 0, th.ones_like(adv), adv)
+    out["clipped_out"] = finish("clipped_out", means, ls, one, nz, shift=-th.sign(nz).double())
+    for name, end in zip(("ends_min", "ends_max"), log_std_range):
+        sd = math.exp(n * end)
+        me = (means.double() * sd).float()
+        out[name] = finish(name, me, th.full((rows, n, a), float(end)), (me.sum(1, keepdim=True).double() + sd * 0.25 * z.double()).float(),
+                           adv0)
+    wm = 0.3 * mw
+    wone = wm.sum(1, keepdim=True) + 0.7 * z
+    out["wide"] = finish("wide", wm, log_stds_of(0.15 * lw - 0.05), wone, adv, old=wone.expand(rows, n, a).contiguous())
+    groups = th.arange(rows) % len(POLICY_MIXED_OF)
+    mixed = [t.clone() for t in out["plain"].inputs]
+    for j, name in enumerate(POLICY_MIXED_OF):
+        for k, t in enumerate(out[name].inputs):
+            mixed[k][groups == j] = t[groups == j]
+    out["mixed"] = Family("mixed", tuple(mixed), {"eps_clip": POLICY_EPS}, groups)
+    return out
+
+
+def policy_clear_kinks(inputs, eps_clip, eps=KINK):
+    """An element (row, agent) has a kink when its fp64 ratio lies within ``eps`` (relative) of 1 - eps_clip or 1 + eps_clip with
+    a non-zero advantage: on which side of clamp's end it falls is arbitrary in any fp32 form.  Their advantages are set to
+    zero IN PLACE (a zero gradient in every form).  Returns the share; the caller asserts it is at most TIE_CAP."""
+    means, log_stds, actions, old, adv = inputs
+    ratio = th.exp(_log_density64(means, log_stds, actions) - old.double().sum(-1))
+    kink = (((ratio / (1.0 - eps_clip) - 1.0).abs() < eps) | ((ratio / (1.0 + eps_clip) - 1.0).abs() < eps)) & (adv != 0)
+    adv[kink] = 0.0
+    return float(kink.double().mean())
+
+
+POLICY_WRONG = ("no_minus_one",)
+
+
+def policy_loss_plain(inputs, eps_clip, dtype, fixed=False, wrong=None):
+    """nets.ppo_policy_loss_torch on a family's ``inputs`` cast to ``dtype``, with autograd: {"loss", "ratio", "d_means",
+    "d_log_stds"} (the last only for per-row log-stds; ``fixed``: ``fixed_log_stds`` of the first one).  ``wrong``
+    "no_minus_one": d log p / d log_std taken as (x - mu)^2 / var, without the - 1 of the density's normalisation (values
+    unchanged: only the backward is wrong)."""
+    import math
+    from safe_marl_amd.nets import ppo_policy_loss_torch
+    assert wrong is None or wrong in POLICY_WRONG, wrong
+    means, log_stds, actions, old, adv = (t.detach().to(dtype) for t in inputs)
+    m = means.clone().requires_grad_(True)
+    ls = fixed_log_stds(m, inputs[1]) if fixed else log_stds.clone().requires_grad_(True)
+    if wrong is None:
+        loss, ratio = ppo_policy_loss_torch(m, ls, actions, old, adv, eps_clip)
+    else:
+        mu, s = m.sum(1, keepdim=True), ls.sum(1, keepdim=True)
+        logp = (-(actions - mu).square() / (2 * s.exp().square()) - s.detach() - math.log(math.sqrt(2 * math.pi))).sum(-1)
+        ratio = th.exp(logp - old.sum(-1))
+        loss = -th.min(ratio * adv, th.clamp(ratio, 1 - eps_clip, 1 + eps_clip) * adv).mean()
+    grads = th.autograd.grad(loss, [m] if fixed else [m, ls])
+    out = {"loss": loss.detach(), "ratio": ratio.detach(), "d_means": grads[0]}
+    if not fixed:
+        out["d_log_stds"] = grads[1]
+    return out
+
+
+def value_families(rows, n, generator):
+    """The PPO value loss's families: inputs (values, old_values, next_values, reward_norm [rows, n], done [rows]), ``params``
+    {"eps_clip"}.
+
+    plain     tests/test_ppo_gpu.py's ``_value_inputs``: V = old + 0.5 randn, eps_clip 0.5, with its constructed rows — every
+              16th exactly on the upper clip boundary, the next on the lower one, the next a tie surr1 == surr2 outside the
+              range (all exact in fp32: old in quarters, no bootstrap).
+    eps0      plain's with eps_clip = 0: the clip range is the point V = old; every 16th row from the fourth has V == old,
+              bit for bit (inside the closed range, and a tie).
+    all_done  plain's with done = 1 on every row: the return is the normalised reward."""
+    g = generator
+    old = th.randn(rows, n, generator=g)
+    values = old + 0.5 * th.randn(rows, n, generator=g)
+    nv, rn = th.randn(rows, n, generator=g), th.randn(rows, n, generator=g)
+    done = (th.rand(rows, generator=g) < 0.05).float()
+    eps = 0.5
+    for k in range(3):
+        old[k::16] = (old[k::16] * 4).round() / 4
+    values[0::16] = old[0::16] + eps
+    values[1::16] = old[1::16] - eps
+    values[2::16] = old[2::16] + 1.5
+    done[2::16] = 1.0
+    rn[2::16] = old[2::16] + 1.0              # V - ret = 0.5, vc - ret = old + 0.5 - ret = -0.5
+    out = {"plain": Family("plain", (values, old, nv, rn, done), {"eps_clip": eps})}
+    v0 = values.clone()
+    v0[3::16] = old[3::16]
+    out["eps0"] = Family("eps0", (v0, old, nv, rn, done), {"eps_clip": 0.0})
+    out["all_done"] = Family("all_done", (values, old, nv, rn, th.ones_like(done)), {"eps_clip": eps})
+    return out
+
+
+VALUE_WRONG = ("clamp_open",)
+
+
+def value_loss_plain(inputs, eps_clip, gamma, coef, dtype, wrong=None):
+    """nets.ppo_value_loss_torch on a family's ``inputs`` cast to ``dtype``, with autograd: {"loss", "d_values", "returns"}.
+    ``wrong`` "clamp_open": clamp's gradient cut AT its ends (V exactly eps_clip away from the old value), where th.clamp
+    passes it."""
+    from safe_marl_amd.nets import ppo_value_loss_torch
+    assert wrong is None or wrong in VALUE_WRONG, wrong
+    values, old, nv, rn, done = (t.detach().to(dtype) for t in inputs)
+    v = values.clone().requires_grad_(True)
+    vv = v
+    if wrong == "clamp_open":
+        vv = th.where((v - old).abs() == eps_clip, v.detach(), v)
+        returns = rn + gamma * (1 - done.reshape(-1, 1)) * nv
+        clipped = old + th.clamp(vv - old, -eps_clip, eps_clip)
+        loss = coef * th.max((v - returns).pow(2), (clipped - returns).pow(2)).mean()
+    else:
+        loss, returns = ppo_value_loss_torch(v, old, nv, rn, done, gamma, eps_clip, coef)
+    (gv,) = th.autograd.grad(loss, [v])
+    return {"loss": loss.detach(), "d_values": gv, "returns": returns.detach()}
+
+
+def value_keep(inputs, eps_clip, gamma, eps=KINK):
+    """bool [rows, n]: the elements whose d_values is compared.  Left out, as arbitrary in any fp32 form: |V - old| within
+    ``eps`` of eps_clip without being exactly on it (which side of clamp's end), and — OUTSIDE the clip range, where the
+    clipped branch has no gradient — |s1 - s2| <= eps max(s1, s2) without s1 == s2 (which of the two squares is th.max's).
+    Inside the range the clipped value is V up to a rounding and both branches carry the same gradient: nothing is arbitrary
+    there.  All in fp64; the constructed boundary and tie rows are exact and stay.  The caller holds 1 - mean to TIE_CAP."""
+    values, old, nv, rn, done = (t.double() for t in inputs)
+    d = values - old
+    ret = rn + gamma * (1 - done.reshape(-1, 1)) * nv
+    s1, s2 = (values - ret).square(), (old + th.clamp(d, -eps_clip, eps_clip) - ret).square()
+    near_clip = ((d.abs() - eps_clip).abs() < eps) & (d.abs() != eps_clip)
+    near_tie = (d.abs() > eps_clip) & ((s1 - s2).abs() <= eps * th.maximum(s1, s2)) & (s1 != s2)
+    return ~(near_clip | near_tie)
+
+
+GAUSS_WRONG = ("one_minus_t",)
+
+
+def gauss_head_plain(inputs, lo, hi, dtype, low=0.0, high=1.0, wrong=None):
+    """nets.gauss_log_std_torch with the exploration epilogue (maddpg.py:88 under util.py:56-64, translate_action
+    util.py:125-128) and autograd, on a family's ``inputs`` (h [rows, 64], w, b, means, noise, d_log_std [rows, a]) cast to
+    ``dtype``.  w [a, 64] / b [a]: the shared head; w [n, a, 64] / b [n, a]: every agent's own, row r through head r % n.
+    {"log_std", "t", "action", "env_action", "d_h", "d_w", "d_b", "d_u"}.  ``wrong`` "one_minus_t": d_u with 1 - t in place of
+    1 - t^2 (values unchanged)."""
+    assert wrong is None or wrong in GAUSS_WRONG, wrong
+    h, w, b, means, noise, d_ls = (t.detach().to(dtype) for t in inputs)
+    h, w, b = (t.clone().requires_grad_(True) for t in (h, w, b))
+    if w.dim() == 3:
+        n = w.shape[0]
+        hv = h.view(-1, n, h.shape[1])
+        u = th.stack([F.linear(hv[:, i], w[i], b[i]) for i in range(n)], 1).reshape(h.shape[0], -1)
+    else:
+        u = F.linear(h, w, b)
+    t = th.tanh(u)
+    tt = t if wrong is None else t.detach() + (u - u.detach()) * (1 - t.detach())
+    log_std = lo + 0.5 * (hi - lo) * (tt + 1)
+    action = th.tanh(means + log_std.exp() * noise)
+    env = 0.5 * (th.clamp(action, min=low, max=high) + 1.0) * (high - low) + low
+    d_h, d_w, d_b, d_u = th.autograd.grad(log_std, (h, w, b, u), d_ls)
+    return {"log_std": log_std.detach(), "t": t.detach(), "action": action.detach(), "env_action": env.detach(), "d_h": d_h,
+            "d_w": d_w, "d_b": d_b, "d_u": d_u}
+
+
+def _gauss_u64(h, w, b):
+    if w.dim() == 3:
+        n = w.shape[0]
+        return (th.einsum("bnk,nak->bna", h.double().view(-1, n, 64), w.double()) + b.double()).reshape(h.shape[0], -1)
+    return h.double() @ w.double().t() + b.double()
+
+
+def gauss_families(rows, a, generator, n=None, attempts=400):
+    """The log-std head's families on ``rows`` rows of 64 hidden units and ``a`` outputs: inputs (h, w, b, means, noise,
+    d_log_std); ``n``: per-agent heads (w [n, a, 64], row r through head r % n, ``rows`` a multiple of n).  ``params``
+    {"range": (lo, hi)} where the family fixes it, {} where the test takes LOG_STD_RANGES.
+
+    plain       h 0.5 randn, weights and bias 0.1 randn, means, noise and the upstream gradient randn.
+    reset       h = 0: u = b.
+    saturated   h = 40 sign(randn), weights 0.3 randn; a row is drawn again until every |u| of it is at least
+                GAUSS_SATURATED in fp64: t = +-1 to the last bit, log_std exactly an end of the range, d_u and d_h exactly zero.
+    flat        plain's inputs with lo == hi: log_std constant, every gradient exactly zero.
+    wide_noise  plain's with the range (-5, 2) and noise 4 randn: the actions saturate and env_action sits on both clamp ends.
+    mixed       GAUSS_MIXED_OF interleaved row by row — per-agent heads: sample by sample — under saturated's weights
+                (``groups``: which), so that one 32-row tile holds each kind."""
+    g = generator
+    rnd = lambda *s: th.randn(*s, generator=g)
+    wshape, bshape = ((a, 64), (a,)) if n is None else ((n, a, 64), (n, a))
+    h, w, b = 0.5 * rnd(rows, 64), 0.1 * rnd(*wshape), 0.1 * rnd(*bshape)
+    means, noise, d_ls = rnd(rows, a), rnd(rows, a), rnd(rows, a)
+    ws = 0.3 * rnd(*wshape)
+    hs = 40.0 * th.sign(rnd(rows, 64))
+    for _ in range(attempts):
+        again = (_gauss_u64(hs, ws, b).abs() < GAUSS_SATURATED).any(1)
+        if not again.any():
+            break
+        fresh = 40.0 * th.sign(rnd(rows, 64))
+        hs[again] = fresh[again]
+    else:
+        raise AssertionError(f"no saturated draw of {rows} rows, {a} outputs in {attempts} attempts")
+    out = {"plain": Family("plain", (h, w, b, means, noise, d_ls), {}),
+           "reset": Family("reset", (th.zeros_like(h), w, b, means, noise, d_ls), {}),
+           "saturated": Family("saturated", (hs, ws, b, means, noise, d_ls), {}),
+           "flat": Family("flat", (h, w, b, means, noise, d_ls), {"range": (0.25, 0.25)}),
+           "wide_noise": Family("wide_noise", (h, w, b, means, 4.0 * noise, d_ls), {"range": LOG_STD_RANGES[1]})}
+    groups = (th.arange(rows) if n is None else th.arange(rows) // n) % len(GAUSS_MIXED_OF)
+    hm = h.clone()
+    hm[groups == 1] = 0.0
+    hm[groups == 2] = hs[groups == 2]
+    out["mixed"] = Family("mixed", (hm, ws, b, means, noise, d_ls), {}, groups)
+    return out
+
+
+def td_families(rows, n, generator):
+    """The stand-alone TD loss's families: inputs (q, next_q, reward [rows, n], done [rows]).  plain: tests/test_tdloss_gpu.py's
+    reward 3 randn - 5; failure: ``gae_families``' reward columns 0 and 1 (exactly FAILURE_REWARD; FAILURE_REWARD +
+    FAILURE_SPREAD randn), the rest plain's."""
+    g = generator
+    reward = 3.0 * th.randn(rows, n, generator=g) - 5.0
+    done = (th.rand(rows, generator=g) < 0.1).float()
+    nq, q = th.randn(rows, n, generator=g), th.randn(rows, n, generator=g)
+    spread = th.randn(rows, generator=g)
+    rf = reward.clone()
+    rf[:, 0] = FAILURE_REWARD
+    if n > 1:
+        rf[:, 1] = FAILURE_REWARD + FAILURE_SPREAD * spread
+    return {"plain": Family("plain", (q, nq, reward, done), {}), "failure": Family("failure", (q, nq, rf, done), {})}
+
+
+def td_run(inputs, gamma, bn, dtype):
+    """``td_loss_plain`` through a training-mode BatchNorm1d module ``bn`` (already in ``dtype``, or None), which is moved as its
+    forward moves it, with autograd: {"loss", "dq", and with a module "running_mean", "running_var", "num_batches_tracked"}."""
+    q, nq, reward, done = (t.detach().to(dtype) for t in inputs)
+    q = q.clone().requires_grad_(True)
+    with th.no_grad():
+        r = bn(reward) if bn is not None else reward
+    loss = td_loss_plain(q, nq, r, done, gamma, None)
+    (dq,) = th.autograd.grad(loss, [q])
+    out = {"loss": loss.detach(), "dq": dq}
+    if bn is not None:
+        out.update(running_mean=bn.running_mean.clone(), running_var=bn.running_var.clone(),
+                   num_batches_tracked=bn.num_batches_tracked.clone())
+    return out
+
+
+def within_budget_rms(kernel, torch32, ref, *, name, margin=4.0, floor_ulps=4.0):
+    """The rms form of tests/test_gauss_head_gpu.py::test_ppo_policy_loss_rows_with_large_ratios, with that test's factors:
+    rms(kernel - ref) <= 4 rms(torch32 - ref) + 4 * 2^-24 rms(ref).  Where log p - old is of order ten or more the LARGEST
+    error of an output is the half-ulp luck of its one largest exponent, for the kernel and the composition alike; an arithmetic
+    that lost accuracy at large arguments would raise every large element's error, hence the rms."""
+    ref = ref.detach().double()
+    assert kernel.shape == ref.shape and torch32.shape == ref.shape, (name, kernel.shape, torch32.shape, ref.shape)
+    rms = lambda x: float(x.double().square().mean().sqrt())
+    err_k, err_t, scale = rms(kernel.detach().double() - ref), rms(torch32.detach().double() - ref), rms(ref)
+    ratio = err_k / err_t if err_t > 0 else (0.0 if err_k == 0 else float("inf"))
+    line = f"fp64-budget {name} [rms] err_k={err_k:.3e} err_t={err_t:.3e} ratio={ratio:.3g} scale={scale:.3e}"
+    print(line)
+    bound = margin * err_t + floor_ulps * ULP * max(scale, TINY)
+    assert err_k <= bound, f"{line} bound={bound:.3e}"
+    return ratio
+
+
+def policy_loss_rounding(inputs, eps_clip):
+    """What fp32 rounding of the exponent's argument alone does to the policy LOSS — one number, a mean over rows n elements
+    whose terms cancel — to first order at the fp64 evaluation: errors that a correct fp32 evaluation reaches whatever its
+    order of operations.  (The gradients and the ratio are tensors: their fp32 yardstick is a maximum over many elements and
+    needs no such floor.  The loss of the fp32 composition can come out within a fraction of an ulp by luck, and the advantages
+    are zero-mean, so the loss — the scale of the 8-ulp floor — is far smaller than its terms.)
+
+    ratio = exp(x), x = log p - old.  log p is a sum of a terms T_k = d_k^2 / (2 var_k) + log sigma_k + log sqrt(2 pi), old a sum
+    of a stored components, each accumulated in fp32: a partial sum P is rounded within 2^-24 |P| (uniform: variance
+    (2^-24 P)^2 / 3, ``gate_rounding``'s model; measured sums have 0.74 of this sigma), every term carries two such roundings
+    of its own (the quotient, the sum with its constants), and the difference log p - old one more.  Behind them, the fp32 sums
+    over the agents: mu (partial sums M_i; d x / d mu_k = d_k / var_k) and the log-std (partial sums L_i;
+    d x / d ls_k = d_k^2 / var_k - 1).  So
+        var x = (2^-24)^2 / 3 * (sum_k P_k^2 + 2 sum_k T_k^2 + sum_k O_k^2 + x^2
+                                 + sum_k (d_k / var_k)^2 sum_i M_ik^2 + sum_k (d_k^2 / var_k - 1)^2 sum_i L_ik^2).
+    An element's surrogate min(ratio A, clamp(ratio) A) moves by w A ratio dx, w = 1 where the unclipped branch is the smaller
+    one or the ratio is inside the range, 0 where the clipped branch is; its own product and exponential add three roundings of
+    2^-24 |s|.  Where the elements' roundings are independent the loss, their mean, has
+        sigma_i^2 = sum_i ((w_i A_i ratio_i)^2 var x_i + (2^-24)^2 s_i^2) / (rows n)^2.
+    They are not all independent: what the rows share — the density's constants where the log-std is one number (the fixed-std
+    policy, a head at an end of its range), and the partial sums of terms T_k that are those constants plus a small square —
+    is rounded the same way in every element, and a common dx moves the loss by dx mean_i(w_i A_i ratio_i), which does not
+    average out (the clipped elements are missing from the mean on one side of each sign of A: 1.4 % of the ratios' scale at
+    eps_clip 0.2 with ratios exp(0.1 randn)).  The fp32 composition's dx has a mean of 0.2 to 0.6 of its root mean square on
+    the families of ``policy_families``; the figure allows all of it to be common:
+        sigma_c = rms_i(sqrt(var x_i)) |mean_i(w_i A_i ratio_i)|,    3 sqrt(sigma_i^2 + sigma_c^2).
+    tests/test_fp64_budget_cpu.py holds it against the fp32 composition's own loss over many draws, and that a budget with
+    this floor still rejects a loss with one row left out."""
+    import math
+    means, log_stds, actions, old, adv = (t.detach().double() for t in inputs)
+    mu, ls = means.sum(1, keepdim=True), log_stds.sum(1, keepdim=True)
+    var = th.exp(2.0 * ls)
+    d = actions - mu                                                                   # [rows, n, a]
+    terms = d.square() / (2.0 * var) + ls + 0.5 * math.log(2.0 * math.pi)
+    x = -terms.sum(-1) - old.sum(-1)
+    m_sq = means.cumsum(1).square().sum(1, keepdim=True)                               # [rows, 1, a]
+    l_sq = log_stds.cumsum(1).square().sum(1, keepdim=True)
+    var_x = (ULP ** 2 / 3.0) * (terms.cumsum(-1).square().sum(-1) + 2.0 * terms.square().sum(-1) + old.cumsum(-1).square().sum(-1)
+                                + x.square() + ((d / var).square() * m_sq).sum(-1) + ((d.square() / var - 1.0).square() * l_sq).sum(-1))
+    ratio = th.exp(x)
+    s1, s2 = ratio * adv, th.clamp(ratio, 1.0 - eps_clip, 1.0 + eps_clip) * adv
+    w = (s1 <= s2).double()
+    sigma2 = ((w * adv * ratio).square() * var_x + ULP ** 2 * th.minimum(s1, s2).square()).sum() / float(adv.numel()) ** 2
+    common2 = var_x.mean() * (w * adv * ratio).mean().square()
+    return 3.0 * (sigma2 + common2).sqrt()
