@@ -284,6 +284,30 @@ typedef struct {
 int flexenv_rollout_burst(FlexEnv* env, const FlexActorArgs* actor, double* reward, uint8_t* done,
                           double* info, uint8_t* failed, float* obs_ring, int32_t steps,
                           const FlexBurstSafety* safety /* NULL: plain MADDPG */, void* stream);
+/* The burst of the agent-summed algorithms (MATD3, IDDPG, FACMADDPG, SQDDPG, IPPO, MAPPO, COMA: matd3.py:92-97 / iddpg.py:66-71
+ * under utils/util.py:57-64) — `steps` repetitions of the three launches policy (means and new hidden state only, no
+ * exploration epilogue), flexnet_agent_sum_explore, environment step with the replay sink, in ONE launch.  Block, groups,
+ * hand-overs, ring and cursor cells are flexenv_rollout_burst's; between policy and environment of a step every wavefront
+ * turns the means of its own two environments into the one action every agent gets, with flexnet_agent_sum_explore's
+ * arithmetic rounding for rounding (one device function serves both): s = ((m_0 + m_1) + m_2) + ... in fp32,
+ * y = tanhf(s + eps * std[k]) with product and sum rounded separately, the NaN-preserving clamp and the four separately rounded
+ * operations of translate_action.  y goes to every agent's row of actor->action (what the sink files), the translated value
+ * to every agent's row of actor->env_action (what the step reads).  No noise is generated in the kernel: step t of the launch
+ * reads eps[t] of a caller-filled buffer, so the draws stay in the caller's generator.  actor->rng_state, noise and std are
+ * ignored.  The finish launch moves the two cursor cells and nothing else.  Afterwards every buffer and both cursor cells hold
+ * what `steps` repetitions of the three launches leave, bit for bit (tests/test_summed_burst_gpu.py).
+ * FLEX_EINVAL (before any HIP call): everything flexenv_rollout_burst refuses about the env, the sink, the ring, the cursor
+ * cells and the actor's shapes (its noise-stream conditions excepted); `summed`, eps or std missing; !(act_high >= act_low);
+ * act_dim != 4; n_agents > 5; steps >= slabs; a sink with an aux_counter (that sink belongs to the in-kernel noise stream of
+ * flexenv_rollout_burst). */
+typedef struct {
+    const float* eps;   /* dev [steps, N, act_dim] standard-normal draws; step t of the launch reads row t */
+    const float* std;   /* dev [act_dim]: exp of the agent-summed log-std (FlexAgentSumArgs.std) */
+    float act_low, act_high;
+} FlexBurstSummed;
+int flexenv_rollout_burst_summed(FlexEnv* env, const FlexActorArgs* actor, double* reward, uint8_t* done,
+                                 double* info, uint8_t* failed, float* obs_ring, int32_t steps,
+                                 const FlexBurstSummed* summed, void* stream);
 /* One TEST-mode episode per environment (madrl/models/model.py:269-306 for every environment at once) in ONE persistent
  * launch, with a per-episode record.  Block b owns environments 16 b .. 16 b + 15 as in flexenv_rollout_burst; the launch
  * starts from the state flexenv_reset leaves and every one of its `steps` steps is

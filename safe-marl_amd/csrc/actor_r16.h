@@ -535,15 +535,20 @@ __device__ __forceinline__ void r16_stage_simple(const FlexActorArgs& a, ActorLd
 // TEST (flexenv_test_episodes): the policy in test mode — tanh(mean) (utils/util.py:79-82), translate_action (util.py:125-128):
 // no noise is drawn and rng_state is not read, no slab ring and no cursor cell: the hidden state alternates between
 // a.hidden_in and a.hidden_out (step 0 reads hidden_in), and env_step is handed the step's index instead of a slab.
-template <bool TEST = false, typename EnvStep, typename Mark>
+// NOISE false without TEST (flexenv_rollout_burst_summed): the ring form — slab ring, cursor cell, observation in place — of a
+// policy that only hands on its means: no noise is drawn (wavefront 3 idles through the policy phase) and rng_state is not
+// read; means and the new hidden state are written as ever, action / env_action are left to the environment phase's
+// agent-summed selection.  env_step(slab or step, step): the second argument is the step's index within the launch.
+template <bool TEST = false, bool NOISE = !TEST, typename EnvStep, typename Mark>
 __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds16B& s, const int n_steps, EnvStep&& env_step,
                                                 Mark&& mark) {
+    static_assert(!(TEST && NOISE), "test mode draws no noise");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 15, g = lane >> 4;
     const int grp = wave >> 2, w = wave & 3;
     const int od = a.obs_dim, na = a.n_agents, ad = a.act_dim;
     const int nq = (od + 15) >> 4;
-    const uint64_t rng_seed = TEST ? 0ull : a.rng_state[0], rng_step = TEST ? 0ull : a.rng_state[1];
+    const uint64_t rng_seed = NOISE ? a.rng_state[0] : 0ull, rng_step = NOISE ? a.rng_state[1] : 0ull;
     // this group's rows, this wavefront's tile
     const int grow0 = (16 * (int)blockIdx.x + 8 * grp) * na;
     const int grows = min(8 * na, a.rows - grow0);                         // (<= 0: a tail block's empty group)
@@ -567,7 +572,7 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
         }
     };
     r16_stage_simple(a, s, tid);
-    if (!TEST && w == 3) draw(rng_step);
+    if (NOISE && w == 3) draw(rng_step);
     if (tid < 2) s.gsync[tid] = 0;
     __syncthreads();
 
@@ -625,7 +630,7 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
                 mo = MFMA16(w2_l[(16 * (st >> 2) + (st & 3)) * R16_P2], hnew[st >> 2][st & 3], mo);
             if (live && 4 * g < ad) {
                 float zr[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                if constexpr (!TEST) {
+                if constexpr (NOISE) {
                     const float4 zv = *reinterpret_cast<const float4*>(&s.noise[(rng_step + step) & 1][grp][w][j][4 * g]);
                     zr[0] = zv.x; zr[1] = zv.y; zr[2] = zv.z; zr[3] = zv.w;
                 }
@@ -636,13 +641,15 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
                         const float o = mo[r] + s.b2[k];
                         const int64_t at = (int64_t)row * ad + k;
                         a.means[at] = o;
-                        const float act = fast_tanh(TEST ? o : o + a.std * zr[r]);            // util.py:57-64 (TEST: 79-82), 125-128
-                        a.action[at] = act;
-                        a.env_action[at] = 0.5f * (clamp_nan(act, a.action_low, a.action_high) + 1.0f) * (a.action_high - a.action_low) + a.action_low;
+                        if constexpr (TEST || NOISE) {
+                            const float act = fast_tanh(TEST ? o : o + a.std * zr[r]);        // util.py:57-64 (TEST: 79-82), 125-128
+                            a.action[at] = act;
+                            a.env_action[at] = 0.5f * (clamp_nan(act, a.action_low, a.action_high) + 1.0f) * (a.action_high - a.action_low) + a.action_low;
+                        }
                     }
                 }
             }
-        } else if (!TEST && w == 3 && step + 1 < n_steps) {
+        } else if (NOISE && w == 3 && step + 1 < n_steps) {
             draw(rng_step + step + 1);                                     // (the other parity: read in the next policy phase)
         }
         // policy outputs (global memory: env action, action, new hidden state) and the noise (LDS) -> the group's other
@@ -651,7 +658,7 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
         ++meets;
         r16_rendezvous(&s.gsync[grp], 4 * meets, lane);
         mark(9, step);
-        env_step(TEST ? (int64_t)step : slab);
+        env_step(TEST ? (int64_t)step : slab, step);
         mark(10, step);
         // ... and the step's outputs (observation, masked hidden state: slab + 1) -> the next policy phase
         ++meets;

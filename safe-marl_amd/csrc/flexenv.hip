@@ -10,6 +10,7 @@
 #include "flex_device.h"
 #include "flexnet.h"
 #include "actor_r16.h"
+#include "agent_sum.h"
 
 #define FLEX_MAX_DEVICES 16
 #define HIP_TRY(x) do { hipError_t _e = (x); if (_e != hipSuccess) { \
@@ -1338,13 +1339,23 @@ struct BurstArgs {
     double* adjusted;           // [N, 4 n_agents] (the replay keeps the policy's own action: nothing reads this)
     float* safe_env_action;     // [N, 4 n_agents] translate_action of the projected vector: what the step reads
     float act_low, act_span;
+    // The agent-summed algorithms (flexenv_rollout_burst_summed; matd3.py:92-97 / iddpg.py:66-71 under util.py:57-64): between
+    // policy and environment each wavefront turns the means of its own two environments into the ONE action every agent gets
+    // (agent_sum_select, csrc/agent_sum.h: the arithmetic of flexnet_agent_sum_explore) — act.action, which the sink files, and
+    // act.env_action, which the step reads
+    const float* eps;           // [n_steps, N, act_dim] standard-normal draws (torch's generator): step t reads row t
+    const float* sum_std;       // [act_dim]
+    float act_high;
 };
+
+// the burst's three forms
+enum { BURST_PLAIN = 0, BURST_SAFE = 1, BURST_SUMMED = 2 };
 
 // (Inlined again since the policy became actor_r16_burst, which keeps almost nothing live across the step: 12 spilled
 //  registers, none in the step's loops, against the 64 the called version saved and restored per step — 34.4 -> 31.8 us per
 //  vector step.  The argument plumbing of the called version stays: it is what keeps the step's scalars out of the policy's.)
-template <int NA_CAP, bool SAFE>
-__device__ __forceinline__ void flex_burst_env_step(int slab_v, unsigned kbase_lo, unsigned kbase_hi) {
+template <int NA_CAP, int MODE>
+__device__ __forceinline__ void flex_burst_env_step(int slab_v, int step_v, unsigned kbase_lo, unsigned kbase_hi) {
     // (arguments of a call arrive in vector registers: back to scalars)
     const unsigned long long kbase = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)kbase_lo) |
                                      ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)kbase_hi) << 32);
@@ -1356,7 +1367,7 @@ __device__ __forceinline__ void flex_burst_env_step(int slab_v, unsigned kbase_l
     // the chain goes first, the stream takes the gaps
     __builtin_amdgcn_s_setprio(3);
     const float* actions = b.act.env_action;
-    if constexpr (SAFE) {
+    if constexpr (MODE == BURST_SAFE) {
         const int na = b.k.cfg.n_agents, lane = threadIdx.x & 63;
         const int env = 2 * wave + lane / na;
         if (lane < 2 * na && env < b.k.n_envs)
@@ -1367,21 +1378,37 @@ __device__ __forceinline__ void flex_burst_env_step(int slab_v, unsigned kbase_l
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         actions = b.safe_env_action;
     }
+    if constexpr (MODE == BURST_SUMMED) {
+        // lane map of flex_test_env_step<2>: lane (environment of the wavefront, action component); the means of both
+        // environments were stored by this group's policy tiles, a rendezvous ago
+        const int na = b.k.cfg.n_agents, ad = b.act.act_dim, lane = threadIdx.x & 63;      // (ad == 4: checked on the host)
+        const int t = __builtin_amdgcn_readfirstlane(step_v);
+        const int env = 2 * wave + lane / ad, k = lane % ad;
+        if (lane < 2 * ad && env < b.k.n_envs) {
+            const int64_t at = (int64_t)env * na * ad + k;
+            agent_sum_select(b.act.means + at, na, ad, b.eps + ((int64_t)t * b.k.n_envs + env) * ad + k, b.sum_std + k, b.act_low,
+                             b.act_high, b.act.action + at, b.act.env_action + at);
+        }
+        // (this wavefront's own stores, read back by its own step and sink: complete before the loads go out)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
     flex_step_body<2, float, float, NA_CAP, true, true>(b.k, wave, actions, b.reward, b.done, b.info, b.failed, b.obs_ring, 1, 1,
                                                   slab, false, kbase);
     __builtin_amdgcn_s_setprio(0);
 }
 
-template <int NA_CAP, bool SAFE>
-__global__ __launch_bounds__(64 * R16_W)
-void flex_rollout_burst_kernel(BurstArgs b) {
-    __shared__ ActorLds16B s;
+template <int NA_CAP, int MODE>
+__device__ __forceinline__ void flex_rollout_burst_body(const BurstArgs& b, ActorLds16B& s) {
     const unsigned long long kb = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
-    auto env_step = [&](int64_t slab) { flex_burst_env_step<NA_CAP, SAFE>((int)slab, (unsigned)kb, (unsigned)(kb >> 32)); };
+    auto env_step = [&](int64_t slab, int step) {
+        flex_burst_env_step<NA_CAP, MODE>((int)slab, step, (unsigned)kb, (unsigned)(kb >> 32));
+    };
+    constexpr bool NOISE = MODE != BURST_SUMMED;
 #ifdef FLEX_STAMPS
     // diagnostic build: phase boundaries of the LAST step, per wavefront, in slots 8-12 of its first environment's row
     const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * R16_W + (threadIdx.x >> 6));
-    actor_r16_burst(b.act, s, b.n_steps, env_step, [&](int slot, int step) {
+    actor_r16_burst<false, NOISE>(b.act, s, b.n_steps, env_step, [&](int slot, int step) {
         unsigned long long t;
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
@@ -1390,9 +1417,27 @@ void flex_rollout_burst_kernel(BurstArgs b) {
             b.k.stamps[(int64_t)(2 * wave) * 16 + slot] = t;
     });
 #else
-    actor_r16_burst(b.act, s, b.n_steps, env_step, [](int, int) {});
+    actor_r16_burst<false, NOISE>(b.act, s, b.n_steps, env_step, [](int, int) {});
 #endif
 }
+
+template <int NA_CAP, bool SAFE>
+__global__ __launch_bounds__(64 * R16_W)
+void flex_rollout_burst_kernel(BurstArgs b) {
+    __shared__ ActorLds16B s;
+    flex_rollout_burst_body<NA_CAP, SAFE ? BURST_SAFE : BURST_PLAIN>(b, s);
+}
+
+// The third form (flexenv_rollout_burst_summed), a kernel of its own name: the plain and SAFE instantiations above are the
+// whole of flex_rollout_burst_kernel<...>, whose resource figures tests pin by that prefix.
+namespace summed {
+template <int NA_CAP>
+__global__ __launch_bounds__(64 * R16_W)
+void flex_rollout_burst_kernel(BurstArgs b) {
+    __shared__ ActorLds16B s;
+    flex_rollout_burst_body<NA_CAP, BURST_SUMMED>(b, s);
+}
+}  // namespace summed
 
 // the cells a burst leaves as `steps` single steps would: cell 0 = the slab the policy reads next, cell 1 = the slab the last
 // step filed into, the noise stream's step counter advanced
@@ -1535,7 +1580,7 @@ void flex_test_episodes_kernel(TestArgs b) {
     __shared__ ActorLds16B s;
     const unsigned long long kb = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
     int alive = 1;
-    auto env_step = [&](int64_t step) { flex_test_env_step<MODE>((int)step, (unsigned)kb, (unsigned)(kb >> 32), alive); };
+    auto env_step = [&](int64_t step, int) { flex_test_env_step<MODE>((int)step, (unsigned)kb, (unsigned)(kb >> 32), alive); };
     actor_r16_burst<true>(b.act, s, b.n_steps, env_step, [](int, int) {});
 }
 
@@ -1960,41 +2005,61 @@ int flexenv_step_many(FlexEnv* e, const void* actions, int32_t act_dtype, int32_
     return FLEX_OK;
 }
 
-int flexenv_rollout_burst(FlexEnv* e, const FlexActorArgs* actor, double* reward, uint8_t* done, double* info,
-                          uint8_t* failed, float* obs_ring, int32_t steps, const FlexBurstSafety* safety, void* stream) {
-    if (!e || !actor || !reward || !done || !obs_ring || steps < 1) return FLEX_EINVAL;
+// What both burst entry points ask of the env, the sink, the ring, the cursor cells and the actor's shapes (everything but the
+// noise): the configuration of the two-launch sink step (flexenv_step with FLEX_STEP_OBS_RING | FLEX_STEP_REPLAY_SINK behind
+// flexnet_actor_forward in ring mode), and the policy's tiles of a block = the block's sixteen environments.  No HIP call.
+static bool burst_config_ok(const FlexEnv* e, const FlexActorArgs* actor, const double* reward, const uint8_t* done,
+                            const float* obs_ring, int32_t steps) {
+    if (!e || !actor || !reward || !done || !obs_ring || steps < 1) return false;
     const FlexActorArgs& p = *actor;
     const int na = e->cfg.n_agents;
-    // the configuration of the two-launch sink step (flexenv_step with FLEX_STEP_OBS_RING | FLEX_STEP_REPLAY_SINK behind
-    // flexnet_actor_forward in ring mode), and the policy's tiles of a block = the block's sixteen environments
-    if (!e->has_sink || e->obs_slabs < 2 || e->hnet.epw != 2 || na > 5) return FLEX_EINVAL;
+    if (!e->has_sink || e->obs_slabs < 2 || e->hnet.epw != 2 || na > 5) return false;
     if (p.rows != (int64_t)e->n_envs * na || p.n_agents != na || p.obs_dim < 1 || p.obs_dim > FLEXNET_MAX_OBS || (p.obs_dim & 3) ||
-        p.act_dim < 1 || p.act_dim > FLEXNET_MAX_ACT) return FLEX_EINVAL;
+        p.act_dim < 1 || p.act_dim > FLEXNET_MAX_ACT) return false;
     if (!p.hidden_in || !p.hidden_out || !p.means || !p.action || !p.env_action || !p.cursor || !p.cursor_out ||
         !p.fc1_w || !p.fc1_b || !p.w_ih || !p.w_hh || !p.b_ih || !p.b_hh || !p.fc2_w || !p.fc2_b ||
-        (p.layernorm && (!p.ln_w || !p.ln_b)) || (!p.noise && !p.rng_state)) return FLEX_EINVAL;
-    if (p.ring_slabs != e->obs_slabs || steps >= e->obs_slabs || p.obs_dim != 6 * e->cfg.history) return FLEX_EINVAL;
+        (p.layernorm && (!p.ln_w || !p.ln_b))) return false;
+    if (p.ring_slabs != e->obs_slabs || steps >= e->obs_slabs || p.obs_dim != 6 * e->cfg.history) return false;
     if (p.cursor_out != e->obs_cursor || p.cursor != e->sink.cursor_out || p.hidden_out != e->sink.hid_new ||
-        p.action != e->sink.policy_action || p.noise) return FLEX_EINVAL;
-    // the burst draws the noise of steps rng_state[1] .. rng_state[1] + steps - 1 in the kernel and the finish launch advances the
-    // step counter through the sink's aux_counter: the two must be the same cell, or the next burst would repeat the draws
-    // (ADVICE r03: a NULL aux_counter used to pass)
-    if (!p.rng_state || !e->sink.aux_counter || (const void*)e->sink.aux_counter != (const void*)(p.rng_state + 1)) return FLEX_EINVAL;
-    if (p.save_z1) return FLEX_EINVAL;
-    KArgs k = make_args(e);
-    k.obs_cursor = e->obs_cursor; k.obs_slab_stride = e->obs_slab_stride; k.obs_slabs = e->obs_slabs;
-    k.sink = e->sink;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((e->n_envs + 15) / 16), block(64 * R16_W);
-    const bool small_obs = na == FLEX_OBS_AGENTS_SMALL && 3 * e->cfg.history <= FLEX_OBS_CLASSES(2) * (FLEX_WAVE / 2);
+        p.action != e->sink.policy_action) return false;
+    return !p.save_z1;
+}
+
+// the launch's arguments without the mode's own: env, ring, sink, the policy reading the stacked observation IN PLACE from this
+// environment's history (what flexenv_obs_source hands out)
+static BurstArgs burst_args(FlexEnv* e, const FlexActorArgs& p, double* reward, uint8_t* done, double* info, uint8_t* failed,
+                            float* obs_ring, int32_t steps) {
     BurstArgs b;
-    b.k = k; b.act = p;
-    // the policy reads the stacked observation IN PLACE from this environment's history (what flexenv_obs_source hands out)
+    b.k = make_args(e);
+    b.k.obs_cursor = e->obs_cursor; b.k.obs_slab_stride = e->obs_slab_stride; b.k.obs_slabs = e->obs_slabs;
+    b.k.sink = e->sink;
+    b.act = p;
     b.act.obs = e->st.ring; b.act.obs_pushed = e->st.ienv + IF_OBSCNT;
     b.act.obs_row_stride = e->cfg.history * 12; b.act.obs_pushed_stride = IF_COUNT; b.act.obs_slots = e->cfg.history; b.act.obs_slot_w = 6;
     b.reward = reward; b.done = done; b.info = info; b.failed = failed; b.obs_ring = obs_ring; b.n_steps = (int)steps;
     b.safety = 0; b.s_p = b.s_q = b.beta = nullptr; b.v_min = b.v_max = b.rho = 0.0; b.adjusted = nullptr; b.safe_env_action = nullptr;
-    b.act_low = b.act_span = 0.0f;
+    b.act_low = b.act_span = b.act_high = 0.0f;
+    b.eps = b.sum_std = nullptr;
+    return b;
+}
+
+static bool burst_small_obs(const FlexEnv* e) {
+    return e->cfg.n_agents == FLEX_OBS_AGENTS_SMALL && 3 * e->cfg.history <= FLEX_OBS_CLASSES(2) * (FLEX_WAVE / 2);
+}
+
+int flexenv_rollout_burst(FlexEnv* e, const FlexActorArgs* actor, double* reward, uint8_t* done, double* info,
+                          uint8_t* failed, float* obs_ring, int32_t steps, const FlexBurstSafety* safety, void* stream) {
+    if (!burst_config_ok(e, actor, reward, done, obs_ring, steps)) return FLEX_EINVAL;
+    const FlexActorArgs& p = *actor;
+    // the burst draws the noise of steps rng_state[1] .. rng_state[1] + steps - 1 in the kernel and the finish launch advances the
+    // step counter through the sink's aux_counter: the two must be the same cell, or the next burst would repeat the draws
+    // (ADVICE r03: a NULL aux_counter used to pass)
+    if (p.noise || !p.rng_state || !e->sink.aux_counter || (const void*)e->sink.aux_counter != (const void*)(p.rng_state + 1))
+        return FLEX_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((e->n_envs + 15) / 16), block(64 * R16_W);
+    const bool small_obs = burst_small_obs(e);
+    BurstArgs b = burst_args(e, p, reward, done, info, failed, obs_ring, steps);
     if (safety) {
         if (!safety->s_p || !safety->s_q || !safety->beta || !safety->adjusted || !safety->env_action ||
             !(safety->act_high >= safety->act_low) || p.act_dim != 4) return FLEX_EINVAL;      // (four controls per building)
@@ -2012,7 +2077,30 @@ int flexenv_rollout_burst(FlexEnv* e, const FlexActorArgs* actor, double* reward
     }
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(flex_burst_finish_kernel, dim3(1), dim3(64), 0, s, const_cast<int64_t*>(p.cursor), p.cursor_out,
-                       e->sink.aux_counter ? const_cast<uint64_t*>(p.rng_state) : nullptr, (int)steps, (int)e->obs_slabs);
+                       const_cast<uint64_t*>(p.rng_state), (int)steps, (int)e->obs_slabs);
+    HIP_TRY(hipGetLastError());
+    return FLEX_OK;
+}
+
+int flexenv_rollout_burst_summed(FlexEnv* e, const FlexActorArgs* actor, double* reward, uint8_t* done, double* info,
+                                 uint8_t* failed, float* obs_ring, int32_t steps, const FlexBurstSummed* summed, void* stream) {
+    // every argument check comes before the first HIP call
+    if (!summed || !summed->eps || !summed->std || !(summed->act_high >= summed->act_low)) return FLEX_EINVAL;
+    if (!burst_config_ok(e, actor, reward, done, obs_ring, steps)) return FLEX_EINVAL;
+    const FlexActorArgs& p = *actor;
+    // four controls per building: the selection's lane map.  A sink with an aux_counter belongs to the in-kernel noise stream
+    // of the plain burst: the finish launch here moves the two cursor cells and nothing else
+    if (p.act_dim != 4 || e->sink.aux_counter) return FLEX_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((e->n_envs + 15) / 16), block(64 * R16_W);
+    BurstArgs b = burst_args(e, p, reward, done, info, failed, obs_ring, steps);
+    b.act.rng_state = nullptr; b.act.noise = nullptr;           // (neither is read: the draws are summed->eps)
+    b.eps = summed->eps; b.sum_std = summed->std; b.act_low = summed->act_low; b.act_high = summed->act_high;
+    if (burst_small_obs(e)) hipLaunchKernelGGL((summed::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_SMALL>), grid, block, 0, s, b);
+    else hipLaunchKernelGGL((summed::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_LARGE>), grid, block, 0, s, b);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(flex_burst_finish_kernel, dim3(1), dim3(64), 0, s, const_cast<int64_t*>(p.cursor), p.cursor_out,
+                       (uint64_t*)nullptr, (int)steps, (int)e->obs_slabs);
     HIP_TRY(hipGetLastError());
     return FLEX_OK;
 }

@@ -11,6 +11,7 @@
 #include "flexnet.h"
 #include "flex_launch.h"
 #include "flex_nan.h"
+#include "agent_sum.h"
 #include "flex_td.h"
 #include "window_refresh.h"
 
@@ -161,20 +162,10 @@ __global__ __launch_bounds__(256) void agent_sum_explore_kernel(FlexAgentSumArgs
     if (tid >= a.n_envs * a.act_dim) return;
     const int e = tid / a.act_dim, k = tid - e * a.act_dim;
     const int n = a.n_agents, ad = a.act_dim;
-    const float* m = a.means + (int64_t)e * n * ad + k;
-    float s = m[0];
-    for (int i = 1; i < n; ++i) s = __fadd_rn(s, m[i * ad]);                            // ((m0 + m1) + m2) + ...
+    const int64_t at = (int64_t)e * n * ad + k;
     // eps == NULL: no exploration — the agent-summed mean itself goes to every agent (util.py:75-77 behind matd3.py:94-96)
-    const float y = a.eps ? tanhf(__fadd_rn(s, __fmul_rn(a.eps[tid], a.std[k]))) : s;  // tanh(loc + eps * scale)
-    const float span = a.act_high - a.act_low;
-    const float c = clamp_nan(y, a.act_low, a.act_high);                               // th.clamp: a NaN action stays NaN
-    const float ev = __fadd_rn(__fmul_rn(__fmul_rn(0.5f, __fadd_rn(c, 1.0f)), span), a.act_low);
-    float* ao = a.action + (int64_t)e * n * ad + k;
-    for (int i = 0; i < n; ++i) ao[i * ad] = y;
-    if (a.env_action) {
-        float* eo = a.env_action + (int64_t)e * n * ad + k;
-        for (int i = 0; i < n; ++i) eo[i * ad] = ev;
-    }
+    agent_sum_select(a.means + at, n, ad, a.eps ? a.eps + tid : nullptr, a.eps ? a.std + k : nullptr, a.act_low, a.act_high,
+                     a.action + at, a.env_action ? a.env_action + at : nullptr);
 }
 
 extern "C" int flexnet_agent_sum_explore(const FlexAgentSumArgs* a, void* stream) {

@@ -284,6 +284,27 @@ class VecFlexProvisionEnv:
                                                   C.byref(sf) if sf is not None else None, _stream()),
                    "flexenv_rollout_burst")
 
+    def rollout_burst_summed(self, actor_args, steps, obs_ring, eps, std, act_low, act_high):
+        """``steps`` vector steps of policy + agent-summed action selection + environment in ONE launch (include/flexenv.h:
+        flexenv_rollout_burst_summed): ``actor_args`` as for ``rollout_burst`` (the means-only ring-mode policy call), ``eps``
+        [steps, N, act_dim] float32 standard-normal draws (step t of the launch reads ``eps[t]``), ``std`` [act_dim] float32 —
+        both contiguous device tensors — and the action range of translate_action."""
+        for name, t, numel in (("eps", eps, int(steps) * self.n_envs * 4), ("std", std, 4)):
+            # (an env built with device="cuda" has no index: its tensors are on cuda:0)
+            if t is not None and not (t.is_cuda and t.device.index == (self.device.index or 0) and t.dtype == torch.float32
+                                      and t.is_contiguous()
+                                      and t.numel() == numel):
+                raise ValueError(f"rollout_burst_summed: `{name}` must be a contiguous float32 device tensor of {numel} elements")
+        sm = _lib.FlexBurstSummed()
+        sm.eps = None if eps is None else eps.data_ptr()           # (None: the library's refusal, not a Python error)
+        sm.std = None if std is None else std.data_ptr()
+        sm.act_low, sm.act_high = float(act_low), float(act_high)
+        self.calls += int(steps)
+        _lib.check(self.lib.flexenv_rollout_burst_summed(self.handle, C.byref(actor_args), _ptr(self.reward), _ptr(self.done),
+                                                         _ptr(self.info), _ptr(self.failed), _ptr(obs_ring), int(steps),
+                                                         C.byref(sm), _stream()),
+                   "flexenv_rollout_burst_summed")
+
     TEST_TRACE = (("actions", torch.float32), ("v", torch.float64), ("agent", torch.float64), ("row", torch.int32),
                   ("reward", torch.float64), ("info", torch.float64), ("flags", torch.uint8))
 

@@ -143,6 +143,15 @@ class RolloutGraph:
             if self.safe:
                 self.burst_adjusted = th.zeros(N, 4 * n, dtype=th.float64, device=dev)
                 self.burst_safe_env_act = th.zeros(N, 4 * n, device=dev)
+        # The same launch for the agent-summed algorithms (include/flexenv.h: flexenv_rollout_burst_summed): the policy hands
+        # on its means, each wavefront sums those of its own two environments and selects the one action (the arithmetic of
+        # flexnet_agent_sum_explore) in front of its step.  The draws stay in torch's generator: one [k, N, 1, a] call per
+        # burst of k steps.  FLEX_SUMMED_BURST=0: three launches per step, graphs of 16 / 8 / 4 / 2 bodies.
+        self.summed_burst = bool(self.summed_sink and n <= 5 and o % 4 == 0 and a == 4
+                                 and hasattr(getattr(env, "vec", env), "rollout_burst_summed")
+                                 and os.environ.get("FLEX_SUMMED_BURST", "1") != "0")
+        if self.summed_burst:
+            self.means_buf = th.zeros(N * n, a, device=dev)
         self._configure_env()
 
     def _configure_env(self):
@@ -196,6 +205,8 @@ class RolloutGraph:
 
     @property
     def fused_burst(self):
+        if self.summed_burst:                           # (its draws are torch's own: torch_noise gates the plain form only)
+            return True
         return (self.burst_launch and self.sink_active and not self._torch_noise
                 and not (self.safe and self.model.intended_actions))       # (that routing transposes in torch)
 
@@ -320,13 +331,32 @@ class RolloutGraph:
         if self.summed and self.summed_sink:
             with th.no_grad():
                 buf = self.buf
+                outs, hook = dict(hidden_out=self.hid_buf), {}
+                if burst:
+                    # policy, action selection and environment for `burst` steps in one persistent launch (include/flexenv.h:
+                    # flexenv_rollout_burst_summed): the policy call's arguments, handed to the env's launch instead of its
+                    # own, and the draws of all its steps from ONE call of the function summed_exploration draws a step's from
+                    import torch.distributions.normal as tdn      # (looked up at call time, as summed_exploration does)
+                    eps = tdn._standard_normal((burst, N, 1, m.act_dim), th.float32, self.act_buf.device)
+                    vec = env.vec if hasattr(env, "vec") else env
+                    outs.update(means=self.means_buf)
+
+                    def launch(args):
+                        # (what the selection phase writes: the action the sink files, the action the step reads)
+                        args.action, args.env_action = self.act_buf.data_ptr(), self.env_act_buf.data_ptr()
+                        vec.rollout_burst_summed(args, burst, buf.row_ring, eps, m.summed_std(eps.device), m.args.action_low,
+                                                 m.args.action_high)
+
+                    hook = dict(ring_slabs=buf.slabs, launch=launch)
                 out = fused_actor_forward(m.policy_dicts[0], self._obs,
                                           buf.hid_ring[0].view(N, m.n_, m.hid_dim), m.n_, m.args.agent_id,
                                           ring_cursor=buf.cursor, obs_slab_stride=0, obs_source=self.obs_src,
                                           hid_slab_stride=buf.hid_ring.stride(0), cursor_out=buf.cursor[1:],
-                                          out=dict(hidden_out=self.hid_buf))
+                                          out=outs, **hook)
                 if out is None:
                     raise RuntimeError("the fused actor kernel declined a configuration RolloutGraph.summed_sink admitted")
+                if burst:
+                    return
                 summed_exploration(m, out[0].view(N, m.n_, m.act_dim), env_action=self.env_act_buf,
                                    action_out=self.act_buf.view(N, m.n_, m.act_dim))
                 env.step(self.env_act_buf, fuse_obs=True, auto_reset=True, obs_ring=buf.row_ring, replay_sink=True)
