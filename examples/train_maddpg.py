@@ -71,6 +71,9 @@ def main():
     ap.add_argument("--batch-scale", type=int, default=None)
     ap.add_argument("--gaussian-policy", action="store_true",
                     help="learned log-std heads (gaussian_policy: True, LOG_STD_MIN 0.0 / LOG_STD_MAX 0.5 of default.yaml)")
+    ap.add_argument("--gauss-burst", action="store_true",
+                    help="with --gaussian-policy and an agent-summed --alg: the rollout as one persistent launch per run of "
+                         "steps, log-std head included (FLEX_GAUSS_BURST=1, flexenv_rollout_burst_summed_gauss)")
     ap.add_argument("--agent-type", choices=["rnn", "mlp"], default="rnn",
                     help="agent_type of default.yaml: the recurrent agent, or the MLP agent on the stacked history (csrc/actor_mlp.hip)")
     ap.add_argument("--unshared", action="store_true",
@@ -80,6 +83,11 @@ def main():
                          "episodes gathered by csrc/episodes.hip (ippo / mappo / coma: the on-policy triple batch_size = "
                          "replay_buffer_size = behaviour_update_freq, in blocks)")
     a = ap.parse_args()
+    if a.gauss_burst:
+        if not a.gaussian_policy or a.alg not in ("matd3", "iddpg", "facmaddpg", "sqddpg", "ippo", "mappo", "coma"):
+            ap.error("--gauss-burst: needs --gaussian-policy and an agent-summed --alg "
+                     "(matd3, iddpg, facmaddpg, sqddpg, ippo, mappo, coma)")
+        os.environ["FLEX_GAUSS_BURST"] = "1"             # (read when the trainer builds its RolloutGraph)
     if a.unshared and a.alg == "matd3":
         ap.error("--unshared: MATD3 is built for shared_params (default.yaml:26)")
 
@@ -165,6 +173,12 @@ def main():
                "stat": {k: (float(v) if not isinstance(v, float) else v) for k, v in stat.items()},
                # fused paths that declined a call and ran their PyTorch composition instead (util.note_fallback): none expected
                "fallbacks": dict(FALLBACKS)}
+        if a.gauss_burst:                   # asked for: the run must have rolled out through it
+            rg = getattr(trainer.behaviour_net, "_rollout_graph", None)
+            out["gauss_burst"] = bool(rg is not None and rg.gauss_burst and rg.fused_burst)
+            if not out["gauss_burst"]:
+                raise SystemExit("--gauss-burst: this configuration did not roll out through the one-launch burst "
+                                 "(learner.RolloutGraph.gauss_burst)")
         if a.agent_type != "rnn":
             out["agent_type"] = a.agent_type
         if a.unshared:

@@ -308,6 +308,31 @@ typedef struct {
 int flexenv_rollout_burst_summed(FlexEnv* env, const FlexActorArgs* actor, double* reward, uint8_t* done,
                                  double* info, uint8_t* failed, float* obs_ring, int32_t steps,
                                  const FlexBurstSummed* summed, void* stream);
+/* The same burst for a shared RNNAgentGaussian actor (gaussian_policy: True; rnn_agent_gaussian.py:37-39 under matd3.py:92-97 /
+ * iddpg.py:66-71): block, groups, tiles, hand-overs, ring and cursor cells are flexenv_rollout_burst_summed's.  actor->fc2_w /
+ * fc2_b are the `mean` head.  The policy phase evaluates the `log_std` head in the same sixteen matrix steps — its [4, 64]
+ * weights and bias sit in columns 4-7 of the fc2 image in LDS — and stores
+ * log_std = log_std_min + 0.5 (log_std_max - log_std_min) (tanhf(W h + b) + 1) to `log_stds` next to actor->means; means and the
+ * new hidden state are those of flexenv_rollout_burst_summed on the same weights, bit for bit.  The selection phase is
+ * flexnet_gauss_sum_explore's arithmetic, rounding for rounding (one device function serves both): means and log-stds summed in
+ * agent order in fp32, y = tanhf(s + eps * expf(ls)) with product and sum rounded separately, the NaN-preserving clamp and the
+ * four separately rounded operations of translate_action; y to every agent's row of actor->action, the translated value to
+ * every agent's row of actor->env_action.  No noise is generated in the kernel: step t reads eps[t].  actor->rng_state, noise and
+ * std are ignored.  The finish launch moves the two cursor cells and nothing else.
+ * FLEX_EINVAL (before any HIP call): everything flexenv_rollout_burst_summed refuses about the env, the sink, the ring, the
+ * cursor cells and the actor's shapes; `gauss` or any of its four pointers missing; !(log_std_max >= log_std_min);
+ * !(act_high >= act_low); act_dim != 4; n_agents > 5; steps >= slabs; a sink with an aux_counter. */
+typedef struct {
+    const float* eps;         /* dev [steps, N, act_dim] standard-normal draws; step t of the launch reads row t */
+    const float* log_std_w;   /* dev [act_dim, 64]: the log_std head's weight */
+    const float* log_std_b;   /* dev [act_dim]: its bias */
+    float* log_stds;          /* dev [N * n_agents, act_dim], out: the last step's log-stds, next to actor->means */
+    float log_std_min, log_std_max;
+    float act_low, act_high;
+} FlexBurstSummedGauss;
+int flexenv_rollout_burst_summed_gauss(FlexEnv* env, const FlexActorArgs* actor, double* reward, uint8_t* done,
+                                       double* info, uint8_t* failed, float* obs_ring, int32_t steps,
+                                       const FlexBurstSummedGauss* gauss, void* stream);
 /* One TEST-mode episode per environment (madrl/models/model.py:269-306 for every environment at once) in ONE persistent
  * launch, with a per-episode record.  Block b owns environments 16 b .. 16 b + 15 as in flexenv_rollout_burst; the launch
  * starts from the state flexenv_reset leaves and every one of its `steps` steps is

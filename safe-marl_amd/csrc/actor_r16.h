@@ -496,8 +496,21 @@ struct __attribute__((aligned(16))) ActorLds16B {
     int gsync[2];                                // arrivals of each group's wavefronts (monotonic)
 };
 
-// the LDS image actor_r16_body stages (same values in the same places), without its choreography: once per burst
-__device__ __forceinline__ void r16_stage_simple(const FlexActorArgs& a, ActorLds16B& s, int tid) {
+// The log-std head of a Gaussian actor next to the burst's policy (LOGSTD below; rnn_agent_gaussian.py:37-39): the head's
+// weights [act_dim, 64] and bias, the range of log_std, and where the policy phase stores it ([rows, act_dim], next to means).
+struct R16LogStd {
+    const float* w;
+    const float* b;
+    float* out;
+    float lo, hi;
+};
+
+// the LDS image actor_r16_body stages (same values in the same places), without its choreography: once per burst.
+// LOGSTD: columns act_dim .. 2 act_dim - 1 of the fc2 image (zero otherwise) and b2[act_dim .. 2 act_dim - 1] take the log-std
+// head (2 act_dim <= FLEXNET_MAX_ACT: the caller's check) — same LDS, same sixteen MFMA steps; a column of the product depends
+// on its own column of the image alone, so the means' accumulators see the same operands as without the head.
+template <bool LOGSTD = false>
+__device__ __forceinline__ void r16_stage_simple(const FlexActorArgs& a, ActorLds16B& s, int tid, const R16LogStd* ls = nullptr) {
     const int od = a.obs_dim, na = a.n_agents, ad = a.act_dim;
     const int ld1 = od + (a.agent_id ? na : 0);
     const int nq = (od + 15) >> 4;
@@ -513,7 +526,10 @@ __device__ __forceinline__ void r16_stage_simple(const FlexActorArgs& a, ActorLd
     }
     for (int idx = tid; idx < 16 * HID; idx += 64 * R16_W) {
         const int o = idx / HID, k = idx % HID;
-        s.w2p[k * R16_P2 + o] = o < ad ? a.fc2_w[o * HID + k] : 0.0f;
+        float v = o < ad ? a.fc2_w[o * HID + k] : 0.0f;
+        if constexpr (LOGSTD)
+            if (o >= ad && o < 2 * ad) v = ls->w[(o - ad) * HID + k];
+        s.w2p[k * R16_P2 + o] = v;
     }
     if (tid < HID) {
         s.gb[tid] = a.b_ih[tid] + a.b_hh[tid];
@@ -530,6 +546,8 @@ __device__ __forceinline__ void r16_stage_simple(const FlexActorArgs& a, ActorLd
         s.w1id[tid] = (a.agent_id && ag < na) ? a.fc1_w[u * ld1 + od + ag] : 0.0f;
     }
     if (tid < ad) s.b2[tid] = a.fc2_b[tid];
+    if constexpr (LOGSTD)
+        if (tid >= ad && tid < 2 * ad) s.b2[tid] = ls->b[tid - ad];
 }
 
 // TEST (flexenv_test_episodes): the policy in test mode — tanh(mean) (utils/util.py:79-82), translate_action (util.py:125-128):
@@ -539,10 +557,15 @@ __device__ __forceinline__ void r16_stage_simple(const FlexActorArgs& a, ActorLd
 // policy that only hands on its means: no noise is drawn (wavefront 3 idles through the policy phase) and rng_state is not
 // read; means and the new hidden state are written as ever, action / env_action are left to the environment phase's
 // agent-summed selection.  env_step(slab or step, step): the second argument is the step's index within the launch.
-template <bool TEST = false, bool NOISE = !TEST, typename EnvStep, typename Mark>
+// LOGSTD (flexenv_rollout_burst_summed_gauss; with NOISE false): the actor is an RNNAgentGaussian — the lanes that end up with
+// columns act_dim .. 2 act_dim - 1 of the fc2 product (r16_stage_simple<true>) turn them into
+// log_std = lo + 0.5 (hi - lo) (tanhf(u) + 1), the precise tanhf of csrc/gauss.hip, and store it to ls->out [rows, act_dim];
+// means and hidden state come out as without it, bit for bit.
+template <bool TEST = false, bool NOISE = !TEST, bool LOGSTD = false, typename EnvStep, typename Mark>
 __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds16B& s, const int n_steps, EnvStep&& env_step,
-                                                Mark&& mark) {
+                                                Mark&& mark, const R16LogStd* ls = nullptr) {
     static_assert(!(TEST && NOISE), "test mode draws no noise");
+    static_assert(!LOGSTD || (!TEST && !NOISE), "the log-std head rides on the means-only ring form");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 15, g = lane >> 4;
     const int grp = wave >> 2, w = wave & 3;
@@ -571,7 +594,7 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
             }
         }
     };
-    r16_stage_simple(a, s, tid);
+    r16_stage_simple<LOGSTD>(a, s, tid, ls);
     if (NOISE && w == 3) draw(rng_step);
     if (tid < 2) s.gsync[tid] = 0;
     __syncthreads();
@@ -628,7 +651,7 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
 #pragma unroll
             for (int st = 0; st < 16; ++st)
                 mo = MFMA16(w2_l[(16 * (st >> 2) + (st & 3)) * R16_P2], hnew[st >> 2][st & 3], mo);
-            if (live && 4 * g < ad) {
+            if (live && 4 * g < (LOGSTD ? 2 * ad : ad)) {
                 float zr[4] = {0.0f, 0.0f, 0.0f, 0.0f};
                 if constexpr (NOISE) {
                     const float4 zv = *reinterpret_cast<const float4*>(&s.noise[(rng_step + step) & 1][grp][w][j][4 * g]);
@@ -646,6 +669,9 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
                             a.action[at] = act;
                             a.env_action[at] = 0.5f * (clamp_nan(act, a.action_low, a.action_high) + 1.0f) * (a.action_high - a.action_low) + a.action_low;
                         }
+                    } else if constexpr (LOGSTD) {
+                        if (k < 2 * ad)                                    // rnn_agent_gaussian.py:37-39, as csrc/gauss.hip forms it
+                            ls->out[(int64_t)row * ad + k - ad] = ls->lo + 0.5f * (ls->hi - ls->lo) * (tanhf(mo[r] + s.b2[k]) + 1.0f);
                     }
                 }
             }

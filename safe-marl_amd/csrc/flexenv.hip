@@ -1346,10 +1346,13 @@ struct BurstArgs {
     const float* eps;           // [n_steps, N, act_dim] standard-normal draws (torch's generator): step t reads row t
     const float* sum_std;       // [act_dim]
     float act_high;
+    // ... with a shared RNNAgentGaussian actor (flexenv_rollout_burst_summed_gauss): the policy phase also evaluates the log-std
+    // head into ls.out [rows, act_dim] (actor_r16_burst's LOGSTD) and the selection is gauss_sum_select on means and log-stds
+    R16LogStd ls;
 };
 
-// the burst's three forms
-enum { BURST_PLAIN = 0, BURST_SAFE = 1, BURST_SUMMED = 2 };
+// the burst's four forms
+enum { BURST_PLAIN = 0, BURST_SAFE = 1, BURST_SUMMED = 2, BURST_SUMMED_GAUSS = 3 };
 
 // (Inlined again since the policy became actor_r16_burst, which keeps almost nothing live across the step: 12 spilled
 //  registers, none in the step's loops, against the 64 the called version saved and restored per step — 34.4 -> 31.8 us per
@@ -1378,7 +1381,7 @@ __device__ __forceinline__ void flex_burst_env_step(int slab_v, int step_v, unsi
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         actions = b.safe_env_action;
     }
-    if constexpr (MODE == BURST_SUMMED) {
+    if constexpr (MODE == BURST_SUMMED || MODE == BURST_SUMMED_GAUSS) {
         // lane map of flex_test_env_step<2>: lane (environment of the wavefront, action component); the means of both
         // environments were stored by this group's policy tiles, a rendezvous ago
         const int na = b.k.cfg.n_agents, ad = b.act.act_dim, lane = threadIdx.x & 63;      // (ad == 4: checked on the host)
@@ -1386,8 +1389,12 @@ __device__ __forceinline__ void flex_burst_env_step(int slab_v, int step_v, unsi
         const int env = 2 * wave + lane / ad, k = lane % ad;
         if (lane < 2 * ad && env < b.k.n_envs) {
             const int64_t at = (int64_t)env * na * ad + k;
-            agent_sum_select(b.act.means + at, na, ad, b.eps + ((int64_t)t * b.k.n_envs + env) * ad + k, b.sum_std + k, b.act_low,
-                             b.act_high, b.act.action + at, b.act.env_action + at);
+            if constexpr (MODE == BURST_SUMMED_GAUSS)      // (the log-stds: stored next to the means by the same tiles)
+                gauss_sum_select(b.act.means + at, b.ls.out + at, na, ad, b.eps[((int64_t)t * b.k.n_envs + env) * ad + k], b.act_low,
+                                 b.act_high, b.act.action + at, b.act.env_action + at);
+            else
+                agent_sum_select(b.act.means + at, na, ad, b.eps + ((int64_t)t * b.k.n_envs + env) * ad + k, b.sum_std + k, b.act_low,
+                                 b.act_high, b.act.action + at, b.act.env_action + at);
         }
         // (this wavefront's own stores, read back by its own step and sink: complete before the loads go out)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1404,20 +1411,20 @@ __device__ __forceinline__ void flex_rollout_burst_body(const BurstArgs& b, Acto
     auto env_step = [&](int64_t slab, int step) {
         flex_burst_env_step<NA_CAP, MODE>((int)slab, step, (unsigned)kb, (unsigned)(kb >> 32));
     };
-    constexpr bool NOISE = MODE != BURST_SUMMED;
+    constexpr bool NOISE = MODE != BURST_SUMMED && MODE != BURST_SUMMED_GAUSS, LOGSTD = MODE == BURST_SUMMED_GAUSS;
 #ifdef FLEX_STAMPS
     // diagnostic build: phase boundaries of the LAST step, per wavefront, in slots 8-12 of its first environment's row
     const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * R16_W + (threadIdx.x >> 6));
-    actor_r16_burst<false, NOISE>(b.act, s, b.n_steps, env_step, [&](int slot, int step) {
+    actor_r16_burst<false, NOISE, LOGSTD>(b.act, s, b.n_steps, env_step, [&](int slot, int step) {
         unsigned long long t;
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
         __builtin_amdgcn_sched_barrier(0);
         if (b.k.stamps && (threadIdx.x & 63) == 0 && 2 * wave < b.k.n_envs && step == b.n_steps - 1)
             b.k.stamps[(int64_t)(2 * wave) * 16 + slot] = t;
-    });
+    }, &b.ls);
 #else
-    actor_r16_burst<false, NOISE>(b.act, s, b.n_steps, env_step, [](int, int) {});
+    actor_r16_burst<false, NOISE, LOGSTD>(b.act, s, b.n_steps, env_step, [](int, int) {}, &b.ls);
 #endif
 }
 
@@ -1438,6 +1445,16 @@ void flex_rollout_burst_kernel(BurstArgs b) {
     flex_rollout_burst_body<NA_CAP, BURST_SUMMED>(b, s);
 }
 }  // namespace summed
+
+// The fourth form (flexenv_rollout_burst_summed_gauss), again under a name of its own.
+namespace summed_gauss {
+template <int NA_CAP>
+__global__ __launch_bounds__(64 * R16_W)
+void flex_rollout_burst_kernel(BurstArgs b) {
+    __shared__ ActorLds16B s;
+    flex_rollout_burst_body<NA_CAP, BURST_SUMMED_GAUSS>(b, s);
+}
+}  // namespace summed_gauss
 
 // the cells a burst leaves as `steps` single steps would: cell 0 = the slab the policy reads next, cell 1 = the slab the last
 // step filed into, the noise stream's step counter advanced
@@ -2040,6 +2057,7 @@ static BurstArgs burst_args(FlexEnv* e, const FlexActorArgs& p, double* reward, 
     b.safety = 0; b.s_p = b.s_q = b.beta = nullptr; b.v_min = b.v_max = b.rho = 0.0; b.adjusted = nullptr; b.safe_env_action = nullptr;
     b.act_low = b.act_span = b.act_high = 0.0f;
     b.eps = b.sum_std = nullptr;
+    b.ls.w = b.ls.b = nullptr; b.ls.out = nullptr; b.ls.lo = b.ls.hi = 0.0f;
     return b;
 }
 
@@ -2098,6 +2116,37 @@ int flexenv_rollout_burst_summed(FlexEnv* e, const FlexActorArgs* actor, double*
     b.eps = summed->eps; b.sum_std = summed->std; b.act_low = summed->act_low; b.act_high = summed->act_high;
     if (burst_small_obs(e)) hipLaunchKernelGGL((summed::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_SMALL>), grid, block, 0, s, b);
     else hipLaunchKernelGGL((summed::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_LARGE>), grid, block, 0, s, b);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(flex_burst_finish_kernel, dim3(1), dim3(64), 0, s, const_cast<int64_t*>(p.cursor), p.cursor_out,
+                       (uint64_t*)nullptr, (int)steps, (int)e->obs_slabs);
+    HIP_TRY(hipGetLastError());
+    return FLEX_OK;
+}
+
+int flexenv_rollout_burst_summed_gauss(FlexEnv* e, const FlexActorArgs* actor, double* reward, uint8_t* done, double* info,
+                                       uint8_t* failed, float* obs_ring, int32_t steps, const FlexBurstSummedGauss* gauss,
+                                       void* stream) {
+    // every argument check comes before the first HIP call
+    if (!gauss || !gauss->eps || !gauss->log_std_w || !gauss->log_std_b || !gauss->log_stds ||
+        !(gauss->log_std_max >= gauss->log_std_min) || !(gauss->act_high >= gauss->act_low)) return FLEX_EINVAL;
+    // four controls per building: the selection's lane map, and the two heads' eight columns are the fc2 image's b2 slots; a
+    // block's sixteen environments are at most five policy tiles (read off the actor: no handle is followed yet)
+    static_assert(2 * 4 <= FLEXNET_MAX_ACT, "mean and log-std head side by side in b2");
+    if (!actor || actor->act_dim != 4 || actor->n_agents > 5) return FLEX_EINVAL;
+    if (!burst_config_ok(e, actor, reward, done, obs_ring, steps)) return FLEX_EINVAL;      // (steps >= slabs: there)
+    const FlexActorArgs& p = *actor;
+    // a sink with an aux_counter belongs to the in-kernel noise stream of the plain burst: the finish launch here moves the two
+    // cursor cells and nothing else
+    if (e->sink.aux_counter) return FLEX_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((e->n_envs + 15) / 16), block(64 * R16_W);
+    BurstArgs b = burst_args(e, p, reward, done, info, failed, obs_ring, steps);
+    b.act.rng_state = nullptr; b.act.noise = nullptr;           // (neither is read: the draws are gauss->eps)
+    b.eps = gauss->eps; b.act_low = gauss->act_low; b.act_high = gauss->act_high;
+    b.ls.w = gauss->log_std_w; b.ls.b = gauss->log_std_b; b.ls.out = gauss->log_stds;
+    b.ls.lo = gauss->log_std_min; b.ls.hi = gauss->log_std_max;
+    if (burst_small_obs(e)) hipLaunchKernelGGL((summed_gauss::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_SMALL>), grid, block, 0, s, b);
+    else hipLaunchKernelGGL((summed_gauss::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_LARGE>), grid, block, 0, s, b);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(flex_burst_finish_kernel, dim3(1), dim3(64), 0, s, const_cast<int64_t*>(p.cursor), p.cursor_out,
                        (uint64_t*)nullptr, (int)steps, (int)e->obs_slabs);

@@ -26,16 +26,14 @@
 #include "flex_launch.h"
 #include "flex_mfma_tile.h"
 #include "flex_nan.h"
+#include "agent_sum.h"
 
 #define GAUSS_THREADS 256
 #define GAUSS_ROWS (GAUSS_THREADS / 2)       // 32 rows per wavefront
 #define GAUSS_MAX_ROWS ((int64_t)1 << 30)
 
-// translate_action (util.py:125-128) with the roundings of scale_action's tensor ops; a NaN action stays NaN, as through th.clamp
-__device__ __forceinline__ float gauss_env_action(float y, float lo, float hi) {
-    const float c = clamp_nan(y, lo, hi);
-    return __fadd_rn(__fmul_rn(__fmul_rn(0.5f, __fadd_rn(c, 1.0f)), hi - lo), lo);
-}
+// (gauss_env_action — translate_action, util.py:125-128 — and the agent-summed selection live in agent_sum.h: the rollout burst
+//  of csrc/flexenv.hip runs the same bodies)
 
 // ---- the head, both ways: ONE body each, a template over the argument struct (A = FlexGaussHeadArgs or, shared_params: False,
 // FlexGaussHeadUnsharedArgs).  The forms differ in the row map, in where W and b come from and in the exploration epilogue,
@@ -262,21 +260,8 @@ __global__ __launch_bounds__(256) void gauss_sum_explore_kernel(FlexGaussSumArgs
     const int64_t e = tid / ad;
     const int k = (int)(tid - e * ad);
     const int64_t at = e * n * ad + k;
-    const float* m = a.means + at;
-    const float* l = a.log_stds + at;
-    float s = m[0], ls = l[0];
-    for (int i = 1; i < n; ++i) {                                                        // ((x0 + x1) + x2) + ...
-        s = __fadd_rn(s, m[i * ad]);
-        ls = __fadd_rn(ls, l[i * ad]);
-    }
-    const float y = tanhf(__fadd_rn(s, __fmul_rn(a.eps[tid], expf(ls))));              // tanh(loc + eps * scale)
-    float* ao = a.action + at;
-    for (int i = 0; i < n; ++i) ao[i * ad] = y;
-    if (a.env_action) {
-        const float ev = gauss_env_action(y, a.act_low, a.act_high);
-        float* eo = a.env_action + at;
-        for (int i = 0; i < n; ++i) eo[i * ad] = ev;
-    }
+    gauss_sum_select(a.means + at, a.log_stds + at, n, ad, a.eps[tid], a.act_low, a.act_high, a.action + at,
+                     a.env_action ? a.env_action + at : nullptr);
 }
 
 extern "C" int flexnet_gauss_sum_explore(const FlexGaussSumArgs* a, void* stream) {

@@ -305,6 +305,31 @@ class VecFlexProvisionEnv:
                                                          C.byref(sm), _stream()),
                    "flexenv_rollout_burst_summed")
 
+    def rollout_burst_summed_gauss(self, actor_args, steps, obs_ring, eps, log_std_w, log_std_b, log_stds, log_std_min,
+                                   log_std_max, act_low, act_high):
+        """``rollout_burst_summed`` for a shared RNNAgentGaussian actor (include/flexenv.h: flexenv_rollout_burst_summed_gauss):
+        ``actor_args`` carry the ``mean`` head as fc2; ``log_std_w`` [act_dim, 64] and ``log_std_b`` [act_dim] are the
+        ``log_std`` head, ``log_stds`` [N * n_agents, act_dim] receives the last step's log-stds, ``eps`` [steps, N, act_dim] are
+        the standard-normal draws — all contiguous float32 device tensors — with the range of log_std and of the action."""
+        rows = self.n_envs * self.n_agents
+        for name, t, numel in (("eps", eps, int(steps) * self.n_envs * 4), ("log_std_w", log_std_w, 4 * 64),
+                               ("log_std_b", log_std_b, 4), ("log_stds", log_stds, rows * 4)):
+            # (an env built with device="cuda" has no index: its tensors are on cuda:0)
+            if t is not None and not (t.is_cuda and t.device.index == (self.device.index or 0) and t.dtype == torch.float32
+                                      and t.is_contiguous()
+                                      and t.numel() == numel):
+                raise ValueError(f"rollout_burst_summed_gauss: `{name}` must be a contiguous float32 device tensor of {numel} elements")
+        sg = _lib.FlexBurstSummedGauss()
+        for name, t in (("eps", eps), ("log_std_w", log_std_w), ("log_std_b", log_std_b), ("log_stds", log_stds)):
+            setattr(sg, name, None if t is None else t.data_ptr())      # (None: the library's refusal, not a Python error)
+        sg.log_std_min, sg.log_std_max = float(log_std_min), float(log_std_max)
+        sg.act_low, sg.act_high = float(act_low), float(act_high)
+        self.calls += int(steps)
+        _lib.check(self.lib.flexenv_rollout_burst_summed_gauss(self.handle, C.byref(actor_args), _ptr(self.reward),
+                                                               _ptr(self.done), _ptr(self.info), _ptr(self.failed),
+                                                               _ptr(obs_ring), int(steps), C.byref(sg), _stream()),
+                   "flexenv_rollout_burst_summed_gauss")
+
     TEST_TRACE = (("actions", torch.float32), ("v", torch.float64), ("agent", torch.float64), ("row", torch.int32),
                   ("reward", torch.float64), ("info", torch.float64), ("flags", torch.uint8))
 

@@ -69,7 +69,8 @@ class RolloutGraph:
         self.std = float(model.args.fixed_policy_std)
         # gaussian_policy: the standard deviation is an output of the policy, per row — the kernels that carry ONE constant std
         # (the actor kernel's exploration epilogue and everything built on it: ring I/O, sink, burst) are not used; the
-        # general bodies draw from the log-stds Model.policy returns and neither ``std`` nor ``summed_std`` is consulted
+        # general bodies draw from the log-stds Model.policy returns and neither ``std`` nor ``summed_std`` is consulted.  (The one
+        # exception is opt-in: ``gauss_burst`` below, the agent-summed burst with the log-std head in its policy phase.)
         self.gaussian = bool(model.args.gaussian_policy)
         self.graph = None
         self.bursts = {}                                       # k -> graph of k bodies (run())
@@ -123,11 +124,21 @@ class RolloutGraph:
         # MATD3 / IDDPG with the one-launch action selection (`summed`): the same ring I/O and sink — policy kernel (slab at the
         # cursor -> means, new hidden state), agent_sum_explore_kernel (-> the action the replay keeps, the env's action), env
         # step (files the transition): three launches, no pack kernel, the observation written once (round 3)
-        self.summed_sink = bool(self.summed and self.cursor_stepped and self.rows_capable
-                                and hasattr(env, "set_replay_sink") and n * a <= 32 and n * h <= 384
-                                and two_per_wave and h == 64 and o <= 144 and not self.gaussian
-                                and os.environ.get("FLEX_SUMMED_SINK", "1") != "0")
-        if self.sink or self.summed_sink:
+        summed_sink_shape = bool(self.summed and self.cursor_stepped and self.rows_capable
+                                 and hasattr(env, "set_replay_sink") and n * a <= 32 and n * h <= 384
+                                 and two_per_wave and h == 64 and o <= 144
+                                 and os.environ.get("FLEX_SUMMED_SINK", "1") != "0")
+        self.summed_sink = bool(summed_sink_shape and not self.gaussian)
+        # gaussian_policy with a shared RNNAgentGaussian (include/flexenv.h: flexenv_rollout_burst_summed_gauss): the summed
+        # burst below with the log-std head evaluated in the policy phase and per-sample log-stds in the selection — the env
+        # configured as for `summed_sink`, every vector step (a single one too) through the one launch.  Off unless
+        # FLEX_GAUSS_BURST=1: the general body stays what a Gaussian RolloutGraph runs by default.
+        self.gauss_burst = bool(summed_sink_shape and self.gaussian and isinstance(model.policy_dicts[0], RNNAgentGaussian)
+                                and n <= 5 and o % 4 == 0 and a == 4
+                                and hasattr(getattr(env, "vec", env), "rollout_burst_summed_gauss")
+                                and os.environ.get("FLEX_SUMMED_BURST", "1") != "0"
+                                and os.environ.get("FLEX_GAUSS_BURST", "0") == "1")
+        if self.sink or self.summed_sink or self.gauss_burst:
             self.act_buf = th.zeros(N * n, a, device=dev)
             self.hid_buf = th.zeros(N * n, h, device=dev)
             self.acc = th.zeros(N, 10, dtype=th.float64, device=dev)
@@ -150,8 +161,10 @@ class RolloutGraph:
         self.summed_burst = bool(self.summed_sink and n <= 5 and o % 4 == 0 and a == 4
                                  and hasattr(getattr(env, "vec", env), "rollout_burst_summed")
                                  and os.environ.get("FLEX_SUMMED_BURST", "1") != "0")
-        if self.summed_burst:
+        if self.summed_burst or self.gauss_burst:
             self.means_buf = th.zeros(N * n, a, device=dev)
+        if self.gauss_burst:
+            self.log_stds_buf = th.zeros(N * n, a, device=dev)
         self._configure_env()
 
     def _configure_env(self):
@@ -173,7 +186,8 @@ class RolloutGraph:
             env.set_step_counter(None)                      # the env step sets cursor[0] itself in this mode
             env.set_obs_ring(buf.cursor[1:], row_stride, buf.slabs)
             env.set_replay_sink(self.act_buf, self.hid_buf, buf.small_ring, buf.hid_ring, self.acc, cursor_out=buf.cursor[0:1],
-                                aux_counter=None if (self._torch_noise or self.summed_sink) else self.rng_state[1:2])
+                                aux_counter=None if (self._torch_noise or self.summed_sink or self.gauss_burst)
+                                else self.rng_state[1:2])
         else:
             env.set_step_counter(buf.cursor[1:], buf.slabs)
             if self.ring_active:
@@ -201,11 +215,11 @@ class RolloutGraph:
 
     @property
     def sink_active(self):
-        return (self.sink and self.fast) or self.summed_sink
+        return (self.sink and self.fast) or self.summed_sink or self.gauss_burst
 
     @property
     def fused_burst(self):
-        if self.summed_burst:                           # (its draws are torch's own: torch_noise gates the plain form only)
+        if self.summed_burst or self.gauss_burst:       # (their draws are torch's own: torch_noise gates the plain form only)
             return True
         return (self.burst_launch and self.sink_active and not self._torch_noise
                 and not (self.safe and self.model.intended_actions))       # (that routing transposes in torch)
@@ -227,7 +241,7 @@ class RolloutGraph:
     @property
     def ring_active(self):
         # (tests switch `fast` off to run the general body on the same object)
-        return (self.ring_io and self.fast) or self.summed_sink
+        return (self.ring_io and self.fast) or self.summed_sink or self.gauss_burst
 
     @property
     def obs(self):
@@ -328,6 +342,32 @@ class RolloutGraph:
                 if not self.sink_active:
                     self._pack(action, hid)
                 return
+        if self.gauss_burst:
+            with th.no_grad():
+                # policy with both heads, per-sample selection and environment for `burst` steps — or ONE step: the same launch,
+                # there is no second form — in one persistent launch (include/flexenv.h: flexenv_rollout_burst_summed_gauss);
+                # the draws of all its steps from ONE call of the function _summed_exploration_rows draws a step's from
+                import torch.distributions.normal as tdn      # (looked up at call time, as summed_exploration does)
+                buf, k = self.buf, burst or 1
+                agent = m.policy_dicts[0]
+                eps = tdn._standard_normal((k, N, 1, m.act_dim), th.float32, self.act_buf.device)
+                vec = env.vec if hasattr(env, "vec") else env
+
+                def launch(args):
+                    # (what the selection phase writes: the action the sink files, the action the step reads)
+                    args.action, args.env_action = self.act_buf.data_ptr(), self.env_act_buf.data_ptr()
+                    vec.rollout_burst_summed_gauss(args, k, buf.row_ring, eps, agent.log_std.weight, agent.log_std.bias,
+                                                   self.log_stds_buf, agent.args.LOG_STD_MIN, agent.args.LOG_STD_MAX,
+                                                   m.args.action_low, m.args.action_high)
+
+                out = fused_actor_forward(agent, self._obs, buf.hid_ring[0].view(N, m.n_, m.hid_dim), m.n_, m.args.agent_id,
+                                          ring_cursor=buf.cursor, obs_slab_stride=0, obs_source=self.obs_src,
+                                          hid_slab_stride=buf.hid_ring.stride(0), cursor_out=buf.cursor[1:],
+                                          out=dict(hidden_out=self.hid_buf, means=self.means_buf), ring_slabs=buf.slabs,
+                                          launch=launch)
+                if out is None:
+                    raise RuntimeError("the fused actor kernel declined a configuration RolloutGraph.gauss_burst admitted")
+            return
         if self.summed and self.summed_sink:
             with th.no_grad():
                 buf = self.buf
@@ -507,7 +547,7 @@ class RolloutGraph:
             self._hid.zero_()
             self.buf.begin_stream(first_obs)
         self._info_sum.zero_(); self._rew_sum.zero_(); self._fail_sum.zero_()
-        if self.sink or self.summed_sink:
+        if self.sink or self.summed_sink or self.gauss_burst:
             self.acc.zero_()
 
 
