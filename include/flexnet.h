@@ -452,9 +452,11 @@ int flexnet_agent_sum_explore(const FlexAgentSumArgs* args, void* stream);
  * registers, inputs straight from memory into MFMA operands):
  *     out[b, 0:64] = bias + x1[b, 0:k1] W[:, c1:c1+k1]^T + x2[b, 0:k2] W[:, c2:c2+k2]^T
  * x1 = every agent's observation ([b, n * obs_dim], row pitch ld1), x2 = every agent's action ([b, n * act_dim]; k2 = 0:
- * none), W = fc1.weight as stored ([64, ldw], the id columns between the two blocks are skipped).  k1, k2, ld1, ld2
- * multiples of 4, x1 / x2 / out 16-byte aligned, k1 + k2 <= 1280; otherwise FLEXNET_EUNSUPPORTED (the caller keeps the two
- * library GEMMs).  Bit-reproducible: every output is a fixed-order sum of four matrix-core accumulations. */
+ * none), W = fc1.weight as stored ([64, ldw], the id columns between the two blocks are skipped).  k1 a multiple of 8 (an
+ * 8-column input piece never straddles the two blocks); k2, ld1, ld2 multiples of 4; x1 / x2 / out 16-byte aligned; at most
+ * 768 input columns (k1 + k2 rounded up to a multiple of 32: the weights stay in the registers of eight wavefronts);
+ * otherwise FLEXNET_EUNSUPPORTED (the caller keeps the two library GEMMs), nothing launched.  Bit-reproducible: every output
+ * is a fixed-order sum of eight matrix-core accumulations. */
 typedef struct {
     int64_t rows;
     int32_t k1, k2, ld1, ld2, ldw, c1, c2, pad0;

@@ -17,7 +17,12 @@ The last part holds what has no module: csrc/ppo.hip (``gae_plain``, ``policy_lo
 log-std head (``gauss_head_plain``) and the stand-alone csrc/tdloss.hip (``td_run``) against the ``nets`` compositions of the same
 formulas in fp64, with their input families (``gae_families``, ``policy_families``, ``value_families``, ``gauss_families``,
 ``td_families``), the elements whose side of a clip end is arbitrary (``policy_clear_kinks``, ``value_keep``) and the one floor
-derived for them (``policy_loss_rounding``)."""
+derived for them (``policy_loss_rounding``).
+
+At the end, the two hand-written GEMMs: csrc/wgrad.hip (``wgrad_plain``, ``wgrad_families``, ``wgrad_floors``) and csrc/linear.hip
+(``linear2_plain``, ``linear2_families``, ``linear2_sum_rounding``), with the floor of a sum of products
+(``product_sum_rounding``; ``ordered_sum_rounding`` where the order of the addends matters, ``equal_addend_drift`` where they are
+all equal) and the shapes both their GPU tests and the CPU test run."""
 import copy
 from typing import NamedTuple
 
@@ -1171,3 +1176,255 @@ def policy_loss_rounding(inputs, eps_clip):
     sigma2 = ((w * adv * ratio).square() * var_x + ULP ** 2 * th.minimum(s1, s2).square()).sum() / float(adv.numel()) ** 2
     common2 = var_x.mean() * (w * adv * ratio).mean().square()
     return 3.0 * (sigma2 + common2).sqrt()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# csrc/wgrad.hip (flexnet_wgrad, flexnet_wgrad_batched) and csrc/linear.hip (flexnet_linear2): tests/test_wgrad_fp64_gpu.py and
+# tests/test_linear_fp64_gpu.py.  The plain products with their wrong evaluations, the floor of a sum of products, the families
+# (CPU generator: tests/test_fp64_budget_cpu.py holds the conditions on the very cases) and the shapes both files run.
+
+WGRAD_WRONG = ("drop_last_row", "drop_slab_tail", "colsum_per_chunk")
+LINEAR2_WRONG = ("drop_last_action_piece", "bias_twice")
+WGRAD_FAMILIES = ("plain", "offset", "constant", "halves", "zero_x", "zero_dy", "mixed")
+LINEAR2_FAMILIES = ("plain", "offset", "constant", "halves", "zero_x", "mixed")
+WGRAD_MIXED_OF = ("plain", "zero", "x30")
+CONSTANT_X = 1.3
+HALVES_X = 30.0
+# (k, m, n) per shape class (MT, NT) of csrc/wgrad.hip's dispatcher, on both sides of m = 32/33, 64/65 and n = 32/33, 64/65,
+# 160/161 (the column-chunk step of NT = 5) and 128/129 (that of NT = 2 under MT = 6)
+WGRAD_SHAPES = {
+    (1, 1): [(1, 1, 1), (9, 32, 32)],
+    (1, 2): [(65, 32, 33), (130, 4, 64)],
+    (1, 5): [(129, 32, 65), (515, 7, 161)],
+    (2, 1): [(63, 33, 32), (257, 64, 20)],
+    (2, 2): [(64, 64, 64), (2051, 33, 33)],
+    (2, 5): [(2049, 64, 160), (1003, 64, 321), (513, 40, 149)],
+    (6, 1): [(66, 65, 32), (2050, 192, 1)],
+    (6, 2): [(7, 192, 65), (2053, 100, 64), (300, 65, 129)],
+}
+WGRAD_CAP_SHAPE = (32777, 64, 20)       # 513 64-row slabs against the cap of 512: 72-row blocks, the last one of 17 rows
+WGRAD_CAP_FAMILIES = ("plain", "constant")
+WGRAD_TWO_SHAPES = ((2049, 64, 720, 20), (515, 64, 75, 161))       # (k, m, n | n2): the second input block, class [2, 5]
+WGRAD_TWO_FAMILIES = ("plain", "halves", "mixed")
+LINEAR2_ROWS = (1, 31, 32, 33, 97, 2049)
+LINEAR2_WIDTHS = ((8, 0), (8, 4), (144, 4), (248, 8), (256, 8), (432, 12), (504, 8), (512, 8), (720, 20), (736, 32), (768, 0))
+LINEAR2_ID_COLUMNS = 5
+
+
+def wgrad_chunks(m, n):
+    """The column chunks of csrc/wgrad.hip's shape class of an [m, n] result (nets._wgrad_class)."""
+    from safe_marl_amd.nets import _wgrad_class
+    return _wgrad_class(m, n)[2]
+
+
+def linear2_ss(k1, k2):
+    """The ``SS`` instantiation flexnet_linear2's entry point picks: 32-column super-steps per wavefront of eight."""
+    return ((k1 + k2 + 31) // 32 + 7) // 8
+
+
+def wgrad_plain(dy, x, wrong=None):
+    """(dW, db) = (dy^T x, the column sum of dy) in the dtype given.  ``wrong``: one of WGRAD_WRONG, the wrong evaluations
+    tests/test_fp64_budget_cpu.py has the budget reject — the sum over rows 0 .. k - 2 ("drop_last_row"); the rows past the last
+    multiple of 8 of every 64-row slab left out, which only a partial last slab has ("drop_slab_tail": a block that rounds its
+    rows DOWN to whole 8-row groups); the column sum times the column chunks of the shape class ("colsum_per_chunk": every chunk
+    accumulates it in the kernel and only chunk 0 may store)."""
+    assert wrong is None or wrong in WGRAD_WRONG, wrong
+    k = dy.shape[0]
+    if wrong == "drop_last_row":
+        dy, x = dy[:k - 1], x[:k - 1]
+    elif wrong == "drop_slab_tail":
+        r = th.arange(k, device=dy.device)
+        slab_rows = (k - 64 * (r // 64)).clamp(max=64)
+        keep = (r % 64) < (slab_rows // 8) * 8
+        dy, x = dy[keep], x[keep]
+    c, cs = dy.t() @ x, dy.sum(0)
+    if wrong == "colsum_per_chunk":
+        cs = cs * wgrad_chunks(dy.shape[1], x.shape[1])
+    return c, cs
+
+
+def linear2_plain(bias, x1, x2, W, c1, c2, wrong=None):
+    """include/flexnet.h's formula of flexnet_linear2 in the dtype given: bias + x1 W[:, c1:c1+k1]^T + x2 W[:, c2:c2+k2]^T (x2
+    None or of no columns: no second block).  ``wrong``: one of LINEAR2_WRONG — the last four action columns left out, the bias
+    added twice."""
+    assert wrong is None or wrong in LINEAR2_WRONG, wrong
+    k1 = x1.shape[1]
+    k2 = 0 if x2 is None else x2.shape[1]
+    out = bias + x1 @ W[:, c1:c1 + k1].t()
+    if wrong == "drop_last_action_piece":
+        k2 = max(k2 - 4, 0)
+    if k2 > 0:
+        out = out + x2[:, :k2] @ W[:, c2:c2 + k2].t()
+    if wrong == "bias_twice":
+        out = out + bias
+    return out
+
+
+def ordered_sum_rounding(segments):
+    """``row_sum_rounding`` for addends that are NOT exchangeable along the summed dimension: ``segments`` lists, in summation
+    order, (L, mean, variance) of runs of L addends each of which is exchangeable in itself.  The partial sum j addends into a
+    run that starts at the prefix P (the sum of the runs before it) has mean square (P + j m)^2 + j (1 - j / L) v; summed over
+    the run: L P^2 + P m L^2 + m^2 L^3 / 3 + v L^2 / 6.  One run is row_sum_rounding's own figure.  It is what a running fp32 sum
+    IN THIS ORDER does, the least accurate order a correct kernel may use: where the first half of the addends is +30 and the
+    second -30 the partial sums reach 15 N on a result of order sqrt(N), which the exchangeable form (partial sums of order
+    30 sqrt(N)) does not know — tests/test_fp64_budget_cpu.py's running sum failed the ``halves`` family with it."""
+    total, prefix = None, None
+    for L, mean, var in segments:
+        L = float(L)
+        p = th.zeros_like(mean) if prefix is None else prefix
+        s = L * p.square() + p * mean * L ** 2 + mean.square() * L ** 3 / 3.0 + var * L ** 2 / 6.0
+        total = s if total is None else total + s
+        prefix = p + L * mean
+    return 3.0 * ULP * (total / 3.0).sqrt()
+
+
+def equal_addend_drift(mean, var, n):
+    """What a running fp32 sum of ``n`` EQUAL addends c loses beyond ``row_sum_rounding``, element by element (zero where the
+    addends of an element are not all equal: ``var`` above 1e-12 of ``mean``^2).  row_sum_rounding takes the roundings of the
+    partial sums to be independent and adds them in quadrature: sqrt(n) / 3 ulps of the sum.  With equal addends they are not:
+    a partial sum inside the binade [2^b, 2^(b+1)) is a multiple of u_b = 2^(b-23), so S + c is rounded by the same amount
+    e_b(c), |e_b| <= u_b / 2, at every step inside that binade, and the 2^b / c steps of a binade add LINEARLY.  The binades
+    below the last one, 2^B <= n c, contribute a geometric series, 2^(2B-24) / (3 c), the last one (n c - 2^B) / c steps of
+    2^(B-24): in all 2^(B-24) (2^B / 3 + n c - 2^B) / c, up to n / 3 ulps of the sum.  tests/test_fp64_budget_cpu.py's running
+    sum of the ``constant`` family was off by 458 ulps at 2 049 rows (sqrt(n) / 3: 15) and by 2 440 at 32 777, inside this
+    figure (683 and 11 580).  A kernel that keeps a running sum per thread block over a few hundred rows and folds the blocks in
+    a tree stays far inside it; the row-order running sum is the least accurate order a correct kernel may use."""
+    c = mean.detach().double().abs()
+    s = float(n) * c
+    safe = s.clamp(min=TINY)
+    top = th.exp2(th.floor(th.log2(safe)))
+    drift = top * ULP * (top / 3.0 + (safe - top)) / c.clamp(min=TINY)
+    equal = (var <= 1e-12 * c.square()) & (c > 0)
+    return th.where(equal, drift, th.zeros_like(drift))
+
+
+def product_sum_rounding(dy, x, split=None):
+    """``row_sum_rounding`` of the addends dy[:, m, None] * x[:, None, n] of dW = dy^T x, [m, n], without materialising them: the
+    mean over rows of the addends is dy^T x / k and their second moment (dy^2)^T (x^2) / k, two fp64 GEMMs.  ``split``: the
+    rows [0, split) and [split, k) are two runs of ``ordered_sum_rounding`` (the ``halves`` family, whose order matters).  Elements
+    whose addends are all equal (the ``constant`` family) get ``equal_addend_drift`` on top."""
+    d, xx = dy.detach().double(), x.detach().double()
+    k = d.shape[0]
+    bounds = [0, k] if split is None or split <= 0 or split >= k else [0, int(split), k]
+    segments = []
+    for lo, hi in zip(bounds[:-1], bounds[1:]):
+        L = float(hi - lo)
+        mean = d[lo:hi].t() @ xx[lo:hi] / L
+        second = d[lo:hi].square().t() @ xx[lo:hi].square() / L
+        segments.append((L, mean, (second - mean.square()).clamp_(min=0.0)))
+    floor = ordered_sum_rounding(segments)
+    if len(segments) == 1:
+        floor = floor + equal_addend_drift(segments[0][1], segments[0][2], k)
+    return floor
+
+
+def linear2_sum_rounding(x1, x2, W, c1, c2, split=None):
+    """The same floor for flexnet_linear2's output [rows, 64]: element (r, u) is a sum over the N = k1 + k2 input columns of
+    x[r, c] W[u, column of c] (the bias is one more addend: one rounding, inside FLOOR_ULPS).  ``split``: a column count, as
+    ``product_sum_rounding``'s row count."""
+    k1 = x1.shape[1]
+    k2 = 0 if x2 is None else x2.shape[1]
+    xs = x1 if k2 == 0 else th.cat((x1, x2), 1)
+    ws = W[:, c1:c1 + k1] if k2 == 0 else th.cat((W[:, c1:c1 + k1], W[:, c2:c2 + k2]), 1)
+    return product_sum_rounding(xs.t(), ws.t(), split)
+
+
+def wgrad_floors(fam):
+    """(floor of dW [m, n], floor of the column sum [m]) of a ``wgrad_families`` case, element by element."""
+    dy, x = fam.inputs
+    d = dy.detach().double()
+    return (product_sum_rounding(dy, x, fam.params.get("split")),
+            row_sum_rounding(dy) + equal_addend_drift(d.mean(0), d.var(0, unbiased=False), d.shape[0]))
+
+
+def wgrad_families(k, m, n, generator):
+    """The named input families of dW = dy^T x over ``k`` rows, inputs (dy [k, m], x [k, n]), from a CPU generator.
+
+    plain      randn for both operands.
+    offset     x = randn + 30: every addend of an element has a mean (30 dy) far above what is left after the rows cancel.
+    constant   dy = CONSTANT_BIAS, x = CONSTANT_X everywhere: nothing cancels and a running sum drifts.
+    halves     dy = 1 + 0.1 randn; x = +30 + 0.5 randn on the first ceil(k / 2) rows, -30 + 0.5 randn on the rest: partial sums
+               of order 15 k, a result of order sqrt(k).  ``params["split"]`` is the row where the sign turns: the order
+               matters to the floor (``ordered_sum_rounding``).
+    zero_x     x exactly zero: dW must be exactly zero (within_budget's TINY floor); the column sum is plain's.
+    zero_dy    dy exactly zero: dW and the column sum exactly zero.
+    mixed      x's rows cycle plain / zero / 30 x plain (``groups``), so one 8-row group and one 64-row slab hold each kind;
+               dy is plain's."""
+    g = generator
+    dy, x = th.randn(k, m, generator=g), th.randn(k, n, generator=g)
+    half = (k + 1) // 2
+    sign = th.where(th.arange(k) < half, 1.0, -1.0).view(k, 1)
+    hdy = 1.0 + 0.1 * th.randn(k, m, generator=g)
+    hx = HALVES_X * sign + 0.5 * th.randn(k, n, generator=g)
+    groups = th.arange(k) % len(WGRAD_MIXED_OF)
+    mx = x.clone()
+    mx[groups == 1] = 0.0
+    mx[groups == 2] *= 30.0
+    return {"plain": Family("plain", (dy, x), {}),
+            "offset": Family("offset", (dy, x + 30.0), {}),
+            "constant": Family("constant", (th.full((k, m), CONSTANT_BIAS), th.full((k, n), CONSTANT_X)), {}),
+            "halves": Family("halves", (hdy, hx), {"split": half}),
+            "zero_x": Family("zero_x", (dy, th.zeros(k, n)), {}),
+            "zero_dy": Family("zero_dy", (th.zeros(k, m), x), {}),
+            "mixed": Family("mixed", (dy, mx), {}, groups)}
+
+
+def linear2_families(rows, k1, k2, generator):
+    """The named input families of flexnet_linear2 on ``rows`` rows: inputs (bias [64], x1 [rows, k1], x2 [rows, k2], W [64, k1 +
+    LINEAR2_ID_COLUMNS + k2]) with c1 = 0, c2 = k1 + LINEAR2_ID_COLUMNS; the id columns of W hold NaN (the kernel must skip
+    them).  The families are ``wgrad_families``' on the input rows, the summed dimension being the N = k1 + k2 columns:
+
+    plain      x randn, W 0.3 randn, bias randn.
+    offset     x = randn + 30.
+    constant   x = CONSTANT_X everywhere and W = CONSTANT_BIAS / 8 everywhere: every output is N equal addends and the bias.
+    halves     W = 1 + 0.1 randn; x = +30 + 0.5 randn in the first ceil(N / 2) columns, -30 + 0.5 randn in the rest
+               (``params["split"]``: that column count).
+    zero_x     x exactly zero: the output is the bias, bit for bit.
+    mixed      the rows cycle plain / zero / 30 x plain (``groups``): one 32-row tile holds each kind."""
+    g = generator
+    N, ldw = k1 + k2, k1 + LINEAR2_ID_COLUMNS + k2
+    c2 = k1 + LINEAR2_ID_COLUMNS
+
+    def weights(cols):
+        W = th.full((64, ldw), float("nan"))
+        W[:, :k1], W[:, c2:] = cols[:, :k1], cols[:, k1:]
+        return W
+
+    def parts(xs):
+        return xs[:, :k1].contiguous(), xs[:, k1:].contiguous()
+
+    bias = th.randn(64, generator=g)
+    xs = th.randn(rows, N, generator=g)
+    W = weights(0.3 * th.randn(64, N, generator=g))
+    half = (N + 1) // 2
+    sign = th.where(th.arange(N) < half, 1.0, -1.0).view(1, N)
+    hW = weights(1.0 + 0.1 * th.randn(64, N, generator=g))
+    hx = HALVES_X * sign + 0.5 * th.randn(rows, N, generator=g)
+    groups = th.arange(rows) % len(WGRAD_MIXED_OF)
+    mx = xs.clone()
+    mx[groups == 1] = 0.0
+    mx[groups == 2] *= 30.0
+    return {"plain": Family("plain", (bias, *parts(xs), W), {}),
+            "offset": Family("offset", (bias, *parts(xs + 30.0), W), {}),
+            "constant": Family("constant", (bias, *parts(th.full((rows, N), CONSTANT_X)), weights(th.full((64, N), CONSTANT_BIAS / 8))), {}),
+            "halves": Family("halves", (bias, *parts(hx), hW), {"split": half}),
+            "zero_x": Family("zero_x", (bias, *parts(th.zeros(rows, N)), W), {}),
+            "mixed": Family("mixed", (bias, *parts(mx), W), {}, groups)}
+
+
+def wgrad_case(k, m, n):
+    """``wgrad_families`` of one shape from the seed both tests/test_wgrad_fp64_gpu.py and tests/test_fp64_budget_cpu.py use."""
+    return wgrad_families(k, m, n, th.Generator().manual_seed(1000003 * k + 1009 * m + n))
+
+
+def wgrad_cases():
+    """Every (shape class, (k, m, n), family names) the GPU test runs: WGRAD_SHAPES on every family, the cap shape, and the
+    two-block shapes with x = [x | x2] as one operand."""
+    out = [(cls, shape, WGRAD_FAMILIES) for cls, shapes in WGRAD_SHAPES.items() for shape in shapes]
+    out.append(((2, 1), WGRAD_CAP_SHAPE, WGRAD_CAP_FAMILIES))
+    return out + [((2, 5), (k, m, n + n2), WGRAD_TWO_FAMILIES) for k, m, n, n2 in WGRAD_TWO_SHAPES]
+
+
+def linear2_case(rows, k1, k2):
+    """``linear2_families`` of one shape from the seed both tests/test_linear_fp64_gpu.py and the CPU test use."""
+    return linear2_families(rows, k1, k2, th.Generator().manual_seed(1000003 * rows + 1009 * k1 + k2))

@@ -4,7 +4,9 @@ cap; the fp32 modules pass their own budget; and the budget rejects five wrong f
 1e-5 of itself, an output off by 1e-5 of its scale) errors that the fixed tolerances of the fp32-against-fp32 tests accept,
 one (LayerNorm statistics from a running fp32 sum) wrong only on rows whose 64 inputs are all equal.  The QMIX mixer's part is
 at the end: ``qmix_plain`` is ``QMixer.forward_torch``, every case of tests/test_qmix_fp64_gpu.py keeps its tie share within the
-cap, and the budget rejects three wrong evaluations of the mixer."""
+cap, and the budget rejects three wrong evaluations of the mixer.  The last part holds the cases of the two hand-written GEMMs
+(tests/test_wgrad_fp64_gpu.py, tests/test_linear_fp64_gpu.py): a running fp32 sum in row (column) order is inside the budget with
+the floors those tests take, and five wrong evaluations are outside it."""
 import pytest
 import torch as th
 
@@ -802,3 +804,156 @@ def test_policy_loss_rounding_is_what_the_fp32_composition_does_and_still_reject
     short = tuple(t[:-1] for t in fam.inputs)
     wrong = fb.policy_loss_plain(short, fb.POLICY_EPS, th.float32, fixed=not per_row)["loss"] * (shape[0] - 1) / shape[0]
     _rejected(wrong, t32, ref, f"mutant loss without its last row {family} {shape}")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# csrc/wgrad.hip and csrc/linear.hip: the products, floors, families and cases of tests/test_wgrad_fp64_gpu.py and
+# tests/test_linear_fp64_gpu.py.  The yardstick here is the CPU's fp32 matmul; on the GPU it is the library GEMM.
+
+@pytest.mark.parametrize("k,m,n", [(37, 5, 7), (130, 4, 9)])
+def test_product_sum_rounding_is_row_sum_rounding_of_the_materialised_addends(k, m, n):
+    g = th.Generator().manual_seed(k)
+    dy, x = th.randn(k, m, generator=g), th.randn(k, n, generator=g) + 0.5
+    addends = dy.double()[:, :, None] * x.double()[:, None, :]
+    want = fb.row_sum_rounding(addends)
+    got = fb.product_sum_rounding(dy, x)
+    assert got.shape == (m, n) and float(((got - want).abs() / want).max()) <= 1e-12
+    # one run of ordered_sum_rounding is the same figure; two runs of exchangeable rows stay of its size
+    two = fb.product_sum_rounding(dy, x, split=(k + 1) // 2)
+    assert 0.7 <= float(two.square().mean().sqrt() / want.square().mean().sqrt()) <= 1.4
+    # flexnet_linear2's floor: the same thing over the input columns
+    W = th.randn(64, k + 5, generator=g)
+    x1, x2 = th.randn(m, k - 4, generator=g), th.randn(m, 4, generator=g)
+    cols = th.cat((W[:, :k - 4], W[:, k + 1:]), 1).double()
+    addends = th.cat((x1, x2), 1).double().t()[:, :, None] * cols.t()[:, None, :]
+    want = fb.row_sum_rounding(addends)
+    got = fb.linear2_sum_rounding(x1, x2, W, 0, k + 1)
+    assert got.shape == (m, 64) and float(((got - want).abs() / want).max()) <= 1e-12
+
+
+def test_wgrad_and_linear2_families_are_what_they_say():
+    fams = fb.wgrad_case(130, 4, 64)
+    assert tuple(fams) == fb.WGRAD_FAMILIES
+    dy, x = fams["constant"].inputs
+    assert bool((dy == fb.CONSTANT_BIAS).all()) and bool((x == fb.CONSTANT_X).all())
+    dy, x = fams["halves"].inputs
+    assert fams["halves"].params["split"] == 65 and bool((x[:65] > 25).all()) and bool((x[65:] < -25).all())
+    ref = fb.wgrad_plain(dy.double(), x.double())[0]
+    assert float(ref.abs().max()) < 0.1 * 15 * 130                      # the rows cancel: far below the partial sums
+    assert not fams["zero_x"].inputs[1].any() and not fams["zero_dy"].inputs[0].any()
+    assert th.equal(fams["zero_x"].inputs[0], fams["plain"].inputs[0])
+    mx, groups = fams["mixed"].inputs[1], fams["mixed"].groups
+    assert not mx[groups == 1].any() and th.equal(mx[groups == 2], 30.0 * fams["plain"].inputs[1][groups == 2])
+    assert set(groups[:8].tolist()) == {0, 1, 2} and set(groups[64:72].tolist()) == {0, 1, 2}
+    again = fb.wgrad_case(130, 4, 64)
+    assert all(th.equal(a, b) for nm in fams for a, b in zip(fams[nm].inputs, again[nm].inputs))
+    # every class is reached by its shapes, on both sides of each boundary
+    from safe_marl_amd.nets import _wgrad_class
+    for cls, shape, _ in fb.wgrad_cases():
+        assert _wgrad_class(shape[1], shape[2])[:2] == cls, (cls, shape)
+    assert len(fb.WGRAD_SHAPES) == 8 and all(len(v) >= 2 for v in fb.WGRAD_SHAPES.values())
+    ms = {s[1] for v in fb.WGRAD_SHAPES.values() for s in v}
+    ns = {s[2] for v in fb.WGRAD_SHAPES.values() for s in v}
+    assert {32, 33, 64, 65} <= ms and {32, 33, 64, 65, 160, 161} <= ns
+    fams = fb.linear2_case(33, 8, 4)
+    assert tuple(fams) == fb.LINEAR2_FAMILIES
+    bias, x1, x2, W = fams["plain"].inputs
+    assert x1.shape == (33, 8) and x2.shape == (33, 4) and W.shape == (64, 17)
+    assert bool(W[:, 8:13].isnan().all()) and bool(W[:, :8].isfinite().all()) and bool(W[:, 13:].isfinite().all())
+    assert [fb.linear2_ss(*w) for w in fb.LINEAR2_WIDTHS] == [1, 1, 1, 1, 2, 2, 2, 3, 3, 3, 3]
+    assert fb.linear2_ss(768, 8) == 4                                   # refused
+
+
+def _wgrad_cannot_differ(k, m, n, family, wrong, tensor):
+    """The cases in which a wrong evaluation of WGRAD_WRONG is the right one (``tensor``: "C" or "colsum")."""
+    if family == "zero_dy" or (family == "zero_x" and tensor == "C"):
+        return "a zero family"
+    if wrong == "colsum_per_chunk":
+        return "C is not touched" if tensor == "C" else ("one column chunk" if fb.wgrad_chunks(m, n) == 1 else None)
+    if wrong == "drop_slab_tail" and k % 8 == 0:
+        return "k is whole 8-row groups"
+    if family == "mixed" and tensor == "C":
+        dropped = [k - 1] if wrong == "drop_last_row" else list(range(k - k % 8, k))
+        if all(r % 3 == 1 for r in dropped):
+            return "mixed: the rows left out are zero rows of x"
+    return None
+
+
+# One case in which the budget cannot tell a wrong evaluation that DOES differ: one of 32 777 equal rows is 2^-15 of the sum,
+# 512 ulps, and the row-order running sum the budget must admit is itself off by 2 440 ulps there (fb.equal_addend_drift).  The
+# plain family at the same shape rejects both row drops.
+WGRAD_BELOW_THE_DRIFT = {(fb.WGRAD_CAP_SHAPE, "constant", "drop_last_row"), (fb.WGRAD_CAP_SHAPE, "constant", "drop_slab_tail")}
+
+
+@pytest.mark.parametrize("cls,shape,names", fb.wgrad_cases(), ids=lambda v: "x".join(map(str, v)) if isinstance(v[0], int) else None)
+def test_wgrad_cases_admit_a_row_order_running_sum_and_reject_the_wrong_evaluations(cls, shape, names):
+    """For every (shape, family) of tests/test_wgrad_fp64_gpu.py: dW and the column sum accumulated in fp32 one row after the
+    other — the least accurate order a correct kernel may use — are inside the budget with the floors the GPU test takes
+    (fb.wgrad_floors), and each of fb.WGRAD_WRONG, evaluated in fp32, is outside it, on dW and on the column sum, unless it
+    cannot differ (``_wgrad_cannot_differ``, checked in fp64) or is in WGRAD_BELOW_THE_DRIFT."""
+    k, m, n = shape
+    fams = fb.wgrad_case(k, m, n)
+    dys = th.stack([fams[nm].inputs[0] for nm in names])
+    xs = th.stack([fams[nm].inputs[1] for nm in names])
+    run_c, run_cs = th.zeros(len(names), m, n), th.zeros(len(names), m)
+    for r in range(k):
+        run_c = run_c + dys[:, r, :, None] * xs[:, r, None, :]
+        run_cs = run_cs + dys[:, r]
+    for i, nm in enumerate(names):
+        dy, x = fams[nm].inputs
+        ref = dict(zip(("C", "colsum"), fb.wgrad_plain(dy.double(), x.double())))
+        yard = dict(zip(("C", "colsum"), fb.wgrad_plain(dy, x)))
+        floors = dict(zip(("C", "colsum"), fb.wgrad_floors(fams[nm])))
+        ulps = {t: fb.floor_ulps(floors[t], ref[t]) for t in ref}
+        for t, run in (("C", run_c[i]), ("colsum", run_cs[i])):
+            fb.within_budget(run, yard[t], ref[t], floor_ulps=ulps[t], name=f"running sum {k}x{m}x{n} {nm} {t} (floor {ulps[t]:.0f} ulps)")
+        if nm in ("zero_x", "zero_dy"):
+            assert not ref["C"].any() and ulps["C"] == fb.FLOOR_ULPS
+        for wrong in fb.WGRAD_WRONG:
+            bad = dict(zip(("C", "colsum"), fb.wgrad_plain(dy, x, wrong=wrong)))
+            bad64 = dict(zip(("C", "colsum"), fb.wgrad_plain(dy.double(), x.double(), wrong=wrong)))
+            for t in ("C", "colsum"):
+                why = _wgrad_cannot_differ(k, m, n, nm, wrong, t)
+                if why is not None:
+                    # (to fp64 rounding: without a row the fp64 GEMM may block the others differently)
+                    assert float((bad64[t] - ref[t]).abs().max()) <= 1e-12 * float(ref[t].abs().max()), (shape, nm, wrong, t, why)
+                    continue
+                if (shape, nm, wrong) in WGRAD_BELOW_THE_DRIFT:
+                    assert float((bad64[t] - ref[t]).abs().max()) < float(floors[t].max())
+                    continue
+                with pytest.raises(AssertionError):
+                    fb.within_budget(bad[t], yard[t], ref[t], floor_ulps=ulps[t], name=f"{wrong} {k}x{m}x{n} {nm} {t}")
+
+
+@pytest.mark.parametrize("k1,k2", fb.LINEAR2_WIDTHS)
+def test_linear2_cases_admit_a_column_order_running_sum_and_reject_the_wrong_evaluations(k1, k2):
+    """The same for every (rows, widths, family) of tests/test_linear_fp64_gpu.py: the output accumulated in fp32 one input
+    column after the other, the bias last.  Exempt: the last action piece where there is no action block (k2 = 0) or the inputs
+    are zero."""
+    c2 = k1 + fb.LINEAR2_ID_COLUMNS
+    cases = [(rows, nm, fam) for rows in fb.LINEAR2_ROWS for nm, fam in fb.linear2_case(rows, k1, k2).items()]
+    for nm in fb.LINEAR2_FAMILIES:
+        mine = [(rows, fam) for rows, name, fam in cases if name == nm]
+        for rows, fam in mine:
+            bias, x1, x2, W = fam.inputs
+            xs = th.cat((x1, x2), 1)
+            ws = th.cat((W[:, :k1], W[:, c2:]), 1)
+            run = th.zeros(rows, 64)
+            for c in range(k1 + k2):
+                run = run + xs[:, c, None] * ws[None, :, c]
+            run = run + bias
+            ref = fb.linear2_plain(bias.double(), x1.double(), x2.double(), W.double(), 0, c2)
+            yard = fb.linear2_plain(bias, x1, x2, W, 0, c2)
+            assert bool(ref.isfinite().all())                           # the NaN id columns of W are skipped
+            floor = fb.linear2_sum_rounding(x1, x2, W, 0, c2, fam.params.get("split"))
+            ulps = fb.floor_ulps(floor, ref)
+            fb.within_budget(run, yard, ref, floor_ulps=ulps, name=f"running sum {rows}x({k1}+{k2}) {nm} (floor {ulps:.0f} ulps)")
+            if nm == "zero_x":
+                assert th.equal(yard, bias.expand(rows, 64))
+            for wrong in fb.LINEAR2_WRONG:
+                bad = fb.linear2_plain(bias, x1, x2, W, 0, c2, wrong=wrong)
+                if wrong == "drop_last_action_piece" and (k2 == 0 or nm == "zero_x"):
+                    assert th.equal(bad, yard)
+                    continue
+                with pytest.raises(AssertionError):
+                    fb.within_budget(bad, yard, ref, floor_ulps=ulps, name=f"{wrong} {rows}x({k1}+{k2}) {nm}")

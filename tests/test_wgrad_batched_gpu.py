@@ -6,7 +6,7 @@ import ctypes as C
 import pytest
 import torch
 
-from .test_wgrad_gpu import _close, _ref
+from .test_wgrad_gpu import _close, _colsum_in_budget, _ref
 
 pytestmark = pytest.mark.gpu
 SENTINEL = -12345.0
@@ -111,6 +111,7 @@ def test_a_mixed_batch_against_fp64_products():
         if p["colsum"] is not None:
             cs = p["dy"].double().sum(0)
             assert (p["colsum"].double() - cs).abs().max().item() <= 3e-7 * max(1.0, k) * max(p["dy"].abs().max().item(), 1e-30)
+            _colsum_in_budget(p["colsum"], p["dy"], f"wgrad batched {k}x{p['dy'].shape[1]} colsum")
     first = [b.clone() for b in bufs]
     for p in problems:                                                 # the accumulating problem starts from the same values
         if p["accumulate"]:

@@ -26,6 +26,14 @@ def _close(got, want, k):
     return (got.double() - want).abs().max().item() / scale < 3e-7 * max(1.0, k ** 0.5)
 
 
+def _colsum_in_budget(cs, dy, name):
+    """The column sum under the fp64 error budget (tests/fp64_budget.py): three times the error of the library's fp32 sum plus
+    FLOOR_ULPS and what a row-order running fp32 sum loses (``row_sum_rounding``)."""
+    from . import fp64_budget as fb
+    want = dy.double().sum(0)
+    fb.within_budget(cs, dy.sum(0), want, floor_ulps=fb.floor_ulps(fb.row_sum_rounding(dy), want), name=name)
+
+
 @pytest.mark.parametrize("k,m,n", SHAPES)
 def test_matches_fp64_product(k, m, n):
     from safe_marl_amd.nets import tall_wgrad, tall_wgrad_supported
@@ -42,6 +50,7 @@ def test_matches_fp64_product(k, m, n):
     assert torch.equal(again, got)
     want = dy.double().sum(0)
     assert (cs.double() - want).abs().max().item() <= 3e-7 * max(1.0, k ** 0.5) * max(dy.abs().max().item(), 1e-30) * max(1.0, k ** 0.5)
+    _colsum_in_budget(cs, dy, f"wgrad {k}x{m}x{n} colsum")        # (the bound above allows 1e-4 of a column sum at 163 840 rows)
 
 
 @pytest.mark.parametrize("k", [32768, 1003])
@@ -170,6 +179,7 @@ def test_second_input_block_in_the_same_launch(k, n, n2):
         assert torch.equal(again[:, n + 5:], dW[:, n + 5:]) and torch.equal(again[:, :n], dW[:, :n])
     assert (want2 - dW[:, n + 5:]).abs().max().item() <= 3e-7 * k ** 0.5 * max(1.0, want2.abs().max().item())
     assert (cs.double() - dy.double().sum(0)).abs().max().item() <= 1e-3
+    _colsum_in_budget(cs, dy, f"wgrad two blocks {k}x64x({n}|{n2}) colsum")
     # the entry point itself refuses what the kernel does not cover (the wrapper then makes two calls)
     lib = _lib.load()
     a = _lib.FlexWgradArgs()
