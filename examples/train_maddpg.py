@@ -73,7 +73,8 @@ def main():
                     help="learned log-std heads (gaussian_policy: True, LOG_STD_MIN 0.0 / LOG_STD_MAX 0.5 of default.yaml)")
     ap.add_argument("--gauss-burst", action="store_true",
                     help="with --gaussian-policy and an agent-summed --alg: the rollout as one persistent launch per run of "
-                         "steps, log-std head included (FLEX_GAUSS_BURST=1, flexenv_rollout_burst_summed_gauss)")
+                         "steps, log-std head included (FLEX_GAUSS_BURST=1, flexenv_rollout_burst_summed_gauss; with --agent-type mlp "
+                         "flexenv_rollout_burst_summed_mlp)")
     ap.add_argument("--agent-type", choices=["rnn", "mlp"], default="rnn",
                     help="agent_type of default.yaml: the recurrent agent, or the MLP agent on the stacked history (csrc/actor_mlp.hip)")
     ap.add_argument("--unshared", action="store_true",
@@ -175,12 +176,16 @@ def main():
                "fallbacks": dict(FALLBACKS)}
         if a.gauss_burst:                   # asked for: the run must have rolled out through it
             rg = getattr(trainer.behaviour_net, "_rollout_graph", None)
-            out["gauss_burst"] = bool(rg is not None and rg.gauss_burst and rg.fused_burst)
+            out["gauss_burst"] = bool(rg is not None and rg.fused_burst
+                                      and (rg.gauss_burst or (rg.gaussian and getattr(rg, "mlp_burst", False))))
             if not out["gauss_burst"]:
                 raise SystemExit("--gauss-burst: this configuration did not roll out through the one-launch burst "
-                                 "(learner.RolloutGraph.gauss_burst)")
+                                 "(learner.RolloutGraph.gauss_burst, or mlp_burst with --agent-type mlp)")
         if a.agent_type != "rnn":
             out["agent_type"] = a.agent_type
+            rg = getattr(trainer.behaviour_net, "_rollout_graph", None)
+            if rg is not None and getattr(rg, "mlp_burst", False) and trainer.graph_rollout:
+                out["rollout"] = "flexenv_rollout_burst_summed_mlp"      # (the one-launch burst with the MLP policy phase)
         if a.unshared:
             out["shared_params"] = False
         if a.episodic:

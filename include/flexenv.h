@@ -333,6 +333,24 @@ typedef struct {
 int flexenv_rollout_burst_summed_gauss(FlexEnv* env, const FlexActorArgs* actor, double* reward, uint8_t* done,
                                        double* info, uint8_t* failed, float* obs_ring, int32_t steps,
                                        const FlexBurstSummedGauss* gauss, void* stream);
+/* The two bursts above for a shared MLP actor (agent_type: mlp; madrl/agents/mlp_agent.py:5-32, mlp_agent_gaussian.py:7-41):
+ * block, groups, tiles, hand-overs, ring, cursor cells and the selection phase are theirs.  The policy phase is
+ * fc1 -> LayerNorm -> ReLU as ever, then h = relu(fc2 x + b) with `mlp->fc2_w` / `fc2_b` on the matrix cores where the GRU cell
+ * stands, then the head: actor->fc2_w / fc2_b carry the OUTPUT head (MLPAgent.fc3, MLPAgentGaussian.mean), and with `gauss` its
+ * log_std head sits in columns 4-7 of the head's image as above.  h is stored to actor->hidden_out — MLPAgent.forward returns
+ * it as the hidden state — and the sink masks and files it like a GRU state.  actor->hidden_in, w_ih, w_hh, b_ih and b_hh are
+ * not read and may be NULL.  Exactly one of `summed` and `gauss` is non-NULL: the selection of flexenv_rollout_burst_summed or
+ * of flexenv_rollout_burst_summed_gauss.  The finish launch moves the two cursor cells and nothing else.
+ * FLEX_EINVAL (before any HIP call): everything flexenv_rollout_burst_summed (with `summed`) or _summed_gauss (with `gauss`)
+ * refuses, the GRU pointers and hidden_in excepted; `mlp`, fc2_w or fc2_b missing; both or neither of `summed` and `gauss`. */
+typedef struct {
+    const float* fc2_w;   /* dev [64, 64]: the second layer's weight */
+    const float* fc2_b;   /* dev [64]: its bias */
+} FlexBurstMlp;
+int flexenv_rollout_burst_summed_mlp(FlexEnv* env, const FlexActorArgs* actor, double* reward, uint8_t* done,
+                                     double* info, uint8_t* failed, float* obs_ring, int32_t steps,
+                                     const FlexBurstMlp* mlp, const FlexBurstSummed* summed,
+                                     const FlexBurstSummedGauss* gauss, void* stream);
 /* One TEST-mode episode per environment (madrl/models/model.py:269-306 for every environment at once) in ONE persistent
  * launch, with a per-episode record.  Block b owns environments 16 b .. 16 b + 15 as in flexenv_rollout_burst; the launch
  * starts from the state flexenv_reset leaves and every one of its `steps` steps is

@@ -505,12 +505,22 @@ struct R16LogStd {
     float lo, hi;
 };
 
+// The second layer of a shared MLPAgent in place of the GRU cell (MLP below; mlp_agent.py:5-32): fc2's weight [64, 64] and bias.
+struct R16Mlp {
+    const float* w;
+    const float* b;
+};
+
 // the LDS image actor_r16_body stages (same values in the same places), without its choreography: once per burst.
 // LOGSTD: columns act_dim .. 2 act_dim - 1 of the fc2 image (zero otherwise) and b2[act_dim .. 2 act_dim - 1] take the log-std
 // head (2 act_dim <= FLEXNET_MAX_ACT: the caller's check) — same LDS, same sixteen MFMA steps; a column of the product depends
 // on its own column of the image alone, so the means' accumulators see the same operands as without the head.
-template <bool LOGSTD = false>
-__device__ __forceinline__ void r16_stage_simple(const FlexActorArgs& a, ActorLds16B& s, int tid, const R16LogStd* ls = nullptr) {
+// MLP: the actor is an MLPAgent — nothing of w_ih, w_hh, b_ih or b_hh is read; its 64 -> 64 layer goes transposed into the front
+// of the gates' region, [k][64 units] at pitch R16_P1 (the w1t layout: the same bank pattern under the same reads), its bias
+// into gb[0 .. 63], and gb[64 .. 127] is the zero vector r16_fc1_tile takes for the id columns; a.fc2_w / fc2_b are the output head.
+template <bool LOGSTD = false, bool MLP = false>
+__device__ __forceinline__ void r16_stage_simple(const FlexActorArgs& a, ActorLds16B& s, int tid, const R16LogStd* ls = nullptr,
+                                                 const R16Mlp* mlp = nullptr) {
     const int od = a.obs_dim, na = a.n_agents, ad = a.act_dim;
     const int ld1 = od + (a.agent_id ? na : 0);
     const int nq = (od + 15) >> 4;
@@ -519,10 +529,18 @@ __device__ __forceinline__ void r16_stage_simple(const FlexActorArgs& a, ActorLd
         if (k < od) s.w1t[k * R16_P1 + u] = a.fc1_w[idx];
     }
     for (int idx = tid; idx < (16 * nq - od) * HID; idx += 64 * R16_W) s.w1t[(od + idx / HID) * R16_P1 + (idx % HID)] = 0.0f;
-    for (int idx = tid; idx < 3 * HID * HID; idx += 64 * R16_W) {
-        const int u = idx / HID, k = idx % HID;
-        s.wg[k * R16_PG + u] = a.w_ih[idx];
-        s.wg[k * R16_PG + 3 * HID + u] = a.w_hh[idx];
+    if constexpr (MLP) {
+        static_assert(HID * R16_P1 <= HID * R16_PG, "the MLP's second layer fits the gates' region");
+        for (int idx = tid; idx < HID * HID; idx += 64 * R16_W) {
+            const int u = idx / HID, k = idx % HID;
+            s.wg[k * R16_P1 + u] = mlp->w[idx];
+        }
+    } else {
+        for (int idx = tid; idx < 3 * HID * HID; idx += 64 * R16_W) {
+            const int u = idx / HID, k = idx % HID;
+            s.wg[k * R16_PG + u] = a.w_ih[idx];
+            s.wg[k * R16_PG + 3 * HID + u] = a.w_hh[idx];
+        }
     }
     for (int idx = tid; idx < 16 * HID; idx += 64 * R16_W) {
         const int o = idx / HID, k = idx % HID;
@@ -532,10 +550,15 @@ __device__ __forceinline__ void r16_stage_simple(const FlexActorArgs& a, ActorLd
         s.w2p[k * R16_P2 + o] = v;
     }
     if (tid < HID) {
-        s.gb[tid] = a.b_ih[tid] + a.b_hh[tid];
-        s.gb[HID + tid] = a.b_ih[HID + tid] + a.b_hh[HID + tid];
-        s.gb[2 * HID + tid] = a.b_ih[2 * HID + tid];
-        s.gb[3 * HID + tid] = a.b_hh[2 * HID + tid];
+        if constexpr (MLP) {
+            s.gb[tid] = mlp->b[tid];
+            s.gb[HID + tid] = 0.0f;
+        } else {
+            s.gb[tid] = a.b_ih[tid] + a.b_hh[tid];
+            s.gb[HID + tid] = a.b_ih[HID + tid] + a.b_hh[HID + tid];
+            s.gb[2 * HID + tid] = a.b_ih[2 * HID + tid];
+            s.gb[3 * HID + tid] = a.b_hh[2 * HID + tid];
+        }
         s.b1[tid] = a.fc1_b[tid];
         s.lnw[tid] = a.layernorm ? a.ln_w[tid] : 1.0f;
         s.lnb[tid] = a.layernorm ? a.ln_b[tid] : 0.0f;
@@ -561,11 +584,16 @@ __device__ __forceinline__ void r16_stage_simple(const FlexActorArgs& a, ActorLd
 // columns act_dim .. 2 act_dim - 1 of the fc2 product (r16_stage_simple<true>) turn them into
 // log_std = lo + 0.5 (hi - lo) (tanhf(u) + 1), the precise tanhf of csrc/gauss.hip, and store it to ls->out [rows, act_dim];
 // means and hidden state come out as without it, bit for bit.
-template <bool TEST = false, bool NOISE = !TEST, bool LOGSTD = false, typename EnvStep, typename Mark>
+// MLP (flexenv_rollout_burst_summed_mlp; with NOISE false): the actor is an MLPAgent (r16_stage_simple<., true>) — where the GRU
+// cell stands, h = relu(fc2 x + b) on the matrix cores: r16_fc1_tile's output layout (x[T][r] = unit 16 T + 4 g + r) is its input
+// layout (xq[q][r] = column 16 q + 4 g + r), so it is that routine over the second layer's image with four column groups.
+// a.hidden_in is not read; h goes to a.hidden_out as the new hidden state (MLPAgent.forward returns it as such) and into the head.
+template <bool TEST = false, bool NOISE = !TEST, bool LOGSTD = false, bool MLP = false, typename EnvStep, typename Mark>
 __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds16B& s, const int n_steps, EnvStep&& env_step,
-                                                Mark&& mark, const R16LogStd* ls = nullptr) {
+                                                Mark&& mark, const R16LogStd* ls = nullptr, const R16Mlp* mlp = nullptr) {
     static_assert(!(TEST && NOISE), "test mode draws no noise");
     static_assert(!LOGSTD || (!TEST && !NOISE), "the log-std head rides on the means-only ring form");
+    static_assert(!MLP || (!TEST && !NOISE), "the MLP actor rides on the means-only ring form");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 15, g = lane >> 4;
     const int grp = wave >> 2, w = wave & 3;
@@ -594,7 +622,7 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
             }
         }
     };
-    r16_stage_simple<LOGSTD>(a, s, tid, ls);
+    r16_stage_simple<LOGSTD, MLP>(a, s, tid, ls, mlp);
     if (NOISE && w == 3) draw(rng_step);
     if (tid < 2) s.gsync[tid] = 0;
     __syncthreads();
@@ -615,8 +643,10 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
     for (int step = 0; step < n_steps; ++step) {
         mark(12, step);
         if (has_tile) {
-            const float* hid_p = (TEST ? ((step & 1) ? a.hidden_out : a.hidden_in) : a.hidden_in + slab * a.hid_slab_stride) +
-                                 (int64_t)row * HID + 4 * g;
+            const float* hid_p = nullptr;
+            if constexpr (!MLP)
+                hid_p = (TEST ? ((step & 1) ? a.hidden_out : a.hidden_in) : a.hidden_in + slab * a.hid_slab_stride) +
+                        (int64_t)row * HID + 4 * g;
             float* const hid_o = TEST && (step & 1) ? const_cast<float*>(a.hidden_in) : a.hidden_out;
             f32x4 xq[FLEXNET_MAX_OBS / 16], hv[4], x[4], hnew[4];
             {
@@ -633,16 +663,25 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
                 for (int q = 0; q < FLEXNET_MAX_OBS / 16; ++q)
                     xq[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(robs, q < nq ? xoff + 64 * q : -1, 0, 0));
             }
+            if constexpr (!MLP) {
 #pragma unroll
-            for (int S = 0; S < 4; ++S) {
-                const float4 t = *reinterpret_cast<const float4*>(hid_p + 16 * S);
-                hv[S] = f32x4{t.x, t.y, t.z, t.w};
+                for (int S = 0; S < 4; ++S) {
+                    const float4 t = *reinterpret_cast<const float4*>(hid_p + 16 * S);
+                    hv[S] = f32x4{t.x, t.y, t.z, t.w};
+                }
             }
             r16_fc1_tile(w1_l, b1_l, w1id_l, xq, nq, x);
             r16_ln_relu(x, a.layernorm != 0, a.ln_eps, lnw_l, lnb_l);
+            if constexpr (MLP) {                                           // mlp_agent.py:29: fc2 and its activation
+                r16_fc1_tile(s.wg + (4 * g) * R16_P1 + j, gb_l, gb_l + HID, x, 4, hnew);
+#pragma unroll
+                for (int T = 0; T < 4; ++T)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) hnew[T][r] = relu_nan(hnew[T][r]);
+            }
 #pragma unroll
             for (int T = 0; T < 4; ++T) {
-                hnew[T] = r16_gru_tile(wg_l, gb_l, T, x, hv);
+                if constexpr (!MLP) hnew[T] = r16_gru_tile(wg_l, gb_l, T, x, hv);
                 if (live)
                     *reinterpret_cast<float4*>(hid_o + (int64_t)row * HID + 16 * T + 4 * g) =
                         make_float4(hnew[T][0], hnew[T][1], hnew[T][2], hnew[T][3]);

@@ -1349,9 +1349,12 @@ struct BurstArgs {
     // ... with a shared RNNAgentGaussian actor (flexenv_rollout_burst_summed_gauss): the policy phase also evaluates the log-std
     // head into ls.out [rows, act_dim] (actor_r16_burst's LOGSTD) and the selection is gauss_sum_select on means and log-stds
     R16LogStd ls;
+    // ... with a shared MLPAgent actor (flexenv_rollout_burst_summed_mlp): the second layer that stands where the GRU cell does
+    // (actor_r16_burst's MLP); act.fc2_* are then the output head, ls the log-std head of an MLPAgentGaussian
+    R16Mlp mlp;
 };
 
-// the burst's four forms
+// the burst's four environment-phase forms (the two agent-summed ones also with an MLP policy phase: flex_rollout_burst_body's MLP)
 enum { BURST_PLAIN = 0, BURST_SAFE = 1, BURST_SUMMED = 2, BURST_SUMMED_GAUSS = 3 };
 
 // (Inlined again since the policy became actor_r16_burst, which keeps almost nothing live across the step: 12 spilled
@@ -1405,7 +1408,7 @@ __device__ __forceinline__ void flex_burst_env_step(int slab_v, int step_v, unsi
     __builtin_amdgcn_s_setprio(0);
 }
 
-template <int NA_CAP, int MODE>
+template <int NA_CAP, int MODE, bool MLP = false>
 __device__ __forceinline__ void flex_rollout_burst_body(const BurstArgs& b, ActorLds16B& s) {
     const unsigned long long kb = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
     auto env_step = [&](int64_t slab, int step) {
@@ -1415,16 +1418,16 @@ __device__ __forceinline__ void flex_rollout_burst_body(const BurstArgs& b, Acto
 #ifdef FLEX_STAMPS
     // diagnostic build: phase boundaries of the LAST step, per wavefront, in slots 8-12 of its first environment's row
     const int wave = __builtin_amdgcn_readfirstlane(blockIdx.x * R16_W + (threadIdx.x >> 6));
-    actor_r16_burst<false, NOISE, LOGSTD>(b.act, s, b.n_steps, env_step, [&](int slot, int step) {
+    actor_r16_burst<false, NOISE, LOGSTD, MLP>(b.act, s, b.n_steps, env_step, [&](int slot, int step) {
         unsigned long long t;
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
         __builtin_amdgcn_sched_barrier(0);
         if (b.k.stamps && (threadIdx.x & 63) == 0 && 2 * wave < b.k.n_envs && step == b.n_steps - 1)
             b.k.stamps[(int64_t)(2 * wave) * 16 + slot] = t;
-    }, &b.ls);
+    }, &b.ls, &b.mlp);
 #else
-    actor_r16_burst<false, NOISE, LOGSTD>(b.act, s, b.n_steps, env_step, [](int, int) {}, &b.ls);
+    actor_r16_burst<false, NOISE, LOGSTD, MLP>(b.act, s, b.n_steps, env_step, [](int, int) {}, &b.ls, &b.mlp);
 #endif
 }
 
@@ -1455,6 +1458,26 @@ void flex_rollout_burst_kernel(BurstArgs b) {
     flex_rollout_burst_body<NA_CAP, BURST_SUMMED_GAUSS>(b, s);
 }
 }  // namespace summed_gauss
+
+// The fifth and sixth form (flexenv_rollout_burst_summed_mlp): the third and fourth with a shared MLPAgent / MLPAgentGaussian in
+// the policy phase, the environment phase as it stands.
+namespace summed_mlp {
+template <int NA_CAP>
+__global__ __launch_bounds__(64 * R16_W)
+void flex_rollout_burst_kernel(BurstArgs b) {
+    __shared__ ActorLds16B s;
+    flex_rollout_burst_body<NA_CAP, BURST_SUMMED, true>(b, s);
+}
+}  // namespace summed_mlp
+
+namespace summed_gauss_mlp {
+template <int NA_CAP>
+__global__ __launch_bounds__(64 * R16_W)
+void flex_rollout_burst_kernel(BurstArgs b) {
+    __shared__ ActorLds16B s;
+    flex_rollout_burst_body<NA_CAP, BURST_SUMMED_GAUSS, true>(b, s);
+}
+}  // namespace summed_gauss_mlp
 
 // the cells a burst leaves as `steps` single steps would: cell 0 = the slab the policy reads next, cell 1 = the slab the last
 // step filed into, the noise stream's step counter advanced
@@ -2025,16 +2048,18 @@ int flexenv_step_many(FlexEnv* e, const void* actions, int32_t act_dtype, int32_
 // What both burst entry points ask of the env, the sink, the ring, the cursor cells and the actor's shapes (everything but the
 // noise): the configuration of the two-launch sink step (flexenv_step with FLEX_STEP_OBS_RING | FLEX_STEP_REPLAY_SINK behind
 // flexnet_actor_forward in ring mode), and the policy's tiles of a block = the block's sixteen environments.  No HIP call.
+// `mlp`: the actor has no GRU cell — hidden_in and the four GRU tensors are not read and may be NULL.
 static bool burst_config_ok(const FlexEnv* e, const FlexActorArgs* actor, const double* reward, const uint8_t* done,
-                            const float* obs_ring, int32_t steps) {
+                            const float* obs_ring, int32_t steps, bool mlp = false) {
     if (!e || !actor || !reward || !done || !obs_ring || steps < 1) return false;
     const FlexActorArgs& p = *actor;
     const int na = e->cfg.n_agents;
     if (!e->has_sink || e->obs_slabs < 2 || e->hnet.epw != 2 || na > 5) return false;
     if (p.rows != (int64_t)e->n_envs * na || p.n_agents != na || p.obs_dim < 1 || p.obs_dim > FLEXNET_MAX_OBS || (p.obs_dim & 3) ||
         p.act_dim < 1 || p.act_dim > FLEXNET_MAX_ACT) return false;
-    if (!p.hidden_in || !p.hidden_out || !p.means || !p.action || !p.env_action || !p.cursor || !p.cursor_out ||
-        !p.fc1_w || !p.fc1_b || !p.w_ih || !p.w_hh || !p.b_ih || !p.b_hh || !p.fc2_w || !p.fc2_b ||
+    if (!mlp && (!p.hidden_in || !p.w_ih || !p.w_hh || !p.b_ih || !p.b_hh)) return false;
+    if (!p.hidden_out || !p.means || !p.action || !p.env_action || !p.cursor || !p.cursor_out ||
+        !p.fc1_w || !p.fc1_b || !p.fc2_w || !p.fc2_b ||
         (p.layernorm && (!p.ln_w || !p.ln_b))) return false;
     if (p.ring_slabs != e->obs_slabs || steps >= e->obs_slabs || p.obs_dim != 6 * e->cfg.history) return false;
     if (p.cursor_out != e->obs_cursor || p.cursor != e->sink.cursor_out || p.hidden_out != e->sink.hid_new ||
@@ -2058,6 +2083,7 @@ static BurstArgs burst_args(FlexEnv* e, const FlexActorArgs& p, double* reward, 
     b.act_low = b.act_span = b.act_high = 0.0f;
     b.eps = b.sum_std = nullptr;
     b.ls.w = b.ls.b = nullptr; b.ls.out = nullptr; b.ls.lo = b.ls.hi = 0.0f;
+    b.mlp.w = b.mlp.b = nullptr;
     return b;
 }
 
@@ -2100,22 +2126,49 @@ int flexenv_rollout_burst(FlexEnv* e, const FlexActorArgs* actor, double* reward
     return FLEX_OK;
 }
 
-int flexenv_rollout_burst_summed(FlexEnv* e, const FlexActorArgs* actor, double* reward, uint8_t* done, double* info,
-                                 uint8_t* failed, float* obs_ring, int32_t steps, const FlexBurstSummed* summed, void* stream) {
-    // every argument check comes before the first HIP call
-    if (!summed || !summed->eps || !summed->std || !(summed->act_high >= summed->act_low)) return FLEX_EINVAL;
-    if (!burst_config_ok(e, actor, reward, done, obs_ring, steps)) return FLEX_EINVAL;
-    const FlexActorArgs& p = *actor;
+// The argument checks of flexenv_rollout_burst_summed, shared with the MLP form (no HIP call).
+static bool burst_summed_ok(const FlexEnv* e, const FlexActorArgs* actor, const double* reward, const uint8_t* done,
+                            const float* obs_ring, int32_t steps, const FlexBurstSummed* summed, bool mlp) {
+    if (!summed || !summed->eps || !summed->std || !(summed->act_high >= summed->act_low)) return false;
+    if (!burst_config_ok(e, actor, reward, done, obs_ring, steps, mlp)) return false;
     // four controls per building: the selection's lane map.  A sink with an aux_counter belongs to the in-kernel noise stream
     // of the plain burst: the finish launch here moves the two cursor cells and nothing else
-    if (p.act_dim != 4 || e->sink.aux_counter) return FLEX_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((e->n_envs + 15) / 16), block(64 * R16_W);
+    return actor->act_dim == 4 && !e->sink.aux_counter;
+}
+
+// ... and of flexenv_rollout_burst_summed_gauss
+static bool burst_gauss_ok(const FlexEnv* e, const FlexActorArgs* actor, const double* reward, const uint8_t* done,
+                           const float* obs_ring, int32_t steps, const FlexBurstSummedGauss* gauss, bool mlp) {
+    if (!gauss || !gauss->eps || !gauss->log_std_w || !gauss->log_std_b || !gauss->log_stds ||
+        !(gauss->log_std_max >= gauss->log_std_min) || !(gauss->act_high >= gauss->act_low)) return false;
+    // four controls per building: the selection's lane map, and the two heads' eight columns are the fc2 image's b2 slots; a
+    // block's sixteen environments are at most five policy tiles (read off the actor: no handle is followed yet)
+    static_assert(2 * 4 <= FLEXNET_MAX_ACT, "mean and log-std head side by side in b2");
+    if (!actor || actor->act_dim != 4 || actor->n_agents > 5) return false;
+    if (!burst_config_ok(e, actor, reward, done, obs_ring, steps, mlp)) return false;      // (steps >= slabs: there)
+    // a sink with an aux_counter belongs to the in-kernel noise stream of the plain burst: the finish launch here moves the two
+    // cursor cells and nothing else
+    return !e->sink.aux_counter;
+}
+
+// the launch's arguments for the two agent-summed forms (exactly one of `summed` and `gauss`)
+static BurstArgs burst_summed_args(FlexEnv* e, const FlexActorArgs& p, double* reward, uint8_t* done, double* info,
+                                   uint8_t* failed, float* obs_ring, int32_t steps, const FlexBurstSummed* summed,
+                                   const FlexBurstSummedGauss* gauss) {
     BurstArgs b = burst_args(e, p, reward, done, info, failed, obs_ring, steps);
-    b.act.rng_state = nullptr; b.act.noise = nullptr;           // (neither is read: the draws are summed->eps)
-    b.eps = summed->eps; b.sum_std = summed->std; b.act_low = summed->act_low; b.act_high = summed->act_high;
-    if (burst_small_obs(e)) hipLaunchKernelGGL((summed::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_SMALL>), grid, block, 0, s, b);
-    else hipLaunchKernelGGL((summed::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_LARGE>), grid, block, 0, s, b);
+    b.act.rng_state = nullptr; b.act.noise = nullptr;           // (neither is read: the draws are the caller's eps)
+    if (summed) {
+        b.eps = summed->eps; b.sum_std = summed->std; b.act_low = summed->act_low; b.act_high = summed->act_high;
+    } else {
+        b.eps = gauss->eps; b.act_low = gauss->act_low; b.act_high = gauss->act_high;
+        b.ls.w = gauss->log_std_w; b.ls.b = gauss->log_std_b; b.ls.out = gauss->log_stds;
+        b.ls.lo = gauss->log_std_min; b.ls.hi = gauss->log_std_max;
+    }
+    return b;
+}
+
+// the finish launch of the agent-summed forms: the two cursor cells and nothing else
+static int burst_summed_finish(const FlexEnv* e, const FlexActorArgs& p, int32_t steps, hipStream_t s) {
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(flex_burst_finish_kernel, dim3(1), dim3(64), 0, s, const_cast<int64_t*>(p.cursor), p.cursor_out,
                        (uint64_t*)nullptr, (int)steps, (int)e->obs_slabs);
@@ -2123,35 +2176,55 @@ int flexenv_rollout_burst_summed(FlexEnv* e, const FlexActorArgs* actor, double*
     return FLEX_OK;
 }
 
+int flexenv_rollout_burst_summed(FlexEnv* e, const FlexActorArgs* actor, double* reward, uint8_t* done, double* info,
+                                 uint8_t* failed, float* obs_ring, int32_t steps, const FlexBurstSummed* summed, void* stream) {
+    // every argument check comes before the first HIP call
+    if (!burst_summed_ok(e, actor, reward, done, obs_ring, steps, summed, false)) return FLEX_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((e->n_envs + 15) / 16), block(64 * R16_W);
+    const BurstArgs b = burst_summed_args(e, *actor, reward, done, info, failed, obs_ring, steps, summed, nullptr);
+    if (burst_small_obs(e)) hipLaunchKernelGGL((summed::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_SMALL>), grid, block, 0, s, b);
+    else hipLaunchKernelGGL((summed::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_LARGE>), grid, block, 0, s, b);
+    return burst_summed_finish(e, *actor, steps, s);
+}
+
 int flexenv_rollout_burst_summed_gauss(FlexEnv* e, const FlexActorArgs* actor, double* reward, uint8_t* done, double* info,
                                        uint8_t* failed, float* obs_ring, int32_t steps, const FlexBurstSummedGauss* gauss,
                                        void* stream) {
     // every argument check comes before the first HIP call
-    if (!gauss || !gauss->eps || !gauss->log_std_w || !gauss->log_std_b || !gauss->log_stds ||
-        !(gauss->log_std_max >= gauss->log_std_min) || !(gauss->act_high >= gauss->act_low)) return FLEX_EINVAL;
-    // four controls per building: the selection's lane map, and the two heads' eight columns are the fc2 image's b2 slots; a
-    // block's sixteen environments are at most five policy tiles (read off the actor: no handle is followed yet)
-    static_assert(2 * 4 <= FLEXNET_MAX_ACT, "mean and log-std head side by side in b2");
-    if (!actor || actor->act_dim != 4 || actor->n_agents > 5) return FLEX_EINVAL;
-    if (!burst_config_ok(e, actor, reward, done, obs_ring, steps)) return FLEX_EINVAL;      // (steps >= slabs: there)
-    const FlexActorArgs& p = *actor;
-    // a sink with an aux_counter belongs to the in-kernel noise stream of the plain burst: the finish launch here moves the two
-    // cursor cells and nothing else
-    if (e->sink.aux_counter) return FLEX_EINVAL;
+    if (!burst_gauss_ok(e, actor, reward, done, obs_ring, steps, gauss, false)) return FLEX_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((e->n_envs + 15) / 16), block(64 * R16_W);
-    BurstArgs b = burst_args(e, p, reward, done, info, failed, obs_ring, steps);
-    b.act.rng_state = nullptr; b.act.noise = nullptr;           // (neither is read: the draws are gauss->eps)
-    b.eps = gauss->eps; b.act_low = gauss->act_low; b.act_high = gauss->act_high;
-    b.ls.w = gauss->log_std_w; b.ls.b = gauss->log_std_b; b.ls.out = gauss->log_stds;
-    b.ls.lo = gauss->log_std_min; b.ls.hi = gauss->log_std_max;
+    const BurstArgs b = burst_summed_args(e, *actor, reward, done, info, failed, obs_ring, steps, nullptr, gauss);
     if (burst_small_obs(e)) hipLaunchKernelGGL((summed_gauss::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_SMALL>), grid, block, 0, s, b);
     else hipLaunchKernelGGL((summed_gauss::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_LARGE>), grid, block, 0, s, b);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(flex_burst_finish_kernel, dim3(1), dim3(64), 0, s, const_cast<int64_t*>(p.cursor), p.cursor_out,
-                       (uint64_t*)nullptr, (int)steps, (int)e->obs_slabs);
-    HIP_TRY(hipGetLastError());
-    return FLEX_OK;
+    return burst_summed_finish(e, *actor, steps, s);
+}
+
+int flexenv_rollout_burst_summed_mlp(FlexEnv* e, const FlexActorArgs* actor, double* reward, uint8_t* done, double* info,
+                                     uint8_t* failed, float* obs_ring, int32_t steps, const FlexBurstMlp* mlp,
+                                     const FlexBurstSummed* summed, const FlexBurstSummedGauss* gauss, void* stream) {
+    // every argument check comes before the first HIP call
+    if (!mlp || !mlp->fc2_w || !mlp->fc2_b || (summed != nullptr) == (gauss != nullptr)) return FLEX_EINVAL;
+    // (what the shared checks below refuse too — the ring's size must be the env's — read off the actor: no handle is followed yet)
+    if (!actor || actor->act_dim != 4 || actor->n_agents > 5 || steps < 1 || steps >= actor->ring_slabs) return FLEX_EINVAL;
+    if (!(summed ? burst_summed_ok(e, actor, reward, done, obs_ring, steps, summed, true)
+                 : burst_gauss_ok(e, actor, reward, done, obs_ring, steps, gauss, true))) return FLEX_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((e->n_envs + 15) / 16), block(64 * R16_W);
+    BurstArgs b = burst_summed_args(e, *actor, reward, done, info, failed, obs_ring, steps, summed, gauss);
+    b.mlp.w = mlp->fc2_w; b.mlp.b = mlp->fc2_b;
+    // (no GRU cell: whatever the caller left in these is not read)
+    b.act.hidden_in = nullptr; b.act.w_ih = b.act.w_hh = b.act.b_ih = b.act.b_hh = nullptr;
+    const bool small_obs = burst_small_obs(e);
+    if (summed) {
+        if (small_obs) hipLaunchKernelGGL((summed_mlp::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_SMALL>), grid, block, 0, s, b);
+        else hipLaunchKernelGGL((summed_mlp::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_LARGE>), grid, block, 0, s, b);
+    } else {
+        if (small_obs) hipLaunchKernelGGL((summed_gauss_mlp::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_SMALL>), grid, block, 0, s, b);
+        else hipLaunchKernelGGL((summed_gauss_mlp::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_LARGE>), grid, block, 0, s, b);
+    }
+    return burst_summed_finish(e, *actor, steps, s);
 }
 
 int flexenv_test_episodes(FlexEnv* e, const FlexActorArgs* actor, int32_t steps, int32_t summed, const FlexBurstSafety* safety,

@@ -284,21 +284,41 @@ class VecFlexProvisionEnv:
                                                   C.byref(sf) if sf is not None else None, _stream()),
                    "flexenv_rollout_burst")
 
+    def _burst_tensors(self, who, triples):
+        """The tensor checks of the agent-summed burst launches: each (name, tensor or None, numel) a contiguous float32
+        tensor of that many elements on this env's device (None passes: the library's refusal, not a Python error)."""
+        for name, t, numel in triples:
+            # (an env built with device="cuda" has no index: its tensors are on cuda:0)
+            if t is not None and not (t.is_cuda and t.device.index == (self.device.index or 0) and t.dtype == torch.float32
+                                      and t.is_contiguous()
+                                      and t.numel() == numel):
+                raise ValueError(f"{who}: `{name}` must be a contiguous float32 device tensor of {numel} elements")
+
+    def _burst_summed_struct(self, who, steps, eps, std, act_low, act_high):
+        self._burst_tensors(who, (("eps", eps, int(steps) * self.n_envs * 4), ("std", std, 4)))
+        sm = _lib.FlexBurstSummed()
+        sm.eps = None if eps is None else eps.data_ptr()
+        sm.std = None if std is None else std.data_ptr()
+        sm.act_low, sm.act_high = float(act_low), float(act_high)
+        return sm
+
+    def _burst_gauss_struct(self, who, steps, eps, log_std_w, log_std_b, log_stds, log_std_min, log_std_max, act_low, act_high):
+        rows = self.n_envs * self.n_agents
+        self._burst_tensors(who, (("eps", eps, int(steps) * self.n_envs * 4), ("log_std_w", log_std_w, 4 * 64),
+                                  ("log_std_b", log_std_b, 4), ("log_stds", log_stds, rows * 4)))
+        sg = _lib.FlexBurstSummedGauss()
+        for name, t in (("eps", eps), ("log_std_w", log_std_w), ("log_std_b", log_std_b), ("log_stds", log_stds)):
+            setattr(sg, name, None if t is None else t.data_ptr())
+        sg.log_std_min, sg.log_std_max = float(log_std_min), float(log_std_max)
+        sg.act_low, sg.act_high = float(act_low), float(act_high)
+        return sg
+
     def rollout_burst_summed(self, actor_args, steps, obs_ring, eps, std, act_low, act_high):
         """``steps`` vector steps of policy + agent-summed action selection + environment in ONE launch (include/flexenv.h:
         flexenv_rollout_burst_summed): ``actor_args`` as for ``rollout_burst`` (the means-only ring-mode policy call), ``eps``
         [steps, N, act_dim] float32 standard-normal draws (step t of the launch reads ``eps[t]``), ``std`` [act_dim] float32 —
         both contiguous device tensors — and the action range of translate_action."""
-        for name, t, numel in (("eps", eps, int(steps) * self.n_envs * 4), ("std", std, 4)):
-            # (an env built with device="cuda" has no index: its tensors are on cuda:0)
-            if t is not None and not (t.is_cuda and t.device.index == (self.device.index or 0) and t.dtype == torch.float32
-                                      and t.is_contiguous()
-                                      and t.numel() == numel):
-                raise ValueError(f"rollout_burst_summed: `{name}` must be a contiguous float32 device tensor of {numel} elements")
-        sm = _lib.FlexBurstSummed()
-        sm.eps = None if eps is None else eps.data_ptr()           # (None: the library's refusal, not a Python error)
-        sm.std = None if std is None else std.data_ptr()
-        sm.act_low, sm.act_high = float(act_low), float(act_high)
+        sm = self._burst_summed_struct("rollout_burst_summed", steps, eps, std, act_low, act_high)
         self.calls += int(steps)
         _lib.check(self.lib.flexenv_rollout_burst_summed(self.handle, C.byref(actor_args), _ptr(self.reward), _ptr(self.done),
                                                          _ptr(self.info), _ptr(self.failed), _ptr(obs_ring), int(steps),
@@ -311,24 +331,33 @@ class VecFlexProvisionEnv:
         ``actor_args`` carry the ``mean`` head as fc2; ``log_std_w`` [act_dim, 64] and ``log_std_b`` [act_dim] are the
         ``log_std`` head, ``log_stds`` [N * n_agents, act_dim] receives the last step's log-stds, ``eps`` [steps, N, act_dim] are
         the standard-normal draws — all contiguous float32 device tensors — with the range of log_std and of the action."""
-        rows = self.n_envs * self.n_agents
-        for name, t, numel in (("eps", eps, int(steps) * self.n_envs * 4), ("log_std_w", log_std_w, 4 * 64),
-                               ("log_std_b", log_std_b, 4), ("log_stds", log_stds, rows * 4)):
-            # (an env built with device="cuda" has no index: its tensors are on cuda:0)
-            if t is not None and not (t.is_cuda and t.device.index == (self.device.index or 0) and t.dtype == torch.float32
-                                      and t.is_contiguous()
-                                      and t.numel() == numel):
-                raise ValueError(f"rollout_burst_summed_gauss: `{name}` must be a contiguous float32 device tensor of {numel} elements")
-        sg = _lib.FlexBurstSummedGauss()
-        for name, t in (("eps", eps), ("log_std_w", log_std_w), ("log_std_b", log_std_b), ("log_stds", log_stds)):
-            setattr(sg, name, None if t is None else t.data_ptr())      # (None: the library's refusal, not a Python error)
-        sg.log_std_min, sg.log_std_max = float(log_std_min), float(log_std_max)
-        sg.act_low, sg.act_high = float(act_low), float(act_high)
+        sg = self._burst_gauss_struct("rollout_burst_summed_gauss", steps, eps, log_std_w, log_std_b, log_stds, log_std_min,
+                                      log_std_max, act_low, act_high)
         self.calls += int(steps)
         _lib.check(self.lib.flexenv_rollout_burst_summed_gauss(self.handle, C.byref(actor_args), _ptr(self.reward),
                                                                _ptr(self.done), _ptr(self.info), _ptr(self.failed),
                                                                _ptr(obs_ring), int(steps), C.byref(sg), _stream()),
                    "flexenv_rollout_burst_summed_gauss")
+
+    def rollout_burst_summed_mlp(self, actor_args, mlp, steps, obs_ring, eps, act_low, act_high, std=None, log_std_w=None,
+                                 log_std_b=None, log_stds=None, log_std_min=0.0, log_std_max=0.0):
+        """The two launches above for a shared MLP actor (include/flexenv.h: flexenv_rollout_burst_summed_mlp): ``actor_args``
+        and ``mlp`` (a ``_lib.FlexBurstMlp`` with the second layer, or None for the library's refusal) from
+        ``nets.mlp_burst_actor_args`` — the output head in the fc2 slot, no GRU tensors.  With ``std`` [act_dim] the selection of
+        ``rollout_burst_summed``; with ``log_stds`` (and the ``log_std`` head, ``rollout_burst_summed_gauss``'s arguments) the
+        Gaussian one; ``eps`` [steps, N, act_dim] are the standard-normal draws."""
+        who = "rollout_burst_summed_mlp"
+        gauss = log_stds is not None or log_std_w is not None or log_std_b is not None
+        sm = self._burst_summed_struct(who, steps, eps, std, act_low, act_high) if std is not None or not gauss else None
+        sg = self._burst_gauss_struct(who, steps, eps, log_std_w, log_std_b, log_stds, log_std_min, log_std_max, act_low,
+                                      act_high) if gauss else None
+        self.calls += int(steps)
+        _lib.check(self.lib.flexenv_rollout_burst_summed_mlp(self.handle, C.byref(actor_args), _ptr(self.reward), _ptr(self.done),
+                                                             _ptr(self.info), _ptr(self.failed), _ptr(obs_ring), int(steps),
+                                                             C.byref(mlp) if mlp is not None else None,
+                                                             C.byref(sm) if sm is not None else None,
+                                                             C.byref(sg) if sg is not None else None, _stream()),
+                   who)
 
     TEST_TRACE = (("actions", torch.float32), ("v", torch.float64), ("agent", torch.float64), ("row", torch.int32),
                   ("reward", torch.float64), ("info", torch.float64), ("flags", torch.uint8))

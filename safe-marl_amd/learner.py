@@ -22,7 +22,7 @@ import torch as th
 import torch.nn as nn
 
 from .nets import (WGRAD_MIN_ROWS, AttentionCritic, attn_critic, CriticTail, critic_first_layer, critic_td_loss, critic_td_loss_supported, critic_policy_loss,
-                   critic_policy_loss_supported, expand_agents, MLPAgent, MLPAgentGaussian, MLPCritic, RNNAgent, RNNAgentGaussian, critic_policy_supported, critic_replayed_supported,
+                   critic_policy_loss_supported, expand_agents, MLPAgent, MLPAgentGaussian, MLPCritic, mlp_burst_actor_args, RNNAgent, RNNAgentGaussian, critic_policy_supported, critic_replayed_supported,
                    critic_tail_supported, fused_actor_forward, fused_actor_forward_unshared, actor_unshared_supported,
                    actor_mlp_declines, actor_mlp_train, fused_actor_forward_mlp, mlp_actor_allowed,
                    actor_mlp_unshared_declines, actor_mlp_unshared_train, fused_actor_forward_mlp_unshared,
@@ -138,7 +138,27 @@ class RolloutGraph:
                                 and hasattr(getattr(env, "vec", env), "rollout_burst_summed_gauss")
                                 and os.environ.get("FLEX_SUMMED_BURST", "1") != "0"
                                 and os.environ.get("FLEX_GAUSS_BURST", "0") == "1")
-        if self.sink or self.summed_sink or self.gauss_burst:
+        # agent_type mlp with a shared MLPAgent (include/flexenv.h: flexenv_rollout_burst_summed_mlp): the same two launches with
+        # the MLP's second layer where the GRU cell stands — one form only, as `gauss_burst`: every vector step, a single one
+        # too, through the one launch, the env configured as for `summed_sink`.  On by default for the fixed std (without it
+        # body() hands the MLP agent to the RNN's kernel, which declines, and the trainer falls back to the eager loop:
+        # FLEX_MLP_BURST=0 keeps exactly that); an MLPAgentGaussian needs FLEX_GAUSS_BURST=1 as well, as the RNN's Gaussian
+        # burst does.  The launch belongs to the burst family of csrc/flexenv.hip and is captured like its siblings — the
+        # capture rule of csrc/actor_mlp.hip (nets.mlp_actor_allowed) concerns that file's entry points, which this body never
+        # calls.
+        agent0 = model.policy_dicts[0]
+        self.mlp_burst = bool(summed_sink_shape
+                              and ((type(agent0) is MLPAgent and not self.gaussian)
+                                   or (type(agent0) is MLPAgentGaussian and self.gaussian
+                                       and os.environ.get("FLEX_GAUSS_BURST", "0") == "1"))
+                              and model.args.hid_size == 64 and model.args.hid_activation == "relu"
+                              and n <= 5 and o % 4 == 0 and a == 4
+                              and hasattr(getattr(env, "vec", env), "rollout_burst_summed_mlp")
+                              and os.environ.get("FLEX_SUMMED_BURST", "1") != "0"
+                              and os.environ.get("FLEX_MLP_BURST", "1") != "0")
+        if self.mlp_burst:
+            self.summed_sink = False                  # (the three-launch form is the RNN agent's: there is no second form here)
+        if self.sink or self.summed_sink or self.gauss_burst or self.mlp_burst:
             self.act_buf = th.zeros(N * n, a, device=dev)
             self.hid_buf = th.zeros(N * n, h, device=dev)
             self.acc = th.zeros(N, 10, dtype=th.float64, device=dev)
@@ -161,9 +181,9 @@ class RolloutGraph:
         self.summed_burst = bool(self.summed_sink and n <= 5 and o % 4 == 0 and a == 4
                                  and hasattr(getattr(env, "vec", env), "rollout_burst_summed")
                                  and os.environ.get("FLEX_SUMMED_BURST", "1") != "0")
-        if self.summed_burst or self.gauss_burst:
+        if self.summed_burst or self.gauss_burst or self.mlp_burst:
             self.means_buf = th.zeros(N * n, a, device=dev)
-        if self.gauss_burst:
+        if self.gauss_burst or (self.mlp_burst and self.gaussian):
             self.log_stds_buf = th.zeros(N * n, a, device=dev)
         self._configure_env()
 
@@ -186,7 +206,7 @@ class RolloutGraph:
             env.set_step_counter(None)                      # the env step sets cursor[0] itself in this mode
             env.set_obs_ring(buf.cursor[1:], row_stride, buf.slabs)
             env.set_replay_sink(self.act_buf, self.hid_buf, buf.small_ring, buf.hid_ring, self.acc, cursor_out=buf.cursor[0:1],
-                                aux_counter=None if (self._torch_noise or self.summed_sink or self.gauss_burst)
+                                aux_counter=None if (self._torch_noise or self.summed_sink or self.gauss_burst or self.mlp_burst)
                                 else self.rng_state[1:2])
         else:
             env.set_step_counter(buf.cursor[1:], buf.slabs)
@@ -215,11 +235,11 @@ class RolloutGraph:
 
     @property
     def sink_active(self):
-        return (self.sink and self.fast) or self.summed_sink or self.gauss_burst
+        return (self.sink and self.fast) or self.summed_sink or self.gauss_burst or self.mlp_burst
 
     @property
     def fused_burst(self):
-        if self.summed_burst or self.gauss_burst:       # (their draws are torch's own: torch_noise gates the plain form only)
+        if self.summed_burst or self.gauss_burst or self.mlp_burst:       # (their draws are torch's own: torch_noise gates the plain form only)
             return True
         return (self.burst_launch and self.sink_active and not self._torch_noise
                 and not (self.safe and self.model.intended_actions))       # (that routing transposes in torch)
@@ -241,7 +261,7 @@ class RolloutGraph:
     @property
     def ring_active(self):
         # (tests switch `fast` off to run the general body on the same object)
-        return (self.ring_io and self.fast) or self.summed_sink or self.gauss_burst
+        return (self.ring_io and self.fast) or self.summed_sink or self.gauss_burst or self.mlp_burst
 
     @property
     def obs(self):
@@ -367,6 +387,30 @@ class RolloutGraph:
                                           launch=launch)
                 if out is None:
                     raise RuntimeError("the fused actor kernel declined a configuration RolloutGraph.gauss_burst admitted")
+            return
+        if self.mlp_burst:
+            with th.no_grad():
+                # the MLP policy, selection and environment for `burst` steps — or ONE step: the same launch, there is no second
+                # form — in one persistent launch (include/flexenv.h: flexenv_rollout_burst_summed_mlp); the draws of all its
+                # steps from ONE call of the function summed_exploration draws a step's from.  Model.policy is not called.
+                import torch.distributions.normal as tdn      # (looked up at call time, as summed_exploration does)
+                buf, k = self.buf, burst or 1
+                agent = m.policy_dicts[0]
+                eps = tdn._standard_normal((k, N, 1, m.act_dim), th.float32, self.act_buf.device)
+                vec = env.vec if hasattr(env, "vec") else env
+                args, mlp = mlp_burst_actor_args(agent, N, m.n_, m.obs_dim, m.args.agent_id, ring_cursor=buf.cursor,
+                                                 cursor_out=buf.cursor[1:], obs_source=self.obs_src, ring_slabs=buf.slabs,
+                                                 hidden_out=self.hid_buf, means=self.means_buf)
+                # (what the selection phase writes: the action the sink files, the action the step reads)
+                args.action, args.env_action = self.act_buf.data_ptr(), self.env_act_buf.data_ptr()
+                if self.gaussian:
+                    vec.rollout_burst_summed_mlp(args, mlp, k, buf.row_ring, eps, m.args.action_low, m.args.action_high,
+                                                 log_std_w=agent.log_std.weight, log_std_b=agent.log_std.bias,
+                                                 log_stds=self.log_stds_buf, log_std_min=agent.args.LOG_STD_MIN,
+                                                 log_std_max=agent.args.LOG_STD_MAX)
+                else:
+                    vec.rollout_burst_summed_mlp(args, mlp, k, buf.row_ring, eps, m.args.action_low, m.args.action_high,
+                                                 std=m.summed_std(eps.device))
             return
         if self.summed and self.summed_sink:
             with th.no_grad():
@@ -547,7 +591,7 @@ class RolloutGraph:
             self._hid.zero_()
             self.buf.begin_stream(first_obs)
         self._info_sum.zero_(); self._rew_sum.zero_(); self._fail_sum.zero_()
-        if self.sink or self.summed_sink or self.gauss_burst:
+        if self.sink or self.summed_sink or self.gauss_burst or self.mlp_burst:
             self.acc.zero_()
 
 

@@ -1597,6 +1597,47 @@ def fused_actor_forward_mlp(agent, obs, n_agents, agent_id):
     return _fused_inference("actor_forward", why, obs.is_cuda, "flexnet_actor_mlp_forward", launch)
 
 
+def mlp_burst_declines(agent, n_agents, obs_dim, agent_id):
+    """Why the burst's MLP policy phase (csrc/actor_r16.h: actor_r16_burst's MLP) does not cover the shared ``agent``, or None."""
+    if type(agent) not in (MLPAgent, MLPAgentGaussian):
+        return f"a {type(agent).__name__}"
+    a = agent.args
+    if not (a.hid_size == _lib.FLEXNET_HID and a.hid_activation == "relu"):
+        return f"hid {a.hid_size}, act {a.hid_activation}"
+    if agent.fc1.weight.shape[1] != obs_dim + (n_agents if agent_id else 0):
+        return f"fc1 takes {agent.fc1.weight.shape[1]} columns, obs {obs_dim}, agent_id {bool(agent_id)}"
+    return _params_decline(_actor_mlp_params(agent))
+
+
+def mlp_burst_actor_args(agent, n_envs, n_agents, obs_dim, agent_id, ring_cursor, cursor_out, obs_source, ring_slabs, hidden_out,
+                         means):
+    """The ring-form FlexActorArgs of the rollout burst for a shared MLPAgent (include/flexenv.h:
+    flexenv_rollout_burst_summed_mlp) — the sibling of what ``fused_actor_forward(..., launch=...)`` fills for the RNN agent:
+    same ring, cursor and ``obs_source`` fields, the output head (``fc3``, the Gaussian agent's ``mean``) in the fc2 slot, no GRU
+    tensors and no ``hidden_in``.  Returns (args, FlexBurstMlp with the second layer).  Raises when the agent is outside what
+    the launch covers: the caller admitted the configuration, and there is no other form to fall back to."""
+    why = mlp_burst_declines(agent, n_agents, obs_dim, agent_id)
+    if why is not None:
+        raise RuntimeError(f"the burst's MLP policy does not cover this agent: {why}")
+    fc1_w, fc1_b, ln_w, ln_b, fc2_w, fc2_b, head_w, head_b = _actor_mlp_params(agent)
+    args = _lib.FlexActorArgs()
+    args.rows, args.n_agents, args.obs_dim, args.act_dim = n_envs * n_agents, n_agents, obs_dim, agent.args.action_dim
+    args.agent_id, args.layernorm, args.ln_eps = int(bool(agent_id)), int(ln_w is not None), _ln_eps(agent)
+    args.cursor, args.cursor_out = ring_cursor.data_ptr(), cursor_out.data_ptr()
+    args.obs_slab_stride, args.hid_slab_stride, args.ring_slabs = 0, 0, int(ring_slabs)
+    for name, t in (("fc1_w", fc1_w), ("fc1_b", fc1_b), ("ln_w", ln_w), ("ln_b", ln_b), ("fc2_w", head_w), ("fc2_b", head_b),
+                    ("means", means), ("hidden_out", hidden_out)):
+        if t is not None and not t.is_contiguous():
+            raise RuntimeError(f"the burst's MLP policy: non-contiguous {name}")
+        setattr(args, name, None if t is None else t.data_ptr())
+    args.obs, args.obs_pushed = obs_source.ring, obs_source.pushed
+    args.obs_row_stride, args.obs_pushed_stride = obs_source.row_stride, obs_source.pushed_stride
+    args.obs_slots, args.obs_slot_w = obs_source.slots, obs_source.slot_w
+    mlp = _lib.FlexBurstMlp()
+    mlp.fc2_w, mlp.fc2_b = fc2_w.data_ptr(), fc2_b.data_ptr()
+    return args, mlp
+
+
 def _actor_mlp_node_forward(ctx, launch_forward, entry, params, keep, obs, n_agents, agent_id, ln_eps, hid_grad):
     """What the ``forward`` of the two MLP-actor nodes share: ``launch_forward`` (``_actor_mlp_launch_forward`` or its per-agent
     form, whose entry point is ``entry``) on ``params`` with the saves z1 | x, then the bookkeeping — obs, h, the saves and
