@@ -76,7 +76,10 @@ def main():
                          "steps, log-std head included (FLEX_GAUSS_BURST=1, flexenv_rollout_burst_summed_gauss; with --agent-type mlp "
                          "flexenv_rollout_burst_summed_mlp)")
     ap.add_argument("--agent-type", choices=["rnn", "mlp"], default="rnn",
-                    help="agent_type of default.yaml: the recurrent agent, or the MLP agent on the stacked history (csrc/actor_mlp.hip)")
+                    help="agent_type of default.yaml: the recurrent agent, or the MLP agent on the stacked history "
+                         "(csrc/actor_mlp.hip; its rollout is the one-launch burst with the MLP policy phase: "
+                         "flexenv_rollout_burst_mlp under maddpg / safemaddpg, flexenv_rollout_burst_summed_mlp under the "
+                         "agent-summed algorithms; FLEX_MLP_BURST=0 switches both off)")
     ap.add_argument("--unshared", action="store_true",
                     help="shared_params: False of default.yaml — one actor and one critic per agent (csrc/actor_unshared.hip)")
     ap.add_argument("--episodic", action="store_true",
@@ -186,6 +189,8 @@ def main():
             rg = getattr(trainer.behaviour_net, "_rollout_graph", None)
             if rg is not None and getattr(rg, "mlp_burst", False) and trainer.graph_rollout:
                 out["rollout"] = "flexenv_rollout_burst_summed_mlp"      # (the one-launch burst with the MLP policy phase)
+            if rg is not None and getattr(rg, "mlp_plain_burst", False) and trainer.graph_rollout:
+                out["rollout"] = "flexenv_rollout_burst_mlp"             # (the same under MADDPG / SAFEMADDPG: in-kernel noise)
         if a.unshared:
             out["shared_params"] = False
         if a.episodic:

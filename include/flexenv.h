@@ -351,6 +351,23 @@ int flexenv_rollout_burst_summed_mlp(FlexEnv* env, const FlexActorArgs* actor, d
                                      double* info, uint8_t* failed, float* obs_ring, int32_t steps,
                                      const FlexBurstMlp* mlp, const FlexBurstSummed* summed,
                                      const FlexBurstSummedGauss* gauss, void* stream);
+/* flexenv_rollout_burst for a shared MLP actor (agent_type: mlp under MADDPG / SAFEMADDPG; madrl/agents/mlp_agent.py:5-32 under
+ * utils/util.py:57-64): env configuration, sink (aux_counter = actor->rng_state + 1), ring, cursor cells, in-kernel noise stream,
+ * exploration epilogue (action = tanh(mean + std * z), translate_action) and, with `safety`, the projection between policy and
+ * environment are flexenv_rollout_burst's; the policy tiles are flexenv_rollout_burst_summed_mlp's — fc1 -> LayerNorm -> ReLU,
+ * h = relu(fc2 x + b) with `mlp->fc2_w` / `fc2_b` on the matrix cores where the GRU cell stands, then the head in
+ * actor->fc2_w / fc2_b (MLPAgent.fc3) — with the same means and h on the same weights and observations, bit for bit.  The draws
+ * are those of flexenv_rollout_burst from the same rng_state: actor_noise4(seed, step, global row, action group).  h is stored
+ * to actor->hidden_out and the sink masks and files it like a GRU state.  actor->hidden_in, w_ih, w_hh, b_ih and b_hh are not
+ * read and may be NULL.  The finish launch moves the two cursor cells and advances the noise stream's step counter by `steps`.
+ * Afterwards every buffer, both cursor cells and the noise position hold what `steps` launches of one step leave, bit for bit
+ * (tests/test_mlp_plain_burst_gpu.py).
+ * FLEX_EINVAL (before any HIP call): everything flexenv_rollout_burst refuses, the GRU pointers and hidden_in excepted — the
+ * env, the sink and its aux_counter, the ring, the cursor cells, the actor's shapes, n_agents > 5, steps >= slabs, the
+ * noise-stream conditions, act_dim != 4 with `safety`; `mlp`, fc2_w or fc2_b missing. */
+int flexenv_rollout_burst_mlp(FlexEnv* env, const FlexActorArgs* actor, double* reward, uint8_t* done,
+                              double* info, uint8_t* failed, float* obs_ring, int32_t steps,
+                              const FlexBurstMlp* mlp, const FlexBurstSafety* safety /* NULL: plain MADDPG */, void* stream);
 /* One TEST-mode episode per environment (madrl/models/model.py:269-306 for every environment at once) in ONE persistent
  * launch, with a per-episode record.  Block b owns environments 16 b .. 16 b + 15 as in flexenv_rollout_burst; the launch
  * starts from the state flexenv_reset leaves and every one of its `steps` steps is

@@ -588,12 +588,14 @@ __device__ __forceinline__ void r16_stage_simple(const FlexActorArgs& a, ActorLd
 // cell stands, h = relu(fc2 x + b) on the matrix cores: r16_fc1_tile's output layout (x[T][r] = unit 16 T + 4 g + r) is its input
 // layout (xq[q][r] = column 16 q + 4 g + r), so it is that routine over the second layer's image with four column groups.
 // a.hidden_in is not read; h goes to a.hidden_out as the new hidden state (MLPAgent.forward returns it as such) and into the head.
+// MLP with NOISE (flexenv_rollout_burst_mlp: MADDPG / SAFEMADDPG): the same policy tiles under the exploration epilogue of the
+// RNN form — wavefront 3 draws as ever, s.noise is a region of its own that the MLP image (front of wg, gb[0 .. 127]) leaves alone.
 template <bool TEST = false, bool NOISE = !TEST, bool LOGSTD = false, bool MLP = false, typename EnvStep, typename Mark>
 __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds16B& s, const int n_steps, EnvStep&& env_step,
                                                 Mark&& mark, const R16LogStd* ls = nullptr, const R16Mlp* mlp = nullptr) {
     static_assert(!(TEST && NOISE), "test mode draws no noise");
     static_assert(!LOGSTD || (!TEST && !NOISE), "the log-std head rides on the means-only ring form");
-    static_assert(!MLP || (!TEST && !NOISE), "the MLP actor rides on the means-only ring form");
+    static_assert(!MLP || !TEST, "the MLP actor rides on the ring forms");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 15, g = lane >> 4;
     const int grp = wave >> 2, w = wave & 3;

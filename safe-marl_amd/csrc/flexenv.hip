@@ -1479,6 +1479,17 @@ void flex_rollout_burst_kernel(BurstArgs b) {
 }
 }  // namespace summed_gauss_mlp
 
+// The seventh and eighth form (flexenv_rollout_burst_mlp): the plain and SAFE forms with a shared MLPAgent in the policy phase
+// under the exploration epilogue (in-kernel noise stream), the environment phase as it stands.
+namespace plain_mlp {
+template <int NA_CAP, bool SAFE>
+__global__ __launch_bounds__(64 * R16_W)
+void flex_rollout_burst_kernel(BurstArgs b) {
+    __shared__ ActorLds16B s;
+    flex_rollout_burst_body<NA_CAP, SAFE ? BURST_SAFE : BURST_PLAIN, true>(b, s);
+}
+}  // namespace plain_mlp
+
 // the cells a burst leaves as `steps` single steps would: cell 0 = the slab the policy reads next, cell 1 = the slab the last
 // step filed into, the noise stream's step counter advanced
 __global__ void flex_burst_finish_kernel(int64_t* cell0, int64_t* cell1, uint64_t* rng_state, int steps, int slabs) {
@@ -2091,9 +2102,12 @@ static bool burst_small_obs(const FlexEnv* e) {
     return e->cfg.n_agents == FLEX_OBS_AGENTS_SMALL && 3 * e->cfg.history <= FLEX_OBS_CLASSES(2) * (FLEX_WAVE / 2);
 }
 
-int flexenv_rollout_burst(FlexEnv* e, const FlexActorArgs* actor, double* reward, uint8_t* done, double* info,
-                          uint8_t* failed, float* obs_ring, int32_t steps, const FlexBurstSafety* safety, void* stream) {
-    if (!burst_config_ok(e, actor, reward, done, obs_ring, steps)) return FLEX_EINVAL;
+// flexenv_rollout_burst and its MLP form: the checks (no HIP call before the last of them), the launch of the plain or SAFE
+// kernel and the finish launch, which advances the noise stream's step counter.  `mlp` non-NULL: the policy phase is the MLPAgent's.
+static int burst_plain_launch(FlexEnv* e, const FlexActorArgs* actor, double* reward, uint8_t* done, double* info,
+                              uint8_t* failed, float* obs_ring, int32_t steps, const FlexBurstSafety* safety,
+                              const FlexBurstMlp* mlp, void* stream) {
+    if (!burst_config_ok(e, actor, reward, done, obs_ring, steps, mlp != nullptr)) return FLEX_EINVAL;
     const FlexActorArgs& p = *actor;
     // the burst draws the noise of steps rng_state[1] .. rng_state[1] + steps - 1 in the kernel and the finish launch advances the
     // step counter through the sink's aux_counter: the two must be the same cell, or the next burst would repeat the draws
@@ -2112,7 +2126,18 @@ int flexenv_rollout_burst(FlexEnv* e, const FlexActorArgs* actor, double* reward
         b.adjusted = safety->adjusted; b.safe_env_action = safety->env_action;
         b.act_low = safety->act_low; b.act_span = safety->act_high - safety->act_low;
     }
-    if (b.safety) {
+    if (mlp) {
+        b.mlp.w = mlp->fc2_w; b.mlp.b = mlp->fc2_b;
+        // (no GRU cell: whatever the caller left in these is not read)
+        b.act.hidden_in = nullptr; b.act.w_ih = b.act.w_hh = b.act.b_ih = b.act.b_hh = nullptr;
+        if (b.safety) {
+            if (small_obs) hipLaunchKernelGGL((plain_mlp::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_SMALL, true>), grid, block, 0, s, b);
+            else hipLaunchKernelGGL((plain_mlp::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_LARGE, true>), grid, block, 0, s, b);
+        } else {
+            if (small_obs) hipLaunchKernelGGL((plain_mlp::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_SMALL, false>), grid, block, 0, s, b);
+            else hipLaunchKernelGGL((plain_mlp::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_LARGE, false>), grid, block, 0, s, b);
+        }
+    } else if (b.safety) {
         if (small_obs) hipLaunchKernelGGL((flex_rollout_burst_kernel<FLEX_OBS_AGENTS_SMALL, true>), grid, block, 0, s, b);
         else hipLaunchKernelGGL((flex_rollout_burst_kernel<FLEX_OBS_AGENTS_LARGE, true>), grid, block, 0, s, b);
     } else {
@@ -2124,6 +2149,21 @@ int flexenv_rollout_burst(FlexEnv* e, const FlexActorArgs* actor, double* reward
                        const_cast<uint64_t*>(p.rng_state), (int)steps, (int)e->obs_slabs);
     HIP_TRY(hipGetLastError());
     return FLEX_OK;
+}
+
+int flexenv_rollout_burst(FlexEnv* e, const FlexActorArgs* actor, double* reward, uint8_t* done, double* info,
+                          uint8_t* failed, float* obs_ring, int32_t steps, const FlexBurstSafety* safety, void* stream) {
+    return burst_plain_launch(e, actor, reward, done, info, failed, obs_ring, steps, safety, nullptr, stream);
+}
+
+int flexenv_rollout_burst_mlp(FlexEnv* e, const FlexActorArgs* actor, double* reward, uint8_t* done, double* info,
+                              uint8_t* failed, float* obs_ring, int32_t steps, const FlexBurstMlp* mlp,
+                              const FlexBurstSafety* safety, void* stream) {
+    // every argument check comes before the first HIP call
+    if (!mlp || !mlp->fc2_w || !mlp->fc2_b) return FLEX_EINVAL;
+    // (what the shared checks refuse too — the ring's size must be the env's — read off the actor: no handle is followed yet)
+    if (!actor || actor->n_agents > 5 || steps < 1 || steps >= actor->ring_slabs || (safety && actor->act_dim != 4)) return FLEX_EINVAL;
+    return burst_plain_launch(e, actor, reward, done, info, failed, obs_ring, steps, safety, mlp, stream);
 }
 
 // The argument checks of flexenv_rollout_burst_summed, shared with the MLP form (no HIP call).

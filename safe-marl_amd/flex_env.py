@@ -359,7 +359,21 @@ class VecFlexProvisionEnv:
                                                              C.byref(sg) if sg is not None else None, _stream()),
                    who)
 
-    TEST_TRACE = (("actions", torch.float32), ("v", torch.float64), ("agent", torch.float64), ("row", torch.int32),
+    def rollout_burst_mlp(self, actor_args, mlp, steps, obs_ring, safety=None):
+        """``rollout_burst`` for a shared MLP actor (include/flexenv.h: flexenv_rollout_burst_mlp; MADDPG / SAFEMADDPG with
+        agent_type mlp): ``actor_args`` and ``mlp`` (a ``_lib.FlexBurstMlp`` with the second layer, or None for the library's
+        refusal) from ``nets.mlp_burst_actor_args`` with ``rng_state``, ``std`` and the action range — the output head in the fc2
+        slot, no GRU tensors; the env's obs ring and replay sink configured as for ``rollout_burst`` (the sink's aux_counter is
+        the noise stream's step counter).  ``safety``: as in ``rollout_burst``."""
+        self.calls += int(steps)
+        sf = self._burst_safety(safety, "rollout_burst_mlp") if safety is not None else None
+        _lib.check(self.lib.flexenv_rollout_burst_mlp(self.handle, C.byref(actor_args), _ptr(self.reward), _ptr(self.done),
+                                                      _ptr(self.info), _ptr(self.failed), _ptr(obs_ring), int(steps),
+                                                      C.byref(mlp) if mlp is not None else None,
+                                                      C.byref(sf) if sf is not None else None, _stream()),
+                   "flexenv_rollout_burst_mlp")
+
+    TEST_TRACE =(("actions", torch.float32), ("v", torch.float64), ("agent", torch.float64), ("row", torch.int32),
                   ("reward", torch.float64), ("info", torch.float64), ("flags", torch.uint8))
 
     def test_out(self, steps, trace=False):

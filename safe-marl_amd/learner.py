@@ -158,7 +158,32 @@ class RolloutGraph:
                               and os.environ.get("FLEX_MLP_BURST", "1") != "0")
         if self.mlp_burst:
             self.summed_sink = False                  # (the three-launch form is the RNN agent's: there is no second form here)
-        if self.sink or self.summed_sink or self.gauss_burst or self.mlp_burst:
+        # agent_type mlp under MADDPG / SAFEMADDPG (include/flexenv.h: flexenv_rollout_burst_mlp): the plain burst below — in-kernel
+        # noise stream, exploration epilogue, SAFEMADDPG's projection as a phase of the launch — with the MLP's policy tiles.  One
+        # form only, as `mlp_burst`: every vector step, a single one too, through the one launch; the env configured as for `sink`
+        # with the noise stream's aux_counter, the replay in row mode.  `fast` stays off (it is the RNN agent's two-launch body),
+        # and without this flag (FLEX_MLP_BURST=0) the general body at the bottom of body() runs Model.policy as before.
+        own_get_actions = SAFEMADDPG.get_actions if self.safe else MADDPG.get_actions
+        self.mlp_plain_burst = bool(type(model).__name__ in ("MADDPG", "SAFEMADDPG")
+                                    and type(model).get_actions is own_get_actions
+                                    and bool(model.args.action_enforcebound) and not self.gaussian
+                                    and model.fused_inference and model.args.shared_params and env.obs.is_cuda
+                                    and type(agent0) is MLPAgent
+                                    and model.args.hid_size == 64 and model.args.hid_activation == "relu" and h == 64
+                                    and n <= 5 and o % 4 == 0 and o <= 144 and (not self.safe or a == 4)
+                                    and n * a <= 32 and n * h <= 384 and two_per_wave
+                                    and self.rows_capable and self.cursor_stepped and hasattr(env, "set_replay_sink")
+                                    and hasattr(getattr(env, "vec", env), "rollout_burst_mlp")
+                                    and not (self.safe and model.intended_actions)
+                                    and os.environ.get("FLEX_ROLLOUT_BURST", "1") != "0"
+                                    and os.environ.get("FLEX_MLP_BURST", "1") != "0")
+        if self.mlp_plain_burst:
+            self.means_buf = th.zeros(N * n, a, device=dev)
+            self.burst_env_act = th.zeros(N * n, a, device=dev)
+            if self.safe:
+                self.burst_adjusted = th.zeros(N, 4 * n, dtype=th.float64, device=dev)
+                self.burst_safe_env_act = th.zeros(N, 4 * n, device=dev)
+        if self.sink or self.summed_sink or self.gauss_burst or self.mlp_burst or self.mlp_plain_burst:
             self.act_buf = th.zeros(N * n, a, device=dev)
             self.hid_buf = th.zeros(N * n, h, device=dev)
             self.acc = th.zeros(N, 10, dtype=th.float64, device=dev)
@@ -207,7 +232,7 @@ class RolloutGraph:
             env.set_obs_ring(buf.cursor[1:], row_stride, buf.slabs)
             env.set_replay_sink(self.act_buf, self.hid_buf, buf.small_ring, buf.hid_ring, self.acc, cursor_out=buf.cursor[0:1],
                                 aux_counter=None if (self._torch_noise or self.summed_sink or self.gauss_burst or self.mlp_burst)
-                                else self.rng_state[1:2])
+                                else self.rng_state[1:2])         # (mlp_plain_burst: always the noise stream's counter)
         else:
             env.set_step_counter(buf.cursor[1:], buf.slabs)
             if self.ring_active:
@@ -221,6 +246,8 @@ class RolloutGraph:
 
     @fast.setter
     def fast(self, value):
+        if self.mlp_plain_burst and value:
+            raise RuntimeError("fast is the RNN agent's two-launch body: the MLP agent's rollout has the burst launch only")
         self._fast = bool(value)
         self._configure_env()
 
@@ -230,16 +257,20 @@ class RolloutGraph:
 
     @torch_noise.setter
     def torch_noise(self, value):
+        if self.mlp_plain_burst and value:
+            raise RuntimeError("torch_noise: the MLP agent's burst draws in the kernel and has no second form")
         self._torch_noise = bool(value)
         self._configure_env()
 
     @property
     def sink_active(self):
-        return (self.sink and self.fast) or self.summed_sink or self.gauss_burst or self.mlp_burst
+        return (self.sink and self.fast) or self.summed_sink or self.gauss_burst or self.mlp_burst or self.mlp_plain_burst
 
     @property
     def fused_burst(self):
         if self.summed_burst or self.gauss_burst or self.mlp_burst:       # (their draws are torch's own: torch_noise gates the plain form only)
+            return True
+        if self.mlp_plain_burst:                                          # (one form only; its setters refuse torch_noise and fast)
             return True
         return (self.burst_launch and self.sink_active and not self._torch_noise
                 and not (self.safe and self.model.intended_actions))       # (that routing transposes in torch)
@@ -261,7 +292,7 @@ class RolloutGraph:
     @property
     def ring_active(self):
         # (tests switch `fast` off to run the general body on the same object)
-        return (self.ring_io and self.fast) or self.summed_sink or self.gauss_burst or self.mlp_burst
+        return (self.ring_io and self.fast) or self.summed_sink or self.gauss_burst or self.mlp_burst or self.mlp_plain_burst
 
     @property
     def obs(self):
@@ -362,6 +393,28 @@ class RolloutGraph:
                 if not self.sink_active:
                     self._pack(action, hid)
                 return
+        if self.mlp_plain_burst:
+            if self.safe and m.intended_actions:
+                raise RuntimeError("SAFEMADDPG.intended_actions was switched on after construction: that routing is not in "
+                                   "the MLP agent's burst launch, which has no second form")
+            # the MLP policy with its exploration epilogue (noise drawn in the kernel: torch's generator is not touched), the
+            # safety projection (SAFEMADDPG) and the environment for `burst` steps — or ONE step: the same launch, there is no
+            # second form — in one persistent launch (include/flexenv.h: flexenv_rollout_burst_mlp).  Model.policy is not called.
+            buf, k = self.buf, burst or 1
+            vec = env.vec if hasattr(env, "vec") else env
+            args, mlp = mlp_burst_actor_args(m.policy_dicts[0], N, m.n_, m.obs_dim, m.args.agent_id, ring_cursor=buf.cursor,
+                                             cursor_out=buf.cursor[1:], obs_source=self.obs_src, ring_slabs=buf.slabs,
+                                             hidden_out=self.hid_buf, means=self.means_buf, rng_state=self.rng_state,
+                                             std=self.std, action_low=m.args.action_low, action_high=m.args.action_high)
+            # (what the epilogue writes: the action the sink files, the action the step — or the projection — reads)
+            args.action, args.env_action = self.act_buf.data_ptr(), self.burst_env_act.data_ptr()
+            safety = None
+            if self.safe:                  # safemaddpg.py:90-111 inside the launch, as in the RNN agent's burst
+                s_p, s_q, beta = self.predictor
+                safety = dict(s_p=s_p, s_q=s_q, beta=beta, v_min=m.V_min, v_max=m.V_max, adjusted=self.burst_adjusted,
+                              env_action=self.burst_safe_env_act, act_low=m.args.action_low, act_high=m.args.action_high)
+            vec.rollout_burst_mlp(args, mlp, k, buf.row_ring, safety=safety)
+            return
         if self.gauss_burst:
             with th.no_grad():
                 # policy with both heads, per-sample selection and environment for `burst` steps — or ONE step: the same launch,
@@ -591,7 +644,7 @@ class RolloutGraph:
             self._hid.zero_()
             self.buf.begin_stream(first_obs)
         self._info_sum.zero_(); self._rew_sum.zero_(); self._fail_sum.zero_()
-        if self.sink or self.summed_sink or self.gauss_burst or self.mlp_burst:
+        if self.sink or self.summed_sink or self.gauss_burst or self.mlp_burst or self.mlp_plain_burst:
             self.acc.zero_()
 
 

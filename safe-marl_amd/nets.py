@@ -1610,11 +1610,13 @@ def mlp_burst_declines(agent, n_agents, obs_dim, agent_id):
 
 
 def mlp_burst_actor_args(agent, n_envs, n_agents, obs_dim, agent_id, ring_cursor, cursor_out, obs_source, ring_slabs, hidden_out,
-                         means):
+                         means, rng_state=None, std=None, action_low=None, action_high=None):
     """The ring-form FlexActorArgs of the rollout burst for a shared MLPAgent (include/flexenv.h:
     flexenv_rollout_burst_summed_mlp) — the sibling of what ``fused_actor_forward(..., launch=...)`` fills for the RNN agent:
     same ring, cursor and ``obs_source`` fields, the output head (``fc3``, the Gaussian agent's ``mean``) in the fc2 slot, no GRU
-    tensors and no ``hidden_in``.  Returns (args, FlexBurstMlp with the second layer).  Raises when the agent is outside what
+    tensors and no ``hidden_in``.  ``rng_state`` (with ``std``, ``action_low``, ``action_high``): what the exploration epilogue
+    of flexenv_rollout_burst_mlp needs — the noise stream's [seed, step] cell, the fixed std and the action range; the agent-summed
+    forms leave them out.  Returns (args, FlexBurstMlp with the second layer).  Raises when the agent is outside what
     the launch covers: the caller admitted the configuration, and there is no other form to fall back to."""
     why = mlp_burst_declines(agent, n_agents, obs_dim, agent_id)
     if why is not None:
@@ -1633,6 +1635,13 @@ def mlp_burst_actor_args(agent, n_envs, n_agents, obs_dim, agent_id, ring_cursor
     args.obs, args.obs_pushed = obs_source.ring, obs_source.pushed
     args.obs_row_stride, args.obs_pushed_stride = obs_source.row_stride, obs_source.pushed_stride
     args.obs_slots, args.obs_slot_w = obs_source.slots, obs_source.slot_w
+    if rng_state is not None:
+        if not (rng_state.dtype == th.int64 and rng_state.numel() == 2 and rng_state.is_contiguous()):
+            raise ValueError("rng_state must be a contiguous int64 tensor [seed, step]")
+        if std is None or action_low is None or action_high is None:
+            raise ValueError("the exploration epilogue needs std, action_low and action_high next to rng_state")
+        args.rng_state = rng_state.data_ptr()
+        args.std, args.action_low, args.action_high = float(std), float(action_low), float(action_high)
     mlp = _lib.FlexBurstMlp()
     mlp.fc2_w, mlp.fc2_b = fc2_w.data_ptr(), fc2_b.data_ptr()
     return args, mlp

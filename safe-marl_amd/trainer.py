@@ -769,7 +769,11 @@ class PGTrainer(object):
                 self.graph_audit[kind] = audit_graph_body(lambda: self._sub_update(which, {}, batch, fresh_leaves=True, flat=flat))
             side = th.cuda.Stream()
             side.wait_stream(th.cuda.current_stream())
-            with th.cuda.stream(side):
+            # (under _graph_audit, as RolloutGraph.capture and _capture_bootstrap: the warm-up runs the body the capture will run.
+            #  An MLP agent's passes stand aside for a capture (nets.mlp_actor_allowed) and run the module composition there; with a
+            #  warm-up on the launches instead, a process whose rollout runs no library GEMM — the MLP agent's burst launch — met
+            #  the library's first-call set-up inside the capture, where it is refused and the process ends.)
+            with th.cuda.stream(side), _graph_audit():
                 for _ in range(2):                        # warm-up off the capturing stream (allocator, rocBLAS handles)
                     self._sub_update(which, out, batch, fresh_leaves=True, flat=flat)
             th.cuda.current_stream().wait_stream(side)
