@@ -404,6 +404,22 @@ typedef struct {
 } FlexTestOut;
 int flexenv_test_episodes(FlexEnv* env, const FlexActorArgs* actor, int32_t steps, int32_t summed,
                           const FlexBurstSafety* safety /* or NULL */, const FlexTestOut* out, void* stream);
+/* flexenv_test_episodes for a shared MLP actor (agent_type: mlp; madrl/agents/mlp_agent.py:5-32, mlp_agent_gaussian.py:7-41 in
+ * test mode): the episode, the record, `safety`, `summed`, the environment phase, the restart and what is left alone are
+ * flexenv_test_episodes's; the policy tiles are flexenv_rollout_burst_mlp's — fc1 -> LayerNorm -> ReLU, h = relu(fc2 x + b)
+ * with `mlp->fc2_w` / `fc2_b` on the matrix cores where the GRU cell stands, then the head in actor->fc2_w / fc2_b
+ * (MLPAgent.fc3, MLPAgentGaussian.mean) — with the same means and h on the same weights and observations, bit for bit, under
+ * the test epilogue: action = tanh(mean), translate_action, no noise.
+ * Read: actor->fc1_w / fc1_b, ln_w / ln_b (with layernorm), fc2_w / fc2_b (the head), mlp->fc2_w / fc2_b, the shapes, the
+ * action range, the environment's own observation history.  Written: actor->means, action, env_action and hidden_out
+ * ([rows, 64]: h of the step, on EVERY step — the policy carries no state, so nothing alternates), the record in `out`.
+ * NOT read: actor->hidden_in, w_ih, w_hh, b_ih, b_hh (they may be NULL; hidden_in is neither read, written nor cleared),
+ * rng_state, noise, cursor, cursor_out, ring_slabs, and everything flexenv_test_episodes leaves alone.
+ * FLEX_EINVAL (before any HIP call): everything flexenv_test_episodes refuses, the GRU pointers and hidden_in excepted; `mlp`,
+ * fc2_w or fc2_b missing.  FLEXNET_EUNSUPPORTED: as flexenv_test_episodes. */
+int flexenv_test_episodes_mlp(FlexEnv* env, const FlexActorArgs* actor, int32_t steps, int32_t summed,
+                              const FlexBurstMlp* mlp, const FlexBurstSafety* safety /* or NULL */,
+                              const FlexTestOut* out, void* stream);
 int32_t flexenv_obs_size(const FlexEnv* env);    /* 6*history, env:71 */
 int32_t flexenv_state_size(const FlexEnv* env);  /* env:72 */
 

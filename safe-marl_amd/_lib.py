@@ -73,7 +73,7 @@ class ResetSpec(C.Structure):
 # every symbol include/flexenv.h declares
 SYMBOLS = (
     "flexenv_create", "flexenv_destroy", "flexenv_reset", "flexenv_step", "flexenv_step_many", "flexenv_obs", "flexenv_obs_view", "flexenv_obs_source", "flexenv_state",
-    "flexenv_peek", "flexenv_poke", "flexenv_num_envs", "flexenv_set_step_counter", "flexenv_set_obs_ring", "flexenv_set_replay_sink", "flexenv_rollout_burst", "flexenv_rollout_burst_summed", "flexenv_rollout_burst_summed_gauss", "flexenv_rollout_burst_summed_mlp", "flexenv_rollout_burst_mlp", "flexenv_test_episodes", "flexenv_obs_size", "flexenv_state_size",
+    "flexenv_peek", "flexenv_poke", "flexenv_num_envs", "flexenv_set_step_counter", "flexenv_set_obs_ring", "flexenv_set_replay_sink", "flexenv_rollout_burst", "flexenv_rollout_burst_summed", "flexenv_rollout_burst_summed_gauss", "flexenv_rollout_burst_summed_mlp", "flexenv_rollout_burst_mlp", "flexenv_test_episodes", "flexenv_test_episodes_mlp", "flexenv_obs_size", "flexenv_state_size",
     "pf_solve_batch", "flexenv_safety_project", "flexenv_safety_project_env", "flexenv_version", "flexenv_abi_version",
     "flexnet_actor_forward", "flexnet_critic_tail_forward", "flexnet_critic_tail_backward", "flexnet_rollout_pack", "flexnet_wgrad", "flexnet_lnrelu_forward", "flexnet_lnrelu_backward", "flexnet_clip_rmsprop", "flexnet_clip_rmsprop_refresh", "flexnet_td_loss", "flexnet_td_stats", "flexnet_critic_td_backward", "flexnet_critic_td_backward_phases", "flexnet_wgrad_critic_finish",
     "flexnet_scaled_sum", "flexnet_agent_sum_explore", "flexnet_gather_rows", "flexnet_gather_rows_td", "flexnet_window_refresh", "flexnet_gather_window", "flexnet_gather_episodes", "flexnet_linear2", "flexnet_gru_backward",
@@ -613,6 +613,9 @@ def load():
     lib.flexenv_rollout_burst_mlp.restype = C.c_int
     lib.flexenv_test_episodes.argtypes = [vp, C.POINTER(FlexActorArgs), i32, i32, C.POINTER(FlexBurstSafety), C.POINTER(FlexTestOut), vp]
     lib.flexenv_test_episodes.restype = C.c_int
+    lib.flexenv_test_episodes_mlp.argtypes = [vp, C.POINTER(FlexActorArgs), i32, i32, C.POINTER(FlexBurstMlp), C.POINTER(FlexBurstSafety),
+                                              C.POINTER(FlexTestOut), vp]
+    lib.flexenv_test_episodes_mlp.restype = C.c_int
     lib.flexnet_critic_td_backward.argtypes = [C.POINTER(FlexCriticTailArgs), C.POINTER(FlexTdLossArgs), vp]
     lib.flexnet_critic_td_backward.restype = C.c_int
     lib.flexnet_critic_td_backward_phases.argtypes = [C.POINTER(FlexCriticTailArgs), C.POINTER(FlexTdLossArgs), i32, vp]

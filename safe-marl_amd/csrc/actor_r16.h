@@ -590,12 +590,13 @@ __device__ __forceinline__ void r16_stage_simple(const FlexActorArgs& a, ActorLd
 // a.hidden_in is not read; h goes to a.hidden_out as the new hidden state (MLPAgent.forward returns it as such) and into the head.
 // MLP with NOISE (flexenv_rollout_burst_mlp: MADDPG / SAFEMADDPG): the same policy tiles under the exploration epilogue of the
 // RNN form — wavefront 3 draws as ever, s.noise is a region of its own that the MLP image (front of wg, gb[0 .. 127]) leaves alone.
+// MLP with TEST (flexenv_test_episodes_mlp): the same policy tiles under the TEST epilogue.  The policy carries no state, so
+// nothing alternates: h goes to a.hidden_out on every step and a.hidden_in is not touched.
 template <bool TEST = false, bool NOISE = !TEST, bool LOGSTD = false, bool MLP = false, typename EnvStep, typename Mark>
 __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds16B& s, const int n_steps, EnvStep&& env_step,
                                                 Mark&& mark, const R16LogStd* ls = nullptr, const R16Mlp* mlp = nullptr) {
     static_assert(!(TEST && NOISE), "test mode draws no noise");
     static_assert(!LOGSTD || (!TEST && !NOISE), "the log-std head rides on the means-only ring form");
-    static_assert(!MLP || !TEST, "the MLP actor rides on the ring forms");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int j = lane & 15, g = lane >> 4;
     const int grp = wave >> 2, w = wave & 3;
@@ -649,7 +650,7 @@ __device__ __forceinline__ void actor_r16_burst(const FlexActorArgs& a, ActorLds
             if constexpr (!MLP)
                 hid_p = (TEST ? ((step & 1) ? a.hidden_out : a.hidden_in) : a.hidden_in + slab * a.hid_slab_stride) +
                         (int64_t)row * HID + 4 * g;
-            float* const hid_o = TEST && (step & 1) ? const_cast<float*>(a.hidden_in) : a.hidden_out;
+            float* const hid_o = TEST && !MLP && (step & 1) ? const_cast<float*>(a.hidden_in) : a.hidden_out;
             f32x4 xq[FLEXNET_MAX_OBS / 16], hv[4], x[4], hnew[4];
             {
                 // (the loads of actor_r16_body: whole-slab descriptor, a 16-column group behind obs_dim reads what follows the

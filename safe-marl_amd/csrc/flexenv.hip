@@ -1534,6 +1534,8 @@ struct TestArgs {
     float* safe_env_action;
     float act_low, act_span;
     FlexTestOut out;
+    // flexenv_test_episodes_mlp: the second layer of a shared MLPAgent (actor_r16_burst's MLP); act.fc2_* are then the output head
+    R16Mlp mlp;
 };
 
 template <int MODE>
@@ -1634,6 +1636,21 @@ void flex_test_episodes_kernel(TestArgs b) {
     auto env_step = [&](int64_t step, int) { flex_test_env_step<MODE>((int)step, (unsigned)kb, (unsigned)(kb >> 32), alive); };
     actor_r16_burst<true>(b.act, s, b.n_steps, env_step, [](int, int) {});
 }
+
+// flexenv_test_episodes_mlp: the three forms with a shared MLPAgent in the policy phase (actor_r16_burst<TEST, MLP>), the
+// environment phase as it stands.  A namespace of its own: the three kernels above are the whole of
+// flex_test_episodes_kernel<...>, whose resource figures tests pin by that prefix.
+namespace test_mlp {
+template <int MODE>
+__global__ __launch_bounds__(64 * R16_W)
+void flex_test_episodes_kernel(TestArgs b) {
+    __shared__ ActorLds16B s;
+    const unsigned long long kb = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
+    int alive = 1;
+    auto env_step = [&](int64_t step, int) { flex_test_env_step<MODE>((int)step, (unsigned)kb, (unsigned)(kb >> 32), alive); };
+    actor_r16_burst<true, false, false, true>(b.act, s, b.n_steps, env_step, [](int, int) {}, nullptr, &b.mlp);
+}
+}  // namespace test_mlp
 
 // -------------------------------------------------------------------------------------------------
 // host side
@@ -2267,8 +2284,10 @@ int flexenv_rollout_burst_summed_mlp(FlexEnv* e, const FlexActorArgs* actor, dou
     return burst_summed_finish(e, *actor, steps, s);
 }
 
-int flexenv_test_episodes(FlexEnv* e, const FlexActorArgs* actor, int32_t steps, int32_t summed, const FlexBurstSafety* safety,
-                          const FlexTestOut* out, void* stream) {
+// flexenv_test_episodes and its MLP form: the checks (no HIP call before the last of them), the record's reset and the launch.
+// `mlp` non-NULL: the policy phase is the MLPAgent's — no GRU tensors, no hidden_in (neither read nor cleared).
+static int test_episodes_launch(FlexEnv* e, const FlexActorArgs* actor, int32_t steps, int32_t summed, const FlexBurstSafety* safety,
+                                const FlexTestOut* out, const FlexBurstMlp* mlp, void* stream) {
     // every argument check comes before the first HIP call
     if (!actor || !out || !out->sums || !out->length || steps < 1 || (summed != 0 && summed != 1)) return FLEX_EINVAL;
     const FlexActorArgs& p = *actor;
@@ -2281,8 +2300,8 @@ int flexenv_test_episodes(FlexEnv* e, const FlexActorArgs* actor, int32_t steps,
     if (p.obs_dim > FLEXNET_MAX_OBS || (p.obs_dim & 3) || e->hnet.epw != 2) return FLEXNET_EUNSUPPORTED;
     // the environment step reads four controls per building (env:260)
     if (p.rows != (int64_t)e->n_envs * na || p.n_agents != na || p.obs_dim != 6 * e->cfg.history || p.act_dim != 4) return FLEX_EINVAL;
-    if (!p.hidden_in || !p.hidden_out || p.hidden_in == p.hidden_out || !p.means || !p.action || !p.env_action ||
-        !p.fc1_w || !p.fc1_b || !p.w_ih || !p.w_hh || !p.b_ih || !p.b_hh || !p.fc2_w || !p.fc2_b ||
+    if (!mlp && (!p.hidden_in || p.hidden_in == p.hidden_out || !p.w_ih || !p.w_hh || !p.b_ih || !p.b_hh)) return FLEX_EINVAL;
+    if (!p.hidden_out || !p.means || !p.action || !p.env_action || !p.fc1_w || !p.fc1_b || !p.fc2_w || !p.fc2_b ||
         (p.layernorm && (!p.ln_w || !p.ln_b)) || p.save_z1 || !(p.action_high >= p.action_low)) return FLEX_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     const int64_t N = e->n_envs;
@@ -2308,16 +2327,39 @@ int flexenv_test_episodes(FlexEnv* e, const FlexActorArgs* actor, int32_t steps,
         b.adjusted = safety->adjusted; b.safe_env_action = safety->env_action;
         b.act_low = safety->act_low; b.act_span = safety->act_high - safety->act_low;
     }
-    // the recurrent state starts at zero (model.py:271), every episode's record at nothing
-    HIP_TRY(hipMemsetAsync(const_cast<float*>(p.hidden_in), 0, (size_t)p.rows * HID * sizeof(float), s));
+    if (mlp) {
+        b.mlp.w = mlp->fc2_w; b.mlp.b = mlp->fc2_b;
+        // (no GRU cell and no carried state: whatever the caller left in these is not read)
+        b.act.hidden_in = nullptr; b.act.w_ih = b.act.w_hh = b.act.b_ih = b.act.b_hh = nullptr;
+    } else {
+        // the recurrent state starts at zero (model.py:271)
+        HIP_TRY(hipMemsetAsync(const_cast<float*>(p.hidden_in), 0, (size_t)p.rows * HID * sizeof(float), s));
+    }
+    // every episode's record starts at nothing
     HIP_TRY(hipMemsetAsync(out->sums, 0, (size_t)N * 10 * sizeof(double), s));
     HIP_TRY(hipMemsetAsync(out->length, 0, (size_t)N * sizeof(int32_t), s));
     const dim3 grid((e->n_envs + 15) / 16), block(64 * R16_W);
-    if (safety) hipLaunchKernelGGL((flex_test_episodes_kernel<1>), grid, block, 0, s, b);
+    if (mlp) {
+        if (safety) hipLaunchKernelGGL((test_mlp::flex_test_episodes_kernel<1>), grid, block, 0, s, b);
+        else if (summed) hipLaunchKernelGGL((test_mlp::flex_test_episodes_kernel<2>), grid, block, 0, s, b);
+        else hipLaunchKernelGGL((test_mlp::flex_test_episodes_kernel<0>), grid, block, 0, s, b);
+    } else if (safety) hipLaunchKernelGGL((flex_test_episodes_kernel<1>), grid, block, 0, s, b);
     else if (summed) hipLaunchKernelGGL((flex_test_episodes_kernel<2>), grid, block, 0, s, b);
     else hipLaunchKernelGGL((flex_test_episodes_kernel<0>), grid, block, 0, s, b);
     HIP_TRY(hipGetLastError());
     return FLEX_OK;
+}
+
+int flexenv_test_episodes(FlexEnv* e, const FlexActorArgs* actor, int32_t steps, int32_t summed, const FlexBurstSafety* safety,
+                          const FlexTestOut* out, void* stream) {
+    return test_episodes_launch(e, actor, steps, summed, safety, out, nullptr, stream);
+}
+
+int flexenv_test_episodes_mlp(FlexEnv* e, const FlexActorArgs* actor, int32_t steps, int32_t summed, const FlexBurstMlp* mlp,
+                              const FlexBurstSafety* safety, const FlexTestOut* out, void* stream) {
+    // every argument check comes before the first HIP call
+    if (!mlp || !mlp->fc2_w || !mlp->fc2_b) return FLEX_EINVAL;
+    return test_episodes_launch(e, actor, steps, summed, safety, out, mlp, stream);
 }
 
 int flexenv_obs(FlexEnv* e, void* obs, int32_t obs_dtype, void* stream) {

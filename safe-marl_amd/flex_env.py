@@ -388,13 +388,16 @@ class VecFlexProvisionEnv:
                 out[k] = torch.zeros(shapes[k], dtype=dt, device=dev)
         return out
 
-    def test_episodes(self, actor_args, steps, summed=False, safety=None, out=None):
+    def test_episodes(self, actor_args, steps, summed=False, safety=None, out=None, mlp=None):
         """One TEST-mode episode per environment — policy (tanh(mean), no noise), optional safety projection or agent-summed
         selection, environment step — for ``steps`` steps in ONE launch (include/flexenv.h: flexenv_test_episodes), from the
         state ``reset`` left.  ``actor_args``: the FlexActorArgs of the policy (nets.fused_actor_forward builds it; hidden_in
         and hidden_out are the two slabs the recurrent state alternates between).  ``safety``: as in ``rollout_burst``.
         ``out``: ``test_out(steps, trace)`` (default: no trace).  Returns ``out``, or None where the library declines the shape
-        (FLEXNET_EUNSUPPORTED).  The environments are left to be reset by the caller."""
+        (FLEXNET_EUNSUPPORTED).  The environments are left to be reset by the caller.
+        ``mlp``: a ``_lib.FlexBurstMlp`` (with ``actor_args`` from ``nets.mlp_test_actor_args``) takes the launch of a shared MLP
+        actor (flexenv_test_episodes_mlp): the output head in the fc2 slot, no GRU tensors, no hidden_in, h of every step in
+        hidden_out."""
         steps = int(steps)
         if out is None:
             out = self.test_out(steps)
@@ -409,11 +412,15 @@ class VecFlexProvisionEnv:
                 raise ValueError(f"test_episodes: {k} must be a contiguous {want[k]} device tensor of {n} elements")
             setattr(rec, k, t.data_ptr())
         sf = self._burst_safety(safety, "test_episodes") if safety is not None else None
-        rc = self.lib.flexenv_test_episodes(self.handle, C.byref(actor_args), steps, int(bool(summed)),
-                                            C.byref(sf) if sf is not None else None, C.byref(rec), _stream())
+        if mlp is not None:
+            rc = self.lib.flexenv_test_episodes_mlp(self.handle, C.byref(actor_args), steps, int(bool(summed)), C.byref(mlp),
+                                                    C.byref(sf) if sf is not None else None, C.byref(rec), _stream())
+        else:
+            rc = self.lib.flexenv_test_episodes(self.handle, C.byref(actor_args), steps, int(bool(summed)),
+                                                C.byref(sf) if sf is not None else None, C.byref(rec), _stream())
         if rc == _lib.FLEXNET_EUNSUPPORTED:
             return None
-        _lib.check(rc, "flexenv_test_episodes")
+        _lib.check(rc, "flexenv_test_episodes_mlp" if mlp is not None else "flexenv_test_episodes")
         self.calls += steps
         return out
 

@@ -22,7 +22,7 @@ import torch as th
 import torch.nn as nn
 
 from .nets import (WGRAD_MIN_ROWS, AttentionCritic, attn_critic, CriticTail, critic_first_layer, critic_td_loss, critic_td_loss_supported, critic_policy_loss,
-                   critic_policy_loss_supported, expand_agents, MLPAgent, MLPAgentGaussian, MLPCritic, mlp_burst_actor_args, RNNAgent, RNNAgentGaussian, critic_policy_supported, critic_replayed_supported,
+                   critic_policy_loss_supported, expand_agents, MLPAgent, MLPAgentGaussian, MLPCritic, mlp_burst_actor_args, mlp_burst_declines, mlp_test_actor_args, RNNAgent, RNNAgentGaussian, critic_policy_supported, critic_replayed_supported,
                    critic_tail_supported, fused_actor_forward, fused_actor_forward_unshared, actor_unshared_supported,
                    actor_mlp_declines, actor_mlp_train, fused_actor_forward_mlp, mlp_actor_allowed,
                    actor_mlp_unshared_declines, actor_mlp_unshared_train, fused_actor_forward_mlp_unshared,
@@ -684,13 +684,19 @@ def episode_stats(sums, length):
 
 
 def one_launch_declines(model):
-    """None where ``Model.test_episodes`` may take the single launch (flexenv_test_episodes), else the reason — decided from the
-    model's class and arguments alone, whatever the device."""
+    """None where ``Model.test_episodes`` may take the single launch (flexenv_test_episodes for a shared RNN actor,
+    flexenv_test_episodes_mlp for a shared MLP one), else the reason — decided from the model's class and arguments, whatever
+    the device, and from one switch of the process environment, read at every call: FLEX_MLP_TEST_LAUNCH=1 admits the MLP
+    agent (unset or 0: it keeps the loop)."""
     args = model.args
     if not args.shared_params:
         return "shared_params is False: the launch stages one shared actor"
-    if args.agent_type != "rnn" or not isinstance(model.policy_dicts[0], RNNAgent):
-        return f"agent_type {args.agent_type}: the launch holds the RNN actor's tiles"
+    # agent_type mlp (include/flexenv.h: flexenv_test_episodes_mlp) is opt-in: FLEX_MLP_TEST_LAUNCH=1, read at every call
+    mlp = (args.agent_type == "mlp" and type(model.policy_dicts[0]) in (MLPAgent, MLPAgentGaussian)
+           and os.environ.get("FLEX_MLP_TEST_LAUNCH", "0") == "1")
+    if not mlp and (args.agent_type != "rnn" or not isinstance(model.policy_dicts[0], RNNAgent)):
+        hint = " (FLEX_MLP_TEST_LAUNCH=1 admits a shared MLP agent)" if args.agent_type == "mlp" else ""
+        return f"agent_type {args.agent_type}: the launch holds the RNN actor's tiles" + hint
     if args.hid_size != 64 or args.hid_activation != "relu":
         return f"hid_size {args.hid_size} / hid_activation {args.hid_activation}: the tiles are built for 64 relu units"
     if model.obs_dim > 144 or model.obs_dim % 4:
@@ -1523,7 +1529,8 @@ class Model(nn.Module):
         return TestEpisodes(out, first, launch=False)
 
     def _test_episodes_launch(self, vec, spec, trace, steps):
-        """flexenv_test_episodes on the model's shared RNN actor; None where the library declines the shape."""
+        """flexenv_test_episodes on the model's shared RNN actor — flexenv_test_episodes_mlp on a shared MLP one
+        (``one_launch_declines`` admitted it); None where the library declines the shape."""
         N, n, a = vec.n_envs, self.n_, self.act_dim
         obs = vec.reset(spec=spec)                 # (pushes every first observation: the launch reads the history in place)
         out = vec.test_out(steps, trace)
@@ -1537,6 +1544,19 @@ class Model(nn.Module):
                           env_action=th.empty(N, 4 * n, dtype=th.float32, device=vec.device),
                           act_low=self.args.action_low, act_high=self.args.action_high)
         summed = own is MATD3.get_actions or own is IDDPG.get_actions
+        agent = self.policy_dicts[0]
+        if type(agent) in (MLPAgent, MLPAgentGaussian):
+            # (parameters the kernels cannot read through a raw pointer — not fp32, not contiguous: the loop, as the RNN form)
+            if mlp_burst_declines(agent, n, self.obs_dim, self.args.agent_id) is not None:
+                return None
+            # no carried state and no GRU tensors: the output head in the fc2 slot, h of every step in `hid`
+            hid = th.empty(N * n, 64, device=vec.device)
+            means, action, env_action = (th.empty(N * n, a, device=vec.device) for _ in range(3))
+            args, mlp = mlp_test_actor_args(agent, N, n, self.obs_dim, self.args.agent_id, hid, means, action, env_action,
+                                            self.args.action_low, self.args.action_high)
+            if vec.test_episodes(args, steps, summed=summed, safety=safety, out=out, mlp=mlp) is None:
+                return None
+            return TestEpisodes(out, first, launch=True)
         done = []
         res = fused_actor_forward(self.policy_dicts[0], obs.view(N, n, -1), th.zeros(N * n, 64, device=vec.device), n,
                                   self.args.agent_id, noise=th.zeros(N, n, a, device=vec.device), std=0.0,

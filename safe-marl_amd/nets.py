@@ -1609,6 +1609,28 @@ def mlp_burst_declines(agent, n_agents, obs_dim, agent_id):
     return _params_decline(_actor_mlp_params(agent))
 
 
+def _mlp_launch_args(agent, n_envs, n_agents, obs_dim, agent_id, outputs):
+    """What the MLP forms of the persistent launches share: ``mlp_burst_declines`` (raises on a reason — the caller admitted the
+    configuration, and there is no other form to fall back to), a FlexActorArgs with the shapes, the first layer, the LayerNorm
+    pair, the output head (``fc3``, the Gaussian agent's ``mean``) in the fc2 slot and ``outputs`` (name -> contiguous tensor),
+    no GRU tensors and no ``hidden_in``; and the FlexBurstMlp with the second layer."""
+    why = mlp_burst_declines(agent, n_agents, obs_dim, agent_id)
+    if why is not None:
+        raise RuntimeError(f"the burst's MLP policy does not cover this agent: {why}")
+    fc1_w, fc1_b, ln_w, ln_b, fc2_w, fc2_b, head_w, head_b = _actor_mlp_params(agent)
+    args = _lib.FlexActorArgs()
+    args.rows, args.n_agents, args.obs_dim, args.act_dim = n_envs * n_agents, n_agents, obs_dim, agent.args.action_dim
+    args.agent_id, args.layernorm, args.ln_eps = int(bool(agent_id)), int(ln_w is not None), _ln_eps(agent)
+    for name, t in (("fc1_w", fc1_w), ("fc1_b", fc1_b), ("ln_w", ln_w), ("ln_b", ln_b), ("fc2_w", head_w), ("fc2_b", head_b),
+                    *outputs.items()):
+        if t is not None and not t.is_contiguous():
+            raise RuntimeError(f"the burst's MLP policy: non-contiguous {name}")
+        setattr(args, name, None if t is None else t.data_ptr())
+    mlp = _lib.FlexBurstMlp()
+    mlp.fc2_w, mlp.fc2_b = fc2_w.data_ptr(), fc2_b.data_ptr()
+    return args, mlp
+
+
 def mlp_burst_actor_args(agent, n_envs, n_agents, obs_dim, agent_id, ring_cursor, cursor_out, obs_source, ring_slabs, hidden_out,
                          means, rng_state=None, std=None, action_low=None, action_high=None):
     """The ring-form FlexActorArgs of the rollout burst for a shared MLPAgent (include/flexenv.h:
@@ -1618,20 +1640,9 @@ def mlp_burst_actor_args(agent, n_envs, n_agents, obs_dim, agent_id, ring_cursor
     of flexenv_rollout_burst_mlp needs — the noise stream's [seed, step] cell, the fixed std and the action range; the agent-summed
     forms leave them out.  Returns (args, FlexBurstMlp with the second layer).  Raises when the agent is outside what
     the launch covers: the caller admitted the configuration, and there is no other form to fall back to."""
-    why = mlp_burst_declines(agent, n_agents, obs_dim, agent_id)
-    if why is not None:
-        raise RuntimeError(f"the burst's MLP policy does not cover this agent: {why}")
-    fc1_w, fc1_b, ln_w, ln_b, fc2_w, fc2_b, head_w, head_b = _actor_mlp_params(agent)
-    args = _lib.FlexActorArgs()
-    args.rows, args.n_agents, args.obs_dim, args.act_dim = n_envs * n_agents, n_agents, obs_dim, agent.args.action_dim
-    args.agent_id, args.layernorm, args.ln_eps = int(bool(agent_id)), int(ln_w is not None), _ln_eps(agent)
+    args, mlp = _mlp_launch_args(agent, n_envs, n_agents, obs_dim, agent_id, dict(means=means, hidden_out=hidden_out))
     args.cursor, args.cursor_out = ring_cursor.data_ptr(), cursor_out.data_ptr()
     args.obs_slab_stride, args.hid_slab_stride, args.ring_slabs = 0, 0, int(ring_slabs)
-    for name, t in (("fc1_w", fc1_w), ("fc1_b", fc1_b), ("ln_w", ln_w), ("ln_b", ln_b), ("fc2_w", head_w), ("fc2_b", head_b),
-                    ("means", means), ("hidden_out", hidden_out)):
-        if t is not None and not t.is_contiguous():
-            raise RuntimeError(f"the burst's MLP policy: non-contiguous {name}")
-        setattr(args, name, None if t is None else t.data_ptr())
     args.obs, args.obs_pushed = obs_source.ring, obs_source.pushed
     args.obs_row_stride, args.obs_pushed_stride = obs_source.row_stride, obs_source.pushed_stride
     args.obs_slots, args.obs_slot_w = obs_source.slots, obs_source.slot_w
@@ -1642,8 +1653,27 @@ def mlp_burst_actor_args(agent, n_envs, n_agents, obs_dim, agent_id, ring_cursor
             raise ValueError("the exploration epilogue needs std, action_low and action_high next to rng_state")
         args.rng_state = rng_state.data_ptr()
         args.std, args.action_low, args.action_high = float(std), float(action_low), float(action_high)
-    mlp = _lib.FlexBurstMlp()
-    mlp.fc2_w, mlp.fc2_b = fc2_w.data_ptr(), fc2_b.data_ptr()
+    return args, mlp
+
+
+def mlp_test_actor_args(agent, n_envs, n_agents, obs_dim, agent_id, hidden_out, means, action, env_action, action_low, action_high):
+    """The test-form FlexActorArgs of flexenv_test_episodes_mlp for a shared MLPAgent / MLPAgentGaussian (include/flexenv.h):
+    the policy of ``mlp_burst_actor_args`` — same checks, the output head in the fc2 slot, no GRU tensors, no ``hidden_in`` —
+    without ring, cursor cells and noise stream (the launch reads the observation in place from the environment's own
+    history), with the four tensors every step writes: ``means`` / ``action`` / ``env_action`` [rows, act_dim] and ``hidden_out``
+    [rows, 64], and the action range of the test epilogue.  Returns (args, FlexBurstMlp with the second layer); raises as
+    ``mlp_burst_actor_args`` does."""
+    why = mlp_burst_declines(agent, n_agents, obs_dim, agent_id)          # (first: an agent outside the launch, whatever the tensors)
+    if why is not None:
+        raise RuntimeError(f"the burst's MLP policy does not cover this agent: {why}")
+    rows, a = n_envs * n_agents, agent.args.action_dim
+    for name, t, w in (("hidden_out", hidden_out, _lib.FLEXNET_HID), ("means", means, a), ("action", action, a),
+                       ("env_action", env_action, a)):
+        if not (t.is_cuda and t.dtype == th.float32 and t.numel() == rows * w):
+            raise ValueError(f"mlp_test_actor_args: {name} must be an fp32 device tensor of {rows * w} elements")
+    args, mlp = _mlp_launch_args(agent, n_envs, n_agents, obs_dim, agent_id,
+                                 dict(means=means, hidden_out=hidden_out, action=action, env_action=env_action))
+    args.std, args.action_low, args.action_high = 0.0, float(action_low), float(action_high)
     return args, mlp
 
 

@@ -53,7 +53,8 @@ def parse():
     ap.add_argument("--lr", type=float, default=None, help="override policy_lrate / value_lrate (default.yaml: 1e-4)")
     ap.add_argument("--one-launch", action="store_true",
                     help="evaluate with Model.test_episodes (one launch per evaluation where the model is eligible; per-episode "
-                         "means, model.py:285-306) instead of evaluate_on's loop")
+                         "means, model.py:285-306) instead of evaluate_on's loop; FLEX_MLP_TEST_LAUNCH=1 in the environment "
+                         "admits a shared MLP agent, as everywhere (learner.one_launch_declines)")
     ap.add_argument("--out", default=None)
     return ap.parse_args()
 
