@@ -10,6 +10,9 @@ flexenv_test_episodes_mlp).  Without it an MLP model takes the stepping loop, an
     python examples/evaluate_policy.py --alg maddpg --agent-type mlp --mlp-launch --days 0:30
     python examples/evaluate_policy.py --alg matd3 --agent-type mlp --load model.pt --days 100:107 --trace-out traces/
 
+``--intended-actions`` (with ``--alg safemaddpg``) evaluates SAFEMADDPG.intended_actions, and ``--intended-launch`` sets
+FLEX_INTENDED_LAUNCH=1 the same way, which admits that routing to the one launch (flexenv_test_episodes_routed).
+
 Prints one JSON line: test_policy.py's keys, ``agent_type``, and in ``launch_form`` the entry point that was used."""
 import argparse
 import json
@@ -28,6 +31,11 @@ def main():
     ap.add_argument("--agent-type", choices=["rnn", "mlp"], default="rnn", help="the policy network (default.yaml: rnn)")
     ap.add_argument("--mlp-launch", action="store_true",
                     help="admit a shared MLP agent to the one launch (sets FLEX_MLP_TEST_LAUNCH=1 for this process)")
+    ap.add_argument("--intended-actions", action="store_true",
+                    help="with --alg safemaddpg: SAFEMADDPG.intended_actions (not the reference's routing; the form that learns)")
+    ap.add_argument("--intended-launch", action="store_true",
+                    help="with --intended-actions: admit that routing to the one launch (sets FLEX_INTENDED_LAUNCH=1 for this "
+                         "process; flexenv_test_episodes_routed)")
     ap.add_argument("--agents", type=int, default=5, choices=[3, 5])
     ap.add_argument("--load", metavar="PATH", default=None,
                     help='a {"model_state_dict": ...} file as train_agent.py:144-147 writes; default: the seeded initial weights')
@@ -42,6 +50,12 @@ def main():
         ap.error("--days takes A:B")
     if not 0 <= d0 < d1:
         ap.error("--days A:B needs 0 <= A < B")
+    if a.intended_actions and a.alg != "safemaddpg":
+        ap.error("--intended-actions: needs --alg safemaddpg")
+    if a.intended_launch:
+        if not a.intended_actions:
+            ap.error("--intended-launch: needs --intended-actions")
+        os.environ["FLEX_INTENDED_LAUNCH"] = "1"                        # (read at call time by one_launch_declines)
     if a.mlp_launch:                                                    # (before the model is built; read at call time)
         os.environ["FLEX_MLP_TEST_LAUNCH"] = "1"
 
@@ -69,12 +83,18 @@ def main():
     model = build_model(a.alg, alg_args(a.alg, env, agent_type=a.agent_type), env)
     if a.load:
         model.load_state_dict(torch.load(a.load, map_location="cuda")["model_state_dict"])
+    if a.intended_actions:
+        model.intended_actions = True
     why = one_launch_declines(model)
     res = model.test_episodes(env, spec=spec, trace=a.trace_out is not None, one_launch=False if a.loop else None)
     ret, viol = res.sums[:, 7], res.sums[:, 8]
     q = (5, 50, 95)
     entry = "flexenv_test_episodes_mlp" if a.agent_type == "mlp" else "flexenv_test_episodes"
+    if a.intended_actions:
+        entry = "flexenv_test_episodes_routed"
     out = dict(res.stat())
+    if a.intended_actions:
+        out["intended_actions"] = True
     out.update(alg=a.alg, agent_type=a.agent_type, n_agents=env.n_agents, episodes=n, days=[d0, d1], checkpoint=a.load,
                launch_form=f"one launch ({entry})" if res.launch else "loop",
                loop_reason=None if res.launch else ("--loop" if a.loop and why is None else why),

@@ -86,7 +86,19 @@ def main():
                     help="episodic: True of default.yaml — one update event per block of 95 vector steps, on batches of whole "
                          "episodes gathered by csrc/episodes.hip (ippo / mappo / coma: the on-policy triple batch_size = "
                          "replay_buffer_size = behaviour_update_freq, in blocks)")
+    ap.add_argument("--intended-actions", action="store_true",
+                    help="with --alg safemaddpg: SAFEMADDPG.intended_actions — every building's adjusted controls reach the env "
+                         "as they are, agent-major (not the reference's routing; the form that learns)")
+    ap.add_argument("--intended-launch", action="store_true",
+                    help="with --intended-actions: that routing inside the one-launch rollout burst (FLEX_INTENDED_LAUNCH=1, "
+                         "flexenv_rollout_burst_routed) instead of a policy, a projection, a transpose and an env launch per step")
     a = ap.parse_args()
+    if a.intended_actions and a.alg != "safemaddpg":
+        ap.error("--intended-actions: needs --alg safemaddpg")
+    if a.intended_launch:
+        if not a.intended_actions:
+            ap.error("--intended-launch: needs --intended-actions")
+        os.environ["FLEX_INTENDED_LAUNCH"] = "1"         # (read when the trainer builds its RolloutGraph)
     if a.gauss_burst:
         if not a.gaussian_policy or a.alg not in ("matd3", "iddpg", "facmaddpg", "sqddpg", "ippo", "mappo", "coma"):
             ap.error("--gauss-burst: needs --gaussian-policy and an agent-summed --alg "
@@ -154,6 +166,8 @@ def main():
                         batch_scale=a.batch_scale,
                         # (on-policy: the trainer's default holds what is collected between two update events)
                         replay_capacity=None if a.alg in ("ippo", "mappo", "coma") else a.envs * 96 * 2)
+    if a.intended_actions:
+        trainer.behaviour_net.intended_actions = True           # (before the first episode builds the RolloutGraph)
     stat = {}
     trainer.behaviour_net.train_process(stat, trainer)          # warm-up episode (allocations, rocBLAS plans)
     torch.cuda.synchronize()
@@ -191,6 +205,15 @@ def main():
                 out["rollout"] = "flexenv_rollout_burst_summed_mlp"      # (the one-launch burst with the MLP policy phase)
             if rg is not None and getattr(rg, "mlp_plain_burst", False) and trainer.graph_rollout:
                 out["rollout"] = "flexenv_rollout_burst_mlp"             # (the same under MADDPG / SAFEMADDPG: in-kernel noise)
+        if a.intended_actions:
+            rg = getattr(trainer.behaviour_net, "_rollout_graph", None)
+            out["intended_actions"] = True
+            out["rollout_burst_launch"] = bool(rg is not None and rg.fused_burst and trainer.graph_rollout)
+            if out["rollout_burst_launch"]:
+                out["rollout"] = "flexenv_rollout_burst_routed"          # (the burst with the intended routing in the launch)
+            if a.intended_launch and not out["rollout_burst_launch"]:     # asked for: the run must have rolled out through it
+                raise SystemExit("--intended-launch: this configuration did not roll out through the one-launch burst "
+                                 "(learner.RolloutGraph.fused_burst)")
         if a.unshared:
             out["shared_params"] = False
         if a.episodic:

@@ -420,6 +420,41 @@ int flexenv_test_episodes(FlexEnv* env, const FlexActorArgs* actor, int32_t step
 int flexenv_test_episodes_mlp(FlexEnv* env, const FlexActorArgs* actor, int32_t steps, int32_t summed,
                               const FlexBurstMlp* mlp, const FlexBurstSafety* safety /* or NULL */,
                               const FlexTestOut* out, void* stream);
+/* Where the safety projection's result goes on its way to the environment step of the same launch.
+ * FLEX_SAFE_ROUTE_REFERENCE: the reference's routing (safemaddpg.py:106-111 -> model.py:217-218), what `safety` does in
+ * the entry points above — translate_action of the fp32 cast of the type-major `adjusted` vector, which the step re-reads
+ * agent-major.
+ * FLEX_SAFE_ROUTE_INTENDED: building i's own adjusted (percentage, charge, discharge, q), cast to fp32 and nothing else — no
+ * clamp, no translate_action — at safety->env_action[env, i, 0..3]: adjusted.reshape(N, 4, n).transpose(1, 2).to(float32),
+ * bit for bit.  `adjusted` itself stays type-major fp64 and holds the same values under either routing. */
+enum { FLEX_SAFE_ROUTE_REFERENCE = 0, FLEX_SAFE_ROUTE_INTENDED = 1 };
+/* flexenv_rollout_burst (`mlp` NULL: the shared RNN actor) or flexenv_rollout_burst_mlp (`mlp` non-NULL) under SAFEMADDPG with
+ * the routing chosen per call.  FLEX_SAFE_ROUTE_REFERENCE is that entry point's launch, through the same host function, with
+ * identical results.  FLEX_SAFE_ROUTE_INTENDED launches kernels of their own (the same block, groups, tiles, hand-overs,
+ * fences, noise stream, sink, ring, cursor cells and finish launch; only the projection's hand-over differs).
+ * Read: everything the corresponding entry point reads, safety->act_low / act_high excepted under FLEX_SAFE_ROUTE_INTENDED —
+ * they are neither read nor checked there.  Written: everything the corresponding entry point writes; safety->adjusted
+ * [N, 4 n_agents] type-major as ever, safety->env_action [N, n_agents, 4] agent-major under FLEX_SAFE_ROUTE_INTENDED.  The
+ * replay keeps the policy's own action under either routing (model.py:232).
+ * FLEX_EINVAL (before any HIP call): `safety` NULL; a routing outside the enum; FLEX_SAFE_ROUTE_INTENDED on an env whose
+ * cfg.raw_actions is 0 (its step would rescale the physical values); everything flexenv_rollout_burst (`mlp` NULL) or
+ * flexenv_rollout_burst_mlp (`mlp` non-NULL) refuses. */
+int flexenv_rollout_burst_routed(FlexEnv* env, const FlexActorArgs* actor, double* reward, uint8_t* done,
+                                 double* info, uint8_t* failed, float* obs_ring, int32_t steps,
+                                 const FlexBurstMlp* mlp /* NULL: RNN actor */,
+                                 const FlexBurstSafety* safety /* required */, int32_t routing, void* stream);
+/* flexenv_test_episodes (`mlp` NULL) or flexenv_test_episodes_mlp (`mlp` non-NULL) with `safety` and summed = 0, the routing
+ * chosen per call.  FLEX_SAFE_ROUTE_REFERENCE is that entry point's launch, through the same host function, with identical
+ * results.  FLEX_SAFE_ROUTE_INTENDED launches kernels of their own: step 2 of the episode hands the projection over as
+ * described at the enum, and out->actions rows then hold those agent-major values — what the step read.
+ * Read and written: as the corresponding entry point; safety->act_low / act_high are neither read nor checked under
+ * FLEX_SAFE_ROUTE_INTENDED.  Left alone: everything flexenv_test_episodes leaves alone.
+ * FLEX_EINVAL (before any HIP call): `safety` NULL; a routing outside the enum; FLEX_SAFE_ROUTE_INTENDED on an env whose
+ * cfg.raw_actions is 0; everything the corresponding entry point refuses.  FLEXNET_EUNSUPPORTED: as flexenv_test_episodes. */
+int flexenv_test_episodes_routed(FlexEnv* env, const FlexActorArgs* actor, int32_t steps,
+                                 const FlexBurstMlp* mlp /* NULL: RNN actor */,
+                                 const FlexBurstSafety* safety /* required */, int32_t routing,
+                                 const FlexTestOut* out, void* stream);
 int32_t flexenv_obs_size(const FlexEnv* env);    /* 6*history, env:71 */
 int32_t flexenv_state_size(const FlexEnv* env);  /* env:72 */
 

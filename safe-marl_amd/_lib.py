@@ -18,6 +18,7 @@ FLEX_INFO_W = 7
 FLEX_F64, FLEX_F32 = 0, 1
 FLEX_OK, FLEX_EINVAL, FLEX_ENOMEM, FLEX_EHIP = 0, -22, -12, -5
 FLEX_ABI_VERSION = 2          # include/flexenv.h
+FLEX_SAFE_ROUTE_REFERENCE, FLEX_SAFE_ROUTE_INTENDED = 0, 1      # flexenv_rollout_burst_routed / flexenv_test_episodes_routed
 FLEX_STEP_AUTORESET = 1
 FLEX_STEP_OBS_RING = 16
 FLEX_STEP_REPLAY_SINK = 4
@@ -73,7 +74,7 @@ class ResetSpec(C.Structure):
 # every symbol include/flexenv.h declares
 SYMBOLS = (
     "flexenv_create", "flexenv_destroy", "flexenv_reset", "flexenv_step", "flexenv_step_many", "flexenv_obs", "flexenv_obs_view", "flexenv_obs_source", "flexenv_state",
-    "flexenv_peek", "flexenv_poke", "flexenv_num_envs", "flexenv_set_step_counter", "flexenv_set_obs_ring", "flexenv_set_replay_sink", "flexenv_rollout_burst", "flexenv_rollout_burst_summed", "flexenv_rollout_burst_summed_gauss", "flexenv_rollout_burst_summed_mlp", "flexenv_rollout_burst_mlp", "flexenv_test_episodes", "flexenv_test_episodes_mlp", "flexenv_obs_size", "flexenv_state_size",
+    "flexenv_peek", "flexenv_poke", "flexenv_num_envs", "flexenv_set_step_counter", "flexenv_set_obs_ring", "flexenv_set_replay_sink", "flexenv_rollout_burst", "flexenv_rollout_burst_summed", "flexenv_rollout_burst_summed_gauss", "flexenv_rollout_burst_summed_mlp", "flexenv_rollout_burst_mlp", "flexenv_test_episodes", "flexenv_test_episodes_mlp", "flexenv_rollout_burst_routed", "flexenv_test_episodes_routed", "flexenv_obs_size", "flexenv_state_size",
     "pf_solve_batch", "flexenv_safety_project", "flexenv_safety_project_env", "flexenv_version", "flexenv_abi_version",
     "flexnet_actor_forward", "flexnet_critic_tail_forward", "flexnet_critic_tail_backward", "flexnet_rollout_pack", "flexnet_wgrad", "flexnet_lnrelu_forward", "flexnet_lnrelu_backward", "flexnet_clip_rmsprop", "flexnet_clip_rmsprop_refresh", "flexnet_td_loss", "flexnet_td_stats", "flexnet_critic_td_backward", "flexnet_critic_td_backward_phases", "flexnet_wgrad_critic_finish",
     "flexnet_scaled_sum", "flexnet_agent_sum_explore", "flexnet_gather_rows", "flexnet_gather_rows_td", "flexnet_window_refresh", "flexnet_gather_window", "flexnet_gather_episodes", "flexnet_linear2", "flexnet_gru_backward",
@@ -616,6 +617,12 @@ def load():
     lib.flexenv_test_episodes_mlp.argtypes = [vp, C.POINTER(FlexActorArgs), i32, i32, C.POINTER(FlexBurstMlp), C.POINTER(FlexBurstSafety),
                                               C.POINTER(FlexTestOut), vp]
     lib.flexenv_test_episodes_mlp.restype = C.c_int
+    lib.flexenv_rollout_burst_routed.argtypes = [vp, C.POINTER(FlexActorArgs), vp, vp, vp, vp, vp, i32, C.POINTER(FlexBurstMlp),
+                                                 C.POINTER(FlexBurstSafety), i32, vp]
+    lib.flexenv_rollout_burst_routed.restype = C.c_int
+    lib.flexenv_test_episodes_routed.argtypes = [vp, C.POINTER(FlexActorArgs), i32, C.POINTER(FlexBurstMlp), C.POINTER(FlexBurstSafety),
+                                                 i32, C.POINTER(FlexTestOut), vp]
+    lib.flexenv_test_episodes_routed.restype = C.c_int
     lib.flexnet_critic_td_backward.argtypes = [C.POINTER(FlexCriticTailArgs), C.POINTER(FlexTdLossArgs), vp]
     lib.flexnet_critic_td_backward.restype = C.c_int
     lib.flexnet_critic_td_backward_phases.argtypes = [C.POINTER(FlexCriticTailArgs), C.POINTER(FlexTdLossArgs), i32, vp]

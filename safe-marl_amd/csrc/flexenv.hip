@@ -1241,6 +1241,9 @@ __device__ __forceinline__ void qp_side(const double x0[4], const double cvec[4]
 }
 
 // one (environment, building) of the safety layer; the kernel below maps threads to them, the rollout burst its wavefronts' lanes
+// INTENDED (flexenv_rollout_burst_routed / flexenv_test_episodes_routed with FLEX_SAFE_ROUTE_INTENDED): env_action receives the
+// building's own adjusted (pct, ch, dis, q) agent-major, cast to fp32 and nothing else — act_low / act_span are not read
+template <bool INTENDED = false>
 __device__ __forceinline__ void flex_safety_one(const KArgs& a, const int env, const int ag, const void* __restrict__ proposed,
                                                 int dtype, const double* __restrict__ s_p, const double* __restrict__ s_q,
                                                 const double* __restrict__ beta, double v_min, double v_max, double rho,
@@ -1270,7 +1273,12 @@ __device__ __forceinline__ void flex_safety_one(const KArgs& a, const int env, c
     if (!ch_up) qp_side(x0, cvec, d, v_min, -1.0, rho, x, ch_lo);
     double* o = adjusted + (int64_t)env * 4 * na;          // type-major, safemaddpg.py:297 (A13)
     o[0 * na + ag] = x[0]; o[1 * na + ag] = x[1]; o[2 * na + ag] = x[2]; o[3 * na + ag] = x[3];
-    if (env_action) {
+    if constexpr (INTENDED) {
+        // learner.SAFEMADDPG.env_action with intended_actions: adjusted.reshape(-1, 4, n).transpose(1, 2).to(float32) — the
+        // four values of this building at [env, agent, 0..3], which a raw-action env (cfg.raw_actions) steps on as they are
+#pragma unroll
+        for (int t = 0; t < 4; ++t) env_action[base + t] = (float)x[t];
+    } else if (env_action) {
         // what the caller would feed env.step: translate_action (util.py:125-128) of the fp32 cast of the same flat vector,
         // 0.5 (clamp(a, low, high) + 1) (high - low) + low, every step rounded to fp32 as the tensor ops round it
         float* eo = env_action + (int64_t)env * 4 * na;
@@ -1354,8 +1362,9 @@ struct BurstArgs {
     R16Mlp mlp;
 };
 
-// the burst's four environment-phase forms (the two agent-summed ones also with an MLP policy phase: flex_rollout_burst_body's MLP)
-enum { BURST_PLAIN = 0, BURST_SAFE = 1, BURST_SUMMED = 2, BURST_SUMMED_GAUSS = 3 };
+// the burst's environment-phase forms (each also with an MLP policy phase: flex_rollout_burst_body's MLP);
+// BURST_SAFE_INTENDED is BURST_SAFE with flex_safety_one<true>'s hand-over (namespace intended below)
+enum { BURST_PLAIN = 0, BURST_SAFE = 1, BURST_SUMMED = 2, BURST_SUMMED_GAUSS = 3, BURST_SAFE_INTENDED = 4 };
 
 // (Inlined again since the policy became actor_r16_burst, which keeps almost nothing live across the step: 12 spilled
 //  registers, none in the step's loops, against the 64 the called version saved and restored per step — 34.4 -> 31.8 us per
@@ -1373,11 +1382,11 @@ __device__ __forceinline__ void flex_burst_env_step(int slab_v, int step_v, unsi
     // the chain goes first, the stream takes the gaps
     __builtin_amdgcn_s_setprio(3);
     const float* actions = b.act.env_action;
-    if constexpr (MODE == BURST_SAFE) {
+    if constexpr (MODE == BURST_SAFE || MODE == BURST_SAFE_INTENDED) {
         const int na = b.k.cfg.n_agents, lane = threadIdx.x & 63;
         const int env = 2 * wave + lane / na;
         if (lane < 2 * na && env < b.k.n_envs)
-            flex_safety_one(b.k, env, lane % na, b.act.action, FLEX_F32, b.s_p, b.s_q, b.beta, b.v_min, b.v_max, b.rho, b.adjusted,
+            flex_safety_one<MODE == BURST_SAFE_INTENDED>(b.k, env, lane % na, b.act.action, FLEX_F32, b.s_p, b.s_q, b.beta, b.v_min, b.v_max, b.rho, b.adjusted,
                             nullptr, b.safe_env_action, b.act_low, b.act_span);
         // (this wavefront's own stores, read back by its own step: complete before the loads go out)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -1490,6 +1499,18 @@ void flex_rollout_burst_kernel(BurstArgs b) {
 }
 }  // namespace plain_mlp
 
+// flexenv_rollout_burst_routed with FLEX_SAFE_ROUTE_INTENDED: the SAFE forms of the RNN and the MLP policy with the intended
+// hand-over of the projection (BURST_SAFE_INTENDED).  Kernels of their own names: the routing is no run-time branch of the
+// instantiations above, whose code and resource figures stay what they were.
+namespace intended {
+template <int NA_CAP, bool MLP>
+__global__ __launch_bounds__(64 * R16_W)
+void flex_rollout_burst_kernel(BurstArgs b) {
+    __shared__ ActorLds16B s;
+    flex_rollout_burst_body<NA_CAP, BURST_SAFE_INTENDED, MLP>(b, s);
+}
+}  // namespace intended
+
 // the cells a burst leaves as `steps` single steps would: cell 0 = the slab the policy reads next, cell 1 = the slab the last
 // step filed into, the noise stream's step counter advanced
 __global__ void flex_burst_finish_kernel(int64_t* cell0, int64_t* cell1, uint64_t* rng_state, int steps, int slabs) {
@@ -1550,11 +1571,11 @@ __device__ __forceinline__ void flex_test_env_step(int step_v, unsigned kbase_lo
     __builtin_amdgcn_s_setprio(3);
     const int lane = threadIdx.x & 63;
     const float* actions = b.act.env_action;
-    if constexpr (MODE == 1) {
+    if constexpr (MODE == 1 || MODE == 3) {                            // (3: MODE 1 with the intended hand-over)
         const int na = b.k.cfg.n_agents;
         const int env = 2 * wave + lane / na;
         if (lane < 2 * na && env < n_envs)
-            flex_safety_one(b.k, env, lane % na, b.act.action, FLEX_F32, b.s_p, b.s_q, b.beta, b.v_min, b.v_max, b.rho, b.adjusted,
+            flex_safety_one<MODE == 3>(b.k, env, lane % na, b.act.action, FLEX_F32, b.s_p, b.s_q, b.beta, b.v_min, b.v_max, b.rho, b.adjusted,
                             nullptr, b.safe_env_action, b.act_low, b.act_span);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -1651,6 +1672,20 @@ void flex_test_episodes_kernel(TestArgs b) {
     actor_r16_burst<true, false, false, true>(b.act, s, b.n_steps, env_step, [](int, int) {}, nullptr, &b.mlp);
 }
 }  // namespace test_mlp
+
+// flexenv_test_episodes_routed with FLEX_SAFE_ROUTE_INTENDED: MODE 3 of the environment phase for both policies, again under
+// names of their own.
+namespace intended {
+template <bool MLP>
+__global__ __launch_bounds__(64 * R16_W)
+void flex_test_episodes_kernel(TestArgs b) {
+    __shared__ ActorLds16B s;
+    const unsigned long long kb = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
+    int alive = 1;
+    auto env_step = [&](int64_t step, int) { flex_test_env_step<3>((int)step, (unsigned)kb, (unsigned)(kb >> 32), alive); };
+    actor_r16_burst<true, false, false, MLP>(b.act, s, b.n_steps, env_step, [](int, int) {}, nullptr, &b.mlp);
+}
+}  // namespace intended
 
 // -------------------------------------------------------------------------------------------------
 // host side
@@ -2121,9 +2156,15 @@ static bool burst_small_obs(const FlexEnv* e) {
 
 // flexenv_rollout_burst and its MLP form: the checks (no HIP call before the last of them), the launch of the plain or SAFE
 // kernel and the finish launch, which advances the noise stream's step counter.  `mlp` non-NULL: the policy phase is the MLPAgent's.
+// `routing` (flexenv_rollout_burst_routed; the other two entry points pass FLEX_SAFE_ROUTE_REFERENCE): with
+// FLEX_SAFE_ROUTE_INTENDED the kernels of namespace intended, which need `safety` and an env that reads raw actions.
 static int burst_plain_launch(FlexEnv* e, const FlexActorArgs* actor, double* reward, uint8_t* done, double* info,
                               uint8_t* failed, float* obs_ring, int32_t steps, const FlexBurstSafety* safety,
-                              const FlexBurstMlp* mlp, void* stream) {
+                              const FlexBurstMlp* mlp, void* stream, int32_t routing = FLEX_SAFE_ROUTE_REFERENCE) {
+    const bool intended = routing == FLEX_SAFE_ROUTE_INTENDED;
+    if (!intended && routing != FLEX_SAFE_ROUTE_REFERENCE) return FLEX_EINVAL;
+    // (an env that rescales its actions would rescale the projection's physical values; of the handle only cfg is read so far)
+    if (intended && (!safety || !e || !e->cfg.raw_actions)) return FLEX_EINVAL;
     if (!burst_config_ok(e, actor, reward, done, obs_ring, steps, mlp != nullptr)) return FLEX_EINVAL;
     const FlexActorArgs& p = *actor;
     // the burst draws the noise of steps rng_state[1] .. rng_state[1] + steps - 1 in the kernel and the finish launch advances the
@@ -2137,7 +2178,7 @@ static int burst_plain_launch(FlexEnv* e, const FlexActorArgs* actor, double* re
     BurstArgs b = burst_args(e, p, reward, done, info, failed, obs_ring, steps);
     if (safety) {
         if (!safety->s_p || !safety->s_q || !safety->beta || !safety->adjusted || !safety->env_action ||
-            !(safety->act_high >= safety->act_low) || p.act_dim != 4) return FLEX_EINVAL;      // (four controls per building)
+            (!intended && !(safety->act_high >= safety->act_low)) || p.act_dim != 4) return FLEX_EINVAL;      // (four controls per building)
         b.safety = 1; b.s_p = safety->s_p; b.s_q = safety->s_q; b.beta = safety->beta;
         b.v_min = safety->v_min; b.v_max = safety->v_max; b.rho = safety->penalty;
         b.adjusted = safety->adjusted; b.safe_env_action = safety->env_action;
@@ -2147,13 +2188,19 @@ static int burst_plain_launch(FlexEnv* e, const FlexActorArgs* actor, double* re
         b.mlp.w = mlp->fc2_w; b.mlp.b = mlp->fc2_b;
         // (no GRU cell: whatever the caller left in these is not read)
         b.act.hidden_in = nullptr; b.act.w_ih = b.act.w_hh = b.act.b_ih = b.act.b_hh = nullptr;
-        if (b.safety) {
+        if (intended) {
+            if (small_obs) hipLaunchKernelGGL((intended::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_SMALL, true>), grid, block, 0, s, b);
+            else hipLaunchKernelGGL((intended::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_LARGE, true>), grid, block, 0, s, b);
+        } else if (b.safety) {
             if (small_obs) hipLaunchKernelGGL((plain_mlp::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_SMALL, true>), grid, block, 0, s, b);
             else hipLaunchKernelGGL((plain_mlp::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_LARGE, true>), grid, block, 0, s, b);
         } else {
             if (small_obs) hipLaunchKernelGGL((plain_mlp::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_SMALL, false>), grid, block, 0, s, b);
             else hipLaunchKernelGGL((plain_mlp::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_LARGE, false>), grid, block, 0, s, b);
         }
+    } else if (intended) {
+        if (small_obs) hipLaunchKernelGGL((intended::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_SMALL, false>), grid, block, 0, s, b);
+        else hipLaunchKernelGGL((intended::flex_rollout_burst_kernel<FLEX_OBS_AGENTS_LARGE, false>), grid, block, 0, s, b);
     } else if (b.safety) {
         if (small_obs) hipLaunchKernelGGL((flex_rollout_burst_kernel<FLEX_OBS_AGENTS_SMALL, true>), grid, block, 0, s, b);
         else hipLaunchKernelGGL((flex_rollout_burst_kernel<FLEX_OBS_AGENTS_LARGE, true>), grid, block, 0, s, b);
@@ -2181,6 +2228,20 @@ int flexenv_rollout_burst_mlp(FlexEnv* e, const FlexActorArgs* actor, double* re
     // (what the shared checks refuse too — the ring's size must be the env's — read off the actor: no handle is followed yet)
     if (!actor || actor->n_agents > 5 || steps < 1 || steps >= actor->ring_slabs || (safety && actor->act_dim != 4)) return FLEX_EINVAL;
     return burst_plain_launch(e, actor, reward, done, info, failed, obs_ring, steps, safety, mlp, stream);
+}
+
+int flexenv_rollout_burst_routed(FlexEnv* e, const FlexActorArgs* actor, double* reward, uint8_t* done, double* info,
+                                 uint8_t* failed, float* obs_ring, int32_t steps, const FlexBurstMlp* mlp,
+                                 const FlexBurstSafety* safety, int32_t routing, void* stream) {
+    // every argument check comes before the first HIP call
+    if (!safety || (routing != FLEX_SAFE_ROUTE_REFERENCE && routing != FLEX_SAFE_ROUTE_INTENDED)) return FLEX_EINVAL;
+    // FLEX_SAFE_ROUTE_REFERENCE: the launch of the entry point that `mlp` selects, through its own function
+    if (mlp && routing == FLEX_SAFE_ROUTE_REFERENCE)
+        return flexenv_rollout_burst_mlp(e, actor, reward, done, info, failed, obs_ring, steps, mlp, safety, stream);
+    // (flexenv_rollout_burst_mlp's own refusals, read off the actor: no handle is followed yet)
+    if (mlp && (!mlp->fc2_w || !mlp->fc2_b || !actor || actor->n_agents > 5 || steps < 1 || steps >= actor->ring_slabs ||
+                actor->act_dim != 4)) return FLEX_EINVAL;
+    return burst_plain_launch(e, actor, reward, done, info, failed, obs_ring, steps, safety, mlp, stream, routing);
 }
 
 // The argument checks of flexenv_rollout_burst_summed, shared with the MLP form (no HIP call).
@@ -2286,16 +2347,23 @@ int flexenv_rollout_burst_summed_mlp(FlexEnv* e, const FlexActorArgs* actor, dou
 
 // flexenv_test_episodes and its MLP form: the checks (no HIP call before the last of them), the record's reset and the launch.
 // `mlp` non-NULL: the policy phase is the MLPAgent's — no GRU tensors, no hidden_in (neither read nor cleared).
+// `routing` (flexenv_test_episodes_routed; the other two entry points pass FLEX_SAFE_ROUTE_REFERENCE): with
+// FLEX_SAFE_ROUTE_INTENDED the kernels of namespace intended, which need `safety` and an env that reads raw actions.
 static int test_episodes_launch(FlexEnv* e, const FlexActorArgs* actor, int32_t steps, int32_t summed, const FlexBurstSafety* safety,
-                                const FlexTestOut* out, const FlexBurstMlp* mlp, void* stream) {
+                                const FlexTestOut* out, const FlexBurstMlp* mlp, void* stream,
+                                int32_t routing = FLEX_SAFE_ROUTE_REFERENCE) {
     // every argument check comes before the first HIP call
+    const bool intended = routing == FLEX_SAFE_ROUTE_INTENDED;
+    if ((!intended && routing != FLEX_SAFE_ROUTE_REFERENCE) || (intended && !safety)) return FLEX_EINVAL;
     if (!actor || !out || !out->sums || !out->length || steps < 1 || (summed != 0 && summed != 1)) return FLEX_EINVAL;
     const FlexActorArgs& p = *actor;
     if (p.n_agents > 5 || (summed && safety) || (safety && p.act_dim != 4) || !e) return FLEX_EINVAL;
+    // (an env that rescales its actions would rescale the projection's physical values; of the handle only cfg is read so far)
+    if (intended && !e->cfg.raw_actions) return FLEX_EINVAL;
     const int na = e->cfg.n_agents;
     if (na > 5) return FLEX_EINVAL;
     if (safety && (!safety->s_p || !safety->s_q || !safety->beta || !safety->adjusted || !safety->env_action ||
-                   !(safety->act_high >= safety->act_low))) return FLEX_EINVAL;
+                   (!intended && !(safety->act_high >= safety->act_low)))) return FLEX_EINVAL;
     // shapes the burst's policy tiles do not hold (the caller keeps its loop)
     if (p.obs_dim > FLEXNET_MAX_OBS || (p.obs_dim & 3) || e->hnet.epw != 2) return FLEXNET_EUNSUPPORTED;
     // the environment step reads four controls per building (env:260)
@@ -2339,7 +2407,10 @@ static int test_episodes_launch(FlexEnv* e, const FlexActorArgs* actor, int32_t 
     HIP_TRY(hipMemsetAsync(out->sums, 0, (size_t)N * 10 * sizeof(double), s));
     HIP_TRY(hipMemsetAsync(out->length, 0, (size_t)N * sizeof(int32_t), s));
     const dim3 grid((e->n_envs + 15) / 16), block(64 * R16_W);
-    if (mlp) {
+    if (intended) {
+        if (mlp) hipLaunchKernelGGL((intended::flex_test_episodes_kernel<true>), grid, block, 0, s, b);
+        else hipLaunchKernelGGL((intended::flex_test_episodes_kernel<false>), grid, block, 0, s, b);
+    } else if (mlp) {
         if (safety) hipLaunchKernelGGL((test_mlp::flex_test_episodes_kernel<1>), grid, block, 0, s, b);
         else if (summed) hipLaunchKernelGGL((test_mlp::flex_test_episodes_kernel<2>), grid, block, 0, s, b);
         else hipLaunchKernelGGL((test_mlp::flex_test_episodes_kernel<0>), grid, block, 0, s, b);
@@ -2360,6 +2431,14 @@ int flexenv_test_episodes_mlp(FlexEnv* e, const FlexActorArgs* actor, int32_t st
     // every argument check comes before the first HIP call
     if (!mlp || !mlp->fc2_w || !mlp->fc2_b) return FLEX_EINVAL;
     return test_episodes_launch(e, actor, steps, summed, safety, out, mlp, stream);
+}
+
+int flexenv_test_episodes_routed(FlexEnv* e, const FlexActorArgs* actor, int32_t steps, const FlexBurstMlp* mlp,
+                                 const FlexBurstSafety* safety, int32_t routing, const FlexTestOut* out, void* stream) {
+    // every argument check comes before the first HIP call
+    if (!safety || (routing != FLEX_SAFE_ROUTE_REFERENCE && routing != FLEX_SAFE_ROUTE_INTENDED)) return FLEX_EINVAL;
+    if (mlp && (!mlp->fc2_w || !mlp->fc2_b)) return FLEX_EINVAL;
+    return test_episodes_launch(e, actor, steps, 0, safety, out, mlp, stream, routing);
 }
 
 int flexenv_obs(FlexEnv* e, void* obs, int32_t obs_dtype, void* stream) {

@@ -276,9 +276,17 @@ class VecFlexProvisionEnv:
         it), the env's obs ring and replay sink are configured as for ``step(..., obs_ring=..., replay_sink=True)``.
         ``safety`` (SAFEMADDPG): dict(s_p, s_q, beta: float64 device tensors [n_agents]; v_min, v_max, penalty; adjusted
         [N, 4 n] float64 and env_action [N, 4 n] float32 device tensors; act_low, act_high) — safety_project(...,
-        env_action_range=...) between policy and step, inside the launch."""
+        env_action_range=...) between policy and step, inside the launch.  ``safety["routing"]`` (default 0, the call as it
+        stands): 1 takes flexenv_rollout_burst_routed with FLEX_SAFE_ROUTE_INTENDED — env_action [N, n, 4] then receives every
+        building's own adjusted values, agent-major, as ``SAFEMADDPG.env_action`` with ``intended_actions`` lays them out."""
         self.calls += int(steps)
         sf = self._burst_safety(safety, "rollout_burst") if safety is not None else None
+        if sf is not None and self._routing(safety, "rollout_burst"):
+            _lib.check(self.lib.flexenv_rollout_burst_routed(self.handle, C.byref(actor_args), _ptr(self.reward), _ptr(self.done),
+                                                             _ptr(self.info), _ptr(self.failed), _ptr(obs_ring), int(steps), None,
+                                                             C.byref(sf), _lib.FLEX_SAFE_ROUTE_INTENDED, _stream()),
+                       "flexenv_rollout_burst_routed")
+            return
         _lib.check(self.lib.flexenv_rollout_burst(self.handle, C.byref(actor_args), _ptr(self.reward), _ptr(self.done),
                                                   _ptr(self.info), _ptr(self.failed), _ptr(obs_ring), int(steps),
                                                   C.byref(sf) if sf is not None else None, _stream()),
@@ -364,9 +372,16 @@ class VecFlexProvisionEnv:
         agent_type mlp): ``actor_args`` and ``mlp`` (a ``_lib.FlexBurstMlp`` with the second layer, or None for the library's
         refusal) from ``nets.mlp_burst_actor_args`` with ``rng_state``, ``std`` and the action range — the output head in the fc2
         slot, no GRU tensors; the env's obs ring and replay sink configured as for ``rollout_burst`` (the sink's aux_counter is
-        the noise stream's step counter).  ``safety``: as in ``rollout_burst``."""
+        the noise stream's step counter).  ``safety``: as in ``rollout_burst``, its ``routing`` included."""
         self.calls += int(steps)
         sf = self._burst_safety(safety, "rollout_burst_mlp") if safety is not None else None
+        if sf is not None and self._routing(safety, "rollout_burst_mlp"):
+            _lib.check(self.lib.flexenv_rollout_burst_routed(self.handle, C.byref(actor_args), _ptr(self.reward), _ptr(self.done),
+                                                             _ptr(self.info), _ptr(self.failed), _ptr(obs_ring), int(steps),
+                                                             C.byref(mlp) if mlp is not None else None,
+                                                             C.byref(sf), _lib.FLEX_SAFE_ROUTE_INTENDED, _stream()),
+                       "flexenv_rollout_burst_routed")
+            return
         _lib.check(self.lib.flexenv_rollout_burst_mlp(self.handle, C.byref(actor_args), _ptr(self.reward), _ptr(self.done),
                                                       _ptr(self.info), _ptr(self.failed), _ptr(obs_ring), int(steps),
                                                       C.byref(mlp) if mlp is not None else None,
@@ -397,7 +412,7 @@ class VecFlexProvisionEnv:
         (FLEXNET_EUNSUPPORTED).  The environments are left to be reset by the caller.
         ``mlp``: a ``_lib.FlexBurstMlp`` (with ``actor_args`` from ``nets.mlp_test_actor_args``) takes the launch of a shared MLP
         actor (flexenv_test_episodes_mlp): the output head in the fc2 slot, no GRU tensors, no hidden_in, h of every step in
-        hidden_out."""
+        hidden_out.  ``safety["routing"]`` = 1: flexenv_test_episodes_routed with FLEX_SAFE_ROUTE_INTENDED, either actor."""
         steps = int(steps)
         if out is None:
             out = self.test_out(steps)
@@ -412,7 +427,15 @@ class VecFlexProvisionEnv:
                 raise ValueError(f"test_episodes: {k} must be a contiguous {want[k]} device tensor of {n} elements")
             setattr(rec, k, t.data_ptr())
         sf = self._burst_safety(safety, "test_episodes") if safety is not None else None
-        if mlp is not None:
+        name = "flexenv_test_episodes_mlp" if mlp is not None else "flexenv_test_episodes"
+        if sf is not None and self._routing(safety, "test_episodes"):
+            if summed:
+                raise ValueError("test_episodes safety: routing 1 is SAFEMADDPG's, not an agent-summed algorithm's")
+            name = "flexenv_test_episodes_routed"
+            rc = self.lib.flexenv_test_episodes_routed(self.handle, C.byref(actor_args), steps,
+                                                       C.byref(mlp) if mlp is not None else None, C.byref(sf),
+                                                       _lib.FLEX_SAFE_ROUTE_INTENDED, C.byref(rec), _stream())
+        elif mlp is not None:
             rc = self.lib.flexenv_test_episodes_mlp(self.handle, C.byref(actor_args), steps, int(bool(summed)), C.byref(mlp),
                                                     C.byref(sf) if sf is not None else None, C.byref(rec), _stream())
         else:
@@ -420,9 +443,17 @@ class VecFlexProvisionEnv:
                                                 C.byref(sf) if sf is not None else None, C.byref(rec), _stream())
         if rc == _lib.FLEXNET_EUNSUPPORTED:
             return None
-        _lib.check(rc, "flexenv_test_episodes_mlp" if mlp is not None else "flexenv_test_episodes")
+        _lib.check(rc, name)
         self.calls += steps
         return out
+
+    @staticmethod
+    def _routing(safety, what):
+        """``safety["routing"]`` of the burst and test launches: 0 (the default: the reference's routing) or 1."""
+        routing = safety.get("routing", 0)
+        if routing not in (0, 1):
+            raise ValueError(f"{what} safety: routing must be 0 (reference) or 1 (intended), not {routing!r}")
+        return int(routing)
 
     def _burst_safety(self, safety, what):
         sf = _lib.FlexBurstSafety()

@@ -164,6 +164,10 @@ class RolloutGraph:
         # with the noise stream's aux_counter, the replay in row mode.  `fast` stays off (it is the RNN agent's two-launch body),
         # and without this flag (FLEX_MLP_BURST=0) the general body at the bottom of body() runs Model.policy as before.
         own_get_actions = SAFEMADDPG.get_actions if self.safe else MADDPG.get_actions
+        # SAFEMADDPG.intended_actions inside the burst launches (include/flexenv.h: flexenv_rollout_burst_routed) is opt-in:
+        # FLEX_INTENDED_LAUNCH=1, read here.  With it both burst forms below admit that routing and body() hands the launch
+        # the routing in force at each call (the buffers are the same for both); without it they exclude it as before.
+        self.intended_launch = bool(self.safe and os.environ.get("FLEX_INTENDED_LAUNCH", "0") == "1")
         self.mlp_plain_burst = bool(type(model).__name__ in ("MADDPG", "SAFEMADDPG")
                                     and type(model).get_actions is own_get_actions
                                     and bool(model.args.action_enforcebound) and not self.gaussian
@@ -174,7 +178,7 @@ class RolloutGraph:
                                     and n * a <= 32 and n * h <= 384 and two_per_wave
                                     and self.rows_capable and self.cursor_stepped and hasattr(env, "set_replay_sink")
                                     and hasattr(getattr(env, "vec", env), "rollout_burst_mlp")
-                                    and not (self.safe and model.intended_actions)
+                                    and not (self.safe and model.intended_actions and not self.intended_launch)
                                     and os.environ.get("FLEX_ROLLOUT_BURST", "1") != "0"
                                     and os.environ.get("FLEX_MLP_BURST", "1") != "0")
         if self.mlp_plain_burst:
@@ -273,7 +277,15 @@ class RolloutGraph:
         if self.mlp_plain_burst:                                          # (one form only; its setters refuse torch_noise and fast)
             return True
         return (self.burst_launch and self.sink_active and not self._torch_noise
-                and not (self.safe and self.model.intended_actions))       # (that routing transposes in torch)
+                # (that routing transposes in torch, unless FLEX_INTENDED_LAUNCH=1 put it into the launch)
+                and not (self.safe and self.model.intended_actions and not self.intended_launch))
+
+    @property
+    def _burst_form(self):
+        """What run() keys its burst graphs by, next to their length: ``fused_burst``, or — truthy as well — the name of the
+        routed launch's intended form, so that a graph recorded under one routing is never replayed under the other."""
+        fused = self.fused_burst
+        return "intended" if fused and self.intended_launch and self.model.intended_actions else fused
 
     # episode statistics: block sums of the pack kernel, or (sink) the env step's per-environment running sums, added up
     # when asked for (outside any graph)
@@ -365,6 +377,8 @@ class RolloutGraph:
                         s_p, s_q, beta = self.predictor
                         safety = dict(s_p=s_p, s_q=s_q, beta=beta, v_min=m.V_min, v_max=m.V_max, adjusted=self.burst_adjusted,
                                       env_action=self.burst_safe_env_act, act_low=m.args.action_low, act_high=m.args.action_high)
+                        if self.intended_launch:       # (flexenv_rollout_burst_routed: the routing in force at this call)
+                            safety["routing"] = int(bool(m.intended_actions))
                     ring.update(ring_slabs=buf.slabs,
                                 launch=lambda args: vec.rollout_burst(args, burst, buf.row_ring, safety=safety))
                 out = fused_actor_forward(m.policy_dicts[0], obs_in, hid_in, m.n_, m.args.agent_id, noise=noise,
@@ -394,7 +408,7 @@ class RolloutGraph:
                     self._pack(action, hid)
                 return
         if self.mlp_plain_burst:
-            if self.safe and m.intended_actions:
+            if self.safe and m.intended_actions and not self.intended_launch:
                 raise RuntimeError("SAFEMADDPG.intended_actions was switched on after construction: that routing is not in "
                                    "the MLP agent's burst launch, which has no second form")
             # the MLP policy with its exploration epilogue (noise drawn in the kernel: torch's generator is not touched), the
@@ -413,6 +427,8 @@ class RolloutGraph:
                 s_p, s_q, beta = self.predictor
                 safety = dict(s_p=s_p, s_q=s_q, beta=beta, v_min=m.V_min, v_max=m.V_max, adjusted=self.burst_adjusted,
                               env_action=self.burst_safe_env_act, act_low=m.args.action_low, act_high=m.args.action_high)
+                if self.intended_launch:       # (flexenv_rollout_burst_routed: the routing in force at this call)
+                    safety["routing"] = int(bool(m.intended_actions))
             vec.rollout_burst_mlp(args, mlp, k, buf.row_ring, safety=safety)
             return
         if self.gauss_burst:
@@ -544,7 +560,7 @@ class RolloutGraph:
             if k == 1:
                 done.append(self.step())
                 continue
-            g = self.bursts.get((k, self.fused_burst))      # (keyed by the body's form too: a flag flipped after capture()
+            g = self.bursts.get((k, self._burst_form))      # (keyed by the body's form too: a flag flipped after capture()
             if g is None:                                    #  must not replay a graph recorded for the other body)
                 g = self._capture_burst(k)
             g.replay()
@@ -577,7 +593,7 @@ class RolloutGraph:
                     self.body()
         if calls is not None:
             self.env.calls = calls
-        self.bursts[(k, self.fused_burst)] = g
+        self.bursts[(k, self._burst_form)] = g
         return g
 
     def capture(self, lengths=None):
@@ -686,8 +702,9 @@ def episode_stats(sums, length):
 def one_launch_declines(model):
     """None where ``Model.test_episodes`` may take the single launch (flexenv_test_episodes for a shared RNN actor,
     flexenv_test_episodes_mlp for a shared MLP one), else the reason — decided from the model's class and arguments, whatever
-    the device, and from one switch of the process environment, read at every call: FLEX_MLP_TEST_LAUNCH=1 admits the MLP
-    agent (unset or 0: it keeps the loop)."""
+    the device, and from two switches of the process environment, read at every call: FLEX_MLP_TEST_LAUNCH=1 admits the MLP
+    agent (unset or 0: it keeps the loop), FLEX_INTENDED_LAUNCH=1 admits SAFEMADDPG with ``intended_actions``
+    (flexenv_test_episodes_routed; unset or 0: it keeps the loop)."""
     args = model.args
     if not args.shared_params:
         return "shared_params is False: the launch stages one shared actor"
@@ -709,7 +726,9 @@ def one_launch_declines(model):
         return "action_enforcebound is False: the launch's test mode is tanh(mean)"
     own = type(model).get_actions
     if own is SAFEMADDPG.get_actions:
-        return "SAFEMADDPG with intended_actions: that routing is not in the launch" if model.intended_actions else None
+        if model.intended_actions and os.environ.get("FLEX_INTENDED_LAUNCH", "0") != "1":
+            return "SAFEMADDPG with intended_actions: that routing is not in the launch"
+        return None
     if own is MADDPG.get_actions or own is MATD3.get_actions or own is IDDPG.get_actions:
         return None
     return f"{type(model).__name__}.get_actions is none of MADDPG's, SAFEMADDPG's, MATD3's or IDDPG's"
@@ -1543,6 +1562,8 @@ class Model(nn.Module):
                           adjusted=th.empty(N, 4 * n, dtype=th.float64, device=vec.device),
                           env_action=th.empty(N, 4 * n, dtype=th.float32, device=vec.device),
                           act_low=self.args.action_low, act_high=self.args.action_high)
+            if self.intended_actions:          # (one_launch_declines admitted it: FLEX_INTENDED_LAUNCH=1)
+                safety["routing"] = 1
         summed = own is MATD3.get_actions or own is IDDPG.get_actions
         agent = self.policy_dicts[0]
         if type(agent) in (MLPAgent, MLPAgentGaussian):

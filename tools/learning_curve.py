@@ -55,8 +55,15 @@ def parse():
                     help="evaluate with Model.test_episodes (one launch per evaluation where the model is eligible; per-episode "
                          "means, model.py:285-306) instead of evaluate_on's loop; FLEX_MLP_TEST_LAUNCH=1 in the environment "
                          "admits a shared MLP agent, as everywhere (learner.one_launch_declines)")
+    ap.add_argument("--intended-launch", action="store_true",
+                    help="runs marked 'intended' roll out and (with --one-launch) evaluate through the one-launch paths: sets "
+                         "FLEX_INTENDED_LAUNCH=1 for this process (flexenv_rollout_burst_routed, flexenv_test_episodes_routed); "
+                         "the same variable in the environment does the same")
     ap.add_argument("--out", default=None)
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.intended_launch:                     # (read when a trainer builds its RolloutGraph and at every one_launch_declines call)
+        os.environ["FLEX_INTENDED_LAUNCH"] = "1"
+    return a
 
 
 def eval_spec(series, n, n_agents, seed=2025):
