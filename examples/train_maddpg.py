@@ -82,6 +82,9 @@ def main():
                          "agent-summed algorithms; FLEX_MLP_BURST=0 switches both off)")
     ap.add_argument("--unshared", action="store_true",
                     help="shared_params: False of default.yaml — one actor and one critic per agent (csrc/actor_unshared.hip)")
+    ap.add_argument("--unshared-twins", action="store_true",
+                    help="shared_params: False under --alg matd3 — one actor and one twin-flag critic per agent "
+                         "(csrc/critic_unshared_twin.hip: both heads from one first layer)")
     ap.add_argument("--episodic", action="store_true",
                     help="episodic: True of default.yaml — one update event per block of 95 vector steps, on batches of whole "
                          "episodes gathered by csrc/episodes.hip (ippo / mappo / coma: the on-policy triple batch_size = "
@@ -105,7 +108,10 @@ def main():
                      "(matd3, iddpg, facmaddpg, sqddpg, ippo, mappo, coma)")
         os.environ["FLEX_GAUSS_BURST"] = "1"             # (read when the trainer builds its RolloutGraph)
     if a.unshared and a.alg == "matd3":
-        ap.error("--unshared: MATD3 is built for shared_params (default.yaml:26)")
+        ap.error("--unshared: MATD3 is built for shared_params (default.yaml:26); its per-agent twin critics are "
+                 "asked for with --unshared-twins")
+    if a.unshared_twins and a.alg != "matd3":
+        ap.error("--unshared-twins: needs --alg matd3 (the other algorithms take --unshared)")
 
     import torch
     import safe_marl_amd  # noqa: F401
@@ -148,7 +154,7 @@ def main():
         alg.update(gaussian_policy=True)
     if a.agent_type != "rnn":
         alg.update(agent_type=a.agent_type)
-    if a.unshared:
+    if a.unshared or a.unshared_twins:
         alg.update(shared_params=False)
     if a.episodic:
         # capacity and cadence count BLOCKS of 95 vector steps of every environment (replay_buffer.EpisodeReplayBuffer)
@@ -214,7 +220,7 @@ def main():
             if a.intended_launch and not out["rollout_burst_launch"]:     # asked for: the run must have rolled out through it
                 raise SystemExit("--intended-launch: this configuration did not roll out through the one-launch burst "
                                  "(learner.RolloutGraph.fused_burst)")
-        if a.unshared:
+        if a.unshared or a.unshared_twins:
             out["shared_params"] = False
         if a.episodic:
             out["episodic"] = True

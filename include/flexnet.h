@@ -1091,6 +1091,93 @@ typedef struct {
 int flexnet_critic_unshared_forward(const FlexCriticUnsharedArgs* args, void* stream);
 int flexnet_critic_unshared_backward(const FlexCriticUnsharedBwdArgs* args, void* stream);
 
+/* ---- shared_params: False, MATD3's twin critics (madrl/models/matd3.py:24-27, 74-82; csrc/critic_unshared_twin.hip) ---------
+ * The per-agent critics above with MATD3's trailing twin-flag input: every agent's fc1.weight is [64, w1 + n_id + w2 + 1] with
+ * the column order [x1 | id columns | x2 | flag], and agent a's critic is evaluated on its row with the flag at 0 (head 0) and
+ * at 1 (head 1).  The input blocks, pitches and agent offsets are FlexCriticUnsharedArgs's (matd3.py:33-66 builds maddpg.py's
+ * row: x1 = obs [b, n o] shared, x2 = act [b, n a] shared).  The first layer — block products, bias, own id column — is formed
+ * ONCE per row and is head 0's pre-activation z1; head 1's is z1 + fc1_w[a][:, last].  Per head: LayerNorm (optional), ReLU,
+ * fc2 on the matrix cores, ReLU, fc3.  Same work map: one wavefront owns 32 samples of one agent on v_mfma_f32_32x32x2_f32.
+ * FOR EAGER CALLS ONLY: no caller in this project launches either entry point on a stream that is being captured.
+ * forward: heads = 1 or 2; q is [heads, b, n_agents] — the memory of the reference's cat([values1, values2], 0).  With both
+ *         save_* set: z1 [rows, 64] (head 0's only) and x [heads, rows, 64].  The launch with and without the saves gives the
+ *         same bits, and head 0 of a heads = 2 launch equals a heads = 1 launch bit for bit.
+ * backward: from dq [heads, b, n_agents] and the saves, per head: fc2's output recomputed, dz2, dx = dz2 @ fc2_w, LayerNorm /
+ *         ReLU backward -> that head's dz1.  Always written: dz1_sum [rows, 64], the heads' dz1 added (head 0 first) — d_fc1_w's
+ *         x1 and x2 column blocks are flexnet_wgrad_batched problems on it.  With param_grads also dz2 [heads, rows, 64]
+ *         (d_fc2_w[a] = dz2[:, a]^T x[:, a] is ONE problem of heads * b rows: in [heads, b, n, 64] agent a's rows keep the pitch
+ *         64 n across the head boundary), the per-agent sums d_ln_w, d_ln_b (layernorm), d_fc1_b, d_fc2_b, d_fc3_w as
+ *         [n_agents, 64] and d_fc3_b [n_agents], each over both heads, and d_flag [n_agents, 64]: the sum of head 1's dz1 over
+ *         the agent's rows, which is the flag column of d_fc1_w[a].  Every sum in a fixed order through `workspace` and a second
+ *         launch: no atomics, bit-reproducible.  Agent a's id column of d_fc1_w equals d_fc1_b[a], its other id columns are zero.
+ *         d_x2_own (optional) [b, n_agents, own_w] is taken from head 0's dz1 ONLY (matd3.py:123-125: the policy loss reads the
+ *         first head) against fc1_w[a][:, w1 + n_id + own_first + a * own_step .. + own_w).  heads = 1, param_grads = 0 is that
+ *         policy pass: it writes dz1_sum and d_x2_own only.
+ * Limits and their split as above: sizes and alignment FLEXNET_EUNSUPPORTED; missing tensors, rows % n_agents != 0, one save
+ * without the other, heads outside {1, 2}, an own block outside x2, a short workspace FLEXNET_EINVAL.  Both before any HIP
+ * call. */
+#define FLEXNET_CRITIC_UNSHARED_TWIN_WS_FLOATS (FLEXNET_MAX_AGENTS * 128 * 448)
+typedef struct {
+    int32_t rows;              /* b * n_agents */
+    int32_t n_agents;
+    int32_t w1, w2;
+    int32_t agent_id;
+    int32_t layernorm;
+    float ln_eps;
+    int32_t heads;             /* 1: the flag at 0 only; 2: both */
+    const float* x1;
+    const float* x2;           /* NULL with w2 = 0 */
+    int64_t x1_pitch, x2_pitch;            /* floats between samples */
+    int64_t x1_agent_off, x2_agent_off;    /* floats between a sample's agents; 0: shared */
+    const float* fc1_w[FLEXNET_MAX_AGENTS];    /* per agent: [64, w1 + n_id + w2 + 1] */
+    const float* fc1_b[FLEXNET_MAX_AGENTS];    /* [64] */
+    const float* ln_w[FLEXNET_MAX_AGENTS];     /* [64] (layernorm) */
+    const float* ln_b[FLEXNET_MAX_AGENTS];
+    const float* fc2_w[FLEXNET_MAX_AGENTS];    /* [64, 64] */
+    const float* fc2_b[FLEXNET_MAX_AGENTS];    /* [64] */
+    const float* fc3_w[FLEXNET_MAX_AGENTS];    /* [1, 64] */
+    const float* fc3_b[FLEXNET_MAX_AGENTS];    /* [1] */
+    float* q;                  /* out [heads, b, n_agents] */
+    float* save_z1;            /* out [rows, 64]; both saves or none */
+    float* save_x;             /* out [heads, rows, 64] */
+} FlexCriticUnsharedTwinArgs;
+
+typedef struct {
+    int32_t rows;
+    int32_t n_agents;
+    int32_t w1, w2;
+    int32_t agent_id;
+    int32_t layernorm;
+    float ln_eps;
+    int32_t param_grads;       /* 0: dz1_sum and d_x2_own only, no gradient buffer is touched */
+    int32_t heads;
+    int32_t pad0;
+    const float* dq;           /* [heads, b, n_agents] */
+    const float* z1;           /* the forward's saves: [rows, 64] */
+    const float* x;            /* [heads, rows, 64] */
+    const float* fc1_w[FLEXNET_MAX_AGENTS];
+    const float* ln_w[FLEXNET_MAX_AGENTS];     /* (layernorm) */
+    const float* fc2_w[FLEXNET_MAX_AGENTS];
+    const float* fc2_b[FLEXNET_MAX_AGENTS];
+    const float* fc3_w[FLEXNET_MAX_AGENTS];
+    float* dz1_sum;            /* out [rows, 64] */
+    float* dz2;                /* out [heads, rows, 64] (param_grads) */
+    float* d_ln_w;             /* out [n_agents, 64] (param_grads and layernorm) */
+    float* d_ln_b;
+    float* d_fc1_b;            /* out [n_agents, 64] (param_grads) */
+    float* d_fc2_b;
+    float* d_fc3_w;
+    float* d_fc3_b;            /* out [n_agents] */
+    float* d_flag;             /* out [n_agents, 64]: the flag column of d_fc1_w */
+    float* d_x2_own;           /* out [b, n_agents, own_w], or NULL */
+    int32_t own_first, own_step, own_w, pad1;
+    float* workspace;          /* (param_grads) */
+    int64_t workspace_floats;  /* >= FLEXNET_CRITIC_UNSHARED_TWIN_WS_FLOATS */
+} FlexCriticUnsharedTwinBwdArgs;
+
+int flexnet_critic_unshared_twin_forward(const FlexCriticUnsharedTwinArgs* args, void* stream);
+int flexnet_critic_unshared_twin_backward(const FlexCriticUnsharedTwinBwdArgs* args, void* stream);
+
 /* ---- agent_type: mlp under shared_params: True (madrl/agents/mlp_agent.py:20-32, mlp_agent_gaussian.py; csrc/actor_mlp.hip) ----
  * The MLP actor (fc1 -> LayerNorm -> ReLU -> fc2 -> ReLU = h -> fc3: the MLPCritic's layers with act_dim outputs) in one entry
  * point per direction, with ONE set of weights.  Row s * n_agents + a of the [rows, .] tensors is agent a of sample s.  One

@@ -85,6 +85,7 @@ SYMBOLS = (
     "flexnet_gauss_head_forward", "flexnet_gauss_head_backward", "flexnet_gauss_sum_explore", "flexnet_ppo_policy_loss_rows",
     "flexnet_actor_unshared_forward", "flexnet_actor_unshared_backward",
     "flexnet_critic_unshared_forward", "flexnet_critic_unshared_backward", "flexnet_wgrad_batched",
+    "flexnet_critic_unshared_twin_forward", "flexnet_critic_unshared_twin_backward",
     "flexnet_actor_mlp_forward", "flexnet_actor_mlp_backward",
     "flexnet_actor_mlp_unshared_forward", "flexnet_actor_mlp_unshared_backward",
     "flexnet_gauss_head_unshared_forward", "flexnet_gauss_head_unshared_backward", "flexnet_actor_unshared_backward_hn",
@@ -229,6 +230,28 @@ class FlexCriticUnsharedBwdArgs(C.Structure):
                [(k, _AgentPtrs) for k in ("fc1_w", "ln_w", "fc2_w", "fc2_b", "fc3_w")] + \
                [(k, C.c_void_p) for k in ("dz1", "dz2", "d_ln_w", "d_ln_b", "d_fc1_b", "d_fc2_b", "d_fc3_w", "d_fc3_b",
                                           "d_x2_own")] + \
+               [(k, C.c_int32) for k in ("own_first", "own_step", "own_w", "pad1")] + \
+               [("workspace", C.c_void_p), ("workspace_floats", C.c_int64)]
+
+
+FLEXNET_CRITIC_UNSHARED_TWIN_WS_FLOATS = FLEXNET_MAX_AGENTS * 128 * 448
+
+
+class FlexCriticUnsharedTwinArgs(C.Structure):
+    """include/flexnet.h: MATD3's per-agent twin critics, fc1 with the trailing flag column (csrc/critic_unshared_twin.hip)"""
+    _fields_ = _CRITIC_UNSHARED_HEAD + [("heads", C.c_int32), ("x1", C.c_void_p), ("x2", C.c_void_p)] + \
+               [(k, C.c_int64) for k in ("x1_pitch", "x2_pitch", "x1_agent_off", "x2_agent_off")] + \
+               [(k, _AgentPtrs) for k in ("fc1_w", "fc1_b", "ln_w", "ln_b", "fc2_w", "fc2_b", "fc3_w", "fc3_b")] + \
+               [(k, C.c_void_p) for k in ("q", "save_z1", "save_x")]
+
+
+class FlexCriticUnsharedTwinBwdArgs(C.Structure):
+    """include/flexnet.h"""
+    _fields_ = _CRITIC_UNSHARED_HEAD + [(k, C.c_int32) for k in ("param_grads", "heads", "pad0")] + \
+               [(k, C.c_void_p) for k in ("dq", "z1", "x")] + \
+               [(k, _AgentPtrs) for k in ("fc1_w", "ln_w", "fc2_w", "fc2_b", "fc3_w")] + \
+               [(k, C.c_void_p) for k in ("dz1_sum", "dz2", "d_ln_w", "d_ln_b", "d_fc1_b", "d_fc2_b", "d_fc3_w", "d_fc3_b",
+                                          "d_flag", "d_x2_own")] + \
                [(k, C.c_int32) for k in ("own_first", "own_step", "own_w", "pad1")] + \
                [("workspace", C.c_void_p), ("workspace_floats", C.c_int64)]
 
@@ -637,6 +660,10 @@ def load():
     lib.flexnet_critic_unshared_forward.restype = C.c_int
     lib.flexnet_critic_unshared_backward.argtypes = [C.POINTER(FlexCriticUnsharedBwdArgs), vp]
     lib.flexnet_critic_unshared_backward.restype = C.c_int
+    for fn, st in ((lib.flexnet_critic_unshared_twin_forward, FlexCriticUnsharedTwinArgs),
+                   (lib.flexnet_critic_unshared_twin_backward, FlexCriticUnsharedTwinBwdArgs)):
+        fn.argtypes = [C.POINTER(st), vp]
+        fn.restype = C.c_int
     for fn, st in ((lib.flexnet_actor_mlp_forward, FlexActorMlpArgs), (lib.flexnet_actor_mlp_backward, FlexActorMlpBwdArgs)):
         fn.argtypes = [C.POINTER(st), vp]
         fn.restype = C.c_int

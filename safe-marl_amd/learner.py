@@ -28,6 +28,7 @@ from .nets import (WGRAD_MIN_ROWS, AttentionCritic, attn_critic, CriticTail, cri
                    actor_mlp_unshared_declines, actor_mlp_unshared_train, fused_actor_forward_mlp_unshared,
                    gauss_head_unshared_declines, gauss_log_std_unshared,
                    actor_unshared_train, critic_unshared_supported, critic_unshared_train, fused_critic_forward_unshared,
+                   critic_unshared_twin_supported, critic_unshared_twin_train, fused_critic_forward_unshared_twin,
                    tall_linear, td_loss, td_loss_supported, wide_batch_linear,
                    batchnorm_stats_supported, batchnorm_update_running_stats, sync_batchnorm, QMixer,
                    sqddpg_draw, sqddpg_fused_config, sqddpg_shapley_fused, ppo_gae, ppo_policy_loss, ppo_value_loss,
@@ -1960,7 +1961,8 @@ class MATD3(MADDPG):
     value loss averaged over the twins (matd3.py:148).  Bug-compatible with the reference's action selection, which
     sums the policy means over the AGENT axis before sampling (matd3.py:92-97)."""
     bootstrap_cacheable = False      # own get_loss (min of twins, target-smoothing noise drawn inside): values are per sub-update
-    unshared_critic_kernel = False
+    unshared_critic_kernel = False   # (its fc1 holds the flag column: not csrc/critic_unshared.hip's row)
+    unshared_twin_kernel = True      # per-agent twin critics (shared_params False): csrc/critic_unshared_twin.hip
 
     # since round 2 the GPU path of both losses reduces only through this project's fixed-order kernels (twin critic
     # nodes, flexnet_td_loss, flexnet_scaled_sum, pointwise agent sums): sub-updates replay as HIP graphs like MADDPG's
@@ -1975,7 +1977,7 @@ class MATD3(MADDPG):
         the policy loss reads, matd3.py:121).  Same column-block evaluation as MADDPG.value; the twin flag only adds
         fc1.weight's last column to the second head's pre-activation."""
         if not self.args.shared_params:
-            raise NotImplementedError("MATD3 is built for shared_params (default.yaml:26)")
+            return self.unshared_twin_values(obs, act, critic_frozen, first_head_only)
         b, n, o, a = obs.size(0), self.n_, self.obs_dim, self.act_dim
         net = self.value_dicts[0]
         W, bias = net.fc1.weight, net.fc1.bias
@@ -2020,6 +2022,53 @@ class MATD3(MADDPG):
             return v1.view(b, n, 1)
         v2, _ = net.forward_from_hidden((h + flag).reshape(b * n, -1), need_hidden=False)
         return th.cat([v1.view(b, n, 1), v2.view(b, n, 1)], dim=0)
+
+    def unshared_twin_values(self, obs, act, critic_frozen=False, first_head_only=False):
+        """matd3.py:74-82 under ``shared_params: False``: agent i's own critic on its row, the twin flag at 0 and at 1 ->
+        cat([Q1, Q2], 0) [2b, n, 1] (``first_head_only``: Q1, [b, n, 1]).  On the GPU with ``fused_inference``
+        csrc/critic_unshared_twin.hip forms the first layer once per row: one launch without gradients at any size
+        (nets.fused_critic_forward_unshared_twin), the node nets._CriticUnsharedTwinFn from WGRAD_MIN_ROWS rows with them.
+        Elsewhere — the CPU, small batches with gradients, both heads of an action that takes a gradient, configurations the
+        kernel declines (after a ``critic_unshared_twin`` note) — the per-agent loop as a tensor composition that carries the
+        own-action gradient as MADDPG.value's loop does."""
+        b, n, o, a = obs.size(0), self.n_, self.obs_dim, self.act_dim
+        critics = list(self.value_dicts)
+        heads = 1 if first_head_only else 2
+        if self.unshared_twin_kernel and obs.is_cuda and self.fused_inference:
+            with_grad = th.is_grad_enabled() and (act.requires_grad or obs.requires_grad
+                                                  or any(p.requires_grad for c in critics for p in c.parameters()))
+            q = None
+            if not with_grad:
+                q = fused_critic_forward_unshared_twin(critics, obs, act.detach(), heads)
+            elif b * n >= WGRAD_MIN_ROWS and not (act.requires_grad and heads == 2):
+                if critic_unshared_twin_supported(critics, obs, act, heads, train=True):
+                    q = critic_unshared_twin_train(critics, obs, act, heads, param_grads=not critic_frozen)
+                else:
+                    self.note_unfused("critic_unshared_twin")
+            if q is not None:
+                return q.view(heads * b, n, 1)
+        act_det = act.detach()
+        obs_cols = obs.reshape(b, n * o)
+        values1, values2 = [], []
+        for i, net in enumerate(critics):
+            acts_i = act_det
+            if act.requires_grad:                                         # the others' actions detached (matd3.py:46-53)
+                acts_i = act_det.clone()
+                acts_i[:, i] = act[:, i]
+            W = net.fc1.weight
+            h = obs_cols @ W[:, :n * o].t() + net.fc1.bias
+            off = n * o
+            if self.args.agent_id:
+                h = h + W[:, off + i]
+                off += n
+            h = h + acts_i.reshape(b, n * a) @ W[:, off:off + n * a].t()
+            values1.append(net.forward_from_hidden(h, need_hidden=False)[0])
+            if not first_head_only:
+                values2.append(net.forward_from_hidden(h + W[:, off + n * a], need_hidden=False)[0])
+        v1 = th.stack(values1, dim=1)
+        if first_head_only:
+            return v1
+        return th.cat([v1, th.stack(values2, dim=1)], dim=0)
 
     def get_actions(self, obs, status, exploration, actions_avail, target=False, last_hid=None, clip=False, need_log_prob=True):
         """matd3.py:88-111 (continuous branch): the agent-summed selection on means masked where unavailable."""
