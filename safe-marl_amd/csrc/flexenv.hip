@@ -300,14 +300,30 @@ struct ObsHist {
 // one is given (`out`).
 // The push count (IF_OBSCNT = k + 1) is the caller's to store: the step kernel folds it into the one 16-byte store of its
 // integer fields.
-template <int EPW, typename OutT>
-__device__ __forceinline__ void obs_store_new(const KArgs& a, int env0, int g, bool valid, const LaneNet& ln, int k,
-                                              double pd, double qd, double ppv, double v, double price, double e,
-                                              OutT* __restrict__ out, float* __restrict__ rows) {
-    const int H = a.cfg.history, na = a.cfg.n_agents;
+// Where the push takes the configuration and the ring from: the kernel's arguments, read at the point of use (ObsSrcArgs), or
+// values the caller holds (ObsSrcHeld: flex_step_many_kernel's constants block and its ring base at the first environment).
+struct ObsSrcArgs {
+    const KArgs& a;
+    __device__ __forceinline__ int history() const { return a.cfg.history; }
+    __device__ __forceinline__ int n_agents() const { return a.cfg.n_agents; }
+    __device__ __forceinline__ float* ring_at(int env0, int ring_floats) const { return a.st.ring + (int64_t)env0 * ring_floats; }
+    __device__ __forceinline__ float inv_h() const { return a.inv_h; }
+};
+struct ObsSrcHeld {
+    float* ring; int H, na; float inv;
+    __device__ __forceinline__ int history() const { return H; }
+    __device__ __forceinline__ int n_agents() const { return na; }
+    __device__ __forceinline__ float* ring_at(int, int) const { return ring; }
+    __device__ __forceinline__ float inv_h() const { return inv; }
+};
+template <int EPW, typename OutT, typename Src>
+__device__ __forceinline__ void obs_store_new_from(const Src& a, int env0, int g, bool valid, const LaneNet& ln, int k,
+                                                   double pd, double qd, double ppv, double v, double price, double e,
+                                                   OutT* __restrict__ out, float* __restrict__ rows) {
+    const int H = a.history(), na = a.n_agents();
     const int ring_floats = na * H * 12, env_floats = na * H * 6;
-    float* const ring = a.st.ring + (int64_t)env0 * ring_floats;          // wavefront-uniform bases
-    const int slot = small_mod(k, H, a.inv_h);
+    float* const ring = a.ring_at(env0, ring_floats);                    // wavefront-uniform bases
+    const int slot = small_mod(k, H, a.inv_h());
     if (valid && ln.agent >= 0) {
         const float2 r0 = make_float2((float)pd, (float)qd), r1 = make_float2((float)ppv, (float)v);
         const float2 r2 = make_float2((float)price, (float)e);
@@ -333,6 +349,12 @@ __device__ __forceinline__ void obs_store_new(const KArgs& a, int env0, int g, b
             }
         }
     }
+}
+template <int EPW, typename OutT>
+__device__ __forceinline__ void obs_store_new(const KArgs& a, int env0, int g, bool valid, const LaneNet& ln, int k,
+                                              double pd, double qd, double ppv, double v, double price, double e,
+                                              OutT* __restrict__ out, float* __restrict__ rows) {
+    obs_store_new_from<EPW, OutT>(ObsSrcArgs{a}, env0, g, valid, ln, k, pd, qd, ppv, v, price, e, out, rows);
 }
 
 // Episode start (reset, restart inside a step): slots 1 .. H-1 of every agent's ring are zeroed — the rows "before the
@@ -571,12 +593,69 @@ void flex_reset_kernel(KArgs a, const uint8_t* __restrict__ mask, DevResetSpec i
 #ifndef FLEX_MANY_HDR_REGS
 #define FLEX_MANY_HDR_REGS 1
 #endif
+// FLEX_MANY_CONSTS: what a step of the loop reads of the launch's arguments comes from a block the host prepares
+//   (ManyConsts: every constant once per phase, in order of use, each phase one run of whole 64-byte lines — a step fetches the
+//   prologue's group and the epilogue's group with a few wide scalar loads and one wait each, not field by field at the point of
+//   use), and the bases of the state records at the wavefront's first environment are formed once in front of the loop (ManyWave);
+//   the step's output rows hang off a running row offset, not off a multiple of k.  =0: every step re-reads KArgs / ManyArgs
+//   through relaunder_kernarg and rebuilds its bases, as flex_step_kernel does.
+//   Two environments per wavefront only (the headline's shape): with the block the one-environment instantiations need 245 / 249
+//   vector registers where they have 244 / 248, so they keep the per-step reads.
+#ifndef FLEX_MANY_CONSTS
+#define FLEX_MANY_CONSTS 1
+#endif
+__host__ __device__ constexpr bool many_consts(int epw) { return FLEX_MANY_CONSTS != 0 && epw == 2; }
+struct alignas(64) ManyConstsP {                  // prologue: addressing, parse_actions, the solve's controls
+    const double* series;
+    const DevNet* net;
+    double pf_tol, e_max, e_min;
+    int32_t n_envs, na_nb;                        // na_nb: n_agents | n_bus << 16
+    int32_t rows, row_bytes;
+    int32_t flags;                                // raw_actions | warm_start << 1 | solver << 8
+    int32_t pf_max_iter;
+    double max_power_reduction, p_ch_max, p_dis_max, tan_phi, eta_ch, eta_dis, inv_eta_ch, inv_eta_dis;
+    const char* actions;                          // slab 0
+    int64_t act_stride;                           // bytes between two slabs ...
+    int32_t act_env_bytes;                        // ... and between two environments of a slab
+    int32_t act_period;
+};
+struct alignas(64) ManyConstsE {                  // epilogue: ESS update, reward terms, episode end, row push, outputs
+    double dt, eta_ch, inv_eta_dis, v_max, v_min, pv_cost, ess_cost, discomfort_coeff;
+    double voltage_coeff, fail_penalty;
+    double* reward; uint8_t* done; double* info; uint8_t* failed;      // row 0 (info, failed: or NULL)
+    int32_t n_envs;                               // elements between two rows of reward / done / failed (info: FLEX_INFO_W x)
+    int32_t episode_limit;
+    int32_t cfgw;                                 // n_agents | n_bus << 8 | auto_reset << 15 | history << 16 (taken out by shifts
+                                                  // alone: a mask constant would sit in a vector register for the whole loop)
+    float inv_h;
+};
+struct ManyConsts { ManyConstsP p; ManyConstsE e; };
+static_assert(sizeof(ManyConstsP) == 192 && sizeof(ManyConstsE) == 128, "whole 64-byte lines per phase");
+// The arguments of flex_step_many_kernel (below).  KArgs first: the step body re-reads it through relaunder_kernarg.
+struct ManyArgs {
+    KArgs k;
+    const void* actions;        // [act_period][N, n_agents, 4]
+    double* reward;             // [n_steps][N]
+    uint8_t* done;              // [n_steps][N]
+    double* info;               // [n_steps][N, FLEX_INFO_W] or NULL
+    uint8_t* failed;            // [n_steps][N] or NULL
+    int32_t n_steps, act_period, auto_reset, carry;
+    ManyConsts c;               // FLEX_MANY_CONSTS: what the carried path of a step reads, filled by flexenv_step_many
+};
+// Wavefront-uniform; the bases are constant for the launch: formed once in front of the loop.
+struct ManyWave {
+    double* agent; uint32_t* vw; double* vm; int32_t* ienv; double* cumrew; float* ring;   // DevState at the first environment
+    int64_t row;                                  // this step's row of the outputs, in elements: k * n_envs, as a running sum
+    int32_t slot;                                 // this step's slab index
+};
 struct StepCarry {
     flex_v4i iv;                 // steps, start, row, pushes: the 16 bytes the step wrote to ienv
     bool have;                   // wavefront-uniform: everything below is current
     bool have_iv;                // wavefront-uniform: `iv` is current although the rest is not (the launch's first step)
     LaneNet ln;
     NetHdrRegs hdr;              // FLEX_MANY_HDR_REGS: the table's header scalars, in scalar registers for the whole launch
+    ManyWave w;                  // FLEX_MANY_CONSTS: the wavefront's bases and this step's rows ...
+    ManyConstsP P;               // ... and this step's prologue constants, requested in the epilogue of the step before
     // FLEX_MANY_PREFETCH_ACT: this step's actions, requested by the step before (by the kernel for the first step); the
     // actions are never written by the launch, so they hold whatever `have` says
     float4 af;
@@ -596,9 +675,16 @@ __device__ __forceinline__ void flex_step_body(const KArgs& a, const int wave, c
                                                const int64_t slab, const bool cells, const unsigned long long kbase,
                                                StepCarry* mc = nullptr, const ActT* __restrict__ next_actions = nullptr) {
     constexpr int LW = FLEX_WAVE / EPW;
+    // MC (FLEX_MANY_CONSTS): the launch's constants come from ManyConsts — the prologue's group was requested by the step before
+    // (StepCarry::P), the epilogue's is fetched behind the solve — and the wavefront's bases from ManyWave; `a`, the pointer
+    // parameters and `auto_reset` are then read by the restart alone
+    constexpr bool MC = MANY && many_consts(EPW);
+    static_assert(!MC || (ROWS && !SINK), "the launch of many steps pushes rows and files into no sink");
     const int lane = threadIdx.x & 63;
     const int env0 = wave * EPW;                               // first environment of this wavefront
-    if (env0 >= a.n_envs) return;
+    ManyConstsP P;
+    if constexpr (MC) P = mc->P;
+    if (env0 >= (MC ? P.n_envs : a.n_envs)) return;
     // (tried in round 3: s_setprio 1 for one of the two hardware wave slots of a SIMD, either parity — 13.5-13.8 us per
     //  launch with and without: the end spread of this kernel is not an arbitration effect)
     float* rowrec = nullptr;
@@ -611,14 +697,22 @@ __device__ __forceinline__ void flex_step_body(const KArgs& a, const int wave, c
         }
     }
     // the spare group of an odd batch computes on env0's inputs (no out-of-bounds reads) and stores nothing
-    const bool valid = env0 + lane / LW < a.n_envs;
+    const bool valid = env0 + lane / LW < (MC ? P.n_envs : a.n_envs);
     const int g = valid ? lane / LW : 0;
     const int env = env0 + g;
     FLEX_STAMP_RT(5);
     FLEX_STAMP(0);
-    const FlexCfg& c = a.cfg;
+    FlexCfg pc;                                                   // MC: what parse_actions reads of the configuration
+    if constexpr (MC) {
+        pc.max_power_reduction = P.max_power_reduction; pc.p_ch_max = P.p_ch_max; pc.p_dis_max = P.p_dis_max; pc.tan_phi = P.tan_phi;
+        pc.eta_ch = P.eta_ch; pc.eta_dis = P.eta_dis; pc.e_max = P.e_max; pc.e_min = P.e_min;
+    }
+    const FlexCfg* const cp = MC ? &pc : &a.cfg;
+    const FlexCfg& c = *cp;
     // the head of the only dependent chain (ienv -> series row) goes out before the 19 table loads
-    int32_t* const b_ienv = a.st.ienv + (int64_t)env0 * IF_COUNT;
+    int32_t* b_ienv;
+    if constexpr (MC) b_ienv = mc->w.ienv;
+    else b_ienv = a.st.ienv + (int64_t)env0 * IF_COUNT;
     const uint32_t o_ienv = g * (IF_COUNT * 4);
     int4 iv;                                                      // steps, start, row, obs_cnt in one load
     LaneNet ln;
@@ -635,23 +729,37 @@ __device__ __forceinline__ void flex_step_body(const KArgs& a, const int wave, c
         load_lane_net<EPW>(a.net, lane, ln);
     }
     ln.pq = ln.pq && valid;
-    const int nb = a.n_bus, na = c.n_agents;
+    const int nb = MC ? P.na_nb >> 16 : a.n_bus, na = MC ? P.na_nb & 0xffff : c.n_agents;
     const bool is_bus = ln.bus >= 0, is_bld = ln.agent >= 0;
     const int ag = is_bld ? ln.agent : 0, busi = is_bus ? ln.bus : 0;
 
     // wavefront-uniform bases and per-lane byte offsets
     const int arec = agent_rec_doubles(na);
-    double* const b_agent = a.st.agent + (int64_t)env0 * arec;
-    uint32_t* const b_vw = a.st.vw + (int64_t)env0 * LW;
-    const ActT* const b_act = actions + (int64_t)env0 * (na * 4);
+    double* b_agent;
+    uint32_t* b_vw;
+    const ActT* b_act;
+    int32_t nslot = 0;                                                               // MC: the slab index of the next step
+    if constexpr (MC) {
+        b_agent = mc->w.agent; b_vw = mc->w.vw;
+        b_act = reinterpret_cast<const ActT*>(P.actions + mc->w.slot * P.act_stride + (int64_t)env0 * P.act_env_bytes);
+        nslot = mc->w.slot + 1 == P.act_period ? 0 : mc->w.slot + 1;
+        mc->w.slot = nslot;
+    } else {
+        b_agent = a.st.agent + (int64_t)env0 * arec;
+        b_vw = a.st.vw + (int64_t)env0 * LW;
+        b_act = actions + (int64_t)env0 * (na * 4);
+    }
+    // (read at the point of use, as ever, where they come from the kernel's arguments)
+    const auto series = [&]() -> const double* { if constexpr (MC) return P.series; else return a.series; };
+    const auto row_bytes = [&]() -> uint32_t { if constexpr (MC) return (uint32_t)P.row_bytes; else return (uint32_t)a.row_bytes; };
     const uint32_t o_agent = (g * arec + ag) * 8;                                    // + field * AFB
     const uint32_t o_volt = (g * LW + ln.l) * 4;
     const uint32_t o_bus = busi * 8, o_qbus = (nb + busi) * 8, o_pv = (2 * nb + ag) * 8, o_price = (2 * nb + na) * 8;
     const uint32_t AFB = na * 8;                                                     // bytes between agent fields
 
     const int steps = iv.x, start = iv.y, obs_cnt = iv.w;
-    const int rows = (int)a.rows;
-    const uint32_t row_off = (uint32_t)clamp_row32(iv.z, rows) * (uint32_t)a.row_bytes;
+    const int rows = MC ? P.rows : (int)a.rows;
+    const uint32_t row_off = (uint32_t)clamp_row32(iv.z, rows) * row_bytes();
 
     // Every load below uses an address that is valid in EVERY lane (idle lanes read bus 0 / agent 0) and is
     // issued unconditionally: a conditional load compiles to a branch with a full s_waitcnt behind it, and a
@@ -678,13 +786,14 @@ __device__ __forceinline__ void flex_step_body(const KArgs& a, const int wave, c
         pd_r = mc->pd; qd_r = mc->qd; ppv_r = mc->ppv; price = mc->price;
         e_cur_r = mc->e_cur; e_init_r = mc->e_init; cum_before = mc->cum; vw_word = mc->vw;
     } else {
-        pd_r = ld_at<double>(a.series, row_off + o_bus); qd_r = ld_at<double>(a.series, row_off + o_qbus);
-        ppv_r = ld_at<double>(a.series, row_off + o_pv); price = ld_at<double>(a.series, row_off + o_price);
+        pd_r = ld_at<double>(series(), row_off + o_bus); qd_r = ld_at<double>(series(), row_off + o_qbus);
+        ppv_r = ld_at<double>(series(), row_off + o_pv); price = ld_at<double>(series(), row_off + o_price);
         e_cur_r = ld_at<double>(b_agent, o_agent + AF_E * AFB);
         e_init_r = ld_at<double>(b_agent, o_agent + AF_EINIT * AFB);
         vw_word = ld_at<uint32_t>(b_vw, o_volt);
         // (the epilogue's only read-modify-write: requested here, not behind the solve — a memory round trip per launch)
-        cum_before = ld_at<double>(a.st.cumrew + env0, g * 8);
+        if constexpr (MC) cum_before = ld_at<double>(mc->w.cumrew, g * 8);
+        else cum_before = ld_at<double>(a.st.cumrew + env0, g * 8);
     }
     double we, wf;
     unpack_warm(vw_word, we, wf);
@@ -692,7 +801,7 @@ __device__ __forceinline__ void flex_step_body(const KArgs& a, const int wave, c
     //    stacked observation, which is copied right away and drains underneath the solve; an environment that
     //    turns out to restart below rewrites its whole observation afterwards (same wavefront, program order)
     const int new_row = clamp_row32(start + steps, rows);
-    const uint32_t nrow_off = (uint32_t)new_row * (uint32_t)a.row_bytes;
+    const uint32_t nrow_off = (uint32_t)new_row * row_bytes();
     // (only building lanes use the next row's Pd / Qd / Ppv: every other lane reads the price cell instead — an address this
     //  wavefront fetches anyway — so the observation touches 5 + 5 + 2 sectors of the next row, not all 18)
     // (MANY: every lane reads its OWN bus's cells — they are its inputs of the launch's next step, StepCarry)
@@ -700,26 +809,30 @@ __device__ __forceinline__ void flex_step_body(const KArgs& a, const int wave, c
         // the NEXT step's actions (the caller hands in a slab that exists: the sequence wraps at its period): they land underneath
         // the solve.  Unconditional per lane, like every load of the prologue, and AHEAD of the next row's cells: loads return
         // in order, so the epilogue's wait for those cells also covers these, and the next step's prologue waits for nothing.
-        const ActT* const b_nact = next_actions + (int64_t)env0 * (na * 4);
+        const ActT* b_nact;
+        if constexpr (MC) {
+            b_nact = reinterpret_cast<const ActT*>(P.actions + nslot * P.act_stride + (int64_t)env0 * P.act_env_bytes);
+        } else b_nact = next_actions + (int64_t)env0 * (na * 4);
         if constexpr (sizeof(ActT) == 4) mc->af = ld_at<float4>(b_nact, o_act);
         else { mc->ad0 = ld_at<double2>(b_nact, o_act); mc->ad1 = ld_at<double2>(b_nact, o_act + 16); }
     }
-    double n_pd = ld_at<double>(a.series, nrow_off + (is_bld || MANY ? o_bus : o_price));
-    double n_qd = ld_at<double>(a.series, nrow_off + (is_bld || MANY ? o_qbus : o_price));
-    double n_ppv = ld_at<double>(a.series, nrow_off + (is_bld || MANY ? o_pv : o_price));
-    const double n_price = ld_at<double>(a.series, nrow_off + o_price);
+    double n_pd = ld_at<double>(series(), nrow_off + (is_bld || MANY ? o_bus : o_price));
+    double n_qd = ld_at<double>(series(), nrow_off + (is_bld || MANY ? o_qbus : o_price));
+    double n_ppv = ld_at<double>(series(), nrow_off + (is_bld || MANY ? o_pv : o_price));
+    const double n_price = ld_at<double>(series(), nrow_off + o_price);
     const bool obs_fast = want_obs && (ROWS || (na <= NA_CAP && 3 * c.history <= FLEX_OBS_CLASSES(EPW) * LW));
     ObsHist<EPW, ROWS ? 1 : NA_CAP, ObsT> hist;
     if constexpr (!ROWS) hist.load(a, env0, g, valid, obs_fast, ln, obs_cnt);
 
-    const bool warm = c.warm_start != 0 && ln.pq;
+    const bool warm = (MC ? (P.flags & 2) != 0 : c.warm_start != 0) && ln.pq;
     double e = warm ? we : 1.0, f = warm ? wf : 0.0;
 
     const double pd = is_bus ? pd_r : 0.0, qd = is_bus ? qd_r : 0.0, ppv = is_bld ? ppv_r : 0.0;
     // initial_ess_energy is current_ess_energy except between a reset and the first step (A5; see the AF_ enum)
     const double e_cur = is_bld ? e_cur_r : 0.0, e_init = is_bld ? (steps == 1 ? e_init_r : e_cur_r) : 0.0;
     // actions -> physical set-points (env:260-293); computed in every lane, kept in building lanes
-    FlexAct act = parse_actions(c, a.inv_eta_ch, a.inv_eta_dis, c.raw_actions != 0, (double)av[0], (double)av[1],
+    FlexAct act = parse_actions(c, MC ? P.inv_eta_ch : a.inv_eta_ch, MC ? P.inv_eta_dis : a.inv_eta_dis,
+                                MC ? (P.flags & 1) != 0 : c.raw_actions != 0, (double)av[0], (double)av[1],
                                 (double)av[2], (double)av[3], pd, ppv, e_cur);
     if (!is_bld) { act.pct = 0.0; act.pred = 0.0; act.ch = 0.0; act.dis = 0.0; act.q = 0.0; }
     // net load per bus (pf.py:69-73, 81-82)
@@ -754,7 +867,11 @@ __device__ __forceinline__ void flex_step_body(const KArgs& a, const int wave, c
     if constexpr (MANY) { asm volatile("" :: "v"(pnet), "v"(qnet), "v"(e), "v"(f)); FLEX_MANY_STAMP(mc, 0); }
 #endif
     bool ok;
-    if constexpr (MANY && FLEX_MANY_HDR_REGS)
+    if constexpr (MC && FLEX_MANY_HDR_REGS)
+        ok = pf_solve<EPW>(mc->hdr, P.net, ln, P.flags >> 8, pnet, qnet, e, f, P.pf_tol, P.pf_max_iter, iters, sweeps);
+    else if constexpr (MC)
+        ok = pf_solve<EPW>(P.net, ln, P.flags >> 8, pnet, qnet, e, f, P.pf_tol, P.pf_max_iter, iters, sweeps);
+    else if constexpr (MANY && FLEX_MANY_HDR_REGS)
         ok = pf_solve<EPW>(mc->hdr, a.net, ln, c.solver, pnet, qnet, e, f, c.pf_tol, c.pf_max_iter, iters, sweeps);
     else
         ok = pf_solve<EPW>(a.net, ln, c.solver, pnet, qnet, e, f, c.pf_tol, c.pf_max_iter, iters, sweeps);
@@ -768,30 +885,49 @@ __device__ __forceinline__ void flex_step_body(const KArgs& a, const int wave, c
 
     // the epilogue re-reads its configuration and rebuilds its bases from fresh kernarg loads (see relaunder_kernarg)
     const KArgs& z = *relaunder_kernarg<KArgs>(kbase);
-    const FlexCfg& cz = z.cfg;
+    // (MC: the epilogue's group of ManyConsts — two lines, fetched here in one go)
+    ManyConstsE E;
+    FlexCfg ec;
+    if constexpr (MC) {
+        E = relaunder_kernarg<ManyArgs>(kbase)->c.e;
+        ec.dt = E.dt; ec.eta_ch = E.eta_ch; ec.v_max = E.v_max; ec.v_min = E.v_min; ec.pv_cost = E.pv_cost; ec.ess_cost = E.ess_cost;
+        ec.discomfort_coeff = E.discomfort_coeff; ec.voltage_coeff = E.voltage_coeff; ec.fail_penalty = E.fail_penalty;
+        ec.episode_limit = E.episode_limit; ec.history = (int)((uint32_t)E.cfgw >> 16); ec.n_agents = E.cfgw & 0xff;
+        auto_reset = (E.cfgw >> 15) & 1;
+    }
+    const FlexCfg* const czp = MC ? &ec : &z.cfg;
+    const FlexCfg& cz = *czp;
     // stacked-output mode: the history copy's stores go out HERE, its loads having been requested before the solve — issued
     // in the prologue (round 2) the stores made the wavefront wait for those loads, a second memory round trip in front of
     // the solve, to let them drain underneath it: 13.63 -> 13.18 us per launch (round 3)
     if constexpr (!ROWS) hist.store(z, env0, obs_fast, obs);
-    double* const e_agent = z.st.agent + (int64_t)env0 * agent_rec_doubles(cz.n_agents);
-    uint32_t* const e_vw = z.st.vw + (int64_t)env0 * LW;
+    double* e_agent;
+    uint32_t* e_vw;
+    if constexpr (MC) {
+        e_agent = mc->w.agent; e_vw = mc->w.vw;
+    } else {
+        e_agent = z.st.agent + (int64_t)env0 * agent_rec_doubles(cz.n_agents);
+        e_vw = z.st.vw + (int64_t)env0 * LW;
+    }
     {
         // pf.py:45: E_next (pf.py:96-98) is declared NonNegativeReals; a negative value makes the reference's NLP infeasible,
         // pf.py:104-105 raises and the step takes the failure path of env:314-337 whatever the network equations say.
         // (Tested AFTER the solve, from values the epilogue needs anyway: nothing extra is live across the solve.)
         bool wave_dom;
-        const bool dom_bad = grp_any<EPW>(is_bld && valid && e_init + cz.dt * (cz.eta_ch * act.ch - z.inv_eta_dis * act.dis) < -FLEX_DOMAIN_EPS,
+        const bool dom_bad = grp_any<EPW>(is_bld && valid && e_init + cz.dt * (cz.eta_ch * act.ch - (MC ? E.inv_eta_dis : z.inv_eta_dis) * act.dis) < -FLEX_DOMAIN_EPS,
                                           ln.grp, wave_dom);
         ok = ok && !dom_bad;
     }
-    double* const e_vm = z.st.vm + (int64_t)env0 * z.n_bus;
-    int32_t* const e_ienv = z.st.ienv + (int64_t)env0 * IF_COUNT;
-    const uint32_t o_vm = (g * z.n_bus + busi) * 8;
+    double* e_vm;
+    int32_t* e_ienv;
+    if constexpr (MC) { e_vm = mc->w.vm; e_ienv = mc->w.ienv; }
+    else { e_vm = z.st.vm + (int64_t)env0 * z.n_bus; e_ienv = z.st.ienv + (int64_t)env0 * IF_COUNT; }
+    const uint32_t o_vm = (g * (MC ? (E.cfgw >> 8) & 0x7f : z.n_bus) + busi) * 8;
     double v, pred, ch, dis, q, e_new;
     if (ok) {
         v = sqrt(e * e + f * f);                                                       // pf.py:108
         pred = act.pred; ch = act.ch; dis = act.dis; q = act.q;
-        e_new = e_init + cz.dt * (cz.eta_ch * ch - z.inv_eta_dis * dis);                 // pf.py:96-98
+        e_new = e_init + cz.dt * (cz.eta_ch * ch - (MC ? E.inv_eta_dis : z.inv_eta_dis) * dis);   // pf.py:96-98
         if (ln.pq) {
             st_at<double>(e_vm, o_vm, v);
             st_at<uint32_t>(e_vw, o_volt, pack_warm(e, f));
@@ -816,7 +952,16 @@ __device__ __forceinline__ void flex_step_body(const KArgs& a, const int wave, c
     }
 
     RewardOut rw = reward_terms<EPW>(cz, ln, is_bld, price, pred, ch, dis, q, v);        // env:330-335
-    double* const b_cum = z.st.cumrew + env0;
+    double* b_cum;
+    double* b_rew;
+    double* b_info;                                                                    // this step's rows at env0 (info: or NULL)
+    if constexpr (MC) {
+        const int64_t row = mc->w.row;
+        b_cum = mc->w.cumrew; b_rew = E.reward + (row + env0); b_info = E.info ? E.info + (row + env0) * FLEX_INFO_W : nullptr;
+        done = E.done + row; failed = E.failed ? E.failed + row : nullptr;
+    } else {
+        b_cum = z.st.cumrew + env0; b_rew = reward + env0; b_info = info;           // (info: offset at the store, as ever)
+    }
     double rwd = rw.reward;
     if (!ok) rwd -= cz.fail_penalty;                                                    // env:336
     const int new_steps = steps + 1;                                                   // env:342
@@ -827,9 +972,9 @@ __device__ __forceinline__ void flex_step_body(const KArgs& a, const int wave, c
     // The group's LAST lane holds the reward terms (reward_terms: the scan's totals stay where they fall) and writes what is
     // made of them; lane 0 writes the rest.  cumrew is the one cell a restart below writes as well — from the same lane.
     if (ln.l == LW - 1 && valid) {
-        st_at<double>(reward + env0, g * 8, rwd);
-        if (info) {
-            double* const io = info + (int64_t)env0 * FLEX_INFO_W;
+        st_at<double>(b_rew, g * 8, rwd);
+        if (b_info) {
+            double* const io = MC ? b_info : b_info + (int64_t)env0 * FLEX_INFO_W;
             const uint32_t oi = g * (FLEX_INFO_W * 8);
             st_at<double>(io, oi, rw.reward); st_at<double>(io, oi + 8, rw.revenue); st_at<double>(io, oi + 16, rw.der);
             st_at<double>(io, oi + 24, rw.ess); st_at<double>(io, oi + 32, rw.disc); st_at<double>(io, oi + 40, rw.vpen);
@@ -899,8 +1044,14 @@ __device__ __forceinline__ void flex_step_body(const KArgs& a, const int wave, c
         n_pd = is_bld ? n_pd : 0.0; n_qd = is_bld ? n_qd : 0.0; n_ppv = is_bld ? n_ppv : 0.0;
         const bool emit = valid && !restart;
         ObsT* const out = ROWS ? nullptr : obs;
-        if (obs_fast) obs_store_new<EPW, ObsT>(z, env0, g, emit, ln, obs_cnt, n_pd, n_qd, n_ppv, v, n_price, e_new, out, rowrec);
+        if constexpr (MC)
+            obs_store_new_from<EPW, ObsT>(ObsSrcHeld{mc->w.ring, cz.history, cz.n_agents, E.inv_h}, env0, g, emit, ln, obs_cnt,
+                                          n_pd, n_qd, n_ppv, v, n_price, e_new, out, rowrec);
+        else if (obs_fast) obs_store_new<EPW, ObsT>(z, env0, g, emit, ln, obs_cnt, n_pd, n_qd, n_ppv, v, n_price, e_new, out, rowrec);
         else push_and_emit_obs<EPW, ObsT>(z, env, emit, ln, obs_cnt, n_pd, n_qd, n_ppv, v, n_price, e_new, out, rowrec, false);
+    }
+    if constexpr (MC) {
+        mc->w.row += E.n_envs;                                       // the next step's row of the outputs
     }
     if (auto_reset && __ballot(restart) != 0ull) {       // wavefront-uniform, taken once per episode
         LaneNet ln0;
@@ -950,16 +1101,6 @@ void flex_step_kernel(KArgs a, const ActT* __restrict__ actions, double* __restr
 // is StepCarry.  Step k reads action slab k mod act_period and writes row k of reward / done / info / failed.
 // KArgs first: the step body re-reads it through relaunder_kernarg.
 // -------------------------------------------------------------------------------------------------
-struct ManyArgs {
-    KArgs k;
-    const void* actions;        // [act_period][N, n_agents, 4]
-    double* reward;             // [n_steps][N]
-    uint8_t* done;              // [n_steps][N]
-    double* info;               // [n_steps][N, FLEX_INFO_W] or NULL
-    uint8_t* failed;            // [n_steps][N] or NULL
-    int32_t n_steps, act_period, auto_reset, carry;
-};
-
 template <int EPW, typename ActT>
 __global__ __launch_bounds__(FLEX_WAVE * FLEX_WAVES_PER_BLOCK, 8 / FLEX_WAVES_PER_BLOCK)
 void flex_step_many_kernel(ManyArgs m) {
@@ -1006,22 +1147,44 @@ void flex_step_many_kernel(ManyArgs m) {
 #endif
     const int n_steps = m.n_steps;
     const bool carry = m.carry != 0;            // (one bit, kept like n_steps: a scalar load and its wait less at every loop top)
+    if constexpr (many_consts(EPW)) {
+        // what hangs off the wavefront's first environment, once per launch; the first step's row, slab and prologue constants
+        const int64_t e0 = (int64_t)wave * EPW;
+        const int na = m.k.cfg.n_agents;
+        ManyWave& w = mc.w;
+        w.agent = m.k.st.agent + e0 * agent_rec_doubles(na);
+        w.vw = m.k.st.vw + e0 * (FLEX_WAVE / EPW);
+        w.vm = m.k.st.vm + e0 * m.k.n_bus;
+        w.ienv = m.k.st.ienv + e0 * IF_COUNT;
+        w.cumrew = m.k.st.cumrew + e0;
+        w.ring = m.k.st.ring + e0 * (na * m.k.cfg.history * 12);
+        w.row = 0;
+        w.slot = 0;
+        mc.P = relaunder_kernarg<ManyArgs>(kb)->c.p;
+    }
     int slot = 0;
     for (int k = 0; k < n_steps; ++k) {
         // (every step reads its arguments through a freshly derived kernarg pointer, as the step body's epilogue does:
         //  nothing of them is carried — spilled — across the solve)
         const ManyArgs& b = *relaunder_kernarg<ManyArgs>(kb);
-        const int64_t ne = b.k.n_envs;
-        const int64_t slab_elems = ne * (b.k.cfg.n_agents * 4);
-        const ActT* act = reinterpret_cast<const ActT*>(b.actions) + (int64_t)slot * slab_elems;
-        slot = slot + 1 == b.act_period ? 0 : slot + 1;
-        // (the slab after this one; behind the launch's last step it is a slab of the period all the same: a valid address,
-        //  a load nobody uses)
-        const ActT* act_next = reinterpret_cast<const ActT*>(b.actions) + (int64_t)slot * slab_elems;
-        if (!carry) mc.have = false;
-        flex_step_body<EPW, float, ActT, FLEX_OBS_AGENTS_SMALL, false, true, true>(
-            b.k, wave, act, b.reward + k * ne, b.done + k * ne, b.info ? b.info + k * ne * FLEX_INFO_W : nullptr,
-            b.failed ? b.failed + k * ne : nullptr, nullptr, 1, b.auto_reset, -1, false, kb, &mc, act_next);
+        if constexpr (many_consts(EPW)) {
+            // (the step reads ManyConsts and ManyWave; `b.k` is for its restart)
+            if (!carry) mc.have = false;
+            flex_step_body<EPW, float, ActT, FLEX_OBS_AGENTS_SMALL, false, true, true>(
+                b.k, wave, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0, -1, false, kb, &mc, nullptr);
+        } else {
+            const int64_t ne = b.k.n_envs;
+            const int64_t slab_elems = ne * (b.k.cfg.n_agents * 4);
+            const ActT* act = reinterpret_cast<const ActT*>(b.actions) + (int64_t)slot * slab_elems;
+            slot = slot + 1 == b.act_period ? 0 : slot + 1;
+            // (the slab after this one; behind the launch's last step it is a slab of the period all the same: a valid address,
+            //  a load nobody uses)
+            const ActT* act_next = reinterpret_cast<const ActT*>(b.actions) + (int64_t)slot * slab_elems;
+            if (!carry) mc.have = false;
+            flex_step_body<EPW, float, ActT, FLEX_OBS_AGENTS_SMALL, false, true, true>(
+                b.k, wave, act, b.reward + k * ne, b.done + k * ne, b.info ? b.info + k * ne * FLEX_INFO_W : nullptr,
+                b.failed ? b.failed + k * ne : nullptr, nullptr, 1, b.auto_reset, -1, false, kb, &mc, act_next);
+        }
         FLEX_MANY_STAMP(&mc, 2);
         // this wavefront's own stores (state, history; a restart's) are what its next step loads: complete and visible
         // within the CU before those loads go out (work-group scope: one vector L1, write-through)
@@ -1030,6 +1193,9 @@ void flex_step_many_kernel(ManyArgs m) {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         FLEX_MANY_STAMP(&mc, 3);
+        // (the next step's prologue constants: requested here, behind everything the step — and a restart — needs registers
+        //  for, so that the next loop top finds them)
+        if constexpr (many_consts(EPW)) mc.P = relaunder_kernarg<ManyArgs>(kb)->c.p;
 #ifdef FLEX_MANY_STAMPS
         if (k == 0) {
 #pragma unroll
@@ -2091,12 +2257,37 @@ int flexenv_step_many(FlexEnv* e, const void* actions, int32_t act_dtype, int32_
     // closed-loop forms (flexenv_step, flexenv_rollout_burst), whose cursor cells a launch of many steps does not walk
     if (flags & ~(FLEX_STEP_AUTORESET | FLEX_STEP_OBS_ROWS | FLEX_STEP_MANY_NO_CARRY)) return FLEX_EINVAL;
     if (!(flags & FLEX_STEP_OBS_ROWS) || e->obs_slabs > 0) return FLEX_EINVAL;
+    if (e->cfg.history >= 32768) return FLEX_EINVAL;          // (ManyConstsE::cfgw keeps it in 15 bits)
     ManyArgs m;
     m.k = make_args(e);
     m.k.step_counter = e->step_counter; m.k.step_modulo = e->step_modulo;
     m.actions = actions; m.reward = reward; m.done = done; m.info = info; m.failed = failed;
     m.n_steps = steps; m.act_period = act_period; m.auto_reset = (flags & FLEX_STEP_AUTORESET) ? 1 : 0;
     m.carry = (flags & FLEX_STEP_MANY_NO_CARRY) ? 0 : 1;
+    {   // ManyConsts: every constant a step of the loop reads, once per phase, in order of use
+        const FlexCfg& c = m.k.cfg;
+        memset(&m.c, 0, sizeof(m.c));
+        ManyConstsP& p = m.c.p;
+        p.series = m.k.series; p.net = m.k.net;
+        p.pf_tol = c.pf_tol; p.e_max = c.e_max; p.e_min = c.e_min;
+        p.n_envs = m.k.n_envs; p.na_nb = c.n_agents | (m.k.n_bus << 16);
+        p.rows = (int32_t)m.k.rows; p.row_bytes = m.k.row_bytes;
+        p.flags = (c.raw_actions != 0 ? 1 : 0) | (c.warm_start != 0 ? 2 : 0) | (c.solver << 8);
+        p.pf_max_iter = c.pf_max_iter;
+        p.max_power_reduction = c.max_power_reduction; p.p_ch_max = c.p_ch_max; p.p_dis_max = c.p_dis_max; p.tan_phi = c.tan_phi;
+        p.eta_ch = c.eta_ch; p.eta_dis = c.eta_dis; p.inv_eta_ch = m.k.inv_eta_ch; p.inv_eta_dis = m.k.inv_eta_dis;
+        p.actions = (const char*)actions;
+        p.act_env_bytes = c.n_agents * 4 * (act_dtype == FLEX_F32 ? 4 : 8);
+        p.act_stride = (int64_t)m.k.n_envs * p.act_env_bytes;
+        p.act_period = act_period;
+        ManyConstsE& q = m.c.e;
+        q.dt = c.dt; q.eta_ch = c.eta_ch; q.inv_eta_dis = m.k.inv_eta_dis; q.v_max = c.v_max; q.v_min = c.v_min;
+        q.pv_cost = c.pv_cost; q.ess_cost = c.ess_cost; q.discomfort_coeff = c.discomfort_coeff; q.voltage_coeff = c.voltage_coeff;
+        q.fail_penalty = c.fail_penalty;
+        q.reward = reward; q.done = done; q.info = info; q.failed = failed;
+        q.n_envs = m.k.n_envs; q.episode_limit = c.episode_limit; q.inv_h = m.k.inv_h;
+        q.cfgw = (int32_t)((uint32_t)c.n_agents | (uint32_t)m.k.n_bus << 8 | (uint32_t)m.auto_reset << 15 | (uint32_t)c.history << 16);
+    }
     hipStream_t s = (hipStream_t)stream;
     const int epw = e->hnet.epw;
     const dim3 grid = env_grid(e->n_envs, epw);
