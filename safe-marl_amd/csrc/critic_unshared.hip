@@ -3,8 +3,10 @@
 // FlexCriticUnsharedBwdArgs).  Reference arithmetic: madrl/critics/mlp_critic.py:28-35 per agent on the input rows of
 // maddpg.py:33-54, mappo.py:34-62, ippo.py:34-59 and iddpg.py:32-59.
 //
-// Work map and the stages shared with actor_unshared.hip and actor_mlp.hip: flex_agent_tile.h.  The weights are read where the
-// modules keep them, through per-agent pointer tables.
+// Work map and the stages shared with actor_unshared.hip and actor_mlp.hip: flex_agent_tile.h.  The backward's own stages — the LDS
+// prologue, a head's dz2 and dx, the own-block product, the d_fc3_b fold — and the entry points' checks are shared with
+// critic_unshared_twin.hip: critic_unshared_stages.h (which also says why the forward's head is not among them).  The weights
+// are read where the modules keep them, through per-agent pointer tables.
 //
 // The first layer's input is never materialised: agent a's row of sample s is [x1 block | onehot(a) | x2 block], each block
 // `base + s * pitch + a * agent_off` (agent_off 0: the block is shared by the sample's agents).  The id block is not read —
@@ -19,14 +21,10 @@
 // atomics, bit-reproducible.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "flexnet.h"
-#include "flex_launch.h"
-#include "flex_agent_tile.h"
+#include "critic_unshared_stages.h"
 
 #define CU_VECS 6                                // d_ln_w | d_ln_b | d_fc1_b | d_fc2_b | d_fc3_w | d_fc3_b (element 0)
 #define CU_PITCH (CU_VECS * SH)                  // a work-group's partial row
-#define CU_MAX_W1 (FLEXNET_MAX_AGENTS * FLEXNET_MAX_OBS)
-#define CU_MAX_W2 (FLEXNET_MAX_AGENTS * FLEXNET_MAX_ACT)
 
 static_assert(FLEXNET_CRITIC_UNSHARED_WS_FLOATS >= FLEXNET_MAX_AGENTS * AT_MAX_BLOCKS * CU_PITCH, "workspace macro");
 
@@ -98,114 +96,36 @@ __global__ __launch_bounds__(64 * AT_W) void critic_unshared_backward_kernel(Fle
     const int n_id = a.agent_id ? n : 0;
     const int ld1 = a.w1 + n_id + a.w2;
     const int ow = a.d_x2_own ? a.own_w : 0;
-    {
-        at_stage_weight(s_buf, a.fc2_w[ag], SH, tid);
-        // the own-block columns of fc1_w: s_own[u * 8 + c] (zero past own_w)
-        const float* W1 = a.fc1_w[ag] + a.w1 + n_id + a.own_first + (int64_t)ag * a.own_step;
-        for (int idx = tid; idx < SH * FLEXNET_MAX_ACT; idx += 64 * AT_W) {
-            const int u = idx >> 3, c = idx & 7;
-            s_own[idx] = c < ow ? W1[(int64_t)u * ld1 + c] : 0.0f;
-        }
-    }
-    if (tid < SH) {
-        s_lnw[tid] = a.layernorm ? a.ln_w[ag][tid] : 1.0f;
-        s_b2[tid] = a.fc2_b[ag][tid];
-        s_w3[tid] = a.fc3_w[ag][tid];
-    }
-    __syncthreads();
+    cu_stage_agent(s_buf, s_own, s_lnw, s_b2, s_w3, nullptr, a.fc1_w[ag],
+                   a.fc1_w[ag] + a.w1 + n_id + a.own_first + (int64_t)ag * a.own_step, ld1, ow, a.layernorm, a.ln_w[ag],
+                   a.fc2_w[ag], a.fc2_b[ag], a.fc3_w[ag], tid);
 
     tv16 acc_g[2], acc_b[2], acc_d[2], acc_b2[2], acc_w3[2];
     float acc_b3 = 0.0f;
-    if (PG) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            acc_g[t] = zero_tile(); acc_b[t] = zero_tile(); acc_d[t] = zero_tile();
-            acc_b2[t] = zero_tile(); acc_w3[t] = zero_tile();
-        }
-    }
+    if (PG) cu_zero_sums(acc_g, acc_b, acc_d, acc_b2, acc_w3);
 #pragma unroll 1
     for (int64_t tile = (int64_t)kb * AT_W + wave; tile < tiles; tile += (int64_t)blocks_per_agent * AT_W) {
         bool ok;
         const int64_t row = at_loop_sample(tile, i, batch, ok) * n + ag;
         const float dqv = ok ? a.dq[row] : 0.0f;               // a dead row's dq is zero: so is everything below
 
-        // z2 = fc2(x) again, dz2 = dq w3 [z2 > 0]
         const tv16 XS[2] = {load_tile(a.x + row * SH + 4 * h), load_tile(a.x + row * SH + 32 + 4 * h)};
-        tv16 dz2[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            tv16 z2 = bias_tile(s_b2 + 32 * t, h);
-            z2 = layer_tile(s_buf + (32 * t + i) * AT_WP + 4 * h, z2, XS[0], XS[1]);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const tv4 w3 = ld4(s_w3 + 32 * t + 8 * q + 4 * h);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int e = 4 * q + j;
-                    const float hv = fmaxf(z2[e], 0.0f);
-                    const float d = z2[e] > 0.0f ? dqv * w3[j] : 0.0f;
-                    dz2[t][e] = d;
-                    if (PG) {
-                        acc_w3[t][e] = fmaf(dqv, hv, acc_w3[t][e]);
-                        acc_b2[t][e] += d;
-                    }
-                }
-            }
-            if (PG) store_tile(a.dz2 + row * SH + 32 * t + 4 * h, dz2[t], ok);
-        }
+        tv16 dz2[2], dx[2];
+        cu_head_dz2<PG>(XS, dqv, s_buf, s_b2, s_w3, dz2, acc_w3, acc_b2, PG ? a.dz2 + row * SH : nullptr, i, h, ok);
         if (PG) acc_b3 += dqv;
-        // dx = dz2 @ fc2_w: never stored
-        tv16 dx[2] = {zero_tile(), zero_tile()};
-#pragma unroll
-        for (int to = 0; to < 2; ++to) {
-            const float* wc = s_buf + (32 * to) * AT_WP + i;
-            dx[0] = transposed_tile(wc, AT_WP, h, dx[0], dz2[to]);
-            dx[1] = transposed_tile(wc + 32, AT_WP, h, dx[1], dz2[to]);
-        }
+        cu_head_dx(s_buf, dz2, dx, i, h);
         // LayerNorm / ReLU backward; ReLU's mask from the forward's own output
         tv16 dzv[2];
         at_ln_relu_backward<PG, false>(a.z1 + row * SH, nullptr, XS, nullptr, dx, s_lnw, a.layernorm, a.ln_eps, a.dz1 + row * SH,
                                        h, ok, acc_g, acc_b, acc_d, dzv);
-        // d_x2_own = dz1 @ the own-block columns: the A operand's rows past own_w are zero; output c = 4 h + r sits in
-        // accumulator register r < 4
-        if (ow > 0) {
-            tv16 m = zero_tile();
-            const bool live = i < FLEXNET_MAX_ACT;
-            const float* wo = s_own + (live ? i : 0);
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const float w = wo[(32 * t + 8 * q + 4 * h + j) * FLEXNET_MAX_ACT];
-                        m = TILE_MFMA(live ? w : 0.0f, dzv[t][4 * q + j], m);
-                    }
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int c = 4 * h + j;
-                if (ok && c < ow) a.d_x2_own[row * ow + c] = m[j];
-            }
-        }
+        if (ow > 0) cu_own_block(s_own, dzv, a.d_x2_own + row * ow, ow, i, h, ok);
     }
     if (!PG) return;
 
     float* out = a.workspace + ((int64_t)ag * blocks_per_agent + kb) * CU_PITCH;
     __syncthreads();                                           // every wavefront is done with the fc2_w tile
     at_fold(fold, out, tid, acc_g, acc_b, acc_d, acc_b2, acc_w3);
-    // d_fc3_b: both halves of a row hold its dq; half 0 counts
-    fold[wave][lane][0] = acc_b3;
-    __syncthreads();
-    if (tid < SH) {
-        float sum = 0.0f;
-        if (tid == 0) {
-            for (int wv = 0; wv < AT_W; ++wv)
-                for (int ii = 0; ii < 32; ++ii) sum += fold[wv][ii][0];
-        }
-        out[5 * SH + tid] = sum;
-    }
+    cu_fold_fc3_b(fold, out + 5 * SH, acc_b3, tid);
 }
 
 // the second launch: block = CU_VECS * agent + vector
@@ -221,29 +141,11 @@ __global__ __launch_bounds__(64 * FLEX_RED_G) void critic_unshared_reduce_kernel
     else if (ex == 0) a.d_fc3_b[ag] = sum;
 }
 
-// ---- entry points -----------------------------------------------------------------------------------------------------
-static int cu_check_shape(int rows, int n, int w1, int w2) {
-    if (rows < 0 || n < 1 || w1 < 1 || w2 < 0 || rows % n != 0) return FLEXNET_EINVAL;
-    if (n > FLEXNET_MAX_AGENTS || w1 > CU_MAX_W1 || w2 > CU_MAX_W2) return FLEXNET_EUNSUPPORTED;
-    return FLEXNET_OK;
-}
-
+// ---- entry points: the checks are critic_unshared_stages.h's ---------------------------------------------------------------
 extern "C" int flexnet_critic_unshared_forward(const FlexCriticUnsharedArgs* a, void* stream) {
     if (!a) return FLEXNET_EINVAL;
-    if (!a->x1 || !a->q || (a->w2 > 0 && !a->x2)) return FLEXNET_EINVAL;
-    if (a->x1_pitch < 0 || a->x2_pitch < 0 || a->x1_agent_off < 0 || a->x2_agent_off < 0) return FLEXNET_EINVAL;
-    const int rc = cu_check_shape(a->rows, a->n_agents, a->w1, a->w2);
+    const int rc = cu_check_forward(a);
     if (rc != FLEXNET_OK) return rc;
-    bool aligned = true;
-    for (int k = 0; k < a->n_agents; ++k) {
-        if (!a->fc1_w[k] || !a->fc1_b[k] || !a->fc2_w[k] || !a->fc2_b[k] || !a->fc3_w[k] || !a->fc3_b[k] ||
-            (a->layernorm && (!a->ln_w[k] || !a->ln_b[k])))
-            return FLEXNET_EINVAL;
-        aligned = aligned && flex_aligned(a->fc2_w[k], 16);
-    }
-    if ((a->save_z1 != nullptr) != (a->save_x != nullptr)) return FLEXNET_EINVAL;       // both or none
-    if (a->save_z1) aligned = aligned && flex_aligned(a->save_z1, 16) && flex_aligned(a->save_x, 16);
-    if (!aligned) return FLEXNET_EUNSUPPORTED;
     if (a->rows == 0) return FLEXNET_OK;
     const int64_t groups = at_groups(a->rows / a->n_agents);
     hipLaunchKernelGGL(critic_unshared_forward_kernel, dim3((unsigned)(groups * a->n_agents)), dim3(64 * AT_W), 0,
@@ -253,25 +155,10 @@ extern "C" int flexnet_critic_unshared_forward(const FlexCriticUnsharedArgs* a, 
 
 extern "C" int flexnet_critic_unshared_backward(const FlexCriticUnsharedBwdArgs* a, void* stream) {
     if (!a) return FLEXNET_EINVAL;
-    if (!a->dq || !a->z1 || !a->x || !a->dz1) return FLEXNET_EINVAL;
-    const bool pg = a->param_grads != 0;
-    if (pg && (!a->dz2 || !a->d_fc1_b || !a->d_fc2_b || !a->d_fc3_w || !a->d_fc3_b || !a->workspace ||
-               (a->layernorm && (!a->d_ln_w || !a->d_ln_b))))
-        return FLEXNET_EINVAL;
-    const int rc = cu_check_shape(a->rows, a->n_agents, a->w1, a->w2);
+    const int rc = cu_check_backward(a, a->dz1);
     if (rc != FLEXNET_OK) return rc;
-    if (a->d_x2_own) {
-        if (a->own_w < 1 || a->own_first < 0 || a->own_step < 0 ||
-            a->own_first + (a->n_agents - 1) * a->own_step + a->own_w > a->w2)
-            return FLEXNET_EINVAL;
-        if (a->own_w > FLEXNET_MAX_ACT) return FLEXNET_EUNSUPPORTED;
-    }
-    bool aligned = flex_aligned(a->z1, 16) && flex_aligned(a->x, 16) && flex_aligned(a->dz1, 16) && (!pg || flex_aligned(a->dz2, 16));
-    for (int k = 0; k < a->n_agents; ++k) {
-        if (!a->fc1_w[k] || !a->fc2_w[k] || !a->fc2_b[k] || !a->fc3_w[k] || (a->layernorm && !a->ln_w[k])) return FLEXNET_EINVAL;
-    }
-    if (!aligned) return FLEXNET_EUNSUPPORTED;
     if (a->rows == 0) return FLEXNET_OK;
+    const bool pg = a->param_grads != 0;
     const int64_t bpa = at_blocks_per_agent(a->rows / a->n_agents);
     if (pg && bpa * a->n_agents * CU_PITCH > a->workspace_floats) return FLEXNET_EINVAL;
     hipStream_t s = (hipStream_t)stream;

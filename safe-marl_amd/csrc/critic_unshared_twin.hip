@@ -4,7 +4,8 @@
 // FlexCriticUnsharedTwinBwdArgs).  Reference arithmetic: madrl/critics/mlp_critic.py:28-35 per agent and head.
 //
 // Work map and stages: flex_agent_tile.h, as critic_unshared.hip uses them — a wavefront per 32 samples of ONE agent, the weights
-// read where the modules keep them through per-agent pointer tables, the first layer's input described by blocks.  What is new
+// read where the modules keep them through per-agent pointer tables, the first layer's input described by blocks.  The backward's
+// stages of a head and the entry points' checks are the ones critic_unshared.hip runs: critic_unshared_stages.h.  What is new
 // is the flag column: every fc1.weight is [64, w1 + n_id + w2 + 1], and the first layer — the block products, the bias and the
 // agent's own id column, where critic_unshared.hip spends its time — is formed ONCE per row.  That is head 0's pre-activation
 // z1; head 1's is z1 + fc1_w[a][:, last].  The rest runs per head.
@@ -22,60 +23,12 @@
 // second launch: no atomics, bit-reproducible.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "flexnet.h"
-#include "flex_launch.h"
-#include "flex_agent_tile.h"
+#include "critic_unshared_stages.h"
 
 #define CT_VECS 7                                // d_ln_w | d_ln_b | d_fc1_b | d_fc2_b | d_fc3_w | d_flag | d_fc3_b (element 0)
 #define CT_PITCH (CT_VECS * SH)                  // a work-group's partial row
-#define CT_MAX_W1 (FLEXNET_MAX_AGENTS * FLEXNET_MAX_OBS)
-#define CT_MAX_W2 (FLEXNET_MAX_AGENTS * FLEXNET_MAX_ACT)
 
 static_assert(FLEXNET_CRITIC_UNSHARED_TWIN_WS_FLOATS >= FLEXNET_MAX_AGENTS * AT_MAX_BLOCKS * CT_PITCH, "workspace macro");
-
-typedef float tv2 __attribute__((ext_vector_type(2)));
-
-// at_fc1_block with wide loads where the operands allow them, for the whole groups of eight columns; the rest (and everything
-// where they do not) goes through at_fc1_block itself.  The lane's four inputs of a group are consecutive (c0 + 4 h + j): one
-// 16-byte load where `xv` (the row 16-byte aligned), and each weight row's four are two 8-byte loads where `wv` (the rows
-// 8-byte aligned: an even row length and first column).  The same values meet the same MFMA steps in the same order: the bits
-// are at_fc1_block's.  Five loads per group instead of twelve: at 746 columns the first layer is bound by its load count.
-__device__ __forceinline__ void ct_fc1_block(tv16 (&x)[2], const float* xp, const float* w0, const float* w1, int width, int h,
-                                             bool xv, bool wv) {
-    int c0 = 0;
-    if (xv || wv) {
-        const int full = width & ~7;
-        for (; c0 < full; c0 += 8) {
-            const int c = c0 + 4 * h;
-            float o[4], wa[4], wb[4];
-            if (xv) {
-                const tv4 v = ld4(xp + c);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = v[j];
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[j] = xp[c + j];
-            }
-            if (wv) {
-                const tv2 a0 = *reinterpret_cast<const tv2*>(w0 + c), a1 = *reinterpret_cast<const tv2*>(w0 + c + 2);
-                const tv2 b0 = *reinterpret_cast<const tv2*>(w1 + c), b1 = *reinterpret_cast<const tv2*>(w1 + c + 2);
-                wa[0] = a0[0]; wa[1] = a0[1]; wa[2] = a1[0]; wa[3] = a1[1];
-                wb[0] = b0[0]; wb[1] = b0[1]; wb[2] = b1[0]; wb[3] = b1[1];
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) { wa[j] = w0[c + j]; wb[j] = w1[c + j]; }
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                x[0] = TILE_MFMA(wa[j], o[j], x[0]);
-                x[1] = TILE_MFMA(wb[j], o[j], x[1]);
-            }
-        }
-    }
-    if (c0 < width) at_fc1_block(x, xp + c0, w0 + c0, w1 + c0, width - c0, h);
-}
-
-__device__ __forceinline__ bool ct_aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
 
 // (The kernels' names begin with twin_: build.kernel_resources filters on a name's beginning, and "critic_unshared" is
 // critic_unshared.hip's four.)
@@ -99,16 +52,16 @@ __global__ __launch_bounds__(64 * AT_W) void twin_critic_unshared_forward_kernel
     // which blocks take the wide loads: uniform over the work-group (the agent's offsets and weights)
     const float* x1b = a.x1 + (int64_t)ag * a.x1_agent_off;
     const float* x2b = a.x2 + (int64_t)ag * a.x2_agent_off;
-    const bool wrows = ct_aligned(W1, 8) && (ld1 & 1) == 0;
-    const bool xv1 = ct_aligned(x1b, 16) && (a.x1_pitch & 3) == 0;
-    const bool xv2 = a.w2 > 0 && ct_aligned(x2b, 16) && (a.x2_pitch & 3) == 0;
+    const bool wrows = at_aligned(W1, 8) && (ld1 & 1) == 0;
+    const bool xv1 = at_aligned(x1b, 16) && (a.x1_pitch & 3) == 0;
+    const bool xv2 = a.w2 > 0 && at_aligned(x2b, 16) && (a.x2_pitch & 3) == 0;
     const bool wv2 = wrows && ((a.w1 + n_id) & 1) == 0;
 
     tv16 z[2] = {zero_tile(), zero_tile()};
-    ct_fc1_block(z, x1b + s * a.x1_pitch, W1 + (int64_t)i * ld1, W1 + (int64_t)(32 + i) * ld1, a.w1, h, xv1, wrows);
+    at_fc1_block_wide(z, x1b + s * a.x1_pitch, W1 + (int64_t)i * ld1, W1 + (int64_t)(32 + i) * ld1, a.w1, h, xv1, wrows);
     if (a.w2 > 0)
-        ct_fc1_block(z, x2b + s * a.x2_pitch, W1 + (int64_t)i * ld1 + a.w1 + n_id, W1 + (int64_t)(32 + i) * ld1 + a.w1 + n_id,
-                     a.w2, h, xv2, wv2);
+        at_fc1_block_wide(z, x2b + s * a.x2_pitch, W1 + (int64_t)i * ld1 + a.w1 + n_id, W1 + (int64_t)(32 + i) * ld1 + a.w1 + n_id,
+                          a.w2, h, xv2, wv2);
     // + bias + the agent's own id column -> z1 (saved once: head 0's pre-activation)
     at_add_bias_id(z, a.fc1_b[ag], a.agent_id ? W1 + a.w1 + ag : nullptr, ld1, h);
     if (SAVE) {
@@ -168,32 +121,13 @@ __global__ __launch_bounds__(64 * AT_W) void twin_critic_unshared_backward_kerne
     const int n_id = a.agent_id ? n : 0;
     const int ld1 = a.w1 + n_id + a.w2 + 1;
     const int ow = a.d_x2_own ? a.own_w : 0;
-    {
-        at_stage_weight(s_buf, a.fc2_w[ag], SH, tid);
-        // the own-block columns of fc1_w: s_own[u * 8 + c] (zero past own_w)
-        const float* W1 = a.fc1_w[ag] + a.w1 + n_id + a.own_first + (int64_t)ag * a.own_step;
-        for (int idx = tid; idx < SH * FLEXNET_MAX_ACT; idx += 64 * AT_W) {
-            const int u = idx >> 3, c = idx & 7;
-            s_own[idx] = c < ow ? W1[(int64_t)u * ld1 + c] : 0.0f;
-        }
-    }
-    if (tid < SH) {
-        s_lnw[tid] = a.layernorm ? a.ln_w[ag][tid] : 1.0f;
-        s_b2[tid] = a.fc2_b[ag][tid];
-        s_w3[tid] = a.fc3_w[ag][tid];
-        s_flag[tid] = a.fc1_w[ag][(int64_t)tid * ld1 + (ld1 - 1)];
-    }
-    __syncthreads();
+    cu_stage_agent(s_buf, s_own, s_lnw, s_b2, s_w3, s_flag, a.fc1_w[ag],
+                   a.fc1_w[ag] + a.w1 + n_id + a.own_first + (int64_t)ag * a.own_step, ld1, ow, a.layernorm, a.ln_w[ag],
+                   a.fc2_w[ag], a.fc2_b[ag], a.fc3_w[ag], tid);
 
     tv16 acc_g[2], acc_b[2], acc_d[2], acc_b2[2], acc_w3[2], acc_f[2];
     float acc_b3 = 0.0f;
-    if (PG) {
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            acc_g[t] = zero_tile(); acc_b[t] = zero_tile(); acc_d[t] = zero_tile();
-            acc_b2[t] = zero_tile(); acc_w3[t] = zero_tile(); acc_f[t] = zero_tile();
-        }
-    }
+    if (PG) cu_zero_sums(acc_g, acc_b, acc_d, acc_b2, acc_w3, acc_f);
 #pragma unroll 1
     for (int64_t tile = (int64_t)kb * AT_W + wave; tile < tiles; tile += (int64_t)blocks_per_agent * AT_W) {
         bool ok;
@@ -205,39 +139,11 @@ __global__ __launch_bounds__(64 * AT_W) void twin_critic_unshared_backward_kerne
             const int64_t hrow = (int64_t)hd * a.rows + row;
             const float dqv = ok ? a.dq[hrow] : 0.0f;          // a dead row's dq is zero: so is everything below
 
-            // z2 = fc2(x) again, dz2 = dq w3 [z2 > 0]
             const tv16 XS[2] = {load_tile(a.x + hrow * SH + 4 * h), load_tile(a.x + hrow * SH + 32 + 4 * h)};
-            tv16 dz2[2];
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                tv16 z2 = bias_tile(s_b2 + 32 * t, h);
-                z2 = layer_tile(s_buf + (32 * t + i) * AT_WP + 4 * h, z2, XS[0], XS[1]);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const tv4 w3 = ld4(s_w3 + 32 * t + 8 * q + 4 * h);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int e = 4 * q + j;
-                        const float hv = fmaxf(z2[e], 0.0f);
-                        const float d = z2[e] > 0.0f ? dqv * w3[j] : 0.0f;
-                        dz2[t][e] = d;
-                        if (PG) {
-                            acc_w3[t][e] = fmaf(dqv, hv, acc_w3[t][e]);
-                            acc_b2[t][e] += d;
-                        }
-                    }
-                }
-                if (PG) store_tile(a.dz2 + hrow * SH + 32 * t + 4 * h, dz2[t], ok);
-            }
+            tv16 dz2[2], dx[2];
+            cu_head_dz2<PG>(XS, dqv, s_buf, s_b2, s_w3, dz2, acc_w3, acc_b2, PG ? a.dz2 + hrow * SH : nullptr, i, h, ok);
             if (PG) acc_b3 += dqv;
-            // dx = dz2 @ fc2_w: never stored
-            tv16 dx[2] = {zero_tile(), zero_tile()};
-#pragma unroll
-            for (int to = 0; to < 2; ++to) {
-                const float* wc = s_buf + (32 * to) * AT_WP + i;
-                dx[0] = transposed_tile(wc, AT_WP, h, dx[0], dz2[to]);
-                dx[1] = transposed_tile(wc + 32, AT_WP, h, dx[1], dz2[to]);
-            }
+            cu_head_dx(s_buf, dz2, dx, i, h);
             // LayerNorm / ReLU backward; ReLU's mask from the forward's own output.  Head 1's pre-activation is z1 + the flag
             // column (`s_add`).  The stage's own store is off (its `ok` false): dz1_sum is stored once, below.
             tv16 dzv[2];
@@ -251,29 +157,8 @@ __global__ __launch_bounds__(64 * AT_W) void twin_critic_unshared_backward_kerne
                     if (PG && hd == 1) acc_f[t][e] += dzv[t][e];
                 }
             }
-            // d_x2_own = head 0's dz1 @ the own-block columns: the A operand's rows past own_w are zero; output c = 4 h + r
-            // sits in accumulator register r < 4
-            if (ow > 0 && hd == 0) {
-                tv16 m = zero_tile();
-                const bool live = i < FLEXNET_MAX_ACT;
-                const float* wo = s_own + (live ? i : 0);
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            const float w = wo[(32 * t + 8 * q + 4 * h + j) * FLEXNET_MAX_ACT];
-                            m = TILE_MFMA(live ? w : 0.0f, dzv[t][4 * q + j], m);
-                        }
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int c = 4 * h + j;
-                    if (ok && c < ow) a.d_x2_own[row * ow + c] = m[j];
-                }
-            }
+            // the own-action gradient is head 0's dz1 alone
+            if (ow > 0 && hd == 0) cu_own_block(s_own, dzv, a.d_x2_own + row * ow, ow, i, h, ok);
         }
         store_tile(a.dz1_sum + row * SH + 4 * h, dsum[0], ok);
         store_tile(a.dz1_sum + row * SH + 32 + 4 * h, dsum[1], ok);
@@ -283,17 +168,7 @@ __global__ __launch_bounds__(64 * AT_W) void twin_critic_unshared_backward_kerne
     float* out = a.workspace + ((int64_t)ag * blocks_per_agent + kb) * CT_PITCH;
     __syncthreads();                                           // every wavefront is done with the fc2_w tile
     at_fold(fold, out, tid, acc_g, acc_b, acc_d, acc_b2, acc_w3, acc_f);
-    // d_fc3_b: both halves of a row hold its dq; half 0 counts
-    fold[wave][lane][0] = acc_b3;
-    __syncthreads();
-    if (tid < SH) {
-        float sum = 0.0f;
-        if (tid == 0) {
-            for (int wv = 0; wv < AT_W; ++wv)
-                for (int ii = 0; ii < 32; ++ii) sum += fold[wv][ii][0];
-        }
-        out[6 * SH + tid] = sum;
-    }
+    cu_fold_fc3_b(fold, out + 6 * SH, acc_b3, tid);
 }
 
 // the second launch: block = CT_VECS * agent + vector
@@ -311,29 +186,11 @@ __global__ __launch_bounds__(64 * FLEX_RED_G) void twin_critic_unshared_reduce_k
     else if (ex == 0) a.d_fc3_b[ag] = sum;
 }
 
-// ---- entry points -----------------------------------------------------------------------------------------------------
-static int ct_check_shape(int rows, int n, int w1, int w2, int heads) {
-    if (rows < 0 || n < 1 || w1 < 1 || w2 < 0 || rows % n != 0 || heads < 1 || heads > 2) return FLEXNET_EINVAL;
-    if (n > FLEXNET_MAX_AGENTS || w1 > CT_MAX_W1 || w2 > CT_MAX_W2) return FLEXNET_EUNSUPPORTED;
-    return FLEXNET_OK;
-}
-
+// ---- entry points: the checks are critic_unshared_stages.h's ---------------------------------------------------------------
 extern "C" int flexnet_critic_unshared_twin_forward(const FlexCriticUnsharedTwinArgs* a, void* stream) {
     if (!a) return FLEXNET_EINVAL;
-    if (!a->x1 || !a->q || (a->w2 > 0 && !a->x2)) return FLEXNET_EINVAL;
-    if (a->x1_pitch < 0 || a->x2_pitch < 0 || a->x1_agent_off < 0 || a->x2_agent_off < 0) return FLEXNET_EINVAL;
-    const int rc = ct_check_shape(a->rows, a->n_agents, a->w1, a->w2, a->heads);
+    const int rc = cu_check_forward(a, a->heads);
     if (rc != FLEXNET_OK) return rc;
-    bool aligned = true;
-    for (int k = 0; k < a->n_agents; ++k) {
-        if (!a->fc1_w[k] || !a->fc1_b[k] || !a->fc2_w[k] || !a->fc2_b[k] || !a->fc3_w[k] || !a->fc3_b[k] ||
-            (a->layernorm && (!a->ln_w[k] || !a->ln_b[k])))
-            return FLEXNET_EINVAL;
-        aligned = aligned && flex_aligned(a->fc2_w[k], 16);
-    }
-    if ((a->save_z1 != nullptr) != (a->save_x != nullptr)) return FLEXNET_EINVAL;       // both or none
-    if (a->save_z1) aligned = aligned && flex_aligned(a->save_z1, 16) && flex_aligned(a->save_x, 16);
-    if (!aligned) return FLEXNET_EUNSUPPORTED;
     if (a->rows == 0) return FLEXNET_OK;
     const int64_t groups = at_groups(a->rows / a->n_agents);
     const dim3 grid((unsigned)(groups * a->n_agents)), block(64 * AT_W);
@@ -344,26 +201,10 @@ extern "C" int flexnet_critic_unshared_twin_forward(const FlexCriticUnsharedTwin
 
 extern "C" int flexnet_critic_unshared_twin_backward(const FlexCriticUnsharedTwinBwdArgs* a, void* stream) {
     if (!a) return FLEXNET_EINVAL;
-    if (!a->dq || !a->z1 || !a->x || !a->dz1_sum) return FLEXNET_EINVAL;
-    const bool pg = a->param_grads != 0;
-    if (pg && (!a->dz2 || !a->d_fc1_b || !a->d_fc2_b || !a->d_fc3_w || !a->d_fc3_b || !a->d_flag || !a->workspace ||
-               (a->layernorm && (!a->d_ln_w || !a->d_ln_b))))
-        return FLEXNET_EINVAL;
-    const int rc = ct_check_shape(a->rows, a->n_agents, a->w1, a->w2, a->heads);
+    const int rc = cu_check_backward(a, a->dz1_sum, a->d_flag != nullptr, a->heads);
     if (rc != FLEXNET_OK) return rc;
-    if (a->d_x2_own) {
-        if (a->own_w < 1 || a->own_first < 0 || a->own_step < 0 ||
-            a->own_first + (a->n_agents - 1) * a->own_step + a->own_w > a->w2)
-            return FLEXNET_EINVAL;
-        if (a->own_w > FLEXNET_MAX_ACT) return FLEXNET_EUNSUPPORTED;
-    }
-    bool aligned = flex_aligned(a->z1, 16) && flex_aligned(a->x, 16) && flex_aligned(a->dz1_sum, 16) &&
-                   (!pg || flex_aligned(a->dz2, 16));
-    for (int k = 0; k < a->n_agents; ++k) {
-        if (!a->fc1_w[k] || !a->fc2_w[k] || !a->fc2_b[k] || !a->fc3_w[k] || (a->layernorm && !a->ln_w[k])) return FLEXNET_EINVAL;
-    }
-    if (!aligned) return FLEXNET_EUNSUPPORTED;
     if (a->rows == 0) return FLEXNET_OK;
+    const bool pg = a->param_grads != 0;
     const int64_t bpa = at_blocks_per_agent(a->rows / a->n_agents);
     if (pg && bpa * a->n_agents * CT_PITCH > a->workspace_floats) return FLEXNET_EINVAL;
     hipStream_t s = (hipStream_t)stream;

@@ -45,6 +45,51 @@ __device__ __forceinline__ void at_fc1_block(tv16 (&x)[2], const float* xp, cons
     }
 }
 
+typedef float tv2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ bool at_aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+
+// at_fc1_block with wide loads where the operands allow them, for the whole groups of eight columns; the rest (and everything
+// where they do not) goes through at_fc1_block itself.  The lane's four inputs of a group are consecutive (c0 + 4 h + j): one
+// 16-byte load where `xv` (the row 16-byte aligned), and each weight row's four are two 8-byte loads where `wv` (the rows
+// 8-byte aligned: an even row length and first column).  The same values meet the same MFMA steps in the same order: the bits
+// are at_fc1_block's.  Five loads per group instead of twelve: at 746 columns the first layer is bound by its load count.
+// (critic_unshared_twin.hip's; critic_unshared.hip's forward calls at_fc1_block.)
+__device__ __forceinline__ void at_fc1_block_wide(tv16 (&x)[2], const float* xp, const float* w0, const float* w1, int width, int h,
+                                                  bool xv, bool wv) {
+    int c0 = 0;
+    if (xv || wv) {
+        const int full = width & ~7;
+        for (; c0 < full; c0 += 8) {
+            const int c = c0 + 4 * h;
+            float o[4], wa[4], wb[4];
+            if (xv) {
+                const tv4 v = ld4(xp + c);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o[j] = v[j];
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o[j] = xp[c + j];
+            }
+            if (wv) {
+                const tv2 a0 = *reinterpret_cast<const tv2*>(w0 + c), a1 = *reinterpret_cast<const tv2*>(w0 + c + 2);
+                const tv2 b0 = *reinterpret_cast<const tv2*>(w1 + c), b1 = *reinterpret_cast<const tv2*>(w1 + c + 2);
+                wa[0] = a0[0]; wa[1] = a0[1]; wa[2] = a1[0]; wa[3] = a1[1];
+                wb[0] = b0[0]; wb[1] = b0[1]; wb[2] = b1[0]; wb[3] = b1[1];
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { wa[j] = w0[c + j]; wb[j] = w1[c + j]; }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                x[0] = TILE_MFMA(wa[j], o[j], x[0]);
+                x[1] = TILE_MFMA(wb[j], o[j], x[1]);
+            }
+        }
+    }
+    if (c0 < width) at_fc1_block(x, xp + c0, w0 + c0, w1 + c0, width - c0, h);
+}
+
 // what unit u's first-layer output gains past the product: its bias + the agent's own id column (`id_col` = fc1_w + the
 // column, NULL without agent_id; `ld1` = fc1_w's row length)
 __device__ __forceinline__ float at_unit_add(const float* b1, const float* id_col, int ld1, int u) {

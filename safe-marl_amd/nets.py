@@ -1341,27 +1341,50 @@ def _critic_unshared_widths(x1, x2, shared):
     return w1, w2
 
 
-def _critic_unshared_declines(critics, x1, x2, shared):
-    """Why csrc/critic_unshared.hip does not cover these per-agent critics on the blocks x1 [b, n, o], x2 [b, n, a] / None."""
+def _critic_unshared_family(heads):
+    """What the two families of per-agent critic kernels differ in on the host — the plain one (``heads`` None,
+    csrc/critic_unshared.hip) and MATD3's twins (csrc/critic_unshared_twin.hip): (forward struct, backward struct, the entry
+    points' stem, the ``note_fallback`` / ``_scratch`` key, the workspace's floats).  The twins' fc1 has one column more: the flag."""
+    if heads is None:
+        return (_lib.FlexCriticUnsharedArgs, _lib.FlexCriticUnsharedBwdArgs, "flexnet_critic_unshared", "critic_unshared",
+                _lib.FLEXNET_CRITIC_UNSHARED_WS_FLOATS)
+    return (_lib.FlexCriticUnsharedTwinArgs, _lib.FlexCriticUnsharedTwinBwdArgs, "flexnet_critic_unshared_twin",
+            "critic_unshared_twin", _lib.FLEXNET_CRITIC_UNSHARED_TWIN_WS_FLOATS)
+
+
+def _critic_unshared_declines(critics, x1, x2, shared, heads=None, names=("x1", "x2")):
+    """Why the per-agent critic kernels do not cover these critics on the blocks x1 [b, n, o], x2 [b, n, a] / None
+    (csrc/critic_unshared.hip), or — ``heads`` 1 or 2 — why csrc/critic_unshared_twin.hip does not: the same conditions with
+    the twin flag's column behind the blocks in fc1, the action block required, the rows counted per head, outside a graph
+    capture."""
     n = len(critics)
-    for name, t in (("x1", x1), ("x2", x2)):
+    flag = int(heads is not None)                    # the twin flag's column behind fc1's blocks
+    if flag and x2 is None:
+        return f"no {names[1]} block"
+    for name, t in zip(names, (x1, x2)):
         if t is not None and not (t.is_cuda and t.dtype == th.float32 and t.dim() == 3 and t.shape[1] == n
                                   and t.shape[0] == x1.shape[0]):
             return f"{name} {tuple(t.shape)} {t.dtype} for {n} agents"
     w1, w2 = _critic_unshared_widths(x1, x2, shared)
+    if flag and heads not in (1, 2):
+        return f"{heads} heads"
     if not (1 <= n <= _lib.FLEXNET_MAX_AGENTS and 1 <= w1 <= _lib.FLEXNET_MAX_AGENTS * _lib.FLEXNET_MAX_OBS
             and w2 <= _lib.FLEXNET_MAX_AGENTS * _lib.FLEXNET_MAX_ACT and (x2 is None or 1 <= x2.shape[2] <= _lib.FLEXNET_MAX_ACT)):
         return f"agents {n}, first block {w1}, second block {w2}"
-    if x1.shape[0] * n >= ACTOR_UNSHARED_MAX_ROWS:
-        return f"{x1.shape[0] * n} rows"
+    rows = (heads if flag else 1) * x1.shape[0] * n
+    if rows >= ACTOR_UNSHARED_MAX_ROWS:
+        return f"{rows} rows"
+    if flag and (th.cuda.is_current_stream_capturing() or in_graph_audit()):
+        return "the entry points are launched eagerly only"
     for i, c in enumerate(critics):
         if type(c) is not MLPCritic:
             return f"critic {i} is a {type(c).__name__}"
         a = c.args
         if not (a.hid_size == 64 and a.hid_activation == "relu" and c.fc3.out_features == 1):
             return f"critic {i}: hid {a.hid_size}, act {a.hid_activation}, out {c.fc3.out_features}"
-        if c.fc1.weight.shape[1] not in (w1 + w2, w1 + n + w2):
-            return f"critic {i}: fc1 takes {c.fc1.weight.shape[1]} columns, blocks {w1} + {w2}, {n} agents"
+        if c.fc1.weight.shape[1] not in (w1 + w2 + flag, w1 + n + w2 + flag):
+            return (f"critic {i}: fc1 takes {c.fc1.weight.shape[1]} columns, blocks {w1} + {w2}{' + the flag' if flag else ''}, "
+                    f"{n} agents")
         if c.fc1.weight.shape[1] != critics[0].fc1.weight.shape[1] or bool(a.layernorm) != bool(critics[0].args.layernorm):
             return f"critic {i} differs from critic 0 in its input width or LayerNorm"
         if not getattr(c, "fused_tail", True):
@@ -1381,29 +1404,35 @@ def critic_unshared_supported(critics, x1, x2=None, shared=False, train=False):
             and (not train or x1.shape[0] * x1.shape[1] >= WGRAD_MIN_ROWS))
 
 
-def _critic_unshared_args(cls, params, x1, x2, shared, ln_eps):
+def _critic_unshared_args(cls, params, x1, x2, shared, ln_eps, heads=None):
+    """The head of either family's forward or backward struct ``cls``: the shape, the switches and the pointer tables."""
     b, n, _ = x1.shape
     w1, w2 = _critic_unshared_widths(x1, x2, shared)
+    flag = int(heads is not None)
     a = cls()
     a.rows, a.n_agents, a.w1, a.w2 = b * n, n, w1, w2
-    a.agent_id, a.layernorm, a.ln_eps = int(params[0][0].shape[1] != w1 + w2), int(params[0][2] is not None), float(ln_eps)
+    if flag:
+        a.heads = heads
+    a.agent_id, a.layernorm, a.ln_eps = int(params[0][0].shape[1] != w1 + w2 + flag), int(params[0][2] is not None), float(ln_eps)
     _fill_tables(a, _CRITIC_UNSHARED_TABLES, params, n)
     return a
 
 
-def _critic_unshared_launch_forward(params, x1, x2, shared, ln_eps, saved=None):
-    """One flexnet_critic_unshared_forward launch on contiguous x1 [b, n, o] / x2 [b, n, a] or None; q [b, n], or None when the
-    library answers FLEXNET_EUNSUPPORTED."""
+def _critic_unshared_launch_forward(params, x1, x2, shared, ln_eps, saved=None, heads=None):
+    """One flexnet_critic_unshared_forward launch on contiguous x1 [b, n, o] / x2 [b, n, a] or None: q [b, n]; or — ``heads``
+    1 or 2 — one flexnet_critic_unshared_twin_forward launch: q [heads, b, n].  None when the library answers
+    FLEXNET_EUNSUPPORTED.  ``saved`` = (z1 [b n, 64], x [b n, 64] or [heads, b n, 64])."""
     b, n, o = x1.shape
-    q = th.empty(b, n, dtype=th.float32, device=x1.device)
-    a = _critic_unshared_args(_lib.FlexCriticUnsharedArgs, params, x1, x2, shared, ln_eps)
+    cls, _, entry = _critic_unshared_family(heads)[:3]
+    q = th.empty((b, n) if heads is None else (heads, b, n), dtype=th.float32, device=x1.device)
+    a = _critic_unshared_args(cls, params, x1, x2, shared, ln_eps, heads)
     a.x1, a.x1_pitch, a.x1_agent_off = x1.data_ptr(), n * o, 0 if shared else o
     if x2 is not None:
         a.x2, a.x2_pitch, a.x2_agent_off = x2.data_ptr(), n * x2.shape[2], 0 if shared else x2.shape[2]
     a.q = q.data_ptr()
     if saved is not None:
         a.save_z1, a.save_x = saved[0].data_ptr(), saved[1].data_ptr()
-    if not _lib.try_launch("flexnet_critic_unshared_forward", a):
+    if not _lib.try_launch(entry + "_forward", a):
         return None
     return q
 
@@ -1430,18 +1459,20 @@ class _CriticUnsharedFn(th.autograd.Function):
     d_fc1_w (its x1 block and its x2 block as two problems into column slices) and d_fc2_w.  The id block of agent a's fc1
     gradient is zero except its own column a, which is its bias gradient (the one-hot input).  ``x1`` takes no gradient; ``x2``
     takes the gradient of agent i's own action block only — maddpg.py:47-54 detaches the others, iddpg.py has no others.
-    ``param_grads`` False: the critics are frozen (the policy sub-update), no parameter gradient is formed.  Bit-reproducible."""
+    ``param_grads`` False: the critics are frozen (the policy sub-update), no parameter gradient is formed.  Bit-reproducible.
+    (``ctx.heads``, set by _CriticUnsharedTwinFn alone: the twin family's launches on the same plumbing.)"""
 
     @staticmethod
     def forward(ctx, x1, x2, shared, ln_eps, param_grads, *flat):
         b, n, _ = x1.shape
+        heads = ctx.heads = getattr(ctx, "heads", None)
         params = [flat[8 * i:8 * i + 8] for i in range(n)]
         x1 = x1.contiguous()
         x2 = None if x2 is None else x2.contiguous()
-        saved = th.empty(2, b * n, 64, dtype=th.float32, device=x1.device)           # z1 | x
-        q = _critic_unshared_launch_forward(params, x1, x2, shared, ln_eps, saved)
+        saved = th.empty(1 + (heads or 1), b * n, 64, dtype=th.float32, device=x1.device)     # z1 | x (per head)
+        q = _critic_unshared_launch_forward(params, x1, x2, shared, ln_eps, (saved[0], saved[1:]), heads)
         if q is None:
-            _lib.check(_lib.FLEXNET_EUNSUPPORTED, "flexnet_critic_unshared_forward")
+            _lib.check(_lib.FLEXNET_EUNSUPPORTED, _critic_unshared_family(heads)[2] + "_forward")
         ctx.shared, ctx.ln_eps, ctx.param_grads = bool(shared), float(ln_eps), bool(param_grads)
         ctx.has_ln, ctx.has_x2 = params[0][2] is not None, x2 is not None
         ctx.save_for_backward(x1, saved, *([x2] if x2 is not None else []), *[p for p in flat if p is not None])
@@ -1456,51 +1487,62 @@ class _CriticUnsharedFn(th.autograd.Function):
         if ctx.has_x2:
             x2, rest = rest[0], rest[1:]
         b, n, _ = x1.shape
-        dev, has_ln, shared = x1.device, ctx.has_ln, ctx.shared
+        dev, has_ln, shared, heads = x1.device, ctx.has_ln, ctx.shared, ctx.heads
+        _, cls, entry, key, ws_floats = _critic_unshared_family(heads)
+        flag = int(heads is not None)
+        hb = (heads or 1) * b                        # the rows per agent of dz2 and x: [heads, b, n, 64] keeps the pitch 64 n
         params = _regroup_params(rest, n, 8, has_ln)
         if dq is None:
             return (None,) * (5 + 8 * n)
+        if flag and th.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{entry}_backward is launched eagerly only")
         rows = b * n
         pg = ctx.param_grads and any(ctx.needs_input_grad[5:])
         want_x2 = x2 is not None and ctx.needs_input_grad[1]
         dq = dq.contiguous()
-        dz1 = th.empty(rows, 64, dtype=th.float32, device=dev)
-        g = _critic_unshared_args(_lib.FlexCriticUnsharedBwdArgs, params, x1, x2, shared, ctx.ln_eps)
+        dz1 = th.empty(rows, 64, dtype=th.float32, device=dev)                # (the twins': head 0's + head 1's)
+        g = _critic_unshared_args(cls, params, x1, x2, shared, ctx.ln_eps, heads)
         g.param_grads = int(pg)
-        g.dq, g.z1, g.x, g.dz1 = dq.data_ptr(), saved[0].data_ptr(), saved[1].data_ptr(), dz1.data_ptr()
+        g.dq, g.z1, g.x = dq.data_ptr(), saved[0].data_ptr(), saved[1].data_ptr()
+        setattr(g, "dz1_sum" if flag else "dz1", dz1.data_ptr())
         d_x2 = None
         if want_x2:
             act_dim = x2.shape[2]
             d_x2 = th.empty(b, n, act_dim, dtype=th.float32, device=dev)
             g.d_x2_own, g.own_first, g.own_step, g.own_w = d_x2.data_ptr(), 0, act_dim if shared else 0, act_dim
         if pg:
-            dz2 = th.empty(rows, 64, dtype=th.float32, device=dev)
-            small = th.empty(5, n, 64, dtype=th.float32, device=dev)          # d_ln_w | d_ln_b | d_fc1_b | d_fc2_b | d_fc3_w
+            dz2 = th.empty(hb * n, 64, dtype=th.float32, device=dev)
+            sums = ("d_ln_w", "d_ln_b", "d_fc1_b", "d_fc2_b", "d_fc3_w") + (("d_flag",) if flag else ())
+            small = th.empty(len(sums), n, 64, dtype=th.float32, device=dev)
             d_fc3_b = th.empty(n, 1, dtype=th.float32, device=dev)
-            ws = _scratch("critic_unshared", dev, _lib.FLEXNET_CRITIC_UNSHARED_WS_FLOATS)
+            ws = _scratch(key, dev, ws_floats)
             g.dz2, g.d_fc3_b = dz2.data_ptr(), d_fc3_b.data_ptr()
-            g.d_ln_w, g.d_ln_b, g.d_fc1_b, g.d_fc2_b, g.d_fc3_w = (small[k].data_ptr() for k in range(5))
+            for k, name in enumerate(sums):
+                setattr(g, name, small[k].data_ptr())
             g.workspace, g.workspace_floats = ws.data_ptr(), ws.numel()
-        _lib.launch("flexnet_critic_unshared_backward", g)
+        _lib.launch(entry + "_backward", g)
         if not pg:
             return (None, d_x2, None, None, None) + (None,) * (8 * n)
-        # the weight gradients: per agent d_fc1_w's x1 block, its x2 block and d_fc2_w, each over the agent's rows through the
-        # row pitch — one flexnet_wgrad_batched call
+        # the weight gradients: per agent d_fc1_w's x1 block and its x2 block from dz1 over the agent's b rows (the twins' heads
+        # share the first layer's input), and d_fc2_w over its heads * b rows, each through the row pitch — one
+        # flexnet_wgrad_batched call
         w1, w2 = g.w1, g.w2
         ld = params[0][0].shape[1]
-        n_id = ld - w1 - w2
+        n_id = ld - w1 - w2 - flag
         d_fc1_w = (th.zeros if n_id else th.empty)(n, 64, ld, dtype=th.float32, device=dev)
         d_fc2_w = th.empty(n, 64, 64, dtype=th.float32, device=dev)
-        dz1_3, dz2_3, x_3 = dz1.view(b, n, 64), dz2.view(b, n, 64), saved[1].view(b, n, 64)
+        dz1_3, dz2_3, x_3 = dz1.view(b, n, 64), dz2.view(hb, n, 64), saved[1:].view(hb, n, 64)
         problems = []
         for i in range(n):
             problems.append((dz1_3[:, i], x1.view(b, w1) if shared else x1[:, i], d_fc1_w[i, :, :w1], None))
             if x2 is not None:
-                problems.append((dz1_3[:, i], x2.view(b, w2) if shared else x2[:, i], d_fc1_w[i, :, w1 + n_id:], None))
+                problems.append((dz1_3[:, i], x2.view(b, w2) if shared else x2[:, i], d_fc1_w[i, :, w1 + n_id:w1 + n_id + w2], None))
             problems.append((dz2_3[:, i], x_3[:, i], d_fc2_w[i], None))
         tall_wgrad_batched(problems)
         if n_id:
             th.diagonal(d_fc1_w[:, :, w1:w1 + n], dim1=0, dim2=2).copy_(small[2].t())     # [64, n]: agent i's own id column
+        if flag:
+            d_fc1_w[:, :, ld - 1] = small[5]                                                # the flag column (zero with one head)
         grads = []
         for i in range(n):
             grads += [d_fc1_w[i], small[2, i], small[0, i] if has_ln else None, small[1, i] if has_ln else None,
@@ -1516,74 +1558,14 @@ def critic_unshared_train(critics, x1, x2=None, shared=False, param_grads=True):
 
 
 # ---- MATD3's per-agent twin critics of shared_params: False (csrc/critic_unshared_twin.hip): eager calls only -------------------
-def _critic_unshared_twin_declines(critics, obs, act, heads=2):
-    """Why csrc/critic_unshared_twin.hip does not cover these per-agent critics on obs [b, n, o] / act [b, n, a]: the conditions
-    of ``_critic_unshared_declines`` on maddpg.py's shared blocks, with the twin flag's column behind them in fc1."""
-    n = len(critics)
-    for name, t in (("obs", obs), ("act", act)):
-        if not (t.is_cuda and t.dtype == th.float32 and t.dim() == 3 and t.shape[1] == n and t.shape[0] == obs.shape[0]):
-            return f"{name} {tuple(t.shape)} {t.dtype} for {n} agents"
-    w1, w2 = _critic_unshared_widths(obs, act, True)
-    if heads not in (1, 2):
-        return f"{heads} heads"
-    if not (1 <= n <= _lib.FLEXNET_MAX_AGENTS and 1 <= w1 <= _lib.FLEXNET_MAX_AGENTS * _lib.FLEXNET_MAX_OBS
-            and 1 <= act.shape[2] <= _lib.FLEXNET_MAX_ACT):
-        return f"agents {n}, first block {w1}, second block {w2}"
-    if heads * obs.shape[0] * n >= ACTOR_UNSHARED_MAX_ROWS:
-        return f"{heads * obs.shape[0] * n} rows"
-    if th.cuda.is_current_stream_capturing() or in_graph_audit():
-        return "the entry points are launched eagerly only"
-    for i, c in enumerate(critics):
-        if type(c) is not MLPCritic:
-            return f"critic {i} is a {type(c).__name__}"
-        a = c.args
-        if not (a.hid_size == 64 and a.hid_activation == "relu" and c.fc3.out_features == 1):
-            return f"critic {i}: hid {a.hid_size}, act {a.hid_activation}, out {c.fc3.out_features}"
-        if c.fc1.weight.shape[1] not in (w1 + w2 + 1, w1 + n + w2 + 1):
-            return f"critic {i}: fc1 takes {c.fc1.weight.shape[1]} columns, blocks {w1} + {w2} + the flag, {n} agents"
-        if c.fc1.weight.shape[1] != critics[0].fc1.weight.shape[1] or bool(a.layernorm) != bool(critics[0].args.layernorm):
-            return f"critic {i} differs from critic 0 in its input width or LayerNorm"
-        if not getattr(c, "fused_tail", True):
-            return f"critic {i}: fused passes switched off"
-        why = _params_decline(_critic_unshared_params(c))
-        if why is not None:
-            return f"critic {i}: {why}"
-    return None
-
-
+# The checks, the launch and the node are the plain family's above with ``heads`` set: obs / act are maddpg.py's shared blocks.
 def critic_unshared_twin_supported(critics, obs, act, heads=2, train=False):
     """What csrc/critic_unshared_twin.hip covers: ``critic_unshared_supported``'s conditions on the blocks obs [b, n, o] (shared)
     and act [b, n, a] (shared), fc1 taking the flag column behind them, outside a graph capture; ``train``: also the row
     threshold of the hand-written weight gradients."""
     critics = list(critics)
-    return (_critic_unshared_twin_declines(critics, obs, act, heads) is None and not obs.requires_grad
+    return (_critic_unshared_declines(critics, obs, act, True, heads, ("obs", "act")) is None and not obs.requires_grad
             and (not train or obs.shape[0] * obs.shape[1] >= WGRAD_MIN_ROWS))
-
-
-def _critic_unshared_twin_args(cls, params, obs, act, heads, ln_eps):
-    b, n, _ = obs.shape
-    w1, w2 = _critic_unshared_widths(obs, act, True)
-    a = cls()
-    a.rows, a.n_agents, a.w1, a.w2, a.heads = b * n, n, w1, w2, heads
-    a.agent_id, a.layernorm, a.ln_eps = int(params[0][0].shape[1] != w1 + w2 + 1), int(params[0][2] is not None), float(ln_eps)
-    _fill_tables(a, _CRITIC_UNSHARED_TABLES, params, n)
-    return a
-
-
-def _critic_unshared_twin_launch_forward(params, obs, act, heads, ln_eps, saved=None):
-    """One flexnet_critic_unshared_twin_forward launch on contiguous obs [b, n, o] / act [b, n, a]; q [heads, b, n], or None
-    when the library answers FLEXNET_EUNSUPPORTED.  ``saved`` = (z1 [b n, 64], x [heads, b n, 64])."""
-    b, n, o = obs.shape
-    q = th.empty(heads, b, n, dtype=th.float32, device=obs.device)
-    a = _critic_unshared_twin_args(_lib.FlexCriticUnsharedTwinArgs, params, obs, act, heads, ln_eps)
-    a.x1, a.x1_pitch, a.x1_agent_off = obs.data_ptr(), n * o, 0
-    a.x2, a.x2_pitch, a.x2_agent_off = act.data_ptr(), n * act.shape[2], 0
-    a.q = q.data_ptr()
-    if saved is not None:
-        a.save_z1, a.save_x = saved[0].data_ptr(), saved[1].data_ptr()
-    if not _lib.try_launch("flexnet_critic_unshared_twin_forward", a):
-        return None
-    return q
 
 
 def fused_critic_forward_unshared_twin(critics, obs, act, heads=2):
@@ -1592,97 +1574,29 @@ def fused_critic_forward_unshared_twin(critics, obs, act, heads=2):
     fc1.weight's last column.  ``obs`` [b, n, o], ``act`` [b, n, a].  Returns q [heads, b, n] — cat([Q1, Q2], 0) — or None
     after ``note_fallback("critic_unshared_twin", ...)`` when it declines on GPU tensors."""
     critics = list(critics)
-    why = _critic_unshared_twin_declines(critics, obs, act, heads) if obs.is_cuda else "CPU tensors"
+    why = _critic_unshared_declines(critics, obs, act, True, heads, ("obs", "act")) if obs.is_cuda else "CPU tensors"
 
     def launch():
-        return _critic_unshared_twin_launch_forward([_critic_unshared_params(c) for c in critics], obs.contiguous(),
-                                                    act.contiguous(), heads, _ln_eps(critics[0]))
+        return _critic_unshared_launch_forward([_critic_unshared_params(c) for c in critics], obs.contiguous(), act.contiguous(),
+                                               True, _ln_eps(critics[0]), heads=heads)
     return _fused_inference("critic_unshared_twin", why, obs.is_cuda, "flexnet_critic_unshared_twin_forward", launch)
 
 
-class _CriticUnsharedTwinFn(th.autograd.Function):
-    """MATD3's per-agent twin critics for an update batch as ONE autograd node (csrc/critic_unshared_twin.hip): the fused
-    forward with its saves (fc1's output once, the first activation per head), the backward launches for dz1_sum, dz2, the
-    per-agent vector sums, the flag column's gradient and the own-action gradient, then ONE flexnet_wgrad_batched call: per
-    agent d_fc1_w's obs block and action block from dz1_sum (both heads share the first layer's input), and d_fc2_w as one
-    problem of heads * b rows.  The id block of agent a's fc1 gradient is zero except its own column a, which is its bias
-    gradient; its flag column is d_flag[a].  ``obs`` takes no gradient; ``act`` takes the gradient of agent i's own action
-    block through the FIRST head only — with heads = 2 and an action that requires a gradient the node refuses.  ``param_grads``
-    False: the critics are frozen (the policy sub-update).  For eager calls only.  Bit-reproducible."""
+class _CriticUnsharedTwinFn(_CriticUnsharedFn):
+    """MATD3's per-agent twin critics for an update batch as ONE autograd node (csrc/critic_unshared_twin.hip), on
+    _CriticUnsharedFn's plumbing: the fused forward with its saves (fc1's output once, the first activation per head), the
+    backward launches for dz1_sum, dz2, the per-agent vector sums, the flag column's gradient and the own-action gradient, then
+    ONE flexnet_wgrad_batched call: per agent d_fc1_w's obs block and action block from dz1_sum (both heads share the first
+    layer's input), and d_fc2_w as one problem of heads * b rows.  The id block of agent a's fc1 gradient is zero except its
+    own column a, which is its bias gradient; its flag column is d_flag[a].  ``obs`` takes no gradient; ``act`` takes the
+    gradient of agent i's own action block through the FIRST head only — with heads = 2 and an action that requires a gradient
+    the node refuses.  ``param_grads`` False: the critics are frozen (the policy sub-update).  For eager calls only.
+    Bit-reproducible."""
 
     @staticmethod
     def forward(ctx, obs, act, heads, ln_eps, param_grads, *flat):
-        b, n, _ = obs.shape
-        params = [flat[8 * i:8 * i + 8] for i in range(n)]
-        obs, act = obs.contiguous(), act.contiguous()
-        z1 = th.empty(b * n, 64, dtype=th.float32, device=obs.device)
-        x = th.empty(heads, b * n, 64, dtype=th.float32, device=obs.device)
-        q = _critic_unshared_twin_launch_forward(params, obs, act, heads, ln_eps, (z1, x))
-        if q is None:
-            _lib.check(_lib.FLEXNET_EUNSUPPORTED, "flexnet_critic_unshared_twin_forward")
-        ctx.heads, ctx.ln_eps, ctx.param_grads = int(heads), float(ln_eps), bool(param_grads)
-        ctx.has_ln = params[0][2] is not None
-        ctx.save_for_backward(obs, act, z1, x, *[p for p in flat if p is not None])
-        ctx.set_materialize_grads(False)
-        return q
-
-    @staticmethod
-    def backward(ctx, dq):
-        obs, act, z1, x = ctx.saved_tensors[:4]
-        b, n, _ = obs.shape
-        dev, has_ln, heads = obs.device, ctx.has_ln, ctx.heads
-        params = _regroup_params(ctx.saved_tensors[4:], n, 8, has_ln)
-        if dq is None:
-            return (None,) * (5 + 8 * n)
-        if th.cuda.is_current_stream_capturing():
-            raise RuntimeError("flexnet_critic_unshared_twin_backward is launched eagerly only")
-        rows = b * n
-        pg = ctx.param_grads and any(ctx.needs_input_grad[5:])
-        want_act = ctx.needs_input_grad[1]
-        dq = dq.contiguous()
-        dz1 = th.empty(rows, 64, dtype=th.float32, device=dev)
-        g = _critic_unshared_twin_args(_lib.FlexCriticUnsharedTwinBwdArgs, params, obs, act, heads, ctx.ln_eps)
-        g.param_grads = int(pg)
-        g.dq, g.z1, g.x, g.dz1_sum = dq.data_ptr(), z1.data_ptr(), x.data_ptr(), dz1.data_ptr()
-        d_act = None
-        if want_act:
-            act_dim = act.shape[2]
-            d_act = th.empty(b, n, act_dim, dtype=th.float32, device=dev)
-            g.d_x2_own, g.own_first, g.own_step, g.own_w = d_act.data_ptr(), 0, act_dim, act_dim
-        if pg:
-            dz2 = th.empty(heads, rows, 64, dtype=th.float32, device=dev)
-            small = th.empty(6, n, 64, dtype=th.float32, device=dev)   # d_ln_w | d_ln_b | d_fc1_b | d_fc2_b | d_fc3_w | d_flag
-            d_fc3_b = th.empty(n, 1, dtype=th.float32, device=dev)
-            ws = _scratch("critic_unshared_twin", dev, _lib.FLEXNET_CRITIC_UNSHARED_TWIN_WS_FLOATS)
-            g.dz2, g.d_fc3_b = dz2.data_ptr(), d_fc3_b.data_ptr()
-            g.d_ln_w, g.d_ln_b, g.d_fc1_b, g.d_fc2_b, g.d_fc3_w, g.d_flag = (small[k].data_ptr() for k in range(6))
-            g.workspace, g.workspace_floats = ws.data_ptr(), ws.numel()
-        _lib.launch("flexnet_critic_unshared_twin_backward", g)
-        if not pg:
-            return (None, d_act, None, None, None) + (None,) * (8 * n)
-        # the weight gradients in one flexnet_wgrad_batched call: per agent d_fc1_w's two column blocks from dz1_sum over the
-        # agent's b rows, and d_fc2_w over its heads * b rows — in [heads, b, n, 64] they keep the pitch 64 n across the heads
-        w1, w2 = g.w1, g.w2
-        ld = params[0][0].shape[1]
-        n_id = ld - w1 - w2 - 1
-        d_fc1_w = (th.zeros if n_id else th.empty)(n, 64, ld, dtype=th.float32, device=dev)
-        d_fc2_w = th.empty(n, 64, 64, dtype=th.float32, device=dev)
-        dz1_3, dz2_3, x_3 = dz1.view(b, n, 64), dz2.view(heads * b, n, 64), x.view(heads * b, n, 64)
-        obs_cols, act_cols = obs.view(b, w1), act.view(b, w2)
-        problems = []
-        for i in range(n):
-            problems.append((dz1_3[:, i], obs_cols, d_fc1_w[i, :, :w1], None))
-            problems.append((dz1_3[:, i], act_cols, d_fc1_w[i, :, w1 + n_id:w1 + n_id + w2], None))
-            problems.append((dz2_3[:, i], x_3[:, i], d_fc2_w[i], None))
-        tall_wgrad_batched(problems)
-        if n_id:
-            th.diagonal(d_fc1_w[:, :, w1:w1 + n], dim1=0, dim2=2).copy_(small[2].t())     # [64, n]: agent i's own id column
-        d_fc1_w[:, :, ld - 1] = small[5]                                                    # the flag column (zero with one head)
-        grads = []
-        for i in range(n):
-            grads += [d_fc1_w[i], small[2, i], small[0, i] if has_ln else None, small[1, i] if has_ln else None,
-                      d_fc2_w[i], small[3, i], small[4, i].view(1, 64), d_fc3_b[i]]
-        return (None, d_act, None, None, None, *grads)
+        ctx.heads = int(heads)
+        return _CriticUnsharedFn.forward(ctx, obs, act, True, ln_eps, param_grads, *flat)
 
 
 def critic_unshared_twin_train(critics, obs, act, heads=2, param_grads=True):
