@@ -85,6 +85,10 @@ def main():
     ap.add_argument("--unshared-twins", action="store_true",
                     help="shared_params: False under --alg matd3 — one actor and one twin-flag critic per agent "
                          "(csrc/critic_unshared_twin.hip: both heads from one first layer)")
+    ap.add_argument("--unshared-critics", action="store_true",
+                    help="with --unshared and --alg sqddpg | facmaddpg: the per-agent critics through the HIP kernels "
+                         "(FLEX_UNSHARED_CRITICS=1: csrc/sqddpg_unshared.hip, csrc/critic_unshared.hip) instead of the tensor "
+                         "composition / the per-agent loop")
     ap.add_argument("--episodic", action="store_true",
                     help="episodic: True of default.yaml — one update event per block of 95 vector steps, on batches of whole "
                          "episodes gathered by csrc/episodes.hip (ippo / mappo / coma: the on-policy triple batch_size = "
@@ -112,6 +116,10 @@ def main():
                  "asked for with --unshared-twins")
     if a.unshared_twins and a.alg != "matd3":
         ap.error("--unshared-twins: needs --alg matd3 (the other algorithms take --unshared)")
+    if a.unshared_critics:
+        if not a.unshared or a.alg not in ("sqddpg", "facmaddpg"):
+            ap.error("--unshared-critics: needs --unshared and --alg sqddpg or facmaddpg")
+        os.environ["FLEX_UNSHARED_CRITICS"] = "1"        # (read at every call of the critics)
 
     import torch
     import safe_marl_amd  # noqa: F401
@@ -222,6 +230,8 @@ def main():
                                  "(learner.RolloutGraph.fused_burst)")
         if a.unshared or a.unshared_twins:
             out["shared_params"] = False
+        if a.unshared_critics:
+            out["unshared_critics"] = True
         if a.episodic:
             out["episodic"] = True
         print(json.dumps(out))

@@ -698,6 +698,67 @@ int flexnet_sqddpg_draw(const FlexSqddpgDrawArgs* args, void* stream);
 int flexnet_sqddpg_forward(const FlexSqddpgArgs* args, void* stream);
 int flexnet_sqddpg_backward(const FlexSqddpgArgs* args, void* stream);
 
+/* SQDDPG with shared_params False: one MLPCritic per agent (csrc/sqddpg_unshared.hip).  Row (b, s, i) goes through critic i:
+ *     z1 = z_shared[b, i] + z_id[i] + W_act_i x,     x as above from pos,
+ * with z_shared[b, i] = W_obs_i obs_all[b] + b1_i formed by the caller ([b, n, 64]) and z_id[i] critic i's OWN id column (no
+ * other id column of critic i ever meets a 1).  The weights are read where the modules keep them, through per-agent pointer
+ * tables: w_act[i] points at the first action column of critic i's fc1.weight and w_id[i] at its id column i, both with the
+ * row pitch ld_fc1 (floats).  One wavefront owns a chunk of whole samples of ONE agent (the agent is a grid dimension); lane
+ * `ls` sums its sample's q over s in order.
+ * forward:  q [b, ns, n] and phi [b, n] (each optional, not both NULL), the layouts of flexnet_sqddpg_forward.  S = sum_i phi
+ *           is the caller's (a sample's agents live in different work-groups).
+ * backward: from d_phi [b, n] (and optionally d_q) recomputes the forward and writes d_z_shared [b, n, 64] and d_act_own
+ *           [b, n, a] where non-NULL; with want_param_grads, per agent, d_z_id [n, 64], d_w_act [n, 64, n a], d_ln_w / d_ln_b
+ *           (layernorm) / d_fc2_b / d_fc3_w [n, 64], d_fc2_w [n, 64, 64], d_fc3_b [n], through per-wavefront partials of a
+ *           persistent grid per agent in `workspace` and a fixed-order reduction.  The grid of one agent is at most
+ *           FLEXNET_SQDDPG_UNSHARED_BWD_GRID wavefronts; `workspace` holds n_agents * FLEXNET_SQDDPG_UNSHARED_BWD_GRID *
+ *           FLEXNET_SQDDPG_UNSHARED_WS_ROW floats.
+ * No atomics: bit-reproducible.  Limits as flexnet_sqddpg_*: n_agents 1..FLEXNET_MAX_AGENTS, act_dim 1..8 with n * act_dim <=
+ * 32, sample_size >= 1 with sample_size * n <= 4096, z_shared and every fc2_w 16-byte aligned; else FLEXNET_EUNSUPPORTED.  A
+ * missing tensor or table entry (of agents 0..n-1), batch < 0, ld_fc1 < n * act_dim: FLEXNET_EINVAL.  Both before any HIP
+ * call. */
+#define FLEXNET_SQDDPG_UNSHARED_WS_ROW 6528
+#define FLEXNET_SQDDPG_UNSHARED_BWD_GRID 256
+typedef struct {
+    int64_t batch;             /* b */
+    int32_t n_agents;
+    int32_t act_dim;
+    int32_t sample_size;       /* ns */
+    int32_t layernorm;
+    float ln_eps;
+    int32_t want_param_grads;  /* backward */
+    int64_t ld_fc1;            /* floats between the rows of every fc1.weight */
+    const float* z_shared;     /* [b, n, 64]: W_obs_i obs_all + fc1_i.bias */
+    const float* act;          /* [b, n, a] */
+    const int32_t* pos;        /* [b ns, n] */
+    const float* w_act[FLEXNET_MAX_AGENTS];    /* per agent: fc1.weight + first action column, [64, n a] at pitch ld_fc1 */
+    const float* w_id[FLEXNET_MAX_AGENTS];     /* fc1.weight + the agent's own id column, [64] at pitch ld_fc1 */
+    const float* ln_w[FLEXNET_MAX_AGENTS];     /* [64] (layernorm) */
+    const float* ln_b[FLEXNET_MAX_AGENTS];
+    const float* fc2_w[FLEXNET_MAX_AGENTS];    /* [64, 64] */
+    const float* fc2_b[FLEXNET_MAX_AGENTS];    /* [64] */
+    const float* fc3_w[FLEXNET_MAX_AGENTS];    /* [1, 64] */
+    const float* fc3_b[FLEXNET_MAX_AGENTS];    /* [1] */
+    float* q;                  /* forward out [b, ns, n] (optional) */
+    float* phi;                /* forward out [b, n] (optional) */
+    const float* d_phi;        /* backward in [b, n] */
+    const float* d_q;          /* backward in [b, ns, n] (optional) */
+    float* d_z_shared;         /* backward out [b, n, 64] (optional) */
+    float* d_act_own;          /* backward out [b, n, a] (optional) */
+    float* d_z_id;             /* backward out, want_param_grads: [n, 64] */
+    float* d_w_act;            /* [n, 64, n a] */
+    float* d_ln_w;             /* [n, 64] each (layernorm) */
+    float* d_ln_b;
+    float* d_fc2_w;            /* [n, 64, 64] */
+    float* d_fc2_b;            /* [n, 64] */
+    float* d_fc3_w;            /* [n, 64] */
+    float* d_fc3_b;            /* [n] */
+    float* workspace;          /* n_agents * FLEXNET_SQDDPG_UNSHARED_BWD_GRID * FLEXNET_SQDDPG_UNSHARED_WS_ROW floats */
+} FlexSqddpgUnsharedArgs;
+
+int flexnet_sqddpg_unshared_forward(const FlexSqddpgUnsharedArgs* args, void* stream);
+int flexnet_sqddpg_unshared_backward(const FlexSqddpgUnsharedArgs* args, void* stream);
+
 /* ---- PPO (IPPO / MAPPO): madrl/learning_algorithms/ppo.py:14-69 around the networks (csrc/ppo.hip) ----------------
  * [rows, n_agents] fp32 tensors, n_agents <= FLEXNET_MAX_AGENTS.  Fixed-order reductions, no atomics: bit-reproducible.
  * gae:    reward_norm = BatchNorm(reward) (reward_bn.enabled, else a copy);

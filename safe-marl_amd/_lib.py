@@ -80,6 +80,7 @@ SYMBOLS = (
     "flexnet_scaled_sum", "flexnet_agent_sum_explore", "flexnet_gather_rows", "flexnet_gather_rows_td", "flexnet_window_refresh", "flexnet_gather_window", "flexnet_gather_episodes", "flexnet_linear2", "flexnet_gru_backward",
     "flexnet_qmix_forward", "flexnet_qmix_backward",
     "flexnet_sqddpg_draw", "flexnet_sqddpg_forward", "flexnet_sqddpg_backward",
+    "flexnet_sqddpg_unshared_forward", "flexnet_sqddpg_unshared_backward",
     "flexnet_ppo_gae", "flexnet_ppo_policy_loss", "flexnet_ppo_value_loss",
     "flexnet_coma_baseline", "flexnet_coma_policy_loss",
     "flexnet_gauss_head_forward", "flexnet_gauss_head_backward", "flexnet_gauss_sum_explore", "flexnet_ppo_policy_loss_rows",
@@ -403,6 +404,21 @@ class FlexSqddpgArgs(C.Structure):
                [(k, C.c_void_p) for k in SQDDPG_PTRS]
 
 
+FLEXNET_SQDDPG_UNSHARED_WS_ROW = 6528
+FLEXNET_SQDDPG_UNSHARED_BWD_GRID = 256          # wavefronts of ONE agent's persistent backward grid
+SQDDPG_UNSHARED_TABLES = ("w_act", "w_id", "ln_w", "ln_b", "fc2_w", "fc2_b", "fc3_w", "fc3_b")
+SQDDPG_UNSHARED_PTRS = ("q", "phi", "d_phi", "d_q", "d_z_shared", "d_act_own", "d_z_id", "d_w_act", "d_ln_w", "d_ln_b",
+                        "d_fc2_w", "d_fc2_b", "d_fc3_w", "d_fc3_b", "workspace")
+
+
+class FlexSqddpgUnsharedArgs(C.Structure):
+    """include/flexnet.h: SQDDPG's per-agent critics (csrc/sqddpg_unshared.hip)"""
+    _fields_ = [("batch", C.c_int64), ("n_agents", C.c_int32), ("act_dim", C.c_int32), ("sample_size", C.c_int32),
+                ("layernorm", C.c_int32), ("ln_eps", C.c_float), ("want_param_grads", C.c_int32), ("ld_fc1", C.c_int64)] + \
+               [(k, C.c_void_p) for k in ("z_shared", "act", "pos")] + \
+               [(k, _AgentPtrs) for k in SQDDPG_UNSHARED_TABLES] + [(k, C.c_void_p) for k in SQDDPG_UNSHARED_PTRS]
+
+
 FLEXNET_PPO_BLOCKS = 256
 FLEXNET_PPO_WS_FLOATS = 2 * FLEXNET_TD_WS_FLOATS + 2 * FLEXNET_PPO_BLOCKS
 
@@ -698,6 +714,9 @@ def load():
         fn.restype = C.c_int
     for fn in (lib.flexnet_sqddpg_forward, lib.flexnet_sqddpg_backward):
         fn.argtypes = [C.POINTER(FlexSqddpgArgs), vp]
+        fn.restype = C.c_int
+    for fn in (lib.flexnet_sqddpg_unshared_forward, lib.flexnet_sqddpg_unshared_backward):
+        fn.argtypes = [C.POINTER(FlexSqddpgUnsharedArgs), vp]
         fn.restype = C.c_int
     for fn, st in ((lib.flexnet_coma_baseline, FlexComaBaselineArgs), (lib.flexnet_coma_policy_loss, FlexComaPolicyArgs)):
         fn.argtypes = [C.POINTER(st), vp]

@@ -20,7 +20,7 @@ SRC = [os.path.join(CSRC, f) for f in ("flexenv.hip", "actor.hip", "critic.hip",
                                        "optim.hip", "tdloss.hip", "gru.hip", "linear.hip", "opf.hip",
                                        "qmix.hip", "sqddpg.hip", "ppo.hip", "coma.hip", "gauss.hip", "actor_unshared.hip",
                                        "critic_unshared.hip", "actor_mlp.hip", "attn_critic.hip", "episodes.hip",
-                                       "critic_unshared_twin.hip")]
+                                       "critic_unshared_twin.hip", "sqddpg_unshared.hip")]
 SRC = [f for f in SRC if os.path.exists(f)]
 # every header under csrc/ and include/ (a list by name missed critic_finish.h and window_refresh.h when they were added:
 # an edit to either neither rebuilt the library nor changed the digest the profiles are stamped with)

@@ -31,7 +31,8 @@ from .nets import (WGRAD_MIN_ROWS, AttentionCritic, attn_critic, CriticTail, cri
                    critic_unshared_twin_supported, critic_unshared_twin_train, fused_critic_forward_unshared_twin,
                    tall_linear, td_loss, td_loss_supported, wide_batch_linear,
                    batchnorm_stats_supported, batchnorm_update_running_stats, sync_batchnorm, QMixer,
-                   sqddpg_draw, sqddpg_fused_config, sqddpg_shapley_fused, ppo_gae, ppo_policy_loss, ppo_value_loss,
+                   sqddpg_draw, sqddpg_fused_config, sqddpg_shapley_fused, sqddpg_shapley_unshared, sqddpg_unshared_config,
+                   unshared_critics_switch, ppo_gae, ppo_policy_loss, ppo_value_loss,
                    coma_baseline, coma_baseline_torch, coma_fused_config, coma_policy_loss, coma_rows)
 from .replay_buffer import Transition
 from .util import _graph_audit, graph_capture, prep_obs, scale_action, select_action, translate_action, mean_all, note_fallback
@@ -984,13 +985,16 @@ class Model(nn.Module):
     # algorithms whose per-agent critics (shared_params False) csrc/critic_unshared.hip covers: their `value` is one MLPCritic
     # per agent on rows made of an observation block, the id columns and an optional action block
     unshared_critic_kernel = False
+    # ... and those that take it only under FLEX_UNSHARED_CRITICS=1 (nets.unshared_critics_switch, read at every call)
+    unshared_critic_opt_in = False
 
     def unshared_values(self, obs, act, shared, critic_frozen=False):
         """The per-agent critics of ``shared_params: False`` on the blocks obs [b, n, o] / act [b, n, a] or None in one launch
         per direction (nets.fused_critic_forward_unshared without a graph at any size, the node nets._CriticUnsharedFn with
         one from WGRAD_MIN_ROWS rows): [b, n, 1], or None where the per-agent loop runs — the CPU, ``fused_inference`` off,
         small batches with a graph (silently) and configurations the kernel declines (after a ``critic_unshared`` note)."""
-        if not (self.unshared_critic_kernel and not self.args.shared_params and obs.is_cuda and self.fused_inference):
+        takes = self.unshared_critic_kernel or (self.unshared_critic_opt_in and unshared_critics_switch())
+        if not (takes and not self.args.shared_params and obs.is_cuda and self.fused_inference):
             return None
         b, n = obs.size(0), self.n_
         critics = list(self.value_dicts)
@@ -2214,7 +2218,8 @@ class FACMADDPG(IDDPG):
     (trainer.mixer_replay_process, args.mixer)."""
 
     graph_safe_updates = False       # sub-updates run eagerly (the mixer's losses are not audited for graph capture)
-    unshared_critic_kernel = False   # (unshared critics keep the per-agent loop)
+    unshared_critic_kernel = False   # (unshared critics keep the per-agent loop ...
+    unshared_critic_opt_in = True    # ... unless FLEX_UNSHARED_CRITICS=1: then IDDPG's rows through csrc/critic_unshared.hip)
     bootstrap_cacheable = False      # own get_loss: the bootstrap target is Q_tot', not per-agent values
 
     def construct_value_net(self):
@@ -2233,7 +2238,8 @@ class FACMADDPG(IDDPG):
             _, actions_pol, _, action_out, _ = self.get_actions(state, status="train", exploration=False,
                                                                 actions_avail=actions_avail, target=False,
                                                                 last_hid=last_hids)
-            policy_loss = self.policy_term(self.value(state, actions_pol).contiguous().view(-1, n))
+            # (a policy sub-update takes the own-action gradient alone: the per-agent kernels skip the critics' parameter gradients)
+            policy_loss = self.policy_term(self.value(state, actions_pol, critic_frozen=(need == "policy")).contiguous().view(-1, n))
         if need in ("both", "value", "mixer"):
             with th.no_grad():
                 # double_q: the next actions from the behaviour policy (facmaddpg.py:90-93), valued by the target critic
@@ -2264,7 +2270,7 @@ class SQDDPG(MADDPG):
     (``marginal_contribution_torch``)."""
 
     graph_safe_updates = False       # sub-updates run eagerly (fresh coalitions per call; not audited for graph capture)
-    unshared_critic_kernel = False   # (unshared critics keep the per-agent loop)
+    unshared_critic_kernel = False   # (unshared critics run the composition; FLEX_UNSHARED_CRITICS=1: csrc/sqddpg_unshared.hip)
     bootstrap_cacheable = False      # own get_loss: the target term draws its own coalitions in every value sub-update
     get_actions = IDDPG.get_actions  # the same function object (RolloutGraph.summed checks identity)
     coalition_source = None          # tests: callable(role, groups) -> pos [groups, n], role "policy" / "value" / "target"
@@ -2324,10 +2330,25 @@ class SQDDPG(MADDPG):
             self.note_unfused("sqddpg")
         return ok
 
+    def _unshared_kernel(self, obs, act):
+        """Per-agent critics (shared_params False) on GPU tensors under FLEX_UNSHARED_CRITICS=1: whether
+        csrc/sqddpg_unshared.hip covers the call; a decline leaves a ``sqddpg_unshared`` note."""
+        ok = (self.fused_inference and act.dtype == th.float32 and obs.dtype == th.float32 and obs.is_cuda
+              and sqddpg_unshared_config(self.value_dicts, self.n_, self.act_dim, self.sample_size))
+        if not ok:
+            self.note_unfused("sqddpg_unshared")
+        return ok
+
     def shapley_values(self, obs, act, pos, want_q=False, frozen=False):
         """(phi [b, n], values [b, ns, n, 1] or None) on the coalitions ``pos``; ``frozen``: no critic-parameter gradients."""
         b, n = obs.size(0), self.n_
-        if self._fused(act):
+        if not self.args.shared_params and act.is_cuda and unshared_critics_switch():
+            # opt-in (the default keeps the composition and its "sqddpg" note): one critic per agent in csrc/sqddpg_unshared.hip
+            if self._unshared_kernel(obs, act):
+                phi, q = sqddpg_shapley_unshared(self.value_dicts, obs.reshape(b, n * self.obs_dim), act, pos,
+                                                 self.sample_size, want_q=want_q, frozen=frozen)
+                return phi, (q.unsqueeze(-1) if want_q else None)
+        elif self._fused(act):
             phi, q = sqddpg_shapley_fused(self.value_dicts[0], obs.reshape(b, n * self.obs_dim), act.to(th.float32),
                                           pos, self.sample_size, want_q=want_q, frozen=frozen)
             return phi, (q.unsqueeze(-1) if want_q else None)

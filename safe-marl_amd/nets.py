@@ -3016,6 +3016,182 @@ def sqddpg_shapley_fused(critic, obs2d, act, pos, ns, want_q=False, frozen=False
     return phi, (q if want_q else None)
 
 
+# ---- SQDDPG with shared_params False: one critic per agent (csrc/sqddpg_unshared.hip) ------------------------------------------
+def unshared_critics_switch():
+    """FLEX_UNSHARED_CRITICS=1: FACMADDPG's and SQDDPG's per-agent critics (shared_params False) take the HIP kernels instead of
+    the per-agent loop / the tensor composition.  Opt-in, and read from the environment at every call."""
+    return os.environ.get("FLEX_UNSHARED_CRITICS", "") == "1"
+
+
+def sqddpg_unshared_config(critics, n_agents, act_dim, sample_size):
+    """The configuration csrc/sqddpg_unshared.hip implements (include/flexnet.h: flexnet_sqddpg_unshared_forward): one
+    ``type(...) is MLPCritic`` per agent with hid 64, ReLU, one output and the agent id columns, all of one input width and one
+    LayerNorm setting, fp32 contiguous device parameters, n <= 8 agents, act_dim <= 8 with n * act_dim <= 32."""
+    critics = list(critics)
+    if not (len(critics) == n_agents and 1 <= n_agents <= 8 and 1 <= act_dim <= 8 and n_agents * act_dim <= 32
+            and sample_size >= 1 and sample_size * n_agents <= 4096):
+        return False
+    for c in critics:
+        if type(c) is not MLPCritic or not (_critic_config_ok(c) and c.args.agent_id and getattr(c, "fused_tail", True)):
+            return False
+        if (c.fc1.weight.shape[1] != critics[0].fc1.weight.shape[1] or c.fc1.weight.shape[1] <= n_agents * act_dim + n_agents
+                or bool(c.args.layernorm) != bool(critics[0].args.layernorm)):
+            return False
+        if _params_decline(_critic_unshared_params(c)) is not None:
+            return False
+    return True
+
+
+class _SqddpgZSharedFn(th.autograd.Function):
+    """z_shared [b, n, 64] of the per-agent critics: z_shared[:, i] = obs2d @ W_i[:, :no].T + b_i, one library GEMM on the
+    stacked observation columns.  Backward: every agent's dW_obs (into the first ``no`` columns of a full-width zero gradient
+    of its fc1.weight) and db in ONE flexnet_wgrad_batched call — agent i's rows dz[:, i] are an ordinary problem at row pitch
+    64 n — from WGRAD_MIN_ROWS samples, the library GEMM below.  Inputs: obs2d [b, no], no, then (fc1.weight, fc1.bias) per
+    agent."""
+
+    @staticmethod
+    def forward(ctx, obs2d, no, *wb):
+        ws, bs = wb[0::2], wb[1::2]
+        wcat = th.cat([w[:, :no] for w in ws], 0)
+        z = th.addmm(th.cat(bs), obs2d, wcat.t())
+        ctx.no, ctx.ld = no, ws[0].shape[1]
+        ctx.save_for_backward(obs2d, wcat if obs2d.requires_grad else obs2d.new_empty(0))
+        return z.view(obs2d.shape[0], len(ws), 64)
+
+    @staticmethod
+    def backward(ctx, dz):
+        obs2d, wcat = ctx.saved_tensors
+        dz = dz.contiguous()
+        b, n, _ = dz.shape
+        no, need = ctx.no, ctx.needs_input_grad
+        grads = [None] * (2 * n)
+        if any(need[2:]):
+            gw = th.zeros(n, 64, ctx.ld, dtype=th.float32, device=dz.device)
+            if b >= WGRAD_MIN_ROWS and tall_wgrad_supported(dz[:, 0], obs2d):
+                gb = th.empty(n, 64, dtype=th.float32, device=dz.device)
+                tall_wgrad_batched([(dz[:, i], obs2d, gw[i][:, :no], gb[i]) for i in range(n)])
+            else:
+                gw[:, :, :no] = (dz.view(b, n * 64).t() @ obs2d).view(n, 64, no)
+                gb = dz.sum(0)
+            for i in range(n):
+                grads[2 * i], grads[2 * i + 1] = (gw[i] if need[2 + 2 * i] else None), (gb[i] if need[3 + 2 * i] else None)
+        dx = dz.view(b, n * 64) @ wcat if need[0] else None
+        return (dx, None, *grads)
+
+
+_SQU_PER_AGENT = 7           # fc1.weight, then the tail: ln_w, ln_b, fc2_w, fc2_b, fc3_w, fc3_b
+
+
+def _sqddpg_unshared_args(z_shared, act, pos, ns, eps, layernorm, no, ps):
+    a = _lib.FlexSqddpgUnsharedArgs()
+    a.batch, a.n_agents, a.act_dim = act.shape
+    n, nka = act.shape[1], act.shape[1] * act.shape[2]
+    a.sample_size, a.layernorm, a.ln_eps = ns, int(layernorm), eps
+    a.ld_fc1 = ps[0][0].stride(0)
+    a.z_shared, a.act, a.pos = z_shared.data_ptr(), act.data_ptr(), pos.data_ptr()
+    for i, (w, ln_w, ln_b, fc2_w, fc2_b, fc3_w, fc3_b) in enumerate(ps):
+        # the action columns and the agent's own id column of fc1.weight, read in place at the weight's row pitch
+        a.w_act[i], a.w_id[i] = w.data_ptr() + 4 * no, w.data_ptr() + 4 * (no + nka + i)
+        if layernorm:
+            a.ln_w[i], a.ln_b[i] = ln_w.data_ptr(), ln_b.data_ptr()
+        a.fc2_w[i], a.fc2_b[i], a.fc3_w[i], a.fc3_b[i] = fc2_w.data_ptr(), fc2_b.data_ptr(), fc3_w.data_ptr(), fc3_b.data_ptr()
+    return a
+
+
+class _SqddpgUnsharedFn(th.autograd.Function):
+    """_SqddpgFn for one critic per agent: phi [b, n] and (want_q) q [b, ns, n] with row (b, s, i) through critic i —
+    flexnet_sqddpg_unshared_forward / flexnet_sqddpg_unshared_backward.  Inputs: z_shared [b, n, 64] (_SqddpgZSharedFn), act
+    [b, n, a] (only agent i's own action takes a gradient from row (b, s, i)), pos [b ns, n], ``no`` = fc1's observation columns;
+    then per agent fc1.weight and the tail's parameters.  fc1.weight's gradient from here is zero outside its action columns and
+    the agent's own id column."""
+
+    @staticmethod
+    def forward(ctx, z_shared, act, pos, ns, eps, layernorm, want_q, no, *flat):
+        ctx.set_materialize_grads(False)
+        z_shared, act = z_shared.contiguous(), act.contiguous()
+        pos = pos.to(th.int32).contiguous()
+        b, n, _ = act.shape
+        ps = [list(flat[_SQU_PER_AGENT * i:_SQU_PER_AGENT * (i + 1)]) for i in range(n)]
+        phi = th.empty(b, n, dtype=th.float32, device=act.device)
+        q = th.empty(b, ns, n, dtype=th.float32, device=act.device) if want_q else phi.new_empty(0)
+        k = _sqddpg_unshared_args(z_shared, act, pos, ns, eps, layernorm, no, ps)
+        k.phi = phi.data_ptr()
+        if want_q:
+            k.q = q.data_ptr()
+        _lib.launch("flexnet_sqddpg_unshared_forward", k)
+        ctx.ns, ctx.eps, ctx.layernorm, ctx.no = ns, eps, layernorm, no
+        ctx.save_for_backward(z_shared, act, pos, *[p for agent in ps for p in agent if p is not None])
+        if not want_q:
+            ctx.mark_non_differentiable(q)
+        return phi, q
+
+    @staticmethod
+    def backward(ctx, d_phi, d_q):
+        z_shared, act, pos, *saved = ctx.saved_tensors
+        b, n, ad = act.shape
+        ps = _regroup_params(saved, n, _SQU_PER_AGENT, ctx.layernorm, ln_slots=(1, 2))
+        dev, no, nka = act.device, ctx.no, n * ad
+        need = ctx.needs_input_grad
+        d_phi = th.zeros(b, n, dtype=th.float32, device=dev) if d_phi is None else d_phi.contiguous()
+        k = _sqddpg_unshared_args(z_shared, act, pos, ctx.ns, ctx.eps, ctx.layernorm, no, ps)
+        k.d_phi = d_phi.data_ptr()
+        if d_q is not None and d_q.numel() == b * ctx.ns * n:
+            d_q = d_q.contiguous()
+            k.d_q = d_q.data_ptr()
+        dz = th.empty(b, n, 64, dtype=th.float32, device=dev) if need[0] else None
+        da = th.empty(b, n, ad, dtype=th.float32, device=dev) if need[1] else None
+        if dz is not None:
+            k.d_z_shared = dz.data_ptr()
+        if da is not None:
+            k.d_act_own = da.data_ptr()
+        out = [None] * (_SQU_PER_AGENT * n)
+        want_w = any(need[8:])
+        if want_w:
+            ws = _scratch(("sqddpg_unshared", n), dev,
+                          n * _lib.FLEXNET_SQDDPG_UNSHARED_BWD_GRID * _lib.FLEXNET_SQDDPG_UNSHARED_WS_ROW)
+            g = dict(d_z_id=th.empty(n, 64, device=dev), d_w_act=th.empty(n, 64, nka, device=dev),
+                     d_ln_w=th.zeros(n, 64, device=dev), d_ln_b=th.zeros(n, 64, device=dev),
+                     d_fc2_w=th.empty(n, 64, 64, device=dev), d_fc2_b=th.empty(n, 64, device=dev),
+                     d_fc3_w=th.empty(n, 64, device=dev), d_fc3_b=th.empty(n, device=dev))
+            k.want_param_grads = 1
+            k.workspace = ws.data_ptr()
+            for name, t in g.items():
+                setattr(k, name, t.data_ptr())
+        _lib.launch("flexnet_sqddpg_unshared_backward", k)
+        if want_w:
+            gw = th.zeros(n, 64, ps[0][0].shape[1], dtype=th.float32, device=dev)
+            gw[:, :, no:no + nka] = g["d_w_act"]
+            gw[:, :, no + nka:no + nka + n].diagonal(dim1=0, dim2=2).copy_(g["d_z_id"].t())
+            for i in range(n):
+                per = [gw[i], g["d_ln_w"][i] if ctx.layernorm else None, g["d_ln_b"][i] if ctx.layernorm else None,
+                       g["d_fc2_w"][i], g["d_fc2_b"][i], g["d_fc3_w"][i].view(1, 64), g["d_fc3_b"][i:i + 1]]
+                for j, t in enumerate(per):
+                    if need[8 + _SQU_PER_AGENT * i + j]:
+                        out[_SQU_PER_AGENT * i + j] = t
+        return (dz, da, None, None, None, None, None, None, *out)
+
+
+def sqddpg_shapley_unshared(critics, obs2d, act, pos, ns, want_q=False, frozen=False):
+    """(phi [b, n], q [b, ns, n] or None) of madrl/models/sqddpg.py:63-104 with one critic per agent (its else branch at
+    :94-100) through csrc/sqddpg_unshared.hip.  z_shared [b, n, 64] comes from obs2d [b, n o] and each critic's observation
+    columns and bias (_SqddpgZSharedFn); the reference's row layout [obs | coalition actions | onehot(i)] fixes the column
+    blocks of every fc1.  ``frozen``: no critic parameter takes a gradient (a policy sub-update)."""
+    critics = list(critics)
+    no = obs2d.shape[1]
+    wb, flat = [], []
+    for c in critics:
+        w, bias = c.fc1.weight, c.fc1.bias
+        *tail, eps = _tail_params(c)
+        if frozen:
+            w, bias = w.detach(), bias.detach()
+            tail = [None if p is None else p.detach() for p in tail]
+        wb += [w, bias]
+        flat += [w, *tail]
+    z_shared = _SqddpgZSharedFn.apply(obs2d, no, *wb)
+    phi, q = _SqddpgUnsharedFn.apply(z_shared, act, pos, ns, eps, bool(critics[0].args.layernorm), want_q, no, *flat)
+    return phi, (q if want_q else None)
+
+
 # ---- PPO (IPPO / MAPPO): madrl/learning_algorithms/ppo.py:14-69 around the networks ---------------------------------------
 # Three pieces, each as a fused launch sequence of csrc/ppo.hip on the GPU and as the tensor composition of the same
 # formulas everywhere else (CPU, fp64, more than 8 agents, a masked action_avail, cross-rank BatchNorm statistics): the
