@@ -293,11 +293,13 @@ int flexnet_lnrelu_backward(const FlexLnReluArgs* args, void* stream);
 typedef struct {
     int32_t n_tensors;         /* <= FLEXNET_OPT_MAX_TENSORS; tensors whose gradient is None are simply not listed */
     float lr, alpha, eps;
-    float max_norm;            /* <= 0: no clipping */
-    int32_t pad0;
+    float max_norm;            /* <= 0: no clipping.  optim.clip_and_step never sends it: clip_grad_norm_ zeroes the gradients at
+                                * 0 and turns them round below it, and the wrapper takes the PyTorch calls there.  A NaN norm
+                                * reaches every gradient, as torch.clamp hands it on */
+    float one_minus_alpha;     /* 1 - alpha rounded from the caller's double, as RMSprop forms it; 0: 1.0f - alpha */
     float* total_norm;         /* out [1]: the pre-clip 2-norm over all listed gradients, or NULL */
     float* workspace;          /* FLEXNET_OPT_WS_FLOATS floats of scratch */
-    int64_t numel[FLEXNET_OPT_MAX_TENSORS];
+    int64_t numel[FLEXNET_OPT_MAX_TENSORS];      /* a tensor of no elements has no address: not listed either */
     float* param[FLEXNET_OPT_MAX_TENSORS];
     float* grad[FLEXNET_OPT_MAX_TENSORS];        /* scaled in place by the clip factor, as clip_grad_norm_ does */
     float* square_avg[FLEXNET_OPT_MAX_TENSORS];  /* RMSprop state */

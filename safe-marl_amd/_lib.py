@@ -345,7 +345,7 @@ FLEXNET_OPT_MAX_ELEMENTS = 1 << 20
 
 class FlexClipRmspropArgs(C.Structure):
     _fields_ = [("n_tensors", C.c_int32), ("lr", C.c_float), ("alpha", C.c_float), ("eps", C.c_float),
-                ("max_norm", C.c_float), ("pad0", C.c_int32), ("total_norm", C.c_void_p), ("workspace", C.c_void_p),
+                ("max_norm", C.c_float), ("one_minus_alpha", C.c_float), ("total_norm", C.c_void_p), ("workspace", C.c_void_p),
                 ("numel", C.c_int64 * FLEXNET_OPT_MAX_TENSORS), ("param", C.c_void_p * FLEXNET_OPT_MAX_TENSORS),
                 ("grad", C.c_void_p * FLEXNET_OPT_MAX_TENSORS), ("square_avg", C.c_void_p * FLEXNET_OPT_MAX_TENSORS),
                 ("step", C.c_void_p * FLEXNET_OPT_MAX_TENSORS)]

@@ -119,8 +119,15 @@ __global__ __launch_bounds__(OPT_THREADS) void clip_rmsprop_kernel(FlexClipRmspr
     const float norm = sqrtf(tot_s);
     if (gid == 0 && a.total_norm) *a.total_norm = norm;
     float coef = 1.0f;
-    if (a.max_norm > 0.0f) coef = fminf(a.max_norm / (norm + 1e-6f), 1.0f);
-    const float alpha = a.alpha, beta = 1.0f - a.alpha, eps = a.eps, lr = a.lr;
+    if (a.max_norm > 0.0f) {
+        // not fminf, which returns the operand that is not NaN: clip_grad_norm_ clamps with torch.clamp, which hands a NaN norm
+        // on to every gradient.  Finite values keep their bits.
+        const float c = a.max_norm / (norm + 1e-6f);
+        coef = c > 1.0f ? 1.0f : c;
+    }
+    // 1 - alpha as PyTorch forms it (the difference in double, then rounded) where the caller sends it: 1.0f - 0.99f is
+    // 0.00999999046, 16 ulps from the 0.01 that RMSprop multiplies g^2 by — all of a first step's square_avg
+    const float alpha = a.alpha, beta = a.one_minus_alpha != 0.0f ? a.one_minus_alpha : 1.0f - a.alpha, eps = a.eps, lr = a.lr;
     for (int64_t base = gid; base < n; base += OPT_UNROLL * T) {
         float *gp[OPT_UNROLL], *pp[OPT_UNROLL], *vp[OPT_UNROLL];
         float g[OPT_UNROLL], v[OPT_UNROLL], pv[OPT_UNROLL];

@@ -22,7 +22,11 @@ derived for them (``policy_loss_rounding``).
 At the end, the two hand-written GEMMs: csrc/wgrad.hip (``wgrad_plain``, ``wgrad_families``, ``wgrad_floors``) and csrc/linear.hip
 (``linear2_plain``, ``linear2_families``, ``linear2_sum_rounding``), with the floor of a sum of products
 (``product_sum_rounding``; ``ordered_sum_rounding`` where the order of the addends matters, ``equal_addend_drift`` where they are
-all equal) and the shapes both their GPU tests and the CPU test run."""
+all equal) and the shapes both their GPU tests and the CPU test run.
+
+Last, what every sub-update ends in and every reported loss goes through: csrc/optim.hip (``clip_rmsprop_plain`` with OPTIM_WRONG,
+``optim_layouts``, ``optim_families``) and csrc/tdloss.hip's scalar mean (``mean_input``, ``mean_within_bound``: a bound derived
+for a sum held in fp64, not a budget) for tests/test_optim_fp64_gpu.py."""
 import copy
 from typing import NamedTuple
 
@@ -1428,3 +1432,154 @@ def wgrad_cases():
 def linear2_case(rows, k1, k2):
     """``linear2_families`` of one shape from the seed both tests/test_linear_fp64_gpu.py and the CPU test use."""
     return linear2_families(rows, k1, k2, th.Generator().manual_seed(1000003 * rows + 1009 * k1 + k2))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# csrc/optim.hip (flexnet_clip_rmsprop through optim.clip_and_step) and the scalar mean of csrc/tdloss.hip (flexnet_scaled_sum
+# through util.mean_all): tests/test_optim_fp64_gpu.py.  The plain step with its wrong evaluations, the tensor layouts on both
+# sides of the kernel's own sizes (16 384 threads, four elements each per trip: 65 536 flat elements), the families (CPU
+# generator: tests/test_fp64_budget_cpu.py holds the conditions on the very cases) and the derived bound of a mean.
+
+OPTIM_LR, OPTIM_ALPHA, OPTIM_EPS = 1e-3, 0.99, 1e-5          # trainer.py:34-35
+OPTIM_THREADS, OPTIM_PASS = 16384, 65536                     # csrc/optim.hip: OPT_BLOCKS * OPT_THREADS, times OPT_UNROLL
+OPTIM_WRONG = ("eps_inside_root", "v_from_unclipped", "no_margin", "per_tensor_clip", "norm_first_pass_only")
+OPTIM_FAMILIES = ("plain", "warm", "inactive", "tiny", "clip_margin", "large", "zero", "zero_warm")
+OPTIM_FAMILY_LAYOUTS = ("actor", "pass+1", "three_passes")   # where every family runs; every layout runs plain and warm
+ACTOR_SHAPES = [(64, 149), (64,), (64,), (64,), (192, 64), (192, 64), (192,), (192,), (4, 64), (4,)]   # tests/test_optim_gpu.py
+CRITIC_SHAPES = [(64, 745), (64,), (64,), (64,), (64, 64), (64,), (1, 64), (1,)]
+MEAN_SIZES = (1, 2, 255, 256, 257, 16383, 16384, 16385, 32767, 32768, 32769, 100003)
+MEAN_INPUTS = ("randn", "randn+1000", "constant")
+
+
+def optim_layouts():
+    """{name: element counts per tensor, in order} for the optimiser step's flat index space.  ``pass+1``: the first element
+    of the second trip of both loops is a tensor of its own; ``cap``: FLEXNET_OPT_MAX_TENSORS tensors and
+    FLEXNET_OPT_MAX_ELEMENTS elements at once."""
+    import math
+    t, p = OPTIM_THREADS, OPTIM_PASS
+    return {"one": [1], "sixteen_ones": [1] * 16,
+            "actor": [math.prod(s) for s in ACTOR_SHAPES], "critic": [math.prod(s) for s in CRITIC_SHAPES],
+            "threads-1": [t - 1], "threads": [t], "threads+1": [t + 1],
+            "pass-1": [1, t - 1, 7, p - t - 8], "pass": [1, t - 1, 7, p - t - 7], "pass+1": [1, t - 1, 7, p - t - 7, 1],
+            "three_passes": [3, 70001, 1, 69996, 16], "cap": [1] * 15 + [2 ** 20 - 15]}
+
+
+def clip_rmsprop_plain(params, grads, square_avgs, max_norm, lr, alpha, eps, wrong=None):
+    """clip_grad_norm_(params, max_norm) followed by RMSprop(lr, alpha, eps).step() (no momentum, not centred, no weight
+    decay) on lists of tensors, in their dtype and modifying none: (norm, new params, clipped grads, new square_avgs) with
+        norm = the 2-norm over every gradient;  coef = clamp(max_norm / (norm + 1e-6), max=1);  g = g coef;
+        v = alpha v + (1 - alpha) g^2;  p = p - lr g / (sqrt(v) + eps).
+    ``max_norm`` <= 0 is that formula too (PyTorch's: the gradients come out zero, or turned round).  ``wrong``: one of
+    OPTIM_WRONG, the wrong evaluations tests/test_fp64_budget_cpu.py has the budget reject — sqrt(v + eps); v moved by the
+    unclipped gradient; the coefficient without its 1e-6; every tensor clipped by its own norm; the norm over the first
+    OPTIM_PASS flat elements alone (a loop that loses its second trip)."""
+    assert wrong is None or wrong in OPTIM_WRONG, wrong
+    if len(grads) == 0:
+        return th.zeros(()), [], [], []
+    seen = grads
+    if wrong == "norm_first_pass_only" and sum(g.numel() for g in grads) > OPTIM_PASS:
+        seen = [th.cat([g.reshape(-1) for g in grads])[:OPTIM_PASS]]
+    norm = th.linalg.vector_norm(th.stack([th.linalg.vector_norm(g) for g in seen]))
+
+    def coefficient(nrm):
+        return th.clamp(max_norm / (nrm if wrong == "no_margin" else nrm + 1e-6), max=1.0)
+
+    coef = coefficient(norm)
+    new_p, new_g, new_v = [], [], []
+    for p, g, v in zip(params, grads, square_avgs):
+        gc = g * (coefficient(th.linalg.vector_norm(g)) if wrong == "per_tensor_clip" else coef)
+        moved_by = g if wrong == "v_from_unclipped" else gc
+        vn = alpha * v + (1.0 - alpha) * moved_by * moved_by
+        avg = (vn + eps).sqrt() if wrong == "eps_inside_root" else vn.sqrt() + eps
+        new_p.append(p - lr * (gc / avg))
+        new_g.append(gc)
+        new_v.append(vn)
+    return norm, new_p, new_g, new_v
+
+
+def optim_families(layout, generator):
+    """The named input families of one optimiser step on tensors of ``layout`` elements each (flat: the kernels know no
+    shapes), inputs (params, grads, square_avgs) as lists, ``params["max_norm"]`` the clip, from ONE set of base draws per
+    tensor on a CPU generator: p = 0.1 randn (every family's parameters), g = randn, r = rand.  ``warm`` state of a gradient
+    x: v = (0.5 + r) x^2, what the running average has near after many such steps.
+
+    plain        g, state zero (a first step: sqrt(v) = |g| / 10).
+    warm         g, state warm.
+    inactive     1e-3 g, warm: the norm is below max_norm 1 up to 10^6 elements, the coefficient exactly 1.
+    tiny         1e-6 g, state zero: sqrt(v) = 1e-7 |g| is far below eps, the step is lr g / eps.
+    clip_margin  g scaled (in fp64) to a norm of 2e-3, warm, max_norm 1e-3: the 1e-6 is 5e-4 of the coefficient.
+    large        1e15 g, warm: squares near the top of fp32 — the sum over 2^20 of them is still in range.
+    zero         g exactly zero, state zero: nothing may move, and 0 / (0 + eps) is no NaN.
+    zero_warm    g exactly zero, the state warm(randn): v decays by alpha, the parameters stay."""
+    def draw(fn, scale=1.0):
+        return [scale * fn(n, generator=generator) for n in layout]
+
+    p, g, r = draw(th.randn, 0.1), draw(th.randn), draw(th.rand)
+
+    def warm(xs):
+        return [(0.5 + ri) * x * x for ri, x in zip(r, xs)]
+
+    def scaled(c):
+        return [c * x for x in g]
+
+    zeros = [th.zeros(n) for n in layout]
+    norm = float(th.cat(g).double().norm())
+    margin = [(x.double() * (2e-3 / norm)).float() for x in g]
+    fam = lambda name, gr, v, max_norm=1.0: Family(name, (p, gr, v), {"max_norm": max_norm})
+    return {"plain": fam("plain", g, zeros), "warm": fam("warm", g, warm(g)),
+            "inactive": fam("inactive", scaled(1e-3), warm(scaled(1e-3))),
+            "tiny": fam("tiny", scaled(1e-6), zeros),
+            "clip_margin": fam("clip_margin", margin, warm(margin), 1e-3),
+            "large": fam("large", scaled(1e15), warm(scaled(1e15))),
+            "zero": fam("zero", zeros, zeros), "zero_warm": fam("zero_warm", zeros, warm(g))}
+
+
+def optim_case(layout_name):
+    """``optim_families`` of one named layout from the seed both tests/test_optim_fp64_gpu.py and the CPU test use."""
+    layouts = optim_layouts()
+    return optim_families(layouts[layout_name], th.Generator().manual_seed(1009 * list(layouts).index(layout_name) + 7))
+
+
+def optim_run(fam, dtype, wrong=None, device="cpu"):
+    """``clip_rmsprop_plain`` of a family's inputs cast to ``dtype`` with the trainer's RMSprop settings:
+    {"norm": ..., "param": [...], "grad": [...], "square_avg": [...]}."""
+    p, g, v = ([t.to(device=device, dtype=dtype) for t in ts] for ts in fam.inputs)
+    out = clip_rmsprop_plain(p, g, v, fam.params["max_norm"], OPTIM_LR, OPTIM_ALPHA, OPTIM_EPS, wrong=wrong)
+    return dict(zip(("norm", "param", "grad", "square_avg"), out))
+
+
+def optim_within_budget(kernel, torch32, ref, *, name):
+    """``within_budget`` on the norm and, tensor by tensor, on every parameter, gradient and square_avg of three results of
+    ``optim_run``'s form; the list of ratios."""
+    ratios = [within_budget(kernel["norm"], torch32["norm"], ref["norm"], name=f"{name} norm")]
+    for key in ("param", "grad", "square_avg"):
+        assert len(kernel[key]) == len(torch32[key]) == len(ref[key]), (name, key)
+        for t, (k, y, r) in enumerate(zip(kernel[key], torch32[key], ref[key])):
+            ratios.append(within_budget(k.reshape(-1), y.reshape(-1), r.reshape(-1), name=f"{name} {key}[{t}]"))
+    return ratios
+
+
+def mean_input(kind, n, generator):
+    """One of MEAN_INPUTS, fp32 [n]: randn, randn + 1000 (the mean 1 000 times the spread: a running fp32 sum loses the spread),
+    CONSTANT_BIAS everywhere (equal addends: a running fp32 sum drifts)."""
+    assert kind in MEAN_INPUTS, kind
+    if kind == "constant":
+        return th.full((n,), CONSTANT_BIAS)
+    x = th.randn(n, generator=generator)
+    return x + 1000.0 if kind == "randn+1000" else x
+
+
+def mean_within_bound(out, x, sign=1.0, *, name):
+    """assert |out - m| <= 2^-23 |m| + 2^-52 sum|x| for ``out`` = sign * mean(x) of fp32 ``x``, m that mean in fp64 of the fp32
+    numbers; the figures are printed in one line either way.  Derived, not measured, for a sum held in fp64 (csrc/tdloss.hip:
+    flexnet_scaled_sum): the fp32 ``scale`` = sign / n and the final cast to fp32 each round by at most 2^-24 of the result;
+    an fp64 sum of n addends in any order is within (n - 1) 2^-53 sum|x| of the exact one, so times 1 / n within 2^-53 sum|x| —
+    doubled here.  A sum held in fp32 cannot meet it on inputs whose mean is far above their spread."""
+    xd = x.detach().double().reshape(-1).cpu()
+    m = float(sign) * float(xd.sum()) / xd.numel()
+    err = abs(float(out) - m)
+    bound = 2.0 ** -23 * abs(m) + 2.0 ** -52 * float(xd.abs().sum())
+    line = f"fp64-mean {name} err={err:.3e} bound={bound:.3e} mean={m:.9e}"
+    print(line)
+    assert err <= bound, line
+    return err

@@ -6,7 +6,9 @@ one (LayerNorm statistics from a running fp32 sum) wrong only on rows whose 64 i
 at the end: ``qmix_plain`` is ``QMixer.forward_torch``, every case of tests/test_qmix_fp64_gpu.py keeps its tie share within the
 cap, and the budget rejects three wrong evaluations of the mixer.  The last part holds the cases of the two hand-written GEMMs
 (tests/test_wgrad_fp64_gpu.py, tests/test_linear_fp64_gpu.py): a running fp32 sum in row (column) order is inside the budget with
-the floors those tests take, and five wrong evaluations are outside it."""
+the floors those tests take, and five wrong evaluations are outside it.  Then the optimiser step and the scalar mean
+(tests/test_optim_fp64_gpu.py): ``clip_rmsprop_plain`` is the two PyTorch calls, its fp32 form and PyTorch's pass each other's budget
+in every family, five wrong steps are outside it, and the bound of a mean rejects a sum held in fp32."""
 import pytest
 import torch as th
 
@@ -957,3 +959,148 @@ def test_linear2_cases_admit_a_column_order_running_sum_and_reject_the_wrong_eva
                     continue
                 with pytest.raises(AssertionError):
                     fb.within_budget(bad, yard, ref, floor_ulps=ulps, name=f"{wrong} {rows}x({k1}+{k2}) {nm}")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# csrc/optim.hip and the scalar mean of csrc/tdloss.hip: the step, layouts, families and bound of tests/test_optim_fp64_gpu.py
+
+def _torch_step(fam, dtype, **kw):
+    """clip_grad_norm_ + RMSprop.step() on copies of a family's tensors in ``dtype``, the state put where PyTorch keeps it."""
+    from torch.optim import RMSprop
+    p, g, v = ([t.to(dtype).clone() for t in ts] for ts in fam.inputs)
+    opt = RMSprop(p, lr=fb.OPTIM_LR, alpha=fb.OPTIM_ALPHA, eps=fb.OPTIM_EPS, **kw)
+    for pi, gi, vi in zip(p, g, v):
+        pi.grad = gi
+        opt.state[pi] = {"step": th.zeros((), dtype=th.float32), "square_avg": vi}
+    norm = th.nn.utils.clip_grad_norm_(p, fam.params["max_norm"])
+    opt.step()
+    assert all(float(opt.state[pi]["step"]) == 1.0 for pi in p)
+    return {"norm": norm, "param": p, "grad": g, "square_avg": v}
+
+
+def test_optim_layouts_are_the_issues():
+    lay = fb.optim_layouts()
+    assert list(lay) == ["one", "sixteen_ones", "actor", "critic", "threads-1", "threads", "threads+1", "pass-1", "pass", "pass+1",
+                         "three_passes", "cap"]
+    total = {k: sum(v) for k, v in lay.items()}
+    assert total["actor"] == 34948 and total["critic"] == 52097 and total["three_passes"] == 140017
+    assert (total["pass-1"], total["pass"], total["pass+1"]) == (65535, 65536, 65537) and lay["pass+1"][-1] == 1
+    assert lay["pass+1"] == [1, 16383, 7, 49145, 1] and lay["pass-1"][-1] == 49144
+    assert total["cap"] == 2 ** 20 and len(lay["cap"]) == 16 and len(lay["sixteen_ones"]) == 16
+    assert set(fb.OPTIM_FAMILY_LAYOUTS) <= set(lay)
+
+
+@pytest.mark.parametrize("layout", ["sixteen_ones", "actor", "pass+1"])
+@pytest.mark.parametrize("family", ["plain", "warm", "clip_margin", "zero_warm"])
+def test_clip_rmsprop_plain_is_the_two_pytorch_calls(layout, family):
+    """In fp64, to 1e-12 of each tensor's scale, against the single-tensor form of the optimiser (capturable False); max_norm
+    0 and -1 are PyTorch's formula too; nothing handed in is modified."""
+    fam = fb.optim_case(layout)[family]
+    for max_norm in (fam.params["max_norm"], 0.0, -1.0):
+        fam = fam._replace(params={"max_norm": max_norm})
+        before = [[t.clone() for t in ts] for ts in fam.inputs]
+        mine, want = fb.optim_run(fam, th.float64), _torch_step(fam, th.float64, capturable=False, foreach=False)
+        assert all(th.equal(a, b) for xs, ys in zip(fam.inputs, before) for a, b in zip(xs, ys))
+        assert abs(float(mine["norm"] - want["norm"])) <= 1e-12 * float(want["norm"])
+        for key in ("param", "grad", "square_avg"):
+            for a, b in zip(mine[key], want[key]):
+                assert a.dtype == th.float64 and float((a - b).abs().max()) <= 1e-12 * max(float(b.abs().max()), fb.TINY), (key, max_norm)
+        if max_norm <= 0:                           # zero, or turned round
+            assert all(float((a - max_norm * b.double() / (mine["norm"] + 1e-6)).abs().max()) < 1e-12 for a, b in zip(mine["grad"], fam.inputs[1]))
+
+
+def test_optim_families_are_what_they_say():
+    for layout in fb.OPTIM_FAMILY_LAYOUTS:
+        fams = fb.optim_case(layout)
+        assert tuple(fams) == fb.OPTIM_FAMILIES
+        norm = {k: float(th.cat(f.inputs[1]).double().norm()) for k, f in fams.items()}
+        print(f"optim families {layout}: " + " ".join(f"{k}={v:.4g}" for k, v in norm.items()))
+        assert norm["inactive"] < fams["inactive"].params["max_norm"] == 1.0
+        assert norm["plain"] > 1.0 and norm["warm"] > 1.0 and fams["plain"].params["max_norm"] == 1.0
+        assert fams["clip_margin"].params["max_norm"] == 1e-3 and abs(norm["clip_margin"] - 2e-3) < 1e-8
+        assert norm["zero"] == 0.0 == norm["zero_warm"]
+        for k, f in fams.items():
+            p, g, v = f.inputs
+            assert all(t.dtype == th.float32 for ts in f.inputs for t in ts) and [t.numel() for t in g] == fb.optim_layouts()[layout]
+            assert all(th.equal(a, b) for a, b in zip(p, fams["plain"].inputs[0]))
+            zero_state = k in ("plain", "tiny", "zero")
+            assert all(bool((t == 0).all()) == zero_state for t in v if t.numel() > 8)
+        # the coefficient of the inactive family is exactly 1 in fp32, so the gradients keep their bits
+        assert all(th.equal(a, b) for a, b in zip(fb.optim_run(fams["inactive"], th.float32)["grad"], fams["inactive"].inputs[1]))
+        tiny = fb.optim_run(fams["tiny"], th.float64)["square_avg"]
+        assert max(float(t.max()) for t in tiny) ** 0.5 < 0.1 * fb.OPTIM_EPS
+    # norm_first_pass_only leaves out one element of pass+1 — the last tensor: it must weigh enough to be seen in the norm
+    last = float(fb.optim_case("pass+1")["plain"].inputs[1][-1])
+    assert abs(last) > 0.5, last
+    # large: the fp32 sum of squares over the 2^20 elements of the cap is finite, and so are the squares of warm's state
+    large = fb.optim_case("cap")["large"]
+    flat = th.cat(large.inputs[1])
+    assert flat.numel() == 2 ** 20 and flat.dtype == th.float32
+    ss = (flat * flat).sum(dtype=th.float32)
+    assert bool(th.isfinite(ss)) and float(ss) > 1e35 and bool(th.isfinite(th.cat(large.inputs[2])).all())
+
+
+@pytest.mark.parametrize("layout", fb.OPTIM_FAMILY_LAYOUTS)
+def test_the_fp32_step_passes_its_own_budget_in_every_optim_family(layout):
+    """``clip_rmsprop_plain`` in fp32 in the kernel's place, PyTorch's two calls in fp32 the yardstick (MARGIN and FLOOR_ULPS as
+    they stand), and the other way round."""
+    for name, fam in fb.optim_case(layout).items():
+        ref, plain, yard = fb.optim_run(fam, th.float64), fb.optim_run(fam, th.float32), _torch_step(fam, th.float32)
+        fb.optim_within_budget(plain, yard, ref, name=f"optim plain-as-kernel {layout} {name}")
+        fb.optim_within_budget(yard, plain, ref, name=f"optim torch-as-kernel {layout} {name}")
+        if name == "zero":
+            assert all(th.equal(a, b) for key, k in (("param", 0), ("square_avg", 2)) for a, b in zip(yard[key], fam.inputs[k]))
+
+
+OPTIM_REJECTED = {"eps_inside_root": ("plain", "param"), "v_from_unclipped": ("plain", "square_avg"), "no_margin": ("clip_margin", "grad"),
+                  "per_tensor_clip": ("plain", "grad"), "norm_first_pass_only": ("plain", "norm")}
+
+
+@pytest.mark.parametrize("wrong", fb.OPTIM_WRONG)
+def test_budget_rejects_five_wrong_optimiser_steps(wrong):
+    """Each wrong evaluation in fp32 in the kernel's place, at the (family, tensor kind) where it must show: at least one tensor
+    of that kind is outside the budget.  norm_first_pass_only differs from the step only past 65 536 flat elements: at pass+1
+    (one element left out) and three_passes; the others at the three layouts every family runs at."""
+    family, kind = OPTIM_REJECTED[wrong]
+    assert set(OPTIM_REJECTED) == set(fb.OPTIM_WRONG)
+    layouts = ("pass+1", "three_passes") if wrong == "norm_first_pass_only" else fb.OPTIM_FAMILY_LAYOUTS
+    for layout in layouts:
+        fam = fb.optim_case(layout)[family]
+        ref, yard, bad = fb.optim_run(fam, th.float64), _torch_step(fam, th.float32), fb.optim_run(fam, th.float32, wrong=wrong)
+        if kind == "norm":
+            _rejected(bad["norm"], yard["norm"], ref["norm"], f"optim {wrong} {layout} {family} norm")
+            continue
+        outside = 0
+        for t, (b, y, r) in enumerate(zip(bad[kind], yard[kind], ref[kind])):
+            try:
+                fb.within_budget(b, y, r, name=f"optim {wrong} {layout} {family} {kind}[{t}]")
+            except AssertionError:
+                outside += 1
+        assert outside >= 1, (wrong, layout)
+    if wrong == "norm_first_pass_only":             # inside the first trip there is nothing to lose
+        fam = fb.optim_case("actor")[family]
+        assert th.equal(fb.optim_run(fam, th.float32, wrong=wrong)["norm"], fb.optim_run(fam, th.float32)["norm"])
+
+
+@pytest.mark.parametrize("kind", fb.MEAN_INPUTS)
+def test_the_bound_of_a_mean_admits_an_fp64_sum_and_rejects_an_fp32_running_sum(kind):
+    """``mean_within_bound`` at every size of tests/test_optim_fp64_gpu.py: a sum held in fp64 in blocks of 256 (any order
+    will do) with the scale and the result rounded to fp32 is inside it; at 100 003 elements of randn + 1000 an fp32 running sum
+    is outside it (partial sums of 1e8 carry roundings of 4 each)."""
+    g = th.Generator().manual_seed(11)
+    for n in fb.MEAN_SIZES:
+        x = fb.mean_input(kind, n, g)
+        for sign in (1.0, -1.0):
+            pad = th.cat((x.double(), th.zeros(-n % 256, dtype=th.float64))).view(-1, 256).sum(1)
+            scale = th.tensor(sign / n, dtype=th.float32).double()
+            fb.mean_within_bound((pad.flip(0).sum() * scale).float(), x, sign, name=f"fp64 blocks {kind} n={n} sign={sign:+.0f}")
+    if kind == "randn+1000":
+        x = fb.mean_input(kind, 100003, g)
+        import numpy as np
+        sums = np.add.accumulate(x.numpy(), dtype=np.float32)           # one fp32 addition after the other
+        seq = th.zeros((), dtype=th.float32)
+        for value in x[:4096]:
+            seq = seq + value
+        assert float(seq) == float(sums[4095])
+        with pytest.raises(AssertionError):
+            fb.mean_within_bound(th.tensor(sums[-1]) / 100003, x, name="fp32 running sum randn+1000 n=100003")

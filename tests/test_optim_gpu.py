@@ -66,6 +66,26 @@ def test_unsupported_configuration_falls_back():
         assert torch.equal(pa, pb)
 
 
+def refresh_args(ws, small, start_cell, rows, n, act_w, stride, cap):
+    """(FlexWindowRefreshArgs, FlexTdLossArgs), the two NaN-filled destinations and the cell of a refresh that copies ``rows``
+    rows of the ring ``small`` [cap, stride] from the slot in ``start_cell`` on — action columns [0, act_w), reward columns
+    [act_w, act_w + n) — with the reward statistics into ``ws`` (tests/test_optim_fp64_gpu.py runs it at another layout)."""
+    from safe_marl_amd import _lib
+    out = {k: torch.full((rows, w), float("nan"), device="cuda") for k, w in (("action", act_w), ("reward", n))}
+    cell = torch.full((1,), -1, dtype=torch.int64, device="cuda")
+    a = _lib.FlexWindowRefreshArgs()
+    a.start, a.ring_rows = start_cell.data_ptr(), cap
+    for j, (col0, w, dst) in enumerate(((0, act_w, out["action"]), (act_w, n, out["reward"]))):
+        a.base[j], a.dst[j], a.rows[j], a.row_off[j] = small.data_ptr() + 4 * col0, dst.data_ptr(), rows, 0
+        a.width[j], a.src_stride[j] = w, stride
+    a.n_jobs, a.n_cells, a.reward_job = 2, 1, 1
+    a.cell[0], a.cell_mod[0] = cell.data_ptr(), cap
+    t = _lib.FlexTdLossArgs()
+    t.rows, t.n_agents, t.normalise, t.reward = rows, n, 1, out["reward"].data_ptr()
+    t.workspace, t.workspace_floats = ws.data_ptr(), 2 * ws.numel()
+    return (a, t), out, cell
+
+
 @pytest.mark.parametrize("supported", [True, False])
 def test_the_next_windows_refresh_rides_in_the_step(supported):
     """include/flexnet.h: flexnet_clip_rmsprop_refresh (optim.clip_and_step(refresh=...)) — the optimiser step of
@@ -83,21 +103,6 @@ def test_the_next_windows_refresh_rides_in_the_step(supported):
     small = torch.randn(cap, stride, device="cuda", generator=g)
     start_cell = torch.tensor([start], dtype=torch.int64, device="cuda")
 
-    def refresh_args(ws):
-        out = {k: torch.full((rows, w), float("nan"), device="cuda") for k, w in (("action", act_w), ("reward", n))}
-        cell = torch.full((1,), -1, dtype=torch.int64, device="cuda")
-        a = _lib.FlexWindowRefreshArgs()
-        a.start, a.ring_rows = start_cell.data_ptr(), cap
-        for j, (col0, w, dst) in enumerate(((0, act_w, out["action"]), (act_w, n, out["reward"]))):
-            a.base[j], a.dst[j], a.rows[j], a.row_off[j] = small.data_ptr() + 4 * col0, dst.data_ptr(), rows, 0
-            a.width[j], a.src_stride[j] = w, stride
-        a.n_jobs, a.n_cells, a.reward_job = 2, 1, 1
-        a.cell[0], a.cell_mod[0] = cell.data_ptr(), cap
-        t = _lib.FlexTdLossArgs()
-        t.rows, t.n_agents, t.normalise, t.reward = rows, n, 1, out["reward"].data_ptr()
-        t.workspace, t.workspace_floats = ws.data_ptr(), 2 * ws.numel()
-        return (a, t), out, cell
-
     kw = {} if supported else {"momentum": 0.9}
     res = []
     for ride in (True, False):
@@ -107,7 +112,7 @@ def test_the_next_windows_refresh_rides_in_the_step(supported):
         for pa in a:
             pa.grad = torch.randn(pa.shape, device="cuda", generator=gg)
         ws = torch.zeros(_lib.FLEXNET_TD_WS_FLOATS // 2, dtype=torch.float64, device="cuda")
-        refresh, out, cell = refresh_args(ws)
+        refresh, out, cell = refresh_args(ws, small, start_cell, rows, n, act_w, stride, cap)
         if ride:
             norm = clip_and_step(opt, a, 1.0, refresh=refresh)
         else:
@@ -131,7 +136,8 @@ def test_the_next_windows_refresh_rides_in_the_step(supported):
         opt = RMSprop(a, lr=1e-3, alpha=0.99, eps=1e-5, capturable=True)
         for pa in a:
             pa.grad = torch.ones_like(pa)
-        (ra, rt), out, cell = refresh_args(torch.zeros(_lib.FLEXNET_TD_WS_FLOATS // 2, dtype=torch.float64, device="cuda"))
+        (ra, rt), out, cell = refresh_args(torch.zeros(_lib.FLEXNET_TD_WS_FLOATS // 2, dtype=torch.float64, device="cuda"), small, start_cell,
+                                          rows, n, act_w, stride, cap)
         other = torch.zeros(rows, n, device="cuda")
         rt.reward = other.data_ptr()
         with pytest.raises(RuntimeError):
